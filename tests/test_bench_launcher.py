@@ -73,7 +73,7 @@ def test_bench_gpus_2_spawns_two_ranks_and_reports_both_scalings():
     if _gpus() < 1:
         pytest.skip("no GPU")
     r = _run(["--gpus", "2", "--npix", "256", "--batch", "32", "--steps", "2", "--warmup", "1", "--cpu-sample", "0",
-              "--no-structured"], env={"SF_BENCH_RANKS_SHARE_GPU": "1"})
+              "--no-structured", "--full"], env={"SF_BENCH_RANKS_SHARE_GPU": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -158,7 +158,7 @@ def test_bench_runs_the_real_rccl_branch_with_one_rank():
     order and the second scaling leg all execute for real."""
     if _gpus() < 1:
         pytest.skip("no GPU")
-    r = _run(["--gpus", "1"] + _SMALL, env=dict(_ONE_RANK, MASTER_PORT=_free_port()))
+    r = _run(["--gpus", "1", "--full"] + _SMALL, env=dict(_ONE_RANK, MASTER_PORT=_free_port()))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -167,6 +167,29 @@ def test_bench_runs_the_real_rccl_branch_with_one_rank():
     assert d["n_gpus"] == 1 and d["value"] > 0 and "error" not in d
     assert d["strong"]["value"] > 0 and d["strong"]["units_per_gpu"] == 16
     assert "before the process group" in d["roofline"]["sustained_clock_note"]
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_step_and_full_adds_the_secondary_figures(tmp_path):
+    """A plain run prints the headline only and, with --dump-outputs, the lnl / info arrays of its last timed step; --full
+    on the same seeded inputs adds roofline and per-stage figures and computes the same values."""
+    if _gpus() < 1:
+        pytest.skip("no GPU")
+    import numpy as np
+
+    small = ["--npix", "512", "--batch", "16", "--steps", "3", "--warmup", "1"]
+    d = _line(_run(small + ["--dump-outputs", str(tmp_path / "plain")]))
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "evals/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert not {"roofline", "stage_ms_per_step", "structured_solver", "cpu_baseline"} & set(d)
+    lnl, info = np.load(tmp_path / "plain" / "lnl.npy"), np.load(tmp_path / "plain" / "info.npy")
+    assert lnl.dtype == info.dtype == np.float64 and lnl.shape == info.shape == (16,)
+    assert (info == 0).all() and np.isfinite(lnl).all()
+    assert abs(lnl.sum() - d["lnl_checksum"]) <= 1e-12 * abs(d["lnl_checksum"])
+
+    f = _line(_run(small + ["--full", "--cpu-sample", "0", "--dump-outputs", str(tmp_path / "full")]))
+    assert f["roofline"]["profiled_steps"] == 1 and {"stage_ms_per_step", "structured_solver"} <= set(f)
+    np.testing.assert_allclose(np.load(tmp_path / "full" / "lnl.npy"), lnl, rtol=1e-12, atol=0)
 
 
 @pytest.mark.gpu
@@ -237,8 +260,8 @@ def test_eight_rank_rehearsal_on_one_gpu_cfg2_strong_and_cfg4():
     if _gpus() < 1:
         pytest.skip("no GPU")
     hook = {"SF_BENCH_RANKS_SHARE_GPU": "1", "OMP_NUM_THREADS": "4"}
-    r = _run(["--gpus", "8", "--scaling", "strong", "--steps", "1", "--warmup", "1", "--cpu-sample", "0", "--no-structured"],
-             env=hook, timeout=1500)
+    r = _run(["--gpus", "8", "--scaling", "strong", "--steps", "1", "--warmup", "1", "--cpu-sample", "0", "--no-structured",
+              "--full"], env=hook, timeout=1500)
     d = _line(r)
     assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["value"] > 0
     assert d["config"]["global_batch"] == 128 and d["config"]["units_per_gpu"] == 16
