@@ -55,11 +55,9 @@ def log_lambda_grid(dv, start, end):
 
 
 # --------------------------------------------------------------------------- covariance kernels
-def matern32_global(wave, amplitude, lengthscale):
-    """Starfish/models/kernels.py:7-41 -- Hann-tapered Matern-3/2 in velocity distance."""
-    w = np.asarray(wave, dtype=np.float64)
-    wi = w[None, :]
-    wj = w[:, None]
+def matern32_elem(wi, wj, amplitude, lengthscale):
+    """Starfish/models/kernels.py:27-40 -- one element (broadcast over arrays) of the global kernel between the
+    wavelengths wi (column) and wj (row)."""
     r = C_KMS / 2 * np.abs((wi - wj) / (wi + wj))
     r0 = 6 * lengthscale
     inside = r <= r0
@@ -71,12 +69,20 @@ def matern32_global(wave, amplitude, lengthscale):
     return np.where(inside, body, 0.0)
 
 
-def gaussian_local(wave, amplitude, mu, sigma):
-    """Starfish/models/kernels.py:44-81 -- Hann-tapered Gaussian patch centred on mu."""
+def matern32_global(wave, amplitude, lengthscale):
+    """Starfish/models/kernels.py:7-41 -- Hann-tapered Matern-3/2 in velocity distance."""
     w = np.asarray(wave, dtype=np.float64)
-    d = C_KMS / mu * np.abs(w - mu)
-    di = d[None, :]
-    dj = d[:, None]
+    return matern32_elem(w[None, :], w[:, None], amplitude, lengthscale)
+
+
+def local_metric(wave, mu):
+    """Starfish/models/kernels.py:69 -- velocity distance of every wavelength from the line centre mu."""
+    return C_KMS / mu * np.abs(np.asarray(wave, dtype=np.float64) - mu)
+
+
+def gaussian_local_elem(di, dj, amplitude, sigma):
+    """Starfish/models/kernels.py:70-80 -- one element (broadcast over arrays) of a local kernel between the metrics
+    di (column) and dj (row) of ``local_metric``."""
     r_tap = np.maximum(di, dj)
     r2 = di**2 + dj**2
     r0 = 4 * sigma
@@ -85,6 +91,12 @@ def gaussian_local(wave, amplitude, mu, sigma):
     taper = 0.5 + 0.5 * np.cos(pi * rt / r0)
     body = taper * amplitude * np.exp(-0.5 * np.where(inside, r2, 0.0) / sigma**2)
     return np.where(inside, body, 0.0)
+
+
+def gaussian_local(wave, amplitude, mu, sigma):
+    """Starfish/models/kernels.py:44-81 -- Hann-tapered Gaussian patch centred on mu."""
+    d = local_metric(wave, mu)
+    return gaussian_local_elem(d[None, :], d[:, None], amplitude, sigma)
 
 
 # --------------------------------------------------------------------------- transforms
@@ -441,13 +453,9 @@ class OracleOrder:
         self.bulk_fluxes = quintic_resample(self.emu_wl, bulk, self.min_dv_wave)
 
 
-def forward_model(order, p):
-    """Steps 1-10 of SURVEY.md section 0 == SpectrumModel.__call__
-    (Starfish/models/spectrum_model.py:277-365).
-
-    ``p`` is a plain dict: optional vsini, vz, cheb (c1..), log_scale, norm (float factor),
-    global_cov=(log_amp, log_ls), local_cov=[(mu, log_amp, log_sigma), ...], grid=[...].
-    Returns flux (N,), cov (N, N) and the scale factor used."""
+def emulator_terms(order, p):
+    """Steps 1-9 of ``forward_model``: the model flux (N,), the scaled emulator rows X (m, N), the emulator's
+    weight covariance w_cov (m, m) and the scale factor -- everything but the N x N covariance."""
     wave = order.min_dv_wave
     rows = order.bulk_fluxes
     if "vsini" in p:
@@ -472,6 +480,12 @@ def forward_model(order, p):
         scale = renorm_factor(order.wave, flux * norm, order.flux) * norm
     flux = flux * scale
     X = X * scale
+    return flux, X, w_cov, scale
+
+
+def assemble_cov(order, p, X, w_cov):
+    """Step 10 of ``forward_model``: the dense covariance from the emulator term and the structured kernels, in the
+    reference's order of additions (spectrum_model.py:334-363)."""
     if p.get("emulator_cov", "code") == "paper":
         # the form printed in the paper / docs (docs/api/emulator.rst:105): Phi Sigma_w Phi^T; non-default switch
         cov = X.T @ w_cov @ X
@@ -488,7 +502,18 @@ def forward_model(order, p):
         for mu, la, ls in p["local_cov"]:
             loc = loc + gaussian_local(order.wave, np.exp(la), mu, np.exp(ls))
         cov += loc
-    return flux, cov, scale
+    return cov
+
+
+def forward_model(order, p):
+    """Steps 1-10 of SURVEY.md section 0 == SpectrumModel.__call__
+    (Starfish/models/spectrum_model.py:277-365).
+
+    ``p`` is a plain dict: optional vsini, vz, cheb (c1..), log_scale, norm (float factor),
+    global_cov=(log_amp, log_ls), local_cov=[(mu, log_amp, log_sigma), ...], grid=[...].
+    Returns flux (N,), cov (N, N) and the scale factor used."""
+    flux, X, w_cov, scale = emulator_terms(order, p)
+    return flux, assemble_cov(order, p, X, w_cov), scale
 
 
 def log_likelihood(order, p, return_parts=False):

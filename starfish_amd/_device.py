@@ -344,7 +344,10 @@ class DeviceOrder:
         return md
 
     def param_stride(self, md):
-        return self.lib.sf_param_stride(self.ctx, C.byref(md))
+        stride = self.lib.sf_param_stride(self.ctx, C.byref(md))
+        if stride < 0:  # a model the library does not take (e.g. more local kernels than SF_MAX_LOCAL): say why
+            _lib.check(stride, "sf_param_stride")
+        return stride
 
     def workspace_bytes(self, md, B):
         return self.lib.sf_workspace_bytes(self.ctx, C.byref(md), int(B))

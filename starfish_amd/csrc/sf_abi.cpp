@@ -458,6 +458,10 @@ extern "C" sf_ctx* sf_ctx_create(const sf_order_desc* d, int device, int* err) {
     // n == 0 builds an emulator-only context (Emulator.__call__ without a SpectrumModel)
     const bool order_ok = d && (d->n == 0 || (d->n >= 2 && d->nf >= 8 && !(d->nf & (d->nf - 1)) && d->wave &&
                                                d->flux && d->sigma && d->min_dv_wave && d->bulk_fluxes));
+    if (d && (d->m < 1 || d->m > SF_MAX_M)) {
+        sf_set_error("sf_ctx_create: %d eigenspectra, between 1 and %d (SF_MAX_M) are supported", d->m, SF_MAX_M);
+        return fail(SF_EINVAL);
+    }
     if (!d || !order_ok || d->m < 1 || d->m > SF_MAX_M || d->n_grid < 1 || d->M < 1 || !d->grid_points ||
         !d->variances || !d->lengthscales || !d->v11 || !d->w_hat) {
         sf_set_error("sf_ctx_create: bad descriptor");
@@ -616,6 +620,10 @@ static int model_ok(const sf_ctx* c, const sf_model_desc* mdl) {
         sf_set_error("bad context / model descriptor");
         return SF_EINVAL;
     }
+    if (mdl->n_local > SF_MAX_LOCAL) {
+        sf_set_error("%d local kernels: at most %d (SF_MAX_LOCAL) are supported", mdl->n_local, SF_MAX_LOCAL);
+        return SF_EINVAL;
+    }
     return SF_OK;
 }
 // the calling thread's current device becomes the context's (HIP's current device is per thread)
@@ -657,7 +665,7 @@ struct Work {
     double2* fft;
     int *info_e, *info_c;
     unsigned char* tilemap;
-    unsigned short* tilelist;  // compact list of the materialised tiles (see sf_fill_args)
+    unsigned* tilelist;        // compact list of the materialised tiles (see sf_fill_args)
     int* tilecount;
     unsigned char* dmap;       // dense fill of caller matrices: structured-support map / list of 64 x 64 tiles
     unsigned short* dlist;
@@ -701,7 +709,7 @@ static Work carve(const Layout& L, const sf_model_desc* mdl, int B, int Bt, void
     w.ltbuf_stride = sf_align_up(sf_potrf_work_doubles(L.npad, potrf_units), 32);
     w.ltbuf = need_C ? k.take<double>(w.ltbuf_stride * potrf_slots) : nullptr;  // Cholesky scratch (per concurrent call)
     w.tilemap = need_C ? k.take<unsigned char>(b * tilemap_bytes(L)) : nullptr;
-    w.tilelist = need_C ? k.take<unsigned short>(b * tilemap_bytes(L)) : nullptr;  // (capacity: every tile)
+    w.tilelist = need_C ? k.take<unsigned>(b * tilemap_bytes(L)) : nullptr;  // (capacity: every tile)
     w.tilecount = need_C ? k.take<int>(b) : nullptr;
     w.gtab = need_C ? k.take<double>(b * (size_t)L.npad) : nullptr;
     w.dmap = k.take<unsigned char>(b * sf_fill_dense_map_tiles(L.npad));

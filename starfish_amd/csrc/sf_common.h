@@ -11,6 +11,7 @@
 #define SF_LEAF 64        // Cholesky leaf block (potrf / trsm granularity); matrices padded to it
 #define SF_NB 256         // outer left-looking panel width
 #define SF_C_KMS 2.99792458e5
+#define SF_MAX_LOCAL 32   // local kernels per model (sf_fill.hip: 32-bit masks of the fill tiles, per-block tables)
 
 typedef double sf_d4 __attribute__((ext_vector_type(4)));
 
@@ -158,10 +159,11 @@ struct sf_fill_args {
     unsigned char* tilemap; // optional [B][nt128*nt128]: 1 = the 128x128 tile is materialised in C
     int nt128;
     int fp;                // 0 or 64: the tile map / list index the tiles of the factorisation's shifted frame (sf_potrf_front_pad)
-    // optional compact work list of the materialised tiles (likelihood path): k_tile_map appends (tm << 8 | tn) per flagged
+    // optional compact work list of the materialised tiles (likelihood path): k_tile_map appends (tm << 16 | tn) per flagged
     // 128 x 128 tile, the fill then launches a few workgroups per walker that walk the list instead of one (mostly empty)
-    // workgroup per 64 x 64 tile of the whole matrix
-    unsigned short* tilelist;  // [B][list_cap]
+    // workgroup per 64 x 64 tile of the whole matrix.  32-bit entries: nothing bounds N here, and 8-bit tile indices
+    // would wrap at 256 tile rows (N > 32 768)
+    unsigned* tilelist;        // [B][list_cap]
     int* tilecount;            // [B]
     int list_cap;
     double* gtab;          // optional [B][n] scratch: K_global per diagonal (log-uniform grids, likelihood path)

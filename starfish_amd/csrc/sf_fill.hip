@@ -62,8 +62,6 @@ __device__ SF_ELEM_CALL double sf_local_elem_t(double d_row, double d_col, doubl
     return sf_local_elem(d_row, d_col, amp, sigma, r0);
 }
 
-#define SF_MAX_LOCAL 32
-
 // Which 128 x 128 tiles of the lower triangle carry anything besides the rank-m term (diagonal
 // SF_NB blocks: sigma^2 / jitter / identity padding; Matern band; local patches)?  Only those are
 // materialised for the factorisation; the MFMA update kernel generates the others from Y on the fly.
@@ -106,7 +104,7 @@ __global__ __launch_bounds__(256) void k_tile_map(sf_fill_args a) {
     a.tilemap[(int64_t)b * nt * nt + e] = flag;
     if (flag && a.tilelist) {
         const int idx = atomicAdd(&a.tilecount[b], 1);  // (the order of the list does not matter: tiles are independent)
-        if (idx < a.list_cap) a.tilelist[(int64_t)b * a.list_cap + idx] = (unsigned short)((tm << 8) | tn);
+        if (idx < a.list_cap) a.tilelist[(int64_t)b * a.list_cap + idx] = ((unsigned)tm << 16) | (unsigned)tn;
     }
 }
 
@@ -315,11 +313,11 @@ template <bool BAND>
 __global__ __launch_bounds__(256, BAND ? 2 : 4) void k_fill_tiles_list(sf_fill_args a, int G) {
     const int b = blockIdx.x / G, g = blockIdx.x - b * G;
     const int cnt = min(a.tilecount[b], a.list_cap) * 4;
-    const unsigned short* __restrict__ list = a.tilelist + (int64_t)b * a.list_cap;
+    const unsigned* __restrict__ list = a.tilelist + (int64_t)b * a.list_cap;
     const int fs = a.fp >> 6;  // the list holds tiles of the factorisation's frame: a.fp / 64 virtual 64-row tiles in front
     for (int li = g; li < cnt; li += G) {
-        const int e = list[li >> 2];
-        const int tm = 2 * (e >> 8) + ((li >> 1) & 1) - fs, tn = 2 * (e & 255) + (li & 1) - fs;
+        const unsigned e = list[li >> 2];
+        const int tm = 2 * (int)(e >> 16) + ((li >> 1) & 1) - fs, tn = 2 * (int)(e & 0xffff) + (li & 1) - fs;
         if (tm >= 0 && tn >= 0) sf_fill_tile<BAND>(a, b, tm, tn);
     }
 }

@@ -392,12 +392,12 @@ __global__ __launch_bounds__(64) void k_spline_solve(double* __restrict__ data, 
 // The walker loop is software pipelined: the fragments of walker b+1 are in flight while the matrix
 // core works on walker b.
 // y is [B][rows][n], c is [B][n][rows] (what k_eval_rows reads); tblk is [n/16][SF_IBLK][16][16] (zero outside
-// the band / the matrix).
+// the band / the matrix).  A launch covers the rows row0 .. row0 + 16 NCB - 1 (the register budget stops at NCB = 2).
 #define SF_IBLK (2 * (SF_IW / 16) + 1)
 template <int NCB>
 __global__ __launch_bounds__(256) void k_spline_apply(const double* __restrict__ y, double* __restrict__ c,
                                                       int rows, int n, const double* __restrict__ tblk, int B,
-                                                      int wchunk) {
+                                                      int wchunk, int row0) {
     const int lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
     const int ib = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ib * 16 >= n) return;
@@ -420,7 +420,7 @@ __global__ __launch_bounds__(256) void k_spline_apply(const double* __restrict__
             kblk = kblk < 0 ? 0 : (kblk >= nblk16 ? nblk16 - 1 : kblk);
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) {
-                const int r = cb * 16 + l15;
+                const int r = row0 + cb * 16 + l15;
                 const double2* p = (const double2*)(yb + (int64_t)(r < rows ? r : 0) * n + kblk * 16 + 4 * lq);
                 const double2 lo = p[0], hi = p[1];  // rows >= `rows` are never stored
                 dst[kb][0][cb] = lo.x;
@@ -447,7 +447,7 @@ __global__ __launch_bounds__(256) void k_spline_apply(const double* __restrict__
             const int i = ib * 16 + lq + 4 * r4;
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) {
-                const int r = cb * 16 + l15;
+                const int r = row0 + cb * 16 + l15;
                 if (r < rows && i < n) cb_[(int64_t)i * rows + r] = acc[cb][r4];
             }
         }
@@ -1157,8 +1157,8 @@ int sf_launch_spline_solve(double* data, int B, int rows, int64_t bstride, int64
 }
 
 int sf_launch_spline_apply(const double* y, double* c, int B, int rows, int n, const double* tblk, hipStream_t s) {
-    const int ncb = (rows + 15) / 16;
-    if (ncb > 2 || n % 16) {
+    const int ncb = (rows + 15) / 16;  // (rows = m + 2 <= SF_MAX_M + 2: at most 3 column blocks)
+    if (ncb > 3 || n % 16) {
         sf_set_error("spline_apply: rows=%d n=%d not supported", rows, n);
         return SF_EINVAL;
     }
@@ -1167,9 +1167,13 @@ int sf_launch_spline_apply(const double* y, double* c, int B, int rows, int n, c
     int wchunk = 32;
     while (wchunk > 4 && (int64_t)(n / 16) * ((B + wchunk - 1) / wchunk) < 2048) wchunk >>= 1;
     const dim3 grid((n / 16 + 3) / 4, (B + wchunk - 1) / wchunk);
-    if (ncb == 1) hipLaunchKernelGGL(k_spline_apply<1>, grid, dim3(256), 0, s, y, c, rows, n, tblk, B, wchunk);
-    else hipLaunchKernelGGL(k_spline_apply<2>, grid, dim3(256), 0, s, y, c, rows, n, tblk, B, wchunk);
+    if (ncb == 1) hipLaunchKernelGGL(k_spline_apply<1>, grid, dim3(256), 0, s, y, c, rows, n, tblk, B, wchunk, 0);
+    else hipLaunchKernelGGL(k_spline_apply<2>, grid, dim3(256), 0, s, y, c, rows, n, tblk, B, wchunk, 0);
     SF_LAUNCH_CHECK();
+    if (ncb == 3) {  // m = 31, 32: the rows past the first 32 in a second pass
+        hipLaunchKernelGGL(k_spline_apply<1>, grid, dim3(256), 0, s, y, c, rows, n, tblk, B, wchunk, 32);
+        SF_LAUNCH_CHECK();
+    }
     return SF_OK;
 }
 
