@@ -104,7 +104,7 @@ size_t sf_fft_workspace_bytes(int rows, int nf);
 /* Starfish/transforms.py:11-42  resample(wave, flux, new_wave): interpolating k=5 spline
  * (FITPACK knots x[0]x6, x[3:-3], x[-1]x6) per row, evaluated at new_wave.
  * h_wave[n] is a HOST pointer (the collocation factor is built on the host once per grid);
- * d_flux rows x n, d_new_wave[nq], d_out rows x nq.  d_work: sf_resample_workspace_bytes. */
+ * d_flux rows x n, d_new_wave[nq], d_out rows x nq (nq = 0: both may be null).  d_work: sf_resample_workspace_bytes. */
 int sf_resample(const double* h_wave, int n, const double* d_flux, int rows,
                 const double* d_new_wave, int nq, double* d_out, void* d_work,
                 size_t work_bytes, void* stream);
@@ -194,7 +194,7 @@ int sf_ctx_lda(const sf_ctx* ctx);  /* row stride used for the covariance matric
  *                               called at spectrum_model.py:298-299: law ccm89, Rv = 3.1)
  * Unused slots are ignored.  Row stride = sf_param_stride(). */
 typedef struct sf_model_desc {
-    int32_t has_vsini;
+    int32_t has_vsini;     /* needs 16 <= nf <= 65536: every call refuses other orders with SF_EINVAL up front */
     int32_t has_vz;
     int32_t has_log_scale; /* 0: renormalise by the integrated-flux ratio (spectrum_model.py:322-326) */
     int32_t has_global;

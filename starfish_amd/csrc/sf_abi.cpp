@@ -624,6 +624,13 @@ static int model_ok(const sf_ctx* c, const sf_model_desc* mdl) {
         sf_set_error("%d local kernels: at most %d (SF_MAX_LOCAL) are supported", mdl->n_local, SF_MAX_LOCAL);
         return SF_EINVAL;
     }
+    // the broadening runs a half-length transform (at most 65536 points in all) and the spline fit of its rows takes
+    // 16-point blocks: refused here, before a batch call enqueues anything, not by the launches themselves
+    if (mdl->has_vsini && c->n && (c->nf < SF_NF_MIN_VSINI || c->nf > SF_NF_MAX_VSINI)) {
+        sf_set_error("nf=%d: a model with vsini needs %d <= nf <= %d (SF_NF_MIN_VSINI, SF_NF_MAX_VSINI)", c->nf,
+                     SF_NF_MIN_VSINI, SF_NF_MAX_VSINI);
+        return SF_EINVAL;
+    }
     return SF_OK;
 }
 // the calling thread's current device becomes the context's (HIP's current device is per thread)
@@ -1152,6 +1159,7 @@ static int multi_layout(const sf_segment* segs, int nseg, const sf_model_desc* m
             sf_set_error("multi-order call: segment %d has no order context / batch / parameters", i);
             return SF_EINVAL;
         }
+        if (model_ok(c, mdl)) return SF_EINVAL;
         if (c->device != c0->device || c->m != c0->m || c->P != c0->P) {
             sf_set_error("multi-order call: segment %d differs from segment 0 in device, eigenspectra or grid dimensions", i);
             return SF_EINVAL;
@@ -1550,7 +1558,8 @@ extern "C" size_t sf_resample_workspace_bytes(int n, int rows) {
 }
 extern "C" int sf_resample(const double* h_wave, int n, const double* d_flux, int rows, const double* d_new_wave,
                            int nq, double* d_out, void* d_work, size_t work_bytes, void* stream) {
-    if (!h_wave || !d_flux || !d_new_wave || !d_out || rows <= 0 || nq < 0 || !d_work ||
+    // (no queries: the caller's query and output buffers may be empty, i.e. null)
+    if (!h_wave || !d_flux || (nq > 0 && (!d_new_wave || !d_out)) || rows <= 0 || nq < 0 || !d_work ||
         work_bytes < sf_resample_workspace_bytes(n, rows)) {
         sf_set_error("sf_resample: bad argument or workspace");
         return SF_EINVAL;

@@ -12,6 +12,8 @@
 #define SF_NB 256         // outer left-looking panel width
 #define SF_C_KMS 2.99792458e5
 #define SF_MAX_LOCAL 32   // local kernels per model (sf_fill.hip: 32-bit masks of the fill tiles, per-block tables)
+#define SF_NF_MIN_VSINI 16     // FFT lengths of a model with vsini: k_spline_apply takes whole 16-point blocks,
+#define SF_NF_MAX_VSINI 65536  // sf_launch_broaden transforms at most 65536 points
 
 typedef double sf_d4 __attribute__((ext_vector_type(4)));
 
