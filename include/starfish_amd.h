@@ -29,10 +29,11 @@
  *     re-entrant (like the reference's model object).  Every context call makes the context's device
  *     current for the calling thread.  Only the bench timing hooks (sf_profile_*) are process-global
  *     (mutex-protected).
- *   - the library reads NO environment variable.  (The tuning / timing switches named in starfish_amd/csrc -- SF_CHOL_*,
- *     SF_DF_*, SF_WIDE_*, ... -- exist only in the separate development build `make -C starfish_amd/csrc TUNING=1`
- *     (-DSF_TUNING -> libstarfish_amd_tuning.so), which tools/ and two GPU tests load on purpose; the shipped
- *     libstarfish_amd.so contains no getenv and none of their names: tests/test_host_logic.py checks the binary.)
+ *   - the library reads NO environment variable.  (The test and tracing switches named in starfish_amd/csrc --
+ *     SF_DF_* fault and trace aids, SF_TRANSFORM_UNFUSED, SF_BAND_TILES_POISON, SF_WIDE_STAMPS, SF_DIAG_STAMPS -- exist
+ *     only in the separate development build `make -C starfish_amd/csrc TUNING=1` (-DSF_TUNING ->
+ *     libstarfish_amd_tuning.so), which tools/ and two GPU tests load on purpose; the shipped libstarfish_amd.so
+ *     contains no getenv and none of their names: tests/test_host_logic.py checks the binary.)
  */
 #ifndef STARFISH_AMD_H
 #define STARFISH_AMD_H

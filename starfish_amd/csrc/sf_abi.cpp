@@ -1185,10 +1185,7 @@ static int multi_layout(const sf_segment* segs, int nseg, const sf_model_desc* m
 // Orders whose transform chains + fills run side by side (own stream and own set of transient buffers each): a chain is
 // ~14 small dependent launches, latency-bound -- alone it takes ~1 ms per order with the chip idle around it.
 #define SF_MULTI_LANES 3  // (4, 6 and 8 lanes measured: no further gain)
-static int multi_first_units(int U) {
-    static const int first = std::max(1, SF_TUNE_INT("SF_MULTI_FIRST", 256));  // tuning aid
-    return std::min(U, first);
-}
+static int multi_first_units(int U) { return std::min(U, 256); }
 static int multi_chunk_cap(int U, int bmax) { return std::min(U, std::max(U - multi_first_units(U), multi_first_units(U) + bmax)); }
 extern "C" size_t sf_multi_workspace_bytes(const sf_segment* segs, int nseg, const sf_model_desc* mdl) {
     Layout L;
@@ -1228,18 +1225,13 @@ extern "C" int sf_loglike_multi_batch(const sf_segment* segs, int nseg, const sf
     sf_exec* ex = &c0->exec;
     rc = sf_exec_prepare(ex);
     if (rc) return rc;
-    static const bool no_pipe = SF_TUNE_FLAG("SF_MULTI_NO_PIPELINE");  // tuning aid
-    static const int lanes_env = SF_TUNE_INT("SF_MULTI_LANES_USED", SF_MULTI_LANES);
-    const int nlanes = no_pipe ? 1 : std::max(1, std::min(lanes_env, SF_MULTI_LANES));
     // (the factorisation has its own executor, exec_potrf: all four streams of `ex` are free for the chains)
     // (no stream is created for the lanes: every additional ACTIVE stream costs dispatch latency on all of them --
     // one more for the wide sequence's A launches made a cfg-2 step 3 % slower)
-    hipStream_t lane_stream[SF_MULTI_LANES] = {no_pipe ? s : ex->aux, ex->side, ex->grp[0]};
+    hipStream_t lane_stream[SF_MULTI_LANES] = {ex->aux, ex->side, ex->grp[0]};
     const int first_units = multi_first_units(U);
-    if (!no_pipe) {
-        SF_HIP(hipEventRecord(ex->fork, s));
-        for (int l = 0; l < nlanes; ++l) SF_HIP(hipStreamWaitEvent(lane_stream[l], ex->fork, 0));
-    }
+    SF_HIP(hipEventRecord(ex->fork, s));
+    for (int l = 0; l < SF_MULTI_LANES; ++l) SF_HIP(hipStreamWaitEvent(lane_stream[l], ex->fork, 0));
     struct Chunk {
         int u0, units;
         hipEvent_t filled[SF_MULTI_LANES];
@@ -1250,7 +1242,7 @@ extern "C" int sf_loglike_multi_batch(const sf_segment* segs, int nseg, const sf
     for (int i = 0; i < nseg; ++i) {
         sf_ctx* c = segs[i].ctx;
         const int B = segs[i].B;
-        const int lane = i % nlanes;
+        const int lane = i % SF_MULTI_LANES;
         hipStream_t sp = lane_stream[lane];
         lane_used[lane] = true;
         Work w = with_trans_set(slice(W, u0), lane);
@@ -1281,8 +1273,8 @@ extern "C" int sf_loglike_multi_batch(const sf_segment* segs, int nseg, const sf
         u0 += B;
         if ((chunks.empty() && u0 - cu0 >= first_units) || i == nseg - 1) {
             Chunk ch{cu0, u0 - cu0, {}};
-            for (int l = 0; l < nlanes; ++l) {
-                if (!lane_used[l] || lane_stream[l] == s) continue;
+            for (int l = 0; l < SF_MULTI_LANES; ++l) {
+                if (!lane_used[l]) continue;
                 rc = sf_exec_event(ex, &ch.filled[l]);
                 if (rc) return rc;
                 SF_HIP(hipEventRecord(ch.filled[l], lane_stream[l]));

@@ -698,11 +698,8 @@ static int launch_forms_kernel(const sf_band_args& a, int nrb, int nblocks, hipS
     }));
     // waves 4.. prefetch the band rows in groups of 256 threads (one 16 x 16 block per group and
     // register): enough groups for SFB_PF registers to cover the nbr blocks of a block row
-    int nwaves = nbr <= SFB_PF ? 8 : nbr <= 2 * SFB_PF ? 12 : 16;
-    static const int force_waves = SF_TUNE_INT("SF_BAND_WAVES", 0);
-    if (force_waves) nwaves = force_waves;
-    if (nwaves < 8 || nwaves > 16 || (nwaves & 3) || ((nwaves - 4) / 4) * SFB_PF < nbr ||
-        nwaves * 64 < (nbr - 1 + nrb) * BB) {
+    const int nwaves = nbr <= SFB_PF ? 8 : nbr <= 2 * SFB_PF ? 12 : 16;
+    if (((nwaves - 4) / 4) * SFB_PF < nbr || nwaves * 64 < (nbr - 1 + nrb) * BB) {
         sf_set_error("band_forms: window too large for one workgroup");
         return SF_EINVAL;
     }
@@ -733,9 +730,8 @@ bool sf_band_twisted_applicable(int n, int halfwidth, int batch) {
             hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
             ncu = 1;
     }
-    static const bool off = SF_TUNE_FLAG("SF_BAND_NO_TWIST");
     const int nbr = band_nbr(halfwidth), nblk = (n + BB - 1) / BB;
-    if (off || n % BB != 0 || nblk < 6 * nbr) return false;
+    if (n % BB != 0 || nblk < 6 * nbr) return false;
     // One workgroup occupies a CU for the whole sweep, so the launch takes ceil(workgroups / CUs) rounds.
     // Two half sweeps per matrix are half as long each but twice as many, plus merge and separator sweep
     // (measured ~12 % of a sweep per round of matrices): take them when that means less time -- batch <=

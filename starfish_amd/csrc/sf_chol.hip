@@ -23,24 +23,14 @@
 #include "sf_common.h"
 #include <stdio.h>
 
-#ifdef SF_TUNING
-#define SF_PANEL_SKIPS(g, bit) ((g).skip & (bit))  // phase switched off (wrong results, timing only)
-#else
-#define SF_PANEL_SKIPS(g, bit) (false)
-#endif
 #define GT 128  // C tile edge of the MFMA kernel
 #define GK 16   // K slab staged in LDS per step
-#ifndef GLD
 #define GLD 17  // LDS row stride (doubles), odd: the 16 rows of a fragment hit 16 distinct bank pairs for
                 // ds_read_b64 (64 banks) and ds_read2_b64 (32 banks) alike
-#endif
 
 // Logical block id such that ids adjacent in work space run on the same XCD (block b is observed on
 // XCD b % 8; each XCD has its own L2).  Bijective for any grid size; placement only affects speed.
 __device__ __forceinline__ int sf_xcd_remap(int bid, int nblk) {
-#ifdef SF_NO_XCD_REMAP
-    return bid;
-#endif
     const int xcd = bid & 7, slot = bid >> 3;
     const int q = nblk >> 3, r = nblk & 7;
     const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
@@ -78,7 +68,7 @@ struct sf_gemm_args {
     int64_t sY;
     int ldy, mpad, nt128, tm_off, tn_off;
     int mt, nt;
-    int no_syrk;  // tuning aid: diagonal tiles through the generic path
+    int no_syrk;  // diagonal tiles through the generic path (the launchers always leave it 0)
 };
 
 // Diagonal 128 x 128 tile of a symmetric update C -= P P^T (block-diagonal launches): only the 36 MFMA
@@ -86,10 +76,9 @@ struct sf_gemm_args {
 // the 8 x 8 block grid hold 9 blocks; one wave takes 5 of them, its partner 4 plus a spare), and the single
 // operand P is staged once instead of twice.  40 block products per slab instead of 64.
 // Blocks above the diagonal are neither read nor written (nothing references them).
-template <bool RHS, int NTH>
+template <bool RHS>
 __device__ __forceinline__ void sf_syrk_diag_tile(const sf_gemm_args& g, int b, int row0, double (*As)[GT * GLD]) {
-    static_assert(NTH == 512, "8 waves");
-    constexpr int NP = 1024 / NTH, RPP = NTH / 8;
+    constexpr int NP = 2, RPP = 64;  // 512 threads (8 waves): two staging passes of 64 rows
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, lq = lane >> 4;
@@ -191,15 +180,12 @@ __device__ __forceinline__ void sf_syrk_diag_tile(const sf_gemm_args& g, int b, 
 // SIMD reach one per ~100 cycles, four waves per SIMD saturate the 64-cycle pipe.  The kernel is
 // therefore built for 4 waves/SIMD: 512 threads (8 waves, each 32 x 64 of the 128 x 128 tile = 2 x 4
 // MFMA tiles = 64 accumulator VGPRs), <= 128 VGPRs, two workgroups per CU.
-// Wave layout: WN waves across the 128 columns, 128/(16*TM) ... the tile is always 128 x 128;
-// NTH = 512 -> 8 waves of 32 x 64 (TM=2, TN=4);  NTH = 1024 -> 16 waves of 32 x 32 (TM=2, TN=2).
-template <bool NEG, bool RHS, int NTH>
-__global__ __launch_bounds__(NTH, (NTH == 256) ? 2 : NTH / 128) void k_gemm_nt(sf_gemm_args g) {
-    constexpr int TM = (NTH == 256) ? 4 : 2;
-    constexpr int TN = (NTH == 1024) ? 2 : 4;
+template <bool NEG, bool RHS>
+__global__ __launch_bounds__(512, 4) void k_gemm_nt(sf_gemm_args g) {
+    constexpr int TM = 2, TN = 4;
     constexpr int WN = 128 / (16 * TN);   // waves across columns
-    constexpr int NP = 1024 / NTH;        // staging passes of NTH/8 rows each
-    constexpr int RPP = NTH / 8;          // rows per staging pass
+    constexpr int NP = 2;                 // staging passes of 64 rows each
+    constexpr int RPP = 64;               // rows per staging pass
     __shared__ __attribute__((aligned(16))) double As[2][GT * GLD];
     __shared__ __attribute__((aligned(16))) double Bs[2][GT * GLD];
 
@@ -223,8 +209,8 @@ __global__ __launch_bounds__(NTH, (NTH == 256) ? 2 : NTH / 128) void k_gemm_nt(s
         if (g.Cin) g.Cin += jb * g.dC;
         g.Cout += jb * g.dC;
         if (RHS && g.rhs) g.rhs += jb * SF_NB;
-        if (NTH == 512 && NEG && tm == tn && rows_here == GT && g.K > 0 && g.A == g.B && g.Cin && !g.no_syrk) {
-            sf_syrk_diag_tile<RHS, 512>(g, b, tm * GT, As);
+        if (NEG && tm == tn && rows_here == GT && g.K > 0 && g.A == g.B && g.Cin && !g.no_syrk) {
+            sf_syrk_diag_tile<RHS>(g, b, tm * GT, As);
             return;
         }
     } else {
@@ -406,111 +392,6 @@ __device__ __forceinline__ double sf_readlane_d(double v, int srclane) {
     return u.d;
 }
 
-// 64 x 64 diagonal block at (c, c), ONE wave per matrix: lane r keeps row r in registers and the
-// unblocked right-looking Cholesky (dpotf2 order: pivot sqrt, column scale by the reciprocal pivot,
-// rank-1 update) broadcasts column entries with v_readlane -- no LDS, no barriers.
-// Besides L (written in place) it leaves Lt[k][j] = L[j][k] (j > k), Lt[k][k] = 1 / L[k][k] in the
-// read-only side buffer `ltbuf` that k_trsm_leaf fetches through the scalar cache.
-// With a right-hand side (rhs != NULL) the forward substitution L z = R rides along: lane r carries
-// R[c + r]; after column k is final, z_k = R_k / L_kk is broadcast and R_r -= L_rk z_k (r > k).
-#define SF_LTB (SF_LEAF * SF_LEAF + SF_LEAF)  // doubles per matrix in the side buffer: Lt + z
-__global__ __launch_bounds__(64) void k_potrf_leaf(double* __restrict__ base, int lda, int64_t stride,
-                                                   int c, int* __restrict__ info, int info_off,
-                                                   double* __restrict__ ltbuf, double* __restrict__ rhs,
-                                                   int ldr) {
-    const int b = blockIdx.x, r = threadIdx.x;
-    double* D = base + (int64_t)b * stride + (int64_t)c * lda + c;
-    double* prow = D + (int64_t)r * lda;
-    double a[SF_LEAF];
-#pragma unroll
-    for (int j = 0; j < SF_LEAF; j += 2) {
-        const double2 v = *(const double2*)(prow + j);
-        a[j] = v.x;
-        a[j + 1] = v.y;
-    }
-    int bad = 0;
-    double* lt = ltbuf + (int64_t)b * SF_LTB;
-    double rv = rhs ? rhs[(int64_t)b * ldr + c + r] : 0.0;
-#pragma unroll
-    for (int k = 0; k < SF_LEAF; ++k) {
-        const double akk = sf_readlane_d(a[k], k);
-        if (!(akk > 0.0) && !bad) bad = info_off + c + k + 1;
-        const double d = sqrt(akk);
-        const double inv = 1.0 / d;
-        a[k] = (r > k) ? a[k] * inv : ((r == k) ? d : 0.0);
-        lt[k * SF_LEAF + r] = (r == k) ? inv : a[k];
-        const double zk = sf_readlane_d(rv, k) * inv;
-        rv = (r > k) ? rv - a[k] * zk : ((r == k) ? zk : rv);
-#pragma unroll
-        for (int j = k + 1; j < SF_LEAF; ++j) {
-            const double ljk = sf_readlane_d(a[k], j);
-            a[j] -= a[k] * ljk;
-        }
-    }
-    // lower triangle back in place (entries above the diagonal of row r are left untouched)
-#pragma unroll
-    for (int j = 0; j < SF_LEAF; ++j)
-        if (j <= r) prow[j] = a[j];
-    if (rhs) {
-        rhs[(int64_t)b * ldr + c + r] = rv;  // z of this block
-        lt[SF_LEAF * SF_LEAF + r] = rv;
-    }
-    if (r == 0 && bad && info[b] == 0) info[b] = bad;
-}
-
-// Rows below a factored 64 x 64 block:  X L^T = A  solved in place.  One wave handles 64 rows: the
-// 64 x 64 slab is fetched with coalesced 16-byte loads (two full rows per instruction), transposed
-// through LDS so that lane r owns row r in registers, eliminated with one v_fma_f64 per element whose
-// L^T operand comes from the read-only side buffer through the scalar cache, and written back the
-// same way.  With a right-hand side, the row's entry is updated right-looking: R[row] -= x . z_block.
-__global__ __launch_bounds__(64) void k_trsm_leaf(double* __restrict__ base, int lda, int64_t stride,
-                                                  int c, int n, const double* __restrict__ ltbuf,
-                                                  double* __restrict__ rhs, int ldr, int rhs_rows) {
-    __shared__ double tile[SF_LEAF * (SF_LEAF + 1)];
-    const int b = blockIdx.y, lane = threadIdx.x;
-    const double* __restrict__ Lt = ltbuf + (int64_t)b * SF_LTB;
-    const int row0 = c + SF_LEAF + blockIdx.x * SF_LEAF;
-    const int nvalid = min(SF_LEAF, n - row0);
-    double* slab = base + (int64_t)b * stride + (int64_t)row0 * lda + c;
-    const int half = lane >> 5, col2 = (lane & 31) * 2;
-#pragma unroll 8
-    for (int i = 0; i < SF_LEAF / 2; ++i) {
-        const int rr = 2 * i + half;
-        if (rr < nvalid) {
-            const double2 v = *(const double2*)(slab + (int64_t)rr * lda + col2);
-            tile[rr * 65 + col2] = v.x;
-            tile[rr * 65 + col2 + 1] = v.y;
-        }
-    }
-    __syncthreads();
-    double x[SF_LEAF];
-#pragma unroll
-    for (int j = 0; j < SF_LEAF; ++j) x[j] = tile[lane * 65 + j];
-#pragma unroll
-    for (int k = 0; k < SF_LEAF; ++k) {
-        x[k] *= Lt[k * SF_LEAF + k];
-        const double xk = x[k];
-#pragma unroll
-        for (int j = k + 1; j < SF_LEAF; ++j) x[j] -= xk * Lt[k * SF_LEAF + j];
-    }
-#pragma unroll
-    for (int j = 0; j < SF_LEAF; ++j) tile[lane * 65 + j] = x[j];
-    if (rhs && lane < nvalid && row0 + lane < rhs_rows) {
-        const double* __restrict__ z = Lt + SF_LEAF * SF_LEAF;
-        double acc = rhs[(int64_t)b * ldr + row0 + lane];
-#pragma unroll
-        for (int j = 0; j < SF_LEAF; ++j) acc -= x[j] * z[j];
-        rhs[(int64_t)b * ldr + row0 + lane] = acc;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int i = 0; i < SF_LEAF / 2; ++i) {
-        const int rr = 2 * i + half;
-        if (rr < nvalid)
-            *(double2*)(slab + (int64_t)rr * lda + col2) = make_double2(tile[rr * 65 + col2], tile[rr * 65 + col2 + 1]);
-    }
-}
-
 __device__ __forceinline__ double sf_wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
@@ -604,34 +485,14 @@ static int launch_gemm(sf_gemm_args g, int batch, bool neg, double flops, hipStr
         sf_set_error("gemm grid too large");
         return SF_EINVAL;
     }
-    static const bool no_syrk = SF_TUNE_FLAG("SF_NO_SYRK");
-    g.no_syrk = no_syrk;
     void* tok;
     sf_prof_gemm_begin(s, flops, &tok);
-    static const bool big = SF_TUNE_FLAG("SF_GEMM_1024");  // tuning aid: 16 waves of 32 x 32
-    static const bool small = SF_TUNE_FLAG("SF_GEMM_256");  // tuning aid: 4 waves of 64 x 64
-    if (small) {
-        if (g.rhs)
-            hipLaunchKernelGGL((k_gemm_nt<true, true, 256>), dim3((unsigned)nblk), dim3(256), 0, s, g);
-        else if (neg)
-            hipLaunchKernelGGL((k_gemm_nt<true, false, 256>), dim3((unsigned)nblk), dim3(256), 0, s, g);
-        else
-            hipLaunchKernelGGL((k_gemm_nt<false, false, 256>), dim3((unsigned)nblk), dim3(256), 0, s, g);
-    } else if (big) {
-        if (g.rhs)
-            hipLaunchKernelGGL((k_gemm_nt<true, true, 1024>), dim3((unsigned)nblk), dim3(1024), 0, s, g);
-        else if (neg)
-            hipLaunchKernelGGL((k_gemm_nt<true, false, 1024>), dim3((unsigned)nblk), dim3(1024), 0, s, g);
-        else
-            hipLaunchKernelGGL((k_gemm_nt<false, false, 1024>), dim3((unsigned)nblk), dim3(1024), 0, s, g);
-    } else {
-        if (g.rhs)
-            hipLaunchKernelGGL((k_gemm_nt<true, true, 512>), dim3((unsigned)nblk), dim3(512), 0, s, g);
-        else if (neg)
-            hipLaunchKernelGGL((k_gemm_nt<true, false, 512>), dim3((unsigned)nblk), dim3(512), 0, s, g);
-        else
-            hipLaunchKernelGGL((k_gemm_nt<false, false, 512>), dim3((unsigned)nblk), dim3(512), 0, s, g);
-    }
+    if (g.rhs)
+        hipLaunchKernelGGL((k_gemm_nt<true, true>), dim3((unsigned)nblk), dim3(512), 0, s, g);
+    else if (neg)
+        hipLaunchKernelGGL((k_gemm_nt<true, false>), dim3((unsigned)nblk), dim3(512), 0, s, g);
+    else
+        hipLaunchKernelGGL((k_gemm_nt<false, false>), dim3((unsigned)nblk), dim3(512), 0, s, g);
     sf_prof_gemm_end(tok);
     SF_LAUNCH_CHECK();
     return SF_OK;
@@ -674,41 +535,8 @@ int sf_launch_logdet_z(const double* L, int n, int lda, int64_t stride, int batc
 }
 
 // Panel scratch T (per matrix, row stride SF_LDT): rows [0, pw) the updated diagonal block,
-// rows [pw, 2pw) an identity block that turns into W = L_kk^-T while the diagonal block is factored,
+// rows [pw, 2pw) the rows of W = L_kk^-T while the diagonal block is factored (k_diag_mfma),
 // rows [2pw, ...) the updated rows below the diagonal block.
-__global__ __launch_bounds__(256) void k_set_identity(double* __restrict__ T, int64_t sT, int pw) {
-    double* I = T + (int64_t)blockIdx.y * sT + (int64_t)pw * SF_LDT;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < pw * pw; e += gridDim.x * 256) {
-        const int i = e / pw, j = e - i * pw;
-        I[(int64_t)i * SF_LDT + j] = (i == j) ? 1.0 : 0.0;
-    }
-}
-
-// After the diagonal block is factored inside T: copy L_kk back into the matrix and store
-// Wt[c][j] = W[j][c] = (L_kk^-1)[c][j] (lower triangular, zero above) for the panel solve GEMM.
-__global__ __launch_bounds__(256) void k_panel_finish(const double* __restrict__ T, int64_t sT, int pw,
-                                                      double* __restrict__ Cdiag, int ldc, int64_t sC,
-                                                      double* __restrict__ Wt, int64_t sW) {
-    __shared__ double tile[32][33];
-    const int b = blockIdx.z;
-    const double* Tb = T + (int64_t)b * sT;
-    double* Cb = Cdiag + (int64_t)b * sC;
-    double* Wb = Wt + (int64_t)b * sW;
-    const int bi = blockIdx.y * 32, bj = blockIdx.x * 32;  // 32 x 32 block (rows bi.., cols bj..)
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8 threads
-    for (int r = ty; r < 32; r += 8) {
-        const int i = bi + r, j = bj + tx;
-        if (i < pw && j < pw) {
-            if (j <= i) Cb[(int64_t)i * ldc + j] = Tb[(int64_t)i * SF_LDT + j];
-            tile[r][tx] = Tb[(int64_t)(pw + i) * SF_LDT + j];  // W[i][j]
-        }
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-        const int c = bj + r, j = bi + tx;  // Wt[c][j] = W[j][c]
-        if (c < pw && j < pw) Wb[(int64_t)c * SF_LDT + j] = (j <= c) ? tile[tx][r] : 0.0;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
 // Diagonal-block step of one panel as ONE launch on the matrix cores (one workgroup of 16 waves per
@@ -725,8 +553,8 @@ __global__ __launch_bounds__(256) void k_panel_finish(const double* __restrict__
 //   X  every wave solves the blocks it still holds as a product with the 16 x 16 inverse F and writes
 //      them out: L to the matrix (and in place, as operand of later columns), W transposed to Wt.
 // The identity block is implicit (row block e of E starts at column e with X = F^T).  Finally
-// z_k = L_kk^-1 r_k as a product with the explicit inverse.  Replaces k_set_identity + 4 x (k_potrf_leaf,
-// k_trsm_leaf, K=64 k_gemm_nt) + k_panel_finish: one scheduling wait on the contended chip instead of 13.
+// z_k = L_kk^-1 r_k as a product with the explicit inverse.  One launch per panel: one scheduling wait on the
+// contended chip.
 #define DBS (16 * 17)
 #define DLD 17
 __device__ __forceinline__ double sfd_rsqrt(double p) {
@@ -739,12 +567,12 @@ __device__ __forceinline__ double sfd_rsqrt(double p) {
     return y;
 }
 
-template <int NT>
-__global__ __launch_bounds__(NT) void k_diag_mfma(double* __restrict__ T, int64_t sT, int pw,
+__global__ __launch_bounds__(1024) void k_diag_mfma(double* __restrict__ T, int64_t sT, int pw,
                                                       int* __restrict__ info, int info_off,
                                                       double* __restrict__ rhs, int ldr,
                                                       double* __restrict__ Cdiag, int ldc, int64_t sC,
                                                       double* __restrict__ Wt, int64_t sW) {
+    constexpr int NT = 1024;  // 16 waves
     __shared__ double LK[(NT / 64 - 1) * DBS];  // L(k, j), j < k: the B operand of the whole block column
     __shared__ double ST[(NT / 64) * DBS];      // per-wave staging block (accumulator layout -> operand layout)
     __shared__ double Fb[DBS];       // inverse of the current 16 x 16 diagonal factor
@@ -1118,41 +946,36 @@ __global__ __launch_bounds__(512) void k_diag_lds(const double* __restrict__ T, 
     sf_diag_lds_body(T, sT, pw, info, info_off, rhs, ldr, Cdiag, ldc, sC, Wt, sW, fp0, blockIdx.x, dsm, threadIdx.x,
                      blockIdx.x == 0 ? stamps : nullptr);
 }
-static const int chain_prio = SF_TUNE_INT("SF_CHAIN_PRIO", 1);  // tuning aid: 0 = the chain's workgroups at normal wave priority
 #define SF_DIAG_LDS_BYTES ((37 * DBS + 128) * sizeof(double))
+// (the chain's workgroups -- this launch and the narrow steps that park the next diagonal tile -- run at raised wave priority)
 static int sf_launch_diag128(double* T, int64_t sT, int pw, int* info, int info_off, double* rhs, int ldr, double* Cdiag,
                              int ldc, int64_t sC, double* Wt, int64_t sW, int batch, hipStream_t s, int fp0 = 0) {
-    static const bool scratch = SF_TUNE_FLAG("SF_DIAG_SCRATCH");  // tuning aid: the L2-resident k_diag_mfma<512>
-    if (scratch && fp0 == 0) {
-        hipLaunchKernelGGL(k_diag_mfma<512>, dim3(batch), dim3(512), 0, s, T, sT, pw, info, info_off, rhs, ldr, Cdiag, ldc, sC, Wt, sW);
-    } else {
-        static sf_dev_once attr_once;  // devices whose function attributes are set
-        SF_CHECK(sf_once_per_device(&attr_once, []() -> int {
-            SF_HIP(hipFuncSetAttribute((const void*)k_diag_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            return SF_OK;
-        }));
-        long long* stamps = nullptr;
+    static sf_dev_once attr_once;  // devices whose function attributes are set
+    SF_CHECK(sf_once_per_device(&attr_once, []() -> int {
+        SF_HIP(hipFuncSetAttribute((const void*)k_diag_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        return SF_OK;
+    }));
+    long long* stamps = nullptr;
 #ifdef SF_TUNING
-        static int printed = 0;
-        static long long* hs = nullptr;
-        if (SF_TUNE_FLAG("SF_DIAG_STAMPS") && printed < 6) {
-            if (!hs) SF_HIP(hipHostMalloc((void**)&hs, 16 * sizeof(long long)));
-            for (int i = 0; i < 16; ++i) hs[i] = 0;
-            stamps = hs;
-        }
-#endif
-        hipLaunchKernelGGL(k_diag_lds, dim3(batch), dim3(512), SF_DIAG_LDS_BYTES, s, T, sT, pw, info, info_off, rhs, ldr, Cdiag, ldc,
-                           sC, Wt, sW, fp0, chain_prio, stamps);
-#ifdef SF_TUNING
-        if (stamps) {  // (synchronises) phases of workgroup 0, us
-            (void)hipStreamSynchronize(s);
-            ++printed;
-            fprintf(stderr, "k_diag_lds batch %d: tile load %.1f | 8 block columns %.1f (last column: U %.1f, P %.1f, barrier %.1f, X + barrier %.1f) | W store %.1f + z %.1f | drain %.1f | total %.1f us\n",
-                    batch, (hs[1] - hs[0]) / 100.0, (hs[2] - hs[1]) / 100.0, (hs[9] - hs[8]) / 100.0, (hs[10] - hs[9]) / 100.0, (hs[11] - hs[10]) / 100.0,
-                    (hs[2] - hs[11]) / 100.0, 0.0, (hs[3] - hs[2]) / 100.0, (hs[4] - hs[3]) / 100.0, (hs[4] - hs[0]) / 100.0);
-        }
-#endif
+    static int printed = 0;
+    static long long* hs = nullptr;
+    if (SF_TUNE_FLAG("SF_DIAG_STAMPS") && printed < 6) {
+        if (!hs) SF_HIP(hipHostMalloc((void**)&hs, 16 * sizeof(long long)));
+        for (int i = 0; i < 16; ++i) hs[i] = 0;
+        stamps = hs;
     }
+#endif
+    hipLaunchKernelGGL(k_diag_lds, dim3(batch), dim3(512), SF_DIAG_LDS_BYTES, s, T, sT, pw, info, info_off, rhs, ldr, Cdiag, ldc,
+                       sC, Wt, sW, fp0, 1, stamps);
+#ifdef SF_TUNING
+    if (stamps) {  // (synchronises) phases of workgroup 0, us
+        (void)hipStreamSynchronize(s);
+        ++printed;
+        fprintf(stderr, "k_diag_lds batch %d: tile load %.1f | 8 block columns %.1f (last column: U %.1f, P %.1f, barrier %.1f, X + barrier %.1f) | W store %.1f + z %.1f | drain %.1f | total %.1f us\n",
+                batch, (hs[1] - hs[0]) / 100.0, (hs[2] - hs[1]) / 100.0, (hs[9] - hs[8]) / 100.0, (hs[10] - hs[9]) / 100.0, (hs[11] - hs[10]) / 100.0,
+                (hs[2] - hs[11]) / 100.0, 0.0, (hs[3] - hs[2]) / 100.0, (hs[4] - hs[3]) / 100.0, (hs[4] - hs[0]) / 100.0);
+    }
+#endif
     SF_LAUNCH_CHECK();
     return SF_OK;
 }
@@ -1179,9 +1002,6 @@ struct sf_panel_args {
     int k0, pw;       // panel columns [k0, k0 + pw), pw in {0, 64, 128}
     int row0, nslab;  // nslab slabs of 128 rows, the first at row0 (multiple of 128); the last one may be shorter
     int slab_step;    // distance between consecutive slabs of this launch, in slabs (slab groups are interleaved)
-#ifdef SF_TUNING
-    int skip;         // tuning builds only (wrong results, timing only): 1 no solve, 2 no rank-pw update, 4 no main loop
-#endif
     // split-K for launches that cannot fill the chip (late panels, small batches): mode 1 = ksplit workgroups per
     // slab each accumulate kchunk K-slabs and park their 128 x 128 partial sum in `part`; mode 2 = one workgroup
     // per slab adds the partial sums in fixed order (deterministic) and runs steps 2-4; mode 0 = everything at once
@@ -1445,9 +1265,7 @@ __device__ __forceinline__ bool sf_df_wait(const int* flag, int target, int* abo
 }
 // call after __syncthreads(): every wave's stores have been issued and waited for
 __device__ __forceinline__ void sf_df_release() {
-#ifndef SF_EXP_DF_NORELEASE  // (timing experiment, stale reads possible: what do the L2 write-backs of the releases cost?)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 __device__ __forceinline__ void sf_df_set(int* flag, int value) {
@@ -1514,11 +1332,7 @@ __device__ __forceinline__ void sf_panel_body(GA& g, const sf_panel_task& tk, co
         // instead of four 64-bit pointers advanced by VALU adds -- the kernel sits at the 128-VGPR limit, and a pointer that
         // spills is reloaded inside the K loop, where the wait for the scratch load also waits for the operand loads)
         unsigned Aoff[2], Boff[2];
-#ifdef SF_EXP_AL2  // timing only: every slab streams the rows of the panel's first slab (L2-resident A operand)
-        const double* Abase = sf_uniform_ptr(Cb + (int64_t)(k0 + (k0 + 2 * GT <= g.n ? GT : 0)) * g.lda);
-#else
         const double* Abase = sf_uniform_ptr(Cb + (int64_t)row0 * g.lda);
-#endif
         const double* Bbase = sf_uniform_ptr(Cb + (int64_t)k0 * g.lda);
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -1549,7 +1363,7 @@ __device__ __forceinline__ void sf_panel_body(GA& g, const sf_panel_task& tk, co
             }
         };
         auto gwait = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
-        const int nk_all = SF_PANEL_SKIPS(g, 4) ? 0 : k0 / GK;
+        const int nk_all = k0 / GK;
         // band: the K loop starts at the first column where both operands can be non-zero (a band slab's own rows;
         // for the dense border rows the panel's rows decide -- what lies left of that was never even written)
         const int klo = g.kband ? min(max((row0 < g.nband ? row0 : k0) - g.kband, 0) / GK, nk_all) : min(g.fp / GK, nk_all);
@@ -1658,40 +1472,9 @@ __device__ __forceinline__ void sf_panel_body(GA& g, const sf_panel_task& tk, co
             const double* Ab = A2 + cur * GT * GK;
             const double* Bb = B2 + cur * GT * GK;
             if (!wave_live) return;
-#ifdef SF_EXP_FRAGPF
-            double2 a[2][TM], bb[2][TN];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    const int row = wm * (16 * TM) + i * 16 + l15;
-                    a[h][i] = *(const double2*)(Ab + row * GK + 2 * ((2 * lq + h) ^ sf_swz(row)));
-                }
-#pragma unroll
-                for (int i = 0; i < TN; ++i) {
-                    const int row = wn * (16 * TN) + i * 16 + l15;
-                    bb[h][i] = *(const double2*)(Bb + row * GK + 2 * ((2 * lq + h) ^ sf_swz(row)));
-                }
-            }
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < TN; ++ni) {
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[h][mi].x, bb[h][ni].x, acc[mi][ni], 0, 0, 1);
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[h][mi].y, bb[h][ni].y, acc[mi][ni], 0, 0, 1);
-                    }
-#else
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 double2 a[TM], bb[TN];
-#ifdef SF_EXP_NOLDSREAD
-#pragma unroll
-                for (int i = 0; i < TM; ++i) asm volatile("" : "=v"(a[i].x), "=v"(a[i].y));
-#pragma unroll
-                for (int i = 0; i < TN; ++i) asm volatile("" : "=v"(bb[i].x), "=v"(bb[i].y));
-#else
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
                     const int row = wm * (16 * TM) + i * 16 + l15;
@@ -1702,10 +1485,6 @@ __device__ __forceinline__ void sf_panel_body(GA& g, const sf_panel_task& tk, co
                     const int row = wn * (16 * TN) + i * 16 + l15;
                     bb[i] = *(const double2*)(Bb + row * GK + 2 * ((2 * lq + h) ^ sf_swz(row)));
                 }
-#endif
-#ifdef SF_EXP_SETPRIO
-                __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
                 for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
@@ -1713,21 +1492,13 @@ __device__ __forceinline__ void sf_panel_body(GA& g, const sf_panel_task& tk, co
                         acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi].x, bb[ni].x, acc[mi][ni], 0, 0, 1);  // neg:[1,0,0]
                         acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi].y, bb[ni].y, acc[mi][ni], 0, 0, 1);
                     }
-#ifdef SF_EXP_SETPRIO
-                __builtin_amdgcn_s_setprio(0);
-#endif
             }
-#endif
         };
         for (int kt = 0; kt + 1 < nk; ++kt) {
-#ifndef SF_EXP_NOGLOAD
             gload(kbeg + kt + 1, (kt & 1) ^ 1);
-#endif
             compute(kt & 1);
             gwait();
-#ifndef SF_EXP_NOBARRIER
             __syncthreads();
-#endif
         }
         if (nk > 0) compute((nk - 1) & 1);
         __syncthreads();  // the epilogue re-uses the LDS with its own layouts
@@ -1752,7 +1523,7 @@ __device__ __forceinline__ void sf_panel_body(GA& g, const sf_panel_task& tk, co
         if (tk.stamps && tid == 0) tk.stamps[1] = wall_clock64();
 #endif
         // ---------------------------------------------------------------- 2: L = T W through LDS
-        const int nsb = SF_PANEL_SKIPS(g, 1) ? 0 : pw >> 4;  // 16-column blocks of the panel (4 or 8)
+        const int nsb = pw >> 4;  // 16-column blocks of the panel (4 or 8)
         const double* Wp[2];
 #pragma unroll
         for (int p = 0; p < 2; ++p)
@@ -1882,7 +1653,7 @@ __device__ __forceinline__ void sf_panel_body(GA& g, const sf_panel_task& tk, co
             }
         }
         const int nstore = h == 0 ? 5 : 4;
-        const int nk2 = SF_PANEL_SKIPS(g, 2) ? 0 : pw / GK;
+        const int nk2 = pw / GK;
         const int lr = tid >> 3, lc = (tid & 7) * 2;
         const double* Lp[2];
 #pragma unroll
@@ -2210,9 +1981,7 @@ __device__ __forceinline__ void sf_panelw_body(const sf_panelw_args& g, const in
                 mfma_part(a0, b0, I0(), I8());
                 __builtin_amdgcn_s_setprio(0);
             }
-#ifndef SF_EXPW_NOGLOAD
             if (kt + 2 < nk) gload(kt + 2, s2);
-#endif
             if (wave_live) {
                 frag(s0, 1, a1, b1);
                 __builtin_amdgcn_s_setprio(1);
@@ -2224,9 +1993,7 @@ __device__ __forceinline__ void sf_panelw_body(const sf_panelw_args& g, const in
                 __builtin_amdgcn_s_setprio(0);
             }
             gwait();
-#ifndef SF_EXPW_NOBARRIER
             __syncthreads();
-#endif
             const int t = s0;
             s0 = s1;
             s1 = s2;
@@ -2527,19 +2294,14 @@ __global__ __launch_bounds__(1024) void k_chol_panel_w(sf_panelw_args g) {
 static size_t sf_split_region_tiles(void) { return 2 * SF_CHIP_WGS; }  // partial-sum tiles per region
 __device__ __forceinline__ size_t sf_split_region_tiles_dev(void) { return 2 * SF_CHIP_WGS; }
 static int sf_split_policy(long long wgs, int nk) {
-    static const int force = SF_TUNE_INT("SF_CHOL_SPLIT", -1);  // tuning aid
     int S = 1;
     // (a split launch stops at 384 of the 512 slots: two slab groups are in flight and the chain's launches need room --
     // N = 4096, cap 512 / 384 / 256 / 192: B = 16 11.22 / 11.18 / 11.26 / 11.71 ms, 32: 16.06 / 15.78 / 16.09 / 17.28,
     // 64: 27.42 / 27.05 / 26.89 / 28.7)
-    static const int cap = SF_TUNE_INT("SF_SPLIT_CAP", 384);
-    while (2 * S <= SF_SPLIT_MAX && wgs * 2 * S <= cap && nk / (2 * S) >= 8) S *= 2;
-    if (force >= 1) {
-        S = 1;
-        while (2 * S <= force && 2 * S <= SF_SPLIT_MAX && wgs * 2 * S <= 2 * SF_CHIP_WGS && nk / (2 * S) >= 8) S *= 2;
-    }
+    while (2 * S <= SF_SPLIT_MAX && wgs * 2 * S <= 384 && nk / (2 * S) >= 8) S *= 2;
     return S;
 }
+// per matrix: a reserved region of SF_LTB_DOUBLES (unused), the panel scratch T and two W^T buffers; then the
 // partial-sum tiles: one region for the chain (top) launches, one per slab group
 size_t sf_potrf_work_doubles(int n, int batch) {
     const size_t b = (size_t)batch;
@@ -2564,7 +2326,7 @@ size_t sf_potrf_work_doubles(int n, int batch) {
 //       K = SF_NB): keeps the next diagonal block ready without a long-K launch of only a few tiles;
 //       its diagonal tiles also apply rhs[j-rows] -= L[j-rows, k0:k1] z[k0:k1]
 //   D   factor the diagonal block together with an identity block -> L_kk and W = L_kk^-T
-//       (64-column leaf steps on the small (2 pw) x pw problem), L_kk -> matrix, W^T (F)
+//       (k_diag_mfma), L_kk -> matrix, W^T (F)
 //   G   C[k1:, k0:k1] <- T[below] W                               MFMA (triangular B)
 // With rhs != NULL (batch x ldr) the forward substitution L z = rhs is fused (R and D); z overwrites rhs.
 //
@@ -2577,8 +2339,7 @@ static int sf_launch_potrf_v1(double* A, int n, int lda, int64_t stride, int bat
         sf_set_error("potrf: n must be a positive multiple of %d, lda >= n and even, workspace required", SF_LEAF);
         return SF_EINVAL;
     }
-    double* ltbuf = work;
-    double* T = ltbuf + (size_t)batch * SF_LTB_DOUBLES;
+    double* T = work + (size_t)batch * SF_LTB_DOUBLES;
     const int64_t sT = (int64_t)(n + SF_NB) * SF_LDT + SF_TSKEW;
     double* Wt2 = T + (size_t)batch * sT;  // two W^T buffers, alternating by panel parity
     const int64_t sW = (int64_t)SF_NB * SF_LDT + SF_TSKEW;
@@ -2587,9 +2348,6 @@ static int sf_launch_potrf_v1(double* A, int n, int lda, int64_t stride, int bat
     SF_TRY(sf_exec_prepare(ex));
     hipStream_t c = ex->side;  // side ("critical chain") stream
     auto next_event = [&](hipEvent_t* e) { return sf_exec_event(ex, e); };
-    static const bool no_lookahead = SF_TUNE_FLAG("SF_NO_LOOKAHEAD");  // tuning aid: single stream
-    static const int rlazy = SF_TUNE_INT("SF_RLAZY", 1);  // tuning aid; measured: no gain for 2, 4, 8
-    if (no_lookahead) c = s;
     hipEvent_t e_fork, e_gt_prev = nullptr;
     SF_TRY(next_event(&e_fork));
     SF_HIP(hipEventRecord(e_fork, s));
@@ -2670,42 +2428,9 @@ static int sf_launch_potrf_v1(double* A, int n, int lda, int64_t stride, int bat
             SF_HIP(hipEventRecord(e_ur, s));
         }
         // ---- D + F on the side stream (T rows [0, pw) already hold the fully updated diagonal block)
-        static const bool leaf_diag = SF_TUNE_FLAG("SF_LEAF_DIAG");  // tuning aid: the 13-launch chain
-        if (!leaf_diag) {
-            hipLaunchKernelGGL(k_diag_mfma<1024>, dim3(batch), dim3(1024), 0, c, T, sT, pw, info, k0,
-                               rhs ? rhs + k0 : nullptr, ldr, A + (int64_t)k0 * lda + k0, lda, stride, Wt, sW);
-            SF_LAUNCH_CHECK();
-        } else {
-            hipLaunchKernelGGL(k_set_identity, dim3(64, batch), dim3(256), 0, c, T, sT, pw);
-            SF_LAUNCH_CHECK();
-            for (int cc = 0; cc < pw; cc += SF_LEAF) {
-                hipLaunchKernelGGL(k_potrf_leaf, dim3(batch), dim3(64), 0, c, T, SF_LDT, sT, cc, info, k0, ltbuf,
-                                   rhs ? rhs + k0 : nullptr, ldr);
-                SF_LAUNCH_CHECK();
-                const int below = 2 * pw - (cc + SF_LEAF);
-                hipLaunchKernelGGL(k_trsm_leaf, dim3((below + 63) / 64, batch), dim3(64), 0, c, T, SF_LDT, sT,
-                                   cc, 2 * pw, (const double*)ltbuf, rhs ? rhs + k0 : nullptr, ldr, pw);
-                SF_LAUNCH_CHECK();
-                if (cc + SF_LEAF < pw) {
-                    sf_gemm_args g = {};
-                    const int o = cc + SF_LEAF;
-                    g.A = g.B = T + (int64_t)o * SF_LDT + cc;
-                    g.Cin = g.Cout = T + (int64_t)o * SF_LDT + o;
-                    g.sA = g.sB = g.sCin = g.sCout = sT;
-                    g.lda = g.ldb = g.ldcin = g.ldcout = SF_LDT;
-                    g.M = below;
-                    g.Nc = pw - o;
-                    g.K = SF_LEAF;
-                    g.tri = 1;
-                    g.remap_after = 0x7fffffff;
-                    const double useful = (double)g.M * g.Nc - 0.5 * (double)g.Nc * (g.Nc - 1);
-                    SF_TRY(launch_gemm(g, batch, true, 2.0 * SF_LEAF * useful * batch, c));
-                }
-            }
-            hipLaunchKernelGGL(k_panel_finish, dim3((pw + 31) / 32, (pw + 31) / 32, batch), dim3(256), 0, c,
-                               (const double*)T, sT, pw, A + (int64_t)k0 * lda + k0, lda, stride, Wt, sW);
-            SF_LAUNCH_CHECK();
-        }
+        hipLaunchKernelGGL(k_diag_mfma, dim3(batch), dim3(1024), 0, c, T, sT, pw, info, k0, rhs ? rhs + k0 : nullptr, ldr,
+                           A + (int64_t)k0 * lda + k0, lda, stride, Wt, sW);
+        SF_LAUNCH_CHECK();
         if (nbelow <= 0) break;
         SF_TRY(next_event(&e_f));
         SF_HIP(hipEventRecord(e_f, c));
@@ -2733,19 +2458,14 @@ static int sf_launch_potrf_v1(double* A, int n, int lda, int64_t stride, int bat
         SF_HIP(hipEventRecord(e_gt, c));
         e_gt_prev = e_gt;
         // next diagonal block: apply this panel's columns and park it in the panel scratch
-        // (the diagonal blocks after the next one are brought up to date only every `rlazy` panels, with a
-        // correspondingly longer K: their read-modify-write traffic is what bounds those launches; the next
-        // block therefore may still miss the last few panels)
-        const int pend0 = (panel / rlazy) * rlazy * SF_NB;  // first panel column not yet applied to block k+1
-        SF_TRY(launch_r(k1, ntop, pend0, k1 - pend0, T, SF_LDT, sT, 0, c));
+        SF_TRY(launch_r(k1, ntop, k0, pw, T, SF_LDT, sT, 0, c));
         if (nbelow > ntop) {
             SF_HIP(hipStreamWaitEvent(s, e_f, 0));
             SF_TRY(launch_g(ntop, nbelow - ntop, s));
-            // the diagonal blocks after the next one are updated in place, every `rlazy` panels
+            // the diagonal blocks after the next one are updated in place
             const int j0 = k1 + ntop;
-            if ((panel + 1) % rlazy == 0 && j0 < n)
-                SF_TRY(launch_r(j0, n - j0, pend0, k1 - pend0, A + (int64_t)j0 * lda + j0, lda, stride,
-                                (int64_t)SF_NB * lda + SF_NB, s));
+            if (j0 < n)
+                SF_TRY(launch_r(j0, n - j0, k0, pw, A + (int64_t)j0 * lda + j0, lda, stride, (int64_t)SF_NB * lda + SF_NB, s));
         }
     }
     // join: the caller's stream continues only after the side chain is done
@@ -2778,6 +2498,97 @@ int sf_set_cholesky_sequence(int mode) {
     return SF_OK;
 }
 
+// The fields of sf_panel_args that stay the same over one factorisation of the fused or the wide sequence (A, rhs and the
+// generator in the shifted frame fp)
+static sf_panel_args sf_panel_base(double* A, int n, int lda, int64_t stride, double* rhs, int ldr, const sf_gen_args* gen,
+                                   int fp, int64_t sW) {
+    sf_panel_args g = {};
+    g.C = A;
+    g.sC = stride;
+    g.lda = lda;
+    g.n = n;
+    g.sW = sW;
+    g.rhs = rhs;
+    g.ldr = ldr;
+    g.fp = fp;
+    if (gen) {
+        g.genY = gen->Y - fp;
+        g.sY = (int64_t)gen->mpad * gen->ldy;
+        g.ldy = gen->ldy;
+        g.mpad = gen->mpad;
+        g.tilemap = gen->tilemap;
+        g.nt128 = gen->nt128;
+    }
+    return g;
+}
+// split-K factor of a narrow step of nblk workgroups (1: not split)
+static int sf_panel_split(int k0, int pw, int fp, long long nblk) {
+    return pw > 0 ? sf_split_policy(nblk, (k0 > fp ? k0 - fp : 0) / GK) : 1;
+}
+// One narrow step (k_chol_panel) of the fused and the wide sequence: panel [k0, k0 + pw) for nslab slabs of every matrix, the
+// first at row0, `step` slabs apart.  to_scratch: the chain's step -- the first slab's updated diagonal tile is parked in the
+// scratch T, the workgroups run at raised wave priority.  A split step parks its partial sums in region `region` of `part`;
+// phase 0 launches the whole step, 1 / 2 only the split-K partial sums / only what follows them.
+static int sf_panel_step(sf_panel_args g, int batch, double* T, int64_t sT, double* part, int k0, int pw, int row0, int nslab,
+                         int step, const double* Wt, bool to_scratch, hipStream_t st, int region, int phase) {
+    const int n = g.n, fp = g.fp;
+    g.k0 = k0;
+    g.pw = pw;
+    g.row0 = row0;
+    g.nslab = nslab;
+    g.slab_step = step;
+    g.Wt = Wt;
+    if (to_scratch) {
+        g.Sout = T;
+        g.sS = sT;
+        g.ldS = SF_LDT;
+        g.prio = 1;
+    }
+    const long long nblk = (long long)nslab * batch;
+    if (nblk > 0x7fffffffLL) {
+        sf_set_error("panel grid too large");
+        return SF_EINVAL;
+    }
+    // algorithmic flops: update 2 k0 rows pw, solve rows pw^2, symmetric rank-pw update of the lower tiles
+    double rows = 0.0;
+    for (int i = 0; i < nslab; ++i) {
+        const int r0 = row0 + i * step * GT;
+        rows += (n - r0 < GT) ? n - r0 : GT;
+    }
+    const double flops_main = 2.0 * (k0 > fp ? k0 - fp : 0) * rows * pw * batch;
+    const double flops_epi = (rows * pw * (double)pw + (double)GT * rows * pw) * batch;
+    const int nk = (k0 > fp ? k0 - fp : 0) / GK;
+    const int S = sf_panel_split(k0, pw, fp, nblk);
+    void* tok;  // (every kernel launch is one profiled launch: what rocprofv3 --stats counts)
+    if (S > 1) {
+        g.ksplit = S;
+        g.kchunk = (nk + S - 1) / S;
+        g.part = part + (size_t)region * sf_split_region_tiles() * (GT * GT);
+        if (phase != 2) {
+            sf_prof_gemm_begin(st, flops_main, &tok);
+            hipLaunchKernelGGL((k_chol_panel<false, 1>), dim3((unsigned)(nblk * S)), dim3(512), 0, st, g);
+            sf_prof_gemm_end(tok);
+        }
+        if (phase != 1) {
+            sf_prof_gemm_begin(st, flops_epi, &tok);
+            if (g.rhs)
+                hipLaunchKernelGGL((k_chol_panel<true, 2>), dim3((unsigned)nblk), dim3(512), 0, st, g);
+            else
+                hipLaunchKernelGGL((k_chol_panel<false, 2>), dim3((unsigned)nblk), dim3(512), 0, st, g);
+            sf_prof_gemm_end(tok);
+        }
+    } else {
+        sf_prof_gemm_begin(st, flops_main + flops_epi, &tok);
+        if (g.rhs)
+            hipLaunchKernelGGL((k_chol_panel<true, 0>), dim3((unsigned)nblk), dim3(512), 0, st, g);
+        else
+            hipLaunchKernelGGL((k_chol_panel<false, 0>), dim3((unsigned)nblk), dim3(512), 0, st, g);
+        sf_prof_gemm_end(tok);
+    }
+    SF_LAUNCH_CHECK();
+    return SF_OK;
+}
+
 // Factorisation with the fused panel kernel (default).  Panels of 128 columns; per panel k
 //   D(k)      k_diag_mfma on the updated diagonal tile (parked in the scratch T): L_kk, L_kk^-1, z_k
 //   top(k)    k_chol_panel for the slab of the NEXT diagonal tile (rows k1 .. k1+128): its updated tile goes to T
@@ -2800,118 +2611,30 @@ static int sf_launch_potrf_v2(double* A, int n, int lda, int64_t stride, int bat
     SF_SHIFT_FRAME();
     SF_HIP(hipMemsetAsync(info, 0, sizeof(int) * (size_t)batch, s));
     SF_TRY(sf_exec_prepare(ex));
-    static const bool no_lookahead = SF_TUNE_FLAG("SF_NO_LOOKAHEAD");
-    static const int ngroups_env = SF_TUNE_INT("SF_CHOL_GROUPS", 2);
-    const int G = no_lookahead ? 1 : (ngroups_env < 1 ? 1 : (ngroups_env > SF_EXEC_GROUPS ? SF_EXEC_GROUPS : ngroups_env));
-    hipStream_t c = no_lookahead ? s : ex->side;
-    hipStream_t gs[SF_EXEC_GROUPS];
-    for (int g = 0; g < G; ++g) gs[g] = g == 0 ? s : ex->grp[g - 1];
+    constexpr int G = 2;  // slab groups: group 0 on the caller's stream, group 1 on grp[0]
+    hipStream_t c = ex->side;
+    const hipStream_t gs[G] = {s, ex->grp[0]};
     hipEvent_t e_fork;
     SF_TRY(sf_exec_event(ex, &e_fork));
     SF_HIP(hipEventRecord(e_fork, s));
-    if (c != s) SF_HIP(hipStreamWaitEvent(c, e_fork, 0));
-    for (int g = 0; g < G; ++g)
-        if (gs[g] != s) SF_HIP(hipStreamWaitEvent(gs[g], e_fork, 0));
+    SF_HIP(hipStreamWaitEvent(c, e_fork, 0));
+    SF_HIP(hipStreamWaitEvent(gs[1], e_fork, 0));
 
+    const sf_panel_args base = sf_panel_base(A, n, lda, stride, rhs, ldr, gen, fp, sW);
     double* part = Wt2 + 2 * (size_t)batch * sW + 64;  // split-K partial sums: region 0 = chain, 1 + g = group g
     const int nt = (n + GT - 1) / GT;
-    // phase 0: the whole step; 1 / 2: only the split-K partial sums / only what follows them (the chain runs the partial
-    // sums of top(k), which do not need D(k), beside D(k) on another stream); split_of() tells whether the step is split
-    auto split_of = [&](int k0, int pw, long long nblk) { return pw > 0 ? sf_split_policy(nblk, (k0 > fp ? k0 - fp : 0) / GK) : 1; };
-    auto launch_panel = [&](int k0, int pw, int row0, int nslab, int step, const double* Wt, bool to_scratch,
-                            hipStream_t st, int region, int phase) -> int {
-        sf_panel_args g = {};
-        g.C = A;
-        g.sC = stride;
-        g.lda = lda;
-        g.n = n;
-        g.k0 = k0;
-        g.pw = pw;
-        g.row0 = row0;
-        g.nslab = nslab;
-        g.slab_step = step;
-#ifdef SF_TUNING
-        static const int skip = SF_TUNE_INT("SF_PANEL_SKIP", 0);
-        g.skip = skip;
-#endif
-        g.Wt = Wt;
-        g.sW = sW;
-        g.rhs = rhs;
-        g.ldr = ldr;
-        if (to_scratch) {
-            g.Sout = T;
-            g.sS = sT;
-            g.ldS = SF_LDT;
-            g.prio = chain_prio;
-        }
-        g.fp = fp;
-        if (gen) {
-            g.genY = gen->Y - fp;
-            g.sY = (int64_t)gen->mpad * gen->ldy;
-            g.ldy = gen->ldy;
-            g.mpad = gen->mpad;
-            g.tilemap = gen->tilemap;
-            g.nt128 = gen->nt128;
-        }
-        const long long nblk = (long long)nslab * batch;
-        if (nblk > 0x7fffffffLL) {
-            sf_set_error("panel grid too large");
-            return SF_EINVAL;
-        }
-        // algorithmic flops: update 2 k0 rows pw, solve rows pw^2, symmetric rank-pw update of the lower tiles
-        double rows = 0.0;
-        for (int i = 0; i < nslab; ++i) {
-            const int r0 = row0 + i * step * GT;
-            rows += (n - r0 < GT) ? n - r0 : GT;
-        }
-        const double flops_main = 2.0 * (k0 > fp ? k0 - fp : 0) * rows * pw * batch;
-        const double flops_epi = (rows * pw * (double)pw + (double)GT * rows * pw) * batch;
-        const int nk = (k0 > fp ? k0 - fp : 0) / GK;
-        const int S = split_of(k0, pw, nblk);
-        void* tok;  // (every kernel launch is one profiled launch: what rocprofv3 --stats counts)
-        if (S > 1) {
-            g.ksplit = S;
-            g.kchunk = (nk + S - 1) / S;
-            g.part = part + (size_t)region * sf_split_region_tiles() * (GT * GT);
-            if (phase != 2) {
-                sf_prof_gemm_begin(st, flops_main, &tok);
-                hipLaunchKernelGGL((k_chol_panel<false, 1>), dim3((unsigned)(nblk * S)), dim3(512), 0, st, g);
-                sf_prof_gemm_end(tok);
-            }
-            if (phase != 1) {
-                sf_prof_gemm_begin(st, flops_epi, &tok);
-                if (rhs)
-                    hipLaunchKernelGGL((k_chol_panel<true, 2>), dim3((unsigned)nblk), dim3(512), 0, st, g);
-                else
-                    hipLaunchKernelGGL((k_chol_panel<false, 2>), dim3((unsigned)nblk), dim3(512), 0, st, g);
-                sf_prof_gemm_end(tok);
-            }
-        } else {
-            sf_prof_gemm_begin(st, flops_main + flops_epi, &tok);
-            if (rhs)
-                hipLaunchKernelGGL((k_chol_panel<true, 0>), dim3((unsigned)nblk), dim3(512), 0, st, g);
-            else
-                hipLaunchKernelGGL((k_chol_panel<false, 0>), dim3((unsigned)nblk), dim3(512), 0, st, g);
-            sf_prof_gemm_end(tok);
-        }
-        SF_LAUNCH_CHECK();
-        return SF_OK;
-    };
-
     // diagonal tile 0 goes to the scratch unchanged
-    SF_TRY(launch_panel(0, 0, 0, 1, 1, nullptr, true, c, 0, 0));
-    static const bool part_on_chain = SF_TUNE_FLAG("SF_PART_ON_CHAIN");  // tuning aid: the partial sums of top(k) after D(k) on the chain
-    hipEvent_t e_epi = nullptr;                   // end of top(k-1) on the chain
-    hipEvent_t e_rest[SF_EXEC_GROUPS] = {};       // last launch of every group
-    hipEvent_t e_rest_prev[SF_EXEC_GROUPS] = {};  // ... one panel earlier (their readers of Wt[panel & 1])
+    SF_TRY(sf_panel_step(base, batch, T, sT, part, 0, 0, 0, 1, 1, nullptr, true, c, 0, 0));
+    hipEvent_t e_epi = nullptr;      // end of top(k-1) on the chain
+    hipEvent_t e_rest[G] = {};       // last launch of every group
+    hipEvent_t e_rest_prev[G] = {};  // ... one panel earlier (their readers of Wt[panel & 1])
     for (int k = 0; k < nt; ++k) {
         const int k0 = k * GT;
         const int pw = (n - k0 < GT) ? n - k0 : GT;
         double* Wt = Wt2 + (size_t)(k & 1) * batch * sW;
         // D(k) overwrites the W buffer of panel k-2: every group must be done reading it
-        if (c != s || G > 1)
-            for (int g = 0; g < G; ++g)
-                if (e_rest_prev[g] && (c != gs[g])) SF_HIP(hipStreamWaitEvent(c, e_rest_prev[g], 0));
+        for (int g = 0; g < G; ++g)
+            if (e_rest_prev[g]) SF_HIP(hipStreamWaitEvent(c, e_rest_prev[g], 0));
         SF_TRY(sf_launch_diag128(T, sT, pw, info, k0 - fp, rhs ? rhs + k0 : nullptr, ldr, A + (int64_t)k0 * lda + k0, lda, stride, Wt, sW,
                                  batch, c, k == 0 ? fp : 0));
         if (k + 1 >= nt) break;
@@ -2925,22 +2648,20 @@ static int sf_launch_potrf_v2(double* A, int n, int lda, int64_t stride, int bat
         {
             hipStream_t gk = gs[(k + 1) % G];
             hipEvent_t dep = e_rest[(k + 1) % G];
-            if (c != gk && !part_on_chain && split_of(k0, pw, batch) > 1) {
+            if (sf_panel_split(k0, pw, fp, batch) > 1) {
                 if (e_epi) SF_HIP(hipStreamWaitEvent(gk, e_epi, 0));  // row k's columns of panel k-1; the partial-sum region
-                SF_TRY(launch_panel(k0, pw, (k + 1) * GT, 1, 1, Wt, true, gk, 0, 1));
+                SF_TRY(sf_panel_step(base, batch, T, sT, part, k0, pw, (k + 1) * GT, 1, 1, Wt, true, gk, 0, 1));
                 hipEvent_t e_part;
                 SF_TRY(sf_exec_event(ex, &e_part));
                 SF_HIP(hipEventRecord(e_part, gk));
                 SF_HIP(hipStreamWaitEvent(c, e_part, 0));
-                SF_TRY(launch_panel(k0, pw, (k + 1) * GT, 1, 1, Wt, true, c, 0, 2));
+                SF_TRY(sf_panel_step(base, batch, T, sT, part, k0, pw, (k + 1) * GT, 1, 1, Wt, true, c, 0, 2));
             } else {
-                if (dep && c != gk) SF_HIP(hipStreamWaitEvent(c, dep, 0));
-                SF_TRY(launch_panel(k0, pw, (k + 1) * GT, 1, 1, Wt, true, c, 0, 0));
+                if (dep) SF_HIP(hipStreamWaitEvent(c, dep, 0));
+                SF_TRY(sf_panel_step(base, batch, T, sT, part, k0, pw, (k + 1) * GT, 1, 1, Wt, true, c, 0, 0));
             }
-            if (c != s) {
-                SF_TRY(sf_exec_event(ex, &e_epi));
-                SF_HIP(hipEventRecord(e_epi, c));
-            }
+            SF_TRY(sf_exec_event(ex, &e_epi));
+            SF_HIP(hipEventRecord(e_epi, c));
         }
         // rest(k): slabs k+2 .. nt-1, slab i on the stream of group i mod G
         for (int g = 0; g < G; ++g) e_rest_prev[g] = e_rest[g];
@@ -2949,21 +2670,18 @@ static int sf_launch_potrf_v2(double* A, int n, int lda, int64_t stride, int bat
             while (first % G != g) ++first;
             if (first >= nt) continue;
             const int cnt = (nt - 1 - first) / G + 1;
-            if (gs[g] != c) SF_HIP(hipStreamWaitEvent(gs[g], e_d, 0));
-            SF_TRY(launch_panel(k0, pw, first * GT, cnt, G, Wt, false, gs[g], 1 + g, 0));
+            SF_HIP(hipStreamWaitEvent(gs[g], e_d, 0));
+            SF_TRY(sf_panel_step(base, batch, T, sT, part, k0, pw, first * GT, cnt, G, Wt, false, gs[g], 1 + g, 0));
             SF_TRY(sf_exec_event(ex, &e_rest[g]));
             SF_HIP(hipEventRecord(e_rest[g], gs[g]));
         }
     }
     // join: the caller's stream continues only after the chain and every group are done
     hipEvent_t e_join;
-    if (c != s) {
-        SF_TRY(sf_exec_event(ex, &e_join));
-        SF_HIP(hipEventRecord(e_join, c));
-        SF_HIP(hipStreamWaitEvent(s, e_join, 0));
-    }
-    for (int g = 0; g < G; ++g)
-        if (e_rest[g] && gs[g] != s) SF_HIP(hipStreamWaitEvent(s, e_rest[g], 0));
+    SF_TRY(sf_exec_event(ex, &e_join));
+    SF_HIP(hipEventRecord(e_join, c));
+    SF_HIP(hipStreamWaitEvent(s, e_join, 0));
+    if (e_rest[1]) SF_HIP(hipStreamWaitEvent(s, e_rest[1], 0));
     return SF_OK;
 }
 
@@ -2975,10 +2693,9 @@ static int sf_launch_potrf_v2(double* A, int n, int lda, int64_t stride, int bat
 //   B(p)      k_chol_panel_w for the slabs k+4 .. on the caller's stream
 // A trailing single panel (odd number of panels) and pairs without rows below them are narrow steps of the chain.
 // The four most recent inverse tiles W(k) live in the two 256-row buffers of the narrow sequence (slot k & 3).
-// tail_rounds: the pairs whose wide launches have at most this many rounds of workgroups left (and everything after them)
-// are single narrow steps; -1 = wide to the end; -2 = switch half-way (test aid: exercises the hand-over on any size).
+// half (test aid, sequence 3): narrow steps from the middle on -- exercises the hand-over on any size.
 static int sf_launch_potrf_v3(double* A, int n, int lda, int64_t stride, int batch, int* info, double* work,
-                              double* rhs, int ldr, hipStream_t s, const sf_gen_args* gen, sf_exec* ex, int tail_rounds, int fp) {
+                              double* rhs, int ldr, hipStream_t s, const sf_gen_args* gen, sf_exec* ex, bool half, int fp) {
     if (n % SF_LEAF != 0 || lda < n || batch <= 0 || (lda & 1) || !work) {
         sf_set_error("potrf: n must be a positive multiple of %d, lda >= n and even, workspace required", SF_LEAF);
         return SF_EINVAL;
@@ -3011,69 +2728,7 @@ static int sf_launch_potrf_v3(double* A, int n, int lda, int64_t stride, int bat
     SF_HIP(hipStreamWaitEvent(ex->grp[0], e_fork, 0));
     const int nt = (n + GT - 1) / GT;
 
-    auto narrow = [&](int k0, int pw, int row0, int nslab, int step, const double* Wt, bool to_scratch, hipStream_t st,
-                      int region) -> int {
-        sf_panel_args g = {};
-        g.C = A;
-        g.sC = stride;
-        g.lda = lda;
-        g.n = n;
-        g.k0 = k0;
-        g.pw = pw;
-        g.row0 = row0;
-        g.nslab = nslab;
-        g.slab_step = step;
-        g.Wt = Wt;
-        g.sW = sW;
-        g.rhs = rhs;
-        g.ldr = ldr;
-        if (to_scratch) {
-            g.Sout = T;
-            g.sS = sT;
-            g.ldS = SF_LDT;
-            g.prio = chain_prio;
-        }
-        g.fp = fp;
-        if (gen) {
-            g.genY = gen->Y - fp;
-            g.sY = (int64_t)gen->mpad * gen->ldy;
-            g.ldy = gen->ldy;
-            g.mpad = gen->mpad;
-            g.tilemap = gen->tilemap;
-            g.nt128 = gen->nt128;
-        }
-        const long long nblk = (long long)nslab * batch;
-        double rows = 0.0;
-        for (int i = 0; i < nslab; ++i) rows += (n - (row0 + i * step * GT) < GT) ? n - (row0 + i * step * GT) : GT;
-        const double flops_main = 2.0 * (k0 > fp ? k0 - fp : 0) * rows * pw * batch;
-        const double flops_epi = (rows * pw * (double)pw + (double)GT * rows * pw) * batch;
-        const int nk = (k0 > fp ? k0 - fp : 0) / GK;
-        const int S = pw > 0 ? sf_split_policy(nblk, nk) : 1;
-        void* tok;
-        if (S > 1) {
-            g.ksplit = S;
-            g.kchunk = (nk + S - 1) / S;
-            g.part = part + (size_t)region * sf_split_region_tiles() * (GT * GT);
-            sf_prof_gemm_begin(st, flops_main, &tok);
-            hipLaunchKernelGGL((k_chol_panel<false, 1>), dim3((unsigned)(nblk * S)), dim3(512), 0, st, g);
-            sf_prof_gemm_end(tok);
-            sf_prof_gemm_begin(st, flops_epi, &tok);
-            if (rhs)
-                hipLaunchKernelGGL((k_chol_panel<true, 2>), dim3((unsigned)nblk), dim3(512), 0, st, g);
-            else
-                hipLaunchKernelGGL((k_chol_panel<false, 2>), dim3((unsigned)nblk), dim3(512), 0, st, g);
-            sf_prof_gemm_end(tok);
-        } else {
-            sf_prof_gemm_begin(st, flops_main + flops_epi, &tok);
-            if (rhs)
-                hipLaunchKernelGGL((k_chol_panel<true, 0>), dim3((unsigned)nblk), dim3(512), 0, st, g);
-            else
-                hipLaunchKernelGGL((k_chol_panel<false, 0>), dim3((unsigned)nblk), dim3(512), 0, st, g);
-            sf_prof_gemm_end(tok);
-        }
-        SF_LAUNCH_CHECK();
-        return SF_OK;
-    };
+    const sf_panel_args base = sf_panel_base(A, n, lda, stride, rhs, ldr, gen, fp, sW);
 #ifdef SF_TUNING
     long long* wstamps = nullptr;
     int wstamp_n = 0, wstamp_k[64];
@@ -3145,7 +2800,7 @@ static int sf_launch_potrf_v3(double* A, int n, int lda, int64_t stride, int bat
                                  batch, c, k == 0 ? fp : 0);
     };
 
-    SF_TRY(narrow(0, 0, 0, 1, 1, nullptr, true, c, 0));  // diagonal tile 0 goes to the scratch unchanged
+    SF_TRY(sf_panel_step(base, batch, T, sT, part, 0, 0, 0, 1, 1, nullptr, true, c, 0, 0));  // diagonal tile 0 goes to the scratch unchanged
     // B(p) runs as two interleaved slab groups on two streams (like the narrow sequence): a group's next launch only
     // needs its own previous one, so the last, partly filled round of one group overlaps the other group's work.
     // Group g = slabs of parity g (k even: k+4+g, k+6+g, ...), in the wide pairs and in the narrow tail alike.
@@ -3158,12 +2813,11 @@ static int sf_launch_potrf_v3(double* A, int n, int lda, int64_t stride, int bat
         readers[slot].clear();
         return SF_OK;
     };
-    // The narrow loop below finishes what the pairs leave (a trailing single panel, the last diagonal block) and can
-    // take over earlier (`tail_rounds`): the timeline suggested that the last pairs -- few rounds of ~1 ms workgroups,
-    // every dependency of the chain costs a round -- would be better off as narrow steps, the measurement says no
-    // (cfg 2: wide to the end 49.3 ms, hand-over with 2 / 5 / 8 / 12 rounds left 50.0 / 50.4 / 51.0 / 51.8, narrow 51.5).
-    // One narrow step of the chain + both slab groups: panel k as D(k), top(k), rest(k) -- the steps before the first pair
-    // (`head`) and after the last one.
+    // The narrow loop below finishes what the pairs leave (a trailing single panel, the last diagonal block).  (The
+    // timeline suggested that the last pairs -- few rounds of ~1 ms workgroups, every dependency of the chain costs a
+    // round -- would be better off as narrow steps, the measurement says no: cfg 2, wide to the end 49.3 ms, hand-over
+    // with 2 / 5 / 8 / 12 rounds left 50.0 / 50.4 / 51.0 / 51.8, narrow 51.5.)
+    // One narrow step of the chain + both slab groups: panel k as D(k), top(k), rest(k).
     auto narrow_step = [&](int k) -> int {
         const int k0 = k * GT;
         const int pw = (n - k0 < GT) ? n - k0 : GT;
@@ -3180,46 +2834,29 @@ static int sf_launch_potrf_v3(double* A, int n, int lda, int64_t stride, int bat
         SF_HIP(hipEventRecord(e_d, c));
         // top(k): the slab of the next diagonal tile, on the chain; its rows were finished by the group of its parity
         if (e_last[(k + 1) & 1]) SF_HIP(hipStreamWaitEvent(c, e_last[(k + 1) & 1], 0));
-        SF_TRY(narrow(k0, pw, (k + 1) * GT, 1, 1, Wslot(k), true, c, 0));
+        SF_TRY(sf_panel_step(base, batch, T, sT, part, k0, pw, (k + 1) * GT, 1, 1, Wslot(k), true, c, 0, 0));
         for (int g = 0; g < 2; ++g) {
             int first = k + 2;
             if ((first & 1) != g) ++first;
             if (first >= nt) continue;
             const int cnt = (nt - 1 - first) / 2 + 1;
             SF_HIP(hipStreamWaitEvent(bs[g], e_d, 0));
-            SF_TRY(narrow(k0, pw, first * GT, cnt, 2, Wslot(k), false, bs[g], 1 + g));
+            SF_TRY(sf_panel_step(base, batch, T, sT, part, k0, pw, first * GT, cnt, 2, Wslot(k), false, bs[g], 1 + g, 0));
             SF_TRY(sf_exec_event(ex, &e_last[g]));
             SF_HIP(hipEventRecord(e_last[g], bs[g]));
             readers[k & 3].push_back(e_last[g]);
         }
         return SF_OK;
     };
-    // The first pairs have short K loops: a wide workgroup (one per CU) is then mostly its epilogue -- tile in, two
-    // triangular solves, tile out, one after the other with nothing beside it on the CU (B = 128: pair 0 runs at 0.44 of
-    // the matrix peak, pair 1 at 0.65, pair 2 at 0.70; the pairs from K = 1024 on at 0.81-0.88,
-    // profiles/r05_d_wide_per_pair_b128.txt).  The panels left of `head` are narrow steps (two workgroups per CU overlap
-    // one's memory phases with the other's solves) -- in tuning builds only: measured without gain for head = 2 ... 12
-    // (profiles/r05_d_wide_narrow_head_sweep.txt), the release library always starts with pair 0.
-    static const int head_env = SF_TUNE_INT("SF_WIDE_HEAD", 0);
-    const int head = std::min(nt, std::max(head_env, 0) & ~1);
     int k = 0;
-    for (; k < head; ++k) SF_TRY(narrow_step(k));
-    bool handover = head > 0;
     for (; k < nt; k += 2) {
         if (k + 2 >= nt) break;  // no rows below the pair: the narrow loop finishes the diagonal block
-        const long long rounds_left = (long long)batch * (nt - (k + 4) > 0 ? nt - (k + 4) : 0) / 256;
-        if (tail_rounds >= 0 && rounds_left <= tail_rounds) break;  // -> narrow tail from panel k
-        if (tail_rounds == -2 && k >= (nt / 4) * 2 && k > 0) break;
+        if (half && k >= (nt / 4) * 2 && k > 0) break;  // -> narrow tail from panel k
         // chain(p): needs the tile parked by A(p-1) and the rows of slab k+1 (A(p-1))
         if (e_A) SF_HIP(hipStreamWaitEvent(c, e_A, 0));
-        if (handover) {  // (after narrow steps: the rows of slab k+1 come from the slab group of its parity)
-            for (int g = 0; g < 2; ++g)
-                if (e_last[g]) SF_HIP(hipStreamWaitEvent(c, e_last[g], 0));
-            handover = false;
-        }
         SF_TRY(wait_readers(k & 3));
         SF_TRY(diag(k));
-        SF_TRY(narrow(k * GT, GT, (k + 1) * GT, 1, 1, Wslot(k), true, c, 0));  // (rows below the pair exist: panel k is full)
+        SF_TRY(sf_panel_step(base, batch, T, sT, part, k * GT, GT, (k + 1) * GT, 1, 1, Wslot(k), true, c, 0, 0));  // (rows below the pair exist: panel k is full)
         SF_TRY(wait_readers((k + 1) & 3));
         SF_TRY(diag(k + 1));
         hipEvent_t e_chain;
@@ -3236,13 +2873,12 @@ static int sf_launch_potrf_v3(double* A, int n, int lda, int64_t stride, int bat
         readers[k & 3].push_back(e_A);
         readers[(k + 1) & 3].push_back(e_A);
         // B(p): slabs k+4 .., slab k+4+g, k+6+g, ... in group g
-        static const int ngrp = SF_TUNE_INT("SF_WIDE_GROUPS", 2);  // tuning aid: 1 = one launch per pair on the caller's stream
-        for (int g = 0; g < ngrp; ++g) {
+        for (int g = 0; g < 2; ++g) {
             const int first = k + 4 + g;
             if (first >= nt) continue;
-            const int cnt = (nt - 1 - first) / ngrp + 1;
+            const int cnt = (nt - 1 - first) / 2 + 1;
             SF_HIP(hipStreamWaitEvent(bs[g], e_chain, 0));
-            SF_TRY(wide(k, first, cnt, ngrp, false, bs[g]));
+            SF_TRY(wide(k, first, cnt, 2, false, bs[g]));
             SF_TRY(sf_exec_event(ex, &e_last[g]));
             SF_HIP(hipEventRecord(e_last[g], bs[g]));
             readers[k & 3].push_back(e_last[g]);
@@ -3476,8 +3112,8 @@ static inline sf_df_stage_packed sf_df_pack(const sf_df_stage& x) {
 // with the same number of matrices share a task table (at most two sizes).
 #define SF_DF_QUEUES 8
 #define SF_DF_MAX_STAGES 127  // (two tables of 12-byte entries in the kernel arguments: < 4 KB; N = 16384 = 128 panels)
-#define SF_DF_FRONT_MAX 6    // slabs k+1 .. k+front of panel k are front slabs (front <= 6, chosen by the batch size)
-#define SF_DF_FRONT_WIDEST 3 // ... and the widest front a release build chooses: the stride of the front's partial sums and counters
+#define SF_DF_FRONT_MAX 6    // slabs k+1 .. k+front of panel k are front slabs (the tables hold fronts up to 6 wide)
+#define SF_DF_FRONT_WIDEST 3 // ... and the widest front chosen (by batch size and panel): the stride of the front's partial sums and counters
 #define SF_DF_QTILES (2 * SF_CHIP_WGS / SF_DF_QUEUES)  // partial-sum tiles per queue and stage parity
 struct sf_df_args {
     sf_panel_args p;  // matrix, right-hand side, generator, frame: the per-task fields are filled in by the kernel
@@ -3508,16 +3144,8 @@ static_assert(sizeof(sf_df_args) <= 4096, "kernel arguments of k_potrf_dataflow"
 typedef const __attribute__((address_space(4))) sf_df_args sf_df_kargs;
 // The dispenser's scans are real function calls (one lane, once per task): inlined at their three sites they pushed the
 // register allocation of the whole task loop over the edge (a spill reload inside a K loop, tools/check_isa.py).
-#ifdef SF_EXP_HELPER_INLINE
-#define SF_DF_HELPER __forceinline__
-#else
 #define SF_DF_HELPER __attribute__((noinline))
-#endif
-#ifdef SF_EXP_NOPROGADD  // (timing experiment: what do the progress counter's adds cost?  The stall bound then fires on any long wait)
-#define SF_DF_PROGRESS()
-#else
 #define SF_DF_PROGRESS() sf_df_add(a.abort_flag + 5, 1)
-#endif
 #ifdef SF_TUNING
 #define SF_DF_MISS_CLAIMS(x) ((a.miss_claims & 1) && (x))
 #else
@@ -3905,9 +3533,6 @@ __global__ __launch_bounds__(512, 4) void k_potrf_dataflow(const sf_df_args a_in
             bool dready = false;
             const int wr = sf_df_wait_r(f1, t1, f2, t2, f3, t3, probe, k + 1, &dready, a.abort_flag, tid, s_ints + 1,
                                         [&]() {  // (one lane) a ready chain / front task that nobody has claimed, on any queue
-#ifdef SF_EXP_NORESCUE
-                                            return false;
-#endif
                                             int cb = 0, ck = 0, cd = 1;
                                             for (int x = 0; x < SF_DF_QUEUES; ++x) {
                                                 const int qx = (qcur + x) & (SF_DF_QUEUES - 1);
@@ -4151,10 +3776,6 @@ static int sf_launch_potrf_v4(double* A, int n, int lda, int64_t stride, int bat
     g.fp = fp;
     g.sS = sT;  // (the parked diagonal tile of matrix b: T + b sT, row stride SF_LDT)
     g.ldS = SF_LDT;
-#ifdef SF_TUNING
-    static const int skip = SF_TUNE_INT("SF_PANEL_SKIP", 0);
-    g.skip = skip;
-#endif
     if (gen) {
         g.genY = gen->Y - fp;
         g.sY = (int64_t)gen->mpad * gen->ldy;
@@ -4167,20 +3788,15 @@ static int sf_launch_potrf_v4(double* A, int n, int lda, int64_t stride, int bat
     // stage (a long-K task, or partial sums + reduce) gets `front` chain periods before the front needs its row.  Front tasks
     // cost more than ordinary ones (partial sums written and read back).  N = 4096, front 1 / 2 / 3 / 4 / 6: B = 16 8.1 / 8.0 /
     // 7.87 / 7.84 / 7.85 ms, B = 32 13.7 / 13.8 / 13.7 / 13.9 / 14.6, B = 64 25.45 / 25.7 / 26.3 / 26.85 / 28.0
-    static const int front_env = SF_TUNE_INT("SF_DF_FRONT", 0);
-    const int F0 = std::max(1, std::min(SF_DF_FRONT_MAX, front_env > 0 ? front_env : (batch <= 20 ? 3 : 1)));
+    const int F0 = batch <= 20 ? 3 : 1;
     // ... and for 21-48 matrices the front widens to three slabs for the last panels: where a stage has fewer tasks than the
     // chip has workgroup slots (batch x slabs left <= 400) AND its K loops are long (2048 columns or more: the front keeps
     // long-K tasks out of the chain's way, its partial sums cost a round trip through memory).  Same-box, wide front from
-    // that panel on / never (`tools/knobs_potrf.sh`): N = 4096: B = 24 10.55 / 11.2 ms, 32: 13.42 / 13.65, 40: 16.7 / 16.93,
-    // 48: 19.75 / 19.8, 64: 25.7 / 25.5 (not taken from 49 matrices on); N = 3008, B = 32: 6.2 / 6.25; a wide front over the
-    // short K loops of N = 2048 loses 3-5 %.
-    static const int tail_env = SF_TUNE_INT("SF_DF_TAIL", -1);  // (tuning aid: panels of wide front, 0 = none)
-    static const int tailw_env = SF_TUNE_INT("SF_DF_TAIL_FRONT", SF_DF_FRONT_WIDEST);
-    const int Ftail = std::max(F0, std::min(SF_DF_FRONT_MAX, tailw_env));
-    int kT = nt;  // first panel of the wide front (nt: none)
-    if (tail_env >= 0) kT = std::max(0, nt - 1 - tail_env);
-    else if (batch > 20 && batch <= 48) kT = std::max(2048 / GT, nt - 400 / batch);
+    // that panel on / never: N = 4096: B = 24 10.55 / 11.2 ms, 32: 13.42 / 13.65, 40: 16.7 / 16.93, 48: 19.75 / 19.8,
+    // 64: 25.7 / 25.5 (not taken from 49 matrices on); N = 3008, B = 32: 6.2 / 6.25; a wide front over the short K loops
+    // of N = 2048 loses 3-5 %.
+    const int Ftail = SF_DF_FRONT_WIDEST;
+    const int kT = batch > 20 && batch <= 48 ? std::max(2048 / GT, nt - 400 / batch) : nt;  // first panel of the wide front
     auto Fof = [&](int k) { return k >= kT ? Ftail : F0; };
     const int F = Ftail;  // (the largest width: strides of the front's partial sums and counters)
     if (2 * (size_t)F * batch > sf_split_region_tiles()) {
@@ -4189,8 +3805,7 @@ static int sf_launch_potrf_v4(double* A, int n, int lda, int64_t stride, int bat
     }
     a.front = F;
     for (int d = 1; d <= SF_DF_FRONT_MAX; ++d) a.fstart[d - 1] = d <= F0 ? 0 : kT;
-    static const int fp_pos_env = SF_TUNE_INT("SF_DF_FP_POS", -1);
-    a.fp_pos = fp_pos_env >= 0 ? fp_pos_env : 256;  // (0 / 64 / 128 / 192 / 256: B = 16 7.75 / 7.7 / 7.6 / 7.7 / 7.55 ms, B = 32 13.8 / 13.9 / 13.75 / 13.7 / 13.65)
+    a.fp_pos = 256;  // (0 / 64 / 128 / 192 / 256: B = 16 7.75 / 7.7 / 7.6 / 7.7 / 7.55 ms, B = 32 13.8 / 13.9 / 13.75 / 13.7 / 13.65)
     a.nt = nt;
     a.batch = batch;
     a.T = T;
@@ -4198,8 +3813,7 @@ static int sf_launch_potrf_v4(double* A, int n, int lda, int64_t stride, int bat
     a.part = part;
     a.info = info;
     a.diag = sf_df_diag();
-    static const int qbal_env = SF_TUNE_INT("SF_DF_QBAL", 1);
-    a.qbal = qbal_env;
+    a.qbal = 1;
 #ifdef SF_TUNING
     if (SF_TUNE_FLAG("SF_DF_VERBOSE")) a.dbg = (long long*)(flags + ((nflags - ndbg + 1) & ~(size_t)1));
     static const char* trace_file = SF_TUNE_STR("SF_DF_TRACE_FILE");  // every task's {what, claimed, body start, end} as text
@@ -4211,17 +3825,15 @@ static int sf_launch_potrf_v4(double* A, int n, int lda, int64_t stride, int bat
 #endif
 
     // ---- the task tables: one per queue size (ceil and floor of batch / 8)
-    static const int cap_env = SF_TUNE_INT("SF_DF_CAP", 0);
     // workgroup slots a queue can count on: those of one XCD -- of 8 / batch XCDs when there are fewer matrices than queues
     // (bounded by the partial-sum tiles a queue owns)
     auto cap_of = [&](int Bq) {
-        if (cap_env > 0) return cap_env;
-        if (!a.qbal || batch % SF_DF_QUEUES == 0) return SF_CHIP_WGS / SF_DF_QUEUES;
+        if (batch % SF_DF_QUEUES == 0) return SF_CHIP_WGS / SF_DF_QUEUES;
         return std::max(16, std::min<int>(SF_DF_QTILES, (int)((long long)Bq * SF_CHIP_WGS / batch)));
     };
     // front partial-sum tasks per queue, panel and front slab (64 / 32 / 16 / 8 with a one-slab front: B = 32 14.9 / 14.8 / 14.55 /
     // 14.45 ms, B = 48 20.8 / 20.2 / 20.2 / 20.6)
-    static const int pt_tasks = SF_TUNE_INT("SF_DF_PT_TASKS", 16);
+    const int pt_tasks = 16;
     const int kpb = GT / GK;
     const int st_cap = (int)std::min<size_t>(SF_SPLIT_MAX, std::max<size_t>(1, sf_split_region_tiles() / (2 * (size_t)F * (size_t)batch)));
     a.pt_cap = st_cap;
@@ -4286,8 +3898,7 @@ static int sf_launch_potrf_v4(double* A, int n, int lda, int64_t stride, int bat
         const int B = (batch - qx + SF_DF_QUEUES - 1) / SF_DF_QUEUES;
         if (B > 0) total += a.ntasks[B == a.bq[0] ? 0 : 1];
     }
-    static const int grid_env = SF_TUNE_INT("SF_DF_GRID", SF_CHIP_WGS);
-    const int grid = (int)std::min<long long>(total, grid_env);
+    const int grid = (int)std::min<long long>(total, SF_CHIP_WGS);
 #ifdef SF_TUNING
     if (SF_TUNE_FLAG("SF_DF_VERBOSE")) {
         fprintf(stderr, "dataflow: n=%d nt=%d batch=%d tasks=%lld grid=%d lds=%zu bq=%d/%d St/Sr:", n, nt, batch, total, grid,
@@ -4414,52 +4025,46 @@ static bool sf_potrf_dataflow_fits(int n, int batch) {
     return g_df_enabled.load() && nt - 1 <= SF_DF_MAX_STAGES && 2 * (size_t)SF_DF_FRONT_WIDEST * batch <= sf_split_region_tiles();
 }
 static bool sf_potrf_dataflow_auto(int n, int batch) {
-    static const int lim = SF_TUNE_INT("SF_DF_BELOW", 2048);
     // (round 6: the panel count is the true one -- N = 4096: up to 64 matrices, the half-ensemble of a 128-walker sampler; same
     // box, persistent kernel / fused sequence there: 25.5 / 26.0 ms.  Rounds 4-5 counted 64 virtual rows more: 62 matrices.)
     const int nt = (n + GT - 1) / GT;
     // (... and stops at N = 8192: the kernel FITS up to N = 16384 -- forced sequence 4, tests -- but was only ever measured to
     // win up to 65 panels; at N = 16384 the tasks are milliseconds long and the launch sequences keep the chip as full:
     // profiles/r06_a_dataflow_n16384.txt)
-    static const int nt_max = SF_TUNE_INT("SF_DF_NT_MAX", 65);
-    return sf_potrf_dataflow_fits(n, batch) && (long long)batch * nt <= lim && batch <= 128 && nt <= nt_max;
+    return sf_potrf_dataflow_fits(n, batch) && (long long)batch * nt <= 2048 && batch <= 128 && nt <= 65;
 }
-int sf_potrf_front_pad(int n, int batch) {
-    static const bool off = SF_TUNE_FLAG("SF_NO_FRONT_PAD");  // tuning aid: A/B of the shifted frame
-    static const char* force = SF_TUNE_STR("SF_CHOL_UNFUSED");
-    const int sel = g_chol_sequence.load();
-    // (a matrix with more panels than the dataflow tables hold takes the fused sequence when the dataflow one is forced)
-    const bool df_fits = sf_potrf_dataflow_fits(n, batch);
-    const bool df = sel >= 0 ? (sel == 4 && df_fits) : (!force && sf_potrf_dataflow_auto(n, batch));
-    const bool v1 = !df && (sel >= 0 ? sel == 1 : (force ? force[0] == '1' : batch < SF_UNFUSED_BELOW));  // (as in sf_launch_potrf)
-    if (off || v1 || n % GT != 64 || n < 2 * GT) return 0;
-    return 64;
-}
-
-int sf_launch_potrf(double* A, int n, int lda, int64_t stride, int batch, int* info, double* work,
-                    double* rhs, int ldr, hipStream_t s, const sf_gen_args* gen, sf_exec* ex) {
-    // The fused panel kernel (128-column panels) is the faster sequence once the batch fills the chip (SF_UNFUSED_BELOW).
-    static const char* force = SF_TUNE_STR("SF_CHOL_UNFUSED");  // tuning aid: "1" always unfused, "0" always fused
-    const int sel = g_chol_sequence.load();                 // sf_debug_cholesky_sequence(): tests drive both
-    const bool df_fits = sf_potrf_dataflow_fits(n, batch);
-    const bool df = sel >= 0 ? (sel == 4 && df_fits) : (!force && sf_potrf_dataflow_auto(n, batch));
-    const bool v1 = !df && (sel >= 0 ? sel == 1 : (force ? force[0] == '1' : batch < SF_UNFUSED_BELOW));
+// The sequence that factorises `batch` matrices of order n (the numbering of sf_set_cholesky_sequence): the forced one, or
+// the automatic choice.  (A matrix with more panels than the dataflow tables hold takes the fused sequence when the dataflow
+// one is forced.)
+static int sf_potrf_pick(int n, int batch) {
+    const int sel = g_chol_sequence.load();  // sf_debug_cholesky_sequence(): tests drive all five
+    if (sel == 4 && !sf_potrf_dataflow_fits(n, batch)) return 0;
+    if (sel >= 0) return sel;
+    if (sf_potrf_dataflow_auto(n, batch)) return 4;
     // The wide sequence (panel pairs, one 16-wave workgroup per CU) halves the A-operand stream and a third of all HBM
     // traffic of the factorisation, but one workgroup per CU has nothing to overlap its epilogue and barriers with: it pays
     // once its launches are many rounds of workgroups.  Measured (bench.py, same box, fused / wide): N = 4096: B = 48
     // 21.45 / 23.1 ms, 64: 27.34 / 27.4, 80: 33.0 / 33.4, 96: 38.2 / 38.6, 112: 44.6 / 43.9, 128: 49.7 / 48.4; N = 16384,
     // B = 32 (cfg 5): 707.7 / 696.6; 1600 units of N = 3008 (cfg 3): 277.3 / 273.2 -> taken from batch x slabs >= 3400.
-    const bool wide_auto = n >= 2048 && (long long)batch * ((n + GT - 1) / GT) >= 3400;
-    const bool v3 = !df && (sel >= 0 ? sel == 2 : (force ? force[0] == '2' : wide_auto));
+    if (n >= 2048 && (long long)batch * ((n + GT - 1) / GT) >= 3400) return 2;
+    // The fused panel kernel (128-column panels) is the faster sequence once the batch fills the chip (SF_UNFUSED_BELOW).
+    return batch < SF_UNFUSED_BELOW ? 1 : 0;
+}
+// Every sequence but the unfused one works in a frame shifted by 64 virtual leading rows when n is 64 mod 128
+int sf_potrf_front_pad(int n, int batch) {
+    if (sf_potrf_pick(n, batch) == 1 || n % GT != 64 || n < 2 * GT) return 0;
+    return 64;
+}
+
+int sf_launch_potrf(double* A, int n, int lda, int64_t stride, int batch, int* info, double* work,
+                    double* rhs, int ldr, hipStream_t s, const sf_gen_args* gen, sf_exec* ex) {
+    const int seq = sf_potrf_pick(n, batch);
     if (!ex) ex = sf_exec_thread_local();
-    static const int tail_env = SF_TUNE_INT("SF_WIDE_TAIL_ROUNDS", -1);  // measured at cfg 2: -1 (wide to the end) 49.3 ms, 2: 50.0, 5: 50.4, 8: 51.0, 12: 51.8 (narrow: 51.5)
-    const bool v3h = sel == 3;  // (test aid) wide pairs for the first half of the panels, narrow steps after
     // frame of the fused sequences: the caller's (whose tile map was built in it) or this call's own
     const int fp = gen ? gen->fp : sf_potrf_front_pad(n, batch);
-    if (df) return sf_launch_potrf_v4(A, n, lda, stride, batch, info, work, rhs, ldr, s, gen, fp);
-    if (v3 || v3h)
-        return sf_launch_potrf_v3(A, n, lda, stride, batch, info, work, rhs, ldr, s, gen, ex, v3h ? -2 : (sel == 2 ? -1 : tail_env), fp);
-    if (v1 && fp == 0) return sf_launch_potrf_v1(A, n, lda, stride, batch, info, work, rhs, ldr, s, gen, ex);
+    if (seq == 4) return sf_launch_potrf_v4(A, n, lda, stride, batch, info, work, rhs, ldr, s, gen, fp);
+    if (seq == 2 || seq == 3) return sf_launch_potrf_v3(A, n, lda, stride, batch, info, work, rhs, ldr, s, gen, ex, seq == 3, fp);
+    if (seq == 1 && fp == 0) return sf_launch_potrf_v1(A, n, lda, stride, batch, info, work, rhs, ldr, s, gen, ex);
     return sf_launch_potrf_v2(A, n, lda, stride, batch, info, work, rhs, ldr, s, gen, ex, fp);
 }
 

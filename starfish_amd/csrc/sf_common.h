@@ -105,7 +105,7 @@ void sf_prof_gemm_end(void* tok);
 
 // ---- launchers implemented in the .hip files (all enqueue on `s`, never synchronise) ----------
 // sf_chol.hip
-#define SF_LTB_DOUBLES (SF_LEAF * SF_LEAF + SF_LEAF)  // side buffer per matrix: L^T of the leaf + its z
+#define SF_LTB_DOUBLES (SF_LEAF * SF_LEAF + SF_LEAF)  // reserved per matrix at the start of the workspace (unused)
 #define SF_LDT (SF_NB + 16)                            // row stride of the panel scratch
 size_t sf_potrf_work_doubles(int n, int batch);        // doubles of scratch sf_launch_potrf needs
 // Optional "matrix-free" start of the factorisation: 128x128 tiles whose tilemap byte is 0 were never

@@ -591,8 +591,9 @@ __global__ __launch_bounds__(256) void k_dense_map(sf_fill_args a, int nt, unsig
 // (tools/probes/write_pattern.hip); a rolling prefetch inside the loop does not help either, hipcc's wait counts then
 // include the previous tile's stores (loads and stores share vmcnt).  Same MFMA sequence per accumulator as
 // sf_fill_tile: same bits.
-template <int KK, int SPAN>
+template <int KK>
 __global__ __launch_bounds__(256, 4) void k_fill_dense_plain(sf_fill_args a, int nt, const unsigned char* __restrict__ smap) {
+    constexpr int SPAN = 4;
     const int nch = (nt + SPAN - 1) / SPAN;
     const int id = sf_xcd_remap_f(blockIdx.x, gridDim.x);
     const int b = id / (nt * nch);
@@ -666,8 +667,7 @@ __global__ __launch_bounds__(256, 4) void k_fill_dense_plain(sf_fill_args a, int
     }
 }
 
-template <int OCC>
-__global__ __launch_bounds__(256, OCC) void k_fill_dense_band(sf_fill_args a, int nt, int G,
+__global__ __launch_bounds__(256, 2) void k_fill_dense_band(sf_fill_args a, int nt, int G,
                                                               const unsigned short* __restrict__ list,
                                                               const int* __restrict__ count) {
     const int b = blockIdx.x / G, g = blockIdx.x - b * G;
@@ -715,9 +715,8 @@ int sf_launch_fill_dense(const sf_fill_args& a, int B, unsigned char* smap, unsi
                          sf_exec* ex) {
     const int nout = sf_fill_extent(a);
     const int nt = (nout + FT - 1) / FT;
-    static const int old_env = SF_TUNE_INT("SF_FILL_OLD", 0);
     const bool all_structured = (a.has_global || a.n_local > 0) && !a.monotonic;  // (unsorted wavelengths: no culling)
-    if (a.lower_only || a.tilemap || nt > 256 || !smap || !list || !count || old_env || all_structured || a.mpad > 16 || (a.mpad & 3))
+    if (a.lower_only || a.tilemap || nt > 256 || !smap || !list || !count || all_structured || a.mpad > 16 || (a.mpad & 3))
         return sf_launch_fill(a, B, s);
     if (a.n_local > SF_MAX_LOCAL) {
         sf_set_error("at most %d local kernels are supported", SF_MAX_LOCAL);
@@ -733,8 +732,8 @@ int sf_launch_fill_dense(const sf_fill_args& a, int B, unsigned char* smap, unsi
     }
     // The structured tiles are bound by fp64 VALU work (exp / cos per entry: 0.85 ms at cfg 2), the plain ones by the HBM
     // write rate: with a context's auxiliary stream the two kernels run side by side (disjoint tiles, both write-only).
-    static const int two_streams = SF_TUNE_INT("SF_FILL_TWO_STREAMS", 1);
-    const bool fork = structured && ex && two_streams;
+    const bool fork = structured && ex;
+    const int G = 32;  // workgroups per matrix of k_fill_dense_band
     hipStream_t sb = s;
     hipEvent_t e_map = nullptr, e_band = nullptr;
     if (fork) {
@@ -743,42 +742,30 @@ int sf_launch_fill_dense(const sf_fill_args& a, int B, unsigned char* smap, unsi
         sb = ex->aux;
         SF_HIP(hipEventRecord(e_map, s));
         SF_HIP(hipStreamWaitEvent(sb, e_map, 0));
-        static const int G = SF_TUNE_INT("SF_FILL_BAND_G", 32);
-        static const int occ = SF_TUNE_INT("SF_FILL_BAND_OCC", 2);
-        if (occ == 4) hipLaunchKernelGGL(k_fill_dense_band<4>, dim3((unsigned)B * G), dim3(256), 0, sb, a2, nt, G, list, count);
-        else if (occ == 3) hipLaunchKernelGGL(k_fill_dense_band<3>, dim3((unsigned)B * G), dim3(256), 0, sb, a2, nt, G, list, count);
-        else hipLaunchKernelGGL(k_fill_dense_band<2>, dim3((unsigned)B * G), dim3(256), 0, sb, a2, nt, G, list, count);
+        hipLaunchKernelGGL(k_fill_dense_band, dim3((unsigned)B * G), dim3(256), 0, sb, a2, nt, G, list, count);
         SF_LAUNCH_CHECK();
         SF_HIP(hipEventRecord(e_band, sb));
     }
     const unsigned char* pm = structured ? smap : nullptr;
     const int KK = a.mpad / 4;
     // (Y fragments of a whole segment live in registers; cfg 2, rank-m part alone: 4 tiles 2.97 ms, 8 tiles 3.12 ms)
-    static const int span8 = SF_TUNE_INT("SF_FILL_SPAN8", 0);
-    const int span = (KK <= 2 && span8) ? 8 : 4;
+    const int span = 4;
     const long long nblk = (long long)nt * ((nt + span - 1) / span) * B;
     if (nblk > 0x7fffffffLL) {
         sf_set_error("fill grid too large");
         return SF_EINVAL;
     }
     switch (KK) {
-        case 1:
-            if (span == 8) hipLaunchKernelGGL((k_fill_dense_plain<1, 8>), dim3((unsigned)nblk), dim3(256), 0, s, a2, nt, pm);
-            else hipLaunchKernelGGL((k_fill_dense_plain<1, 4>), dim3((unsigned)nblk), dim3(256), 0, s, a2, nt, pm);
-            break;
-        case 2:
-            if (span == 8) hipLaunchKernelGGL((k_fill_dense_plain<2, 8>), dim3((unsigned)nblk), dim3(256), 0, s, a2, nt, pm);
-            else hipLaunchKernelGGL((k_fill_dense_plain<2, 4>), dim3((unsigned)nblk), dim3(256), 0, s, a2, nt, pm);
-            break;
-        case 3: hipLaunchKernelGGL((k_fill_dense_plain<3, 4>), dim3((unsigned)nblk), dim3(256), 0, s, a2, nt, pm); break;
-        default: hipLaunchKernelGGL((k_fill_dense_plain<4, 4>), dim3((unsigned)nblk), dim3(256), 0, s, a2, nt, pm); break;
+        case 1: hipLaunchKernelGGL(k_fill_dense_plain<1>, dim3((unsigned)nblk), dim3(256), 0, s, a2, nt, pm); break;
+        case 2: hipLaunchKernelGGL(k_fill_dense_plain<2>, dim3((unsigned)nblk), dim3(256), 0, s, a2, nt, pm); break;
+        case 3: hipLaunchKernelGGL(k_fill_dense_plain<3>, dim3((unsigned)nblk), dim3(256), 0, s, a2, nt, pm); break;
+        default: hipLaunchKernelGGL(k_fill_dense_plain<4>, dim3((unsigned)nblk), dim3(256), 0, s, a2, nt, pm); break;
     }
     SF_LAUNCH_CHECK();
     if (fork) {
         SF_HIP(hipStreamWaitEvent(s, e_band, 0));
     } else if (structured) {
-        const int G = 32;
-        hipLaunchKernelGGL(k_fill_dense_band<2>, dim3((unsigned)B * G), dim3(256), 0, s, a2, nt, G, list, count);
+        hipLaunchKernelGGL(k_fill_dense_band, dim3((unsigned)B * G), dim3(256), 0, s, a2, nt, G, list, count);
         SF_LAUNCH_CHECK();
     }
     return SF_OK;

@@ -1,6 +1,5 @@
 """Timing of the dense covariance fill alone (sf_cov_fill_batch, both triangles):  python tools/bench_fill.py [N] [B] [ld]
-Prints ms per launch and GB/s for the model with / without structured kernels, next to the streaming-write probe.
-Tuning switches (SF_FILL_SPAN, SF_FILL_OLD) need the tuning build: SF_LIB_PATH=starfish_amd/libstarfish_amd_tuning.so."""
+Prints ms per launch and GB/s for the model with / without structured kernels, next to the streaming-write probe."""
 import ctypes as C
 import json
 import os
@@ -17,7 +16,7 @@ N = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 128
 ld = int(sys.argv[3]) if len(sys.argv) > 3 else N
 o = synth.make_order(N=N)
-out = {"N": N, "B": B, "ld": ld, "env": {k: v for k, v in os.environ.items() if k.startswith("SF_FILL")}}
+out = {"N": N, "B": B, "ld": ld}
 for name, params in (("structured", None), ("rank_m_only", {k: v for k, v in synth.centre_params(o).items() if k not in ("global_cov", "local_cov")})):
     model = synth.build_model(o, params=params)
     P = synth.walker_ball(o, B=B, seed=1)
