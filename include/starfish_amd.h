@@ -269,7 +269,8 @@ int sf_loglike_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const doubl
  * sum(B_i) matrices share one batched Cholesky.  Outputs are concatenated in segment order
  * (unit = sum_{j<i} B_j + b); the caller sums over orders.  All contexts must live on the same
  * device and agree in the number of eigenspectra and grid dimensions; one model descriptor describes
- * the parameter rows of every segment.  Same values as nseg calls of sf_loglike_batch. */
+ * the parameter rows of every segment (sf_loglike_multi_batch_md below: one per segment).  Same values
+ * as nseg calls of sf_loglike_batch. */
 typedef struct sf_segment {
     sf_ctx* ctx;
     const double* d_params; /* DEVICE: B x sf_param_stride() rows of this order */
@@ -280,6 +281,16 @@ size_t sf_multi_workspace_bytes(const sf_segment* segs, int nseg, const sf_model
 int sf_loglike_multi_batch(const sf_segment* segs, int nseg, const sf_model_desc* model,
                            double* d_lnl, double* d_logdet, double* d_sqmah, double* d_log_scale,
                            int* d_info, void* d_work, size_t work_bytes, void* stream);
+/* The same with one model descriptor PER SEGMENT: models[i] describes the parameter rows of segs[i]
+ * (row stride sf_param_stride(segs[i].ctx, models[i])), so orders with their own nuisance parameters
+ * -- another number of local kernels or Chebyshev terms, with or without a global kernel -- still
+ * share one batched Cholesky.  Every segment is checked before anything is enqueued (the error names
+ * the segment); the transient buffers are sized for the union of the descriptors.  With every
+ * models[i] equal to one descriptor the result is bit-identical to sf_loglike_multi_batch. */
+size_t sf_multi_workspace_bytes_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models);
+int sf_loglike_multi_batch_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                              double* d_lnl, double* d_logdet, double* d_sqmah, double* d_log_scale,
+                              int* d_info, void* d_work, size_t work_bytes, void* stream);
 
 /* ---- structure-exploiting solver -----------------------------------
  * Same value as sf_loglike_batch, computed without ever forming the N x N matrix: the covariance of

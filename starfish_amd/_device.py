@@ -147,38 +147,57 @@ class MultiPlan:
     """Device-resident state of a repeated multi-order evaluation (sf_loglike_multi_batch): parameter rows,
     outputs and workspace are allocated once; :meth:`enqueue` only launches.  ``orders`` are
     :class:`DeviceOrder` objects of ONE device, ``rows_list[i]`` the (B_i, stride) C-ABI rows of order i.
+    ``md`` is one ModelDesc for every order (all rows of one layout), or a list with one ModelDesc per order
+    (sf_loglike_multi_batch_md: orders with their own row layouts still share one batched Cholesky).
     Unit lists that do not fit the free HBM (or ``max_units``) are cut into several calls."""
 
     def __init__(self, orders, md, rows_list, max_units=None):
         torch = _torch()
         self.orders = list(orders)
-        self.md = md
+        self.per_order = isinstance(md, (list, tuple))
+        self.md = list(md) if self.per_order else md
         self.lib = orders[0].lib
         self.dev = orders[0].dev
         if any(o.dev != self.dev for o in orders):
             raise ValueError("multi-order call: all orders must live on the same device")
-        stride = orders[0].param_stride(md)
-        for o, r in zip(orders, rows_list):
-            if o.param_stride(md) != stride or int(r.shape[-1]) != stride:
+        if self.per_order:
+            if len(self.md) != len(self.orders) or len(rows_list) != len(self.orders):
+                raise ValueError(f"multi-order call: {len(self.md)} descriptors and {len(rows_list)} row blocks for "
+                                 f"{len(self.orders)} orders")
+            mds = self.md
+        else:
+            mds = [md] * len(self.orders)
+        strides = [o.param_stride(m) for o, m in zip(orders, mds)]
+        if not self.per_order and len(set(strides)) > 1:
+            raise ValueError(f"multi-order call: one descriptor gives the orders row strides {sorted(set(strides))}")
+        for want, r in zip(strides, rows_list):
+            if int(r.shape[-1]) != want:
                 raise ValueError(f"multi-order call: parameter rows of {int(r.shape[-1])} doubles do not match the "
-                                 f"descriptor's stride {stride} (orders with different descriptors need separate calls)")
+                                 f"descriptor's stride {want} (orders with different descriptors need one descriptor "
+                                 f"per order)")
         self.sizes = [int(np.atleast_2d(r).shape[0]) if not torch.is_tensor(r) else int(r.shape[0]) for r in rows_list]
         U = sum(self.sizes)
         with torch.cuda.device(self.dev):
             self.P = [r if torch.is_tensor(r) else to_dev(np.atleast_2d(r), self.dev) for r in rows_list]
             self.quad = empty((4, U), self.dev)  # lnl, logdet, sqmah, log_scale: one device->host copy
             self.info = empty((U,), self.dev, torch.int32)
-            one = _lib.Segment(orders[0].ctx, ptr(self.P[0]).value, 1, 0)
-            # units that fit: the workspace is linear in the unit count up to the fixed Cholesky scratch
-            w1 = self.lib.sf_multi_workspace_bytes(C.byref(one), 1, C.byref(md))
-            one.B = 2
-            w2 = self.lib.sf_multi_workspace_bytes(C.byref(one), 1, C.byref(md))
-            per_unit = max(w2 - w1, 1)
+            # units that fit: the workspace is linear in the unit count up to the fixed Cholesky scratch.  With one
+            # descriptor per order the largest estimate of any order counts (e.g. the only order whose descriptor
+            # needs the broadening buffers: the call allocates them for all)
+            fixed, per_unit = 0, 1
+            for i in range(len(orders)) if self.per_order else (0,):
+                one = _lib.Segment(orders[i].ctx, ptr(self.P[i]).value, 1, 0)
+                desc = self._desc_array(mds[i:i + 1]) if self.per_order else C.byref(md)
+                w1 = self._workspace_bytes(C.byref(one), 1, desc)
+                one.B = 2
+                w2 = self._workspace_bytes(C.byref(one), 1, desc)
+                pu = max(w2 - w1, 1)
+                per_unit, fixed = max(per_unit, pu), max(fixed, w1 - pu)
             free, _total = torch.cuda.mem_get_info(self.dev)
             lead = orders[0]
             if lead._ws_multi is not None:
                 free += lead._ws_multi.numel()
-            cap = max(1, (int(free * 0.85) - (w1 - per_unit)) // per_unit)
+            cap = max(1, (int(free * 0.85) - fixed) // per_unit)
             if max_units:
                 cap = min(cap, int(max_units))
             self.pieces, cur, cur_n = [], [], 0
@@ -200,16 +219,28 @@ class MultiPlan:
                 segs = (_lib.Segment * len(piece))()
                 for k, (i, lo, hi) in enumerate(piece):
                     segs[k] = _lib.Segment(orders[i].ctx, ptr(self.P[i][lo:hi]).value, hi - lo, 0)
-                nb = self.lib.sf_multi_workspace_bytes(segs, len(piece), C.byref(md))
+                models = self._desc_array([mds[i] for i, _, _ in piece]) if self.per_order else C.byref(md)
+                nb = self._workspace_bytes(segs, len(piece), models)
                 if nb == 0:
                     _lib.check(-1, "sf_multi_workspace_bytes")
                 need = max(need, nb)
                 u0 = int(offs[piece[0][0]] + piece[0][1])  # the pieces of one call are contiguous in unit order
-                self.calls.append((segs, len(piece), u0, sum(hi - lo for _, lo, hi in piece)))
+                self.calls.append((segs, len(piece), u0, sum(hi - lo for _, lo, hi in piece), models))
             if lead._ws_multi is None or lead._ws_multi.numel() < need:
                 lead._ws_multi = None
                 lead._ws_multi = workspace(need, self.dev)
             self.ws = lead._ws_multi
+
+    @staticmethod
+    def _desc_array(mds):
+        """``const sf_model_desc* const*`` of the given descriptors (the array keeps them alive)."""
+        arr = (C.POINTER(_lib.ModelDesc) * len(mds))(*[C.pointer(m) for m in mds])
+        arr._keep = mds
+        return arr
+
+    def _workspace_bytes(self, segs, nseg, models):
+        fn = self.lib.sf_multi_workspace_bytes_md if self.per_order else self.lib.sf_multi_workspace_bytes
+        return fn(segs, nseg, models)
 
     @property
     def units(self):
@@ -218,15 +249,17 @@ class MultiPlan:
     def enqueue(self):
         """Launch only: results land in ``self.quad`` / ``self.info`` once the device's current stream is done."""
         torch = _torch()
+        fn, name = ((self.lib.sf_loglike_multi_batch_md, "sf_loglike_multi_batch_md") if self.per_order
+                    else (self.lib.sf_loglike_multi_batch, "sf_loglike_multi_batch"))
         with torch.cuda.device(self.dev):
             s = stream_ptr(self.dev)
             q = self.quad
-            for segs, nseg, u0, n in self.calls:
-                rc = self.lib.sf_loglike_multi_batch(
-                    segs, nseg, C.byref(self.md), ptr(q[0][u0:u0 + n]), ptr(q[1][u0:u0 + n]), ptr(q[2][u0:u0 + n]),
+            for segs, nseg, u0, n, models in self.calls:
+                rc = fn(
+                    segs, nseg, models, ptr(q[0][u0:u0 + n]), ptr(q[1][u0:u0 + n]), ptr(q[2][u0:u0 + n]),
                     ptr(q[3][u0:u0 + n]), ptr(self.info[u0:u0 + n]), ptr(self.ws), self.ws.numel(), s,
                 )
-                _lib.check(rc, "sf_loglike_multi_batch")
+                _lib.check(rc, name)
 
     def collect(self):
         out = collect_multi(self.quad, self.info, self.sizes)
@@ -242,6 +275,7 @@ class MultiPlan:
 
 def loglike_multi(orders, md, rows_list, max_units=None, sync=True):
     """(order x walker) units of several orders of ONE device in one enqueue and one host synchronisation.
+    ``md``: one ModelDesc shared by every order, or a list with one per order (see :class:`MultiPlan`).
     Returns a list of dicts (lnl, logdet, sqmah, log_scale, info) per order; with ``sync=False`` the
     un-synchronised :class:`MultiPlan` (callers overlapping several devices call ``plan.collect()`` later)."""
     plan = MultiPlan(orders, md, rows_list, max_units=max_units)

@@ -1143,14 +1143,22 @@ extern "C" int sf_loglike_batch(sf_ctx* c, const sf_model_desc* mdl, int B, cons
 // and covariance fill into its slice of a common [units][npad][lda] array, padded (identity block) to the largest
 // order of the group; the Cholesky, which is where the time goes, then sees sum(B_i) matrices in one launch
 // sequence instead of nseg half-filled ones, and the host synchronises once.
-static int multi_layout(const sf_segment* segs, int nseg, const sf_model_desc* mdl, Layout* L, int* units, int* bmax) {
-    if (!segs || nseg <= 0 || !mdl) {
+// models[i] describes the rows of segment i; *uni receives what the shared buffers are sized for (segment 0's
+// descriptor with has_vsini set if ANY segment broadens: the transient buffers of the transform chains are shared)
+static int multi_layout(const sf_segment* segs, int nseg, const sf_model_desc* const* models, Layout* L, int* units,
+                        int* bmax, sf_model_desc* uni) {
+    if (!segs || nseg <= 0 || !models) {
         sf_set_error("multi-order call: bad segment list / model descriptor");
         return SF_EINVAL;
     }
+    for (int i = 0; i < nseg; ++i) {
+        if (!models[i]) {
+            sf_set_error("multi-order call: segment %d has no model descriptor", i);
+            return SF_EINVAL;
+        }
+    }
     const sf_ctx* c0 = segs[0].ctx;
-    if (model_ok(c0, mdl)) return SF_EINVAL;
-    *L = layout_of(c0);
+    *uni = *models[0];
     long long U = 0;
     int bm = 0;
     for (int i = 0; i < nseg; ++i) {
@@ -1159,11 +1167,18 @@ static int multi_layout(const sf_segment* segs, int nseg, const sf_model_desc* m
             sf_set_error("multi-order call: segment %d has no order context / batch / parameters", i);
             return SF_EINVAL;
         }
-        if (model_ok(c, mdl)) return SF_EINVAL;
+        if (model_ok(c, models[i])) {
+            char why[sizeof(g_err)];
+            snprintf(why, sizeof(why), "%s", g_err);
+            sf_set_error("multi-order call: segment %d: %s", i, why);
+            return SF_EINVAL;
+        }
         if (c->device != c0->device || c->m != c0->m || c->P != c0->P) {
             sf_set_error("multi-order call: segment %d differs from segment 0 in device, eigenspectra or grid dimensions", i);
             return SF_EINVAL;
         }
+        if (models[i]->has_vsini) uni->has_vsini = 1;
+        if (i == 0) *L = layout_of(c0);
         L->M = std::max(L->M, c->M);
         L->nf = std::max(L->nf, c->nf);
         L->npad = std::max(L->npad, c->npad);
@@ -1187,24 +1202,37 @@ static int multi_layout(const sf_segment* segs, int nseg, const sf_model_desc* m
 #define SF_MULTI_LANES 3  // (4, 6 and 8 lanes measured: no further gain)
 static int multi_first_units(int U) { return std::min(U, 256); }
 static int multi_chunk_cap(int U, int bmax) { return std::min(U, std::max(U - multi_first_units(U), multi_first_units(U) + bmax)); }
-extern "C" size_t sf_multi_workspace_bytes(const sf_segment* segs, int nseg, const sf_model_desc* mdl) {
+static size_t multi_workspace_bytes(const sf_segment* segs, int nseg, const sf_model_desc* const* models) {
     Layout L;
+    sf_model_desc uni;
     int U = 0, bmax = 0;
-    if (multi_layout(segs, nseg, mdl, &L, &U, &bmax)) return 0;
-    return carve(L, mdl, U, bmax, nullptr, 0, true, multi_chunk_cap(U, bmax), 1, SF_MULTI_LANES).bytes;
+    if (multi_layout(segs, nseg, models, &L, &U, &bmax, &uni)) return 0;
+    return carve(L, &uni, U, bmax, nullptr, 0, true, multi_chunk_cap(U, bmax), 1, SF_MULTI_LANES).bytes;
 }
-extern "C" int sf_loglike_multi_batch(const sf_segment* segs, int nseg, const sf_model_desc* mdl, double* d_lnl,
-                                      double* d_logdet, double* d_sqmah, double* d_log_scale, int* d_info,
-                                      void* d_work, size_t work_bytes, void* stream) {
+// the single-descriptor entry points: every segment described by `mdl`
+static std::vector<const sf_model_desc*> same_desc(int nseg, const sf_model_desc* mdl) {
+    return std::vector<const sf_model_desc*>(nseg > 0 ? nseg : 0, mdl);
+}
+extern "C" size_t sf_multi_workspace_bytes(const sf_segment* segs, int nseg, const sf_model_desc* mdl) {
+    if (!mdl) return 0;
+    return multi_workspace_bytes(segs, nseg, same_desc(nseg, mdl).data());
+}
+extern "C" size_t sf_multi_workspace_bytes_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models) {
+    return multi_workspace_bytes(segs, nseg, models);
+}
+static int loglike_multi(const char* who, const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                         double* d_lnl, double* d_logdet, double* d_sqmah, double* d_log_scale, int* d_info,
+                         void* d_work, size_t work_bytes, void* stream) {
     Layout L;
+    sf_model_desc uni;
     int U = 0, bmax = 0;
-    int rc = multi_layout(segs, nseg, mdl, &L, &U, &bmax);
+    int rc = multi_layout(segs, nseg, models, &L, &U, &bmax, &uni);
     if (rc) return rc;
     if (!d_lnl || !d_work) {
-        sf_set_error("sf_loglike_multi_batch: d_lnl and a workspace are required");
+        sf_set_error("%s: d_lnl and a workspace are required", who);
         return SF_EINVAL;
     }
-    const size_t need = carve(L, mdl, U, bmax, nullptr, 0, true, multi_chunk_cap(U, bmax), 1, SF_MULTI_LANES).bytes;
+    const size_t need = carve(L, &uni, U, bmax, nullptr, 0, true, multi_chunk_cap(U, bmax), 1, SF_MULTI_LANES).bytes;
     if (work_bytes < need) {
         sf_set_error("workspace too small: have %zu, need %zu", work_bytes, need);
         return SF_ENOMEM;
@@ -1212,7 +1240,7 @@ extern "C" int sf_loglike_multi_batch(const sf_segment* segs, int nseg, const sf
     sf_ctx* c0 = segs[0].ctx;
     if (use_device(c0)) return SF_EHIP;
     hipStream_t s = (hipStream_t)stream;
-    Work W = carve(L, mdl, U, bmax, d_work, work_bytes, true, multi_chunk_cap(U, bmax), 1, SF_MULTI_LANES);
+    Work W = carve(L, &uni, U, bmax, d_work, work_bytes, true, multi_chunk_cap(U, bmax), 1, SF_MULTI_LANES);
     prof_count_call();
     const int64_t stride = (int64_t)L.npad * L.lda;
     // (one frame for every chunk: the fills run before the chunk sizes are known; a chunk too small for the fused
@@ -1248,13 +1276,13 @@ extern "C" int sf_loglike_multi_batch(const sf_segment* segs, int nseg, const sf
         Work w = with_trans_set(slice(W, u0), lane);
         {
             ProfScope ps(sp, PS_TRANSFORM);
-            rc = run_transforms(c, mdl, B, segs[i].d_params, w, nullptr, nullptr, nullptr,
+            rc = run_transforms(c, models[i], B, segs[i].d_params, w, nullptr, nullptr, nullptr,
                                 d_log_scale ? d_log_scale + u0 : nullptr, true, sp);
             if (rc) return rc;
         }
         {
             ProfScope ps(sp, PS_FILL);
-            sf_fill_args f = fill_args(c, mdl, segs[i].d_params, w);
+            sf_fill_args f = fill_args(c, models[i], segs[i].d_params, w);
             f.C = w.C;
             f.lda = L.lda;
             f.stride = stride;
@@ -1316,6 +1344,22 @@ extern "C" int sf_loglike_multi_batch(const sf_segment* segs, int nseg, const sf
     if (d_logdet) SF_HIP(hipMemcpyAsync(d_logdet, W.logdet, sizeof(double) * (size_t)U, hipMemcpyDeviceToDevice, s));
     if (d_sqmah) SF_HIP(hipMemcpyAsync(d_sqmah, W.sqmah, sizeof(double) * (size_t)U, hipMemcpyDeviceToDevice, s));
     return SF_OK;
+}
+extern "C" int sf_loglike_multi_batch(const sf_segment* segs, int nseg, const sf_model_desc* mdl, double* d_lnl,
+                                      double* d_logdet, double* d_sqmah, double* d_log_scale, int* d_info,
+                                      void* d_work, size_t work_bytes, void* stream) {
+    if (!mdl) {
+        sf_set_error("multi-order call: bad segment list / model descriptor");
+        return SF_EINVAL;
+    }
+    return loglike_multi("sf_loglike_multi_batch", segs, nseg, same_desc(nseg, mdl).data(), d_lnl, d_logdet, d_sqmah,
+                         d_log_scale, d_info, d_work, work_bytes, stream);
+}
+extern "C" int sf_loglike_multi_batch_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                         double* d_lnl, double* d_logdet, double* d_sqmah, double* d_log_scale,
+                                         int* d_info, void* d_work, size_t work_bytes, void* stream) {
+    return loglike_multi("sf_loglike_multi_batch_md", segs, nseg, models, d_lnl, d_logdet, d_sqmah, d_log_scale,
+                         d_info, d_work, work_bytes, stream);
 }
 
 // ------------------------------------------------------------------- structure-exploiting solver

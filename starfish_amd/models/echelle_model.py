@@ -7,18 +7,29 @@ independent given the stellar parameters (docs/intro.rst:71-73), so lnL = sum ov
 order is a :class:`SpectrumModel` whose (walker x order) units are evaluated in batched device passes
 and may live on different GPUs (``devices``) with only a host-side sum -- no collective.
 """
+import re
+
 import numpy as np
 
+from .._flatdict import FlatterDict
 from ..spectrum import Spectrum
 from .spectrum_model import SpectrumModel
 
+#: top-level parameters that may be sampled per order (flux calibration, noise model, velocity, broadening,
+#: extinction); the emulator grid parameters are always shared
+PER_ORDER_PARAMS = ("cheb", "log_scale", "global_cov", "local_cov", "vz", "vsini", "Av")
+_PREFIXED = re.compile(r"order(\d+):(.+)$")
+
 
 class EchelleModel:
-    def __init__(self, emulator, data, grid_params, devices=None, name="EchelleModel", solver="dense", **params):
-        """``params`` are shared by every order (vz, vsini, log_scale, global_cov, cheb, ...);
+    def __init__(self, emulator, data, grid_params, devices=None, name="EchelleModel", solver="dense", per_order=None,
+                 **params):
+        """``params`` are the starting values of every order (vz, vsini, log_scale, global_cov, cheb, ...);
         per-order overrides can be set afterwards on ``self.orders[i]``.  ``solver`` as in
         :class:`SpectrumModel`: "dense" (the reference's algorithm: all (order x walker) units in one batched
-        Cholesky), "auto" / "banded" (band + rank-m Woodbury per order, same value to rounding)."""
+        Cholesky), "auto" / "banded" (band + rank-m Woodbury per order, same value to rounding).
+        ``per_order``: names from :data:`PER_ORDER_PARAMS` that every order samples on its own (labels
+        ``order{i}:<name>...``, after the shared labels); None: every parameter is shared."""
         self.name = name
         self.orders = []
         for i, order in enumerate(data):
@@ -27,21 +38,75 @@ class EchelleModel:
             kw = {k: (dict(v) if isinstance(v, dict) else ([dict(x) for x in v] if k == "local_cov" else
                        (list(v) if isinstance(v, (list, tuple)) else v))) for k, v in params.items()}
             self.orders.append(SpectrumModel(emulator, single, grid_params, device=dev, name=f"{name}[{i}]", solver=solver, **kw))
+        self.per_order = self._check_per_order(per_order, self.orders)
 
     @classmethod
-    def from_orders(cls, models, name="EchelleModel"):
+    def from_orders(cls, models, name="EchelleModel", per_order=None):
         """Assemble from existing per-order :class:`SpectrumModel` objects (e.g. one emulator chunk per order,
-        per-order frozen local kernels).  All orders must expose the same thawed labels."""
+        per-order frozen local kernels).  Without ``per_order`` all orders must expose the same thawed labels;
+        with it only the shared ones (values from order 0), the per-order groups may differ in membership too."""
         self = cls.__new__(cls)
         self.name = name
         self.orders = list(models)
         if not self.orders:
             raise ValueError("EchelleModel needs at least one order")
-        labels = self.orders[0].labels
-        for m in self.orders[1:]:
-            if m.labels != labels:
-                raise ValueError(f"orders disagree on the thawed parameters: {m.labels} vs {labels}")
+        self.per_order = self._check_per_order(per_order, self.orders)
+        if self.per_order is None:
+            labels = self.orders[0].labels
+            for m in self.orders[1:]:
+                if m.labels != labels:
+                    raise ValueError(f"orders disagree on the thawed parameters: {m.labels} vs {labels}")
+        else:
+            self._layout()  # (raises if the shared labels disagree)
         return self
+
+    @staticmethod
+    def _check_per_order(per_order, orders):
+        if per_order is None:
+            return None
+        names = tuple(str(n) for n in np.atleast_1d(per_order))
+        grid = set(orders[0].emulator.param_names) if orders else set()
+        for n in names:
+            if n in grid:
+                raise ValueError(f"{n!r} is an emulator grid parameter: those are shared by every order")
+            if n not in PER_ORDER_PARAMS:
+                raise ValueError(f"{n!r} cannot be sampled per order (one of {', '.join(PER_ORDER_PARAMS)})")
+        return names
+
+    def _is_per_order(self, key):
+        return self.per_order is not None and key.split(":", 1)[0] in self.per_order
+
+    def _order_of(self, name):
+        """``order{i}:<key>`` -> (i, key); None for a bare name."""
+        hit = _PREFIXED.match(name)
+        if not hit:
+            return None
+        i, key = int(hit.group(1)), hit.group(2)
+        if not 0 <= i < len(self.orders):
+            raise ValueError(f"{name}: the model has {len(self.orders)} orders")
+        if not self._is_per_order(key):
+            raise ValueError(f"{name}: {key!r} is not a per-order parameter of this model")
+        return i, key
+
+    def _layout(self):
+        """(labels, cols): the model's labels, and for every order the columns of a parameter vector that hold
+        that order's own labels (shared labels first, then each order's per-order labels, prefixed)."""
+        shared = [k for k in self.orders[0].labels if not self._is_per_order(k)]
+        labels, cols = list(shared), []
+        for i, m in enumerate(self.orders):
+            own = m.labels
+            mine = [k for k in own if not self._is_per_order(k)]
+            if mine != shared:
+                raise ValueError(f"order {i} disagrees with order 0 on the shared thawed parameters: {mine} vs {shared}")
+            c = []
+            for k in own:
+                if self._is_per_order(k):
+                    c.append(len(labels))
+                    labels.append(f"order{i}:{k}")
+                else:
+                    c.append(shared.index(k))
+            cols.append(np.array(c, dtype=np.intp))
+        return tuple(labels), cols
 
     def __len__(self):
         return len(self.orders)
@@ -57,42 +122,144 @@ class EchelleModel:
 
     @property
     def labels(self):
-        return self.orders[0].labels
+        if self.per_order is None:
+            return self.orders[0].labels
+        return self._layout()[0]
+
+    def _route(self, op, names):
+        names = [str(n) for n in np.atleast_1d(names)]
+        if self.per_order is None or names[0] == "all":
+            for m in self.orders:
+                getattr(m, op)(names)
+            return
+        for name in names:
+            hit = self._order_of(name)
+            if hit is not None:  # one order's parameter or group
+                getattr(self.orders[hit[0]], op)(hit[1])
+                continue
+            targets = [m for m in self.orders if name in m.params] or self.orders
+            for m in targets:
+                getattr(m, op)(name)
 
     def freeze(self, names):
-        for m in self.orders:
-            m.freeze(names)
+        """As :meth:`SpectrumModel.freeze` on every order; a prefixed name (``order3:cheb:2``, ``order1:local_cov``)
+        acts on that order only."""
+        self._route("freeze", names)
 
     def thaw(self, names):
-        for m in self.orders:
-            m.thaw(names)
+        """As :meth:`SpectrumModel.thaw` on every order; a prefixed name acts on that order only."""
+        self._route("thaw", names)
 
     def get_param_vector(self):
-        return self.orders[0].get_param_vector()
+        if self.per_order is None:
+            return self.orders[0].get_param_vector()
+        labels, cols = self._layout()
+        out = np.empty(len(labels))
+        for i in reversed(range(len(self.orders))):  # (shared values: order 0's)
+            out[cols[i]] = self.orders[i].get_param_vector()
+        return out
 
     def set_param_vector(self, P):
-        for m in self.orders:
-            m.set_param_vector(P)
+        if self.per_order is None:
+            for m in self.orders:
+                m.set_param_vector(P)
+            return
+        labels, cols = self._layout()
+        P = np.asarray(P, dtype=np.float64)
+        if len(P) != len(labels):
+            raise ValueError("Param Vector does not match length of thawed parameters")
+        for m, c in zip(self.orders, cols):
+            m.set_param_vector(P[c])
+
+    def get_param_dict(self, flat=False):
+        """Thawed parameters under :attr:`labels` (shared ones from order 0), nested or flat."""
+        out = FlatterDict()
+        own = [m.get_param_dict(flat=True) for m in self.orders]
+        for key, val in own[0].items():
+            if not self._is_per_order(key):
+                out[key] = val
+        for i, d in enumerate(own):
+            for key, val in d.items():
+                if self._is_per_order(key):
+                    out[f"order{i}:{key}"] = val
+        return out if flat else out.as_dict()
+
+    def set_param_dict(self, params):
+        """Update parameters: a prefixed key goes to its order, a bare key to every order that has it."""
+        for key, val in FlatterDict(params).items():
+            hit = self._order_of(key)
+            if hit is not None:
+                self.orders[hit[0]].set_param_dict({hit[1]: val})
+                continue
+            targets = [m for m in self.orders if key in m.params]
+            if not targets:
+                raise KeyError(f"{key} is not a parameter of any order")
+            for m in targets:
+                m.set_param_dict({key: val})
+
+    def _prior_terms(self, priors):
+        """(prior, order index, key in that order) of every prior term: keys are looked up as the reference does
+        (``key in params``); a prefixed key is its order's, a bare per-order key counts once per order that has it,
+        a shared key once (order 0's)."""
+        terms = []
+        for key, prior in (priors or {}).items():
+            hit = _PREFIXED.match(key)
+            if hit and self._is_per_order(hit.group(2)):
+                i, k = int(hit.group(1)), hit.group(2)
+                if i < len(self.orders) and k in self.orders[i].params:
+                    terms.append((prior, i, k))
+            elif self._is_per_order(key):
+                terms += [(prior, i, key) for i, m in enumerate(self.orders) if key in m.params]
+            elif key in self.orders[0].params:
+                terms.append((prior, 0, key))
+        return terms
+
+    def _batch_prior(self, P, priors, cols):
+        """Log-prior of every row of ``P`` (:attr:`labels` order); parameters not sampled use the current value."""
+        lp = np.zeros(P.shape[0])
+        for prior, i, key in self._prior_terms(priors):
+            own = self.orders[i].labels
+            if key in own:
+                lp += np.asarray(prior.logpdf(P[:, cols[i][own.index(key)]]), dtype=np.float64)
+            else:
+                lp += prior.logpdf(self.orders[i][key])
+        return lp
 
     def log_likelihood(self, priors=None):
-        """Sum of the per-order likelihoods; the prior is counted once."""
-        total = self.orders[0].log_likelihood(priors)
-        for m in self.orders[1:]:
-            total += m.log_likelihood(None)
-        return total
+        """Sum of the per-order likelihoods; the prior is counted once (per order for a per-order parameter)."""
+        if self.per_order is None:
+            total = self.orders[0].log_likelihood(priors)
+            for m in self.orders[1:]:
+                total += m.log_likelihood(None)
+            return total
+        lp = 0.0
+        for prior, i, key in self._prior_terms(priors):
+            lp += prior.logpdf(self.orders[i][key])
+        if not np.isfinite(lp):
+            return -np.inf
+        return sum(m.log_likelihood(None) for m in self.orders) + lp
 
     def log_likelihood_batch(self, P, priors=None, return_info=False, return_orders=False):
-        """lnL (B,) for B shared parameter vectors.  All (order x walker) units of a device are evaluated in ONE
-        enqueue (``sf_loglike_multi_batch``: every order fills its own covariance matrices, all of them share one
-        batched Cholesky) with one host synchronisation per device; devices work concurrently.  The sum over
-        orders happens on the host (no collective).  Walkers that fail in any order get ``-inf``; ``info`` is the
-        first non-zero per-order code.  With ``return_orders`` the (n_orders, B) per-order values are returned too."""
+        """lnL (B,) for B parameter vectors (rows of ``P`` in :attr:`labels` order; every order gets the columns of
+        its own labels).  All (order x walker) units of a device are evaluated in ONE enqueue
+        (``sf_loglike_multi_batch``, or ``sf_loglike_multi_batch_md`` when the orders' row layouts differ: every
+        order fills its own covariance matrices, all of them share one batched Cholesky) with one host
+        synchronisation per device; devices work concurrently.  The sum over orders happens on the host (no
+        collective).  Walkers that fail in any order get ``-inf``; ``info`` is the first non-zero per-order code.
+        With ``return_orders`` the (n_orders, B) per-order values are returned too."""
         from .. import _device as D
 
         P = np.atleast_2d(np.asarray(P, dtype=np.float64))
         B = P.shape[0]
-        first = self.orders[0]
-        prior_lp = first._batch_prior(P, priors)
+        if self.per_order is None:
+            order_P = [P] * len(self.orders)
+            prior_lp = self.orders[0]._batch_prior(P, priors)
+        else:
+            labels, cols = self._layout()
+            if P.shape[1] != len(labels):
+                raise ValueError("Param Vector does not match length of thawed parameters")
+            order_P = [P[:, c] for c in cols]
+            prior_lp = self._batch_prior(P, priors, cols)
         finite = np.isfinite(prior_lp)
         lnl = np.full(B, -np.inf)
         info = np.zeros(B, dtype=np.int32)
@@ -109,7 +276,7 @@ class EchelleModel:
 
             pending, used = [], {}
             for i, m in enumerate(self.orders):
-                dev, md, rows = m._pack(P[finite], update_caches=False)
+                dev, md, rows = m._pack(order_P[i][finite], update_caches=False)
                 if m.solver == "dense":
                     pending.append((i, dev, md, None, rows))
                     continue
@@ -130,19 +297,19 @@ class EchelleModel:
             bad = codes != 0
             info[finite] = np.where(bad.any(axis=0), codes[bad.argmax(axis=0), np.arange(codes.shape[1])], 0)
         elif finite.any():
-            packed = [m._pack(P[finite], update_caches=False) for m in self.orders]
-            # one multi-order call per (device, row layout): the C-ABI reads every segment of a call with ONE
-            # ModelDesc (row stride, offsets of the local kernels / Chebyshev terms, has_* flags), so orders whose
-            # descriptors differ -- e.g. a different number of frozen local kernels -- go to separate calls
+            packed = [m._pack(order_P[i][finite], update_caches=False) for i, m in enumerate(self.orders)]
+            # one multi-order call per device (and emulator shape): orders whose row layouts differ -- per-order
+            # Chebyshev terms, another number of local kernels, ... -- pass one descriptor each
             groups = {}
             for idx, (dev, md, rows) in enumerate(packed):
-                key = (str(dev.dev), dev.m, dev.P, int(np.atleast_2d(rows).shape[1])) + D.model_desc_key(md)
-                groups.setdefault(key, []).append(idx)
+                groups.setdefault((str(dev.dev), dev.m, dev.P), []).append(idx)
             pending = []
             for idxs in groups.values():  # enqueue everything first, synchronise afterwards
                 devs = [packed[i][0] for i in idxs]
-                md = packed[idxs[0]][1]
-                pending.append((idxs, D.loglike_multi(devs, md, [packed[i][2] for i in idxs], sync=False)))
+                mds = [packed[i][1] for i in idxs]
+                same = all(D.model_desc_key(m) == D.model_desc_key(mds[0]) for m in mds)
+                pending.append((idxs, D.loglike_multi(devs, mds[0] if same else mds, [packed[i][2] for i in idxs],
+                                                      sync=False)))
             vals = np.zeros((len(self.orders), int(finite.sum())))
             codes = np.zeros((len(self.orders), int(finite.sum())), dtype=np.int32)
             for idxs, plan in pending:
