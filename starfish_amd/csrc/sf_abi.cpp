@@ -1070,6 +1070,54 @@ extern "C" int sf_cov_fill_batch(sf_ctx* c, const sf_model_desc* mdl, int B, con
     return SF_OK;
 }
 
+// The likelihood's fill of the workspace matrices of layout L (lower tiles, identity padding, jitter), in the frame fp of
+// the factorisation: only the tiles that carry more than the rank-m term are materialised (tile map and list)
+static sf_fill_args loglike_fill_args(sf_ctx* c, const sf_model_desc* mdl, const double* d_params, const Work& w, const Layout& L,
+                                      int fp) {
+    sf_fill_args f = fill_args(c, mdl, d_params, w);
+    f.C = w.C;
+    f.lda = L.lda;
+    f.stride = (int64_t)L.npad * L.lda;
+    f.lower_only = 1;
+    f.add_jitter = 1;
+    f.gtab = w.gtab;  // per-diagonal table of the global kernel (used on log-uniform grids only)
+    f.tilemap = w.tilemap;
+    f.tilelist = w.tilelist;
+    f.tilecount = w.tilecount;
+    f.list_cap = (int)tilemap_bytes(L);
+    f.fp = fp;
+    f.nt128 = (L.npad + fp + 127) / 128;
+    return f;
+}
+// The rest of the likelihood of `units` matrices filled that way: the factorisation, whose generator (Y, tile map, same
+// frame) supplies the tiles the fill left out and through which the residual rides (w.resid becomes z = L^-1 R); then
+// logdet and the squared Mahalanobis distance -> lnL.  ltbuf: the factorisation's scratch, ex: its executor.
+static int loglike_factor_finish(const Work& w, const Layout& L, int fp, int units, double* ltbuf, double* d_lnl, int* d_info,
+                                 hipStream_t s, sf_exec* ex) {
+    const int64_t stride = (int64_t)L.npad * L.lda;
+    int rc;
+    {
+        ProfScope ps(s, PS_POTRF);
+        sf_gen_args gen;
+        gen.Y = w.Y;
+        gen.mpad = L.mpad;
+        gen.ldy = L.npad;
+        gen.tilemap = w.tilemap;
+        gen.fp = fp;
+        gen.nt128 = (L.npad + fp + 127) / 128;
+        rc = sf_launch_potrf(w.C, L.npad, L.lda, stride, units, w.info_c, ltbuf, w.resid, L.npad, s, &gen, ex);
+        if (rc) return rc;
+    }
+    {
+        ProfScope ps(s, PS_SOLVE);
+        rc = sf_launch_logdet_z(w.C, L.npad, L.lda, stride, units, w.resid, L.npad, w.logdet, w.sqmah, s);
+        if (rc) return rc;
+        rc = sf_launch_finish(units, w.logdet, w.sqmah, w.info_e, w.info_c, d_lnl, d_info, s);
+        if (rc) return rc;
+    }
+    return SF_OK;
+}
+
 extern "C" int sf_loglike_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params,
                                 double* d_lnl, double* d_logdet, double* d_sqmah, double* d_resid,
                                 double* d_log_scale, int* d_info, void* d_work, size_t work_bytes,
@@ -1083,55 +1131,23 @@ extern "C" int sf_loglike_batch(sf_ctx* c, const sf_model_desc* mdl, int B, cons
     hipStream_t s = (hipStream_t)stream;
     Work w = carve(c, mdl, B, d_work, work_bytes, true);
     prof_count_call();
-    const int64_t stride = (int64_t)c->npad * c->lda;
-    int call_fp = 0;
+    const Layout L = layout_of(c);
     {
         ProfScope ps(s, PS_TRANSFORM);
         rc = run_transforms(c, mdl, B, d_params, w, nullptr, nullptr, d_resid, d_log_scale, true, s);
         if (rc) return rc;
     }
+    // (the tiles of the factorisation's frame: see sf_potrf_front_pad.  Evaluated ONCE per call and handed on to the fill
+    // and the factorisation: it depends on the process-global persistent-kernel switch, which a recovery on another host
+    // thread may flip between the two stages -- tile map and factorisation must agree on the frame)
+    const int fp = sf_potrf_front_pad(c->npad, B);
     {
         ProfScope ps(s, PS_FILL);
-        sf_fill_args f = fill_args(c, mdl, d_params, w);
-        f.C = w.C;
-        f.lda = c->lda;
-        f.stride = stride;
-        f.lower_only = 1;
-        f.add_jitter = 1;
-        f.gtab = w.gtab;        // per-diagonal table of the global kernel (used on log-uniform grids only)
-        f.tilemap = w.tilemap;  // only tiles that carry more than the rank-m term are materialised
-        f.tilelist = w.tilelist;
-        f.tilecount = w.tilecount;
-        f.list_cap = (int)tilemap_bytes(layout_of(c));
-        // (the tiles of the factorisation's frame: see sf_potrf_front_pad.  Evaluated ONCE per call and handed on to the
-        // factorisation below: it depends on the process-global persistent-kernel switch, which a recovery on another host
-        // thread may flip between the two stages -- tile map and factorisation must agree on the frame)
-        f.fp = sf_potrf_front_pad(c->npad, B);
-        f.nt128 = (c->npad + f.fp + 127) / 128;
-        call_fp = f.fp;
-        rc = sf_launch_fill(f, B, s);
+        rc = sf_launch_fill(loglike_fill_args(c, mdl, d_params, w, L, fp), B, s);
         if (rc) return rc;
     }
-    {
-        ProfScope ps(s, PS_POTRF);
-        // the residual rides through the factorisation: w.resid is overwritten with z = L^-1 R
-        sf_gen_args gen;
-        gen.Y = w.Y;
-        gen.mpad = c->mpad;
-        gen.ldy = c->npad;
-        gen.tilemap = w.tilemap;
-        gen.fp = call_fp;
-        gen.nt128 = (c->npad + gen.fp + 127) / 128;
-        rc = sf_launch_potrf(w.C, c->npad, c->lda, stride, B, w.info_c, w.ltbuf, w.resid, c->npad, s, &gen, &c->exec);
-        if (rc) return rc;
-    }
-    {
-        ProfScope ps(s, PS_SOLVE);
-        rc = sf_launch_logdet_z(w.C, c->npad, c->lda, stride, B, w.resid, c->npad, w.logdet, w.sqmah, s);
-        if (rc) return rc;
-        rc = sf_launch_finish(B, w.logdet, w.sqmah, w.info_e, w.info_c, d_lnl, d_info, s);
-        if (rc) return rc;
-    }
+    rc = loglike_factor_finish(w, L, fp, B, w.ltbuf, d_lnl, d_info, s, &c->exec);
+    if (rc) return rc;
     if (d_logdet) SF_HIP(hipMemcpyAsync(d_logdet, w.logdet, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, s));
     if (d_sqmah) SF_HIP(hipMemcpyAsync(d_sqmah, w.sqmah, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, s));
     return SF_OK;
@@ -1242,11 +1258,9 @@ static int loglike_multi(const char* who, const sf_segment* segs, int nseg, cons
     hipStream_t s = (hipStream_t)stream;
     Work W = carve(L, &uni, U, bmax, d_work, work_bytes, true, multi_chunk_cap(U, bmax), 1, SF_MULTI_LANES);
     prof_count_call();
-    const int64_t stride = (int64_t)L.npad * L.lda;
     // (one frame for every chunk: the fills run before the chunk sizes are known; a chunk too small for the fused
     // sequences is factorised by them all the same -- sf_launch_potrf honours the frame of the tile map)
     const int fp = sf_potrf_front_pad(L.npad, 1 << 20);
-    const int nt128 = (L.npad + fp + 127) / 128;
     // Pipeline: the per-order transform chains and fills (many small launches, a few per cent of the step) run on
     // the context's auxiliary stream one chunk of orders ahead of the factorisation on the caller's stream, so all
     // but the first chunk's are hidden behind the Cholesky of the previous chunk (see multi_first_units).
@@ -1282,20 +1296,7 @@ static int loglike_multi(const char* who, const sf_segment* segs, int nseg, cons
         }
         {
             ProfScope ps(sp, PS_FILL);
-            sf_fill_args f = fill_args(c, models[i], segs[i].d_params, w);
-            f.C = w.C;
-            f.lda = L.lda;
-            f.stride = stride;
-            f.lower_only = 1;
-            f.add_jitter = 1;
-            f.gtab = w.gtab;
-            f.tilemap = w.tilemap;
-            f.tilelist = w.tilelist;
-            f.tilecount = w.tilecount;
-            f.list_cap = (int)tilemap_bytes(L);
-            f.nt128 = nt128;
-            f.fp = fp;
-            rc = sf_launch_fill(f, B, sp);
+            rc = sf_launch_fill(loglike_fill_args(c, models[i], segs[i].d_params, w, L, fp), B, sp);
             if (rc) return rc;
         }
         u0 += B;
@@ -1318,28 +1319,9 @@ static int loglike_multi(const char* who, const sf_segment* segs, int nseg, cons
     for (const Chunk& ch : chunks) {
         for (int l = 0; l < SF_MULTI_LANES; ++l)
             if (ch.filled[l]) SF_HIP(hipStreamWaitEvent(s, ch.filled[l], 0));
-        Work w = slice(W, ch.u0);
-        {
-            ProfScope ps(s, PS_POTRF);
-            sf_gen_args gen;
-            gen.Y = w.Y;
-            gen.mpad = L.mpad;
-            gen.ldy = L.npad;
-            gen.tilemap = w.tilemap;
-            gen.nt128 = nt128;
-            gen.fp = fp;
-            rc = sf_launch_potrf(w.C, L.npad, L.lda, stride, ch.units, w.info_c, W.ltbuf, w.resid, L.npad, s, &gen,
-                                 &c0->exec_potrf);
-            if (rc) return rc;
-        }
-        {
-            ProfScope ps(s, PS_SOLVE);
-            rc = sf_launch_logdet_z(w.C, L.npad, L.lda, stride, ch.units, w.resid, L.npad, w.logdet, w.sqmah, s);
-            if (rc) return rc;
-            rc = sf_launch_finish(ch.units, w.logdet, w.sqmah, w.info_e, w.info_c, d_lnl + ch.u0,
-                                  d_info ? d_info + ch.u0 : nullptr, s);
-            if (rc) return rc;
-        }
+        rc = loglike_factor_finish(slice(W, ch.u0), L, fp, ch.units, W.ltbuf, d_lnl + ch.u0, d_info ? d_info + ch.u0 : nullptr, s,
+                                   &c0->exec_potrf);
+        if (rc) return rc;
     }
     if (d_logdet) SF_HIP(hipMemcpyAsync(d_logdet, W.logdet, sizeof(double) * (size_t)U, hipMemcpyDeviceToDevice, s));
     if (d_sqmah) SF_HIP(hipMemcpyAsync(d_sqmah, W.sqmah, sizeof(double) * (size_t)U, hipMemcpyDeviceToDevice, s));

@@ -690,12 +690,8 @@ static int launch_forms_kernel(const sf_band_args& a, int nrb, int nblocks, hipS
     const int nbr = a.nbr;
     const size_t shm = band_lds_bytes(nbr, nrb);
     static sf_dev_once attr_once;  // devices whose function attributes are set
-    SF_CHECK(sf_once_per_device(&attr_once, []() -> int {
-        SF_HIP(hipFuncSetAttribute((const void*)k_band_forms<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        SF_HIP(hipFuncSetAttribute((const void*)k_band_forms<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        SF_HIP(hipFuncSetAttribute((const void*)k_band_forms<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        return SF_OK;
-    }));
+    SF_CHECK(sf_lds_limit_once(&attr_once, 160 * 1024,
+                               {(const void*)k_band_forms<1>, (const void*)k_band_forms<2>, (const void*)k_band_forms<3>}));
     // waves 4.. prefetch the band rows in groups of 256 threads (one 16 x 16 block per group and
     // register): enough groups for SFB_PF registers to cover the nbr blocks of a block row
     const int nwaves = nbr <= SFB_PF ? 8 : nbr <= 2 * SFB_PF ? 12 : 16;

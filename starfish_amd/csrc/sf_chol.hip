@@ -951,10 +951,7 @@ __global__ __launch_bounds__(512) void k_diag_lds(const double* __restrict__ T, 
 static int sf_launch_diag128(double* T, int64_t sT, int pw, int* info, int info_off, double* rhs, int ldr, double* Cdiag,
                              int ldc, int64_t sC, double* Wt, int64_t sW, int batch, hipStream_t s, int fp0 = 0) {
     static sf_dev_once attr_once;  // devices whose function attributes are set
-    SF_CHECK(sf_once_per_device(&attr_once, []() -> int {
-        SF_HIP(hipFuncSetAttribute((const void*)k_diag_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        return SF_OK;
-    }));
+    SF_CHECK(sf_lds_limit_once(&attr_once, 160 * 1024, {(const void*)k_diag_lds}));
     long long* stamps = nullptr;
 #ifdef SF_TUNING
     static int printed = 0;
@@ -2301,12 +2298,64 @@ static int sf_split_policy(long long wgs, int nk) {
     while (2 * S <= SF_SPLIT_MAX && wgs * 2 * S <= 384 && nk / (2 * S) >= 8) S *= 2;
     return S;
 }
-// per matrix: a reserved region of SF_LTB_DOUBLES (unused), the panel scratch T and two W^T buffers; then the
-// partial-sum tiles: one region for the chain (top) launches, one per slab group
-size_t sf_potrf_work_doubles(int n, int batch) {
+// The scratch of one factorisation of `batch` matrices of order n (the real n, before the frame shift of the fused
+// sequences): per matrix a reserved region of SF_LTB_DOUBLES (unused), the panel scratch T and two W^T buffers; then
+// the partial-sum tiles: one region for the chain (top) launches, one per slab group.
+struct sf_potrf_scratch {
+    double* T;  // [batch] x sT
+    int64_t sT;
+    double* W;  // two buffers of [batch] x sW, one after the other
+    int64_t sW;
+    double* part;
+    int batch;
+    size_t doubles;  // the whole scratch: sf_potrf_work_doubles
+    double* Wbuf(int i) const { return W + (size_t)i * batch * sW; }
+    size_t Wdoubles() const { return 2 * (size_t)batch * sW; }  // both buffers
+    // the wide sequence's four most recent inverse tiles W(k): slot k & 3, two 128-row slots to a buffer
+    double* Wslot(int k) const { return Wbuf((k >> 1) & 1) + (size_t)(k & 1) * GT * SF_LDT; }
+};
+static sf_potrf_scratch sf_potrf_scratch_of(double* work, int n, int batch) {
+    sf_potrf_scratch w = {};
     const size_t b = (size_t)batch;
-    return b * SF_LTB_DOUBLES + b * ((size_t)(n + SF_NB) * SF_LDT + SF_TSKEW) + 2 * b * ((size_t)SF_NB * SF_LDT + SF_TSKEW) + 64 +
-           (size_t)(SF_EXEC_GROUPS + 1) * sf_split_region_tiles() * (GT * GT);
+    w.sT = (int64_t)(n + SF_NB) * SF_LDT + SF_TSKEW;
+    w.sW = (int64_t)SF_NB * SF_LDT + SF_TSKEW;
+    w.batch = batch;
+    const size_t oT = b * SF_LTB_DOUBLES, oW = oT + b * w.sT, opart = oW + w.Wdoubles() + 64;
+    w.doubles = opart + (size_t)(SF_EXEC_GROUPS + 1) * sf_split_region_tiles() * (GT * GT);
+    if (work) {
+        w.T = work + oT;
+        w.W = work + oW;
+        w.part = work + opart;
+    }
+    return w;
+}
+size_t sf_potrf_work_doubles(int n, int batch) { return sf_potrf_scratch_of(nullptr, n, batch).doubles; }
+
+// The generator fields (matrix-free start) of sf_gemm_args, sf_panel_args and sf_panelw_args, in the frame fp
+template <class Args>
+static void sf_set_gen(Args& g, const sf_gen_args* gen, int fp) {
+    if (!gen) return;
+    g.genY = gen->Y - fp;
+    g.sY = (int64_t)gen->mpad * gen->ldy;
+    g.ldy = gen->ldy;
+    g.mpad = gen->mpad;
+    g.tilemap = gen->tilemap;
+    g.nt128 = gen->nt128;
+}
+// The fields of sf_panel_args / sf_panelw_args that stay the same over one factorisation (A, rhs and the generator in the
+// shifted frame fp)
+template <class Args>
+static Args sf_panel_frame(double* A, int n, int lda, int64_t stride, double* rhs, int ldr, const sf_gen_args* gen, int fp) {
+    Args g = {};
+    g.C = A;
+    g.sC = stride;
+    g.lda = lda;
+    g.n = n;
+    g.rhs = rhs;
+    g.ldr = ldr;
+    g.fp = fp;
+    sf_set_gen(g, gen, fp);
+    return g;
 }
 
 // ---- two-stream lookahead ---------------------------------------------------------------------
@@ -2318,6 +2367,24 @@ size_t sf_potrf_work_doubles(int n, int batch) {
         int rc__ = (x);    \
         if (rc__) return rc__; \
     } while (0)
+// fork: the streams `to` (in order) wait for what the caller's stream s holds so far
+static int sf_exec_fork(sf_exec* ex, hipStream_t s, std::initializer_list<hipStream_t> to) {
+    hipEvent_t e;
+    SF_TRY(sf_exec_event(ex, &e));
+    SF_HIP(hipEventRecord(e, s));
+    for (hipStream_t t : to) SF_HIP(hipStreamWaitEvent(t, e, 0));
+    return SF_OK;
+}
+// join: the caller's stream s continues only after the chain stream c and the launches `also` (NULL: none) are done
+static int sf_exec_join(sf_exec* ex, hipStream_t s, hipStream_t c, std::initializer_list<hipEvent_t> also = {}) {
+    hipEvent_t e;
+    SF_TRY(sf_exec_event(ex, &e));
+    SF_HIP(hipEventRecord(e, c));
+    SF_HIP(hipStreamWaitEvent(s, e, 0));
+    for (hipEvent_t x : also)
+        if (x) SF_HIP(hipStreamWaitEvent(s, x, 0));
+    return SF_OK;
+}
 
 // Factor each n x n matrix in place (lower), panels of SF_NB columns:
 //   Ur  T[below] <- C[k1:, k0:k1] - L[k1:, :k0] L[k0:k1, :k0]^T   LEFT-looking for everything below the
@@ -2333,25 +2400,18 @@ size_t sf_potrf_work_doubles(int n, int batch) {
 // Lookahead (two streams): only the rows of the NEXT diagonal block are on the critical chain.
 //   side:  D(k) F(k) | wait Ur(k) | Gt(k) Rnext(k -> k+1) | D(k+1) ...
 //   main:  wait Gt(k-1) | Ur(k) | wait F(k) | Gr(k) Rrest(k) | ...
-static int sf_launch_potrf_v1(double* A, int n, int lda, int64_t stride, int batch, int* info, double* work,
-                              double* rhs, int ldr, hipStream_t s, const sf_gen_args* gen, sf_exec* ex) {
-    if (n % SF_LEAF != 0 || lda < n || batch <= 0 || (lda & 1) || !work) {
-        sf_set_error("potrf: n must be a positive multiple of %d, lda >= n and even, workspace required", SF_LEAF);
-        return SF_EINVAL;
-    }
-    double* T = work + (size_t)batch * SF_LTB_DOUBLES;
-    const int64_t sT = (int64_t)(n + SF_NB) * SF_LDT + SF_TSKEW;
-    double* Wt2 = T + (size_t)batch * sT;  // two W^T buffers, alternating by panel parity
-    const int64_t sW = (int64_t)SF_NB * SF_LDT + SF_TSKEW;
+static int sf_launch_potrf_v1(double* A, int n, int lda, int64_t stride, int* info, const sf_potrf_scratch& ws, double* rhs,
+                              int ldr, hipStream_t s, const sf_gen_args* gen, sf_exec* ex) {
+    const int batch = ws.batch;
+    double* T = ws.T;
+    const int64_t sT = ws.sT, sW = ws.sW;
     SF_HIP(hipMemsetAsync(info, 0, sizeof(int) * (size_t)batch, s));
 
     SF_TRY(sf_exec_prepare(ex));
     hipStream_t c = ex->side;  // side ("critical chain") stream
     auto next_event = [&](hipEvent_t* e) { return sf_exec_event(ex, e); };
-    hipEvent_t e_fork, e_gt_prev = nullptr;
-    SF_TRY(next_event(&e_fork));
-    SF_HIP(hipEventRecord(e_fork, s));
-    SF_HIP(hipStreamWaitEvent(c, e_fork, 0));
+    hipEvent_t e_gt_prev = nullptr;
+    SF_TRY(sf_exec_fork(ex, s, {c}));
 
     // R: right-looking update of `nblk` future diagonal blocks starting at row/col j0 with panel [k0,k1)
     auto launch_r = [&](int j0, int nrows, int k0, int pw, double* cout, int ldcout, int64_t scout,
@@ -2395,7 +2455,7 @@ static int sf_launch_potrf_v1(double* A, int n, int lda, int64_t stride, int bat
         const int pw = k1 - k0;
         const int nbelow = n - k1;
         const int ntop = nbelow < SF_NB ? nbelow : SF_NB;  // rows of the next diagonal block
-        double* Wt = Wt2 + (size_t)(panel & 1) * batch * sW;
+        double* Wt = ws.Wbuf(panel & 1);  // alternating by panel parity
         hipEvent_t e_ur = nullptr, e_f, e_gt;
         // ---- Ur on the main stream: rows [k1, n) -> T rows [2pw, ...)
         if (nbelow > 0) {
@@ -2413,13 +2473,8 @@ static int sf_launch_potrf_v1(double* A, int n, int lda, int64_t stride, int bat
             g.Nc = pw;
             g.K = k0;
             g.remap_after = 0x7fffffff;
+            sf_set_gen(g, gen, 0);  // (the unshifted frame)
             if (gen) {
-                g.genY = gen->Y;
-                g.sY = (int64_t)gen->mpad * gen->ldy;
-                g.ldy = gen->ldy;
-                g.mpad = gen->mpad;
-                g.tilemap = gen->tilemap;
-                g.nt128 = gen->nt128;
                 g.tm_off = k1 / GT;
                 g.tn_off = k0 / GT;
             }
@@ -2469,25 +2524,19 @@ static int sf_launch_potrf_v1(double* A, int n, int lda, int64_t stride, int bat
         }
     }
     // join: the caller's stream continues only after the side chain is done
-    hipEvent_t e_join;
-    SF_TRY(next_event(&e_join));
-    SF_HIP(hipEventRecord(e_join, c));
-    SF_HIP(hipStreamWaitEvent(s, e_join, 0));
+    SF_TRY(sf_exec_join(ex, s, c));
     return SF_OK;
 }
 
-// The fused sequences work in the frame of sf_potrf_front_pad: from here on A / rhs point fp (lda + 1) / fp elements before
-// the data and n counts the fp virtual leading rows too (the scratch layout above is sized with the real n).
-#define SF_SHIFT_FRAME()                                                              \
-    do {                                                                              \
-        if (fp != 0 && (fp != 64 || n % GT != 64)) {                                  \
-            sf_set_error("potrf: front pad %d does not fit n = %d", fp, n);           \
-            return SF_EINVAL;                                                         \
-        }                                                                             \
-        A -= (int64_t)fp * (lda + 1);                                                 \
-        if (rhs) rhs -= fp;                                                           \
-        n += fp;                                                                      \
-    } while (0)
+// The fused sequences work in the frame of sf_potrf_front_pad (sf_launch_potrf shifts it): A / rhs point fp (lda + 1) / fp
+// elements before the data and n counts the fp virtual leading rows too (the scratch layout is sized with the real n).
+static int sf_check_front_pad(int fp, int n) {
+    if (fp != 0 && (fp != 64 || n % GT != 64)) {
+        sf_set_error("potrf: front pad %d does not fit n = %d", fp, n);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
 static std::atomic<int> g_chol_sequence{-1};
 int sf_set_cholesky_sequence(int mode) {
     if (mode < -1 || mode > 4) {
@@ -2498,49 +2547,28 @@ int sf_set_cholesky_sequence(int mode) {
     return SF_OK;
 }
 
-// The fields of sf_panel_args that stay the same over one factorisation of the fused or the wide sequence (A, rhs and the
-// generator in the shifted frame fp)
-static sf_panel_args sf_panel_base(double* A, int n, int lda, int64_t stride, double* rhs, int ldr, const sf_gen_args* gen,
-                                   int fp, int64_t sW) {
-    sf_panel_args g = {};
-    g.C = A;
-    g.sC = stride;
-    g.lda = lda;
-    g.n = n;
-    g.sW = sW;
-    g.rhs = rhs;
-    g.ldr = ldr;
-    g.fp = fp;
-    if (gen) {
-        g.genY = gen->Y - fp;
-        g.sY = (int64_t)gen->mpad * gen->ldy;
-        g.ldy = gen->ldy;
-        g.mpad = gen->mpad;
-        g.tilemap = gen->tilemap;
-        g.nt128 = gen->nt128;
-    }
-    return g;
-}
 // split-K factor of a narrow step of nblk workgroups (1: not split)
 static int sf_panel_split(int k0, int pw, int fp, long long nblk) {
     return pw > 0 ? sf_split_policy(nblk, (k0 > fp ? k0 - fp : 0) / GK) : 1;
 }
 // One narrow step (k_chol_panel) of the fused and the wide sequence: panel [k0, k0 + pw) for nslab slabs of every matrix, the
-// first at row0, `step` slabs apart.  to_scratch: the chain's step -- the first slab's updated diagonal tile is parked in the
-// scratch T, the workgroups run at raised wave priority.  A split step parks its partial sums in region `region` of `part`;
-// phase 0 launches the whole step, 1 / 2 only the split-K partial sums / only what follows them.
-static int sf_panel_step(sf_panel_args g, int batch, double* T, int64_t sT, double* part, int k0, int pw, int row0, int nslab,
-                         int step, const double* Wt, bool to_scratch, hipStream_t st, int region, int phase) {
-    const int n = g.n, fp = g.fp;
+// first at row0, `step` slabs apart.  g: the fields that stay the same over the factorisation (sf_panel_frame).  to_scratch:
+// the chain's step -- the first slab's updated diagonal tile is parked in the scratch T, the workgroups run at raised wave
+// priority.  A split step parks its partial sums in region `region` of `part`; phase 0 launches the whole step, 1 / 2 only
+// the split-K partial sums / only what follows them.
+static int sf_panel_step(sf_panel_args g, const sf_potrf_scratch& ws, int k0, int pw, int row0, int nslab, int step, const double* Wt,
+                         bool to_scratch, hipStream_t st, int region, int phase) {
+    const int n = g.n, fp = g.fp, batch = ws.batch;
     g.k0 = k0;
     g.pw = pw;
     g.row0 = row0;
     g.nslab = nslab;
     g.slab_step = step;
     g.Wt = Wt;
+    g.sW = ws.sW;
     if (to_scratch) {
-        g.Sout = T;
-        g.sS = sT;
+        g.Sout = ws.T;
+        g.sS = ws.sT;
         g.ldS = SF_LDT;
         g.prio = 1;
     }
@@ -2563,7 +2591,7 @@ static int sf_panel_step(sf_panel_args g, int batch, double* T, int64_t sT, doub
     if (S > 1) {
         g.ksplit = S;
         g.kchunk = (nk + S - 1) / S;
-        g.part = part + (size_t)region * sf_split_region_tiles() * (GT * GT);
+        g.part = ws.part + (size_t)region * sf_split_region_tiles() * (GT * GT);
         if (phase != 2) {
             sf_prof_gemm_begin(st, flops_main, &tok);
             hipLaunchKernelGGL((k_chol_panel<false, 1>), dim3((unsigned)(nblk * S)), dim3(512), 0, st, g);
@@ -2598,45 +2626,33 @@ static int sf_panel_step(sf_panel_args g, int batch, double* T, int64_t sT, doub
 // group), so there is no chip-wide barrier between panels: while one group's launch drains its last
 // workgroups the other groups keep the CUs full (one launch per panel left 0.25-0.75 of a round of 512
 // workgroups idle at every panel boundary).
-static int sf_launch_potrf_v2(double* A, int n, int lda, int64_t stride, int batch, int* info, double* work,
-                              double* rhs, int ldr, hipStream_t s, const sf_gen_args* gen, sf_exec* ex, int fp) {
-    if (n % SF_LEAF != 0 || lda < n || batch <= 0 || (lda & 1) || !work) {
-        sf_set_error("potrf: n must be a positive multiple of %d, lda >= n and even, workspace required", SF_LEAF);
-        return SF_EINVAL;
-    }
-    double* T = work + (size_t)batch * SF_LTB_DOUBLES;
-    const int64_t sT = (int64_t)(n + SF_NB) * SF_LDT + SF_TSKEW;  // (layout shared with the unfused path)
-    double* Wt2 = T + (size_t)batch * sT;
-    const int64_t sW = (int64_t)SF_NB * SF_LDT + SF_TSKEW;
-    SF_SHIFT_FRAME();
+static int sf_launch_potrf_v2(double* A, int n, int lda, int64_t stride, int* info, const sf_potrf_scratch& ws, double* rhs,
+                              int ldr, hipStream_t s, const sf_gen_args* gen, sf_exec* ex, int fp) {
+    const int batch = ws.batch;
     SF_HIP(hipMemsetAsync(info, 0, sizeof(int) * (size_t)batch, s));
     SF_TRY(sf_exec_prepare(ex));
     constexpr int G = 2;  // slab groups: group 0 on the caller's stream, group 1 on grp[0]
     hipStream_t c = ex->side;
     const hipStream_t gs[G] = {s, ex->grp[0]};
-    hipEvent_t e_fork;
-    SF_TRY(sf_exec_event(ex, &e_fork));
-    SF_HIP(hipEventRecord(e_fork, s));
-    SF_HIP(hipStreamWaitEvent(c, e_fork, 0));
-    SF_HIP(hipStreamWaitEvent(gs[1], e_fork, 0));
+    SF_TRY(sf_exec_fork(ex, s, {c, gs[1]}));
 
-    const sf_panel_args base = sf_panel_base(A, n, lda, stride, rhs, ldr, gen, fp, sW);
-    double* part = Wt2 + 2 * (size_t)batch * sW + 64;  // split-K partial sums: region 0 = chain, 1 + g = group g
+    // (split-K partial sums in ws.part: region 0 = chain, 1 + g = group g)
+    const sf_panel_args base = sf_panel_frame<sf_panel_args>(A, n, lda, stride, rhs, ldr, gen, fp);
     const int nt = (n + GT - 1) / GT;
     // diagonal tile 0 goes to the scratch unchanged
-    SF_TRY(sf_panel_step(base, batch, T, sT, part, 0, 0, 0, 1, 1, nullptr, true, c, 0, 0));
+    SF_TRY(sf_panel_step(base, ws, 0, 0, 0, 1, 1, nullptr, true, c, 0, 0));
     hipEvent_t e_epi = nullptr;      // end of top(k-1) on the chain
     hipEvent_t e_rest[G] = {};       // last launch of every group
     hipEvent_t e_rest_prev[G] = {};  // ... one panel earlier (their readers of Wt[panel & 1])
     for (int k = 0; k < nt; ++k) {
         const int k0 = k * GT;
         const int pw = (n - k0 < GT) ? n - k0 : GT;
-        double* Wt = Wt2 + (size_t)(k & 1) * batch * sW;
+        double* Wt = ws.Wbuf(k & 1);
         // D(k) overwrites the W buffer of panel k-2: every group must be done reading it
         for (int g = 0; g < G; ++g)
             if (e_rest_prev[g]) SF_HIP(hipStreamWaitEvent(c, e_rest_prev[g], 0));
-        SF_TRY(sf_launch_diag128(T, sT, pw, info, k0 - fp, rhs ? rhs + k0 : nullptr, ldr, A + (int64_t)k0 * lda + k0, lda, stride, Wt, sW,
-                                 batch, c, k == 0 ? fp : 0));
+        SF_TRY(sf_launch_diag128(ws.T, ws.sT, pw, info, k0 - fp, rhs ? rhs + k0 : nullptr, ldr, A + (int64_t)k0 * lda + k0, lda, stride, Wt,
+                                 ws.sW, batch, c, k == 0 ? fp : 0));
         if (k + 1 >= nt) break;
         hipEvent_t e_d;
         SF_TRY(sf_exec_event(ex, &e_d));
@@ -2650,15 +2666,15 @@ static int sf_launch_potrf_v2(double* A, int n, int lda, int64_t stride, int bat
             hipEvent_t dep = e_rest[(k + 1) % G];
             if (sf_panel_split(k0, pw, fp, batch) > 1) {
                 if (e_epi) SF_HIP(hipStreamWaitEvent(gk, e_epi, 0));  // row k's columns of panel k-1; the partial-sum region
-                SF_TRY(sf_panel_step(base, batch, T, sT, part, k0, pw, (k + 1) * GT, 1, 1, Wt, true, gk, 0, 1));
+                SF_TRY(sf_panel_step(base, ws, k0, pw, (k + 1) * GT, 1, 1, Wt, true, gk, 0, 1));
                 hipEvent_t e_part;
                 SF_TRY(sf_exec_event(ex, &e_part));
                 SF_HIP(hipEventRecord(e_part, gk));
                 SF_HIP(hipStreamWaitEvent(c, e_part, 0));
-                SF_TRY(sf_panel_step(base, batch, T, sT, part, k0, pw, (k + 1) * GT, 1, 1, Wt, true, c, 0, 2));
+                SF_TRY(sf_panel_step(base, ws, k0, pw, (k + 1) * GT, 1, 1, Wt, true, c, 0, 2));
             } else {
                 if (dep) SF_HIP(hipStreamWaitEvent(c, dep, 0));
-                SF_TRY(sf_panel_step(base, batch, T, sT, part, k0, pw, (k + 1) * GT, 1, 1, Wt, true, c, 0, 0));
+                SF_TRY(sf_panel_step(base, ws, k0, pw, (k + 1) * GT, 1, 1, Wt, true, c, 0, 0));
             }
             SF_TRY(sf_exec_event(ex, &e_epi));
             SF_HIP(hipEventRecord(e_epi, c));
@@ -2671,17 +2687,13 @@ static int sf_launch_potrf_v2(double* A, int n, int lda, int64_t stride, int bat
             if (first >= nt) continue;
             const int cnt = (nt - 1 - first) / G + 1;
             SF_HIP(hipStreamWaitEvent(gs[g], e_d, 0));
-            SF_TRY(sf_panel_step(base, batch, T, sT, part, k0, pw, first * GT, cnt, G, Wt, false, gs[g], 1 + g, 0));
+            SF_TRY(sf_panel_step(base, ws, k0, pw, first * GT, cnt, G, Wt, false, gs[g], 1 + g, 0));
             SF_TRY(sf_exec_event(ex, &e_rest[g]));
             SF_HIP(hipEventRecord(e_rest[g], gs[g]));
         }
     }
     // join: the caller's stream continues only after the chain and every group are done
-    hipEvent_t e_join;
-    SF_TRY(sf_exec_event(ex, &e_join));
-    SF_HIP(hipEventRecord(e_join, c));
-    SF_HIP(hipStreamWaitEvent(s, e_join, 0));
-    if (e_rest[1]) SF_HIP(hipStreamWaitEvent(s, e_rest[1], 0));
+    SF_TRY(sf_exec_join(ex, s, c, {e_rest[1]}));
     return SF_OK;
 }
 
@@ -2694,25 +2706,11 @@ static int sf_launch_potrf_v2(double* A, int n, int lda, int64_t stride, int bat
 // A trailing single panel (odd number of panels) and pairs without rows below them are narrow steps of the chain.
 // The four most recent inverse tiles W(k) live in the two 256-row buffers of the narrow sequence (slot k & 3).
 // half (test aid, sequence 3): narrow steps from the middle on -- exercises the hand-over on any size.
-static int sf_launch_potrf_v3(double* A, int n, int lda, int64_t stride, int batch, int* info, double* work,
-                              double* rhs, int ldr, hipStream_t s, const sf_gen_args* gen, sf_exec* ex, bool half, int fp) {
-    if (n % SF_LEAF != 0 || lda < n || batch <= 0 || (lda & 1) || !work) {
-        sf_set_error("potrf: n must be a positive multiple of %d, lda >= n and even, workspace required", SF_LEAF);
-        return SF_EINVAL;
-    }
+static int sf_launch_potrf_v3(double* A, int n, int lda, int64_t stride, int* info, const sf_potrf_scratch& ws, double* rhs,
+                              int ldr, hipStream_t s, const sf_gen_args* gen, sf_exec* ex, bool half, int fp) {
+    const int batch = ws.batch;
     static sf_dev_once attr_once;
-    SF_CHECK(sf_once_per_device(&attr_once, []() -> int {
-        SF_HIP(hipFuncSetAttribute((const void*)k_chol_panel_w<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        SF_HIP(hipFuncSetAttribute((const void*)k_chol_panel_w<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        return SF_OK;
-    }));
-    double* T = work + (size_t)batch * SF_LTB_DOUBLES;
-    const int64_t sT = (int64_t)(n + SF_NB) * SF_LDT + SF_TSKEW;
-    double* Wt2 = T + (size_t)batch * sT;
-    const int64_t sW = (int64_t)SF_NB * SF_LDT + SF_TSKEW;
-    auto Wslot = [&](int k) { return Wt2 + (size_t)((k >> 1) & 1) * batch * sW + (size_t)(k & 1) * GT * SF_LDT; };
-    double* part = Wt2 + 2 * (size_t)batch * sW + 64;
-    SF_SHIFT_FRAME();
+    SF_CHECK(sf_lds_limit_once(&attr_once, 160 * 1024, {(const void*)k_chol_panel_w<true>, (const void*)k_chol_panel_w<false>}));
     SF_HIP(hipMemsetAsync(info, 0, sizeof(int) * (size_t)batch, s));
     SF_TRY(sf_exec_prepare(ex));
     // A(p) sits between chain(p) and chain(p+1) anyway: it shares the chain's stream.  A stream of its own made a cfg-2
@@ -2720,15 +2718,11 @@ static int sf_launch_potrf_v3(double* A, int n, int lda, int64_t stride, int bat
     // transform chain ahead of the factorisation went from 0.40 to 0.70 ms); at cfg 3, where an A launch is ten rounds of
     // workgroups, a separate stream measured the same (265.1 / 267.0 vs 266.8 / 265.8 ms).
     hipStream_t c = ex->side, xa = ex->side;
-    hipEvent_t e_fork;
-    SF_TRY(sf_exec_event(ex, &e_fork));
-    SF_HIP(hipEventRecord(e_fork, s));
-    SF_HIP(hipStreamWaitEvent(c, e_fork, 0));
-    SF_HIP(hipStreamWaitEvent(xa, e_fork, 0));
-    SF_HIP(hipStreamWaitEvent(ex->grp[0], e_fork, 0));
+    SF_TRY(sf_exec_fork(ex, s, {c, xa, ex->grp[0]}));
     const int nt = (n + GT - 1) / GT;
 
-    const sf_panel_args base = sf_panel_base(A, n, lda, stride, rhs, ldr, gen, fp, sW);
+    const sf_panel_args base = sf_panel_frame<sf_panel_args>(A, n, lda, stride, rhs, ldr, gen, fp);
+    const sf_panelw_args wbase = sf_panel_frame<sf_panelw_args>(A, n, lda, stride, rhs, ldr, gen, fp);
 #ifdef SF_TUNING
     long long* wstamps = nullptr;
     int wstamp_n = 0, wstamp_k[64];
@@ -2738,33 +2732,18 @@ static int sf_launch_potrf_v3(double* A, int n, int lda, int64_t stride, int bat
     }
 #endif
     auto wide = [&](int k, int slab0, int nslab, int step, bool park, hipStream_t st) -> int {
-        sf_panelw_args g = {};
-        g.C = A;
-        g.sC = stride;
-        g.lda = lda;
-        g.n = n;
+        sf_panelw_args g = wbase;
         g.k0 = k * GT;
         g.row0 = slab0 * GT;
         g.nslab = nslab;
         g.slab_step = step;
-        g.Wt0 = Wslot(k);
-        g.Wt1 = Wslot(k + 1);
-        g.sW = sW;
-        g.rhs = rhs;
-        g.ldr = ldr;
+        g.Wt0 = ws.Wslot(k);
+        g.Wt1 = ws.Wslot(k + 1);
+        g.sW = ws.sW;
         if (park) {
-            g.Sout = T;
-            g.sS = sT;
+            g.Sout = ws.T;
+            g.sS = ws.sT;
             g.ldS = SF_LDT;
-        }
-        g.fp = fp;
-        if (gen) {
-            g.genY = gen->Y - fp;
-            g.sY = (int64_t)gen->mpad * gen->ldy;
-            g.ldy = gen->ldy;
-            g.mpad = gen->mpad;
-            g.tilemap = gen->tilemap;
-            g.nt128 = gen->nt128;
         }
         const long long nblk = (long long)nslab * batch;
         if (nblk > 0x7fffffffLL) {
@@ -2796,11 +2775,11 @@ static int sf_launch_potrf_v3(double* A, int n, int lda, int64_t stride, int bat
     auto diag = [&](int k) -> int {
         const int k0 = k * GT;
         const int pw = (n - k0 < GT) ? n - k0 : GT;
-        return sf_launch_diag128(T, sT, pw, info, k0 - fp, rhs ? rhs + k0 : nullptr, ldr, A + (int64_t)k0 * lda + k0, lda, stride, Wslot(k), sW,
-                                 batch, c, k == 0 ? fp : 0);
+        return sf_launch_diag128(ws.T, ws.sT, pw, info, k0 - fp, rhs ? rhs + k0 : nullptr, ldr, A + (int64_t)k0 * lda + k0, lda, stride,
+                                 ws.Wslot(k), ws.sW, batch, c, k == 0 ? fp : 0);
     };
 
-    SF_TRY(sf_panel_step(base, batch, T, sT, part, 0, 0, 0, 1, 1, nullptr, true, c, 0, 0));  // diagonal tile 0 goes to the scratch unchanged
+    SF_TRY(sf_panel_step(base, ws, 0, 0, 0, 1, 1, nullptr, true, c, 0, 0));  // diagonal tile 0 goes to the scratch unchanged
     // B(p) runs as two interleaved slab groups on two streams (like the narrow sequence): a group's next launch only
     // needs its own previous one, so the last, partly filled round of one group overlaps the other group's work.
     // Group g = slabs of parity g (k even: k+4+g, k+6+g, ...), in the wide pairs and in the narrow tail alike.
@@ -2834,14 +2813,14 @@ static int sf_launch_potrf_v3(double* A, int n, int lda, int64_t stride, int bat
         SF_HIP(hipEventRecord(e_d, c));
         // top(k): the slab of the next diagonal tile, on the chain; its rows were finished by the group of its parity
         if (e_last[(k + 1) & 1]) SF_HIP(hipStreamWaitEvent(c, e_last[(k + 1) & 1], 0));
-        SF_TRY(sf_panel_step(base, batch, T, sT, part, k0, pw, (k + 1) * GT, 1, 1, Wslot(k), true, c, 0, 0));
+        SF_TRY(sf_panel_step(base, ws, k0, pw, (k + 1) * GT, 1, 1, ws.Wslot(k), true, c, 0, 0));
         for (int g = 0; g < 2; ++g) {
             int first = k + 2;
             if ((first & 1) != g) ++first;
             if (first >= nt) continue;
             const int cnt = (nt - 1 - first) / 2 + 1;
             SF_HIP(hipStreamWaitEvent(bs[g], e_d, 0));
-            SF_TRY(sf_panel_step(base, batch, T, sT, part, k0, pw, first * GT, cnt, 2, Wslot(k), false, bs[g], 1 + g, 0));
+            SF_TRY(sf_panel_step(base, ws, k0, pw, first * GT, cnt, 2, ws.Wslot(k), false, bs[g], 1 + g, 0));
             SF_TRY(sf_exec_event(ex, &e_last[g]));
             SF_HIP(hipEventRecord(e_last[g], bs[g]));
             readers[k & 3].push_back(e_last[g]);
@@ -2856,7 +2835,7 @@ static int sf_launch_potrf_v3(double* A, int n, int lda, int64_t stride, int bat
         if (e_A) SF_HIP(hipStreamWaitEvent(c, e_A, 0));
         SF_TRY(wait_readers(k & 3));
         SF_TRY(diag(k));
-        SF_TRY(sf_panel_step(base, batch, T, sT, part, k * GT, GT, (k + 1) * GT, 1, 1, Wslot(k), true, c, 0, 0));  // (rows below the pair exist: panel k is full)
+        SF_TRY(sf_panel_step(base, ws, k * GT, GT, (k + 1) * GT, 1, 1, ws.Wslot(k), true, c, 0, 0));  // (rows below the pair exist: panel k is full)
         SF_TRY(wait_readers((k + 1) & 3));
         SF_TRY(diag(k + 1));
         hipEvent_t e_chain;
@@ -2887,12 +2866,7 @@ static int sf_launch_potrf_v3(double* A, int n, int lda, int64_t stride, int bat
     }
     // narrow tail (also: a trailing single panel, pairs without rows below them)
     for (; k < nt; ++k) SF_TRY(narrow_step(k));
-    hipEvent_t e_join;
-    SF_TRY(sf_exec_event(ex, &e_join));
-    SF_HIP(hipEventRecord(e_join, c));
-    SF_HIP(hipStreamWaitEvent(s, e_join, 0));
-    if (e_A) SF_HIP(hipStreamWaitEvent(s, e_A, 0));
-    if (e_last[1]) SF_HIP(hipStreamWaitEvent(s, e_last[1], 0));
+    SF_TRY(sf_exec_join(ex, s, c, {e_A, e_last[1]}));
 #ifdef SF_TUNING
     if (wstamps) {  // (synchronises: phases of one workgroup per wide launch, us)
         (void)hipStreamSynchronize(s);
@@ -2983,10 +2957,7 @@ int sf_launch_potrf_band(int n, int nband, int halfwidth, int batch, const doubl
                        nband, A, sA, lda);
     SF_LAUNCH_CHECK();
 
-    double* T = work + (size_t)batch * SF_LTB_DOUBLES;
-    const int64_t sT = (int64_t)(next + SF_NB) * SF_LDT + SF_TSKEW;
-    double* Wt = T + (size_t)batch * sT;
-    const int64_t sW = (int64_t)SF_NB * SF_LDT + SF_TSKEW;
+    const sf_potrf_scratch ws = sf_potrf_scratch_of(work, next, batch);  // (one W buffer is used)
     // (info is NOT cleared here: the band fill may have flagged a half-width that is too small; a non-zero entry stays)
     // One stream, two launches per panel: the launches are short (a few slabs, K <= halfwidth + 128), so the
     // lookahead of the dense sequence has nothing to hide behind -- measured with the chain on a side stream:
@@ -3002,14 +2973,14 @@ int sf_launch_potrf_band(int n, int nband, int halfwidth, int batch, const doubl
         g.row0 = row0;
         g.nslab = nslab + (border ? 1 : 0);
         g.slab_step = 1;
-        g.Wt = Wt;
-        g.sW = sW;
+        g.Wt = ws.W;
+        g.sW = ws.sW;
         g.kband = halfwidth > 0 ? halfwidth : 1;
         g.nband = nband;
         g.xrow0 = border ? nband : 0;
         if (nslab > 0) {  // the first slab is the next diagonal tile: its update is parked in the scratch for D(k+1)
-            g.Sout = T;
-            g.sS = sT;
+            g.Sout = ws.T;
+            g.sS = ws.sT;
             g.ldS = SF_LDT;
         }
         const long long nblk = (long long)g.nslab * batch;
@@ -3025,7 +2996,7 @@ int sf_launch_potrf_band(int n, int nband, int halfwidth, int batch, const doubl
     for (int k = 0; k < nt; ++k) {
         const int k0 = k * GT;
         const int pw = (nband - k0 < GT) ? nband - k0 : GT;
-        SF_TRY(sf_launch_diag128(T, sT, pw, info, k0, nullptr, 0, A + (int64_t)k0 * lda + k0, lda, sA, Wt, sW, batch, s));
+        SF_TRY(sf_launch_diag128(ws.T, ws.sT, pw, info, k0, nullptr, 0, A + (int64_t)k0 * lda + k0, lda, sA, ws.W, ws.sW, batch, s));
         // the slabs k+1 .. k+wt that meet the band, and the border
         const int last = (k + wt < nt - 1) ? k + wt : nt - 1;
         SF_TRY(launch_panel(k0, pw, (k + 1) * GT, last - k, true));
@@ -3709,32 +3680,19 @@ int sf_persistent_potrf_read_status(long long* out8) {
     return SF_OK;
 }
 
-static int sf_launch_potrf_v4(double* A, int n, int lda, int64_t stride, int batch, int* info, double* work,
-                              double* rhs, int ldr, hipStream_t s, const sf_gen_args* gen, int fp) {
-    if (n % SF_LEAF != 0 || lda < n || batch <= 0 || (lda & 1) || !work) {
-        sf_set_error("potrf: n must be a positive multiple of %d, lda >= n and even, workspace required", SF_LEAF);
-        return SF_EINVAL;
-    }
+static int sf_launch_potrf_v4(double* A, int n, int lda, int64_t stride, int* info, const sf_potrf_scratch& ws, double* rhs,
+                              int ldr, hipStream_t s, const sf_gen_args* gen, int fp) {
+    const int batch = ws.batch;
     static sf_dev_once attr_once;
-    SF_CHECK(sf_once_per_device(&attr_once, []() -> int {
-        SF_HIP(hipFuncSetAttribute((const void*)k_potrf_dataflow<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SF_DF_LDS_BYTES));
-        SF_HIP(hipFuncSetAttribute((const void*)k_potrf_dataflow<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SF_DF_LDS_BYTES));
-        return SF_OK;
-    }));
-    double* T = work + (size_t)batch * SF_LTB_DOUBLES;
-    const int64_t sT = (int64_t)(n + SF_NB) * SF_LDT + SF_TSKEW;  // parked tile + one inverse tile per panel: (n + 64 + 128) rows
-    double* Wt2 = T + (size_t)batch * sT;
-    const int64_t sW = (int64_t)SF_NB * SF_LDT + SF_TSKEW;
-    double* part = Wt2 + 2 * (size_t)batch * sW + 64;
-    SF_SHIFT_FRAME();
+    SF_CHECK(sf_lds_limit_once(&attr_once, (int)SF_DF_LDS_BYTES, {(const void*)k_potrf_dataflow<true>, (const void*)k_potrf_dataflow<false>}));
     const int nt = (n + GT - 1) / GT;
     // counters: in the two inverse-tile buffers of the launch sequences (2 x batch x sW doubles), which this sequence does not use
-    int* flags = (int*)Wt2;
+    int* flags = (int*)ws.W;
     const size_t ndbg = 2 * (16 * SF_CHIP_WGS + 16 * 64 + 8 * 64);
     const size_t nflags = 64 + (size_t)batch * (3 * nt + 2 + 3 * SF_DF_FRONT_MAX) + (size_t)SF_DF_QUEUES * nt + 8 + ndbg;
     // (region 2 of `part` holds 2 x front x batch x pt_cap tiles with pt_cap >= 1: batches beyond what it holds at the widest
     // front are refused here -- the automatic choice stops at 128 matrices, a forced sequence 4 falls back in sf_launch_potrf)
-    if (nt - 1 > SF_DF_MAX_STAGES || nflags * sizeof(int) > 2 * (size_t)batch * sW * sizeof(double) ||
+    if (nt - 1 > SF_DF_MAX_STAGES || nflags * sizeof(int) > ws.Wdoubles() * sizeof(double) ||
         2 * (size_t)SF_DF_FRONT_WIDEST * batch > sf_split_region_tiles()) {
         sf_set_error("potrf: dataflow sequence: %d panels / %d matrices do not fit its tables", nt, batch);
         return SF_EINVAL;
@@ -3766,24 +3724,9 @@ static int sf_launch_potrf_v4(double* A, int n, int lda, int64_t stride, int bat
     a.miss_claims = SF_TUNE_INT("SF_DF_MISS_CLAIMS", 0);
 #endif
 
-    sf_panel_args& g = a.p;
-    g.C = A;
-    g.sC = stride;
-    g.lda = lda;
-    g.n = n;
-    g.rhs = rhs;
-    g.ldr = ldr;
-    g.fp = fp;
-    g.sS = sT;  // (the parked diagonal tile of matrix b: T + b sT, row stride SF_LDT)
-    g.ldS = SF_LDT;
-    if (gen) {
-        g.genY = gen->Y - fp;
-        g.sY = (int64_t)gen->mpad * gen->ldy;
-        g.ldy = gen->ldy;
-        g.mpad = gen->mpad;
-        g.tilemap = gen->tilemap;
-        g.nt128 = gen->nt128;
-    }
+    a.p = sf_panel_frame<sf_panel_args>(A, n, lda, stride, rhs, ldr, gen, fp);
+    a.p.sS = ws.sT;  // (the parked diagonal tile of matrix b: T + b sT, row stride SF_LDT)
+    a.p.ldS = SF_LDT;
     // front width: the rows the chain needs next must be a reduce-and-epilogue behind it, and the first ORDINARY slab of a
     // stage (a long-K task, or partial sums + reduce) gets `front` chain periods before the front needs its row.  Front tasks
     // cost more than ordinary ones (partial sums written and read back).  N = 4096, front 1 / 2 / 3 / 4 / 6: B = 16 8.1 / 8.0 /
@@ -3808,9 +3751,9 @@ static int sf_launch_potrf_v4(double* A, int n, int lda, int64_t stride, int bat
     a.fp_pos = 256;  // (0 / 64 / 128 / 192 / 256: B = 16 7.75 / 7.7 / 7.6 / 7.7 / 7.55 ms, B = 32 13.8 / 13.9 / 13.75 / 13.7 / 13.65)
     a.nt = nt;
     a.batch = batch;
-    a.T = T;
-    a.sT = sT;
-    a.part = part;
+    a.T = ws.T;
+    a.sT = ws.sT;
+    a.part = ws.part;
     a.info = info;
     a.diag = sf_df_diag();
     a.qbal = 1;
@@ -4058,14 +4001,24 @@ int sf_potrf_front_pad(int n, int batch) {
 
 int sf_launch_potrf(double* A, int n, int lda, int64_t stride, int batch, int* info, double* work,
                     double* rhs, int ldr, hipStream_t s, const sf_gen_args* gen, sf_exec* ex) {
+    if (n % SF_LEAF != 0 || lda < n || batch <= 0 || (lda & 1) || !work) {
+        sf_set_error("potrf: n must be a positive multiple of %d, lda >= n and even, workspace required", SF_LEAF);
+        return SF_EINVAL;
+    }
+    const sf_potrf_scratch ws = sf_potrf_scratch_of(work, n, batch);
     const int seq = sf_potrf_pick(n, batch);
     if (!ex) ex = sf_exec_thread_local();
     // frame of the fused sequences: the caller's (whose tile map was built in it) or this call's own
     const int fp = gen ? gen->fp : sf_potrf_front_pad(n, batch);
-    if (seq == 4) return sf_launch_potrf_v4(A, n, lda, stride, batch, info, work, rhs, ldr, s, gen, fp);
-    if (seq == 2 || seq == 3) return sf_launch_potrf_v3(A, n, lda, stride, batch, info, work, rhs, ldr, s, gen, ex, seq == 3, fp);
-    if (seq == 1 && fp == 0) return sf_launch_potrf_v1(A, n, lda, stride, batch, info, work, rhs, ldr, s, gen, ex);
-    return sf_launch_potrf_v2(A, n, lda, stride, batch, info, work, rhs, ldr, s, gen, ex, fp);
+    if (seq == 1 && fp == 0) return sf_launch_potrf_v1(A, n, lda, stride, info, ws, rhs, ldr, s, gen, ex);
+    // the other sequences work in that frame
+    SF_CHECK(sf_check_front_pad(fp, n));
+    A -= (int64_t)fp * (lda + 1);
+    if (rhs) rhs -= fp;
+    n += fp;
+    if (seq == 4) return sf_launch_potrf_v4(A, n, lda, stride, info, ws, rhs, ldr, s, gen, fp);
+    if (seq == 2 || seq == 3) return sf_launch_potrf_v3(A, n, lda, stride, info, ws, rhs, ldr, s, gen, ex, seq == 3, fp);
+    return sf_launch_potrf_v2(A, n, lda, stride, info, ws, rhs, ldr, s, gen, ex, fp);
 }
 
 int sf_launch_logdet_sqmah(const double* L, int n, int lda, int64_t stride, int batch, const double* R,
@@ -4078,11 +4031,7 @@ int sf_launch_logdet_sqmah(const double* L, int n, int lda, int64_t stride, int 
     const size_t with_z = fixed + sizeof(double) * (size_t)n;
     if (with_z <= 160 * 1024) {
         static sf_dev_once attr_once;  // devices whose function attributes are set
-        SF_CHECK(sf_once_per_device(&attr_once, []() -> int {
-            SF_HIP(hipFuncSetAttribute((const void*)k_trsv_logdet<false>,
-            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            return SF_OK;
-        }));
+        SF_CHECK(sf_lds_limit_once(&attr_once, 160 * 1024, {(const void*)k_trsv_logdet<false>}));
         hipLaunchKernelGGL(k_trsv_logdet<false>, dim3(batch), dim3(256), with_z, s, L, n, lda, stride, R,
                            ldr, (double*)nullptr, logdet, sqmah);
     } else {

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdlib.h>
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 #include "../../include/starfish_amd.h"
 
@@ -57,6 +58,13 @@ static inline int sf_once_per_device(sf_dev_once* once, F&& setup) {
     const int rc = setup();
     if (rc == SF_OK) once->done.fetch_or(bit, std::memory_order_release);
     return rc;
+}
+// the usual set-up: raise the dynamic LDS limit of `kernels` (in order) to `bytes`
+static inline int sf_lds_limit_once(sf_dev_once* once, int bytes, std::initializer_list<const void*> kernels) {
+    return sf_once_per_device(once, [&]() -> int {
+        for (const void* k : kernels) SF_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        return SF_OK;
+    });
 }
 #define SF_CHECK(expr)              \
     do {                            \

@@ -1065,13 +1065,7 @@ static int launch_broaden_t(const sf_broaden_args& a, hipStream_t s) {
     dim3 grid(a.rows, a.B);
     if (lds) {
         static sf_dev_once attr_once;  // devices whose function attributes are set
-        SF_CHECK(sf_once_per_device(&attr_once, []() -> int {
-            SF_HIP(hipFuncSetAttribute((const void*)k_broaden<true, true>,
-            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            SF_HIP(hipFuncSetAttribute((const void*)k_broaden<false, true>,
-            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            return SF_OK;
-        }));
+        SF_CHECK(sf_lds_limit_once(&attr_once, 160 * 1024, {(const void*)k_broaden<true, true>, (const void*)k_broaden<false, true>}));
         hipLaunchKernelGGL((k_broaden<FWD, true>), grid, dim3(256), shm, s, a.in, a.spec, a.rows, a.nf, a.tw,
                            a.dv, a.kind, a.params, a.pstride, a.poff, a.scalar_param, a.out, a.ob, a.orow,
                            a.oelem, (double2*)nullptr, a.info);
@@ -1098,11 +1092,7 @@ static int launch_broaden_half(const sf_broaden_args& a, hipStream_t s) {
     dim3 grid(a.rows, a.B);
     if (lds) {
         static sf_dev_once attr_once;  // devices whose function attributes are set
-        SF_CHECK(sf_once_per_device(&attr_once, []() -> int {
-            SF_HIP(hipFuncSetAttribute((const void*)k_broaden_half<true>,
-            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            return SF_OK;
-        }));
+        SF_CHECK(sf_lds_limit_once(&attr_once, 160 * 1024, {(const void*)k_broaden_half<true>}));
         hipLaunchKernelGGL(k_broaden_half<true>, grid, dim3(256), sizeof(double2) * (size_t)(a.nf / 2), s, a.spec,
                            a.mult, a.rows, a.nf, a.tw, a.kind, a.params, a.pstride, a.poff, a.scalar_param, a.out,
                            a.ob, a.orow, a.oelem, (double2*)nullptr);
@@ -1132,11 +1122,7 @@ int sf_launch_rfft_rows(const double* in, int rows, int nf, const double2* tw, d
     const bool lds = (size_t)nf <= kLdsFftMax;
     if (lds) {
         static sf_dev_once attr_once;  // devices whose function attributes are set
-        SF_CHECK(sf_once_per_device(&attr_once, []() -> int {
-            SF_HIP(hipFuncSetAttribute((const void*)k_rfft_rows<true>,
-            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            return SF_OK;
-        }));
+        SF_CHECK(sf_lds_limit_once(&attr_once, 160 * 1024, {(const void*)k_rfft_rows<true>}));
         hipLaunchKernelGGL(k_rfft_rows<true>, dim3(rows), dim3(256), sizeof(double2) * (size_t)nf, s, in, nf, tw,
                            spec, (double2*)nullptr);
     } else {

@@ -180,6 +180,28 @@ def test_c_abi_library_loads_and_exports_every_declared_symbol():
     assert lib.sf_version().startswith(b"starfish_amd")
 
 
+# sf_potrf_workspace_bytes(n, batch) for batch = 1, 16, 64, 128: the factorisation's scratch layout, byte for byte (its
+# sizing and the launchers' carving are one function; a change to either moves these numbers)
+POTRF_WORKSPACE_BYTES = {
+    64: [404499200, 432176896, 520745728, 638837504],
+    128: [404638976, 434413312, 529691392, 656728832],
+    3008: [410928896, 535052032, 932246272, 1461838592],
+    3072: [411068672, 537288448, 941191936, 1479729920],
+    4096: [413305088, 573071104, 1084322560, 1765991168],
+    16384: [440142080, 1002462976, 2801890048, 5201126144],
+    33024: [476483840, 1583931136, 5127762688, 9852871424],
+}
+
+
+def test_potrf_workspace_bytes_are_pinned():
+    from starfish_amd import _lib
+
+    lib = _lib.load()  # loading needs no GPU
+    for n, want in POTRF_WORKSPACE_BYTES.items():
+        got = [lib.sf_potrf_workspace_bytes(n, b) for b in (1, 16, 64, 128)]
+        assert got == want, (n, got, want)
+
+
 def test_product_fails_loudly_without_gpu():
     import torch
 
