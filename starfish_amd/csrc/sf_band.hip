@@ -39,6 +39,7 @@
 // is left of a (W rounded up to 16)-row separator, k_band_merge adds the two Schur contributions and a
 // short third sweep finishes the separator: 0.74 ms.
 #include "sf_common.h"
+#include "sf_device.h"
 #include <type_traits>
 
 #define BB 16
@@ -79,23 +80,6 @@ struct sf_band_args {
     double* dumpG;             // [batch][2][nrhs*nrhs] partial Gram matrices
     double* dumpL;             // [batch][2]          partial log-determinants
 };
-
-__device__ __forceinline__ double sfb_readlane(double v, int lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
-// 1/sqrt(p): hardware estimate + two Newton steps (full double precision for p > 0)
-__device__ __forceinline__ double sfb_rsqrt(double p) {
-    double y = __builtin_amdgcn_rsq(p);
-    const double h = 0.5 * p;
-    double e = __builtin_fma(-h * y, y, 0.5);
-    y = __builtin_fma(y, e, y);
-    e = __builtin_fma(-h * y, y, 0.5);
-    y = __builtin_fma(y, e, y);
-    return y;
-}
 
 // Workgroup barrier for LDS data only: the HBM prefetch loads stay in flight across it (the compiler
 // waits for them where their registers are first used).
@@ -183,11 +167,9 @@ __global__ __launch_bounds__(1024) void k_band_forms(sf_band_args a) {
     if (tid < 16) sync[tid] = 0;
 
     const int l15 = lane & 15, lq = lane >> 4;
-    // Wave 0: Cholesky of the 16 x 16 diagonal block AND the inverse of its factor, both kept in the
-    // MFMA accumulator layout (lane (lq, l15), register r <-> element (lq + 4r, l15)).  Column j of the
-    // symmetric block is also its row j = register j/4 of the 16 lanes of quarter j%4, which is exactly
-    // where a K-slice of the MFMA operands lives: the rank-1 elimination  A -= v v^T  and the update of
-    // F = L^-1 (F -= v g^T) are one v_mfma_f64_16x16x4_f64 each, with no data movement at all.
+    // Wave 0: Cholesky of the 16 x 16 diagonal block AND the inverse of its factor in the MFMA accumulator layout: the
+    // step of SF_POTRF16_ACC (sf_device.h, explained there) without L^T and with the identity set in the load loop.
+    // Its own copy: written with the macro the sweep compiles to another instruction order.
     int bad = 0;
     auto potrf16 = [&](int kb, int ks) {  // ks = kb % nbr
         const double* D = Wb + sfb_pair(ks, ks) * BS;
@@ -198,22 +180,20 @@ __global__ __launch_bounds__(1024) void k_band_forms(sf_band_args a) {
             acc[r] = D[max(row, l15) * BLD + min(row, l15)];  // only the lower triangle is maintained
             f[r] = row == l15 ? 1.0 : 0.0;
         }
-        double p = sfb_readlane(acc[0], 0);
+        double p = sf_readlane_d(acc[0], 0);
         double pkeep = 1.0;  // lane j keeps pivot j: one LDS store and one sign test after the loop
 #pragma unroll
         for (int j = 0; j < BB; ++j) {
             const int qj = j & 3, rj = j >> 2;
             pkeep = lane == j ? p : pkeep;
-            const double rs = sfb_rsqrt(p);
+            const double rs = sf_rsqrt(p);
             const bool in_q = lq == qj;
             const double v = (in_q && l15 > j) ? acc[rj] * rs : 0.0;  // l_ij, i = l15 > j
             const double g = in_q ? f[rj] * rs : 0.0;                 // row j of F, scaled
             if (in_q) f[rj] = g;
             if (j + 1 < BB) {
-                // next pivot a_{j+1,j+1} - l_{j+1,j}^2 from scalars, so that its rsqrt chain runs while
-                // the matrix core applies this column's rank-1 update
-                const double an = sfb_readlane(acc[(j + 1) >> 2], ((j + 1) & 3) * 16 + j + 1);
-                const double vn = sfb_readlane(v, qj * 16 + j + 1);
+                const double an = sf_readlane_d(acc[(j + 1) >> 2], ((j + 1) & 3) * 16 + j + 1);
+                const double vn = sf_readlane_d(v, qj * 16 + j + 1);
                 p = __builtin_fma(-vn, vn, an);
             }
             acc = __builtin_amdgcn_mfma_f64_16x16x4f64(v, v, acc, 0, 0, 1);  // blgp = neg:[1,0,0]: -A B + C

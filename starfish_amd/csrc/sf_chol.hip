@@ -3,18 +3,35 @@
 // Replaces the LAPACK calls of the reference: scipy.linalg.cho_factor / cho_solve at
 // Starfish/models/spectrum_model.py:400-404 (dpotrf + dpotrs on the N x N covariance).
 //
-// Structure (one launch sequence serves the whole batch; the batch supplies the parallelism):
-//   default (>= 28 matrices): LEFT-looking panels of 128 columns with the FUSED panel kernel k_chol_panel -- one
-//     workgroup per 128-row slab does the long-K update (v_mfma_f64_16x16x4_f64, > 80 % of the flops), the
-//     triangular solve against the explicit inverse of the diagonal tile, the in-place store of L, the forward
-//     substitution of the right-hand side and the rank-128 update of its own diagonal tile; k_diag_mfma factors
-//     the 128 x 128 diagonal tile (L_kk, L_kk^-1, z_k) on a side stream one panel ahead (lookahead); launches
-//     that cannot fill the chip are split along K (partial sums + deterministic reduce).  sf_launch_potrf_v2.
-//   small batches: the unfused sequence of round 1 (panels of SF_NB = 256 columns; k_gemm_nt long-K update into a
-//     panel scratch, k_diag_mfma on 256 x 256 blocks, separate panel-solve and diagonal-update launches): half as
-//     many sequential long-K steps.  sf_launch_potrf_v1.
-//   k_logdet_z: logdet = 2 sum log L_ii and sqmah = |z|^2 (z = L^-1 R is produced inside the factorisation);
-//   k_trsv_logdet: the stand-alone forward substitution of sf_logdet_sqmah_batch.
+// One launch sequence serves the whole batch (the batch supplies the parallelism).  sf_potrf_pick chooses among four
+// (numbers and measurements: DESIGN.md section 3; sf_debug_cholesky_sequence forces one):
+//   4  dataflow: the whole factorisation as ONE persistent launch, k_potrf_dataflow, whose workgroups draw tasks (the
+//      bodies of the panel step and of the diagonal tile) ordered by counters -- while batch x panels <= 2048, up to 128
+//      matrices and 65 panels, unless the persistent kernel has been switched off.  sf_launch_potrf_v4.
+//   2  wide: a PAIR of 128-column panels per launch, k_chol_panel_w (one 16-wave workgroup per CU keeps a 128 x 256
+//      tile), with narrow steps for the chain -- from batch x slabs >= 3400 at n >= 2048.  sf_launch_potrf_v3.
+//   0  fused: LEFT-looking panels of 128 columns, k_chol_panel -- one workgroup per 128-row slab does the long-K update,
+//      the triangular solve against the explicit inverse of the diagonal tile, the in-place store of L, the forward
+//      substitution of the right-hand side and the update of its own diagonal tile; k_diag_lds factors the diagonal
+//      tile (L_kk, L_kk^-1, z_k) on the side stream; launches that cannot fill the chip are split along K -- every
+//      other batch of 16 matrices or more.  sf_launch_potrf_v2.
+//   1  unfused (round 1): panels of SF_NB = 256 columns, k_gemm_nt into a panel scratch, k_diag_mfma on 256 x 256
+//      blocks, separate solve and diagonal-update launches -- below 16 matrices while the persistent kernel is
+//      switched off.  sf_launch_potrf_v1.
+// sf_launch_potrf_band runs bordered band matrices on the fused kernels.  k_logdet_z: logdet = 2 sum log L_ii and
+// sqmah = |z|^2 (z = L^-1 R is produced inside the factorisation); k_trsv_logdet: the stand-alone forward substitution.
+//
+// ONE translation unit; layers are headers, included in dependency order (a later one may use an earlier one):
+//   sf_device.h          lane / wave helpers, XCD remap, the 16 x 16 factor step (shared with the other .hip files)
+//   sf_chol_tile.h       tile constants
+//   sf_chol_host.h       scratch layout, split-K policy, frame helpers, fork / join: what every launcher shares
+//   sf_chol_unfused.h    everything only sequence 1 uses
+//   sf_chol_diag.h       the diagonal tile in LDS: sf_diag_lds_body, k_diag_lds
+//   sf_chol_sync.h       counters, waits, watch and rescue of the persistent kernel
+//   sf_chol_solve.h      k_logdet_z, k_trsv_logdet, the clock probe
+// Still in this file, in this order: the panel step (k_chol_panel), the wide step (k_chol_panel_w), the narrow-step
+// launcher with the fused and wide sequences, the band driver, the persistent kernel with sf_launch_potrf_v4, the choice
+// of the sequence.
 #include <atomic>
 #include <cstdlib>
 #include <type_traits>
@@ -22,966 +39,19 @@
 
 #include "sf_common.h"
 #include <stdio.h>
-
-#define GT 128  // C tile edge of the MFMA kernel
-#define GK 16   // K slab staged in LDS per step
-#define GLD 17  // LDS row stride (doubles), odd: the 16 rows of a fragment hit 16 distinct bank pairs for
-                // ds_read_b64 (64 banks) and ds_read2_b64 (32 banks) alike
-
-// Logical block id such that ids adjacent in work space run on the same XCD (block b is observed on
-// XCD b % 8; each XCD has its own L2).  Bijective for any grid size; placement only affects speed.
-__device__ __forceinline__ int sf_xcd_remap(int bid, int nblk) {
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int q = nblk >> 3, r = nblk & 7;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + slot;
-}
-
-// Batched MFMA update  Cout = Cin -/+ A * B^T  on 128 x 128 tiles (v_mfma_f64_16x16x4_f64, 4 waves,
-// each 64 x 64 = 4 x 4 MFMA tiles; K staged through LDS in slabs of GK with register prefetch).
-// All operands are row-major blocks addressed from their own origin (the host passes pointers already
-// offset to the block): A is M x K, B is Nc x K, C is M x Nc.
-struct sf_gemm_args {
-    const double* A;
-    const double* B;
-    const double* Cin;  // NULL: start from zero
-    double* Cout;
-    int64_t sA, sB, sCin, sCout;  // batch strides (doubles)
-    int lda, ldb, ldcin, ldcout;
-    int M, Nc, K;
-    int tri;    // block is diagonal-aligned: skip tiles lying entirely above the diagonal
-    int btri;   // B[c][k] == 0 for k > c: column tile tn only needs k < (tn + 1) * GT
-    int remap_after, remap_shift;  // output row i >= remap_after is stored at row i + remap_shift
-    // fused left-looking right-hand-side update, done by the tiles with tm == tn while B streams by:
-    //   rhs[c] -= sum_k B[c][k] * z[k]
-    double* rhs;
-    const double* z;
-    int64_t srhs, sz;
-    // block-diagonal mode (diag_blocks > 0): the launch updates diag_blocks independent SF_NB x SF_NB
-    // diagonal blocks; block j takes A/B at +j*dA and C at +j*dC (M = Nc = total rows covered)
-    int diag_blocks;
-    int64_t dA, dC;
-    // matrix-free start: if tilemap says this 128 x 128 tile was never materialised, its initial value is
-    // Y^T Y (rank-mpad product of the rows/columns of Y) instead of Cin
-    const double* genY;
-    const unsigned char* tilemap;
-    int64_t sY;
-    int ldy, mpad, nt128, tm_off, tn_off;
-    int mt, nt;
-    int no_syrk;  // diagonal tiles through the generic path (the launchers always leave it 0)
-};
-
-// Diagonal 128 x 128 tile of a symmetric update C -= P P^T (block-diagonal launches): only the 36 MFMA
-// blocks on or below the diagonal are computed, dealt to the 8 waves in equal shares (rows p and 7-p of
-// the 8 x 8 block grid hold 9 blocks; one wave takes 5 of them, its partner 4 plus a spare), and the single
-// operand P is staged once instead of twice.  40 block products per slab instead of 64.
-// Blocks above the diagonal are neither read nor written (nothing references them).
-template <bool RHS>
-__device__ __forceinline__ void sf_syrk_diag_tile(const sf_gemm_args& g, int b, int row0, double (*As)[GT * GLD]) {
-    constexpr int NP = 2, RPP = 64;  // 512 threads (8 waves): two staging passes of 64 rows
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l15 = lane & 15, lq = lane >> 4;
-    const int p = w >> 1, h = w & 1;
-    int bi[5], bj[5];
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-        if (h == 0) {
-            bi[q] = 7 - p;
-            bj[q] = q;
-        } else {
-            const int n_hi = 3 - p;  // blocks 5 .. 7-p of row 7-p, then blocks 0 .. p of row p
-            const int qq = q < 4 ? q : 0;
-            bi[q] = qq < n_hi ? 7 - p : p;
-            bj[q] = qq < n_hi ? 5 + qq : qq - n_hi;
-        }
-    }
-    const int nstore = h == 0 ? 5 : 4;
-
-    const int lr = tid >> 3, lc = (tid & 7) * 2;
-    const double* Ap[NP];
-#pragma unroll
-    for (int q = 0; q < NP; ++q) Ap[q] = g.A + (int64_t)b * g.sA + (int64_t)(row0 + lr + RPP * q) * g.lda + lc;
-    double2 ra[NP];
-    const bool do_rhs = RHS && g.rhs;
-    const double* zg = do_rhs ? g.z + (int64_t)b * g.sz + lc : nullptr;
-    double2 zv = make_double2(0.0, 0.0);
-    double part[NP];
-#pragma unroll
-    for (int q = 0; q < NP; ++q) part[q] = 0.0;
-    auto gload = [&](int kt) {
-#pragma unroll
-        for (int q = 0; q < NP; ++q) ra[q] = *(const double2*)(Ap[q] + kt * GK);
-        if (RHS && do_rhs) zv = *(const double2*)(zg + kt * GK);
-    };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int q = 0; q < NP; ++q) {
-            double* pa = &As[buf][(lr + RPP * q) * GLD + lc];
-            pa[0] = ra[q].x;
-            pa[1] = ra[q].y;
-        }
-        if (RHS && do_rhs) {
-#pragma unroll
-            for (int q = 0; q < NP; ++q) part[q] += ra[q].x * zv.x + ra[q].y * zv.y;
-        }
-    };
-    const int nk = g.K / GK;
-    if (nk > 0) gload(0);
-    sf_d4 acc[5];
-    const double* Cin = g.Cin + (int64_t)b * g.sCin + (int64_t)row0 * g.ldcin + row0;
-#pragma unroll
-    for (int q = 0; q < 5; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            acc[q][r] = Cin[(int64_t)(16 * bi[q] + lq + 4 * r) * g.ldcin + 16 * bj[q] + l15];
-    if (nk > 0) lstore(0);
-    __syncthreads();
-    auto compute = [&](int cur) {
-        const double* S = &As[cur][l15 * GLD + lq];
-#pragma unroll
-        for (int ks = 0; ks < GK / 4; ++ks) {
-#pragma unroll
-            for (int q = 0; q < 5; ++q)
-                acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(S[bi[q] * 16 * GLD + ks * 4], S[bj[q] * 16 * GLD + ks * 4],
-                                                              acc[q], 0, 0, 1);  // blgp 1 = neg:[1,0,0]: -A B + C
-        }
-    };
-    for (int kt = 0; kt + 1 < nk; ++kt) {
-        gload(kt + 1);
-        compute(kt & 1);
-        lstore((kt & 1) ^ 1);
-        __syncthreads();
-    }
-    if (nk > 0) compute((nk - 1) & 1);
-    double* Cout = g.Cout + (int64_t)b * g.sCout + (int64_t)row0 * g.ldcout + row0;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-        if (q >= nstore) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            Cout[(int64_t)(16 * bi[q] + lq + 4 * r) * g.ldcout + 16 * bj[q] + l15] = acc[q][r];
-    }
-    if (RHS && do_rhs) {
-        double* rhs = g.rhs + (int64_t)b * g.srhs + row0;
-#pragma unroll
-        for (int q = 0; q < NP; ++q) {
-            double v = part[q];
-            v += __shfl_xor(v, 1);
-            v += __shfl_xor(v, 2);
-            v += __shfl_xor(v, 4);
-            if ((tid & 7) == 0) rhs[lr + RPP * q] -= v;
-        }
-    }
-}
-
-// Occupancy note (measured on MI355X, tools/probes/mfma_clock.hip): ONE wave issues a
-// v_mfma_f64_16x16x4_f64 only every ~140 cycles even with independent accumulators, two waves per
-// SIMD reach one per ~100 cycles, four waves per SIMD saturate the 64-cycle pipe.  The kernel is
-// therefore built for 4 waves/SIMD: 512 threads (8 waves, each 32 x 64 of the 128 x 128 tile = 2 x 4
-// MFMA tiles = 64 accumulator VGPRs), <= 128 VGPRs, two workgroups per CU.
-template <bool NEG, bool RHS>
-__global__ __launch_bounds__(512, 4) void k_gemm_nt(sf_gemm_args g) {
-    constexpr int TM = 2, TN = 4;
-    constexpr int WN = 128 / (16 * TN);   // waves across columns
-    constexpr int NP = 2;                 // staging passes of 64 rows each
-    constexpr int RPP = 64;               // rows per staging pass
-    __shared__ __attribute__((aligned(16))) double As[2][GT * GLD];
-    __shared__ __attribute__((aligned(16))) double Bs[2][GT * GLD];
-
-    const int id = sf_xcd_remap(blockIdx.x, gridDim.x);
-    const int tiles = g.mt * g.nt;
-    const int b = id / tiles;
-    const int t = id - b * tiles;
-    int tm, tn, rows_here, cols_here;
-    if (g.diag_blocks) {
-        // 2 x 2 tiles per SF_NB block, the upper-right one is never needed
-        const int jb = t >> 2;
-        tm = (t >> 1) & 1;
-        tn = t & 1;
-        if (tn > tm) return;
-        const int blk = min(SF_NB, g.M - jb * SF_NB);  // the last block may be narrower
-        rows_here = min(GT, blk - tm * GT);
-        cols_here = min(GT, blk - tn * GT);
-        if (rows_here <= 0 || cols_here <= 0) return;
-        g.A += jb * g.dA;
-        g.B += jb * g.dA;
-        if (g.Cin) g.Cin += jb * g.dC;
-        g.Cout += jb * g.dC;
-        if (RHS && g.rhs) g.rhs += jb * SF_NB;
-        if (NEG && tm == tn && rows_here == GT && g.K > 0 && g.A == g.B && g.Cin && !g.no_syrk) {
-            sf_syrk_diag_tile<RHS>(g, b, tm * GT, As);
-            return;
-        }
-    } else {
-        tm = t / g.nt;
-        tn = t - tm * g.nt;
-        if (g.tri && tn * GT > tm * GT + GT - 1) return;
-        rows_here = min(GT, g.M - tm * GT);
-        cols_here = min(GT, g.Nc - tn * GT);
-    }
-    const int row0 = tm * GT, col0 = tn * GT;
-    const int Kt = g.btri ? min(g.K, col0 + GT) : g.K;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, w = tid >> 6;
-    const int wm = w / WN, wn = w % WN;  // rows wm*32.., cols wn*(16*TN)..
-    const int l15 = lane & 15, lq = lane >> 4;
-
-    // ---- global -> register -> LDS staging: thread covers rows lr+64p, two doubles at column lc.
-    // Rows past the block edge are CLAMPED to the last valid row instead of being predicated: the
-    // duplicated data only feeds accumulator rows / columns that are never stored, and the loads stay
-    // branch-free (a predicated load makes hipcc wait for the whole vm queue).
-    const int lr = tid >> 3, lc = (tid & 7) * 2;
-    const double* Ap[NP];
-    const double* Bp[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        Ap[p] = g.A + (int64_t)b * g.sA + (int64_t)(row0 + min(lr + RPP * p, rows_here - 1)) * g.lda + lc;
-        Bp[p] = g.B + (int64_t)b * g.sB + (int64_t)(col0 + min(lr + RPP * p, cols_here - 1)) * g.ldb + lc;
-    }
-    double2 ra[NP], rb[NP];
-    const bool do_rhs = RHS && g.rhs && (tm == tn);
-    const double* zg = do_rhs ? g.z + (int64_t)b * g.sz + lc : nullptr;
-    double2 zv = make_double2(0.0, 0.0);
-    double part[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) part[p] = 0.0;
-
-    auto gload = [&](int kt) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            ra[p] = *(const double2*)(Ap[p] + kt * GK);
-            rb[p] = *(const double2*)(Bp[p] + kt * GK);
-        }
-        if (RHS && do_rhs) zv = *(const double2*)(zg + kt * GK);
-    };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            double* pa = &As[buf][(lr + RPP * p) * GLD + lc];
-            double* pb = &Bs[buf][(lr + RPP * p) * GLD + lc];
-            pa[0] = ra[p].x;
-            pa[1] = ra[p].y;
-            pb[0] = rb[p].x;
-            pb[1] = rb[p].y;
-        }
-        if (RHS && do_rhs) {
-#pragma unroll
-            for (int p = 0; p < NP; ++p) part[p] += rb[p].x * zv.x + rb[p].y * zv.y;
-        }
-    };
-
-    // the first operand slab is requested before the accumulators are initialised so that both
-    // latencies overlap (matters for the short-K launches)
-    const int nk = Kt / GK;
-    if (nk > 0) gload(0);
-
-    // ---- accumulators start as the C tile (read, or generated from Y when it was never materialised)
-    sf_d4 acc[TM][TN];
-    const double* Cin = g.Cin ? g.Cin + (int64_t)b * g.sCin + (int64_t)row0 * g.ldcin + col0 : nullptr;
-    bool generate = false;
-    if (g.tilemap && !g.diag_blocks)
-        generate = !g.tilemap[(int64_t)b * g.nt128 * g.nt128 + (g.tm_off + tm) * g.nt128 + (g.tn_off + tn)];
-    if (generate) {
-        const double* Yb = g.genY + (int64_t)b * g.sY;
-        // global pixel index of this lane's row / column (clamped: Y has ldy columns; rows past the
-        // matrix edge are never stored)
-        const int gr = (g.tm_off + tm) * GT + wm * (16 * TM) + l15;
-        const int gc = (g.tn_off + tn) * GT + wn * (16 * TN) + l15;
-#pragma unroll
-        for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < TN; ++ni) acc[mi][ni] = (sf_d4){0.0, 0.0, 0.0, 0.0};
-        for (int kk = 0; kk < g.mpad; kk += 4) {
-            const double* yk = Yb + (int64_t)(kk + lq) * g.ldy;
-            double ya[TM], yb[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) ya[i] = yk[min(gr + i * 16, g.ldy - 1)];
-#pragma unroll
-            for (int i = 0; i < TN; ++i) yb[i] = yk[min(gc + i * 16, g.ldy - 1)];
-#pragma unroll
-            for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < TN; ++ni)
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(ya[mi], yb[ni], acc[mi][ni], 0, 0, 0);
-        }
-    } else {
-#pragma unroll
-        for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < TN; ++ni) {
-                const int col = wn * (16 * TN) + ni * 16 + l15;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = wm * (16 * TM) + mi * 16 + lq + 4 * r;
-                    double v = 0.0;
-                    if (Cin && row < rows_here && col < cols_here) v = Cin[(int64_t)row * g.ldcin + col];
-                    acc[mi][ni][r] = v;
-                }
-            }
-    }
-
-    if (nk > 0) lstore(0);
-    __syncthreads();
-
-    auto compute = [&](int cur) {
-        const double* Ab = &As[cur][(wm * (16 * TM) + l15) * GLD + lq];
-        const double* Bb = &Bs[cur][(wn * (16 * TN) + l15) * GLD + lq];
-#pragma unroll
-        for (int ks = 0; ks < GK / 4; ++ks) {
-            double a[TM], bb[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a[i] = Ab[i * 16 * GLD + ks * 4];
-#pragma unroll
-            for (int i = 0; i < TN; ++i) bb[i] = Bb[i * 16 * GLD + ks * 4];
-#pragma unroll
-            for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < TN; ++ni)
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], bb[ni], acc[mi][ni], 0, 0, NEG ? 1 : 0);  // the f64 MFMA's blgp bits negate: neg:[1,0,0]
-        }
-    };
-    // steady state is ONE basic block: issue the next slab's global loads, run this slab's MFMAs from
-    // LDS, then park the loaded slab in the other LDS buffer; the last slab is peeled
-    for (int kt = 0; kt + 1 < nk; ++kt) {
-        gload(kt + 1);
-        compute(kt & 1);
-        lstore((kt & 1) ^ 1);
-        __syncthreads();
-    }
-    if (nk > 0) compute((nk - 1) & 1);
-
-    double* Cout = g.Cout + (int64_t)b * g.sCout + col0;
-#pragma unroll
-    for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < TN; ++ni) {
-            const int col = wn * (16 * TN) + ni * 16 + l15;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = wm * (16 * TM) + mi * 16 + lq + 4 * r;
-                if (row < rows_here && col < cols_here) {
-                    int orow = row0 + row;
-                    if (orow >= g.remap_after) orow += g.remap_shift;
-                    Cout[(int64_t)orow * g.ldcout + col] = acc[mi][ni][r];
-                }
-            }
-        }
-
-    if (RHS && do_rhs) {
-        // the 8 threads sharing lr cover the 16 k-columns of a slab: fold them, one of them commits
-        double* rhs = g.rhs + (int64_t)b * g.srhs + col0;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            double v = part[p];
-            v += __shfl_xor(v, 1);
-            v += __shfl_xor(v, 2);
-            v += __shfl_xor(v, 4);
-            const int rr = lr + RPP * p;
-            if ((tid & 7) == 0 && rr < cols_here) rhs[rr] -= v;
-        }
-    }
-}
-
-__device__ __forceinline__ double sf_readlane_d(double v, int srclane) {
-    union { double d; int i[2]; } u;
-    u.d = v;
-    u.i[0] = __builtin_amdgcn_readlane(u.i[0], srclane);
-    u.i[1] = __builtin_amdgcn_readlane(u.i[1], srclane);
-    return u.d;
-}
-
-__device__ __forceinline__ double sf_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// One workgroup per matrix: forward substitution L z = R by 64-row blocks (left-looking: the
-// row block is read once, coalesced), then logdet = 2 sum log L_ii and sqmah = z.z.
-template <bool ZGLOBAL>
-__global__ __launch_bounds__(256) void k_trsv_logdet(const double* __restrict__ base, int n, int lda,
-                                                     int64_t stride, const double* __restrict__ R,
-                                                     int ldr, double* __restrict__ zscratch,
-                                                     double* __restrict__ logdet,
-                                                     double* __restrict__ sqmah) {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    double* Ts = sm;                     // 64 x 65 diagonal block
-    double* tv = Ts + SF_LEAF * 65;      // 64 right-hand sides of the block
-    double* red = tv + SF_LEAF;          // 8 reduction slots
-    double* z = ZGLOBAL ? zscratch + (int64_t)blockIdx.x * n : red + 8;
-
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int lane = tid & 63, w = tid >> 6;
-    const double* Mx = base + (int64_t)b * stride;
-    const double* Rb = R + (int64_t)b * ldr;
-
-    for (int c = 0; c < n; c += SF_LEAF) {
-        for (int e = tid; e < SF_LEAF * SF_LEAF; e += 256) {
-            const int i = e >> 6, j = e & 63;
-            Ts[i * 65 + j] = Mx[(int64_t)(c + i) * lda + c + j];
-        }
-        // 16 rows per wave, all 16 row streams in flight together
-        double s[16];
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) s[rr] = 0.0;
-        const double* prow = Mx + (int64_t)(c + w * 16) * lda;
-        for (int k = lane; k < c; k += 64) {
-            const double zk = z[k];
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) s[rr] += prow[(int64_t)rr * lda + k] * zk;
-        }
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-            const double tot = sf_wave_sum(s[rr]);
-            if (lane == 0) tv[w * 16 + rr] = Rb[c + w * 16 + rr] - tot;
-        }
-        __syncthreads();
-        if (w == 0) {
-            double tval = tv[lane];
-#pragma unroll 8
-            for (int k = 0; k < SF_LEAF; ++k) {
-                const double zk = __shfl(tval, k) / Ts[k * 65 + k];
-                if (lane > k)
-                    tval -= Ts[lane * 65 + k] * zk;
-                else if (lane == k)
-                    tval = zk;
-            }
-            z[c + lane] = tval;
-        }
-        __syncthreads();
-    }
-    double slog = 0.0, ssq = 0.0;
-    for (int i = tid; i < n; i += 256) {
-        slog += log(Mx[(int64_t)i * lda + i]);
-        const double zi = z[i];
-        ssq += zi * zi;
-    }
-    slog = sf_wave_sum(slog);
-    ssq = sf_wave_sum(ssq);
-    if (lane == 0) {
-        red[w] = slog;
-        red[4 + w] = ssq;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        logdet[b] = 2.0 * (red[0] + red[1] + red[2] + red[3]);
-        sqmah[b] = red[4] + red[5] + red[6] + red[7];
-    }
-}
-
-// ------------------------------------------------------------------------------------ launchers
-static int launch_gemm(sf_gemm_args g, int batch, bool neg, double flops, hipStream_t s) {
-    if (g.M <= 0 || g.Nc <= 0) return SF_OK;
-    g.mt = (g.M + GT - 1) / GT;
-    g.nt = (g.Nc + GT - 1) / GT;
-    if (g.diag_blocks) {  // 4 tile slots per block
-        g.mt = g.diag_blocks;
-        g.nt = 4;
-    }
-    const long long nblk = (long long)g.mt * g.nt * batch;
-    if (nblk > 0x7fffffffLL) {
-        sf_set_error("gemm grid too large");
-        return SF_EINVAL;
-    }
-    void* tok;
-    sf_prof_gemm_begin(s, flops, &tok);
-    if (g.rhs)
-        hipLaunchKernelGGL((k_gemm_nt<true, true>), dim3((unsigned)nblk), dim3(512), 0, s, g);
-    else if (neg)
-        hipLaunchKernelGGL((k_gemm_nt<true, false>), dim3((unsigned)nblk), dim3(512), 0, s, g);
-    else
-        hipLaunchKernelGGL((k_gemm_nt<false, false>), dim3((unsigned)nblk), dim3(512), 0, s, g);
-    sf_prof_gemm_end(tok);
-    SF_LAUNCH_CHECK();
-    return SF_OK;
-}
-
-// One workgroup per matrix: logdet = 2 sum log L_ii and sqmah = |z|^2 where z = L^-1 R was produced
-// in place of R by the factorisation.
-__global__ __launch_bounds__(256) void k_logdet_z(const double* __restrict__ base, int n, int lda,
-                                                  int64_t stride, const double* __restrict__ zbuf, int ldr,
-                                                  double* __restrict__ logdet,
-                                                  double* __restrict__ sqmah) {
-    __shared__ double red[8];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const double* Mx = base + (int64_t)b * stride;
-    const double* z = zbuf ? zbuf + (int64_t)b * ldr : nullptr;
-    double slog = 0.0, ssq = 0.0;
-    for (int i = tid; i < n; i += 256) {
-        slog += log(Mx[(int64_t)i * lda + i]);
-        const double zi = z ? z[i] : 0.0;
-        ssq += zi * zi;
-    }
-    slog = sf_wave_sum(slog);
-    ssq = sf_wave_sum(ssq);
-    if (lane == 0) {
-        red[w] = slog;
-        red[4 + w] = ssq;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        logdet[b] = 2.0 * (red[0] + red[1] + red[2] + red[3]);
-        sqmah[b] = red[4] + red[5] + red[6] + red[7];
-    }
-}
-
-int sf_launch_logdet_z(const double* L, int n, int lda, int64_t stride, int batch, const double* z, int ldr,
-                       double* logdet, double* sqmah, hipStream_t s) {
-    hipLaunchKernelGGL(k_logdet_z, dim3(batch), dim3(256), 0, s, L, n, lda, stride, z, ldr, logdet, sqmah);
-    SF_LAUNCH_CHECK();
-    return SF_OK;
-}
-
-// Panel scratch T (per matrix, row stride SF_LDT): rows [0, pw) the updated diagonal block,
-// rows [pw, 2pw) the rows of W = L_kk^-T while the diagonal block is factored (k_diag_mfma),
-// rows [2pw, ...) the updated rows below the diagonal block.
-
-// ---------------------------------------------------------------------------------------------
-// Diagonal-block step of one panel as ONE launch on the matrix cores (one workgroup of 16 waves per
-// matrix, one 16 x 16 block of the current block column per wave): L_kk and its inverse for the pw x pw block (pw <= 256), LEFT-looking over 16-column block
-// columns so that nothing is read-modify-written in memory:
-//   U  every wave accumulates its blocks of column k in registers:  M(i,k) - sum_{j<k} L(i,j) L(k,j)^T
-//      for the rows of the matrix block and  - sum_{e<=j<k} X(e,j) L(k,j)^T  for the rows of the "identity
-//      block" E (whose solved rows X = rows of W = L_kk^-T).  A operands stream from L2, the row L(k,:)
-//      shared by the whole column is staged in LDS once;
-//   P  wave 0, which owns M(k,k), factorises it and inverts the factor in the MFMA accumulator layout
-//      (column j of the symmetric block is register j/4 of quarter j%4 = a K-slice of the MFMA operands,
-//      so every rank-1 elimination is one MFMA without data movement; pivots from scalars so that the
-//      rsqrt chain overlaps the matrix core);
-//   X  every wave solves the blocks it still holds as a product with the 16 x 16 inverse F and writes
-//      them out: L to the matrix (and in place, as operand of later columns), W transposed to Wt.
-// The identity block is implicit (row block e of E starts at column e with X = F^T).  Finally
-// z_k = L_kk^-1 r_k as a product with the explicit inverse.  One launch per panel: one scheduling wait on the
-// contended chip.
-#define DBS (16 * 17)
-#define DLD 17
-__device__ __forceinline__ double sfd_rsqrt(double p) {
-    double y = __builtin_amdgcn_rsq(p);
-    const double h = 0.5 * p;
-    double e = __builtin_fma(-h * y, y, 0.5);
-    y = __builtin_fma(y, e, y);
-    e = __builtin_fma(-h * y, y, 0.5);
-    y = __builtin_fma(y, e, y);
-    return y;
-}
-
-__global__ __launch_bounds__(1024) void k_diag_mfma(double* __restrict__ T, int64_t sT, int pw,
-                                                      int* __restrict__ info, int info_off,
-                                                      double* __restrict__ rhs, int ldr,
-                                                      double* __restrict__ Cdiag, int ldc, int64_t sC,
-                                                      double* __restrict__ Wt, int64_t sW) {
-    constexpr int NT = 1024;  // 16 waves
-    __shared__ double LK[(NT / 64 - 1) * DBS];  // L(k, j), j < k: the B operand of the whole block column
-    __shared__ double ST[(NT / 64) * DBS];      // per-wave staging block (accumulator layout -> operand layout)
-    __shared__ double Fb[DBS];       // inverse of the current 16 x 16 diagonal factor
-    __shared__ double rz[256];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l15 = lane & 15, lq = lane >> 4;
-    const int nb = pw >> 4;
-    double* Tb = T + (int64_t)b * sT;
-    double* Eb = Tb + (int64_t)pw * SF_LDT;
-    double* Cb = Cdiag + (int64_t)b * sC;
-    double* Wb = Wt + (int64_t)b * sW;
-    double* st = ST + wave * DBS;
-
-    // Wt is lower triangular: zero the blocks above the diagonal (the buffer alternates between panels)
-    for (int e = tid; e < nb * nb * 256; e += NT) {
-        const int blk = e >> 8, bc = blk / nb, be = blk - bc * nb;
-        if (be > bc) Wb[(int64_t)(bc * 16 + ((e >> 4) & 15)) * SF_LDT + be * 16 + (e & 15)] = 0.0;
-    }
-    int bad = 0;
-    for (int k = 0; k < nb; ++k) {
-        const int m = nb - 1 - k;  // matrix row blocks below the diagonal block
-        // ---- stage L(k, 0..k-1) (final since the previous columns) in LDS
-        for (int e = tid; e < k * 256; e += NT) {
-            const int j = e >> 8, r = (e >> 4) & 15, cc = e & 15;
-            LK[j * DBS + r * DLD + cc] = Tb[(int64_t)(16 * k + r) * SF_LDT + 16 * j + cc];
-        }
-        __syncthreads();
-        // ---- U: block of this wave: t = 0 -> M(k,k), 1..m -> M(k+t,k), then E(e,k)
-        sf_d4 acc[1];
-        int kind[1];  // 0 none, 1 matrix row block, 2 inverse row block
-        int ibk[1];
-        {
-            constexpr int u = 0;
-            const int t = wave;
-            kind[u] = 0;
-            ibk[u] = 0;
-            acc[u] = (sf_d4){0.0, 0.0, 0.0, 0.0};
-            if (t <= m + k) {
-                const bool isM = t <= m;
-                const int ib = isM ? k + t : t - m - 1;
-                kind[u] = isM ? 1 : 2;
-                ibk[u] = ib;
-                const double* rowp = (isM ? Tb : Eb) + (int64_t)(16 * ib) * SF_LDT;
-                if (isM) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int row = lq + 4 * r;
-                        // the diagonal block is read symmetrically from its lower triangle
-                        acc[u][r] = (t == 0) ? rowp[(int64_t)max(row, l15) * SF_LDT + 16 * k + min(row, l15)]
-                                             : rowp[(int64_t)row * SF_LDT + 16 * k + l15];
-                    }
-                }
-                const int j0 = isM ? 0 : ib;  // X(e, j) exists for j >= e
-                // K is a summation index: lane (l15, lq) takes the four CONTIGUOUS columns 4 lq .. 4 lq + 3
-                // of its row (two 16-byte loads, full 128-B lines per 4 lanes) and MFMA kk uses element kk, i.e.
-                // slice lq of instruction kk stands for k = 4 lq + kk -- in both operands.
-                const double2* ap = (const double2*)(rowp + (int64_t)l15 * SF_LDT + 4 * lq);
-                // A fragments stream from L2: four block columns in flight (clamped loads past the end)
-                double2 av[4][2];
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const int jj = min(j0 + d, max(k - 1, 0));
-                    av[d][0] = ap[8 * jj];
-                    av[d][1] = ap[8 * jj + 1];
-                }
-                for (int j = j0; j < k; ++j) {
-                    // rotating register window: block column j is consumed, j + 4 is requested
-                    const double* lk = LK + j * DBS + l15 * DLD + 4 * lq;
-                    const double a4[4] = {av[0][0].x, av[0][0].y, av[0][1].x, av[0][1].y};
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk)
-                        acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[kk], lk[kk], acc[u], 0, 0, 1);  // neg:[1,0,0]
-#pragma unroll
-                    for (int d = 0; d < 3; ++d) {
-                        av[d][0] = av[d + 1][0];
-                        av[d][1] = av[d + 1][1];
-                    }
-                    const int jj = min(j + 4, max(k - 1, 0));
-                    av[3][0] = ap[8 * jj];
-                    av[3][1] = ap[8 * jj + 1];
-                }
-            }
-        }
-        // ---- P: wave 0 holds the updated diagonal block in acc[0]
-        if (wave == 0) {
-            sf_d4 a0 = acc[0], f, lt;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                f[r] = (lq + 4 * r) == l15 ? 1.0 : 0.0;
-                lt[r] = 0.0;
-            }
-            double p = sf_readlane_d(a0[0], 0);
-            double pkeep = 1.0;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int qj = j & 3, rj = j >> 2;
-                pkeep = lane == j ? p : pkeep;
-                const double rs = sfd_rsqrt(p);
-                const bool in_q = lq == qj;
-                const double v = (in_q && l15 > j) ? a0[rj] * rs : 0.0;  // l_ij, i = l15 > j
-                const double g = in_q ? f[rj] * rs : 0.0;                // row j of F, scaled
-                if (in_q) {
-                    f[rj] = g;
-                    lt[rj] = l15 == j ? p * rs : v;  // L^T[j][i]
-                }
-                if (j + 1 < 16) {
-                    const double an = sf_readlane_d(a0[(j + 1) >> 2], ((j + 1) & 3) * 16 + j + 1);
-                    const double vn = sf_readlane_d(v, qj * 16 + j + 1);
-                    p = __builtin_fma(-vn, vn, an);
-                }
-                a0 = __builtin_amdgcn_mfma_f64_16x16x4f64(v, v, a0, 0, 0, 1);  // neg:[1,0,0]
-                f = __builtin_amdgcn_mfma_f64_16x16x4f64(v, g, f, 0, 0, 1);
-            }
-            const unsigned long long neg = __ballot(lane < 16 && !(pkeep > 0.0));
-            if (neg && !bad) bad = 16 * k + __ffsll((long long)neg);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = lq + 4 * r;
-                Fb[row * DLD + l15] = f[r];
-                Wb[(int64_t)(16 * k + row) * SF_LDT + 16 * k + l15] = f[r];  // diagonal block of L_kk^-1
-                // X of the identity row block k is F^T: operand of later columns
-                Eb[(int64_t)(16 * k + l15) * SF_LDT + 16 * k + row] = f[r];
-                if (l15 >= row) {
-                    Cb[(int64_t)(16 * k + l15) * ldc + 16 * k + row] = lt[r];          // L[i][j] -> matrix
-                    Tb[(int64_t)(16 * k + l15) * SF_LDT + 16 * k + row] = lt[r];        // and in place
-                }
-            }
-            kind[0] = 0;
-        }
-        __syncthreads();
-        // ---- X: solve the blocks still held in registers, write them out
-#pragma unroll
-        for (int u = 0; u < 1; ++u) {
-            if (kind[u] == 0) continue;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) st[(lq + 4 * r) * DLD + l15] = acc[u][r];
-            sf_d4 x = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-                x = __builtin_amdgcn_mfma_f64_16x16x4f64(st[l15 * DLD + kk * 4 + lq], Fb[l15 * DLD + kk * 4 + lq], x,
-                                                         0, 0, 0);
-            const int ib = ibk[u];
-            double* rowp = (kind[u] == 1 ? Tb : Eb) + (int64_t)(16 * ib) * SF_LDT + 16 * k;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = lq + 4 * r;
-                rowp[(int64_t)row * SF_LDT + l15] = x[r];  // in place: operand of the later columns
-                if (kind[u] == 1) Cb[(int64_t)(16 * ib + row) * ldc + 16 * k + l15] = x[r];  // L
-                else Wb[(int64_t)(16 * k + l15) * SF_LDT + 16 * ib + row] = x[r];             // (L^-T)^T
-            }
-        }
-        __syncthreads();
-    }
-    if (tid == 0 && bad && info && info[b] == 0) info[b] = info_off + bad;
-    // ---- z_k = L_kk^-1 r_k with the explicit inverse
-    if (rhs) {
-        double* rb = rhs + (int64_t)b * ldr;
-        for (int i = tid; i < pw; i += NT) rz[i] = rb[i];
-        __syncthreads();
-        for (int i = tid; i < pw; i += NT) {
-            const double* wrow = Wb + (int64_t)i * SF_LDT;
-            double zacc = 0.0;
-            for (int j = 0; j <= i; ++j) zacc = __builtin_fma(wrow[j], rz[j], zacc);
-            rb[i] = zacc;
-        }
-    }
-}
-
-
-// The same diagonal-block step for the 128-column panels of the fused sequence, with the tile and its growing inverse
-// RESIDENT IN LDS: k_diag_mfma keeps them in the L2-backed scratch, so every one of its 8 block columns pays two global
-// round trips (stage L(k,:), write X / read it back as an operand of the next column), 55-65 us per tile when the chip
-// is idle and three times that beside the panel launches.  Here the tile is read once, the eight columns run out of LDS
-// (no staging buffers: an accumulator block is written to its own destination block and read back in operand layout
-// by the same wave), and L / L^-1 / z are written once.
-// The inverse grows IN PLACE of the factor (36 blocks of 16 x 17 doubles + one: 79.6 KB, two workgroups per CU or one
-// beside a panel workgroup; with a second set of blocks for the inverse it was 157 KB = a whole CU): block column k of
-// W = L^-T is row k of L^-1, and row k of L is read for the last time at step k -- by the waves that update block column
-// k and by the waves that accumulate row k of the inverse, all before that step's first barrier -- so after it the
-// inverse waves drop X(e, k) into the slot of L(k, e).  L leaves for global memory block by block as it becomes final.
-// (body shared by the kernel below and by the diagonal-tile tasks of k_potrf_dataflow; dsm: SF_DIAG_LDS_BYTES of LDS)
-__device__ __forceinline__ void sf_diag_lds_body(const double* __restrict__ T, int64_t sT, int pw, int* __restrict__ info,
-                                                 int info_off, double* __restrict__ rhs, int ldr,
-                                                 double* __restrict__ Cdiag, int ldc, int64_t sC,
-                                                 double* __restrict__ Wt, int64_t sW, int fp0, const int b,
-                                                 double* __restrict__ dsm, const int tid, long long* stamps = nullptr) {
-#ifdef SF_TUNING
-#define SF_D_STAMP(i) do { if (stamps && tid == 0) stamps[i] = wall_clock64(); } while (0)
-#else
-#define SF_D_STAMP(i)
-#endif
-    SF_D_STAMP(0);
-    // fp0: the first fp0 rows / columns of the tile are virtual (identity in T; Cdiag and rhs point fp0 elements BEFORE
-    // the matrix there: never stored, read as zero) -- the first tile of a shifted frame, see sf_potrf_front_pad
-    double* Tl = dsm;              // lower blocks (bi >= bj) of the tile at (bi (bi + 1) / 2 + bj) * DBS
-    double* El = Tl;               // blocks X(e, j), e <= j, of W = L_kk^-T: in the slot of L(j, e) once row j of L is dead
-    double* Fb = Tl + 36 * DBS;    // inverse of the current 16 x 16 diagonal factor
-    double* rz = Fb + DBS;         // [128]
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l15 = lane & 15, lq = lane >> 4;
-    const int nb = pw >> 4;
-    const double* Tb = T + (int64_t)b * sT;
-    double* Cb = Cdiag + (int64_t)b * sC;
-    double* Wb = Wt + (int64_t)b * sW;
-    auto tb = [](int bi, int bj) { return (bi * (bi + 1) / 2 + bj) * DBS; };
-    auto eb = [](int e, int j) { return (j * (j + 1) / 2 + e) * DBS; };  // = tb(j, e)
-
-    {
-        // the lower blocks only, 16 bytes per load, ALL of a thread's loads in flight before the first LDS store (nine per
-        // thread for a full tile: one round trip instead of thirty-two short ones; 5.5 -> ~3 us of the tile's 41)
-        const int cnt = nb * (nb + 1) / 2 * 128;
-        double2 v[9];
-#pragma unroll
-        for (int u = 0; u < 9; ++u) {
-            const int e = min(tid + 512 * u, cnt - 1);
-            const int blk = e >> 7, r = (e >> 3) & 15, c2 = e & 7;
-            int bi = 0;
-            while ((bi + 1) * (bi + 2) / 2 <= blk) ++bi;
-            const int bj = blk - bi * (bi + 1) / 2;
-            v[u] = *(const double2*)(Tb + (int64_t)(16 * bi + r) * SF_LDT + 16 * bj + 2 * c2);
-        }
-#pragma unroll
-        for (int u = 0; u < 9; ++u) {
-            const int e = tid + 512 * u;
-            if (e < cnt) {
-                const int r = (e >> 3) & 15, c2 = e & 7;
-                double* d = Tl + (e >> 7) * DBS + r * DLD + 2 * c2;  // (tb(bi, bj) = blk * DBS: the same enumeration)
-                d[0] = v[u].x;
-                d[1] = v[u].y;
-            }
-        }
-    }
-    __syncthreads();
-    SF_D_STAMP(1);
-    int bad = 0;
-    const int oF = l15 * DLD + lq;  // operand fragment: row l15, K slice lq of instruction kk stands for k = 4 kk + lq
-    for (int k = 0; k < nb; ++k) {
-        const int m = nb - 1 - k;
-        if (k == 7) SF_D_STAMP(8);
-        // ---- U: wave t <= m holds M(k + t, k), wave t > m the block X(t - m - 1, k) of the inverse
-        const int t = wave;
-        const bool has = t <= m + k, isM = t <= m;
-        const int ib = isM ? k + t : t - m - 1;
-        double* own = has ? (isM ? Tl + tb(ib, k) : El + eb(ib, k)) : Fb;
-        sf_d4 acc = {0.0, 0.0, 0.0, 0.0};
-        if (has) {
-            if (isM) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = lq + 4 * r;  // (the diagonal block is read symmetrically from its lower triangle)
-                    acc[r] = t == 0 ? own[max(row, l15) * DLD + min(row, l15)] : own[row * DLD + l15];
-                }
-            }
-            for (int j = isM ? 0 : ib; j < k; ++j) {
-                const double* ap = (isM ? Tl + tb(ib, j) : El + eb(ib, j)) + oF;
-                const double* bp = Tl + tb(k, j) + oF;
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[4 * kk], bp[4 * kk], acc, 0, 0, 1);  // neg:[1,0,0]
-            }
-        }
-        // ---- P: wave 0 factorises the diagonal block and inverts the factor in the accumulator layout
-        if (k == 7) SF_D_STAMP(9);
-        if (wave == 0) {
-            sf_d4 a0 = acc, f, lt;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                f[r] = (lq + 4 * r) == l15 ? 1.0 : 0.0;
-                lt[r] = 0.0;
-            }
-            double p = sf_readlane_d(a0[0], 0);
-            double pkeep = 1.0;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int qj = j & 3, rj = j >> 2;
-                pkeep = lane == j ? p : pkeep;
-                const double rs = sfd_rsqrt(p);
-                const bool in_q = lq == qj;
-                const double v = (in_q && l15 > j) ? a0[rj] * rs : 0.0;  // l_ij, i = l15 > j
-                const double g = in_q ? f[rj] * rs : 0.0;                // row j of F, scaled
-                if (in_q) {
-                    f[rj] = g;
-                    lt[rj] = l15 == j ? p * rs : v;  // L^T[j][i]
-                }
-                if (j + 1 < 16) {
-                    const double an = sf_readlane_d(a0[(j + 1) >> 2], ((j + 1) & 3) * 16 + j + 1);
-                    const double vn = sf_readlane_d(v, qj * 16 + j + 1);
-                    p = __builtin_fma(-vn, vn, an);
-                }
-                a0 = __builtin_amdgcn_mfma_f64_16x16x4f64(v, v, a0, 0, 0, 1);  // neg:[1,0,0]
-                f = __builtin_amdgcn_mfma_f64_16x16x4f64(v, g, f, 0, 0, 1);
-            }
-            const unsigned long long neg = __ballot(lane < 16 && !(pkeep > 0.0));
-            if (neg && !bad) bad = 16 * k + __ffsll((long long)neg);
-            double* Ekk = El + eb(k, k);  // (= own: the diagonal block of the tile has been consumed)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = lq + 4 * r;
-                Fb[row * DLD + l15] = f[r];
-                Ekk[l15 * DLD + row] = f[r];                      // X of the identity row block k is F^T
-                // L[i][j], lower triangle of the diagonal block: straight to the matrix
-                if (l15 >= row && 16 * k + row >= fp0) Cb[(int64_t)(16 * k + l15) * ldc + 16 * k + row] = lt[r];
-            }
-        }
-        if (k == 7) SF_D_STAMP(10);
-        __syncthreads();
-        if (k == 7) SF_D_STAMP(11);
-        // ---- X: the other blocks times F^T, through their own destination block (accumulator -> operand layout)
-        if (has && wave != 0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) own[(lq + 4 * r) * DLD + l15] = acc[r];
-            double a[4], f4[4];
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                a[kk] = own[oF + 4 * kk];
-                f4[kk] = Fb[oF + 4 * kk];
-            }
-            sf_d4 x = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) x = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], f4[kk], x, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) own[(lq + 4 * r) * DLD + l15] = x[r];
-            if (isM && 16 * k + l15 >= fp0) {  // block (k + t, k) of L is final
-#pragma unroll
-                for (int r = 0; r < 4; ++r) Cb[(int64_t)(16 * ib + lq + 4 * r) * ldc + 16 * k + l15] = x[r];
-            }
-        }
-        __syncthreads();
-    }
-    SF_D_STAMP(2);
-    if (tid == 0 && bad && info && info[b] == 0) info[b] = info_off + bad;
-    // ---- Wt[c][j] = (L_kk^-1)[c][j] (block (cb, jb) = X(jb, cb)^T, zero above)
-    for (int idx = tid; idx < nb * nb * 128; idx += 512) {  // (16-byte stores: half as many store instructions per thread)
-        const int blk = idx >> 7, bi = blk / nb, bj = blk - bi * nb, r = (idx >> 3) & 15, c = (idx & 7) * 2;
-        const double* e = El + eb(bj, bi) + c * DLD + r;
-        *(double2*)(Wb + (int64_t)(16 * bi + r) * SF_LDT + 16 * bj + c) = bj <= bi ? make_double2(e[0], e[DLD]) : make_double2(0.0, 0.0);
-    }
-    // ---- z_k = L_kk^-1 r_k with the explicit inverse
-    if (rhs) {
-        double* rb = rhs + (int64_t)b * ldr;
-        if (tid < pw) rz[tid] = tid >= fp0 ? rb[tid] : 0.0;
-        __syncthreads();
-        {
-            // four lanes per row (j = p, p + 4, ... <= i each), added by two shuffles: the 128-term chain of one lane per row
-            // was 3.9 us of the tile's 41
-            const int i = tid >> 2, p = tid & 3, ibk = i >> 4, ir = i & 15;
-            double zacc = 0.0;
-            if (i < pw)
-                for (int j = p; j <= i; j += 4) zacc = __builtin_fma(El[eb(j >> 4, ibk) + (j & 15) * DLD + ir], rz[j], zacc);
-            zacc += __shfl_xor(zacc, 1);
-            zacc += __shfl_xor(zacc, 2);
-            if (p == 0 && i < pw && i >= fp0) rb[i] = zacc;
-        }
-    }
-#ifdef SF_TUNING
-    if (stamps) {
-        SF_D_STAMP(3);
-        __syncthreads();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        SF_D_STAMP(4);
-    }
-#endif
-}
-__global__ __launch_bounds__(512) void k_diag_lds(const double* __restrict__ T, int64_t sT, int pw, int* __restrict__ info,
-                                                  int info_off, double* __restrict__ rhs, int ldr,
-                                                  double* __restrict__ Cdiag, int ldc, int64_t sC,
-                                                  double* __restrict__ Wt, int64_t sW, int fp0, int prio, long long* stamps) {
-    extern __shared__ double dsm[];
-    if (prio) __builtin_amdgcn_s_setprio(2);
-    sf_diag_lds_body(T, sT, pw, info, info_off, rhs, ldr, Cdiag, ldc, sC, Wt, sW, fp0, blockIdx.x, dsm, threadIdx.x,
-                     blockIdx.x == 0 ? stamps : nullptr);
-}
-#define SF_DIAG_LDS_BYTES ((37 * DBS + 128) * sizeof(double))
-// (the chain's workgroups -- this launch and the narrow steps that park the next diagonal tile -- run at raised wave priority)
-static int sf_launch_diag128(double* T, int64_t sT, int pw, int* info, int info_off, double* rhs, int ldr, double* Cdiag,
-                             int ldc, int64_t sC, double* Wt, int64_t sW, int batch, hipStream_t s, int fp0 = 0) {
-    static sf_dev_once attr_once;  // devices whose function attributes are set
-    SF_CHECK(sf_lds_limit_once(&attr_once, 160 * 1024, {(const void*)k_diag_lds}));
-    long long* stamps = nullptr;
-#ifdef SF_TUNING
-    static int printed = 0;
-    static long long* hs = nullptr;
-    if (SF_TUNE_FLAG("SF_DIAG_STAMPS") && printed < 6) {
-        if (!hs) SF_HIP(hipHostMalloc((void**)&hs, 16 * sizeof(long long)));
-        for (int i = 0; i < 16; ++i) hs[i] = 0;
-        stamps = hs;
-    }
-#endif
-    hipLaunchKernelGGL(k_diag_lds, dim3(batch), dim3(512), SF_DIAG_LDS_BYTES, s, T, sT, pw, info, info_off, rhs, ldr, Cdiag, ldc,
-                       sC, Wt, sW, fp0, 1, stamps);
-#ifdef SF_TUNING
-    if (stamps) {  // (synchronises) phases of workgroup 0, us
-        (void)hipStreamSynchronize(s);
-        ++printed;
-        fprintf(stderr, "k_diag_lds batch %d: tile load %.1f | 8 block columns %.1f (last column: U %.1f, P %.1f, barrier %.1f, X + barrier %.1f) | W store %.1f + z %.1f | drain %.1f | total %.1f us\n",
-                batch, (hs[1] - hs[0]) / 100.0, (hs[2] - hs[1]) / 100.0, (hs[9] - hs[8]) / 100.0, (hs[10] - hs[9]) / 100.0, (hs[11] - hs[10]) / 100.0,
-                (hs[2] - hs[11]) / 100.0, 0.0, (hs[3] - hs[2]) / 100.0, (hs[4] - hs[3]) / 100.0, (hs[4] - hs[0]) / 100.0);
-    }
-#endif
-    SF_LAUNCH_CHECK();
-    return SF_OK;
-}
+#include "sf_device.h"
+#include "sf_chol_tile.h"
+#include "sf_chol_host.h"
+#include "sf_chol_unfused.h"
+#include "sf_chol_diag.h"
+#include "sf_chol_sync.h"
+#include "sf_chol_solve.h"
 
 // ---------------------------------------------------------------------------------------------
 // Fused left-looking panel step (panel width = tile edge = 128).  One workgroup owns a 128-row slab
 // of the panel [k0, k0 + pw) and does, without leaving the CU:
 //   1  T  = C[slab, panel] - L[slab, :k0] L[panel rows, :k0]^T          long K, the k_gemm_nt main loop
-//   2  L  = T W,  W = L_kk^-T (Wt = L_kk^-1 from k_diag_mfma)           K = pw, triangular
+//   2  L  = T W,  W = L_kk^-T (Wt = L_kk^-1 from k_diag_lds)            K = pw, triangular
 //   3  L -> C[slab, panel] in place;  rhs[slab] -= L z_k                (forward substitution rides along)
 //   4  S  = C[slab, slab] - L L^T                                       K = pw, lower triangle only
 // Steps 2 and 4 take their A operand from the accumulators through LDS (32-column chunks): the panel
@@ -991,7 +61,6 @@ static int sf_launch_diag128(double* T, int64_t sT, int pw, int* info, int info_
 // dumps a T block at the moment its registers become the accumulators of the L block -- no second
 // accumulator set.  Step 4 uses the 36-blocks-on-8-waves layout of sf_syrk_diag_tile.
 // pw == 0: nothing but the copy of the diagonal tile to Sout (start of the factorisation).
-#define CLD 33  // row stride (doubles) of the 128 x 32 chunk buffer
 struct sf_panel_args {
     double* C;
     int64_t sC;
@@ -1110,166 +179,6 @@ __device__ __forceinline__ void sf_solve_step(sf_d4 (&acc)[2][4], const double* 
             for (int ni = NI_LO; ni < 4; ++ni)
                 acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], bb[ni], acc[mi][ni], 0, 0, 0);
     }
-}
-
-// ---- dataflow sequence (k_potrf_dataflow): dependencies between workgroups of ONE launch ------------------------
-// A producer finishes its global stores, __syncthreads(), then ONE lane: agent-scope release (write-back of the XCD's L2),
-// s_waitcnt by hand (the compiler may drop its own when the wave's scoreboard is provably empty), relaxed agent-scope
-// store / add on a monotone counter.  A consumer: ONE lane polls the counter with relaxed agent-scope loads (L2-served,
-// s_sleep between polls), then ONE agent-scope acquire (invalidates this CU's L1), __syncthreads(), plain loads.
-// (/opt/skills/guides/MI355X_MICROARCH.md, "Valid forms".)  Every wait is bounded: after SF_DF_TIMEOUT_TICKS of the 100 MHz
-// wall clock the waiter raises the launch's abort flag, which every other wait and the task dispenser observe.
-#define SF_DF_TIMEOUT_TICKS 400000000LL  // 4 s
-// ... and the launch is also aborted when NO task of the launch has completed for SF_DF_STALL_TICKS while a workgroup was
-// waiting (round 6): every task end bumps a progress counter (abort_flag[5]); the longest task of the largest matrix the tables
-// hold (N = 16384: one slab's 1024 K slabs) runs ~5 ms, so 25 ms without a single completion chip-wide means the workgroups
-// that hold the claimed tasks are not running -- a device shared with other processes (profiles/r05_g_shared_gpu_abort.txt: the
-// stall begins mid-launch, an arrival gate at the head of the kernel would not see it).  The caller's fall-back then costs
-// ~25 ms + one factorisation on the launch sequences instead of 4 s.  abort_flag[6] counts the workgroups that started (a
-// diagnostic: grid not co-resident), abort_flag[7] != 0 replaces the bound (units of 2^16 ticks; tuning builds).
-#define SF_DF_STALL_TICKS 2500000LL  // 25 ms
-#define SF_DF_ABORT_TIMEOUT 1
-#define SF_DF_ABORT_STALL 2
-__device__ __forceinline__ int sf_df_load(const int* flag) {
-    return __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// the waiter that raises the abort flag leaves what it was waiting for behind it: abort_flag[1..] = {counter (offset from the abort
-// flag, in ints), target, value} of the first counter that had not arrived (tuning builds print it)
-// (abort_flag[8..9]: address of the process's abort record in host memory, sf_df_diag -- what the caller's warning quotes:
-// {aborted launches, reason, workgroups that had started, grid, ticks the reporting wait had lasted, tasks completed})
-__device__ __forceinline__ void sf_df_report(int* abort_flag, const int* f, int target, int reason = SF_DF_ABORT_TIMEOUT,
-                                             long long waited = 0) {
-    if (__hip_atomic_exchange(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-        if (f) {
-            abort_flag[1] = (int)(f - abort_flag);
-            abort_flag[2] = target;
-            abort_flag[3] = __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        long long* diag = (long long*)__hip_atomic_load((long long*)(abort_flag + 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (diag) {
-            diag[1] = reason;
-            diag[2] = sf_df_load(abort_flag + 6);
-            diag[3] = gridDim.x;
-            diag[4] = waited;
-            diag[5] = sf_df_load(abort_flag + 5);
-            __hip_atomic_fetch_add(diag, 1LL, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-}
-__device__ __forceinline__ long long sf_df_stall_ticks(const int* abort_flag) {
-    const int o = abort_flag[7];
-    return o ? (long long)o << 16 : SF_DF_STALL_TICKS;
-}
-// Waits until *f1 >= t1 and *f2 >= t2 and *f3 >= t3 (NULL flags are skipped), then ONE acquire for all of them.  `probe`
-// (optional) is only looked at, before the acquire: *probe_ok tells whether it had reached its target -- the data it guards
-// is then covered by this acquire and needs no wait of its own later.  Returns false when the launch is being aborted.
-// (s_okp: one int of LDS -- the kernels keep their LDS image at offset 0 of the workgroup's allocation, so no static __shared__
-// variable may exist beside the dynamic buffer: with sm at offset 16 the direct-to-LDS operand loads lose their alignment)
-// `rescue` (queued tasks' waits BEFORE their bodies only): a callable that looks for a ready chain / front task nobody has
-// claimed and claims it; after SF_DF_RESCUE_TICKS inside one wait the polling lane calls it every ~50 us.  When it returns
-// true the wait ends with SF_DF_DEFERRED: the workgroup sets its task aside, runs the chain task it has just claimed and
-// comes back (k_potrf_dataflow).  This is what makes the schedule live BY CONSTRUCTION: chain and front tasks are claimed by
-// whoever finds them ready at the dispenser, and a claim can be missed (see there); a workgroup that waits before a body
-// holds nothing but its task number, and in-body waits only ever depend on tasks that are already running.  The normal path
-// never gets here: waits that long mean the chip is starved of chain progress anyway.
-#define SF_DF_RESCUE_TICKS 50000LL  // 500 us of the 100 MHz wall clock
-#define SF_DF_DEFERRED 4
-struct sf_df_no_rescue {
-    __device__ __forceinline__ bool operator()() const { return false; }
-};
-// The rare part of a wait (every 32nd poll), out of line: the waits are inlined at a dozen sites of a kernel whose task loop is
-// 100 KB of code -- with the abort record and the stall bound inlined as well every site grew, and launches of 32-64 matrices
-// ran 1.2 % slower (same-box A/B, both orders: profiles/r06_b_dataflow_wait_code_size_ab.txt).
-// Returns 0: keep polling; 1: give up (the launch is being aborted, by somebody else or by this call); 2: keep polling, and
-// the wait has lasted long enough for the caller to look for an unclaimed chain task (SF_DF_RESCUE_TICKS).
-struct sf_df_watch {
-    long long t0, tp;  // start of the wait; when the launch's progress counter last moved, as seen from this wait
-    int pg0;
-};
-__device__ __attribute__((noinline)) int sf_df_wait_slow(sf_df_watch& w, int* abort_flag, const int* f1, int t1, const int* f2, int t2,
-                                                         const int* f3, int t3, const bool look_at_progress) {
-    if (sf_df_load(abort_flag) != 0) return 1;
-    const long long now = wall_clock64();
-    const long long waited = now - w.t0;
-    int reason = 0;
-    if (look_at_progress) {  // (every ~0.3 ms: one more L2 round trip in the polling loop)
-        const int pg = sf_df_load(abort_flag + 5);
-        if (pg != w.pg0) {
-            w.pg0 = pg;
-            w.tp = now;
-        } else if (now - w.tp > sf_df_stall_ticks(abort_flag)) {  // nothing completes any more: see SF_DF_STALL_TICKS
-            reason = SF_DF_ABORT_STALL;
-        }
-    }
-    // (abort_flag[4]: the bound in units of 2^20 ticks when the host asked for another one -- tuning builds)
-    if (!reason && waited > SF_DF_TIMEOUT_TICKS && (abort_flag[4] == 0 || (waited >> 20) > abort_flag[4])) reason = SF_DF_ABORT_TIMEOUT;
-    if (reason) {
-        const bool m1 = f1 && sf_df_load(f1) < t1, m2 = f2 && sf_df_load(f2) < t2;
-        sf_df_report(abort_flag, m1 ? f1 : (m2 ? f2 : f3), m1 ? t1 : (m2 ? t2 : t3), reason, waited);
-        return 1;
-    }
-    return waited > SF_DF_RESCUE_TICKS ? 2 : 0;
-}
-template <class RESCUE>
-__device__ __forceinline__ int sf_df_wait_r(const int* f1, int t1, const int* f2, int t2, const int* f3, int t3,
-                                            const int* probe, int tprobe, bool* probe_ok, int* abort_flag, const int tid,
-                                            int* s_okp, RESCUE&& rescue, const bool can_rescue) {
-    if (tid == 0) {
-        int ok = 1;
-        // (short-circuit on purpose: a poller asks for the first counter that is missing only -- polls of all three, every
-        // time, from a few hundred waiting workgroups slowed the launch by 2 %)
-        auto ready = [&]() {
-            return (!f1 || sf_df_load(f1) >= t1) && (!f2 || sf_df_load(f2) >= t2) && (!f3 || sf_df_load(f3) >= t3);
-        };
-        if (!ready()) {
-            sf_df_watch w;
-            w.t0 = w.tp = wall_clock64();
-            w.pg0 = sf_df_load(abort_flag + 5);
-            unsigned it = 0;
-            for (;;) {
-                __builtin_amdgcn_s_sleep(4);
-                if (ready()) break;
-                if ((++it & 31) == 0) {
-                    const int r = sf_df_wait_slow(w, abort_flag, f1, t1, f2, t2, f3, t3, (it & 255) == 0);
-                    if (r == 1) {
-                        ok = 0;
-                        break;
-                    }
-                    if (r == 2 && can_rescue && rescue()) {
-                        ok = SF_DF_DEFERRED;
-                        break;
-                    }
-                }
-            }
-        }
-        if (probe && sf_df_load(probe) >= tprobe) ok |= 2;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        *s_okp = ok;
-    }
-    __syncthreads();
-    const int ok = __builtin_amdgcn_readfirstlane(*s_okp);
-    __syncthreads();  // (s_ok is rewritten by the next wait)
-    if (probe_ok) *probe_ok = (ok & 2) != 0;
-    return ok & (1 | SF_DF_DEFERRED);
-}
-__device__ __forceinline__ bool sf_df_wait(const int* f1, int t1, const int* f2, int t2, const int* f3, int t3,
-                                           const int* probe, int tprobe, bool* probe_ok, int* abort_flag, const int tid,
-                                           int* s_okp) {
-    return sf_df_wait_r(f1, t1, f2, t2, f3, t3, probe, tprobe, probe_ok, abort_flag, tid, s_okp, sf_df_no_rescue(), false) == 1;
-}
-__device__ __forceinline__ bool sf_df_wait(const int* flag, int target, int* abort_flag, const int tid, int* s_okp) {
-    return sf_df_wait(flag, target, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, abort_flag, tid, s_okp);
-}
-// call after __syncthreads(): every wave's stores have been issued and waited for
-__device__ __forceinline__ void sf_df_release() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-__device__ __forceinline__ void sf_df_set(int* flag, int value) {
-    __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void sf_df_add(int* flag, int value) {
-    __hip_atomic_fetch_add(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // MODE 0: the whole step; 1: split-K partial sums only; 2: partial sums added in split order + steps 2-4; 3: as 2, with the
@@ -2278,255 +1187,7 @@ __global__ __launch_bounds__(1024) void k_chol_panel_w(sf_panelw_args g) {
     // without any gain at cfg 2 and cfg 3: profiles/r05_h_wide_tasks_per_workgroup_ab.txt)
     sf_panelw_body<RHS>(g, sf_xcd_remap(blockIdx.x, gridDim.x), smw, threadIdx.x);
 }
-
-// The per-matrix scratch strides are skewed by a few hundred bytes: with strides that are multiples of
-// 32 KiB every workgroup of the batch touches the same HBM channel / L2 bank at the same time (measured:
-// 3.6 us per dependent load in k_diag_mfma before the skew).
-#define SF_TSKEW 40
-// Split-K policy of the fused factorisation: a launch of `wgs` workgroups with `nk` K-slabs each is split
-// `S` ways when it cannot fill the chip (512 resident workgroups): late panels and small batches, where the
-// time of a launch is the time of ONE workgroup's K loop.  S is a power of two, every part keeps >= 8 slabs.
-#define SF_CHIP_WGS 512
-#define SF_SPLIT_MAX 8
-static size_t sf_split_region_tiles(void) { return 2 * SF_CHIP_WGS; }  // partial-sum tiles per region
-__device__ __forceinline__ size_t sf_split_region_tiles_dev(void) { return 2 * SF_CHIP_WGS; }
-static int sf_split_policy(long long wgs, int nk) {
-    int S = 1;
-    // (a split launch stops at 384 of the 512 slots: two slab groups are in flight and the chain's launches need room --
-    // N = 4096, cap 512 / 384 / 256 / 192: B = 16 11.22 / 11.18 / 11.26 / 11.71 ms, 32: 16.06 / 15.78 / 16.09 / 17.28,
-    // 64: 27.42 / 27.05 / 26.89 / 28.7)
-    while (2 * S <= SF_SPLIT_MAX && wgs * 2 * S <= 384 && nk / (2 * S) >= 8) S *= 2;
-    return S;
-}
-// The scratch of one factorisation of `batch` matrices of order n (the real n, before the frame shift of the fused
-// sequences): per matrix a reserved region of SF_LTB_DOUBLES (unused), the panel scratch T and two W^T buffers; then
-// the partial-sum tiles: one region for the chain (top) launches, one per slab group.
-struct sf_potrf_scratch {
-    double* T;  // [batch] x sT
-    int64_t sT;
-    double* W;  // two buffers of [batch] x sW, one after the other
-    int64_t sW;
-    double* part;
-    int batch;
-    size_t doubles;  // the whole scratch: sf_potrf_work_doubles
-    double* Wbuf(int i) const { return W + (size_t)i * batch * sW; }
-    size_t Wdoubles() const { return 2 * (size_t)batch * sW; }  // both buffers
-    // the wide sequence's four most recent inverse tiles W(k): slot k & 3, two 128-row slots to a buffer
-    double* Wslot(int k) const { return Wbuf((k >> 1) & 1) + (size_t)(k & 1) * GT * SF_LDT; }
-};
-static sf_potrf_scratch sf_potrf_scratch_of(double* work, int n, int batch) {
-    sf_potrf_scratch w = {};
-    const size_t b = (size_t)batch;
-    w.sT = (int64_t)(n + SF_NB) * SF_LDT + SF_TSKEW;
-    w.sW = (int64_t)SF_NB * SF_LDT + SF_TSKEW;
-    w.batch = batch;
-    const size_t oT = b * SF_LTB_DOUBLES, oW = oT + b * w.sT, opart = oW + w.Wdoubles() + 64;
-    w.doubles = opart + (size_t)(SF_EXEC_GROUPS + 1) * sf_split_region_tiles() * (GT * GT);
-    if (work) {
-        w.T = work + oT;
-        w.W = work + oW;
-        w.part = work + opart;
-    }
-    return w;
-}
-size_t sf_potrf_work_doubles(int n, int batch) { return sf_potrf_scratch_of(nullptr, n, batch).doubles; }
-
-// The generator fields (matrix-free start) of sf_gemm_args, sf_panel_args and sf_panelw_args, in the frame fp
-template <class Args>
-static void sf_set_gen(Args& g, const sf_gen_args* gen, int fp) {
-    if (!gen) return;
-    g.genY = gen->Y - fp;
-    g.sY = (int64_t)gen->mpad * gen->ldy;
-    g.ldy = gen->ldy;
-    g.mpad = gen->mpad;
-    g.tilemap = gen->tilemap;
-    g.nt128 = gen->nt128;
-}
-// The fields of sf_panel_args / sf_panelw_args that stay the same over one factorisation (A, rhs and the generator in the
-// shifted frame fp)
-template <class Args>
-static Args sf_panel_frame(double* A, int n, int lda, int64_t stride, double* rhs, int ldr, const sf_gen_args* gen, int fp) {
-    Args g = {};
-    g.C = A;
-    g.sC = stride;
-    g.lda = lda;
-    g.n = n;
-    g.rhs = rhs;
-    g.ldr = ldr;
-    g.fp = fp;
-    sf_set_gen(g, gen, fp);
-    return g;
-}
-
-// ---- two-stream lookahead ---------------------------------------------------------------------
-// The diagonal-block chain is a sequence of small latency-bound launches; it runs on the side stream of
-// the caller's sf_exec (owned by the context or by the calling thread) concurrently with the big MFMA
-// launches of the caller's stream.
-#define SF_TRY(x)          \
-    do {                   \
-        int rc__ = (x);    \
-        if (rc__) return rc__; \
-    } while (0)
-// fork: the streams `to` (in order) wait for what the caller's stream s holds so far
-static int sf_exec_fork(sf_exec* ex, hipStream_t s, std::initializer_list<hipStream_t> to) {
-    hipEvent_t e;
-    SF_TRY(sf_exec_event(ex, &e));
-    SF_HIP(hipEventRecord(e, s));
-    for (hipStream_t t : to) SF_HIP(hipStreamWaitEvent(t, e, 0));
-    return SF_OK;
-}
-// join: the caller's stream s continues only after the chain stream c and the launches `also` (NULL: none) are done
-static int sf_exec_join(sf_exec* ex, hipStream_t s, hipStream_t c, std::initializer_list<hipEvent_t> also = {}) {
-    hipEvent_t e;
-    SF_TRY(sf_exec_event(ex, &e));
-    SF_HIP(hipEventRecord(e, c));
-    SF_HIP(hipStreamWaitEvent(s, e, 0));
-    for (hipEvent_t x : also)
-        if (x) SF_HIP(hipStreamWaitEvent(s, x, 0));
-    return SF_OK;
-}
-
-// Factor each n x n matrix in place (lower), panels of SF_NB columns:
-//   Ur  T[below] <- C[k1:, k0:k1] - L[k1:, :k0] L[k0:k1, :k0]^T   LEFT-looking for everything below the
-//                                                                diagonal block: C read once, long K
-//   R   C[jj] -= L[j-rows, k0:k1] L[j-rows, k0:k1]^T for the future DIAGONAL blocks j > k (RIGHT-looking,
-//       K = SF_NB): keeps the next diagonal block ready without a long-K launch of only a few tiles;
-//       its diagonal tiles also apply rhs[j-rows] -= L[j-rows, k0:k1] z[k0:k1]
-//   D   factor the diagonal block together with an identity block -> L_kk and W = L_kk^-T
-//       (k_diag_mfma), L_kk -> matrix, W^T (F)
-//   G   C[k1:, k0:k1] <- T[below] W                               MFMA (triangular B)
-// With rhs != NULL (batch x ldr) the forward substitution L z = rhs is fused (R and D); z overwrites rhs.
-//
-// Lookahead (two streams): only the rows of the NEXT diagonal block are on the critical chain.
-//   side:  D(k) F(k) | wait Ur(k) | Gt(k) Rnext(k -> k+1) | D(k+1) ...
-//   main:  wait Gt(k-1) | Ur(k) | wait F(k) | Gr(k) Rrest(k) | ...
-static int sf_launch_potrf_v1(double* A, int n, int lda, int64_t stride, int* info, const sf_potrf_scratch& ws, double* rhs,
-                              int ldr, hipStream_t s, const sf_gen_args* gen, sf_exec* ex) {
-    const int batch = ws.batch;
-    double* T = ws.T;
-    const int64_t sT = ws.sT, sW = ws.sW;
-    SF_HIP(hipMemsetAsync(info, 0, sizeof(int) * (size_t)batch, s));
-
-    SF_TRY(sf_exec_prepare(ex));
-    hipStream_t c = ex->side;  // side ("critical chain") stream
-    auto next_event = [&](hipEvent_t* e) { return sf_exec_event(ex, e); };
-    hipEvent_t e_gt_prev = nullptr;
-    SF_TRY(sf_exec_fork(ex, s, {c}));
-
-    // R: right-looking update of `nblk` future diagonal blocks starting at row/col j0 with panel [k0,k1)
-    auto launch_r = [&](int j0, int nrows, int k0, int pw, double* cout, int ldcout, int64_t scout,
-                        int64_t dcout, hipStream_t st) -> int {
-        sf_gemm_args g = {};
-        g.A = g.B = A + (int64_t)j0 * lda + k0;
-        g.Cin = A + (int64_t)j0 * lda + j0;
-        g.Cout = cout;
-        g.sA = g.sB = g.sCin = stride;
-        g.sCout = scout;
-        g.lda = g.ldb = g.ldcin = lda;
-        g.ldcout = ldcout;
-        g.M = g.Nc = nrows;
-        g.K = pw;
-        g.remap_after = 0x7fffffff;
-        g.diag_blocks = (nrows + SF_NB - 1) / SF_NB;
-        g.dA = (int64_t)SF_NB * lda;
-        g.dC = dcout;
-        if (rhs && pw > 0) {
-            g.rhs = rhs + j0;
-            g.z = rhs + k0;
-            g.srhs = g.sz = ldr;
-        }
-        // algorithmic flops: lower triangle of every block
-        double useful = 0.0;
-        for (int r = 0; r < nrows; r += SF_NB) {
-            const double bw = (nrows - r < SF_NB) ? nrows - r : SF_NB;
-            useful += 0.5 * bw * (bw + 1);
-        }
-        return launch_gemm(g, batch, true, 2.0 * pw * useful * batch, st);
-    };
-
-    // diagonal block 0 goes to the panel scratch unchanged (K = 0: a copy)
-    {
-        const int pw0 = n < SF_NB ? n : SF_NB;
-        SF_TRY(launch_r(0, pw0, 0, 0, T, SF_LDT, sT, 0, c));
-    }
-    int panel = 0;
-    for (int k0 = 0; k0 < n; k0 += SF_NB, ++panel) {
-        const int k1 = (k0 + SF_NB < n) ? k0 + SF_NB : n;
-        const int pw = k1 - k0;
-        const int nbelow = n - k1;
-        const int ntop = nbelow < SF_NB ? nbelow : SF_NB;  // rows of the next diagonal block
-        double* Wt = ws.Wbuf(panel & 1);  // alternating by panel parity
-        hipEvent_t e_ur = nullptr, e_f, e_gt;
-        // ---- Ur on the main stream: rows [k1, n) -> T rows [2pw, ...)
-        if (nbelow > 0) {
-            if (e_gt_prev) SF_HIP(hipStreamWaitEvent(s, e_gt_prev, 0));
-            sf_gemm_args g = {};
-            g.A = A + (int64_t)k1 * lda;
-            g.B = A + (int64_t)k0 * lda;
-            g.Cin = A + (int64_t)k1 * lda + k0;
-            g.Cout = T + (int64_t)(2 * pw) * SF_LDT;
-            g.sA = g.sB = g.sCin = stride;
-            g.sCout = sT;
-            g.lda = g.ldb = g.ldcin = lda;
-            g.ldcout = SF_LDT;
-            g.M = nbelow;
-            g.Nc = pw;
-            g.K = k0;
-            g.remap_after = 0x7fffffff;
-            sf_set_gen(g, gen, 0);  // (the unshifted frame)
-            if (gen) {
-                g.tm_off = k1 / GT;
-                g.tn_off = k0 / GT;
-            }
-            SF_TRY(launch_gemm(g, batch, true, 2.0 * k0 * (double)nbelow * pw * batch, s));
-            SF_TRY(next_event(&e_ur));
-            SF_HIP(hipEventRecord(e_ur, s));
-        }
-        // ---- D + F on the side stream (T rows [0, pw) already hold the fully updated diagonal block)
-        hipLaunchKernelGGL(k_diag_mfma, dim3(batch), dim3(1024), 0, c, T, sT, pw, info, k0, rhs ? rhs + k0 : nullptr, ldr,
-                           A + (int64_t)k0 * lda + k0, lda, stride, Wt, sW);
-        SF_LAUNCH_CHECK();
-        if (nbelow <= 0) break;
-        SF_TRY(next_event(&e_f));
-        SF_HIP(hipEventRecord(e_f, c));
-        // ---- G: T[below] W.  Top rows (next diagonal block) on the side stream, the rest on main.
-        auto launch_g = [&](int row_lo, int nrows, hipStream_t st) -> int {
-            sf_gemm_args g = {};
-            g.A = T + (int64_t)(2 * pw + row_lo) * SF_LDT;
-            g.B = Wt;
-            g.Cout = A + (int64_t)(k1 + row_lo) * lda + k0;
-            g.sA = sT;
-            g.sB = sW;
-            g.sCout = stride;
-            g.lda = g.ldb = SF_LDT;
-            g.ldcout = lda;
-            g.M = nrows;
-            g.Nc = pw;
-            g.K = pw;
-            g.btri = 1;
-            g.remap_after = 0x7fffffff;
-            return launch_gemm(g, batch, false, (double)nrows * pw * pw * batch, st);
-        };
-        SF_HIP(hipStreamWaitEvent(c, e_ur, 0));
-        SF_TRY(launch_g(0, ntop, c));
-        SF_TRY(next_event(&e_gt));
-        SF_HIP(hipEventRecord(e_gt, c));
-        e_gt_prev = e_gt;
-        // next diagonal block: apply this panel's columns and park it in the panel scratch
-        SF_TRY(launch_r(k1, ntop, k0, pw, T, SF_LDT, sT, 0, c));
-        if (nbelow > ntop) {
-            SF_HIP(hipStreamWaitEvent(s, e_f, 0));
-            SF_TRY(launch_g(ntop, nbelow - ntop, s));
-            // the diagonal blocks after the next one are updated in place
-            const int j0 = k1 + ntop;
-            if (j0 < n)
-                SF_TRY(launch_r(j0, n - j0, k0, pw, A + (int64_t)j0 * lda + j0, lda, stride, (int64_t)SF_NB * lda + SF_NB, s));
-        }
-    }
-    // join: the caller's stream continues only after the side chain is done
-    SF_TRY(sf_exec_join(ex, s, c));
-    return SF_OK;
-}
+#undef SF_W_STAMP
 
 // The fused sequences work in the frame of sf_potrf_front_pad (sf_launch_potrf shifts it): A / rhs point fp (lda + 1) / fp
 // elements before the data and n counts the fp virtual leading rows too (the scratch layout is sized with the real n).
@@ -2618,7 +1279,7 @@ static int sf_panel_step(sf_panel_args g, const sf_potrf_scratch& ws, int k0, in
 }
 
 // Factorisation with the fused panel kernel (default).  Panels of 128 columns; per panel k
-//   D(k)      k_diag_mfma on the updated diagonal tile (parked in the scratch T): L_kk, L_kk^-1, z_k
+//   D(k)      k_diag_lds on the updated diagonal tile (parked in the scratch T): L_kk, L_kk^-1, z_k
 //   top(k)    k_chol_panel for the slab of the NEXT diagonal tile (rows k1 .. k1+128): its updated tile goes to T
 //   rest(k)   k_chol_panel for all slabs below, as G launches on G streams: slab i belongs to group i mod G
 // Lookahead: the chain  D(k) -> [wait group of slab k+1] top(k) -> D(k+1) ...  runs on the side stream;
@@ -3005,7 +1666,6 @@ int sf_launch_potrf_band(int n, int nband, int halfwidth, int batch, const doubl
     SF_LAUNCH_CHECK();
     return SF_OK;
 }
-
 
 // =====================================================================================================================
 // DATAFLOW sequence (round 4): the whole factorisation of a batch as ONE persistent launch.
@@ -3641,6 +2301,10 @@ __global__ __launch_bounds__(512, 4) void k_potrf_dataflow(const sf_df_args a_in
 #endif
     }
 }
+#undef SF_DF_MARK
+#undef SF_DF_MISS_CLAIMS
+#undef SF_DF_PROGRESS
+#undef SF_DF_HELPER
 
 // split factor of a stage's tasks: the largest power of two that keeps the stage within the workgroup slots of its queue's
 // XCD and every K chunk at 8 slabs or more
@@ -4019,52 +2683,4 @@ int sf_launch_potrf(double* A, int n, int lda, int64_t stride, int batch, int* i
     if (seq == 4) return sf_launch_potrf_v4(A, n, lda, stride, info, ws, rhs, ldr, s, gen, fp);
     if (seq == 2 || seq == 3) return sf_launch_potrf_v3(A, n, lda, stride, info, ws, rhs, ldr, s, gen, ex, seq == 3, fp);
     return sf_launch_potrf_v2(A, n, lda, stride, info, ws, rhs, ldr, s, gen, ex, fp);
-}
-
-int sf_launch_logdet_sqmah(const double* L, int n, int lda, int64_t stride, int batch, const double* R,
-                           int ldr, double* zscratch, double* logdet, double* sqmah, hipStream_t s) {
-    if (n % SF_LEAF != 0 || batch <= 0) {
-        sf_set_error("logdet_sqmah: n must be a multiple of %d", SF_LEAF);
-        return SF_EINVAL;
-    }
-    const size_t fixed = sizeof(double) * (SF_LEAF * 65 + SF_LEAF + 8);
-    const size_t with_z = fixed + sizeof(double) * (size_t)n;
-    if (with_z <= 160 * 1024) {
-        static sf_dev_once attr_once;  // devices whose function attributes are set
-        SF_CHECK(sf_lds_limit_once(&attr_once, 160 * 1024, {(const void*)k_trsv_logdet<false>}));
-        hipLaunchKernelGGL(k_trsv_logdet<false>, dim3(batch), dim3(256), with_z, s, L, n, lda, stride, R,
-                           ldr, (double*)nullptr, logdet, sqmah);
-    } else {
-        if (!zscratch) {
-            sf_set_error("logdet_sqmah: n=%d needs a z scratch buffer", n);
-            return SF_ENOMEM;
-        }
-        hipLaunchKernelGGL(k_trsv_logdet<true>, dim3(batch), dim3(256), fixed, s, L, n, lda, stride, R, ldr,
-                           zscratch, logdet, sqmah);
-    }
-    SF_LAUNCH_CHECK();
-    return SF_OK;
-}
-
-// Debug aid for the tuning scripts: one wave spins for `wall_ticks` ticks of the 100 MHz wall clock and
-// reports how many shader-clock ticks (s_memtime) elapsed -> sustained shader clock while other
-// streams are busy.  out[0] = s_memtime ticks, out[1] = wall ticks.
-__global__ void k_clock_probe(long long* out, long long wall_ticks) {
-    const long long w0 = wall_clock64();
-    const long long t0 = __builtin_amdgcn_s_memtime();
-    long long w1 = w0;
-    while (w1 - w0 < wall_ticks) {
-        __builtin_amdgcn_s_sleep(32);
-        w1 = wall_clock64();
-    }
-    const long long t1 = __builtin_amdgcn_s_memtime();
-    if (threadIdx.x == 0) {
-        out[0] = t1 - t0;
-        out[1] = w1 - w0;
-    }
-}
-int sf_launch_clock_probe(long long* out, long long wall_ticks, hipStream_t s) {
-    hipLaunchKernelGGL(k_clock_probe, dim3(1), dim3(64), 0, s, out, wall_ticks);
-    SF_LAUNCH_CHECK();
-    return SF_OK;
 }

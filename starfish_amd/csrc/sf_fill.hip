@@ -10,15 +10,9 @@
 // 4 lanes); the banded/patch kernels are evaluated only in wave sub-tiles that intersect their
 // support.  Compiled with -ffp-contract=off: element formulas keep the reference's operation order.
 #include "sf_common.h"
+#include "sf_device.h"
 
 #define FT 64  // tile edge per workgroup (4 waves, 32 x 32 each)
-
-__device__ __forceinline__ int sf_xcd_remap_f(int bid, int nblk) {
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int q = nblk >> 3, r = nblk & 7;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + slot;
-}
 
 // kernels.py:27-40 with wx = wave[col], wy = wave[row]
 __device__ __forceinline__ double sf_matern_elem(double w_row, double w_col, double amp, double ls,
@@ -300,7 +294,7 @@ __device__ __forceinline__ void sf_fill_tile(const sf_fill_args& a, int b, int t
 
 template <bool BAND>
 __global__ __launch_bounds__(256, BAND ? 2 : 4) void k_fill_tiles(sf_fill_args a, int nt) {
-    const int id = sf_xcd_remap_f(blockIdx.x, gridDim.x);
+    const int id = sf_xcd_remap(blockIdx.x, gridDim.x);
     const int tiles = nt * nt;
     const int b = id / tiles;
     const int t = id - b * tiles;
@@ -595,7 +589,7 @@ template <int KK>
 __global__ __launch_bounds__(256, 4) void k_fill_dense_plain(sf_fill_args a, int nt, const unsigned char* __restrict__ smap) {
     constexpr int SPAN = 4;
     const int nch = (nt + SPAN - 1) / SPAN;
-    const int id = sf_xcd_remap_f(blockIdx.x, gridDim.x);
+    const int id = sf_xcd_remap(blockIdx.x, gridDim.x);
     const int b = id / (nt * nch);
     const int r = id - b * nt * nch;
     const int tm = r / nch, ch = r - tm * nch;

@@ -8,6 +8,7 @@
 //   k_scale, k_resid_y   rescale / renorm, residual and the rank-m factor Y   spectrum_model.py:316-335
 //   k_emu_prep/z/post GP conditional of the PCA weights     Starfish/emulator/emulator.py:330-394
 #include "sf_common.h"
+#include "sf_device.h"
 #include "sf_transform.h"
 typedef double sf_d4x __attribute__((ext_vector_type(4)));
 
@@ -713,8 +714,7 @@ __global__ __launch_bounds__(256) void k_eval_rows(sf_eval_args a) {
 }
 
 __device__ __forceinline__ double sf_block_sum(double v, double* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    v = sf_wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -833,11 +833,6 @@ __global__ __launch_bounds__(256) void k_cheb_rows(const double* __restrict__ wa
 //                example m = 4, M = 330 -- took 0.5 ms per 128 walkers.)
 //   k_emu_post   per walker: cov = v22 - z^T z, chol(cov)
 #define EMU_WCHUNK 8
-__device__ __forceinline__ double sf_wave_sum_t(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 __global__ __launch_bounds__(256) void k_emu_prep(sf_emu_args a) {
     __shared__ int bad;
     __shared__ double red[4];
@@ -941,7 +936,7 @@ __global__ __launch_bounds__(256) void k_emu_post(sf_emu_args a) {
         }
 #pragma unroll
         for (int q = 0; q < EMU_PAIRS; ++q) {
-            const double v = sf_wave_sum_t(acc[q]);
+            const double v = sf_wave_sum(acc[q]);
             if ((tid & 63) == 0) wsum[tid >> 6][q] = v;
         }
         __syncthreads();
