@@ -342,6 +342,29 @@ int sf_profile_read(double* ms_by_stage, double* gemm_flops, long* gemm_launches
 int sf_emulator_v11_build(const double* d_grid, int M, int P, int m, const double* d_hyper, const double* d_iphiphi,
                           double* d_A, int npad, int lda, void* stream);
 
+/* The same matrix (emulator.py:126-128, kernels.py:5-49) for B hyper-parameter vectors in one launch: what Emulator.train
+ * (emulator.py:484-524) evaluates when the points of a simplex iteration go to the device as one batch.
+ * B matrices v11(hyper_b) in the layout of sf_potrf_batch; d_R (may be NULL): B x ldr copies of w_hat, zero padded.
+ * d_hyper: B rows of {lambda_xi, variances[m], lengthscales[m*P]} (raw values, not logs), row stride hyper_stride >= 1 + m + m P.
+ * Matrix b at d_A + b*stride (doubles), row stride lda >= npad, npad a multiple of 64 and >= m M, identity block from m M to
+ * npad; columns npad..lda of a row are never touched.  lda and stride must be even and d_A 16-byte aligned (16-byte stores).
+ * lower_only: 64 x 64 tiles strictly above the diagonal are skipped (entries above the diagonal INSIDE a diagonal tile may be
+ * written; a factorisation never reads them), as in sf_cov_fill_batch.  P <= 8; SF_EINVAL otherwise, nothing is written. */
+int sf_emulator_v11_build_batch(const double* d_grid, int M, int P, int m, const double* d_hyper, int hyper_stride, int B,
+                                const double* d_iphiphi, double* d_A, int npad, int lda, int64_t stride, int lower_only,
+                                const double* d_w_hat, double* d_R, int ldr, void* stream);
+
+/* Emulator.log_likelihood (Starfish/emulator/emulator.py:602-619) for B hyper-parameter vectors in ONE enqueue:
+ * build (lower triangle) + sf_potrf_batch + sf_logdet_sqmah_batch + finish.  d_lnl[B] = -(logdet + sqmah)/2, -inf where
+ * d_info[b] != 0 (k > 0: first non-positive pivot of matrix b; SF_INFO_INTERNAL as for every batched factorisation).
+ * d_logdet / d_sqmah may be NULL.  No allocation: d_work (256-byte aligned) of sf_emulator_loglike_workspace_bytes(M, m, B),
+ * which holds the B matrices, the right-hand sides and the workspace of sf_potrf_batch.  Arguments are checked before
+ * anything is enqueued (SF_EINVAL; SF_ENOMEM for a short workspace); the call never synchronises. */
+size_t sf_emulator_loglike_workspace_bytes(int M, int m, int B);
+int sf_emulator_loglike_batch(const double* d_grid, int M, int P, int m, const double* d_hyper, int hyper_stride, int B,
+                              const double* d_iphiphi, const double* d_w_hat, double* d_lnl, double* d_logdet,
+                              double* d_sqmah, int* d_info, void* d_work, size_t work_bytes, void* stream);
+
 /* Process-global switch of the persistent-kernel ("dataflow") Cholesky sequence: enable = 0 makes every later factorisation
  * take a launch sequence (kernels without waits inside), 1 restores the default choice, < 0 only queries.  Returns the
  * previous setting.  The recovery path after SF_INFO_INTERNAL.

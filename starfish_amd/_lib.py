@@ -93,6 +93,16 @@ SIGNATURES = {
     "sf_extinct_ccm89": (C.c_int, [_VP, C.c_int, _VP, C.c_int, C.c_double, C.c_double, _VP, _VP]),
     "sf_extinct": (C.c_int, [_VP, C.c_int, _VP, C.c_int, C.c_double, C.c_double, C.c_int, _VP, _VP]),
     "sf_emulator_v11_build": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, _VP]),
+    "sf_emulator_v11_build_batch": (
+        C.c_int,
+        [_VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_int64, C.c_int, _VP, _VP,
+         C.c_int, _VP],
+    ),
+    "sf_emulator_loglike_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sf_emulator_loglike_batch": (
+        C.c_int,
+        [_VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP],
+    ),
     "sf_potrf_batch": (
         C.c_int,
         [_VP, C.c_int, C.c_int, C.c_int64, C.c_int, _VP, _VP, C.c_size_t, _VP],

@@ -1750,6 +1750,73 @@ extern "C" int sf_emulator_v11_build(const double* d_grid, int M, int P, int m, 
                                      double* d_A, int npad, int lda, void* stream) {
     return sf_launch_v11_build(d_grid, M, P, m, d_hyper, d_iphiphi, d_A, npad, lda, (hipStream_t)stream);
 }
+extern "C" int sf_emulator_v11_build_batch(const double* d_grid, int M, int P, int m, const double* d_hyper, int hyper_stride,
+                                           int B, const double* d_iphiphi, double* d_A, int npad, int lda, int64_t stride,
+                                           int lower_only, const double* d_w_hat, double* d_R, int ldr, void* stream) {
+    return sf_launch_v11_build_batch(d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, d_A, npad, lda, stride, lower_only,
+                                     d_w_hat, d_R, ldr, (hipStream_t)stream);
+}
+
+// The training objective for B hyper-parameter rows: the B matrices (npad = m M rounded up to the Cholesky leaf, row stride
+// npad + 16 as Emulator.log_likelihood lays its one matrix out), the B x npad right-hand sides, logdet / sqmah / the
+// factorisation's info, then the workspace of sf_potrf_batch exactly as sf_potrf_workspace_bytes sizes and sf_potrf_batch
+// carves it (z scratch of the solve, then the factorisation's scratch).
+struct EmuTrainWork {
+    int npad, lda;
+    int64_t stride;
+    size_t oA, oR, oLogdet, oSqmah, oInfo, oPotrf, potrf_bytes, bytes;
+};
+static EmuTrainWork emu_train_work(int M, int m, int B) {
+    EmuTrainWork w = {};
+    if (M <= 0 || m <= 0 || B <= 0 || (int64_t)m * M > (1 << 30)) return w;
+    w.npad = (m * M + SF_LEAF - 1) / SF_LEAF * SF_LEAF;
+    w.lda = w.npad + 16;
+    w.stride = (int64_t)w.npad * w.lda;
+    const size_t b = (size_t)B;
+    w.oA = 0;
+    w.oR = w.oA + sf_align_up(sizeof(double) * b * (size_t)w.stride, 256);
+    w.oLogdet = w.oR + sf_align_up(sizeof(double) * b * w.npad, 256);
+    w.oSqmah = w.oLogdet + sf_align_up(sizeof(double) * b, 256);
+    w.oInfo = w.oSqmah + sf_align_up(sizeof(double) * b, 256);
+    w.oPotrf = w.oInfo + sf_align_up(sizeof(int) * b, 256);
+    w.potrf_bytes = sf_potrf_workspace_bytes(w.npad, B);
+    w.bytes = w.oPotrf + w.potrf_bytes;
+    return w;
+}
+extern "C" size_t sf_emulator_loglike_workspace_bytes(int M, int m, int B) { return emu_train_work(M, m, B).bytes; }
+extern "C" int sf_emulator_loglike_batch(const double* d_grid, int M, int P, int m, const double* d_hyper, int hyper_stride,
+                                         int B, const double* d_iphiphi, const double* d_w_hat, double* d_lnl, double* d_logdet,
+                                         double* d_sqmah, int* d_info, void* d_work, size_t work_bytes, void* stream) {
+    const EmuTrainWork w = emu_train_work(M, m, B);
+    if (!w.bytes || !d_grid || !d_hyper || !d_iphiphi || !d_w_hat || !d_lnl || !d_info || !d_work || P <= 0 || B > 65535 ||
+        (int64_t)hyper_stride < 1 + (int64_t)m + (int64_t)m * P || ((uintptr_t)d_work & 255)) {
+        sf_set_error("sf_emulator_loglike_batch: bad argument (d_lnl, d_info and a 256-byte aligned d_work are required, "
+                     "hyper_stride >= 1 + m + m P, B <= 65535)");
+        return SF_EINVAL;
+    }
+    if (work_bytes < w.bytes) {
+        sf_set_error("sf_emulator_loglike_batch: workspace of %zu bytes, %zu needed", work_bytes, w.bytes);
+        return SF_ENOMEM;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)d_work;
+    double* A = (double*)(base + w.oA);
+    double* R = (double*)(base + w.oR);
+    double* logdet = d_logdet ? d_logdet : (double*)(base + w.oLogdet);
+    double* sqmah = d_sqmah ? d_sqmah : (double*)(base + w.oSqmah);
+    int* info_c = (int*)(base + w.oInfo);
+    void* pw = base + w.oPotrf;
+    // (every argument check of the stages is made by the first one before it enqueues anything: P <= 8 is the build's)
+    int rc = sf_launch_v11_build_batch(d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, A, w.npad, w.lda, w.stride, 1, d_w_hat,
+                                       R, w.npad, s);
+    if (rc) return rc;
+    rc = sf_potrf_batch(A, w.npad, w.lda, w.stride, B, info_c, pw, w.potrf_bytes, stream);
+    if (rc) return rc;
+    rc = sf_logdet_sqmah_batch(A, w.npad, w.lda, w.stride, B, R, w.npad, pw, w.potrf_bytes, logdet, sqmah, stream);
+    if (rc) return rc;
+    ProfScope ps(s, PS_SOLVE);
+    return sf_launch_finish(B, logdet, sqmah, info_c, nullptr, d_lnl, d_info, s);
+}
 
 // Recovery switch of the callers (process-global): after a batch came back SF_INFO_INTERNAL the host layer turns the
 // persistent-kernel sequence off and re-runs the batch on a launch sequence (starfish_amd/_device.py).

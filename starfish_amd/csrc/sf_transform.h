@@ -113,3 +113,6 @@ int sf_launch_finish(int B, const double* logdet, const double* sqmah, const int
                      double* lnl, int* info_out, hipStream_t s);
 int sf_launch_v11_build(const double* grid, int M, int P, int m, const double* hyper, const double* iphiphi, double* A, int npad,
                         int lda, hipStream_t s);
+int sf_launch_v11_build_batch(const double* grid, int M, int P, int m, const double* hyper, int hyper_stride, int B,
+                              const double* iphiphi, double* A, int npad, int lda, int64_t stride, int lower_only,
+                              const double* w_hat, double* R, int ldr, hipStream_t s);

@@ -8,6 +8,7 @@ weights), ``bulk_fluxes``, ``norm_factor``, hyper-parameter accessors, ``load`` 
 ``log_likelihood`` / ``train`` reuse the batched Cholesky kernels.
 Out of scope (one-time offline set-up): ``from_grid`` (PCA), plotting.
 """
+import ctypes as C
 import logging
 import os
 import warnings
@@ -361,6 +362,29 @@ class Emulator:
     def from_grid(cls, grid, **pca_kwargs):
         raise NotImplementedError("Emulator.from_grid (PCA of a spectral library) is offline set-up, out of scope")
 
+    def _train_resident(self, lib, dev):
+        """The resident training state (grid, iPhiPhi, w_hat, the scalar path's matrix and workspace), shared by
+        :meth:`log_likelihood` and :meth:`log_likelihood_batch`.  Keyed on the identity of the arrays it was uploaded from:
+        reassigning grid_points, iPhiPhi or w_hat re-uploads; after an IN-PLACE edit of one of them set
+        ``emu._train_dev = None``."""
+        torch = D._torch()
+        td = self._train_dev
+        if (td is None or td["dev"] != dev or td["w_hat"] is not self.w_hat or td["grid_src"] is not self.grid_points
+                or td["iphiphi_src"] is not self.iPhiPhi):
+            n = self.ncomps * self.grid_points.shape[0]
+            npad = -(-n // 64) * 64
+            lda = npad + 16
+            R = np.zeros(npad)
+            R[:n] = self.w_hat
+            td = self._train_dev = dict(
+                dev=dev, w_hat=self.w_hat, grid_src=self.grid_points, iphiphi_src=self.iPhiPhi,
+                grid=D.to_dev(self.grid_points, dev), iphiphi=D.to_dev(self.iPhiPhi, dev),
+                R=D.to_dev(R, dev), A=D.empty((npad, lda), dev), out=D.empty((2,), dev), info=D.empty((1,), dev, torch.int32),
+                ws=D.workspace(lib.sf_potrf_workspace_bytes(npad, 1), dev),
+                w_hat_dev=D.to_dev(self.w_hat, dev), ws_batch=None,
+            )
+        return td
+
     def log_likelihood(self, _retry=True):
         """-(logdet v11 + w_hat^T v11^-1 w_hat) / 2  (Starfish/emulator/emulator.py:602-619), entirely on the device:
         v11 is built from the hyper-parameters by ``sf_emulator_v11_build`` (grid, iPhiPhi and w_hat stay resident), then
@@ -377,19 +401,7 @@ class Emulator:
         n = m * M
         npad = -(-n // 64) * 64
         lda = npad + 16
-        td = self._train_dev
-        # resident training state, keyed on the identity of the arrays it was uploaded from: reassigning grid_points,
-        # iPhiPhi or w_hat re-uploads; after an IN-PLACE edit of one of them set ``emu._train_dev = None``
-        if (td is None or td["dev"] != dev or td["w_hat"] is not self.w_hat or td["grid_src"] is not self.grid_points
-                or td["iphiphi_src"] is not self.iPhiPhi):
-            R = np.zeros(npad)
-            R[:n] = self.w_hat
-            td = self._train_dev = dict(
-                dev=dev, w_hat=self.w_hat, grid_src=self.grid_points, iphiphi_src=self.iPhiPhi,
-                grid=D.to_dev(self.grid_points, dev), iphiphi=D.to_dev(self.iPhiPhi, dev),
-                R=D.to_dev(R, dev), A=D.empty((npad, lda), dev), out=D.empty((2,), dev), info=D.empty((1,), dev, torch.int32),
-                ws=D.workspace(lib.sf_potrf_workspace_bytes(npad, 1), dev),
-            )
+        td = self._train_resident(lib, dev)
         s = D.stream_ptr(dev)
         A = td["A"]
         if self._v11_assigned:
@@ -418,10 +430,120 @@ class Emulator:
         ld, sq = td["out"].cpu().tolist()
         return -(ld + sq) / 2
 
-    def train(self, **opt_kwargs):
+    def _hyper_rows(self, P):
+        """Rows in the units of :meth:`get_param_vector` (logs) -> the raw rows {lambda_xi, variances[m], lengthscales[m][P]}
+        of the C-ABI, in the order the property getters read ``hyperparams``."""
+        keys = list(self.hyperparams)
+        order = ([keys.index("log_lambda_xi")] + [i for i, k in enumerate(keys) if k.startswith("log_variance:")]
+                 + [i for i, k in enumerate(keys) if k.startswith("log_lengthscale:")])
+        with np.errstate(over="ignore"):
+            return np.ascontiguousarray(np.exp(P[:, order]))
+
+    def log_likelihood_batch(self, P, return_info=False, _retry=True):
+        """:meth:`log_likelihood` (Starfish/emulator/emulator.py:602-619) for the ``B`` rows of ``P`` -- hyper-parameter
+        vectors in the units of :meth:`get_param_vector`, i.e. logs -- as ONE device call (``sf_emulator_loglike_batch``:
+        the B matrices built, factored and solved in one enqueue): one upload of the raw hyper-parameter rows, one download.
+        Returns ``lnl (B,)``, ``-inf`` where ``info != 0`` (k > 0: the k-th leading minor of that row's v11 is not positive
+        definite -- where the scalar call raises), and with ``return_info`` also ``info``.  The emulator's own
+        hyper-parameters, ``v11`` and ``_trained`` are not touched.  Batches that do not fit the free device memory are cut
+        into chunks."""
+        from .. import _lib
+
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        if P.ndim != 2 or P.shape[1] != len(self.hyperparams):
+            raise ValueError("P must be (B, len(get_param_vector()))")
+        if self._v11_assigned:
+            raise ValueError("log_likelihood_batch: this emulator's v11 was assigned by hand and has no hyper-parameter row "
+                             "(set_param_vector / set_param_dict make the hyper-parameters rule again)")
+        lib = _lib.require_gpu()
+        torch = D._torch()
+        dev = D.device_of()
+        M, npar = self.grid_points.shape
+        m = self.ncomps
+        td = self._train_resident(lib, dev)
+        hyper = self._hyper_rows(P)
+        B = len(hyper)
+        lnl = np.empty(B)
+        info = np.empty(B, dtype=np.int32)
+        # chunks sized from the free device memory as DeviceOrder.max_batch does (same 15 % reserve); the workspace is
+        # a fixed part (the factorisation's partial-sum regions) plus a part per matrix
+        one, two = (int(lib.sf_emulator_loglike_workspace_bytes(M, m, b)) for b in (1, 2))
+        free, _total = torch.cuda.mem_get_info(dev)
+        if td["ws_batch"] is not None:
+            free += td["ws_batch"].numel()
+        cap = int(min(max(1, (int(free * 0.85) - (2 * one - two)) // (two - one)), 65535))
+        s = D.stream_ptr(dev)
+        for lo in range(0, B, cap):
+            nb = min(cap, B - lo)
+            need = int(lib.sf_emulator_loglike_workspace_bytes(M, m, nb))
+            if td["ws_batch"] is None or td["ws_batch"].numel() < need:
+                td["ws_batch"] = None
+                td["ws_batch"] = D.workspace(need, dev)
+            ws = td["ws_batch"]
+            d_hyper = D.to_dev(hyper[lo:lo + nb], dev)
+            out = torch.empty(12 * nb, dtype=torch.uint8, device=dev)  # lnl[nb] then info[nb]: one download
+            _lib.check(lib.sf_emulator_loglike_batch(
+                D.ptr(td["grid"]), M, npar, m, D.ptr(d_hyper), hyper.shape[1], nb, D.ptr(td["iphiphi"]), D.ptr(td["w_hat_dev"]),
+                C.c_void_p(out.data_ptr()), None, None, C.c_void_p(out.data_ptr() + 8 * nb), D.ptr(ws), ws.numel(), s),
+                "sf_emulator_loglike_batch")
+            host = out.cpu().numpy()
+            lnl[lo:lo + nb] = host[:8 * nb].view(np.float64)
+            info[lo:lo + nb] = host[8 * nb:].view(np.int32)
+        if np.any(info == D.INFO_INTERNAL):
+            if not _retry:
+                raise RuntimeError(D.INFO_MESSAGES[D.INFO_INTERNAL])
+            D.recover_from_internal(lib, "Emulator.log_likelihood_batch", B)
+            return self.log_likelihood_batch(P, return_info, _retry=False)
+        return (lnl, info) if return_info else lnl
+
+    def _batched_objective(self, evaluate):
+        """The objective of :meth:`train` for the rows of a batch, ``evaluate(X) -> (lnl, info)`` being the batch evaluator
+        (:meth:`log_likelihood_batch`; a host stand-in in the CPU tests).  Row for row what the scalar objective gives:
+        ``+inf`` without a device call for rows with a non-finite entry or a lengthscale below twice the grid separation
+        (emulator.py:497-503), and for a row whose v11 is not positive definite the scalar path's ``LinAlgError`` -- raised
+        by the ``raiser`` hook, i.e. only when the method actually uses that row's value."""
+
+        keys = list(self.hyperparams)
+        ls_idx = [i for i, k in enumerate(keys) if k.startswith("log_lengthscale:")]
+
+        def nll_batch(X):
+            X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+            vals = np.full(len(X), np.inf)
+            info = np.zeros(len(X), dtype=np.int64)
+            ok = np.all(np.isfinite(X), axis=1)
+            with np.errstate(all="ignore"):
+                ls = np.exp(X[:, ls_idx]).reshape(len(X), self.ncomps, -1)
+                ok &= ~np.any(ls < 2 * self._grid_sep, axis=(1, 2))
+            if ok.any():
+                lnl, inf = evaluate(X[ok])
+                vals[ok] = -np.asarray(lnl, dtype=np.float64)
+                info[ok] = inf
+
+            def raiser(i):
+                if info[i] != 0:
+                    self.set_param_vector(X[i])  # (where the scalar objective stood when it raised)
+                if info[i] > 0:
+                    raise np.linalg.LinAlgError(f"{int(info[i])}-th leading minor of the array is not positive definite")
+                if info[i] < 0:
+                    raise RuntimeError(D.INFO_MESSAGES.get(int(info[i]), f"emulator likelihood failed (info {int(info[i])})"))
+
+            return vals, raiser
+
+        return nll_batch
+
+    def train(self, batch_simplex=False, **opt_kwargs):
         """Nelder-Mead over the hyper-parameter vector (Starfish/emulator/emulator.py:484-524); every
-        likelihood evaluation factors v11 on the GPU."""
+        likelihood evaluation factors v11 on the GPU.
+
+        The default is the reference's loop: ``scipy.optimize.minimize`` over the scalar objective, one device call per
+        point.  With ``batch_simplex=True`` (a plain Nelder-Mead run: no other ``method``, no bounds) the points an iteration
+        of the simplex method may ask for go to the device as ONE batch (:mod:`starfish_amd._neldermead`,
+        :meth:`log_likelihood_batch`): the initial simplex, the four candidates of an iteration, the vertices of a shrink
+        step.  The decisions, ``nit`` / ``nfev`` / ``status`` and the exceptions of used points are scipy's; the result also
+        carries ``nbatches`` and ``nfev_speculative``.  The emulator is left as the reference's loop leaves it."""
         from scipy.optimize import minimize
+
+        from .._neldermead import minimize_neldermead_batched, split_minimize_kwargs
 
         def nll(P):
             if np.any(~np.isfinite(P)):
@@ -433,7 +555,19 @@ class Emulator:
 
         kwargs = {"method": "Nelder-Mead", "options": {"maxiter": 10000}}
         kwargs.update(opt_kwargs)
-        soln = minimize(nll, self.get_param_vector(), **kwargs)
+        nm_opts = None
+        if batch_simplex:
+            nm_opts, why_not = split_minimize_kwargs(kwargs)
+            if nm_opts is None:
+                warnings.warn(f"Emulator.train: batch_simplex=True does not cover {why_not}; running the serial loop",
+                              RuntimeWarning, stacklevel=2)
+        if nm_opts is None:
+            soln = minimize(nll, self.get_param_vector(), **kwargs)
+        else:
+            objective = self._batched_objective(lambda X: self.log_likelihood_batch(X, return_info=True))
+            soln = minimize_neldermead_batched(objective, self.get_param_vector(), **nm_opts)
+            if np.all(np.isfinite(soln.last_x)):
+                self.set_param_vector(soln.last_x)  # where the reference's last objective call left the emulator
         if not soln.success:
             self.log.warning("Optimization did not succeed.")
             self.log.info(soln.message)
