@@ -32,7 +32,7 @@ def persistent_status(lib):
     return dict(zip(keys, (int(v) for v in buf)))
 
 
-def recover_from_internal(lib, where, count):
+def recover_from_internal(lib, where, count, stacklevel=3):
     """A dense call came back with SF_INFO_INTERNAL: the persistent-kernel Cholesky gave a launch up and the whole batch
     is invalid (include/starfish_amd.h).  The reference would never turn that into a rejected proposal
     (spectrum_model.py:400 raises out of cho_factor), so: say so loudly -- with what the aborting workgroup recorded --,
@@ -51,9 +51,26 @@ def recover_from_internal(lib, where, count):
         "one process per GPU.  It is now disabled for this whole process, on every device and thread "
         "(sf_persistent_potrf(0)), and the batch is re-run on the launch sequence.",
         RuntimeWarning,
-        stacklevel=3,
+        stacklevel=stacklevel,
     )
     lib.sf_persistent_potrf(0)
+
+
+def retry_internal(lib, where, evaluate, count=None):
+    """THE policy for SF_INFO_INTERNAL of the dense path.  ``evaluate(again) -> (result, info)`` runs the call and fetches
+    its status codes; ``again`` is False for the first run and True for the one repeat after
+    :func:`recover_from_internal` (never a silent -inf: warn, switch the persistent kernel off, evaluate again).  A -5 that
+    survives the repeat is never an ordinary per-unit status -- no value of the call is valid: RuntimeError.  ``count``:
+    the units the warning names (default: the -5 entries of ``info``)."""
+    result, info = evaluate(False)
+    bad = int(np.count_nonzero(np.asarray(info) == INFO_INTERNAL))
+    if not bad:
+        return result
+    recover_from_internal(lib, where, bad if count is None else count, stacklevel=4)  # (the frame that called our caller)
+    result, info = evaluate(True)
+    if np.any(np.asarray(info) == INFO_INTERNAL):
+        raise RuntimeError(INFO_MESSAGES[INFO_INTERNAL])
+    return result
 
 
 def _torch():
@@ -79,19 +96,62 @@ def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
-def stream_ptr(dev):
-    torch = _torch()
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def empty(shape, dev, dtype=None):
     torch = _torch()
     return torch.empty(shape, dtype=dtype or torch.float64, device=dev)
 
 
+def current_stream(dev):
+    return _torch().cuda.current_stream(dev)
+
+
+def stream_ptr(dev):
+    return C.c_void_p(current_stream(dev).cuda_stream)
+
+
 def workspace(nbytes, dev):
     torch = _torch()
     return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dev)
+
+
+def grow_workspace(slot, key, need, dev):
+    """The byte buffer ``slot[key]``, grown to at least ``need`` bytes.  ``slot`` is the mapping that owns the buffer (an
+    object's ``vars()`` or a dict): a buffer that is too small is dropped BEFORE the new one is allocated, which no
+    reference held by a caller may prevent.  The buffer is handed to kernels on whatever stream is current (EchelleModel
+    rotates orders over side streams), so that stream is recorded on it: the caching allocator then does not recycle a
+    dropped buffer before the work queued on it has finished."""
+    if slot[key] is None or slot[key].numel() < need:
+        slot[key] = None
+        slot[key] = workspace(need, dev)
+    slot[key].record_stream(current_stream(dev))
+    return slot[key]
+
+
+HBM_RESERVE = 0.15  # share of the free HBM that the chunk sizes leave alone
+
+
+def units_that_fit(dev, fixed_bytes, per_unit_bytes, held_bytes=0, limit=None):
+    """How many units of ``per_unit_bytes`` workspace fit the free HBM of ``dev`` next to ``fixed_bytes``, at least 1, at
+    most ``limit``.  ``held_bytes``: the buffer the caller is about to replace counts as free."""
+    free, _total = _torch().cuda.mem_get_info(dev)
+    cap = max(1, (int((free + held_bytes) * (1.0 - HBM_RESERVE)) - fixed_bytes) // per_unit_bytes)
+    return cap if limit is None else min(cap, int(limit))
+
+
+def result_buffers(B, dev, resid_cols=None):
+    """Device outputs of a likelihood call of ``B`` units: the (4, B) "quad" lnl / logdet / sqmah / log_scale (ONE
+    device->host copy for the four double outputs), the int32 ``info`` and, asked for, the (B, resid_cols) residuals."""
+    torch = _torch()
+    return (empty((4, B), dev), empty((B,), dev, torch.int32),
+            empty((B, resid_cols), dev) if resid_cols is not None else None)
+
+
+def fetch_results(quad, info, resid=None):
+    """Download what :func:`result_buffers` allocated: dict of numpy arrays lnl, logdet, sqmah, log_scale, info (+ resid)."""
+    out = dict(zip(("lnl", "logdet", "sqmah", "log_scale"), quad.cpu().numpy()), info=info.cpu().numpy())
+    if resid is not None:
+        out["resid"] = resid.cpu().numpy()
+    return out
 
 
 def band_halfwidth_bound(wave, rows, n_grid, has_global, n_local, n_cheb):
@@ -179,8 +239,7 @@ class MultiPlan:
         U = sum(self.sizes)
         with torch.cuda.device(self.dev):
             self.P = [r if torch.is_tensor(r) else to_dev(np.atleast_2d(r), self.dev) for r in rows_list]
-            self.quad = empty((4, U), self.dev)  # lnl, logdet, sqmah, log_scale: one device->host copy
-            self.info = empty((U,), self.dev, torch.int32)
+            self.quad, self.info, _ = result_buffers(U, self.dev)
             # units that fit: the workspace is linear in the unit count up to the fixed Cholesky scratch.  With one
             # descriptor per order the largest estimate of any order counts (e.g. the only order whose descriptor
             # needs the broadening buffers: the call allocates them for all)
@@ -193,13 +252,9 @@ class MultiPlan:
                 w2 = self._workspace_bytes(C.byref(one), 1, desc)
                 pu = max(w2 - w1, 1)
                 per_unit, fixed = max(per_unit, pu), max(fixed, w1 - pu)
-            free, _total = torch.cuda.mem_get_info(self.dev)
             lead = orders[0]
-            if lead._ws_multi is not None:
-                free += lead._ws_multi.numel()
-            cap = max(1, (int(free * 0.85) - fixed) // per_unit)
-            if max_units:
-                cap = min(cap, int(max_units))
+            held = lead._ws_multi.numel() if lead._ws_multi is not None else 0
+            cap = units_that_fit(self.dev, fixed, per_unit, held, max_units or None)
             self.pieces, cur, cur_n = [], [], 0
             for i, n in enumerate(self.sizes):
                 lo = 0
@@ -226,10 +281,7 @@ class MultiPlan:
                 need = max(need, nb)
                 u0 = int(offs[piece[0][0]] + piece[0][1])  # the pieces of one call are contiguous in unit order
                 self.calls.append((segs, len(piece), u0, sum(hi - lo for _, lo, hi in piece), models))
-            if lead._ws_multi is None or lead._ws_multi.numel() < need:
-                lead._ws_multi = None
-                lead._ws_multi = workspace(need, self.dev)
-            self.ws = lead._ws_multi
+            self.ws = grow_workspace(vars(lead), "_ws_multi", need, self.dev)
 
     @staticmethod
     def _desc_array(mds):
@@ -262,15 +314,13 @@ class MultiPlan:
                 _lib.check(rc, name)
 
     def collect(self):
-        out = collect_multi(self.quad, self.info, self.sizes)
-        bad = sum(int((o["info"] == INFO_INTERNAL).sum()) for o in out)
-        if bad:  # an aborted persistent launch invalidates the whole call: re-run on the launch sequence, once
-            recover_from_internal(self.lib, "sf_loglike_multi_batch", bad)
-            self.enqueue()
+        def fetch(again):  # (the first run was enqueued by the caller)
+            if again:
+                self.enqueue()
             out = collect_multi(self.quad, self.info, self.sizes)
-            if any((o["info"] == INFO_INTERNAL).any() for o in out):  # (never an ordinary per-unit status: nothing is valid)
-                raise RuntimeError(INFO_MESSAGES[INFO_INTERNAL])
-        return out
+            return out, np.concatenate([o["info"] for o in out])
+
+        return retry_internal(self.lib, "sf_loglike_multi_batch", fetch)
 
 
 def loglike_multi(orders, md, rows_list, max_units=None, sync=True):
@@ -284,14 +334,9 @@ def loglike_multi(orders, md, rows_list, max_units=None, sync=True):
 
 
 def collect_multi(quad, info, sizes):
-    host = quad.cpu().numpy()
-    hinfo = info.cpu().numpy()
-    out, u = [], 0
-    for n in sizes:
-        out.append(dict(lnl=host[0, u:u + n], logdet=host[1, u:u + n], sqmah=host[2, u:u + n],
-                        log_scale=host[3, u:u + n], info=hinfo[u:u + n]))
-        u += n
-    return out
+    host = fetch_results(quad, info)
+    ends = np.cumsum(sizes)
+    return [{key: v[hi - n:hi] for key, v in host.items()} for n, hi in zip(sizes, ends)]
 
 
 class DeviceOrder:
@@ -386,26 +431,25 @@ class DeviceOrder:
     def workspace_bytes(self, md, B):
         return self.lib.sf_workspace_bytes(self.ctx, C.byref(md), int(B))
 
-    def max_batch(self, md, reserve_fraction=0.15):
+    def max_batch(self, md):
         """Largest batch whose workspace fits the free HBM (leaving a safety margin)."""
-        torch = _torch()
-        free, _total = torch.cuda.mem_get_info(self.dev)
-        if self._ws is not None:
-            free += self._ws.numel()
-        budget = int(free * (1.0 - reserve_fraction))
-        per = self.workspace_bytes(md, 1)
-        return max(1, budget // max(per, 1))
+        held = self._ws.numel() if self._ws is not None else 0
+        return units_that_fit(self.dev, 0, max(self.workspace_bytes(md, 1), 1), held)
 
     def _reserve(self, need):
-        """The order's workspace, grown to ``need`` bytes.  The buffer is handed to kernels on whatever stream is
-        current (EchelleModel rotates orders over side streams), so that stream is recorded on it: the caching
-        allocator then does not recycle a dropped buffer before the work queued on it has finished."""
-        torch = _torch()
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = workspace(need, self.dev)
-        self._ws.record_stream(torch.cuda.current_stream(self.dev))
-        return self._ws
+        """The order's workspace, grown to ``need`` bytes (:func:`grow_workspace`)."""
+        return grow_workspace(vars(self), "_ws", need, self.dev)
+
+    def _call(self, name, md, B, P, *args, ws=None):
+        """Enqueue ``sf_<name>(ctx, &md, B, P, *args, ws, ws_bytes, stream)`` on the current stream and check its return
+        code.  ``args``: integers as they are, tensors (or None) as their device pointers; ``ws``: the order's workspace
+        sized for ``(md, B)`` unless the caller reserved another (the banded solver's)."""
+        if ws is None:
+            ws = self._work(md, B)
+        args = [a if isinstance(a, (int, np.integer)) else ptr(a) for a in args]
+        rc = getattr(self.lib, "sf_" + name)(self.ctx, C.byref(md), B, ptr(P), *args, ptr(ws), ws.numel(),
+                                             stream_ptr(self.dev))
+        _lib.check(rc, "sf_" + name)
 
     def _work(self, md, B):
         return self._reserve(self.workspace_bytes(md, B))
@@ -437,15 +481,11 @@ class DeviceOrder:
                               resid=None, log_scale=None):
         """Enqueue-only banded + rank-m solve (sf_loglike_banded_batch); device tensors in/out."""
         B = int(P_dev.shape[0])
-        ws = self._work_banded(md, B, halfwidth)
-        rc = self.lib.sf_loglike_banded_batch(
-            self.ctx, C.byref(md), B, ptr(P_dev), int(halfwidth), ptr(out_lnl), ptr(logdet), ptr(sqmah),
-            ptr(resid), ptr(log_scale), ptr(info), ptr(ws), ws.numel(), stream_ptr(self.dev),
-        )
-        _lib.check(rc, "sf_loglike_banded_batch")
+        self._call("loglike_banded_batch", md, B, P_dev, int(halfwidth), out_lnl, logdet, sqmah, resid, log_scale, info,
+                   ws=self._work_banded(md, B, halfwidth))
 
     # ------------------------------------------------------------------ batched calls
-    def loglike(self, md, params, want_resid=False, max_chunk=None, solver="dense", _retry=True):
+    def loglike(self, md, params, want_resid=False, max_chunk=None, solver="dense"):
         """params: (B, stride) float64 (numpy or cuda tensor) in the C-ABI row layout.
         Returns dict of numpy arrays: lnl, logdet, sqmah, log_scale, info (+ resid).
 
@@ -461,31 +501,18 @@ class DeviceOrder:
         with torch.cuda.device(self.dev):
             P = params if torch.is_tensor(params) else to_dev(params, self.dev)
             B = int(P.shape[0])
-            chunk = min(B, max_chunk or B, self.max_batch(md))
-            quad = empty((4, B), self.dev)  # one device->host copy for the four double outputs
-            lnl, logdet, sqmah, lsc = quad[0], quad[1], quad[2], quad[3]
-            info = empty((B,), self.dev, torch.int32)
-            resid = empty((B, self.n), self.dev) if want_resid else None
-            s = stream_ptr(self.dev)
-            for lo in range(0, B, chunk):
-                hi = min(lo + chunk, B)
-                ws = self._work(md, hi - lo)
-                rc = self.lib.sf_loglike_batch(
-                    self.ctx, C.byref(md), hi - lo, ptr(P[lo:hi]), ptr(lnl[lo:hi]), ptr(logdet[lo:hi]),
-                    ptr(sqmah[lo:hi]), ptr(resid[lo:hi]) if want_resid else C.c_void_p(0), ptr(lsc[lo:hi]),
-                    ptr(info[lo:hi]), ptr(ws), ws.numel(), s,
-                )
-                _lib.check(rc, "sf_loglike_batch")
-            host = quad.cpu().numpy()
-            out = dict(lnl=host[0], logdet=host[1], sqmah=host[2], log_scale=host[3], info=info.cpu().numpy())
-            internal = out["info"] == INFO_INTERNAL
-            if internal.any() and _retry:
-                # never a silent -inf: warn, switch the persistent kernel off, evaluate the batch again
-                recover_from_internal(self.lib, "sf_loglike_batch", internal.sum())
-                return self.loglike(md, P, want_resid=want_resid, max_chunk=max_chunk, solver="dense", _retry=False)
-            if want_resid:
-                out["resid"] = resid.cpu().numpy()
-            return out
+
+            def run(again):
+                chunk = min(B, max_chunk or B, self.max_batch(md))
+                quad, info, resid = result_buffers(B, self.dev, self.n if want_resid else None)
+                for lo in range(0, B, chunk):
+                    hi = min(lo + chunk, B)
+                    self._call("loglike_batch", md, hi - lo, P[lo:hi], quad[0][lo:hi], quad[1][lo:hi], quad[2][lo:hi],
+                               resid[lo:hi] if want_resid else None, quad[3][lo:hi], info[lo:hi])
+                out = fetch_results(quad, info, resid)
+                return out, out["info"]
+
+            return retry_internal(self.lib, "sf_loglike_batch", run)
 
     def _loglike_structured(self, md, params, want_resid, max_chunk, solver):
         return self.structured_collect(md, self.structured_enqueue(md, params, want_resid, max_chunk), solver)
@@ -522,10 +549,8 @@ class DeviceOrder:
             with torch.cuda.device(self.dev):
                 P = to_dev(rows[idx], self.dev)
                 nb = idx.size
-                quad = empty((4, nb), self.dev)  # one device->host copy for the four double outputs
+                quad, info, resid = result_buffers(nb, self.dev, self.n if want_resid else None)
                 lnl, logdet, sqmah, lsc = quad[0], quad[1], quad[2], quad[3]
-                info = empty((nb,), self.dev, torch.int32)
-                resid = empty((nb, self.n), self.dev) if want_resid else None
                 chunk = min(nb, max_chunk or nb)
                 for lo in range(0, nb, chunk):
                     hi = min(lo + chunk, nb)
@@ -539,12 +564,8 @@ class DeviceOrder:
     def structured_collect(self, md, pend, solver):
         out, rows, fits, want_resid = pend["out"], pend["rows"], pend["fits"], pend["want_resid"]
         for idx, quad, info, resid, _ in pend["groups"]:
-            host = quad.cpu().numpy()
-            for row, key in enumerate(("lnl", "logdet", "sqmah", "log_scale")):
-                out[key][idx] = host[row]
-            out["info"][idx] = info.cpu().numpy()
-            if want_resid:
-                out["resid"][idx] = resid.cpu().numpy()
+            for key, v in fetch_results(quad, info, resid).items():
+                out[key][idx] = v
         # an internal wait timeout of the sweep (-5, not expected: the bound keeps a logic error from hanging the GPU) is
         # recomputed by the dense solver -- under "banded" too -- instead of silently turning into a rejected walker
         internal = out["info"] == INFO_INTERNAL
@@ -564,13 +585,7 @@ class DeviceOrder:
 
     def loglike_device(self, md, P_dev, out_lnl, info=None):
         """Enqueue-only variant for bench.py: device tensors in/out, no synchronisation."""
-        B = int(P_dev.shape[0])
-        ws = self._work(md, B)
-        rc = self.lib.sf_loglike_batch(
-            self.ctx, C.byref(md), B, ptr(P_dev), ptr(out_lnl), C.c_void_p(0), C.c_void_p(0), C.c_void_p(0),
-            C.c_void_p(0), ptr(info), ptr(ws), ws.numel(), stream_ptr(self.dev),
-        )
-        _lib.check(rc, "sf_loglike_batch")
+        self._call("loglike_batch", md, int(P_dev.shape[0]), P_dev, out_lnl, None, None, None, None, info)
 
     def forward(self, md, params):
         """SpectrumModel.__call__ for B rows: flux (B, n), cov (B, n, n), log_scale, info."""
@@ -582,12 +597,7 @@ class DeviceOrder:
             cov = empty((B, self.n, self.n), self.dev)
             lsc = empty((B,), self.dev)
             info = empty((B,), self.dev, torch.int32)
-            ws = self._work(md, B)
-            rc = self.lib.sf_forward_batch(
-                self.ctx, C.byref(md), B, ptr(P), ptr(flux), ptr(cov), ptr(lsc), ptr(info), ptr(ws),
-                ws.numel(), stream_ptr(self.dev),
-            )
-            _lib.check(rc, "sf_forward_batch")
+            self._call("forward_batch", md, B, P, flux, cov, lsc, info)
             return dict(
                 flux=flux.cpu().numpy(), cov=cov.cpu().numpy(), log_scale=lsc.cpu().numpy(),
                 info=info.cpu().numpy(),
@@ -608,12 +618,7 @@ class DeviceOrder:
                 buf[B * self.n * ld:] = -7.0
             cov = buf[: B * self.n * ld].view(B, self.n, ld)
             info = empty((B,), self.dev, torch.int32)
-            ws = self._work(md, B)
-            rc = self.lib.sf_cov_fill_batch(
-                self.ctx, C.byref(md), B, ptr(P), ptr(cov), ld, self.n * ld, int(lower_only), int(add_jitter), ptr(info),
-                ptr(ws), ws.numel(), stream_ptr(self.dev),
-            )
-            _lib.check(rc, "sf_cov_fill_batch")
+            self._call("cov_fill_batch", md, B, P, cov, ld, self.n * ld, int(lower_only), int(add_jitter), info)
             if guard:
                 return cov.cpu().numpy(), info.cpu().numpy(), buf[B * self.n * ld:].cpu().numpy()
             return cov.cpu().numpy(), info.cpu().numpy()
@@ -622,13 +627,8 @@ class DeviceOrder:
         """Enqueue-only sf_cov_fill_batch into a caller-held device array (bench.py's fill leg): no host copies."""
         torch = _torch()
         with torch.cuda.device(self.dev):
-            B = int(P_dev.shape[0])
-            ws = self._work(md, B)
-            rc = self.lib.sf_cov_fill_batch(
-                self.ctx, C.byref(md), B, ptr(P_dev), ptr(cov), int(ld), int(stride), int(lower_only), int(add_jitter),
-                ptr(info) if info is not None else C.c_void_p(0), ptr(ws), ws.numel(), stream_ptr(self.dev),
-            )
-            _lib.check(rc, "sf_cov_fill_batch")
+            self._call("cov_fill_batch", md, int(P_dev.shape[0]), P_dev, cov, int(ld), int(stride), int(lower_only),
+                       int(add_jitter), info)
 
     def transform(self, md, params):
         torch = _torch()
@@ -640,59 +640,43 @@ class DeviceOrder:
             resid = empty((B, self.n), self.dev)
             lsc = empty((B,), self.dev)
             info = empty((B,), self.dev, torch.int32)
-            ws = self._work(md, B)
-            rc = self.lib.sf_transform_batch(
-                self.ctx, C.byref(md), B, ptr(P), ptr(flux), ptr(X), ptr(resid), ptr(lsc), ptr(info),
-                ptr(ws), ws.numel(), stream_ptr(self.dev),
-            )
-            _lib.check(rc, "sf_transform_batch")
+            self._call("transform_batch", md, B, P, flux, X, resid, lsc, info)
             return dict(
                 flux=flux.cpu().numpy(), X=X.cpu().numpy(), resid=resid.cpu().numpy(),
                 log_scale=lsc.cpu().numpy(), info=info.cpu().numpy(),
             )
 
+    def _grid_rows(self, grid_params):
+        """(B, P) grid points as the C-ABI rows of the emulator queries (descriptor with log_scale only): md, rows."""
+        gp = np.atleast_2d(np.asarray(grid_params, dtype=np.float64))
+        md = self.model_desc(0, 0, 1, 0, 0, 0)
+        rows = np.zeros((gp.shape[0], self.param_stride(md)))
+        rows[:, 3] = 1.0
+        rows[:, 6 : 6 + self.P] = gp
+        return md, rows
+
     def emulator_query(self, grid_params):
         """grid_params: (B, P).  Returns mu (B, m), cov (B, m, m), info (B,)."""
         torch = _torch()
-        gp = np.atleast_2d(np.asarray(grid_params, dtype=np.float64))
-        B = gp.shape[0]
-        md = self.model_desc(0, 0, 1, 0, 0, 0)
-        stride = self.param_stride(md)
-        rows = np.zeros((B, stride))
-        rows[:, 3] = 1.0
-        rows[:, 6 : 6 + self.P] = gp
+        md, rows = self._grid_rows(grid_params)
+        B = rows.shape[0]
         with torch.cuda.device(self.dev):
             P = to_dev(rows, self.dev)
             mu = empty((B, self.m), self.dev)
             cov = empty((B, self.m, self.m), self.dev)
             info = empty((B,), self.dev, torch.int32)
-            ws = self._work(md, B)
-            rc = self.lib.sf_emulator_query_batch(
-                self.ctx, C.byref(md), B, ptr(P), ptr(mu), ptr(cov), ptr(info), ptr(ws), ws.numel(),
-                stream_ptr(self.dev),
-            )
-            _lib.check(rc, "sf_emulator_query_batch")
+            self._call("emulator_query_batch", md, B, P, mu, cov, info)
             return mu.cpu().numpy(), cov.cpu().numpy(), info.cpu().numpy()
 
     def emulator_query_joint(self, grid_params):
         """grid_params: (B, P).  Joint conditional over the B points, component-major: mu (B*m,), cov (B*m, B*m)."""
         torch = _torch()
-        gp = np.atleast_2d(np.asarray(grid_params, dtype=np.float64))
-        B = gp.shape[0]
-        md = self.model_desc(0, 0, 1, 0, 0, 0)
-        stride = self.param_stride(md)
-        rows = np.zeros((B, stride))
-        rows[:, 3] = 1.0
-        rows[:, 6 : 6 + self.P] = gp
+        md, rows = self._grid_rows(grid_params)
+        B = rows.shape[0]
         with torch.cuda.device(self.dev):
             P = to_dev(rows, self.dev)
             mu = empty((B * self.m,), self.dev)
             cov = empty((B * self.m, B * self.m), self.dev)
             info = empty((B,), self.dev, torch.int32)
-            ws = self._work(md, B)
-            rc = self.lib.sf_emulator_joint_batch(
-                self.ctx, C.byref(md), B, ptr(P), ptr(mu), ptr(cov), ptr(info), ptr(ws), ws.numel(),
-                stream_ptr(self.dev),
-            )
-            _lib.check(rc, "sf_emulator_joint_batch")
+            self._call("emulator_joint_batch", md, B, P, mu, cov, info)
             return mu.cpu().numpy(), cov.cpu().numpy(), info.cpu().numpy()

@@ -377,7 +377,7 @@ class Emulator:
             R = np.zeros(npad)
             R[:n] = self.w_hat
             td = self._train_dev = dict(
-                dev=dev, w_hat=self.w_hat, grid_src=self.grid_points, iphiphi_src=self.iPhiPhi,
+                n=n, npad=npad, lda=lda, dev=dev, w_hat=self.w_hat, grid_src=self.grid_points, iphiphi_src=self.iPhiPhi,
                 grid=D.to_dev(self.grid_points, dev), iphiphi=D.to_dev(self.iPhiPhi, dev),
                 R=D.to_dev(R, dev), A=D.empty((npad, lda), dev), out=D.empty((2,), dev), info=D.empty((1,), dev, torch.int32),
                 ws=D.workspace(lib.sf_potrf_workspace_bytes(npad, 1), dev),
@@ -385,7 +385,7 @@ class Emulator:
             )
         return td
 
-    def log_likelihood(self, _retry=True):
+    def log_likelihood(self):
         """-(logdet v11 + w_hat^T v11^-1 w_hat) / 2  (Starfish/emulator/emulator.py:602-619), entirely on the device:
         v11 is built from the hyper-parameters by ``sf_emulator_v11_build`` (grid, iPhiPhi and w_hat stay resident), then
         factored and solved by the same batched HIP kernels as the spectrum likelihood (``sf_potrf_batch`` /
@@ -398,33 +398,31 @@ class Emulator:
         dev = D.device_of()
         M, P = self.grid_points.shape
         m = self.ncomps
-        n = m * M
-        npad = -(-n // 64) * 64
-        lda = npad + 16
         td = self._train_resident(lib, dev)
-        s = D.stream_ptr(dev)
-        A = td["A"]
-        if self._v11_assigned:
-            host = np.zeros((npad, lda))
-            host[:n, :n] = self._v11
-            idx = np.arange(n, npad)
-            host[idx, idx] = 1.0  # identity padding: log 1 = 0, zero right-hand side
-            A.copy_(torch.from_numpy(host))
-        else:
-            hyper = D.to_dev(np.concatenate([[self.lambda_xi], self.variances, np.asarray(self.lengthscales).ravel()]), dev)
-            _lib.check(lib.sf_emulator_v11_build(D.ptr(td["grid"]), M, P, m, D.ptr(hyper), D.ptr(td["iphiphi"]), D.ptr(A),
-                                                 npad, lda, s), "sf_emulator_v11_build")
-        ws = td["ws"]
-        _lib.check(lib.sf_potrf_batch(D.ptr(A), npad, lda, npad * lda, 1, D.ptr(td["info"]), D.ptr(ws), ws.numel(), s),
-                   "sf_potrf_batch")
-        _lib.check(lib.sf_logdet_sqmah_batch(D.ptr(A), npad, lda, npad * lda, 1, D.ptr(td["R"]), npad, D.ptr(ws),
-                                             ws.numel(), D.ptr(td["out"][0:1]), D.ptr(td["out"][1:2]), s), "sf_logdet_sqmah_batch")
-        code = int(td["info"].cpu()[0])
-        if code == D.INFO_INTERNAL:
-            if not _retry:
-                raise RuntimeError(D.INFO_MESSAGES[D.INFO_INTERNAL])
-            D.recover_from_internal(lib, "Emulator.log_likelihood", 1)
-            return self.log_likelihood(_retry=False)  # (A was overwritten: it is rebuilt / re-uploaded above)
+        n, npad, lda = td["n"], td["npad"], td["lda"]
+        A, ws = td["A"], td["ws"]
+
+        def factor(again):  # (the factorisation overwrites A: every run rebuilds / re-uploads it)
+            s = D.stream_ptr(dev)
+            if self._v11_assigned:
+                host = np.zeros((npad, lda))
+                host[:n, :n] = self._v11
+                idx = np.arange(n, npad)
+                host[idx, idx] = 1.0  # identity padding: log 1 = 0, zero right-hand side
+                A.copy_(torch.from_numpy(host))
+            else:
+                hyper = D.to_dev(np.concatenate([[self.lambda_xi], self.variances, np.asarray(self.lengthscales).ravel()]), dev)
+                _lib.check(lib.sf_emulator_v11_build(D.ptr(td["grid"]), M, P, m, D.ptr(hyper), D.ptr(td["iphiphi"]), D.ptr(A),
+                                                     npad, lda, s), "sf_emulator_v11_build")
+            _lib.check(lib.sf_potrf_batch(D.ptr(A), npad, lda, npad * lda, 1, D.ptr(td["info"]), D.ptr(ws), ws.numel(), s),
+                       "sf_potrf_batch")
+            _lib.check(lib.sf_logdet_sqmah_batch(D.ptr(A), npad, lda, npad * lda, 1, D.ptr(td["R"]), npad, D.ptr(ws),
+                                                 ws.numel(), D.ptr(td["out"][0:1]), D.ptr(td["out"][1:2]), s),
+                       "sf_logdet_sqmah_batch")
+            code = int(td["info"].cpu()[0])
+            return code, code
+
+        code = D.retry_internal(lib, "Emulator.log_likelihood", factor)
         if code != 0:
             raise np.linalg.LinAlgError(f"{code}-th leading minor of the array is not positive definite")
         ld, sq = td["out"].cpu().tolist()
@@ -439,7 +437,7 @@ class Emulator:
         with np.errstate(over="ignore"):
             return np.ascontiguousarray(np.exp(P[:, order]))
 
-    def log_likelihood_batch(self, P, return_info=False, _retry=True):
+    def log_likelihood_batch(self, P, return_info=False):
         """:meth:`log_likelihood` (Starfish/emulator/emulator.py:602-619) for the ``B`` rows of ``P`` -- hyper-parameter
         vectors in the units of :meth:`get_param_vector`, i.e. logs -- as ONE device call (``sf_emulator_loglike_batch``:
         the B matrices built, factored and solved in one enqueue): one upload of the raw hyper-parameter rows, one download.
@@ -463,37 +461,31 @@ class Emulator:
         td = self._train_resident(lib, dev)
         hyper = self._hyper_rows(P)
         B = len(hyper)
-        lnl = np.empty(B)
-        info = np.empty(B, dtype=np.int32)
-        # chunks sized from the free device memory as DeviceOrder.max_batch does (same 15 % reserve); the workspace is
-        # a fixed part (the factorisation's partial-sum regions) plus a part per matrix
-        one, two = (int(lib.sf_emulator_loglike_workspace_bytes(M, m, b)) for b in (1, 2))
-        free, _total = torch.cuda.mem_get_info(dev)
-        if td["ws_batch"] is not None:
-            free += td["ws_batch"].numel()
-        cap = int(min(max(1, (int(free * 0.85) - (2 * one - two)) // (two - one)), 65535))
-        s = D.stream_ptr(dev)
-        for lo in range(0, B, cap):
-            nb = min(cap, B - lo)
-            need = int(lib.sf_emulator_loglike_workspace_bytes(M, m, nb))
-            if td["ws_batch"] is None or td["ws_batch"].numel() < need:
-                td["ws_batch"] = None
-                td["ws_batch"] = D.workspace(need, dev)
-            ws = td["ws_batch"]
-            d_hyper = D.to_dev(hyper[lo:lo + nb], dev)
-            out = torch.empty(12 * nb, dtype=torch.uint8, device=dev)  # lnl[nb] then info[nb]: one download
-            _lib.check(lib.sf_emulator_loglike_batch(
-                D.ptr(td["grid"]), M, npar, m, D.ptr(d_hyper), hyper.shape[1], nb, D.ptr(td["iphiphi"]), D.ptr(td["w_hat_dev"]),
-                C.c_void_p(out.data_ptr()), None, None, C.c_void_p(out.data_ptr() + 8 * nb), D.ptr(ws), ws.numel(), s),
-                "sf_emulator_loglike_batch")
-            host = out.cpu().numpy()
-            lnl[lo:lo + nb] = host[:8 * nb].view(np.float64)
-            info[lo:lo + nb] = host[8 * nb:].view(np.int32)
-        if np.any(info == D.INFO_INTERNAL):
-            if not _retry:
-                raise RuntimeError(D.INFO_MESSAGES[D.INFO_INTERNAL])
-            D.recover_from_internal(lib, "Emulator.log_likelihood_batch", B)
-            return self.log_likelihood_batch(P, return_info, _retry=False)
+
+        def run(again):
+            lnl = np.empty(B)
+            info = np.empty(B, dtype=np.int32)
+            # chunks sized from the free device memory as DeviceOrder.max_batch does; the workspace is a fixed part (the
+            # factorisation's partial-sum regions) plus a part per matrix
+            one, two = (int(lib.sf_emulator_loglike_workspace_bytes(M, m, b)) for b in (1, 2))
+            held = td["ws_batch"].numel() if td["ws_batch"] is not None else 0
+            cap = D.units_that_fit(dev, 2 * one - two, two - one, held, 65535)
+            s = D.stream_ptr(dev)
+            for lo in range(0, B, cap):
+                nb = min(cap, B - lo)
+                ws = D.grow_workspace(td, "ws_batch", int(lib.sf_emulator_loglike_workspace_bytes(M, m, nb)), dev)
+                d_hyper = D.to_dev(hyper[lo:lo + nb], dev)
+                out = torch.empty(12 * nb, dtype=torch.uint8, device=dev)  # lnl[nb] then info[nb]: one download
+                _lib.check(lib.sf_emulator_loglike_batch(
+                    D.ptr(td["grid"]), M, npar, m, D.ptr(d_hyper), hyper.shape[1], nb, D.ptr(td["iphiphi"]),
+                    D.ptr(td["w_hat_dev"]), C.c_void_p(out.data_ptr()), None, None, C.c_void_p(out.data_ptr() + 8 * nb),
+                    D.ptr(ws), ws.numel(), s), "sf_emulator_loglike_batch")
+                host = out.cpu().numpy()
+                lnl[lo:lo + nb] = host[:8 * nb].view(np.float64)
+                info[lo:lo + nb] = host[8 * nb:].view(np.int32)
+            return (lnl, info), info
+
+        lnl, info = D.retry_internal(lib, "Emulator.log_likelihood_batch", run, count=B)
         return (lnl, info) if return_info else lnl
 
     def _batched_objective(self, evaluate):

@@ -265,11 +265,18 @@ class EchelleModel:
         info = np.zeros(B, dtype=np.int32)
         per_order = np.full((len(self.orders), B), -np.inf)
         structured = any(m.solver != "dense" for m in self.orders)
+        vals = np.zeros((len(self.orders), int(finite.sum())))  # per order, of the walkers with a finite prior
+        codes = np.zeros((len(self.orders), int(finite.sum())), dtype=np.int32)
+
+        def reduce_orders():
+            per_order[:, finite] = vals
+            lnl[finite] = vals.sum(axis=0) + prior_lp[finite]
+            bad = codes != 0
+            info[finite] = np.where(bad.any(axis=0), codes[bad.argmax(axis=0), np.arange(codes.shape[1])], 0)
+
         if finite.any() and structured:
             # structure-exploiting solver: one banded call per order (a few ms each instead of a share of the dense
             # batch; orders may need different half-widths, so they are not merged)
-            vals = np.zeros((len(self.orders), int(finite.sum())))
-            codes = np.zeros((len(self.orders), int(finite.sum())), dtype=np.int32)
             # every order is enqueued before anything is waited for; the orders of a device take turns on a few
             # side streams (a banded call of 64 walkers fills half of the chip) -- ONE synchronisation per device
             import torch
@@ -292,10 +299,7 @@ class EchelleModel:
                 out = dev.loglike(md, rows) if pend is None else dev.structured_collect(md, pend, self.orders[i].solver)
                 vals[i] = np.where(out["info"] == 0, out["lnl"], -np.inf)
                 codes[i] = out["info"]
-            per_order[:, finite] = vals
-            lnl[finite] = vals.sum(axis=0) + prior_lp[finite]
-            bad = codes != 0
-            info[finite] = np.where(bad.any(axis=0), codes[bad.argmax(axis=0), np.arange(codes.shape[1])], 0)
+            reduce_orders()
         elif finite.any():
             packed = [m._pack(order_P[i][finite], update_caches=False) for i, m in enumerate(self.orders)]
             # one multi-order call per device (and emulator shape): orders whose row layouts differ -- per-order
@@ -310,16 +314,11 @@ class EchelleModel:
                 same = all(D.model_desc_key(m) == D.model_desc_key(mds[0]) for m in mds)
                 pending.append((idxs, D.loglike_multi(devs, mds[0] if same else mds, [packed[i][2] for i in idxs],
                                                       sync=False)))
-            vals = np.zeros((len(self.orders), int(finite.sum())))
-            codes = np.zeros((len(self.orders), int(finite.sum())), dtype=np.int32)
             for idxs, plan in pending:
                 for i, out in zip(idxs, plan.collect()):
                     vals[i] = out["lnl"]
                     codes[i] = out["info"]
-            per_order[:, finite] = vals
-            lnl[finite] = vals.sum(axis=0) + prior_lp[finite]
-            bad = codes != 0
-            info[finite] = np.where(bad.any(axis=0), codes[bad.argmax(axis=0), np.arange(codes.shape[1])], 0)
+            reduce_orders()
         self.last_info = info
         out = (lnl,)
         if return_info:

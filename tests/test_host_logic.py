@@ -408,3 +408,166 @@ def test_multiplan_collect_raises_when_the_internal_status_survives_the_retry(mo
     with pytest.warns(RuntimeWarning, match="disabled for this whole process"):
         out = plan.collect()
     assert (out[0]["info"] == 0).all()
+
+
+class _RecoveryLib:
+    """What the retry policy touches of the library: the abort record and the process-wide switch."""
+
+    def __init__(self):
+        self.switched = []
+
+    def sf_persistent_potrf_status(self, buf):
+        for i, v in enumerate((1, 2, 400, 512, 3_000_000, 77, 1, 1)):
+            buf[i] = v
+        return 0
+
+    def sf_persistent_potrf(self, v):
+        self.switched.append(v)
+        return 1
+
+
+def test_retry_internal_runs_once_when_clean_twice_after_an_abort_and_raises_when_it_survives(recwarn):
+    from starfish_amd import _device as D
+
+    clean, aborted = np.zeros(3, dtype=np.int32), np.array([0, D.INFO_INTERNAL, D.INFO_INTERNAL], dtype=np.int32)
+
+    def evaluator(script, seen):
+        results = iter(script)
+
+        def evaluate(again):
+            seen.append(again)
+            info = next(results)
+            return ("value", len(seen)), info
+
+        return evaluate
+
+    lib, seen = _RecoveryLib(), []
+    assert D.retry_internal(lib, "here", evaluator([clean], seen)) == ("value", 1)
+    assert seen == [False] and lib.switched == [] and len(recwarn) == 0
+
+    lib, seen = _RecoveryLib(), []
+    with pytest.warns(RuntimeWarning, match=r"here: internal status -5 for 2 unit\(s\)") as caught:
+        assert D.retry_internal(lib, "here", evaluator([aborted, clean], seen)) == ("value", 2)
+    assert seen == [False, True] and lib.switched == [0] and len(caught) == 1
+
+    lib, seen = _RecoveryLib(), []
+    with pytest.warns(RuntimeWarning, match="disabled for this whole process"):
+        with pytest.raises(RuntimeError, match="internal error"):
+            D.retry_internal(lib, "here", evaluator([aborted, aborted], seen))
+    assert seen == [False, True] and lib.switched == [0]
+
+
+def _host_order(monkeypatch, free):
+    """A DeviceOrder without a device: ``__new__``, host tensors, and ``free`` bytes reported as free HBM."""
+    import contextlib
+
+    import torch
+    from starfish_amd import _device as D
+
+    do = D.DeviceOrder.__new__(D.DeviceOrder)
+    do.lib, do.dev, do.n, do.ctx, do._ws, do._ws_multi = _RecoveryLib(), torch.device("cpu"), 5, None, None, None
+    monkeypatch.setattr(torch.cuda, "mem_get_info", lambda dev=None: (free, 2 * free))
+    monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
+    return do
+
+
+def test_device_order_loglike_raises_when_the_internal_status_survives_the_retry(monkeypatch):
+    """The sibling of the MultiPlan test above: DeviceOrder.loglike handed a second -5 back as a per-walker status."""
+    from starfish_amd import _device as D
+
+    do = _host_order(monkeypatch, free=1 << 30)
+    do.workspace_bytes = lambda md, B: 1 << 20
+    calls = []
+    do._call = lambda name, md, B, P, *args, **kw: calls.append((name, B))
+    codes = iter([[D.INFO_INTERNAL] * 4, [D.INFO_INTERNAL] * 4, [D.INFO_INTERNAL] * 4, [0] * 4])
+
+    def fetch(quad, info, resid=None):
+        assert quad.shape == (4, 4) and info.shape == (4,) and resid is None
+        return dict(lnl=np.ones(4), logdet=np.zeros(4), sqmah=np.zeros(4), log_scale=np.zeros(4),
+                    info=np.array(next(codes), dtype=np.int32))
+
+    monkeypatch.setattr(D, "fetch_results", fetch)
+    with pytest.warns(RuntimeWarning, match=r"sf_loglike_batch: internal status -5 for 4 unit\(s\)") as caught:
+        with pytest.raises(RuntimeError, match="internal error"):
+            do.loglike(None, np.zeros((4, 9)), max_chunk=3)
+    assert calls == [("loglike_batch", 3), ("loglike_batch", 1)] * 2 and do.lib.switched == [0]
+    assert [os.path.samefile(w.filename, __file__) for w in caught] == [True]  # attributed to the caller of loglike
+    # ... and a retry that succeeds is returned
+    with pytest.warns(RuntimeWarning, match="disabled for this whole process"):
+        out = do.loglike(None, np.zeros((4, 9)))
+    assert (out["info"] == 0).all() and (out["lnl"] == 1).all()
+
+
+def test_units_that_fit_gives_the_three_chunk_sizes_it_replaced(monkeypatch):
+    """The helper against the three expressions it replaced (DeviceOrder.max_batch, MultiPlan and
+    Emulator.log_likelihood_batch), written out as they stood: no chunk boundary may move (the Cholesky sequence is
+    chosen by batch size)."""
+    from starfish_amd import _device as D
+
+    cases = [  # free, held, fixed, per_unit, limit
+        (200 << 30, 0, 0, 805_306_368, None),
+        (200 << 30, 3 << 30, 1 << 28, 134_217_733, None),
+        (1000, 0, 900, 7, None),                  # free * 0.85 < fixed: one unit all the same
+        (1 << 30, 1 << 20, 4096, 12_345, 5),      # a limit below what fits
+        (1 << 30, 1 << 20, 4096, 12_345, 65535),  # ... far more fit: the emulator's limit holds
+        (1 << 30, 0, 4096, 123_456, 65535),       # ... and does not where fewer fit
+        (10_000_019, 77, 123, 1, None),
+    ]
+    got = []
+    for free, held, fixed, per_unit, limit in cases:
+        do = _host_order(monkeypatch, free)
+        got.append(D.units_that_fit(do.dev, fixed, per_unit, held, limit))
+        avail = free + held
+        multiplan = max(1, (int(avail * 0.85) - fixed) // per_unit)
+        if limit:
+            multiplan = min(multiplan, int(limit))
+        assert got[-1] == multiplan and isinstance(got[-1], int)
+        if limit == 65535:  # Emulator.log_likelihood_batch: fixed = 2 * one - two, per_unit = two - one
+            one, two = fixed + per_unit, fixed + 2 * per_unit
+            assert got[-1] == int(min(max(1, (int(avail * 0.85) - (2 * one - two)) // (two - one)), 65535))
+        if fixed == 0 and limit is None:  # DeviceOrder.max_batch
+            assert got[-1] == max(1, int(avail * (1.0 - 0.15)) // max(per_unit, 1))
+    assert got[2:6] == [1, 5, 65535, 7392]
+
+    # DeviceOrder.max_batch: free HBM plus the workspace it holds, over the workspace of one walker
+    import torch
+
+    do = _host_order(monkeypatch, free=100 << 30)
+    do.workspace_bytes = lambda md, B: 805_306_368 * B
+    assert do.max_batch(None) == max(1, int((100 << 30) * (1.0 - 0.15)) // 805_306_368) == 113
+    do._ws = torch.empty(1 << 20, dtype=torch.uint8)
+    assert do.max_batch(None) == max(1, int(((100 << 30) + (1 << 20)) * (1.0 - 0.15)) // 805_306_368)
+    do.workspace_bytes = lambda md, B: 0
+    assert do.max_batch(None) == int(((100 << 30) + (1 << 20)) * (1.0 - 0.15))
+
+
+def test_grow_workspace_reuses_replaces_and_records_the_stream(monkeypatch):
+    from starfish_amd import _device as D
+
+    class Buffer:
+        def __init__(self, nbytes):
+            self.nbytes, self.recorded = nbytes, []
+
+        def numel(self):
+            return self.nbytes
+
+        def record_stream(self, stream):
+            self.recorded.append(stream)
+
+    made = []
+
+    def factory(nbytes, dev):
+        assert slot["ws"] is None  # the old buffer is dropped before the new one is allocated
+        made.append(Buffer(nbytes))
+        return made[-1]
+
+    monkeypatch.setattr(D, "workspace", factory)
+    monkeypatch.setattr(D, "current_stream", lambda dev: ("stream of", dev))
+    slot = dict(ws=None)
+    first = D.grow_workspace(slot, "ws", 100, "dev0")
+    assert first is slot["ws"] is made[0] and first.nbytes == 100 and first.recorded == [("stream of", "dev0")]
+    assert D.grow_workspace(slot, "ws", 100, "dev0") is first and D.grow_workspace(slot, "ws", 8, "dev0") is first
+    assert len(made) == 1 and len(first.recorded) == 3  # large enough: returned as it is, stream recorded every time
+    second = D.grow_workspace(slot, "ws", 101, "dev0")
+    assert second is slot["ws"] is made[1] and second is not first and second.nbytes == 101
+    assert second.recorded == [("stream of", "dev0")] and len(first.recorded) == 3
