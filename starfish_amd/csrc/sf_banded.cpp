@@ -1,0 +1,115 @@
+// C-ABI host layer: the structure-exploiting (banded + low-rank) solver.
+#include "sf_stages.h"
+
+extern "C" int sf_banded_max_halfwidth(const sf_ctx* c) {
+    if (!c || !c->n) return SF_EINVAL;
+    if (!c->monotonic) return -1;
+    const int lds_max = sf_band_max_halfwidth(c->m + 1), wide_max = SF_BAND_TILES_MAX_HALFWIDTH;
+    return c->m + 1 <= 48 ? (wide_max > lds_max ? wide_max : lds_max) : lds_max;
+}
+extern "C" int sf_banded_window_halfwidth(const sf_ctx* c) {
+    if (!c || !c->n) return SF_EINVAL;
+    return c->monotonic ? sf_band_max_halfwidth(c->m + 1) : -1;
+}
+extern "C" size_t sf_banded_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth) {
+    if (model_ok(c, mdl) || B <= 0 || halfwidth < 0) return 0;
+    const size_t base = carve(c, mdl, B, nullptr, 0, false).bytes;
+    return carve_band(c, B, halfwidth, nullptr, 0, base).bytes;
+}
+extern "C" int sf_loglike_banded_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params,
+                                       int halfwidth, double* d_lnl, double* d_logdet, double* d_sqmah,
+                                       double* d_resid, double* d_log_scale, int* d_info, void* d_work,
+                                       size_t work_bytes, void* stream) {
+    if (model_ok(c, mdl)) return SF_EINVAL;
+    if (B <= 0 || !d_work || !d_lnl) {
+        sf_set_error("sf_loglike_banded_batch: bad batch size / workspace / d_lnl");
+        return SF_EINVAL;
+    }
+    const int wmax = sf_banded_max_halfwidth(c);
+    if (halfwidth < 0 || halfwidth > wmax) {
+        sf_set_error("sf_loglike_banded_batch: half-width %d outside [0, %d] (use sf_loglike_batch)", halfwidth, wmax);
+        return SF_EINVAL;
+    }
+    Work w = carve(c, mdl, B, d_work, work_bytes, false);
+    BandWork bw = carve_band(c, B, halfwidth, d_work, work_bytes, w.bytes);
+    int rc = work_fits(work_bytes, bw.bytes);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (use_device(c)) return SF_EHIP;
+    prof_count_call();
+    // The band fill depends on the covariance hyper-parameters only, the transforms on the stellar ones:
+    // the two run side by side (fill on a library-owned auxiliary stream, joined before the sweep).
+    sf_exec* aux = &c->exec;
+    rc = sf_exec_prepare(aux);
+    if (rc) return rc;
+    hipStream_t sf = aux->aux;
+    if (sf != s) {
+        SF_HIP(hipEventRecord(aux->fork, s));
+        SF_HIP(hipStreamWaitEvent(sf, aux->fork, 0));
+    }
+    const int64_t sband = (int64_t)c->npad * bw.ldb;
+    {
+        ProfScope ps(sf, PS_FILL);
+        SF_HIP(hipMemsetAsync(w.info_c, 0, sizeof(int) * (size_t)B, sf));
+        sf_fill_args f = fill_args(c, mdl, d_params, w);
+        f.C = nullptr;
+        f.lda = 0;
+        f.stride = 0;
+        f.lower_only = 1;
+        f.add_jitter = 1;
+        f.npad = (c->n + 15) / 16 * 16;
+        if (bw.tiles) {  // straight into the 128 x 128 tiles of the bordered band matrix
+            static const bool poison = SF_TUNE_FLAG("SF_BAND_TILES_POISON");  // test aid: NaN wherever a tile is read before it is written
+            if (poison) SF_HIP(hipMemsetAsync(bw.tiles, 0xff, sizeof(double) * sf_band_tiles_doubles(c->npad, B), sf));
+            f.npad = c->npad;
+            const int lda_t = sf_band_tiles_lda(c->npad);
+            rc = sf_launch_band_fill(f, B, bw.tiles, bw.ldb, halfwidth, lda_t, (int64_t)(c->npad + 64) * lda_t, w.info_c, bw.gtab, sf,
+                                     sf_band_tiles_wt(halfwidth));
+        } else
+            rc = sf_launch_band_fill(f, B, bw.band, halfwidth + 1, halfwidth, bw.ldb, sband, w.info_c, bw.gtab, sf);
+        if (rc) return rc;
+    }
+    if (sf != s) SF_HIP(hipEventRecord(aux->join, sf));
+    {
+        ProfScope ps(s, PS_TRANSFORM);
+        rc = run_transforms(c, mdl, B, d_params, w, nullptr, nullptr, d_resid, d_log_scale, true, s);
+        if (rc) return rc;
+    }
+    if (sf != s) SF_HIP(hipStreamWaitEvent(s, aux->join, 0));
+    {
+        ProfScope ps(s, PS_POTRF);
+        const int n16 = (c->n + 15) / 16 * 16;
+        if (bw.tiles)
+            rc = sf_launch_potrf_band(c->n, c->npad, halfwidth, B, w.resid, c->npad, w.Y, c->m + 1, c->npad,
+                                      (int64_t)c->mpad * c->npad, bw.logdet_band, bw.gram, w.info_c, bw.tiles, s);
+        else if (sf_band_twisted_applicable(n16, halfwidth, B))
+            rc = sf_launch_band_forms_twisted(bw.band, n16, halfwidth, bw.ldb, sband, B, w.resid, c->npad, w.Y,
+                                              c->m + 1, c->npad, (int64_t)c->mpad * c->npad, bw.logdet_band,
+                                              bw.gram, w.info_c, bw.twist, s);
+        else
+            rc = sf_launch_band_forms(bw.band, n16, halfwidth, bw.ldb, sband, B, w.resid, c->npad, w.Y, c->m + 1,
+                                      c->npad, (int64_t)c->mpad * c->npad, bw.logdet_band, bw.gram, w.info_c, s);
+        if (rc) return rc;
+    }
+    {
+        ProfScope ps(s, PS_SOLVE);
+        rc = sf_launch_woodbury(bw.gram, c->m + 1, B, bw.logdet_band, w.logdet, w.sqmah, w.info_c, s);
+        if (rc) return rc;
+        rc = sf_launch_finish(B, w.logdet, w.sqmah, w.info_e, w.info_c, d_lnl, d_info, s);
+        if (rc) return rc;
+    }
+    return export_logdet_sqmah(d_logdet, d_sqmah, w, B, s);
+}
+
+extern "C" int sf_band_logdet_gram_batch(const double* d_band, int n, int halfwidth, int ldb, int64_t stride,
+                                         int batch, const double* d_rhs, int nrhs, int ldr, int64_t rhs_stride,
+                                         double* d_logdet, double* d_gram, int* d_info, void* stream) {
+    if (!d_band || !d_rhs || !d_logdet || !d_gram || !d_info) {
+        sf_set_error("sf_band_logdet_gram_batch: null pointer");
+        return SF_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    SF_HIP(hipMemsetAsync(d_info, 0, sizeof(int) * (size_t)batch, s));
+    return sf_launch_band_forms(d_band, n, halfwidth, ldb, stride, batch, nullptr, 0, d_rhs, nrhs, ldr, rhs_stride,
+                                d_logdet, d_gram, d_info, s);
+}

@@ -1,5 +1,5 @@
 // Bordered band matrices on the fused panel kernel: the border / finish kernels and the driver sf_launch_potrf_band.
-// Used by the band solver in sf_abi.cpp for half-widths beyond the LDS window of k_band_forms.
+// Used by the band solver in sf_banded.cpp for half-widths beyond the LDS window of k_band_forms.
 #pragma once
 #include "sf_chol_host.h"
 #include "sf_chol_panel.h"

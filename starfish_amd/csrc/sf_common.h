@@ -7,18 +7,15 @@
 #include <atomic>
 #include <initializer_list>
 #include <mutex>
-#include "../../include/starfish_amd.h"
+#include "sf_base.h"
 
 #define SF_LEAF 64        // Cholesky leaf block (potrf / trsm granularity); matrices padded to it
 #define SF_NB 256         // outer left-looking panel width
-#define SF_C_KMS 2.99792458e5
 #define SF_MAX_LOCAL 32   // local kernels per model (sf_fill.hip: 32-bit masks of the fill tiles, per-block tables)
 #define SF_NF_MIN_VSINI 16     // FFT lengths of a model with vsini: k_spline_apply takes whole 16-point blocks,
 #define SF_NF_MAX_VSINI 65536  // sf_launch_broaden transforms at most 65536 points
 
 typedef double sf_d4 __attribute__((ext_vector_type(4)));
-
-void sf_set_error(const char* fmt, ...);
 
 #define SF_HIP(call)                                                                     \
     do {                                                                                 \
@@ -107,7 +104,7 @@ int sf_exec_event(sf_exec* ex, hipEvent_t* e);  // next pooled event (timing dis
 void sf_exec_release(sf_exec* ex);
 sf_exec* sf_exec_thread_local(void);
 
-// profiling hooks (sf_abi.cpp)
+// profiling hooks (sf_prof.cpp)
 void sf_prof_gemm_begin(hipStream_t s, double flops, void** tok);
 void sf_prof_gemm_end(void* tok);
 

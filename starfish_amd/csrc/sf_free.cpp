@@ -1,0 +1,259 @@
+// C-ABI host layer: the context-free entry points (Starfish's free functions, the stand-alone Cholesky stage, emulator
+// training) and the tuning / debug hooks.
+#include <vector>
+
+#include "sf_hostmath.h"
+#include "sf_prof.h"
+#include "sf_work.h"
+
+extern "C" int sf_global_cov(const double* d_wave, int n, double amplitude, double lengthscale, double* d_out,
+                             void* stream) {
+    if (!d_wave || !d_out || n < 0) {
+        sf_set_error("sf_global_cov: bad argument");
+        return SF_EINVAL;
+    }
+    return sf_launch_global_cov(d_wave, n, amplitude, lengthscale, d_out, (hipStream_t)stream);
+}
+extern "C" int sf_local_cov(const double* d_wave, int n, double amplitude, double mu, double sigma,
+                            int accumulate, double* d_out, void* stream) {
+    if (!d_wave || !d_out || n < 0) {
+        sf_set_error("sf_local_cov: bad argument");
+        return SF_EINVAL;
+    }
+    return sf_launch_local_cov(d_wave, n, amplitude, mu, sigma, accumulate, d_out, (hipStream_t)stream);
+}
+
+extern "C" size_t sf_fft_workspace_bytes(int rows, int nf) {
+    if (rows <= 0 || nf <= 0) return 0;
+    return carve_fft(rows, nf, nullptr, 0).bytes;
+}
+static int broaden_free(const double* d_flux, int rows, int nf, double dv, int kind, double param,
+                        double* d_out, void* d_work, size_t work_bytes, hipStream_t s) {
+    if (!d_flux || !d_out || rows <= 0 || !d_work || work_bytes < sf_fft_workspace_bytes(rows, nf)) {
+        sf_set_error("broaden: bad argument or workspace");
+        return SF_EINVAL;
+    }
+    if (nf < 2 || (nf & (nf - 1))) {
+        sf_set_error("broaden: nf=%d must be a power of two", nf);
+        return SF_EINVAL;
+    }
+    const FftWork w = carve_fft(rows, nf, d_work, work_bytes);
+    std::vector<double> tw;
+    make_twiddles(nf, tw);
+    // pageable host -> device copy: synchronous w.r.t. the host buffer, safe to free afterwards
+    SF_HIP(hipMemcpyAsync(w.tw, tw.data(), sizeof(double) * (size_t)nf, hipMemcpyHostToDevice, s));
+    SF_HIP(hipStreamSynchronize(s));
+    sf_broaden_args a;
+    a.in = d_flux;
+    a.spec = nullptr;
+    a.B = 1;
+    a.rows = rows;
+    a.nf = nf;
+    a.tw = (const double2*)w.tw;
+    a.dv = dv;
+    a.kind = kind;
+    a.params = nullptr;
+    a.pstride = 0;
+    a.poff = 0;
+    a.scalar_param = param;
+    a.out = d_out;
+    a.ob = 0;
+    a.orow = nf;
+    a.oelem = 1;
+    a.gscratch = w.scratch;
+    a.mult = nullptr;
+    a.info = nullptr;
+    return sf_launch_broaden(a, s);
+}
+extern "C" int sf_rotational_broaden(const double* d_flux, int rows, int nf, double dv, double vsini,
+                                     double* d_out, void* d_work, size_t work_bytes, void* stream) {
+    if (!(vsini > 0.0)) {
+        sf_set_error("vsini must be positive");  // transforms.py:121-122
+        return SF_EINVAL;
+    }
+    return broaden_free(d_flux, rows, nf, dv, 1, vsini, d_out, d_work, work_bytes, (hipStream_t)stream);
+}
+extern "C" int sf_instrumental_broaden(const double* d_flux, int rows, int nf, double dv, double fwhm,
+                                       double* d_out, void* d_work, size_t work_bytes, void* stream) {
+    if (fwhm < 0.0) {
+        sf_set_error("FWHM must be non-negative");  // transforms.py:78-79
+        return SF_EINVAL;
+    }
+    return broaden_free(d_flux, rows, nf, dv, 2, fwhm, d_out, d_work, work_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t sf_resample_workspace_bytes(int n, int rows) {
+    if (n <= 0 || rows <= 0) return 0;
+    return carve_resample(n, rows, nullptr, 0).bytes;
+}
+extern "C" int sf_resample(const double* h_wave, int n, const double* d_flux, int rows, const double* d_new_wave,
+                           int nq, double* d_out, void* d_work, size_t work_bytes, void* stream) {
+    // (no queries: the caller's query and output buffers may be empty, i.e. null)
+    if (!h_wave || !d_flux || (nq > 0 && (!d_new_wave || !d_out)) || rows <= 0 || nq < 0 || !d_work ||
+        work_bytes < sf_resample_workspace_bytes(n, rows)) {
+        sf_set_error("sf_resample: bad argument or workspace");
+        return SF_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<double> t, Lf, Uf, rdiag;
+    int rc = quintic_collocation_lu(h_wave, n, t, Lf, Uf, rdiag);
+    if (rc) return rc;
+    const ResampleWork w = carve_resample(n, rows, d_work, work_bytes);
+    SF_HIP(hipMemcpyAsync(w.t, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, s));
+    SF_HIP(hipMemcpyAsync(w.Lf, Lf.data(), sizeof(double) * Lf.size(), hipMemcpyHostToDevice, s));
+    SF_HIP(hipMemcpyAsync(w.Uf, Uf.data(), sizeof(double) * Uf.size(), hipMemcpyHostToDevice, s));
+    SF_HIP(hipMemcpyAsync(w.rdiag, rdiag.data(), sizeof(double) * rdiag.size(), hipMemcpyHostToDevice, s));
+    SF_HIP(hipMemcpyAsync(w.coef, d_flux, sizeof(double) * (size_t)n * rows, hipMemcpyDeviceToDevice, s));
+    SF_HIP(hipStreamSynchronize(s));  // the host vectors go out of scope below
+    rc = sf_launch_spline_solve(w.coef, 1, rows, 0, n, 1, n, w.Lf, w.Uf, w.rdiag, s);
+    if (rc) return rc;
+    if (nq == 0) return SF_OK;
+    return sf_launch_spline_eval(w.coef, rows, n, w.t, d_new_wave, nq, d_out, s);
+}
+
+// `count` host doubles ride in a small device buffer of `cap` doubles owned by this call: uploaded on s, run(buffer)
+// enqueues its user, then the stream is synchronised and the buffer freed (also when the upload or the launch failed)
+template <class F>
+static int with_device_copy(const double* h_src, size_t count, size_t cap, hipStream_t s, F&& run) {
+    double* d = nullptr;
+    SF_HIP(hipMalloc((void**)&d, sizeof(double) * cap));
+    int rc = SF_OK;
+    if (hipMemcpyAsync(d, h_src, sizeof(double) * count, hipMemcpyHostToDevice, s) != hipSuccess) rc = SF_EHIP;
+    if (!rc) rc = run(d);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(d);
+    return rc;
+}
+
+extern "C" int sf_chebyshev_correct(const double* d_wave, int n, double wave_max, const double* d_flux, int rows,
+                                    const double* h_coeffs, int ncoef, double* d_out, void* stream) {
+    if (!d_wave || !d_flux || !h_coeffs || !d_out || n < 0 || rows <= 0 || ncoef < 1 || ncoef > 64) {
+        sf_set_error("sf_chebyshev_correct: bad argument");
+        return SF_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    return with_device_copy(h_coeffs, ncoef, 64, s, [&](const double* dco) {
+        return sf_launch_cheb_rows(d_wave, n, wave_max, d_flux, rows, dco, ncoef, d_out, s);
+    });
+}
+
+extern "C" int sf_extinct_ccm89(const double* d_wave, int n, const double* d_flux, int rows, double Av, double Rv,
+                                double* d_out, void* stream) {
+    if (!d_wave || !d_flux || !d_out || n < 0 || rows <= 0 || !(Rv > 0.0)) {
+        sf_set_error("sf_extinct_ccm89: bad argument");
+        return SF_EINVAL;
+    }
+    return sf_launch_extinct_rows(d_wave, n, d_flux, rows, Av, Rv, 0, d_out, (hipStream_t)stream);
+}
+extern "C" int sf_extinct(const double* d_wave, int n, const double* d_flux, int rows, double Av, double Rv, int law,
+                          double* d_out, void* stream) {
+    if (!d_wave || !d_flux || !d_out || n < 0 || rows <= 0 || !(Rv > 0.0) || law < 0 || law > 4) {
+        sf_set_error("sf_extinct: bad argument");
+        return SF_EINVAL;
+    }
+    if (law <= 2) return sf_launch_extinct_rows(d_wave, n, d_flux, rows, Av, Rv, law, d_out, (hipStream_t)stream);
+    std::vector<double> tab;
+    int rc = extinct_spline_table(law, Rv, tab);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    return with_device_copy(tab.data(), tab.size(), tab.size(), s, [&](const double* dtab) {
+        return sf_launch_extinct_spline_rows(d_wave, n, d_flux, rows, Av, Rv, dtab, d_out, s);
+    });
+}
+
+extern "C" size_t sf_potrf_workspace_bytes(int n, int batch) {
+    if (n <= 0 || batch <= 0) return 0;
+    return carve_potrf(n, batch, nullptr, 0).bytes;
+}
+extern "C" int sf_potrf_batch(double* d_A, int n, int lda, int64_t stride, int batch, int* d_info, void* d_work,
+                              size_t work_bytes, void* stream) {
+    if (!d_A || !d_info || !d_work || work_bytes < sf_potrf_workspace_bytes(n, batch)) {
+        sf_set_error("sf_potrf_batch: bad argument or workspace");
+        return SF_EINVAL;
+    }
+    double* ltbuf = carve_potrf(n, batch, d_work, work_bytes).ltbuf;
+    ProfScope ps((hipStream_t)stream, PS_POTRF);
+    return sf_launch_potrf(d_A, n, lda, stride, batch, d_info, ltbuf, nullptr, 0, (hipStream_t)stream);
+}
+extern "C" int sf_logdet_sqmah_batch(const double* d_L, int n, int lda, int64_t stride, int batch,
+                                     const double* d_R, int ldr, void* d_work, size_t work_bytes,
+                                     double* d_logdet, double* d_sqmah, void* stream) {
+    if (!d_L || !d_R || !d_logdet || !d_sqmah || ldr < n) {
+        sf_set_error("sf_logdet_sqmah_batch: bad argument");
+        return SF_EINVAL;
+    }
+    double* z = nullptr;
+    if (d_work && work_bytes >= sf_potrf_workspace_bytes(n, batch)) z = carve_potrf(n, batch, d_work, work_bytes).z;
+    ProfScope ps((hipStream_t)stream, PS_SOLVE);
+    return sf_launch_logdet_sqmah(d_L, n, lda, stride, batch, d_R, ldr, z, d_logdet, d_sqmah,
+                                  (hipStream_t)stream);
+}
+
+extern "C" int sf_emulator_v11_build(const double* d_grid, int M, int P, int m, const double* d_hyper, const double* d_iphiphi,
+                                     double* d_A, int npad, int lda, void* stream) {
+    return sf_launch_v11_build(d_grid, M, P, m, d_hyper, d_iphiphi, d_A, npad, lda, (hipStream_t)stream);
+}
+extern "C" int sf_emulator_v11_build_batch(const double* d_grid, int M, int P, int m, const double* d_hyper, int hyper_stride,
+                                           int B, const double* d_iphiphi, double* d_A, int npad, int lda, int64_t stride,
+                                           int lower_only, const double* d_w_hat, double* d_R, int ldr, void* stream) {
+    return sf_launch_v11_build_batch(d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, d_A, npad, lda, stride, lower_only,
+                                     d_w_hat, d_R, ldr, (hipStream_t)stream);
+}
+
+// The training objective for B hyper-parameter rows (workspace: carve_emu_train)
+extern "C" size_t sf_emulator_loglike_workspace_bytes(int M, int m, int B) { return carve_emu_train(M, m, B, nullptr, 0).bytes; }
+extern "C" int sf_emulator_loglike_batch(const double* d_grid, int M, int P, int m, const double* d_hyper, int hyper_stride,
+                                         int B, const double* d_iphiphi, const double* d_w_hat, double* d_lnl, double* d_logdet,
+                                         double* d_sqmah, int* d_info, void* d_work, size_t work_bytes, void* stream) {
+    const EmuTrainWork w = carve_emu_train(M, m, B, d_work, work_bytes);
+    if (!w.bytes || !d_grid || !d_hyper || !d_iphiphi || !d_w_hat || !d_lnl || !d_info || !d_work || P <= 0 || B > 65535 ||
+        (int64_t)hyper_stride < 1 + (int64_t)m + (int64_t)m * P || ((uintptr_t)d_work & 255)) {
+        sf_set_error("sf_emulator_loglike_batch: bad argument (d_lnl, d_info and a 256-byte aligned d_work are required, "
+                     "hyper_stride >= 1 + m + m P, B <= 65535)");
+        return SF_EINVAL;
+    }
+    if (work_bytes < w.bytes) {
+        sf_set_error("sf_emulator_loglike_batch: workspace of %zu bytes, %zu needed", work_bytes, w.bytes);
+        return SF_ENOMEM;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    double* logdet = d_logdet ? d_logdet : w.logdet;
+    double* sqmah = d_sqmah ? d_sqmah : w.sqmah;
+    // (every argument check of the stages is made by the first one before it enqueues anything: P <= 8 is the build's)
+    int rc = sf_launch_v11_build_batch(d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, w.A, w.npad, w.lda, w.stride, 1, d_w_hat,
+                                       w.R, w.npad, s);
+    if (rc) return rc;
+    rc = sf_potrf_batch(w.A, w.npad, w.lda, w.stride, B, w.info_c, w.potrf, w.potrf_bytes, stream);
+    if (rc) return rc;
+    rc = sf_logdet_sqmah_batch(w.A, w.npad, w.lda, w.stride, B, w.R, w.npad, w.potrf, w.potrf_bytes, logdet, sqmah, stream);
+    if (rc) return rc;
+    ProfScope ps(s, PS_SOLVE);
+    return sf_launch_finish(B, logdet, sqmah, w.info_c, nullptr, d_lnl, d_info, s);
+}
+
+// Recovery switch of the callers (process-global): after a batch came back SF_INFO_INTERNAL the host layer turns the
+// persistent-kernel sequence off and re-runs the batch on a launch sequence (starfish_amd/_device.py).
+extern "C" int sf_persistent_potrf(int enable) { return sf_set_persistent_potrf(enable); }
+extern "C" int sf_persistent_potrf_status(long long* h_out8) {
+    if (!h_out8) {
+        sf_set_error("sf_persistent_potrf_status: h_out8 is required");
+        return SF_EINVAL;
+    }
+    return sf_persistent_potrf_read_status(h_out8);
+}
+
+// Tuning / test aid: pin the launch sequence of the batched Cholesky (process-global).
+extern "C" int sf_debug_cholesky_sequence(int mode) { return sf_set_cholesky_sequence(mode); }
+
+// Tuning aid (not part of the Starfish surface): sustained shader clock while other streams are busy.
+extern "C" int sf_debug_stream_write(double* d_dst, size_t count, double value, void* stream) {
+    if (!d_dst) {
+        sf_set_error("sf_debug_stream_write: d_dst is required");
+        return SF_EINVAL;
+    }
+    return sf_launch_stream_write(d_dst, count, value, (hipStream_t)stream);
+}
+
+extern "C" int sf_debug_clock_probe(long long* d_out2, long long wall_ticks_100mhz, void* stream) {
+    return sf_launch_clock_probe(d_out2, wall_ticks_100mhz, (hipStream_t)stream);
+}

@@ -1,0 +1,22 @@
+// Stages of the likelihood that the single-order, multi-order and banded sequences share (internal; sf_abi.cpp).
+#pragma once
+#include "sf_prof.h"
+#include "sf_work.h"
+
+#pragma GCC visibility push(hidden)
+// emulator + transform chain -> unscaled X / flux, scale, then residual / Y
+int run_transforms(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const Work& w, double* d_flux_out,
+                   double* d_X_out, double* d_resid_out, double* d_log_scale, bool want_Y, hipStream_t s);
+sf_fill_args fill_args(sf_ctx* c, const sf_model_desc* mdl, const double* d_params, const Work& w);
+// The likelihood's fill of the workspace matrices of layout L (lower tiles, identity padding, jitter), in the frame fp of
+// the factorisation: only the tiles that carry more than the rank-m term are materialised (tile map and list)
+sf_fill_args loglike_fill_args(sf_ctx* c, const sf_model_desc* mdl, const double* d_params, const Work& w, const Layout& L, int fp);
+// The rest of the likelihood of `units` matrices filled that way: the factorisation, whose generator (Y, tile map, same
+// frame) supplies the tiles the fill left out and through which the residual rides (w.resid becomes z = L^-1 R); then
+// logdet and the squared Mahalanobis distance -> lnL.  ltbuf: the factorisation's scratch, ex: its executor.
+int loglike_factor_finish(const Work& w, const Layout& L, int fp, int units, double* ltbuf, double* d_lnl, int* d_info,
+                          hipStream_t s, sf_exec* ex);
+// optional results of `units` units, copied out of the workspace behind everything enqueued on s
+int export_info(int* d_info, const Work& w, int units, hipStream_t s);
+int export_logdet_sqmah(double* d_logdet, double* d_sqmah, const Work& w, int units, hipStream_t s);
+#pragma GCC visibility pop

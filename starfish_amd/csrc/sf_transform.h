@@ -2,9 +2,8 @@
 #pragma once
 #include "sf_common.h"
 
-#define SF_KB 5      // sub/super-diagonals stored for the quintic collocation LU
+// (SF_KB, SF_IW: sf_base.h)
 #define SF_MAX_M 32  // eigenspectra handled by the per-pixel rank-m factor kernel
-#define SF_IW 64     // half-width of the truncated inverse of the collocation matrix (decay ~0.43^k: < 1e-23)
 
 struct sf_broaden_args {
     const double* in;      // rows x nf real input (free functions) or NULL

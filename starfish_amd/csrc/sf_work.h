@@ -1,0 +1,229 @@
+// Workspace layouts of the C-ABI (internal): every caller-provided workspace is carved by ONE function, which the size
+// query runs on a null base and the entry point on the caller's pointer.
+#pragma once
+#include <type_traits>
+
+#include "sf_ctx.h"
+
+struct Carve {
+    char* base;
+    size_t off = 0, cap;
+    Carve(void* p, size_t bytes) : base((char*)p), cap(bytes) {}
+    template <typename T>
+    T* take(size_t count) {
+        off = sf_align_up(off, 256);
+        T* r = base ? (T*)(base + off) : nullptr;
+        off += sizeof(T) * count;
+        return r;
+    }
+};
+static int work_fits(size_t have, size_t need) {
+    if (have < need) {
+        sf_set_error("workspace too small: have %zu, need %zu", have, need);
+        return SF_ENOMEM;
+    }
+    return SF_OK;
+}
+// Row strides / per-unit sizes of the batched buffers.  A single-order call uses the order's own padding; a
+// multi-order call (sf_loglike_multi_batch) pads every order to the largest one of the group so that all
+// units share ONE batched factorisation.
+struct Layout {
+    int m, mpad, M, nf, rows, npad, lda;
+};
+static size_t tilemap_bytes(const Layout& L) {  // per unit: one byte per 128 x 128 tile, as the kernels index it
+    const size_t nt128 = (size_t)(L.npad + 127) / 128;  // (the same count in the frame shifted by 64: npad = 64 mod 128 there)
+    return nt128 * nt128;
+}
+static Layout layout_of(const sf_ctx* c) { return Layout{c->m, c->mpad, c->M, c->nf, c->rows, c->npad, c->lda}; }
+struct Work {
+    double *mu, *Lw, *zs, *kv, *scale, *logdet, *sqmah, *coef, *ybro, *Xraw, *fraw, *resid, *Y, *C, *ltbuf, *mult, *gtab;
+    double2* fft;
+    int *info_e, *info_c;
+    unsigned char* tilemap;
+    unsigned* tilelist;        // compact list of the materialised tiles (see sf_fill_args)
+    int* tilecount;
+    unsigned char* dmap;       // dense fill of caller matrices: structured-support map / list of 64 x 64 tiles
+    unsigned short* dlist;
+    int* dcount;
+    size_t bytes;
+    Layout L;
+    int trans_bt = 0;      // walkers one set of transient buffers is sized for
+    size_t fft_set = 0;    // double2 per set
+};
+// The buffers of Work in carve order: f(pointer, elements, present, kind).
+//   PER_UNIT  `elements` per unit; a slice of the units [u0, ...) starts u0 * elements further on
+//   PER_SET   `elements` per set of the transient buffers of the transform chain (used by one launch sequence at a time,
+//             stream ordered; one set per lane of a multi-order call)
+//   SHARED    one per workspace, sized by carve
+enum WorkKind { PER_UNIT, PER_SET, SHARED };
+template <class F>
+static void work_buffers(Work& w, bool has_vsini, bool need_C, F&& f) {
+    const Layout& L = w.L;
+    const size_t npad = (size_t)L.npad, bt = (size_t)w.trans_bt;
+    f(w.mu, (size_t)L.m, true, PER_UNIT);
+    f(w.Lw, (size_t)L.m * L.m, true, PER_UNIT);
+    f(w.zs, (size_t)L.m * L.M * L.m, true, PER_UNIT);
+    f(w.kv, (size_t)L.m * L.M, true, PER_UNIT);
+    f(w.scale, 1, true, PER_UNIT);
+    f(w.logdet, 1, true, PER_UNIT);
+    f(w.sqmah, 1, true, PER_UNIT);
+    f(w.info_e, 1, true, PER_UNIT);
+    f(w.info_c, 1, true, PER_UNIT);
+    f(w.coef, bt * L.nf * L.rows, has_vsini, PER_SET);
+    f(w.ybro, bt * L.nf * L.rows, has_vsini, PER_SET);  // broadened rows before the fit
+    f(w.mult, bt * (L.nf / 2 + 1), has_vsini, PER_SET);  // broadening kernel per walker
+    f(w.fft, w.fft_set, w.fft_set != 0, PER_SET);
+    f(w.Xraw, L.m * npad, true, PER_UNIT);
+    f(w.fraw, npad, true, PER_UNIT);
+    f(w.resid, npad, true, PER_UNIT);
+    f(w.Y, L.mpad * npad, true, PER_UNIT);
+    double* reserved = nullptr;  // npad doubles per unit that nothing reads (once the z of a separate triangular solve):
+    f(reserved, npad, true, PER_UNIT);  // kept so that C and the Cholesky scratch stay at the offsets they were measured at
+    f(w.ltbuf, 0, need_C, SHARED);  // Cholesky scratch
+    f(w.tilemap, tilemap_bytes(L), need_C, PER_UNIT);
+    f(w.tilelist, tilemap_bytes(L), need_C, PER_UNIT);  // (capacity: every tile)
+    f(w.tilecount, 1, need_C, PER_UNIT);
+    f(w.gtab, npad, need_C, PER_UNIT);
+    f(w.dmap, sf_fill_dense_map_tiles(L.npad), true, PER_UNIT);
+    f(w.dlist, sf_fill_dense_map_tiles(L.npad), true, PER_UNIT);
+    f(w.dcount, 1, true, PER_UNIT);
+    f(w.C, npad * L.lda, need_C, PER_UNIT);
+}
+// B units of per-unit buffers; the transient buffers are sized for Bt walkers, trans_sets independent sets of them (for
+// transform chains running side by side); the Cholesky scratch for potrf_units matrices per factorisation (0: all B)
+static Work carve(const Layout& L, const sf_model_desc* mdl, int B, int Bt, void* p, size_t cap, bool need_C,
+                  int potrf_units = 0, int trans_sets = 1) {
+    Carve k(p, cap);
+    Work w{};
+    w.L = L;
+    w.trans_bt = Bt;
+    w.fft_set = (mdl->has_vsini ? sf_fft_half_scratch_bytes(Bt * L.rows, L.nf) : 0) / sizeof(double2);
+    const size_t ltbuf = sf_align_up(sf_potrf_work_doubles(L.npad, potrf_units > 0 ? potrf_units : B), 32);
+    work_buffers(w, mdl->has_vsini != 0, need_C, [&](auto*& ptr, size_t elements, bool present, WorkKind kind) {
+        using T = std::remove_reference_t<decltype(*ptr)>;
+        const size_t count = kind == PER_UNIT ? (size_t)B * elements : kind == PER_SET ? (size_t)trans_sets * elements : ltbuf;
+        ptr = present ? k.take<T>(count) : nullptr;
+    });
+    w.bytes = sf_align_up(k.off, 256);
+    return w;
+}
+static Work carve(const sf_ctx* c, const sf_model_desc* mdl, int B, void* p, size_t cap, bool need_C) {
+    return carve(layout_of(c), mdl, B, B, p, cap, need_C);
+}
+// the buffers of the units [u0, ...) of a multi-order workspace (transient buffers are shared)
+static Work slice(const Work& w, int u0) {
+    Work s = w;
+    work_buffers(s, false, false, [&](auto*& ptr, size_t elements, bool, WorkKind kind) {
+        if (ptr && kind == PER_UNIT) ptr += (size_t)u0 * elements;
+    });
+    return s;
+}
+// set `set` of the transient buffers (multi-order calls run several orders' transform chains side by side)
+static Work with_trans_set(const Work& w, int set) {
+    Work s = w;
+    work_buffers(s, false, false, [&](auto*& ptr, size_t elements, bool, WorkKind kind) {
+        if (ptr && kind == PER_SET) ptr += (size_t)set * elements;
+    });
+    return s;
+}
+
+// ------------------------------------------------------------------- structure-exploiting solver
+// (behind the Work of the same call: base_bytes = its size)
+struct BandWork {
+    double *band, *gram, *logdet_band, *twist, *gtab, *tiles;
+    int ldb;
+    size_t bytes;
+};
+static BandWork carve_band(const sf_ctx* c, int B, int halfwidth, void* p, size_t cap, size_t base_bytes) {
+    Carve k(p, cap);
+    k.off = base_bytes;
+    BandWork w;
+    // Half-widths beyond the LDS window are factorised as bordered band matrices on the tile kernels of the dense
+    // path (sf_launch_potrf_band); the band fill writes those tiles directly.
+    const bool tiles = halfwidth > sf_band_max_halfwidth(c->m + 1);
+    w.ldb = tiles ? 128 * (sf_band_tiles_wt(halfwidth) + 1) : ((halfwidth + 2) & ~1);
+    w.band = tiles ? nullptr : k.take<double>((size_t)B * c->npad * w.ldb);  // (the tiles are filled directly)
+    w.gram = k.take<double>((size_t)B * (c->m + 1) * (c->m + 1));
+    w.logdet_band = k.take<double>((size_t)B);
+    w.twist = tiles ? nullptr : k.take<double>(sf_band_twisted_work_doubles(halfwidth, c->m + 1, B));
+    w.gtab = k.take<double>((size_t)B * (w.ldb + 2));
+    w.tiles = tiles ? k.take<double>(sf_band_tiles_doubles(c->npad, B)) : nullptr;
+    w.bytes = sf_align_up(k.off, 256);
+    return w;
+}
+
+// ------------------------------------------------------------------- context-free workspaces
+// sf_potrf_batch / sf_logdet_sqmah_batch: z scratch of the stand-alone solve + the transposed leaf factor read by the panel solves
+struct PotrfWork {
+    double *z, *ltbuf;
+    size_t bytes;
+};
+static PotrfWork carve_potrf(int n, int batch, void* p, size_t cap) {
+    Carve k(p, cap);
+    PotrfWork w;
+    w.z = k.take<double>((size_t)n * batch);
+    w.ltbuf = k.take<double>(sf_potrf_work_doubles(n, batch));
+    w.bytes = sf_align_up(k.off, 256) + 256;  // (slack the size query has always included)
+    return w;
+}
+// the broadening free functions: twiddles, then the scratch of a transform that does not fit the LDS
+struct FftWork {
+    double* tw;
+    double2* scratch;
+    size_t bytes;
+};
+static FftWork carve_fft(int rows, int nf, void* p, size_t cap) {
+    Carve k(p, cap);
+    FftWork w;
+    const size_t fb = sf_fft_scratch_bytes(rows, nf);
+    w.tw = k.take<double>((size_t)nf);
+    w.scratch = k.take<double2>(fb / sizeof(double2));
+    if (!fb) w.scratch = nullptr;
+    w.bytes = k.off + 256;  // (slack the size query has always included)
+    return w;
+}
+// sf_resample: knots, Lf, Uf, rdiag, coefficient rows
+struct ResampleWork {
+    double *t, *Lf, *Uf, *rdiag, *coef;
+    size_t bytes;
+};
+static ResampleWork carve_resample(int n, int rows, void* p, size_t cap) {
+    Carve k(p, cap);
+    ResampleWork w;
+    w.t = k.take<double>((size_t)n + 6);
+    w.Lf = k.take<double>((size_t)n * SF_KB);
+    w.Uf = k.take<double>((size_t)n * SF_KB);
+    w.rdiag = k.take<double>((size_t)n);
+    w.coef = k.take<double>((size_t)n * rows);
+    w.bytes = sf_align_up(k.off, 256) + 1024;  // (slack the size query has always included)
+    return w;
+}
+// The training objective for B hyper-parameter rows: the B matrices (npad = m M rounded up to the Cholesky leaf, row stride
+// npad + 16 as Emulator.log_likelihood lays its one matrix out), the B x npad right-hand sides, logdet / sqmah / the
+// factorisation's info, then the workspace of sf_potrf_batch (carve_potrf).
+struct EmuTrainWork {
+    int npad, lda;
+    int64_t stride;
+    double *A, *R, *logdet, *sqmah;
+    int* info_c;
+    char* potrf;
+    size_t potrf_bytes, bytes;
+};
+static EmuTrainWork carve_emu_train(int M, int m, int B, void* p, size_t cap) {
+    EmuTrainWork w = {};
+    if (M <= 0 || m <= 0 || B <= 0 || (int64_t)m * M > (1 << 30)) return w;
+    w.npad = (m * M + SF_LEAF - 1) / SF_LEAF * SF_LEAF;
+    w.lda = w.npad + 16;
+    w.stride = (int64_t)w.npad * w.lda;
+    const size_t b = (size_t)B;
+    Carve k(p, cap);
+    w.A = k.take<double>(b * (size_t)w.stride);
+    w.R = k.take<double>(b * w.npad);
+    w.logdet = k.take<double>(b);
+    w.sqmah = k.take<double>(b);
+    w.info_c = k.take<int>(b);
+    w.potrf_bytes = carve_potrf(w.npad, B, nullptr, 0).bytes;
+    w.potrf = k.take<char>(w.potrf_bytes);
+    w.bytes = k.off;
+    return w;
+}
