@@ -37,24 +37,9 @@ __device__ __forceinline__ double sf_local_elem(double d_row, double d_col, doub
 __device__ __forceinline__ double sf_local_metric(double w, double mu) {
     return SF_C_KMS / mu * fabs(w - mu);  // kernels.py:69
 }
-
-// The tile bodies evaluate the two element formulas for 16 entries per lane: inlined (fp64 cos with its argument reduction, exp:
-// ~1 KB of code each) the structured tile body is 66-70 KB of straight-line code per tile -- more than the 64 KB instruction
-// cache of a CU pair holds.  As real calls (-DSF_FILL_CALL_ELEMS) the kernels are 15 KB, 143 instead of 163 VGPRs, same bits
-// -- and no faster where it counts (round 6, same box: dense fill of cfg 2 3.39 -> 3.43 ms, N = 3000 with ld = N 2.40 ->
-// 2.27, ld = 3008 2.15 -> 2.09, the likelihood's tile-list fill 0.495 both: profiles/r06_d_fill_called_elements_ab.txt):
-// sequential code streams through the instruction prefetch, the kernel is bound by the latency of its fp64 chains.  Inlined.
-#ifndef SF_FILL_CALL_ELEMS
-#define SF_ELEM_CALL __forceinline__
-#else
-#define SF_ELEM_CALL __attribute__((noinline))
-#endif
-__device__ SF_ELEM_CALL double sf_matern_elem_t(double w_row, double w_col, double amp, double ls, double r0) {
-    return sf_matern_elem(w_row, w_col, amp, ls, r0);
-}
-__device__ SF_ELEM_CALL double sf_local_elem_t(double d_row, double d_col, double amp, double sigma, double r0) {
-    return sf_local_elem(d_row, d_col, amp, sigma, r0);
-}
+// The tile bodies inline both element formulas, 16 entries per lane: 66-70 KB of straight-line code per structured tile.
+// As real calls the kernels were 15 KB with 143 instead of 163 VGPRs, the same bits, and no faster (round 6:
+// profiles/r06_d_fill_called_elements_ab.txt): the kernel is bound by the latency of its fp64 chains.
 
 // Which 128 x 128 tiles of the lower triangle carry anything besides the rank-m term (diagonal
 // SF_NB blocks: sigma^2 / jitter / identity padding; Matern band; local patches)?  Only those are
@@ -204,7 +189,7 @@ __device__ __forceinline__ void sf_tile_finish(const sf_fill_args& a, int b, int
                 } else if (do_glob) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        if (col0 + r < a.n) v[r] = v[r] + sf_matern_elem_t(w_row, w_col[r], g_amp, g_ls, g_r0);
+                        if (col0 + r < a.n) v[r] = v[r] + sf_matern_elem(w_row, w_col[r], g_amp, g_ls, g_r0);
                 }
                 if (lmask) {
                     double loc[4] = {0.0, 0.0, 0.0, 0.0};
@@ -216,7 +201,7 @@ __device__ __forceinline__ void sf_tile_finish(const sf_fill_args& a, int b, int
                         const double d_row = sf_local_metric(w_row, mu);
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            loc[r] = loc[r] + sf_local_elem_t(d_row, sf_local_metric(w_col[r], mu), amp, sig, 4 * sig);
+                            loc[r] = loc[r] + sf_local_elem(d_row, sf_local_metric(w_col[r], mu), amp, sig, 4 * sig);
                     }
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
@@ -265,7 +250,6 @@ __device__ __forceinline__ void sf_fill_tile(const sf_fill_args& a, int b, int t
     const int gam = lane & 15, q = lane >> 4;
 
     const double* __restrict__ Yb = a.Y + (int64_t)b * a.mpad * a.ldy;
-    double* __restrict__ Cb = a.C + (int64_t)b * a.stride;
 
     // acc[ti][tj] element (row R0+ti*16+gam, cols C0+tj*16+4q+r)
     sf_d4 acc[2][2];
@@ -318,11 +302,23 @@ __global__ __launch_bounds__(256, BAND ? 2 : 4) void k_fill_tiles_list(sf_fill_a
 
 __global__ void k_band_gtab(sf_fill_args a, double* __restrict__ gtab, int ws);
 
-int sf_launch_fill(const sf_fill_args& a, int B, hipStream_t s) {
+static int sf_check_n_local(const sf_fill_args& a) {  // the 32-bit masks of the tiles, the per-block table of the band fill
     if (a.n_local > SF_MAX_LOCAL) {
         sf_set_error("at most %d local kernels are supported", SF_MAX_LOCAL);
         return SF_EINVAL;
     }
+    return SF_OK;
+}
+static int sf_check_fill_grid(long long nblk) {  // one workgroup per tile (segment): a one-dimensional grid
+    if (nblk > 0x7fffffffLL) {
+        sf_set_error("fill grid too large");
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+
+int sf_launch_fill(const sf_fill_args& a, int B, hipStream_t s) {
+    SF_CHECK(sf_check_n_local(a));
     if (a.fp != 0 && (a.fp != 64 || !a.tilemap || !a.lower_only)) {
         sf_set_error("fill: a shifted tile frame needs fp = 64, a tile map and lower_only");
         return SF_EINVAL;
@@ -330,10 +326,7 @@ int sf_launch_fill(const sf_fill_args& a, int B, hipStream_t s) {
     const int nout = sf_fill_extent(a);
     const int nt = (nout + FT - 1) / FT;
     const long long nblk = (long long)nt * nt * B;
-    if (nblk > 0x7fffffffLL) {
-        sf_set_error("fill grid too large");
-        return SF_EINVAL;
-    }
+    SF_CHECK(sf_check_fill_grid(nblk));
     const bool listed = a.tilemap && a.tilelist && a.tilecount && a.lower_only;
     if (a.tilemap) {
         if (listed) SF_HIP(hipMemsetAsync(a.tilecount, 0, sizeof(int) * (size_t)B, s));
@@ -365,7 +358,9 @@ int sf_launch_fill(const sf_fill_args& a, int B, hipStream_t s) {
 // covariance otherwise) -- independently of how many diagonals the storage happens to hold.
 // The element formulas are those of sf_matern_elem / sf_local_elem with the per-walker divisions
 // hoisted into reciprocals and cos(pi x) evaluated as cospi(x) (differences ~1e-16 relative, far inside
-// the 1e-10 covariance tolerance; the dense fill keeps the reference's exact operation order).
+// the 1e-10 covariance tolerance; the dense fill keeps the reference's exact operation order).  k_band_fill and
+// k_band_gtab each keep their OWN spelling (r * (1 / r0) here, r / r0 in the table): they differ from the dense formulas
+// and from each other in the last bit, on purpose -- not to be merged with sf_matern_elem / sf_local_elem or each other.
 // On a log-uniform wavelength grid (lambda_i = lambda_0 e^(i delta): every synthetic order, rectified
 // spectra) the metric of the global kernel depends on the offset only, (l_i - l_j)/(l_i + l_j) =
 // tanh((i-j) delta/2), so K_global is one value per diagonal: tabulated here per walker from a pair in
@@ -491,10 +486,7 @@ int sf_launch_band_fill(const sf_fill_args& a, int B, double* band, int ws, int 
         sf_set_error("band fill: half-width %d does not fit the %d stored diagonals", halfwidth, ws);
         return SF_EINVAL;
     }
-    if (a.n_local > SF_MAX_LOCAL) {
-        sf_set_error("at most %d local kernels are supported", SF_MAX_LOCAL);
-        return SF_EINVAL;
-    }
+    SF_CHECK(sf_check_n_local(a));
     if (!a.monotonic) {
         sf_set_error("the banded solver needs a strictly increasing wavelength grid");
         return SF_EINVAL;
@@ -712,10 +704,7 @@ int sf_launch_fill_dense(const sf_fill_args& a, int B, unsigned char* smap, unsi
     const bool all_structured = (a.has_global || a.n_local > 0) && !a.monotonic;  // (unsorted wavelengths: no culling)
     if (a.lower_only || a.tilemap || nt > 256 || !smap || !list || !count || all_structured || a.mpad > 16 || (a.mpad & 3))
         return sf_launch_fill(a, B, s);
-    if (a.n_local > SF_MAX_LOCAL) {
-        sf_set_error("at most %d local kernels are supported", SF_MAX_LOCAL);
-        return SF_EINVAL;
-    }
+    SF_CHECK(sf_check_n_local(a));
     sf_fill_args a2 = a;
     a2.gtab = nullptr;  // (the dense matrices keep the per-entry formula of the global kernel)
     const int structured = a.has_global || a.n_local > 0;
@@ -745,10 +734,7 @@ int sf_launch_fill_dense(const sf_fill_args& a, int B, unsigned char* smap, unsi
     // (Y fragments of a whole segment live in registers; cfg 2, rank-m part alone: 4 tiles 2.97 ms, 8 tiles 3.12 ms)
     const int span = 4;
     const long long nblk = (long long)nt * ((nt + span - 1) / span) * B;
-    if (nblk > 0x7fffffffLL) {
-        sf_set_error("fill grid too large");
-        return SF_EINVAL;
-    }
+    SF_CHECK(sf_check_fill_grid(nblk));
     switch (KK) {
         case 1: hipLaunchKernelGGL(k_fill_dense_plain<1>, dim3((unsigned)nblk), dim3(256), 0, s, a2, nt, pm); break;
         case 2: hipLaunchKernelGGL(k_fill_dense_plain<2>, dim3((unsigned)nblk), dim3(256), 0, s, a2, nt, pm); break;

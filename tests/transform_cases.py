@@ -23,7 +23,7 @@ from starfish_amd import synth
 EPS = np.finfo(np.float64).eps
 C_ROT = 4.0  # rot_mult_bound's constant: the measured worst case of scipy's j1 / numpy's cos, sin is 1.02 (u in [1e-5, 10])
 FLOOR = 1e-10  # relative floor of every flux / X comparison (the repository's transform parity tolerance)
-LDS_FFT_MAX = 8192  # complex points that sf_transform.hip keeps in LDS
+LDS_FFT_MAX = 8192  # complex points that sf_transform_fft.h (kLdsFftMax) keeps in LDS
 NF_MIN_VSINI, NF_MAX_VSINI = 16, 65536  # FFT lengths the broadened model accepts
 DV = 2.0  # km/s, pixel spacing of every synthetic order here
 VZ_FAR = 1500.0  # km/s: shifts a synthetic order by 750 pixels
