@@ -145,6 +145,23 @@ int sf_logdet_sqmah_batch(const double* d_L, int n, int lda, int64_t stride, int
                           const double* d_R, int ldr, void* d_work, size_t work_bytes,
                           double* d_logdet, double* d_sqmah, void* stream);
 
+/* scipy.linalg.cho_solve call site Starfish/models/spectrum_model.py:404 (LAPACK dpotrs), and the factor on its own:
+ * applies the L left by sf_potrf_batch (same n, lda, stride; only the lower triangle is read) to nrhs right-hand sides
+ * per matrix.  op: */
+#define SF_APPLY_L 0     /* L Z                                        */
+#define SF_APPLY_LINV 1  /* L^-1 B  (forward substitution)             */
+#define SF_APPLY_LINVT 2 /* L^-T B  (back substitution)                */
+#define SF_APPLY_CINV 3  /* L^-T L^-1 B = (L L^T)^-1 B  (cho_solve)    */
+/* Right-hand side r of matrix b: d_rhs + b*rhs_stride + r*ldr, its n rows contiguous (the layout of
+ * sf_band_logdet_gram_batch's d_rhs); rhs_stride == 0: one block of right-hand sides shared by every matrix.  Results in
+ * the same layout at d_out (ldo, out_stride).  d_out may be d_rhs when rhs_stride != 0, ldo == ldr and out_stride ==
+ * rhs_stride; any other overlap is the caller's error.  No workspace.  SF_EINVAL before anything is enqueued: n not a
+ * positive multiple of 64, lda < n, ldr < n, ldo < n, nrhs < 1, batch < 1, unknown op, null pointers, d_out == d_rhs with
+ * rhs_stride == 0 or differing strides.  Componentwise backward stable (Higham, Accuracy and Stability of Numerical
+ * Algorithms, Thms 8.5 and 10.4 with gamma_n). */
+int sf_potrs_batch(const double* d_L, int n, int lda, int64_t stride, int batch, int op, const double* d_rhs, int nrhs,
+                   int ldr, int64_t rhs_stride, double* d_out, int ldo, int64_t out_stride, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Per-order context: static data resident in HBM for the whole chain
  * ---------------------------------------------------------------------------------------- */
@@ -258,6 +275,19 @@ int sf_loglike_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const doubl
                      double* d_lnl, double* d_logdet, double* d_sqmah, double* d_resid,
                      double* d_log_scale, int* d_info, void* d_work, size_t work_bytes,
                      void* stream);
+
+/* The Cholesky factor of the walkers' covariance matrices applied to right-hand sides: the same transform chain, fill
+ * (lower triangle, 1e-10 jitter) and dense factorisation as sf_loglike_batch, then sf_potrs_batch's `op` (SF_APPLY_*):
+ * C^-1 rhs (cho_solve, spectrum_model.py:404), whitened vectors L^-1 rhs, noise draws L z.  The structure-exploiting
+ * solver is not involved.  d_rhs: right-hand side r of walker b at d_rhs + b*rhs_stride + r*ldr, n = data pixels
+ * contiguous rows, ldr >= n; rhs_stride == 0: one block shared by all walkers; d_rhs == NULL: each walker's own residual
+ * flux - data.flux (nrhs must be 1).  d_out[B*nrhs*n] (must not overlap d_rhs); d_flux[B*n] (model flux) and d_info[B]
+ * may be NULL.  Walkers with d_info[b] != 0 (the codes of sf_loglike_batch) get NaN in d_out.
+ * d_work: sf_apply_workspace_bytes(ctx, model, B, nrhs) (0 for bad arguments). */
+size_t sf_apply_workspace_bytes(const sf_ctx* ctx, const sf_model_desc* model, int B, int nrhs);
+int sf_apply_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, int op, const double* d_rhs,
+                   int nrhs, int ldr, int64_t rhs_stride, double* d_out, double* d_flux, int* d_info, void* d_work,
+                   size_t work_bytes, void* stream);
 
 /* ---- multi-order batches (reference: the multi-order container
  * Starfish/spectrum.py:96-115, orders independent docs/intro.rst:71-73, EchelleModel stub

@@ -18,6 +18,7 @@ INFO_MESSAGES = {
         "no result of that call is valid -- is the GPU shared with another process?)",
     -6: "the log-likelihood evaluated to NaN (non-finite input or intermediate)",
 }
+APPLY_OPS = {"L": 0, "Linv": 1, "LinvT": 2, "Cinv": 3}  # SF_APPLY_* of include/starfish_amd.h
 INFO_BANDWIDTH = -4
 INFO_INTERNAL = -5
 C_KMS = 2.99792458e5
@@ -582,6 +583,50 @@ class DeviceOrder:
             for key in out:
                 out[key][rest] = dense[key]
         return out
+
+    def apply_workspace_bytes(self, md, B, nrhs):
+        return self.lib.sf_apply_workspace_bytes(self.ctx, C.byref(md), int(B), int(nrhs))
+
+    def apply(self, md, params, op, rhs=None, want_flux=False, max_chunk=None):
+        """The Cholesky factor of every walker's covariance matrix applied to right-hand sides (sf_apply_batch): ``op`` is
+        "L" (L z), "Linv" (L^-1 b), "LinvT" (L^-T b) or "Cinv" (C^-1 b = cho_solve), or its SF_APPLY_* number.
+        params: (B, stride) rows as for :meth:`loglike`.  rhs: None (each walker's own residual), (nrhs, n) shared by all
+        walkers or (B, nrhs, n).  Returns dict of numpy arrays: out (B, nrhs, n), NaN for walkers with info != 0, info
+        (the codes of :meth:`loglike`) and, asked for, flux (B, n).  Always the dense factor."""
+        torch = _torch()
+        code = APPLY_OPS[op] if isinstance(op, str) else int(op)
+        with torch.cuda.device(self.dev):
+            P = params if torch.is_tensor(params) else to_dev(params, self.dev)
+            B = int(P.shape[0])
+            R, nrhs, per_walker = None, 1, False
+            if rhs is not None:
+                R = rhs if torch.is_tensor(rhs) else to_dev(rhs, self.dev)
+                if R.dim() not in (2, 3) or int(R.shape[-1]) != self.n or (R.dim() == 3 and int(R.shape[0]) != B):
+                    raise ValueError(f"rhs of shape {tuple(R.shape)}: expected (nrhs, {self.n}) or ({B}, nrhs, {self.n})")
+                R = R.contiguous()
+                nrhs, per_walker = int(R.shape[-2]), R.dim() == 3
+            if nrhs < 1:
+                raise ValueError("rhs holds no right-hand side")
+
+            def run(again):
+                held = self._ws.numel() if self._ws is not None else 0
+                fit = units_that_fit(self.dev, 0, max(self.apply_workspace_bytes(md, 1, nrhs), 1), held)
+                chunk = min(B, max_chunk or B, fit)
+                out = empty((B, nrhs, self.n), self.dev)
+                info = empty((B,), self.dev, torch.int32)
+                flux = empty((B, self.n), self.dev) if want_flux else None
+                ws = self._reserve(self.apply_workspace_bytes(md, chunk, nrhs))
+                for lo in range(0, B, chunk):
+                    hi = min(lo + chunk, B)
+                    self._call("apply_batch", md, hi - lo, P[lo:hi], code, R[lo:hi] if per_walker else R, nrhs, self.n,
+                               nrhs * self.n if per_walker else 0, out[lo:hi], flux[lo:hi] if want_flux else None,
+                               info[lo:hi], ws=ws)
+                res = dict(out=out.cpu().numpy(), info=info.cpu().numpy())
+                if want_flux:
+                    res["flux"] = flux.cpu().numpy()
+                return res, res["info"]
+
+            return retry_internal(self.lib, "sf_apply_batch", run)
 
     def loglike_device(self, md, P_dev, out_lnl, info=None):
         """Enqueue-only variant for bench.py: device tensors in/out, no synchronisation."""

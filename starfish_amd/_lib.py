@@ -112,6 +112,16 @@ SIGNATURES = {
         C.c_int,
         [_VP, C.c_int, C.c_int, C.c_int64, C.c_int, _VP, C.c_int, _VP, C.c_size_t, _VP, _VP, _VP],
     ),
+    "sf_potrs_batch": (
+        C.c_int,
+        [_VP, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _VP, C.c_int, C.c_int, C.c_int64, _VP, C.c_int, C.c_int64, _VP],
+    ),
+    "sf_apply_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int]),
+    "sf_apply_batch": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int64, _VP, _VP, _VP, _VP, C.c_size_t,
+         _VP],
+    ),
     "sf_ctx_create": (_VP, [C.POINTER(OrderDesc), C.c_int, c_int_p]),
     "sf_ctx_destroy": (None, [_VP]),
     "sf_ctx_npad": (C.c_int, [_VP]),

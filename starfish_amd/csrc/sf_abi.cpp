@@ -379,3 +379,62 @@ extern "C" int sf_loglike_batch(sf_ctx* c, const sf_model_desc* mdl, int B, cons
     if (rc) return rc;
     return export_logdet_sqmah(d_logdet, d_sqmah, w, B, s);
 }
+
+// ----------------------------------------------------------------------------------- the factor applied to right-hand sides
+static int apply_args_ok(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs) {
+    if (model_ok(c, mdl)) return SF_EINVAL;
+    // (the staging and export launches take one grid row per right-hand side and one grid plane per walker)
+    if (B <= 0 || B > 65535 || nrhs < 1 || nrhs > 65535) {
+        sf_set_error("sf_apply_batch: B=%d and nrhs=%d must lie in 1 .. 65535", B, nrhs);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_apply_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs) {
+    if (apply_args_ok(c, mdl, B, nrhs)) return 0;
+    return carve_apply(c, B, nrhs, nullptr, 0, carve(c, mdl, B, nullptr, 0, true).bytes).bytes;
+}
+extern "C" int sf_apply_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int op, const double* d_rhs,
+                              int nrhs, int ldr, int64_t rhs_stride, double* d_out, double* d_flux, int* d_info, void* d_work,
+                              size_t work_bytes, void* stream) {
+    int rc = apply_args_ok(c, mdl, B, nrhs);
+    if (rc) return rc;
+    if (!d_params || !d_out || op < SF_APPLY_L || op > SF_APPLY_CINV || (d_rhs ? ldr < c->n || rhs_stride < 0 : nrhs != 1)) {
+        sf_set_error("sf_apply_batch: d_params and d_out are required, op is one of SF_APPLY_*, ldr >= n (%d) and rhs_stride >= 0 "
+                     "with d_rhs, nrhs == 1 without", c->n);
+        return SF_EINVAL;
+    }
+    Work w;
+    rc = open_call(c, mdl, B, d_work, work_bytes, true, &w);
+    if (rc) return rc;
+    const ApplyWork aw = carve_apply(c, B, nrhs, d_work, work_bytes, w.bytes);
+    rc = work_fits(work_bytes, aw.bytes);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const Layout L = layout_of(c);
+    {
+        ProfScope ps(s, PS_TRANSFORM);
+        rc = run_transforms(c, mdl, B, d_params, w, d_flux, nullptr, nullptr, nullptr, true, s);
+        if (rc) return rc;
+    }
+    // (before the factorisation: the residual rides through it and comes out as L^-1 R)
+    rc = sf_launch_apply_stage(d_rhs, ldr, rhs_stride, w.resid, c->n, L.npad, nrhs, B, aw.stage, s);
+    if (rc) return rc;
+    const int fp = sf_potrf_front_pad(c->npad, B);  // (once per call: see sf_loglike_batch)
+    {
+        ProfScope ps(s, PS_FILL);
+        rc = sf_launch_fill(loglike_fill_args(c, mdl, d_params, w, L, fp), B, s);
+        if (rc) return rc;
+    }
+    // the likelihood's factorisation and status, as sf_loglike_batch reports it
+    rc = loglike_factor_finish(w, L, fp, B, w.ltbuf, aw.lnl, aw.info, s, &c->exec);
+    if (rc) return rc;
+    const int64_t sstride = (int64_t)nrhs * L.npad;
+    rc = sf_launch_chol_apply(w.C, L.npad, L.lda, (int64_t)L.npad * L.lda, B, op, aw.stage, nrhs, L.npad, sstride, aw.stage,
+                              L.npad, sstride, s);
+    if (rc) return rc;
+    rc = sf_launch_apply_export(aw.stage, aw.info, c->n, L.npad, nrhs, B, d_out, s);
+    if (rc) return rc;
+    if (d_info) SF_HIP(hipMemcpyAsync(d_info, aw.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return SF_OK;
+}

@@ -144,6 +144,15 @@ int sf_launch_logdet_z(const double* L, int n, int lda, int64_t stride, int batc
                        double* logdet, double* sqmah, hipStream_t s);
 int sf_launch_logdet_sqmah(const double* L, int n, int lda, int64_t stride, int batch,
                            const double* R, int ldr, double* zscratch, double* logdet, double* sqmah, hipStream_t s);
+// the factor applied to nrhs right-hand sides per matrix (op: SF_APPLY_*; layouts: sf_potrs_batch); arguments checked by the caller
+int sf_launch_chol_apply(const double* L, int n, int lda, int64_t stride, int batch, int op, const double* rhs, int nrhs,
+                         int ldr, int64_t rhs_stride, double* out, int ldo, int64_t out_stride, hipStream_t s);
+// sf_apply_batch: right-hand sides (or, rhs NULL, the residuals [batch][npad]) into the staging area [batch][nrhs][npad],
+// zero on the padding; its n data rows out again, NaN where info[b] != 0
+int sf_launch_apply_stage(const double* rhs, int ldr, int64_t rhs_stride, const double* resid, int n, int npad, int nrhs,
+                          int batch, double* stage, hipStream_t s);
+int sf_launch_apply_export(const double* stage, const int* info, int n, int npad, int nrhs, int batch, double* out,
+                           hipStream_t s);
 
 int sf_launch_clock_probe(long long* out, long long wall_ticks, hipStream_t s);
 

@@ -188,6 +188,38 @@ extern "C" int sf_logdet_sqmah_batch(const double* d_L, int n, int lda, int64_t 
     return sf_launch_logdet_sqmah(d_L, n, lda, stride, batch, d_R, ldr, z, d_logdet, d_sqmah,
                                   (hipStream_t)stream);
 }
+// every argument check of the factor's application, before any HIP call
+static int potrs_args_ok(const double* d_L, int n, int lda, int batch, int op, const double* d_rhs, int nrhs, int ldr,
+                         int64_t rhs_stride, const double* d_out, int ldo, int64_t out_stride) {
+    if (!d_L || !d_rhs || !d_out) {
+        sf_set_error("sf_potrs_batch: d_L, d_rhs and d_out are required");
+        return SF_EINVAL;
+    }
+    if (n <= 0 || n % SF_LEAF != 0 || lda < n || batch < 1) {
+        sf_set_error("sf_potrs_batch: n=%d must be a positive multiple of %d, lda=%d >= n, batch=%d >= 1", n, SF_LEAF, lda, batch);
+        return SF_EINVAL;
+    }
+    if (nrhs < 1 || ldr < n || ldo < n || rhs_stride < 0 || out_stride < 0) {
+        sf_set_error("sf_potrs_batch: nrhs=%d must be at least 1, ldr=%d and ldo=%d at least n=%d, strides not negative", nrhs,
+                     ldr, ldo, n);
+        return SF_EINVAL;
+    }
+    if (op < SF_APPLY_L || op > SF_APPLY_CINV) {
+        sf_set_error("sf_potrs_batch: unknown op %d (SF_APPLY_L 0, SF_APPLY_LINV 1, SF_APPLY_LINVT 2, SF_APPLY_CINV 3)", op);
+        return SF_EINVAL;
+    }
+    if (d_out == d_rhs && (rhs_stride == 0 || ldo != ldr || out_stride != rhs_stride)) {
+        sf_set_error("sf_potrs_batch: in place (d_out == d_rhs) needs rhs_stride != 0, ldo == ldr and out_stride == rhs_stride");
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" int sf_potrs_batch(const double* d_L, int n, int lda, int64_t stride, int batch, int op, const double* d_rhs,
+                              int nrhs, int ldr, int64_t rhs_stride, double* d_out, int ldo, int64_t out_stride, void* stream) {
+    SF_CHECK(potrs_args_ok(d_L, n, lda, batch, op, d_rhs, nrhs, ldr, rhs_stride, d_out, ldo, out_stride));
+    return sf_launch_chol_apply(d_L, n, lda, stride, batch, op, d_rhs, nrhs, ldr, rhs_stride, d_out, ldo, out_stride,
+                                (hipStream_t)stream);
+}
 
 extern "C" int sf_emulator_v11_build(const double* d_grid, int M, int P, int m, const double* d_hyper, const double* d_iphiphi,
                                      double* d_A, int npad, int lda, void* stream) {

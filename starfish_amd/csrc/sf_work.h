@@ -152,6 +152,25 @@ static BandWork carve_band(const sf_ctx* c, int B, int halfwidth, void* p, size_
     return w;
 }
 
+// ------------------------------------------------------------------- the factor applied to right-hand sides
+// (sf_apply_batch; behind the Work of the same call: base_bytes = its size)  The staging area holds the right-hand sides
+// padded to npad rows; the factor is applied to it in place.  lnl / info: what the likelihood's last step leaves.
+struct ApplyWork {
+    double *stage, *lnl;
+    int* info;
+    size_t bytes;
+};
+static ApplyWork carve_apply(const sf_ctx* c, int B, int nrhs, void* p, size_t cap, size_t base_bytes) {
+    Carve k(p, cap);
+    k.off = base_bytes;
+    ApplyWork w;
+    w.stage = k.take<double>((size_t)B * nrhs * c->npad);
+    w.lnl = k.take<double>((size_t)B);
+    w.info = k.take<int>((size_t)B);
+    w.bytes = sf_align_up(k.off, 256);
+    return w;
+}
+
 // ------------------------------------------------------------------- context-free workspaces
 // sf_potrf_batch / sf_logdet_sqmah_batch: z scratch of the stand-alone solve + the transposed leaf factor read by the panel solves
 struct PotrfWork {

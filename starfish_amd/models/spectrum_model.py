@@ -465,6 +465,71 @@ class SpectrumModel:
         self.last_info = info
         return (lnl, info) if return_info else lnl
 
+    # ------------------------------------------------------------------ the Cholesky factor of the covariance, applied
+    # Diagnostics, not likelihood evaluations: none of them touches residuals, _lnprob, _log_scale or the covariance caches.
+    def _rhs_block(self, rhs, what="rhs"):
+        """``rhs`` as a (k, n) block, and whether it came as one vector."""
+        r = np.asarray(rhs, dtype=np.float64)
+        if r.ndim not in (1, 2) or r.shape[-1] != len(self.data.wave):
+            raise ValueError(f"{what} of shape {r.shape}: expected ({len(self.data.wave)},) or (k, {len(self.data.wave)})")
+        return np.atleast_2d(r), r.ndim == 1
+
+    def _apply_factor(self, op, rhs, want_flux=False):
+        """``op`` of :meth:`apply_factor_batch` for the current parameters; raises as :meth:`log_likelihood` does."""
+        single = True
+        if rhs is not None:
+            rhs, single = self._rhs_block(rhs)
+        dev, md, rows = self._pack(update_caches=False)
+        out = dev.apply(md, rows, op, rhs=rhs, want_flux=want_flux)
+        self._raise_for_info(out["info"][0])
+        res = out["out"][0]
+        return (res[0] if single else res), (out["flux"][0] if want_flux else None)
+
+    def cho_solve(self, rhs=None):
+        """``C^-1 rhs`` for the covariance of the current parameters, jitter included (the reference's
+        ``cho_solve(factor, R)``, spectrum_model.py:404), solved on the device with the factor the likelihood uses.
+        ``rhs``: (n,) or (k, n); None = the current residual ``flux - data.flux``."""
+        return self._apply_factor("Cinv", rhs)[0]
+
+    def whiten(self, rhs=None):
+        """``L^-1 rhs`` (C = L L^T): iid N(0, 1) if ``rhs`` is noise drawn from C.  None = the current residual."""
+        return self._apply_factor("Linv", rhs)[0]
+
+    def draw(self, size=None, rng=None, z=None):
+        """Noise realisations ``flux + L z`` of the current model.  Pass standard-normal ``z`` of shape (n,) or (k, n), or
+        ``size`` (None: one draw of shape (n,); k: (k, n)) and ``rng`` (a ``numpy.random.Generator`` or a seed)."""
+        n = len(self.data.wave)
+        if z is None:
+            gen = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+            z = gen.standard_normal(n if size is None else (int(size), n))
+        elif size is not None:
+            raise ValueError("pass either z or size, not both")
+        lz, flux = self._apply_factor("L", z, want_flux=True)
+        return flux + lz
+
+    def apply_factor_batch(self, P, op, rhs=None, return_info=False):
+        """The factor of B walkers' covariance matrices (rows of ``P`` in :attr:`labels` order) applied in one batched
+        device pass: ``op`` "L" (L rhs), "Linv" (L^-1 rhs), "LinvT" (L^-T rhs) or "Cinv" (C^-1 rhs).  ``rhs``: None (each
+        walker's own residual), (n,) / (k, n) shared by all walkers, or (B, k, n).  Returns (B, k, n) -- (B, n) for None
+        or (n,) --; walkers that fail (outside the emulator grid, covariance not positive definite, ...) get NaN rows,
+        ``info`` the codes of :meth:`log_likelihood_batch`.  The model's own state is not modified."""
+        if op not in D.APPLY_OPS:
+            raise ValueError(f"op must be one of {sorted(D.APPLY_OPS)}")
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        single = True
+        if rhs is not None:
+            r = np.asarray(rhs, dtype=np.float64)
+            if r.ndim == 3:
+                if r.shape[0] != P.shape[0] or r.shape[-1] != len(self.data.wave):
+                    raise ValueError(f"rhs of shape {r.shape}: expected ({P.shape[0]}, k, {len(self.data.wave)})")
+                rhs, single = r, False
+            else:
+                rhs, single = self._rhs_block(r)
+        dev, md, rows = self._pack(P, update_caches=False)
+        out = dev.apply(md, rows, op, rhs=rhs)
+        res = out["out"][:, 0] if single else out["out"]
+        return (res, out["info"]) if return_info else res
+
     def train(self, priors=None, batch_simplex=True, **kwargs):
         """MAP estimate by Nelder-Mead over :meth:`log_likelihood` (spectrum_model.py:635-696).  ``kwargs`` go to
         ``scipy.optimize.minimize`` as in the reference.
