@@ -289,6 +289,28 @@ int sf_apply_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double*
                    int nrhs, int ldr, int64_t rhs_stride, double* d_out, double* d_flux, int* d_info, void* d_work,
                    size_t work_bytes, void* stream);
 
+/* The residual split by covariance component: alpha = C^-1 rhs by the sequence of sf_apply_batch with SF_APPLY_CINV (same
+ * transform chain, fill, factorisation: the same bits), then the conditional mean of every term of
+ *     C = Y^T Y (emulator) + diag(sigma^2 + 1e-10) (noise, the likelihood's jitter) + K_global + sum_j K_local,j
+ * given rhs, mu_k = K_k alpha, without materialising a matrix.  Component order: 0 emulator, 1 noise, 2 global (zeros for
+ * a model without has_global), 3 + j local kernel j: ncomp = 3 + n_local, d_comp[B][ncomp][nrhs][n].  The components add
+ * up to C alpha = rhs to rounding.  The structured entries are evaluated by the element formulas of the fill on the same
+ * operands; every sum has a fixed order (a repeated call gives the same bits); rows beyond n are never written.
+ * d_rhs, nrhs, ldr, rhs_stride: as sf_apply_batch (NULL: each walker's own residual, nrhs must be 1; rhs_stride == 0:
+ * one block shared by all walkers).  d_alpha[B*nrhs*n], d_flux[B*n] and d_info[B] may be NULL.  Walkers with
+ * d_info[b] != 0 (the codes of sf_loglike_batch) get NaN in every row of d_comp and d_alpha.  SF_EINVAL before anything is
+ * enqueued: B or nrhs outside 1 .. 65535, null d_params or d_comp, rhs_stride < 0, nrhs != 1 without d_rhs, a bad context
+ * or model, ldr < n.  d_work: sf_decompose_workspace_bytes(ctx, model, B, nrhs) (0 for bad arguments): the workspace of
+ * sf_apply_batch plus m doubles per right-hand side. */
+size_t sf_decompose_workspace_bytes(const sf_ctx* ctx, const sf_model_desc* model, int B, int nrhs);
+int sf_decompose_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, const double* d_rhs, int nrhs,
+                       int ldr, int64_t rhs_stride, double* d_comp, double* d_alpha, double* d_flux, int* d_info,
+                       void* d_work, size_t work_bytes, void* stream);
+/* Timing aid (tools/bench_decompose.py): the last step of sf_decompose_batch alone, K_k alpha -> d_comp, on the workspace
+ * that a call of sf_decompose_batch with the same ctx, model, B, nrhs and d_params left behind. */
+int sf_debug_decompose_matvec(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, int nrhs,
+                              double* d_comp, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- multi-order batches (reference: the multi-order container
  * Starfish/spectrum.py:96-115, orders independent docs/intro.rst:71-73, EchelleModel stub
  * Starfish/models/echelle_model.py:1-2) -------------------------------------------------------------

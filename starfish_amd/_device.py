@@ -587,6 +587,49 @@ class DeviceOrder:
     def apply_workspace_bytes(self, md, B, nrhs):
         return self.lib.sf_apply_workspace_bytes(self.ctx, C.byref(md), int(B), int(nrhs))
 
+    def decompose_workspace_bytes(self, md, B, nrhs):
+        return self.lib.sf_decompose_workspace_bytes(self.ctx, C.byref(md), int(B), int(nrhs))
+
+    def _rhs_on_device(self, rhs, B):
+        """``rhs`` of :meth:`apply` / :meth:`decompose` as (contiguous device tensor or None, nrhs, per_walker)."""
+        torch = _torch()
+        if rhs is None:
+            return None, 1, False
+        R = rhs if torch.is_tensor(rhs) else to_dev(rhs, self.dev)
+        if R.dim() not in (2, 3) or int(R.shape[-1]) != self.n or (R.dim() == 3 and int(R.shape[0]) != B):
+            raise ValueError(f"rhs of shape {tuple(R.shape)}: expected (nrhs, {self.n}) or ({B}, nrhs, {self.n})")
+        nrhs = int(R.shape[-2])
+        if nrhs < 1:
+            raise ValueError("rhs holds no right-hand side")
+        return R.contiguous(), nrhs, R.dim() == 3
+
+    def _run_applied(self, name, md, P, R, nrhs, per_walker, outputs, want_flux, max_chunk, workspace_bytes, lead=()):
+        """The chunk loop and retry of the calls that apply the factor: ``sf_<name>(ctx, &md, B, P, *lead, rhs, nrhs, ldr,
+        rhs_stride, *outputs, flux, info, ws, ...)``.  ``outputs``: key -> trailing shape of a (B, ...) double result."""
+        torch = _torch()
+        B = int(P.shape[0])
+
+        def run(again):
+            held = self._ws.numel() if self._ws is not None else 0
+            fit = units_that_fit(self.dev, 0, max(workspace_bytes(md, 1, nrhs), 1), held)
+            chunk = min(B, max_chunk or B, fit)
+            outs = {key: empty((B,) + tuple(shape), self.dev) for key, shape in outputs.items()}
+            info = empty((B,), self.dev, torch.int32)
+            flux = empty((B, self.n), self.dev) if want_flux else None
+            ws = self._reserve(workspace_bytes(md, chunk, nrhs))
+            for lo in range(0, B, chunk):
+                hi = min(lo + chunk, B)
+                self._call(name, md, hi - lo, P[lo:hi], *lead, R[lo:hi] if per_walker else R, nrhs, self.n,
+                           nrhs * self.n if per_walker else 0, *[o[lo:hi] for o in outs.values()],
+                           flux[lo:hi] if want_flux else None, info[lo:hi], ws=ws)
+            res = {key: o.cpu().numpy() for key, o in outs.items()}
+            res["info"] = info.cpu().numpy()
+            if want_flux:
+                res["flux"] = flux.cpu().numpy()
+            return res, res["info"]
+
+        return retry_internal(self.lib, "sf_" + name, run)
+
     def apply(self, md, params, op, rhs=None, want_flux=False, max_chunk=None):
         """The Cholesky factor of every walker's covariance matrix applied to right-hand sides (sf_apply_batch): ``op`` is
         "L" (L z), "Linv" (L^-1 b), "LinvT" (L^-T b) or "Cinv" (C^-1 b = cho_solve), or its SF_APPLY_* number.
@@ -597,36 +640,23 @@ class DeviceOrder:
         code = APPLY_OPS[op] if isinstance(op, str) else int(op)
         with torch.cuda.device(self.dev):
             P = params if torch.is_tensor(params) else to_dev(params, self.dev)
-            B = int(P.shape[0])
-            R, nrhs, per_walker = None, 1, False
-            if rhs is not None:
-                R = rhs if torch.is_tensor(rhs) else to_dev(rhs, self.dev)
-                if R.dim() not in (2, 3) or int(R.shape[-1]) != self.n or (R.dim() == 3 and int(R.shape[0]) != B):
-                    raise ValueError(f"rhs of shape {tuple(R.shape)}: expected (nrhs, {self.n}) or ({B}, nrhs, {self.n})")
-                R = R.contiguous()
-                nrhs, per_walker = int(R.shape[-2]), R.dim() == 3
-            if nrhs < 1:
-                raise ValueError("rhs holds no right-hand side")
+            R, nrhs, per_walker = self._rhs_on_device(rhs, int(P.shape[0]))
+            return self._run_applied("apply_batch", md, P, R, nrhs, per_walker, {"out": (nrhs, self.n)}, want_flux,
+                                     max_chunk, self.apply_workspace_bytes, lead=(code,))
 
-            def run(again):
-                held = self._ws.numel() if self._ws is not None else 0
-                fit = units_that_fit(self.dev, 0, max(self.apply_workspace_bytes(md, 1, nrhs), 1), held)
-                chunk = min(B, max_chunk or B, fit)
-                out = empty((B, nrhs, self.n), self.dev)
-                info = empty((B,), self.dev, torch.int32)
-                flux = empty((B, self.n), self.dev) if want_flux else None
-                ws = self._reserve(self.apply_workspace_bytes(md, chunk, nrhs))
-                for lo in range(0, B, chunk):
-                    hi = min(lo + chunk, B)
-                    self._call("apply_batch", md, hi - lo, P[lo:hi], code, R[lo:hi] if per_walker else R, nrhs, self.n,
-                               nrhs * self.n if per_walker else 0, out[lo:hi], flux[lo:hi] if want_flux else None,
-                               info[lo:hi], ws=ws)
-                res = dict(out=out.cpu().numpy(), info=info.cpu().numpy())
-                if want_flux:
-                    res["flux"] = flux.cpu().numpy()
-                return res, res["info"]
-
-            return retry_internal(self.lib, "sf_apply_batch", run)
+    def decompose(self, md, params, rhs=None, want_flux=False, max_chunk=None):
+        """The right-hand sides split by covariance component (sf_decompose_batch): ``alpha = C^-1 rhs`` as :meth:`apply`
+        with "Cinv" gives it, and ``comp[b, k] = K_k alpha`` for k = 0 emulator, 1 noise (jitter included), 2 global (zeros
+        without one), 3 + j local kernel j.  params, rhs: as for :meth:`apply`.  Returns dict of numpy arrays: comp
+        (B, 3 + n_local, nrhs, n), alpha (B, nrhs, n), info and, asked for, flux (B, n); NaN rows where info != 0.
+        Chunked and retried like :meth:`apply`."""
+        torch = _torch()
+        with torch.cuda.device(self.dev):
+            P = params if torch.is_tensor(params) else to_dev(params, self.dev)
+            R, nrhs, per_walker = self._rhs_on_device(rhs, int(P.shape[0]))
+            outputs = {"comp": (3 + int(md.n_local), nrhs, self.n), "alpha": (nrhs, self.n)}
+            return self._run_applied("decompose_batch", md, P, R, nrhs, per_walker, outputs, want_flux, max_chunk,
+                                     self.decompose_workspace_bytes)
 
     def loglike_device(self, md, P_dev, out_lnl, info=None):
         """Enqueue-only variant for bench.py: device tensors in/out, no synchronisation."""

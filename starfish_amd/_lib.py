@@ -122,6 +122,15 @@ SIGNATURES = {
         [_VP, C.POINTER(ModelDesc), C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int64, _VP, _VP, _VP, _VP, C.c_size_t,
          _VP],
     ),
+    "sf_decompose_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int]),
+    "sf_decompose_batch": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP],
+    ),
+    "sf_debug_decompose_matvec": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, C.c_int, _VP, _VP, C.c_size_t, _VP],
+    ),
     "sf_ctx_create": (_VP, [C.POINTER(OrderDesc), C.c_int, c_int_p]),
     "sf_ctx_destroy": (None, [_VP]),
     "sf_ctx_npad": (C.c_int, [_VP]),

@@ -394,24 +394,11 @@ extern "C" size_t sf_apply_workspace_bytes(const sf_ctx* c, const sf_model_desc*
     if (apply_args_ok(c, mdl, B, nrhs)) return 0;
     return carve_apply(c, B, nrhs, nullptr, 0, carve(c, mdl, B, nullptr, 0, true).bytes).bytes;
 }
-extern "C" int sf_apply_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int op, const double* d_rhs,
-                              int nrhs, int ldr, int64_t rhs_stride, double* d_out, double* d_flux, int* d_info, void* d_work,
-                              size_t work_bytes, void* stream) {
-    int rc = apply_args_ok(c, mdl, B, nrhs);
-    if (rc) return rc;
-    if (!d_params || !d_out || op < SF_APPLY_L || op > SF_APPLY_CINV || (d_rhs ? ldr < c->n || rhs_stride < 0 : nrhs != 1)) {
-        sf_set_error("sf_apply_batch: d_params and d_out are required, op is one of SF_APPLY_*, ldr >= n (%d) and rhs_stride >= 0 "
-                     "with d_rhs, nrhs == 1 without", c->n);
-        return SF_EINVAL;
-    }
-    Work w;
-    rc = open_call(c, mdl, B, d_work, work_bytes, true, &w);
-    if (rc) return rc;
-    const ApplyWork aw = carve_apply(c, B, nrhs, d_work, work_bytes, w.bytes);
-    rc = work_fits(work_bytes, aw.bytes);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
+// transform chain, staging, fill, the likelihood's factorisation and `op` on the staging area, in place
+static int apply_staged(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int op, const double* d_rhs, int nrhs,
+                        int ldr, int64_t rhs_stride, double* d_flux, const Work& w, const ApplyWork& aw, hipStream_t s) {
     const Layout L = layout_of(c);
+    int rc;
     {
         ProfScope ps(s, PS_TRANSFORM);
         rc = run_transforms(c, mdl, B, d_params, w, d_flux, nullptr, nullptr, nullptr, true, s);
@@ -430,11 +417,100 @@ extern "C" int sf_apply_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const 
     rc = loglike_factor_finish(w, L, fp, B, w.ltbuf, aw.lnl, aw.info, s, &c->exec);
     if (rc) return rc;
     const int64_t sstride = (int64_t)nrhs * L.npad;
-    rc = sf_launch_chol_apply(w.C, L.npad, L.lda, (int64_t)L.npad * L.lda, B, op, aw.stage, nrhs, L.npad, sstride, aw.stage,
-                              L.npad, sstride, s);
+    return sf_launch_chol_apply(w.C, L.npad, L.lda, (int64_t)L.npad * L.lda, B, op, aw.stage, nrhs, L.npad, sstride, aw.stage,
+                                L.npad, sstride, s);
+}
+extern "C" int sf_apply_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int op, const double* d_rhs,
+                              int nrhs, int ldr, int64_t rhs_stride, double* d_out, double* d_flux, int* d_info, void* d_work,
+                              size_t work_bytes, void* stream) {
+    int rc = apply_args_ok(c, mdl, B, nrhs);
     if (rc) return rc;
-    rc = sf_launch_apply_export(aw.stage, aw.info, c->n, L.npad, nrhs, B, d_out, s);
+    if (!d_params || !d_out || op < SF_APPLY_L || op > SF_APPLY_CINV || (d_rhs ? ldr < c->n || rhs_stride < 0 : nrhs != 1)) {
+        sf_set_error("sf_apply_batch: d_params and d_out are required, op is one of SF_APPLY_*, ldr >= n (%d) and rhs_stride >= 0 "
+                     "with d_rhs, nrhs == 1 without", c->n);
+        return SF_EINVAL;
+    }
+    Work w;
+    rc = open_call(c, mdl, B, d_work, work_bytes, true, &w);
+    if (rc) return rc;
+    const ApplyWork aw = carve_apply(c, B, nrhs, d_work, work_bytes, w.bytes);
+    rc = work_fits(work_bytes, aw.bytes);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = apply_staged(c, mdl, B, d_params, op, d_rhs, nrhs, ldr, rhs_stride, d_flux, w, aw, s);
+    if (rc) return rc;
+    rc = sf_launch_apply_export(aw.stage, aw.info, c->n, c->npad, nrhs, B, d_out, s);
     if (rc) return rc;
     if (d_info) SF_HIP(hipMemcpyAsync(d_info, aw.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
     return SF_OK;
+}
+
+// ----------------------------------------------------------------------------------- the residual split by covariance component
+// (sf_decompose_batch, sf_debug_decompose_matvec)  The checks that need no context come first: B, nrhs, the required
+// pointers and the right-hand-side conventions; then the context and the model; then ldr against the order's n.
+static int decompose_counts_ok(int B, int nrhs) {
+    if (B <= 0 || B > 65535 || nrhs < 1 || nrhs > 65535) {
+        sf_set_error("sf_decompose_batch: B=%d and nrhs=%d must lie in 1 .. 65535", B, nrhs);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+static int decompose_args_ok(const sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const double* d_rhs,
+                             int nrhs, int ldr, int64_t rhs_stride, const double* d_comp) {
+    SF_CHECK(decompose_counts_ok(B, nrhs));
+    if (!d_params || !d_comp || (d_rhs ? rhs_stride < 0 : nrhs != 1)) {
+        sf_set_error("sf_decompose_batch: d_params and d_comp are required, rhs_stride >= 0 with d_rhs, nrhs == 1 without");
+        return SF_EINVAL;
+    }
+    SF_CHECK(model_ok(c, mdl));
+    if (d_rhs && ldr < c->n) {
+        sf_set_error("sf_decompose_batch: ldr=%d < n (%d)", ldr, c->n);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_decompose_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs) {
+    if (decompose_counts_ok(B, nrhs) || model_ok(c, mdl)) return 0;
+    return carve_decompose(c, B, nrhs, nullptr, 0, carve(c, mdl, B, nullptr, 0, true).bytes).bytes;
+}
+// the workspace of a call whose arguments passed
+static int open_decompose(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs, void* d_work, size_t work_bytes, Work* w,
+                          DecomposeWork* dw) {
+    SF_CHECK(open_call(c, mdl, B, d_work, work_bytes, true, w));
+    *dw = carve_decompose(c, B, nrhs, d_work, work_bytes, w->bytes);
+    return work_fits(work_bytes, dw->bytes);
+}
+// K_k v for the v in the staging area, with the Y the transform chain left (the factorisation only reads it)
+static int decompose_matvec(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int nrhs, const Work& w,
+                            const DecomposeWork& dw, double* d_comp, hipStream_t s) {
+    return sf_launch_cov_matvec(fill_args(c, mdl, d_params, w), c->m, dw.a.stage, c->npad, nrhs, B, dw.yv, dw.a.info, d_comp, s);
+}
+extern "C" int sf_decompose_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const double* d_rhs,
+                                  int nrhs, int ldr, int64_t rhs_stride, double* d_comp, double* d_alpha, double* d_flux,
+                                  int* d_info, void* d_work, size_t work_bytes, void* stream) {
+    SF_CHECK(decompose_args_ok(c, mdl, B, d_params, d_rhs, nrhs, ldr, rhs_stride, d_comp));
+    Work w;
+    DecomposeWork dw;
+    SF_CHECK(open_decompose(c, mdl, B, nrhs, d_work, work_bytes, &w, &dw));
+    hipStream_t s = (hipStream_t)stream;
+    SF_CHECK(apply_staged(c, mdl, B, d_params, SF_APPLY_CINV, d_rhs, nrhs, ldr, rhs_stride, d_flux, w, dw.a, s));
+    SF_CHECK(decompose_matvec(c, mdl, B, d_params, nrhs, w, dw, d_comp, s));
+    if (d_alpha) SF_CHECK(sf_launch_apply_export(dw.a.stage, dw.a.info, c->n, c->npad, nrhs, B, d_alpha, s));
+    if (d_info) SF_HIP(hipMemcpyAsync(d_info, dw.a.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return SF_OK;
+}
+// The last step of sf_decompose_batch alone, on the workspace a call with the same ctx, model, B, nrhs and d_params left
+// (tools/bench_decompose.py times it)
+extern "C" int sf_debug_decompose_matvec(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int nrhs,
+                                         double* d_comp, void* d_work, size_t work_bytes, void* stream) {
+    SF_CHECK(decompose_counts_ok(B, nrhs));
+    if (!d_params || !d_comp) {
+        sf_set_error("sf_debug_decompose_matvec: d_params and d_comp are required");
+        return SF_EINVAL;
+    }
+    SF_CHECK(model_ok(c, mdl));
+    Work w;
+    DecomposeWork dw;
+    SF_CHECK(open_decompose(c, mdl, B, nrhs, d_work, work_bytes, &w, &dw));
+    return decompose_matvec(c, mdl, B, d_params, nrhs, w, dw, d_comp, (hipStream_t)stream);
 }

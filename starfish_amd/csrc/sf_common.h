@@ -194,6 +194,11 @@ size_t sf_fill_dense_map_tiles(int n);
 int sf_launch_fill_dense(const sf_fill_args& a, int B, unsigned char* smap, unsigned short* list, int* count, hipStream_t s,
                          sf_exec* ex);
 int sf_launch_stream_write(double* dst, size_t count, double v, hipStream_t s);
+// sf_cov_matvec.h: out[b][k][r][0:n) = K_k v[b][r], k = emulator, noise (+ jitter), global, local 0 ... (3 + n_local
+// components; zeros for a global kernel the model lacks; NaN where info[b] != 0).  f: fill_args (C unused); m rows of Y
+// exist; v: [batch][nrhs][ldv]; yv: [batch][nrhs][m] scratch for Y v
+int sf_launch_cov_matvec(const sf_fill_args& f, int m, const double* v, int ldv, int nrhs, int batch, double* yv,
+                         const int* info, double* out, hipStream_t s);
 // band storage of the structured part of C (sf_band.hip consumes it); a.npad = rows written (>= a.n)
 int sf_launch_band_fill(const sf_fill_args& a, int B, double* band, int ws, int halfwidth, int ldb, int64_t sband,
                         int* info, double* gtab, hipStream_t s, int tile_wt = -1);  // ws stored diagonals > halfwidth; gtab: B x (ws+1) or NULL

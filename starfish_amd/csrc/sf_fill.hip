@@ -778,3 +778,6 @@ int sf_launch_stream_write(double* dst, size_t count, double v, hipStream_t s) {
     SF_LAUNCH_CHECK();
     return SF_OK;
 }
+
+// ---- the components of C applied to vectors (sf_decompose_batch): k_cov_yv, k_cov_matvec
+#include "sf_cov_matvec.h"

@@ -171,6 +171,23 @@ static ApplyWork carve_apply(const sf_ctx* c, int B, int nrhs, void* p, size_t c
     return w;
 }
 
+// sf_decompose_batch: the layout of sf_apply_batch (the staging area ends up holding alpha = C^-1 rhs), then t = Y alpha,
+// m doubles per right-hand side
+struct DecomposeWork {
+    ApplyWork a;
+    double* yv;
+    size_t bytes;
+};
+static DecomposeWork carve_decompose(const sf_ctx* c, int B, int nrhs, void* p, size_t cap, size_t base_bytes) {
+    DecomposeWork w;
+    w.a = carve_apply(c, B, nrhs, p, cap, base_bytes);
+    Carve k(p, cap);
+    k.off = w.a.bytes;
+    w.yv = k.take<double>((size_t)B * nrhs * c->m);
+    w.bytes = sf_align_up(k.off, 256);
+    return w;
+}
+
 // ------------------------------------------------------------------- context-free workspaces
 // sf_potrf_batch / sf_logdet_sqmah_batch: z scratch of the stand-alone solve + the transposed leaf factor read by the panel solves
 struct PotrfWork {

@@ -516,18 +516,67 @@ class SpectrumModel:
         if op not in D.APPLY_OPS:
             raise ValueError(f"op must be one of {sorted(D.APPLY_OPS)}")
         P = np.atleast_2d(np.asarray(P, dtype=np.float64))
-        single = True
-        if rhs is not None:
-            r = np.asarray(rhs, dtype=np.float64)
-            if r.ndim == 3:
-                if r.shape[0] != P.shape[0] or r.shape[-1] != len(self.data.wave):
-                    raise ValueError(f"rhs of shape {r.shape}: expected ({P.shape[0]}, k, {len(self.data.wave)})")
-                rhs, single = r, False
-            else:
-                rhs, single = self._rhs_block(r)
+        rhs, single = self._batch_rhs(P, rhs)
         dev, md, rows = self._pack(P, update_caches=False)
         out = dev.apply(md, rows, op, rhs=rhs)
         res = out["out"][:, 0] if single else out["out"]
+        return (res, out["info"]) if return_info else res
+
+    def _batch_rhs(self, P, rhs):
+        """``rhs`` of the batched diagnostics: None, (n,) / (k, n) shared by the walkers, or (B, k, n); and whether every
+        walker has one vector."""
+        if rhs is None:
+            return None, True
+        r = np.asarray(rhs, dtype=np.float64)
+        if r.ndim == 3:
+            if r.shape[0] != P.shape[0] or r.shape[-1] != len(self.data.wave):
+                raise ValueError(f"rhs of shape {r.shape}: expected ({P.shape[0]}, k, {len(self.data.wave)})")
+            return r, False
+        return self._rhs_block(r)
+
+    # ------------------------------------------------------------------ the residual split by covariance component
+    # C = Y^T Y (emulator) + diag(sigma^2 + 1e-10) (noise) + K_global + sum_j K_local,j: the conditional mean of each term
+    # given the residual is K_k alpha with alpha = C^-1 r; the means add up to r.  Diagnostics like the ones above.
+    @staticmethod
+    def _component_dict(comp, alpha, has_global, n_local, single):
+        """The component axis of :meth:`DeviceOrder.decompose` as a dict: ``comp`` (..., 3 + n_local, k, n) and ``alpha``
+        (..., k, n) -> emulator, noise, global (with ``has_global``), local (..., n_local, k, n) (with local kernels) and
+        alpha; the k axis is dropped for ``single``."""
+        comp, alpha = np.asarray(comp), np.asarray(alpha)
+        if comp.ndim < 3 or comp.shape[-3] != 3 + n_local or alpha.shape != comp.shape[:-3] + comp.shape[-2:]:
+            raise ValueError(f"components of shape {comp.shape} and alpha of shape {alpha.shape} do not belong to a model "
+                             f"with {n_local} local kernel(s)")
+        pick = (lambda a: a[..., 0, :]) if single else (lambda a: a)
+        out = {"emulator": pick(comp[..., 0, :, :]), "noise": pick(comp[..., 1, :, :])}
+        if has_global:
+            out["global"] = pick(comp[..., 2, :, :])
+        if n_local:
+            out["local"] = pick(comp[..., 3:, :, :])
+        out["alpha"] = pick(alpha)
+        return out
+
+    def residual_components(self, rhs=None):
+        """The conditional mean of every covariance component given ``rhs`` (None: the current residual ``flux -
+        data.flux``; (n,) or (k, n)): dict with "emulator", "noise", "global" (models with ``global_cov``), "local"
+        (models with ``local_cov``: one row per kernel, in the order of ``self["local_cov"]``) and "alpha" = ``C^-1 rhs``
+        (:meth:`cho_solve`).  The components add up to ``rhs``.  Raises as :meth:`log_likelihood` does."""
+        single = True
+        if rhs is not None:
+            rhs, single = self._rhs_block(rhs)
+        dev, md, rows = self._pack(update_caches=False)
+        out = dev.decompose(md, rows, rhs=rhs)
+        self._raise_for_info(out["info"][0])
+        return self._component_dict(out["comp"][0], out["alpha"][0], bool(md.has_global), int(md.n_local), single)
+
+    def residual_components_batch(self, P, rhs=None, return_info=False):
+        """:meth:`residual_components` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device pass:
+        the same keys with a leading B axis.  ``rhs`` as for :meth:`apply_factor_batch`; walkers that fail get NaN rows,
+        ``info`` their codes.  The model's own state is not modified."""
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        rhs, single = self._batch_rhs(P, rhs)
+        dev, md, rows = self._pack(P, update_caches=False)
+        out = dev.decompose(md, rows, rhs=rhs)
+        res = self._component_dict(out["comp"], out["alpha"], bool(md.has_global), int(md.n_local), single)
         return (res, out["info"]) if return_info else res
 
     def train(self, priors=None, batch_simplex=True, **kwargs):
