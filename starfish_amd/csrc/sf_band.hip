@@ -625,6 +625,18 @@ int sf_band_max_halfwidth(int nrhs) {
 
 static int launch_forms_kernel(const sf_band_args& a, int nrb, int nblocks, hipStream_t s);
 
+// What both launchers pass alike; everything else zero (no results, no additive terms, no sweep halves, no dumps).
+static sf_band_args band_args(const double* band, int n, int halfwidth, int ldb, int64_t sband, const double* rhs0,
+                              int64_t srhs0, const double* rhs, int nrhs, int ldr, int64_t srhs, int* info) {
+    sf_band_args a = {};
+    a.band = band, a.sband = sband, a.ldb = ldb, a.halfwidth = halfwidth;
+    a.rhs = rhs, a.srhs = srhs, a.ldr = ldr, a.nrhs = nrhs;
+    a.rhs0 = rhs0, a.srhs0 = srhs0;
+    a.n = n, a.nbr = band_nbr(halfwidth);
+    a.info = info;
+    return a;
+}
+
 int sf_launch_band_forms(const double* band, int n, int halfwidth, int ldb, int64_t sband, int batch,
                          const double* rhs0, int64_t srhs0, const double* rhs, int nrhs, int ldr,
                          int64_t srhs, double* logdet, double* gram, int* info, hipStream_t s,
@@ -634,35 +646,15 @@ int sf_launch_band_forms(const double* band, int n, int halfwidth, int ldb, int6
         sf_set_error("band_forms: bad arguments (n=%d halfwidth=%d ldb=%d nrhs=%d)", n, halfwidth, ldb, nrhs);
         return SF_EINVAL;
     }
-    const int nbr = band_nbr(halfwidth);
-    const size_t shm = band_lds_bytes(nbr, nrb);
-    if (shm > 160 * 1024) {
+    if (band_lds_bytes(band_nbr(halfwidth), nrb) > 160 * 1024) {
         sf_set_error("band_forms: half-width %d with %d right-hand sides exceeds the LDS window (max %d)",
                      halfwidth, nrhs, sf_band_max_halfwidth(nrhs));
         return SF_EINVAL;
     }
-    sf_band_args a;
-    a.band = band;
-    a.sband = sband;
-    a.ldb = ldb;
-    a.halfwidth = halfwidth;
-    a.rhs = rhs;
-    a.srhs = srhs;
-    a.ldr = ldr;
-    a.nrhs = nrhs;
-    a.rhs0 = rhs0;
-    a.srhs0 = srhs0;
-    a.n = n;
-    a.nbr = nbr;
-    a.logdet = logdet;
-    a.gram = gram;
-    a.info = info;
-    a.logdet_add = logdet_add;
-    a.gram_add = gram_add;
-    a.info_off = info_off;
+    sf_band_args a = band_args(band, n, halfwidth, ldb, sband, rhs0, srhs0, rhs, nrhs, ldr, srhs, info);
+    a.logdet = logdet, a.gram = gram;
+    a.logdet_add = logdet_add, a.gram_add = gram_add, a.info_off = info_off;
     a.nhalf = 1;
-    a.kend0 = a.kend1 = 0;
-    a.dumpM = a.dumpR = a.dumpG = a.dumpL = nullptr;
     return launch_forms_kernel(a, nrb, batch, s);
 }
 
@@ -728,25 +720,7 @@ int sf_launch_band_forms_twisted(const double* band, int n, int halfwidth, int l
         sf_set_error("band_forms_twisted: bad arguments");
         return SF_EINVAL;
     }
-    sf_band_args a;
-    a.band = band;
-    a.sband = sband;
-    a.ldb = ldb;
-    a.halfwidth = halfwidth;
-    a.rhs = rhs;
-    a.srhs = srhs;
-    a.ldr = ldr;
-    a.nrhs = nrhs;
-    a.rhs0 = rhs0;
-    a.srhs0 = srhs0;
-    a.n = n;
-    a.nbr = nbr;
-    a.logdet = nullptr;
-    a.gram = nullptr;
-    a.info = info;
-    a.logdet_add = nullptr;
-    a.gram_add = nullptr;
-    a.info_off = 0;
+    sf_band_args a = band_args(band, n, halfwidth, ldb, sband, rhs0, srhs0, rhs, nrhs, ldr, srhs, info);  // no results: the halves dump
     a.nhalf = 2;
     a.kend0 = (nblk - nb1) / 2;
     a.kend1 = nblk - nb1 - a.kend0;

@@ -11,7 +11,7 @@
 
 #define SF_LEAF 64        // Cholesky leaf block (potrf / trsm granularity); matrices padded to it
 #define SF_NB 256         // outer left-looking panel width
-#define SF_MAX_LOCAL 32   // local kernels per model (sf_fill.hip: 32-bit masks of the fill tiles, per-block tables)
+#define SF_MAX_LOCAL 32   // local kernels per model (sf_fill_elem.h: 32-bit masks of the fill tiles, per-block tables)
 #define SF_NF_MIN_VSINI 16     // FFT lengths of a model with vsini: k_spline_apply takes whole 16-point blocks,
 #define SF_NF_MAX_VSINI 65536  // sf_launch_broaden transforms at most 65536 points
 
@@ -156,7 +156,7 @@ int sf_launch_apply_export(const double* stage, const int* info, int n, int npad
 
 int sf_launch_clock_probe(long long* out, long long wall_ticks, hipStream_t s);
 
-// sf_fill.hip
+// sf_fill.hip (layers: sf_fill_elem.h, sf_fill_band.h, sf_fill_tile.h, sf_fill_dense.h, sf_fill_free.h, sf_cov_matvec.h)
 struct sf_fill_args {
     const double* wave;    // [n]
     const double* sigma;   // [n]
@@ -187,22 +187,22 @@ struct sf_fill_args {
 static inline __host__ __device__ int sf_fill_extent(const sf_fill_args& a) {
     return a.nout > 0 ? a.nout : (a.lower_only ? a.npad : a.n);
 }
-int sf_launch_fill(const sf_fill_args& a, int B, hipStream_t s);
-// dense (both triangles) matrices of the caller: plain / structured tiles split (smap, list: sf_fill_dense_map_tiles(n) per matrix)
+int sf_launch_fill(const sf_fill_args& a, int B, hipStream_t s);  // sf_fill_tile.h
+// sf_fill_dense.h: dense (both triangles) matrices of the caller: plain / structured tiles split (smap, list: sf_fill_dense_map_tiles(n) per matrix)
 size_t sf_fill_dense_map_tiles(int n);
 // (ex: prepared executor whose auxiliary stream takes the structured tiles beside the plain ones, or NULL)
 int sf_launch_fill_dense(const sf_fill_args& a, int B, unsigned char* smap, unsigned short* list, int* count, hipStream_t s,
                          sf_exec* ex);
-int sf_launch_stream_write(double* dst, size_t count, double v, hipStream_t s);
+int sf_launch_stream_write(double* dst, size_t count, double v, hipStream_t s);  // sf_fill_free.h
 // sf_cov_matvec.h: out[b][k][r][0:n) = K_k v[b][r], k = emulator, noise (+ jitter), global, local 0 ... (3 + n_local
 // components; zeros for a global kernel the model lacks; NaN where info[b] != 0).  f: fill_args (C unused); m rows of Y
 // exist; v: [batch][nrhs][ldv]; yv: [batch][nrhs][m] scratch for Y v
 int sf_launch_cov_matvec(const sf_fill_args& f, int m, const double* v, int ldv, int nrhs, int batch, double* yv,
                          const int* info, double* out, hipStream_t s);
-// band storage of the structured part of C (sf_band.hip consumes it); a.npad = rows written (>= a.n)
+// sf_fill_band.h: band storage of the structured part of C (sf_band.hip consumes it); a.npad = rows written (>= a.n)
 int sf_launch_band_fill(const sf_fill_args& a, int B, double* band, int ws, int halfwidth, int ldb, int64_t sband,
                         int* info, double* gtab, hipStream_t s, int tile_wt = -1);  // ws stored diagonals > halfwidth; gtab: B x (ws+1) or NULL
-int sf_launch_global_cov(const double* wave, int n, double amp, double ls, double* out, hipStream_t s);
+int sf_launch_global_cov(const double* wave, int n, double amp, double ls, double* out, hipStream_t s);  // sf_fill_free.h
 int sf_launch_local_cov(const double* wave, int n, double amp, double mu, double sigma, int accumulate,
                         double* out, hipStream_t s);
 

@@ -2,8 +2,8 @@
 //     out[b][k][r][:] = K_k v[b][r][:],   C = sum_k K_k = Y^T Y + diag(sigma^2 + 1e-10) + K_global + sum_j K_local,j
 // k = 0 emulator, 1 noise (the likelihood's jitter included: the components sum to C v for the matrix that is factorised),
 // 2 global, 3 + j local kernel j.  With v = C^-1 r these are the conditional means of the components given the residual
-// (sf_decompose_batch).  Included at the end of sf_fill.hip: the structured entries come from the fill's own
-// sf_matern_elem / sf_local_elem / sf_local_metric with the fill's operands under the same -ffp-contract=off, so an entry
+// (sf_decompose_batch).  A layer of sf_fill.hip: the structured entries come from the fill's own sf_matern_elem /
+// sf_local_elem / sf_local_metric with the fill's operands (sf_load_global / sf_load_local) under the same -ffp-contract=off, so an entry
 // multiplied here has the bits of the entry the fill adds to C (the per-entry fill: on a log-uniform grid the likelihood's
 // fill reads K_global from its per-diagonal table, equal to the rounding of the grid).
 //
@@ -86,22 +86,17 @@ __global__ __launch_bounds__(256) void k_cov_matvec(const sf_matvec_args a) {
         }
     }
     const double* __restrict__ P = f.params + (int64_t)b * f.pstride;
-    double g_amp = 0, g_ls = 1, g_r0 = 0;
-    if (f.has_global) {
-        g_amp = exp(P[f.off_global]);     // the operands of sf_tile_finish
-        g_ls = exp(P[f.off_global + 1]);
-        g_r0 = 6 * g_ls;
-    }
+    sf_global_hyper gh = {0, 1, 0};
+    if (f.has_global) gh = sf_load_global(f, P);
     const double w_row = valid ? f.wave[i] : 1.0;
     const int ncb = (n + 63) / 64;
     int flags_of = -1;  // first column block of the support flags in LDS
     for (int c = f.has_global ? 0 : 1; c <= f.n_local; ++c) {  // 0: global, 1 + k: local kernel k
-        double mu = 1, amp = 0, sig = 1, d_row = 0;
+        sf_local_hyper l = {1, 0, 1};
+        double d_row = 0;
         if (c > 0) {
-            mu = P[f.off_local + 3 * (c - 1)];
-            amp = exp(P[f.off_local + 3 * (c - 1) + 1]);
-            sig = exp(P[f.off_local + 3 * (c - 1) + 2]);
-            d_row = sf_local_metric(w_row, mu);
+            l = sf_load_local(f, P, c - 1);
+            d_row = sf_local_metric(w_row, l.mu);
         }
         double acc[SF_MV_NR];
 #pragma unroll
@@ -114,7 +109,7 @@ __global__ __launch_bounds__(256) void k_cov_matvec(const sf_matvec_args a) {
                     const int clo = (sb0 + tid) * 64;
                     bool dg;
                     unsigned lm;
-                    sf_block_support(f, P, R0, rhi, clo, min(clo + 63, n - 1), g_r0, dg, lm);
+                    sf_block_support(f, P, R0, rhi, clo, min(clo + 63, n - 1), gh.r0, dg, lm);
                     s_glob[tid] = dg ? 1 : 0;
                     s_lmask[tid] = lm;
                 }
@@ -138,8 +133,8 @@ __global__ __launch_bounds__(256) void k_cov_matvec(const sf_matvec_args a) {
                     if (!((hit >> q) & 1u)) continue;
                     for (int jj = q * 64 + w; jj < q * 64 + 64 && c0 + jj < n; jj += 4) {
                         const double w_col = Ws[jj];
-                        const double e = c == 0 ? sf_matern_elem(w_row, w_col, g_amp, g_ls, g_r0)
-                                                : sf_local_elem(d_row, sf_local_metric(w_col, mu), amp, sig, 4 * sig);
+                        const double e = c == 0 ? sf_matern_elem(w_row, w_col, gh.amp, gh.ls, gh.r0)
+                                                : sf_local_elem(d_row, sf_local_metric(w_col, l.mu), l.amp, l.sig, 4 * l.sig);
 #pragma unroll
                         for (int r = 0; r < SF_MV_NR; ++r)
                             if (r < nr) acc[r] = acc[r] + e * Vs[r * SF_MV_CH + jj];
