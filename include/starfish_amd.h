@@ -162,6 +162,20 @@ int sf_logdet_sqmah_batch(const double* d_L, int n, int lda, int64_t stride, int
 int sf_potrs_batch(const double* d_L, int n, int lda, int64_t stride, int batch, int op, const double* d_rhs, int nrhs,
                    int ldr, int64_t rhs_stride, double* d_out, int ldo, int64_t out_stride, void* stream);
 
+/* The diagonal of the inverse from the factor (LAPACK dpotri, of which only the diagonal is formed): d_out[b*out_stride + j]
+ * = (C_b^-1)_jj = sum_{i >= j} (L_b^-1)_ij^2 for the L left by sf_potrf_batch (same n, lda, stride).  With alpha = C^-1 r
+ * (sf_potrs_batch, SF_APPLY_CINV) this is the leave-one-out predictive of a Gaussian process (Rasmussen & Williams, Gaussian
+ * Processes for Machine Learning, 5.4.2): mean r_j - alpha_j / d_j, variance 1 / d_j.  The lower triangle of d_L is read and
+ * left bit-identical; the strict upper triangle is scratch (nothing in it is read before it has been written) and is
+ * undefined afterwards.  Every sum has a fixed order: a repeated call gives the same bits.  d_work:
+ * sf_potri_diag_workspace_bytes(n, batch) (0 for bad arguments): the inverses of the 64 x 64 diagonal blocks.  SF_EINVAL
+ * before anything is enqueued: n not a positive multiple of 64, lda < n, batch < 1, out_stride < n, null pointers, workspace
+ * too small.  Componentwise |d^ - d| <= 2 gamma_2n diag(|X|^T |X||L||X|) + gamma_{n+1} d with X = L^-1 (Higham, Accuracy and
+ * Stability of Numerical Algorithms, ch. 14). */
+size_t sf_potri_diag_workspace_bytes(int n, int batch);
+int sf_potri_diag_batch(double* d_L, int n, int lda, int64_t stride, int batch, double* d_out, int64_t out_stride, void* d_work,
+                        size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Per-order context: static data resident in HBM for the whole chain
  * ---------------------------------------------------------------------------------------- */
@@ -310,6 +324,22 @@ int sf_decompose_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const dou
  * that a call of sf_decompose_batch with the same ctx, model, B, nrhs and d_params left behind. */
 int sf_debug_decompose_matvec(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, int nrhs,
                               double* d_comp, void* d_work, size_t work_bytes, void* stream);
+
+/* Per-pixel leave-one-out diagnostics: alpha = C^-1 rhs by the sequence of sf_apply_batch with SF_APPLY_CINV (same transform
+ * chain, fill, factorisation: the same bits), then sf_potri_diag_batch on the workspace matrices: d_cinv_diag[B][n] =
+ * diag(C_b^-1).  Pixel i predicted from all the others has mean rhs_i - alpha_i / d_i and variance 1 / d_i.
+ * d_cov_diag[B][n] (may be NULL): the diagonal of the matrix that is factorised, the 1e-10 jitter included, copied out
+ * between fill and factorisation (the marginal variances).  d_rhs, nrhs, ldr, rhs_stride: as sf_apply_batch (NULL: each
+ * walker's own residual, nrhs must be 1; rhs_stride == 0: one block shared by all walkers).  d_alpha[B*nrhs*n] and
+ * d_cinv_diag are required; d_flux[B*n] and d_info[B] may be NULL.  Walkers with d_info[b] != 0 (the codes of
+ * sf_loglike_batch) get NaN in every row of d_alpha, d_cinv_diag and d_cov_diag.  SF_EINVAL before anything is enqueued: B
+ * or nrhs outside 1 .. 65535, null d_params, d_alpha or d_cinv_diag, rhs_stride < 0, nrhs != 1 without d_rhs, a bad context
+ * or model, ldr < n.  d_work: sf_pointwise_workspace_bytes(ctx, model, B, nrhs) (0 for bad arguments): the workspace of
+ * sf_apply_batch, two rows of npad doubles per walker and the workspace of sf_potri_diag_batch. */
+size_t sf_pointwise_workspace_bytes(const sf_ctx* ctx, const sf_model_desc* model, int B, int nrhs);
+int sf_pointwise_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, const double* d_rhs, int nrhs,
+                       int ldr, int64_t rhs_stride, double* d_alpha, double* d_cinv_diag, double* d_cov_diag, double* d_flux,
+                       int* d_info, void* d_work, size_t work_bytes, void* stream);
 
 /* ---- multi-order batches (reference: the multi-order container
  * Starfish/spectrum.py:96-115, orders independent docs/intro.rst:71-73, EchelleModel stub

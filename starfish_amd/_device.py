@@ -590,6 +590,9 @@ class DeviceOrder:
     def decompose_workspace_bytes(self, md, B, nrhs):
         return self.lib.sf_decompose_workspace_bytes(self.ctx, C.byref(md), int(B), int(nrhs))
 
+    def pointwise_workspace_bytes(self, md, B, nrhs):
+        return self.lib.sf_pointwise_workspace_bytes(self.ctx, C.byref(md), int(B), int(nrhs))
+
     def _rhs_on_device(self, rhs, B):
         """``rhs`` of :meth:`apply` / :meth:`decompose` as (contiguous device tensor or None, nrhs, per_walker)."""
         torch = _torch()
@@ -657,6 +660,19 @@ class DeviceOrder:
             outputs = {"comp": (3 + int(md.n_local), nrhs, self.n), "alpha": (nrhs, self.n)}
             return self._run_applied("decompose_batch", md, P, R, nrhs, per_walker, outputs, want_flux, max_chunk,
                                      self.decompose_workspace_bytes)
+
+    def pointwise(self, md, params, rhs=None, want_flux=False, max_chunk=None):
+        """What the per-pixel leave-one-out diagnostics need (sf_pointwise_batch): ``alpha = C^-1 rhs`` as :meth:`apply`
+        with "Cinv" gives it, ``cinv_diag = diag(C^-1)`` and ``cov_diag = diag(C)``, jitter included, as it was factorised.
+        params, rhs: as for :meth:`apply`.  Returns dict of numpy arrays: alpha (B, nrhs, n), cinv_diag (B, n), cov_diag
+        (B, n), info and, asked for, flux (B, n); NaN rows where info != 0.  Chunked and retried like :meth:`apply`."""
+        torch = _torch()
+        with torch.cuda.device(self.dev):
+            P = params if torch.is_tensor(params) else to_dev(params, self.dev)
+            R, nrhs, per_walker = self._rhs_on_device(rhs, int(P.shape[0]))
+            outputs = {"alpha": (nrhs, self.n), "cinv_diag": (self.n,), "cov_diag": (self.n,)}
+            return self._run_applied("pointwise_batch", md, P, R, nrhs, per_walker, outputs, want_flux, max_chunk,
+                                     self.pointwise_workspace_bytes)
 
     def loglike_device(self, md, P_dev, out_lnl, info=None):
         """Enqueue-only variant for bench.py: device tensors in/out, no synchronisation."""

@@ -116,6 +116,11 @@ SIGNATURES = {
         C.c_int,
         [_VP, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _VP, C.c_int, C.c_int, C.c_int64, _VP, C.c_int, C.c_int64, _VP],
     ),
+    "sf_potri_diag_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sf_potri_diag_batch": (
+        C.c_int,
+        [_VP, C.c_int, C.c_int, C.c_int64, C.c_int, _VP, C.c_int64, _VP, C.c_size_t, _VP],
+    ),
     "sf_apply_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int]),
     "sf_apply_batch": (
         C.c_int,
@@ -126,6 +131,12 @@ SIGNATURES = {
     "sf_decompose_batch": (
         C.c_int,
         [_VP, C.POINTER(ModelDesc), C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP],
+    ),
+    "sf_pointwise_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int]),
+    "sf_pointwise_batch": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t,
+         _VP],
     ),
     "sf_debug_decompose_matvec": (
         C.c_int,

@@ -394,9 +394,11 @@ extern "C" size_t sf_apply_workspace_bytes(const sf_ctx* c, const sf_model_desc*
     if (apply_args_ok(c, mdl, B, nrhs)) return 0;
     return carve_apply(c, B, nrhs, nullptr, 0, carve(c, mdl, B, nullptr, 0, true).bytes).bytes;
 }
-// transform chain, staging, fill, the likelihood's factorisation and `op` on the staging area, in place
+// transform chain, staging, fill, the likelihood's factorisation and `op` on the staging area, in place.  cov_diag (may be
+// NULL): [B][npad], the diagonal of the filled matrices, copied out before the factorisation overwrites it
 static int apply_staged(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int op, const double* d_rhs, int nrhs,
-                        int ldr, int64_t rhs_stride, double* d_flux, const Work& w, const ApplyWork& aw, hipStream_t s) {
+                        int ldr, int64_t rhs_stride, double* d_flux, const Work& w, const ApplyWork& aw, hipStream_t s,
+                        double* cov_diag = nullptr) {
     const Layout L = layout_of(c);
     int rc;
     {
@@ -413,6 +415,7 @@ static int apply_staged(sf_ctx* c, const sf_model_desc* mdl, int B, const double
         rc = sf_launch_fill(loglike_fill_args(c, mdl, d_params, w, L, fp), B, s);
         if (rc) return rc;
     }
+    if (cov_diag) SF_CHECK(sf_launch_diag_copy(w.C, L.npad, L.lda, (int64_t)L.npad * L.lda, B, cov_diag, s));
     // the likelihood's factorisation and status, as sf_loglike_batch reports it
     rc = loglike_factor_finish(w, L, fp, B, w.ltbuf, aw.lnl, aw.info, s, &c->exec);
     if (rc) return rc;
@@ -513,4 +516,49 @@ extern "C" int sf_debug_decompose_matvec(sf_ctx* c, const sf_model_desc* mdl, in
     DecomposeWork dw;
     SF_CHECK(open_decompose(c, mdl, B, nrhs, d_work, work_bytes, &w, &dw));
     return decompose_matvec(c, mdl, B, d_params, nrhs, w, dw, d_comp, (hipStream_t)stream);
+}
+
+// ----------------------------------------------------------------------------------- per-pixel leave-one-out diagnostics
+// (sf_pointwise_batch)  The checks that need no context come first, as for sf_decompose_batch.
+static int pointwise_counts_ok(int B, int nrhs) {
+    if (B <= 0 || B > 65535 || nrhs < 1 || nrhs > 65535) {
+        sf_set_error("sf_pointwise_batch: B=%d and nrhs=%d must lie in 1 .. 65535", B, nrhs);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_pointwise_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs) {
+    if (pointwise_counts_ok(B, nrhs) || model_ok(c, mdl)) return 0;
+    return carve_pointwise(c, B, nrhs, nullptr, 0, carve(c, mdl, B, nullptr, 0, true).bytes).bytes;
+}
+extern "C" int sf_pointwise_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const double* d_rhs,
+                                  int nrhs, int ldr, int64_t rhs_stride, double* d_alpha, double* d_cinv_diag,
+                                  double* d_cov_diag, double* d_flux, int* d_info, void* d_work, size_t work_bytes,
+                                  void* stream) {
+    SF_CHECK(pointwise_counts_ok(B, nrhs));
+    if (!d_params || !d_alpha || !d_cinv_diag || (d_rhs ? rhs_stride < 0 : nrhs != 1)) {
+        sf_set_error("sf_pointwise_batch: d_params, d_alpha and d_cinv_diag are required, rhs_stride >= 0 with d_rhs, nrhs == 1 "
+                     "without");
+        return SF_EINVAL;
+    }
+    SF_CHECK(model_ok(c, mdl));
+    if (d_rhs && ldr < c->n) {
+        sf_set_error("sf_pointwise_batch: ldr=%d < n (%d)", ldr, c->n);
+        return SF_EINVAL;
+    }
+    Work w;
+    SF_CHECK(open_call(c, mdl, B, d_work, work_bytes, true, &w));
+    const PointwiseWork pw = carve_pointwise(c, B, nrhs, d_work, work_bytes, w.bytes);
+    SF_CHECK(work_fits(work_bytes, pw.bytes));
+    hipStream_t s = (hipStream_t)stream;
+    const Layout L = layout_of(c);
+    SF_CHECK(apply_staged(c, mdl, B, d_params, SF_APPLY_CINV, d_rhs, nrhs, ldr, rhs_stride, d_flux, w, pw.a, s,
+                          d_cov_diag ? pw.cov_diag : nullptr));
+    // (the factor applied first: the inverse's launch takes the strict upper triangle of the matrices as scratch)
+    SF_CHECK(sf_launch_chol_inverse_diag(w.C, L.npad, L.lda, (int64_t)L.npad * L.lda, B, pw.winv, pw.cinv_diag, L.npad, s));
+    SF_CHECK(sf_launch_apply_export(pw.a.stage, pw.a.info, c->n, c->npad, nrhs, B, d_alpha, s));
+    SF_CHECK(sf_launch_apply_export(pw.cinv_diag, pw.a.info, c->n, c->npad, 1, B, d_cinv_diag, s));
+    if (d_cov_diag) SF_CHECK(sf_launch_apply_export(pw.cov_diag, pw.a.info, c->n, c->npad, 1, B, d_cov_diag, s));
+    if (d_info) SF_HIP(hipMemcpyAsync(d_info, pw.a.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return SF_OK;
 }

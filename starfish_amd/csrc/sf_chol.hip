@@ -30,6 +30,7 @@
 //   sf_chol_sync.h       counters, waits, watch and rescue of the persistent kernel
 //   sf_chol_solve.h      k_logdet_z, k_trsv_logdet, the clock probe
 //   sf_chol_apply.h      the factor applied to right-hand sides (L Z, L^-1 B, L^-T B, C^-1 B): k_chol_apply; independent of the sequences
+//   sf_chol_inverse.h    diag(C^-1) from the factor, the column norms of L^-1: k_chol_block_inverse, k_chol_inverse_diag; independent of the sequences
 //   sf_chol_panel.h      the panel step: sf_panel_args, sf_panel_body, k_chol_panel
 //   sf_chol_wide.h       the wide step (a pair of panels): sf_panelw_args, k_chol_panel_w
 //   sf_chol_seq.h        the narrow and wide steps as launches, the narrow step of a chain and two slab groups,
@@ -52,6 +53,7 @@
 #include "sf_chol_sync.h"
 #include "sf_chol_solve.h"
 #include "sf_chol_apply.h"
+#include "sf_chol_inverse.h"
 #include "sf_chol_panel.h"
 #include "sf_chol_wide.h"
 #include "sf_chol_seq.h"

@@ -153,6 +153,13 @@ int sf_launch_apply_stage(const double* rhs, int ldr, int64_t rhs_stride, const 
                           int batch, double* stage, hipStream_t s);
 int sf_launch_apply_export(const double* stage, const int* info, int n, int npad, int nrhs, int batch, double* out,
                            hipStream_t s);
+// diag(C^-1) of the factored matrices (sf_potri_diag_batch): winv = sf_chol_inverse_work_doubles(n, batch) doubles of scratch,
+// the strict upper triangle of L outside the 64 x 64 diagonal blocks is scratch too; arguments checked by the caller
+size_t sf_chol_inverse_work_doubles(int n, int batch);
+int sf_launch_chol_inverse_diag(double* L, int n, int lda, int64_t stride, int batch, double* winv, double* out,
+                                int64_t out_stride, hipStream_t s);
+// diag[batch][n] = the diagonals of the matrices
+int sf_launch_diag_copy(const double* A, int n, int lda, int64_t stride, int batch, double* diag, hipStream_t s);
 
 int sf_launch_clock_probe(long long* out, long long wall_ticks, hipStream_t s);
 

@@ -221,6 +221,29 @@ extern "C" int sf_potrs_batch(const double* d_L, int n, int lda, int64_t stride,
                                 (hipStream_t)stream);
 }
 
+extern "C" size_t sf_potri_diag_workspace_bytes(int n, int batch) {
+    if (n <= 0 || n % SF_LEAF != 0 || batch <= 0) return 0;
+    return carve_potri(n, batch, nullptr, 0).bytes;
+}
+extern "C" int sf_potri_diag_batch(double* d_L, int n, int lda, int64_t stride, int batch, double* d_out, int64_t out_stride,
+                                   void* d_work, size_t work_bytes, void* stream) {
+    if (!d_L || !d_out || !d_work) {
+        sf_set_error("sf_potri_diag_batch: d_L, d_out and d_work are required");
+        return SF_EINVAL;
+    }
+    if (n <= 0 || n % SF_LEAF != 0 || lda < n || batch < 1 || out_stride < n) {
+        sf_set_error("sf_potri_diag_batch: n=%d must be a positive multiple of %d, lda=%d >= n, batch=%d >= 1, out_stride=%lld >= n",
+                     n, SF_LEAF, lda, batch, (long long)out_stride);
+        return SF_EINVAL;
+    }
+    const PotriWork w = carve_potri(n, batch, d_work, work_bytes);
+    if (work_bytes < w.bytes) {
+        sf_set_error("sf_potri_diag_batch: workspace too small: have %zu, need %zu", work_bytes, w.bytes);
+        return SF_EINVAL;
+    }
+    return sf_launch_chol_inverse_diag(d_L, n, lda, stride, batch, w.winv, d_out, out_stride, (hipStream_t)stream);
+}
+
 extern "C" int sf_emulator_v11_build(const double* d_grid, int M, int P, int m, const double* d_hyper, const double* d_iphiphi,
                                      double* d_A, int npad, int lda, void* stream) {
     return sf_launch_v11_build(d_grid, M, P, m, d_hyper, d_iphiphi, d_A, npad, lda, (hipStream_t)stream);

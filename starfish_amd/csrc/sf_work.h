@@ -188,7 +188,39 @@ static DecomposeWork carve_decompose(const sf_ctx* c, int B, int nrhs, void* p, 
     return w;
 }
 
+// sf_pointwise_batch: the layout of sf_apply_batch (the staging area ends up holding alpha = C^-1 rhs), then the diagonal
+// of the matrix that is factorised and the diagonal of its inverse, npad doubles per walker each, then the scratch of the
+// inverse's launch (carve_potri)
+struct PointwiseWork {
+    ApplyWork a;
+    double *cov_diag, *cinv_diag, *winv;
+    size_t bytes;
+};
+static PointwiseWork carve_pointwise(const sf_ctx* c, int B, int nrhs, void* p, size_t cap, size_t base_bytes) {
+    PointwiseWork w;
+    w.a = carve_apply(c, B, nrhs, p, cap, base_bytes);
+    Carve k(p, cap);
+    k.off = w.a.bytes;
+    w.cov_diag = k.take<double>((size_t)B * c->npad);
+    w.cinv_diag = k.take<double>((size_t)B * c->npad);
+    w.winv = k.take<double>(sf_chol_inverse_work_doubles(c->npad, B));
+    w.bytes = sf_align_up(k.off, 256);
+    return w;
+}
+
 // ------------------------------------------------------------------- context-free workspaces
+// sf_potri_diag_batch: the transposed inverses of the 64 x 64 diagonal blocks, [batch][n / 64][64][64]
+struct PotriWork {
+    double* winv;
+    size_t bytes;
+};
+static PotriWork carve_potri(int n, int batch, void* p, size_t cap) {
+    Carve k(p, cap);
+    PotriWork w;
+    w.winv = k.take<double>(sf_chol_inverse_work_doubles(n, batch));
+    w.bytes = sf_align_up(k.off, 256);
+    return w;
+}
 // sf_potrf_batch / sf_logdet_sqmah_batch: z scratch of the stand-alone solve + the transposed leaf factor read by the panel solves
 struct PotrfWork {
     double *z, *ltbuf;

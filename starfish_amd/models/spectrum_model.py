@@ -579,6 +579,62 @@ class SpectrumModel:
         res = self._component_dict(out["comp"], out["alpha"], bool(md.has_global), int(md.n_local), single)
         return (res, out["info"]) if return_info else res
 
+    # ------------------------------------------------------------------ per-pixel leave-one-out diagnostics
+    # Pixel i predicted from all the others under the fitted covariance (Rasmussen & Williams, Gaussian Processes for
+    # Machine Learning, 5.4.2): with alpha = C^-1 r and d = diag(C^-1), mean r_i - alpha_i / d_i and variance 1 / d_i.
+    @staticmethod
+    def _pointwise_dict(rhs, alpha, cinv_diag, cov_diag, single):
+        """The results of :meth:`DeviceOrder.pointwise` as the dict of :meth:`pointwise`: ``rhs`` and ``alpha`` (..., k, n),
+        ``cinv_diag`` and ``cov_diag`` (..., n); the k axis is dropped for ``single``."""
+        rhs, alpha = np.asarray(rhs, dtype=np.float64), np.asarray(alpha, dtype=np.float64)
+        cinv_diag, cov_diag = np.asarray(cinv_diag, dtype=np.float64), np.asarray(cov_diag, dtype=np.float64)
+        if alpha.ndim < 2 or cinv_diag.shape != alpha.shape[:-2] + alpha.shape[-1:] or cov_diag.shape != cinv_diag.shape:
+            raise ValueError(f"alpha of shape {alpha.shape}, cinv_diag of shape {cinv_diag.shape} and cov_diag of shape "
+                             f"{cov_diag.shape} do not belong together")
+        rhs = np.broadcast_to(rhs, alpha.shape)
+        d = cinv_diag[..., None, :]
+        z = alpha / np.sqrt(d)
+        pick = (lambda a: a[..., 0, :]) if single else (lambda a: a)
+        return {
+            "alpha": pick(alpha),
+            "marginal_std": np.sqrt(cov_diag),
+            "loo_mean": pick(rhs - alpha / d),
+            "loo_std": 1.0 / np.sqrt(cinv_diag),
+            "z": pick(z),
+            "log_density": pick(-0.5 * np.log(2.0 * np.pi / d) - 0.5 * z * z),
+        }
+
+    def pointwise(self, rhs=None):
+        """Every pixel of ``rhs`` (None: the current residual ``flux - data.flux``; (n,) or (k, n)) judged against the
+        prediction from all the OTHER pixels under the covariance of the current parameters: dict with "alpha" = ``C^-1
+        rhs`` (:meth:`cho_solve`), "marginal_std" = ``sqrt(diag(C))`` (jitter included; the band the reference's plot
+        shades), "loo_mean" = ``rhs - alpha / d`` and "loo_std" = ``1 / sqrt(d)`` with ``d = diag(C^-1)``, the
+        standardised residual "z" = ``alpha / sqrt(d)`` and the per-pixel "log_density" = ``-log(2 pi / d) / 2 - z^2 / 2``,
+        whose sum is the leave-one-out pseudo-likelihood.  "marginal_std" and "loo_std" are (n,) whatever ``rhs`` is.
+        Raises as :meth:`log_likelihood` does."""
+        single = True
+        if rhs is not None:
+            rhs, single = self._rhs_block(rhs)
+        dev, md, rows = self._pack(update_caches=False)
+        out = dev.pointwise(md, rows, rhs=rhs, want_flux=rhs is None)
+        self._raise_for_info(out["info"][0])
+        if rhs is None:
+            rhs = (out["flux"][0] - self.data.flux)[None, :]
+        return self._pointwise_dict(rhs, out["alpha"][0], out["cinv_diag"][0], out["cov_diag"][0], single)
+
+    def pointwise_batch(self, P, rhs=None, return_info=False):
+        """:meth:`pointwise` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device pass: the same
+        keys with a leading B axis.  ``rhs`` as for :meth:`apply_factor_batch`; walkers that fail get NaN rows, ``info``
+        their codes.  The model's own state is not modified."""
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        rhs, single = self._batch_rhs(P, rhs)
+        dev, md, rows = self._pack(P, update_caches=False)
+        out = dev.pointwise(md, rows, rhs=rhs, want_flux=rhs is None)
+        if rhs is None:
+            rhs = (out["flux"] - self.data.flux)[:, None, :]
+        res = self._pointwise_dict(rhs, out["alpha"], out["cinv_diag"], out["cov_diag"], single)
+        return (res, out["info"]) if return_info else res
+
     def train(self, priors=None, batch_simplex=True, **kwargs):
         """MAP estimate by Nelder-Mead over :meth:`log_likelihood` (spectrum_model.py:635-696).  ``kwargs`` go to
         ``scipy.optimize.minimize`` as in the reference.
