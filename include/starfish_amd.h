@@ -176,6 +176,19 @@ size_t sf_potri_diag_workspace_bytes(int n, int batch);
 int sf_potri_diag_batch(double* d_L, int n, int lda, int64_t stride, int batch, double* d_out, int64_t out_stride, void* d_work,
                         size_t work_bytes, void* stream);
 
+/* Selected 64 x 64 blocks of the inverse from the factor (the blocks of LAPACK dpotri's result that a caller names):
+ * d_out[((b*npairs + p)*64 + r)*64 + c] = (C_b^-1)[64 I_p + r][64 J_p + c] for the L left by sf_potrf_batch (same n, lda,
+ * stride).  d_pairs: device array of npairs x (I, J) int32 with 0 <= J <= I < n / 64; a pair may be listed more than once; a
+ * pair outside that range gives a block of NaN and reads nothing.  Runs the two launches of sf_potri_diag_batch (X = L^-1 into
+ * the strict upper triangle, which is scratch and undefined afterwards; the lower triangle is read and left bit-identical),
+ * then G_IJ = sum_{K >= I} X_KI^T X_KJ on the matrix cores.  Every sum has a fixed order: a repeated call gives the same bits.
+ * d_work: sf_potri_blocks_workspace_bytes(n, batch) (0 for bad arguments).  SF_EINVAL before anything is enqueued: n not a
+ * positive multiple of 64, lda < n, batch < 1, npairs < 1, null pointers, workspace too small.  Entrywise |G^ - G| <=
+ * gamma_2n (E + E^T) + gamma_{n+1} |X|^T |X| with E = |X|^T |X||L||X|. */
+size_t sf_potri_blocks_workspace_bytes(int n, int batch);
+int sf_potri_blocks_batch(double* d_L, int n, int lda, int64_t stride, int batch, const int* d_pairs, int npairs, double* d_out,
+                          void* d_work, size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Per-order context: static data resident in HBM for the whole chain
  * ---------------------------------------------------------------------------------------- */
@@ -340,6 +353,28 @@ size_t sf_pointwise_workspace_bytes(const sf_ctx* ctx, const sf_model_desc* mode
 int sf_pointwise_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, const double* d_rhs, int nrhs,
                        int ldr, int64_t rhs_stride, double* d_alpha, double* d_cinv_diag, double* d_cov_diag, double* d_flux,
                        int* d_info, void* d_work, size_t work_bytes, void* stream);
+
+/* The likelihood and its gradient in the covariance hyper-parameters: d lnL / d theta = 1/2 sum_ij (alpha_i alpha_j -
+ * (C^-1)_ij) (dC / d theta)_ij (Rasmussen & Williams, Gaussian Processes for Machine Learning, eq. 5.9) with alpha = C^-1 r by
+ * the sequence of sf_apply_batch with SF_APPLY_CINV on each walker's own residual (same transform chain, fill, factorisation
+ * and finish: d_lnl and d_info have sf_loglike_batch's bits), the blocks of C^-1 on the kernels' support as
+ * sf_potri_blocks_batch forms them, and the analytic entry derivatives.  d_grad[b*grad_stride + s], slots in parameter-row
+ * order: log_amp, log_ls of the global kernel if the model has one, then mu, log_amp, log_sigma of every local kernel.  In mu
+ * the likelihood has a kink wherever two pixels of a patch are equidistant from mu; the derivative is the almost-everywhere
+ * one.  The matrix is the one that is factorised (jitter included).  d_flux[B*n] and d_info[B] may be NULL.  Walkers with
+ * d_info[b] != 0 get NaN in every slot.  Every sum has a fixed order: a repeated call gives the same bits.  SF_EINVAL before
+ * anything is enqueued: B outside 1 .. 65535, null d_params, d_lnl or d_grad, a model without global and local kernels
+ * ("nothing to differentiate"), grad_stride below the number of slots, a bad context or model.  d_work:
+ * sf_loglike_grad_workspace_bytes(ctx, model, B) (0 for bad arguments): the workspace of sf_apply_batch with one right-hand
+ * side, a row of npad doubles per walker, the workspace of sf_potri_diag_batch and one double per (walker, 64-row block,
+ * slot). */
+size_t sf_loglike_grad_workspace_bytes(const sf_ctx* ctx, const sf_model_desc* model, int B);
+int sf_loglike_grad_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, double* d_lnl, double* d_grad,
+                          int grad_stride, double* d_flux, int* d_info, void* d_work, size_t work_bytes, void* stream);
+/* Timing aid (tools/bench_gradient.py): the contraction launches of sf_loglike_grad_batch alone, on the workspace that a
+ * call of sf_loglike_grad_batch with the same ctx, model, B and d_params left behind. */
+int sf_debug_loglike_grad_contract(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, double* d_grad,
+                                   int grad_stride, void* d_work, size_t work_bytes, void* stream);
 
 /* ---- multi-order batches (reference: the multi-order container
  * Starfish/spectrum.py:96-115, orders independent docs/intro.rst:71-73, EchelleModel stub

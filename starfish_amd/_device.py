@@ -674,6 +674,40 @@ class DeviceOrder:
             return self._run_applied("pointwise_batch", md, P, R, nrhs, per_walker, outputs, want_flux, max_chunk,
                                      self.pointwise_workspace_bytes)
 
+    def loglike_grad_workspace_bytes(self, md, B):
+        return self.lib.sf_loglike_grad_workspace_bytes(self.ctx, C.byref(md), int(B))
+
+    def loglike_grad(self, md, params, want_flux=False, max_chunk=None):
+        """The likelihood and its gradient in the covariance hyper-parameters (sf_loglike_grad_batch).  params: (B, stride)
+        rows as for :meth:`loglike`.  Returns dict of numpy arrays: lnl (B,) and info (B,) with :meth:`loglike`'s bits, grad
+        (B, slots) with the slots in parameter-row order (log_amp, log_ls of the global kernel if the model has one, then mu,
+        log_amp, log_sigma per local kernel), NaN rows where info != 0, and, asked for, flux (B, n).  Chunked and retried
+        like :meth:`apply`."""
+        torch = _torch()
+        slots = (2 if md.has_global else 0) + 3 * int(md.n_local)
+        with torch.cuda.device(self.dev):
+            P = params if torch.is_tensor(params) else to_dev(params, self.dev)
+            B = int(P.shape[0])
+
+            def run(again):
+                held = self._ws.numel() if self._ws is not None else 0
+                fit = units_that_fit(self.dev, 0, max(self.loglike_grad_workspace_bytes(md, 1), 1), held)
+                chunk = min(B, max_chunk or B, fit)
+                lnl, grad = empty((B,), self.dev), empty((B, max(slots, 1)), self.dev)
+                info = empty((B,), self.dev, torch.int32)
+                flux = empty((B, self.n), self.dev) if want_flux else None
+                ws = self._reserve(self.loglike_grad_workspace_bytes(md, chunk))
+                for lo in range(0, B, chunk):
+                    hi = min(lo + chunk, B)
+                    self._call("loglike_grad_batch", md, hi - lo, P[lo:hi], lnl[lo:hi], grad[lo:hi], max(slots, 1),
+                               flux[lo:hi] if want_flux else None, info[lo:hi], ws=ws)
+                res = dict(lnl=lnl.cpu().numpy(), grad=grad.cpu().numpy()[:, :slots], info=info.cpu().numpy())
+                if want_flux:
+                    res["flux"] = flux.cpu().numpy()
+                return res, res["info"]
+
+            return retry_internal(self.lib, "sf_loglike_grad_batch", run)
+
     def loglike_device(self, md, P_dev, out_lnl, info=None):
         """Enqueue-only variant for bench.py: device tensors in/out, no synchronisation."""
         self._call("loglike_batch", md, int(P_dev.shape[0]), P_dev, out_lnl, None, None, None, None, info)

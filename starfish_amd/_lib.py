@@ -121,6 +121,11 @@ SIGNATURES = {
         C.c_int,
         [_VP, C.c_int, C.c_int, C.c_int64, C.c_int, _VP, C.c_int64, _VP, C.c_size_t, _VP],
     ),
+    "sf_potri_blocks_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sf_potri_blocks_batch": (
+        C.c_int,
+        [_VP, C.c_int, C.c_int, C.c_int64, C.c_int, _VP, C.c_int, _VP, _VP, C.c_size_t, _VP],
+    ),
     "sf_apply_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int]),
     "sf_apply_batch": (
         C.c_int,
@@ -137,6 +142,15 @@ SIGNATURES = {
         C.c_int,
         [_VP, C.POINTER(ModelDesc), C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t,
          _VP],
+    ),
+    "sf_loglike_grad_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int]),
+    "sf_loglike_grad_batch": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_size_t, _VP],
+    ),
+    "sf_debug_loglike_grad_contract": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, _VP, C.c_int, _VP, C.c_size_t, _VP],
     ),
     "sf_debug_decompose_matvec": (
         C.c_int,

@@ -562,3 +562,73 @@ extern "C" int sf_pointwise_batch(sf_ctx* c, const sf_model_desc* mdl, int B, co
     if (d_info) SF_HIP(hipMemcpyAsync(d_info, pw.a.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
     return SF_OK;
 }
+
+// ----------------------------------------------------------------------------------- gradient in the covariance hyper-parameters
+// (sf_loglike_grad_batch, sf_debug_loglike_grad_contract)  The checks that need no context come first, as for
+// sf_pointwise_batch.
+static int grad_args_ok(const sf_model_desc* mdl, int B, bool have_pointers, int grad_stride) {
+    if (B <= 0 || B > 65535) {
+        sf_set_error("sf_loglike_grad_batch: B=%d must lie in 1 .. 65535", B);
+        return SF_EINVAL;
+    }
+    if (!have_pointers) {
+        sf_set_error("sf_loglike_grad_batch: d_params, d_lnl and d_grad are required");
+        return SF_EINVAL;
+    }
+    if (!mdl || mdl->n_local < 0 || mdl->n_local > SF_MAX_LOCAL) return SF_OK;  // (model_ok refuses it next)
+    const int slots = sf_cov_grad_slots(mdl->has_global, mdl->n_local);
+    if (slots == 0) {
+        sf_set_error("sf_loglike_grad_batch: nothing to differentiate (no global and no local kernel)");
+        return SF_EINVAL;
+    }
+    if (grad_stride < slots) {
+        sf_set_error("sf_loglike_grad_batch: grad_stride=%d < %d slots", grad_stride, slots);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_loglike_grad_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B) {
+    if (B <= 0 || B > 65535 || model_ok(c, mdl) || sf_cov_grad_slots(mdl->has_global, mdl->n_local) == 0) return 0;
+    return carve_grad(c, mdl, B, nullptr, 0, carve(c, mdl, B, nullptr, 0, true).bytes).bytes;
+}
+// the workspace of a call whose arguments passed
+static int open_grad(const sf_ctx* c, const sf_model_desc* mdl, int B, void* d_work, size_t work_bytes, Work* w, GradWork* gw) {
+    SF_CHECK(model_ok(c, mdl));
+    SF_CHECK(open_call(c, mdl, B, d_work, work_bytes, true, w));
+    *gw = carve_grad(c, mdl, B, d_work, work_bytes, w->bytes);
+    return work_fits(work_bytes, gw->bytes);
+}
+// 1/2 sum (alpha alpha^T - C^-1) o dC/dtheta from the alpha in the staging area and the X the inverse's launch left in the matrices
+static int grad_contract(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const Work& w, const GradWork& gw,
+                         double* d_grad, int grad_stride, hipStream_t s) {
+    sf_fill_args f = fill_args(c, mdl, d_params, w);
+    f.C = w.C, f.lda = w.L.lda, f.stride = (int64_t)w.L.npad * w.L.lda, f.lower_only = 1, f.add_jitter = 1;
+    return sf_launch_cov_grad(f, B, gw.winv, gw.a.stage, w.L.npad, gw.a.info, gw.part, d_grad, grad_stride, s);
+}
+extern "C" int sf_loglike_grad_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, double* d_lnl,
+                                     double* d_grad, int grad_stride, double* d_flux, int* d_info, void* d_work,
+                                     size_t work_bytes, void* stream) {
+    SF_CHECK(grad_args_ok(mdl, B, d_params && d_lnl && d_grad, grad_stride));
+    Work w;
+    GradWork gw;
+    SF_CHECK(open_grad(c, mdl, B, d_work, work_bytes, &w, &gw));
+    hipStream_t s = (hipStream_t)stream;
+    const Layout L = layout_of(c);
+    SF_CHECK(apply_staged(c, mdl, B, d_params, SF_APPLY_CINV, nullptr, 1, c->n, 0, d_flux, w, gw.a, s));
+    // (the factor applied first: the inverse's launch takes the strict upper triangle of the matrices as scratch)
+    SF_CHECK(sf_launch_chol_inverse_diag(w.C, L.npad, L.lda, (int64_t)L.npad * L.lda, B, gw.winv, gw.cinv_diag, L.npad, s));
+    SF_CHECK(grad_contract(c, mdl, B, d_params, w, gw, d_grad, grad_stride, s));
+    SF_HIP(hipMemcpyAsync(d_lnl, gw.a.lnl, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    if (d_info) SF_HIP(hipMemcpyAsync(d_info, gw.a.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return SF_OK;
+}
+// The contraction launches of sf_loglike_grad_batch alone, on the workspace a call with the same ctx, model, B and d_params
+// left (tools/bench_gradient.py times them)
+extern "C" int sf_debug_loglike_grad_contract(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, double* d_grad,
+                                              int grad_stride, void* d_work, size_t work_bytes, void* stream) {
+    SF_CHECK(grad_args_ok(mdl, B, d_params && d_grad, grad_stride));  // (no d_lnl here)
+    Work w;
+    GradWork gw;
+    SF_CHECK(open_grad(c, mdl, B, d_work, work_bytes, &w, &gw));
+    return grad_contract(c, mdl, B, d_params, w, gw, d_grad, grad_stride, (hipStream_t)stream);
+}

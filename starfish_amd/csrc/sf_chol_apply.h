@@ -30,17 +30,6 @@ struct sf_apply_args {
     int nrhs, op, ngroups, row_blocks;  // row_blocks: workgroups per (matrix, group): n / 64 for L Z out of place, else 1
 };
 
-// four consecutive doubles; al: p is 16-byte aligned
-__device__ __forceinline__ void sf_ap_ld4(const double* p, bool al, double (&v)[4]) {
-    if (al) {
-        const double2 lo = *(const double2*)p, hi = *(const double2*)(p + 2);
-        v[0] = lo.x, v[1] = lo.y, v[2] = hi.x, v[3] = hi.y;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = p[j];
-    }
-}
-
 // sum over k in [k0, k1) of L[row][k] X[k][col]: lane (lq, l15) holds row l15 of the wave's 16 rows as the A operand and
 // right-hand side l15 as the B operand, both at k = 16 t + 4 lq + j (any order of k sums the same products).  Lrow: row
 // l15 of the wave; xcol: right-hand side l15 (read only where `has`).  Result: register r = (row lq + 4 r, right-hand side l15).

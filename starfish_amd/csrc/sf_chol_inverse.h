@@ -59,34 +59,6 @@ __global__ __launch_bounds__(256) void k_chol_block_inverse(const sf_inverse_arg
     for (int q = 0; q < 16; ++q) W[(16 * w + q) * SF_LEAF + lane] = t[q];
 }
 
-// acc[t] += sum over k in [k0, k1) of L[row][k] X[k][16 t + l15]: Lrow = row l15 of the wave's 16 rows, xc[t] = column
-// 16 t + l15 of X indexed by k.  Lane (lq, l15) holds k = 16 s + 4 lq + j of both operands.
-__device__ __forceinline__ void sf_inv_sweep(const double* Lrow, bool al_l, const double* (&xc)[4], bool al_x, int k0,
-                                             int k1, int lq, sf_d4 (&acc)[4]) {
-    if (k0 >= k1) return;
-    // the operands of the next 16 columns are read under this step's products (the last step reads its own again)
-    double l[4], x[4][4];
-    sf_ap_ld4(Lrow + k0 + 4 * lq, al_l, l);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) sf_ap_ld4(xc[t] + k0 + 4 * lq, al_x, x[t]);
-    for (int kk = k0; kk < k1; kk += 16) {
-        const int kn = min(kk + 16, k1 - 16) + 4 * lq;
-        double ln[4], xn[4][4];
-        sf_ap_ld4(Lrow + kn, al_l, ln);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) sf_ap_ld4(xc[t] + kn, al_x, xn[t]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(l[j], x[t][j], acc[t], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            l[j] = ln[j];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) x[t][j] = xn[t][j];
-        }
-    }
-}
 // dacc += the squares of rows 16 sq .. 16 sq + 15 of column sc of the X tile, in row order
 __device__ __forceinline__ double sf_inv_squares(const double* Xs, int sc, int sq, double dacc) {
 #pragma unroll

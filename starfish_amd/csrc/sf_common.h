@@ -163,7 +163,7 @@ int sf_launch_diag_copy(const double* A, int n, int lda, int64_t stride, int bat
 
 int sf_launch_clock_probe(long long* out, long long wall_ticks, hipStream_t s);
 
-// sf_fill.hip (layers: sf_fill_elem.h, sf_fill_band.h, sf_fill_tile.h, sf_fill_dense.h, sf_fill_free.h, sf_cov_matvec.h)
+// sf_fill.hip (layers: sf_fill_elem.h, sf_fill_band.h, sf_fill_tile.h, sf_fill_dense.h, sf_fill_free.h, sf_cov_matvec.h, sf_cov_grad.h)
 struct sf_fill_args {
     const double* wave;    // [n]
     const double* sigma;   // [n]
@@ -206,6 +206,18 @@ int sf_launch_stream_write(double* dst, size_t count, double v, hipStream_t s); 
 // exist; v: [batch][nrhs][ldv]; yv: [batch][nrhs][m] scratch for Y v
 int sf_launch_cov_matvec(const sf_fill_args& f, int m, const double* v, int ldv, int nrhs, int batch, double* yv,
                          const int* info, double* out, hipStream_t s);
+// sf_cov_grad.h: selected 64 x 64 blocks of C^-1 = X^T X from what sf_launch_chol_inverse_diag leaves (X^T above the diagonal,
+// winv); pairs: device [npairs][2] = (I, J), 0 <= J <= I < n / 64 (any other pair: a block of NaN); out: [batch][npairs][64][64]
+int sf_launch_cinv_blocks(const double* L, int n, int lda, int64_t stride, int batch, const double* winv, const int* pairs,
+                          int npairs, double* out, hipStream_t s);
+// ... and the likelihood's gradient in the covariance hyper-parameters contracted from them: f as the fill gets it with C = the
+// factored matrices after the inverse's launch; alpha: [batch][ld_alpha] = C^-1 r; part: sf_cov_grad_work_doubles of scratch;
+// grad[b * grad_stride + slot]: log_amp, log_ls of the global kernel, then mu, log_amp, log_sigma per local kernel; NaN where
+// info[b] != 0
+static inline __host__ __device__ int sf_cov_grad_slots(int has_global, int n_local) { return (has_global ? 2 : 0) + 3 * n_local; }
+size_t sf_cov_grad_work_doubles(int n, int has_global, int n_local, int batch);
+int sf_launch_cov_grad(const sf_fill_args& f, int batch, const double* winv, const double* alpha, int ld_alpha, const int* info,
+                       double* part, double* grad, int grad_stride, hipStream_t s);
 // sf_fill_band.h: band storage of the structured part of C (sf_band.hip consumes it); a.npad = rows written (>= a.n)
 int sf_launch_band_fill(const sf_fill_args& a, int B, double* band, int ws, int halfwidth, int ldb, int64_t sband,
                         int* info, double* gtab, hipStream_t s, int tile_wt = -1);  // ws stored diagonals > halfwidth; gtab: B x (ws+1) or NULL

@@ -1,5 +1,6 @@
 // Device helpers shared by the .hip files: lane and wave primitives and the XCD remap of block ids (all four files), and
-// the Cholesky of a 16 x 16 block in the MFMA accumulator layout (k_diag_mfma, sf_diag_lds_body; sf_band.hip keeps its own).
+// the Cholesky of a 16 x 16 block in the MFMA accumulator layout (k_diag_mfma, sf_diag_lds_body; sf_band.hip keeps its own),
+// and the k-contiguous operand reads of the 64-column MFMA sweep (the factor's application, its inverse, the gradient).
 // Floating-point contraction: the helpers spell every fused multiply-add as __builtin_fma and hold no other candidate,
 // so the objects built with -ffp-contract=off (sf_fill, sf_transform) and the others get the same code from them.
 #pragma once
@@ -38,6 +39,47 @@ __device__ __forceinline__ int sf_xcd_remap(int bid, int nblk) {
     const int q = nblk >> 3, r = nblk & 7;
     const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return base + slot;
+}
+
+// ---- operands of v_mfma_f64_16x16x4_f64 read k-contiguously (sf_chol_apply.h, sf_chol_inverse.h, sf_cov_grad.h)
+// four consecutive doubles; al: p is 16-byte aligned
+__device__ __forceinline__ void sf_ap_ld4(const double* p, bool al, double (&v)[4]) {
+    if (al) {
+        const double2 lo = *(const double2*)p, hi = *(const double2*)(p + 2);
+        v[0] = lo.x, v[1] = lo.y, v[2] = hi.x, v[3] = hi.y;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = p[j];
+    }
+}
+
+// acc[t] += sum over k in [k0, k1) of L[row][k] X[k][16 t + l15]: Lrow = row l15 of the wave's 16 rows, xc[t] = column
+// 16 t + l15 of X indexed by k.  Lane (lq, l15) holds k = 16 s + 4 lq + j of both operands.
+__device__ __forceinline__ void sf_inv_sweep(const double* Lrow, bool al_l, const double* (&xc)[4], bool al_x, int k0,
+                                             int k1, int lq, sf_d4 (&acc)[4]) {
+    if (k0 >= k1) return;
+    // the operands of the next 16 columns are read under this step's products (the last step reads its own again)
+    double l[4], x[4][4];
+    sf_ap_ld4(Lrow + k0 + 4 * lq, al_l, l);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) sf_ap_ld4(xc[t] + k0 + 4 * lq, al_x, x[t]);
+    for (int kk = k0; kk < k1; kk += 16) {
+        const int kn = min(kk + 16, k1 - 16) + 4 * lq;
+        double ln[4], xn[4][4];
+        sf_ap_ld4(Lrow + kn, al_l, ln);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) sf_ap_ld4(xc[t] + kn, al_x, xn[t]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(l[j], x[t][j], acc[t], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            l[j] = ln[j];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) x[t][j] = xn[t][j];
+        }
+    }
 }
 
 // One wave: Cholesky of the symmetric 16 x 16 block a0 AND the inverse of its factor, both kept in the MFMA

@@ -17,6 +17,7 @@
 //   sf_fill_dense.h   k_dense_map, k_fill_dense_plain, k_fill_dense_band: both triangles of caller matrices
 //   sf_fill_free.h    k_global_cov, k_local_cov, k_stream_write: stand-alone kernels and the write probe
 //   sf_cov_matvec.h   k_cov_yv, k_cov_matvec: the components of C applied to vectors (sf_decompose_batch)
+//   sf_cov_grad.h     k_cinv_blocks, k_cov_grad, k_cov_grad_sum: blocks of C^-1 and the gradient in the covariance hyper-parameters
 #include "sf_common.h"
 #include "sf_device.h"
 #include "sf_fill_elem.h"
@@ -25,3 +26,4 @@
 #include "sf_fill_dense.h"
 #include "sf_fill_free.h"
 #include "sf_cov_matvec.h"
+#include "sf_cov_grad.h"

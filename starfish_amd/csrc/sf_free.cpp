@@ -244,6 +244,31 @@ extern "C" int sf_potri_diag_batch(double* d_L, int n, int lda, int64_t stride, 
     return sf_launch_chol_inverse_diag(d_L, n, lda, stride, batch, w.winv, d_out, out_stride, (hipStream_t)stream);
 }
 
+extern "C" size_t sf_potri_blocks_workspace_bytes(int n, int batch) {
+    if (n <= 0 || n % SF_LEAF != 0 || batch <= 0) return 0;
+    return carve_potri_blocks(n, batch, nullptr, 0).bytes;
+}
+extern "C" int sf_potri_blocks_batch(double* d_L, int n, int lda, int64_t stride, int batch, const int* d_pairs, int npairs,
+                                     double* d_out, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_L || !d_pairs || !d_out || !d_work) {
+        sf_set_error("sf_potri_blocks_batch: d_L, d_pairs, d_out and d_work are required");
+        return SF_EINVAL;
+    }
+    if (n <= 0 || n % SF_LEAF != 0 || lda < n || batch < 1 || npairs < 1) {
+        sf_set_error("sf_potri_blocks_batch: n=%d must be a positive multiple of %d, lda=%d >= n, batch=%d >= 1, npairs=%d >= 1", n,
+                     SF_LEAF, lda, batch, npairs);
+        return SF_EINVAL;
+    }
+    const PotriBlocksWork w = carve_potri_blocks(n, batch, d_work, work_bytes);
+    if (work_bytes < w.bytes) {
+        sf_set_error("sf_potri_blocks_batch: workspace too small: have %zu, need %zu", work_bytes, w.bytes);
+        return SF_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    SF_CHECK(sf_launch_chol_inverse_diag(d_L, n, lda, stride, batch, w.winv, w.diag, n, s));
+    return sf_launch_cinv_blocks(d_L, n, lda, stride, batch, w.winv, d_pairs, npairs, d_out, s);
+}
+
 extern "C" int sf_emulator_v11_build(const double* d_grid, int M, int P, int m, const double* d_hyper, const double* d_iphiphi,
                                      double* d_A, int npad, int lda, void* stream) {
     return sf_launch_v11_build(d_grid, M, P, m, d_hyper, d_iphiphi, d_A, npad, lda, (hipStream_t)stream);

@@ -208,6 +208,26 @@ static PointwiseWork carve_pointwise(const sf_ctx* c, int B, int nrhs, void* p, 
     return w;
 }
 
+// sf_loglike_grad_batch: the layout of sf_apply_batch with one right-hand side (the staging area ends up holding alpha =
+// C^-1 r), then the diagonal of the inverse (npad doubles per walker: the inverse's launch writes it, nothing reads it), the
+// scratch of that launch (carve_potri) and the contraction's partial sums per (walker, block row, slot)
+struct GradWork {
+    ApplyWork a;
+    double *cinv_diag, *winv, *part;
+    size_t bytes;
+};
+static GradWork carve_grad(const sf_ctx* c, const sf_model_desc* mdl, int B, void* p, size_t cap, size_t base_bytes) {
+    GradWork w;
+    w.a = carve_apply(c, B, 1, p, cap, base_bytes);
+    Carve k(p, cap);
+    k.off = w.a.bytes;
+    w.cinv_diag = k.take<double>((size_t)B * c->npad);
+    w.winv = k.take<double>(sf_chol_inverse_work_doubles(c->npad, B));
+    w.part = k.take<double>(sf_cov_grad_work_doubles(c->n, mdl->has_global, mdl->n_local, B));
+    w.bytes = sf_align_up(k.off, 256);
+    return w;
+}
+
 // ------------------------------------------------------------------- context-free workspaces
 // sf_potri_diag_batch: the transposed inverses of the 64 x 64 diagonal blocks, [batch][n / 64][64][64]
 struct PotriWork {
@@ -218,6 +238,19 @@ static PotriWork carve_potri(int n, int batch, void* p, size_t cap) {
     Carve k(p, cap);
     PotriWork w;
     w.winv = k.take<double>(sf_chol_inverse_work_doubles(n, batch));
+    w.bytes = sf_align_up(k.off, 256);
+    return w;
+}
+// sf_potri_blocks_batch: the same, then the diagonal of the inverse ([batch][n]: the inverse's launch writes it)
+struct PotriBlocksWork {
+    double *winv, *diag;
+    size_t bytes;
+};
+static PotriBlocksWork carve_potri_blocks(int n, int batch, void* p, size_t cap) {
+    Carve k(p, cap);
+    PotriBlocksWork w;
+    w.winv = k.take<double>(sf_chol_inverse_work_doubles(n, batch));
+    w.diag = k.take<double>((size_t)n * batch);
     w.bytes = sf_align_up(k.off, 256);
     return w;
 }

@@ -635,6 +635,107 @@ class SpectrumModel:
         res = self._pointwise_dict(rhs, out["alpha"], out["cinv_diag"], out["cov_diag"], single)
         return (res, out["info"]) if return_info else res
 
+    # ------------------------------------------------------------------ gradient in the covariance hyper-parameters
+    @property
+    def gradient_labels(self):
+        """tuple of str : the thawed labels under ``global_cov:`` / ``local_cov:``, in :attr:`labels` order: the parameters
+        :meth:`log_likelihood_gradient` differentiates in."""
+        return tuple(key for key in self.labels if key.startswith(("global_cov:", "local_cov:")))
+
+    def _gradient_slots(self, md):
+        """For every label of :attr:`gradient_labels`, its slot in the device's gradient row (log_amp, log_ls of the global
+        kernel if the model has one, then mu, log_amp, log_sigma per local kernel)."""
+        first_local = 2 if md.has_global else 0
+        slots = []
+        for key in self.gradient_labels:
+            group, rest = key.split(":", 1)
+            if group == "global_cov":
+                slots.append(self._GLOBAL_PARAMS.index(rest))
+            else:
+                i, leaf = rest.split(":")
+                slots.append(first_local + 3 * int(i) + self._LOCAL_PARAMS.index(leaf))
+        return slots
+
+    def log_likelihood_gradient(self):
+        """``(lnL, {label: d lnL / d label})`` of the current state for the labels of :attr:`gradient_labels`: the analytic
+        gradient of :meth:`log_likelihood` (no priors) in the covariance hyper-parameters, from one factorisation
+        (Rasmussen & Williams, GPML, eq. 5.9).  In ``mu`` of a local kernel it is the almost-everywhere derivative: the
+        likelihood has a kink wherever two pixels of the patch are equidistant from ``mu``.  Raises as
+        :meth:`log_likelihood` does; the model's state is not modified."""
+        labels = self.gradient_labels
+        if not labels:
+            raise ValueError("no thawed global_cov / local_cov parameter to differentiate in")
+        dev, md, rows = self._pack(update_caches=False)
+        out = dev.loglike_grad(md, rows)
+        self._raise_for_info(out["info"][0])
+        g = out["grad"][0, self._gradient_slots(md)]
+        return float(out["lnl"][0]), dict(zip(labels, (float(v) for v in g)))
+
+    def log_likelihood_gradient_batch(self, P, return_info=False):
+        """:meth:`log_likelihood_gradient` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device pass:
+        ``(lnL (B,), grad (B, len(gradient_labels)))``.  Walkers that fail get ``-inf`` and a NaN row, ``info`` their codes.
+        The model's own state is not modified."""
+        if not self.gradient_labels:
+            raise ValueError("no thawed global_cov / local_cov parameter to differentiate in")
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        dev, md, rows = self._pack(P, update_caches=False)
+        out = dev.loglike_grad(md, rows)
+        lnl = np.where(out["info"] == 0, out["lnl"], -np.inf)
+        grad = out["grad"][:, self._gradient_slots(md)]
+        return (lnl, grad, out["info"]) if return_info else (lnl, grad)
+
+    def train_covariance(self, priors=None, **kwargs):
+        """MAP estimate of the covariance hyper-parameters alone: ``scipy.optimize.minimize(method="L-BFGS-B", jac=True)``
+        over :attr:`gradient_labels` with the analytic gradient of :meth:`log_likelihood_gradient_batch`; every other
+        parameter keeps its value.  ``priors`` are checked as :meth:`train` checks them; a prior on an optimised label adds
+        its ``logpdf`` and the slope of it by a central difference with step ``eps^(1/3) max(1, |x|)`` (scipy's frozen
+        distributions expose no derivative), priors on other parameters a constant.  ``kwargs`` go to ``minimize``.  On
+        success the model is left at ``soln.x``."""
+        from scipy.optimize import minimize
+
+        priors = self._checked_priors(priors)
+        glabels = self.gradient_labels
+        if not glabels:
+            raise ValueError("no thawed global_cov / local_cov parameter to optimise")
+        labels = self.labels
+        cols = [labels.index(key) for key in glabels]
+        x_all = self.get_param_vector().astype(np.float64)
+        const_lp = sum(prior.logpdf(self[key]) for key, prior in priors.items() if key in self.params and key not in glabels)
+        h0 = np.finfo(np.float64).eps ** (1.0 / 3.0)
+
+        def objective(x):
+            row = x_all.copy()
+            row[cols] = x
+            lnl, grad, info = self.log_likelihood_gradient_batch(row[None, :], return_info=True)
+            self._raise_for_info(info[0])
+            value, slope = float(lnl[0]) + const_lp, grad[0].copy()
+            for i, key in enumerate(glabels):
+                if key in priors:
+                    h = h0 * max(1.0, abs(x[i]))
+                    value += priors[key].logpdf(x[i])
+                    slope[i] += (priors[key].logpdf(x[i] + h) - priors[key].logpdf(x[i] - h)) / (2 * h)
+            return -value, -slope
+
+        opts = {"method": "L-BFGS-B", "jac": True}
+        opts.update(kwargs)
+        soln = minimize(objective, x_all[cols], **opts)
+        if soln.success:
+            self.set_param_dict(dict(zip(glabels, soln.x)))
+        return soln
+
+    def _checked_priors(self, priors):
+        """``priors`` ({} for None) after the checks of :meth:`train` (spectrum_model.py:655-668)."""
+        priors = {} if priors is None else priors
+        for key, val in priors.items():
+            if key not in self.params and not key.startswith("cheb"):
+                raise ValueError(f"Invalid priors: {key!r} is not a parameter of this model")
+            if not callable(getattr(val, "logpdf", None)):
+                raise ValueError(f"Invalid priors. {key} does not have a `logpdf` method")
+            log_prob = val.logpdf(self[key])
+            if not np.isfinite(log_prob):
+                raise RuntimeError(f"{key}'s logpdf evaluated to {log_prob}")
+        return priors
+
     def train(self, priors=None, batch_simplex=True, **kwargs):
         """MAP estimate by Nelder-Mead over :meth:`log_likelihood` (spectrum_model.py:635-696).  ``kwargs`` go to
         ``scipy.optimize.minimize`` as in the reference.
@@ -650,15 +751,7 @@ class SpectrumModel:
 
         from .._neldermead import minimize_neldermead_batched, split_minimize_kwargs
 
-        priors = {} if priors is None else priors
-        for key, val in priors.items():
-            if key not in self.params and not key.startswith("cheb"):
-                raise ValueError(f"Invalid priors: {key!r} is not a parameter of this model")
-            if not callable(getattr(val, "logpdf", None)):
-                raise ValueError(f"Invalid priors. {key} does not have a `logpdf` method")
-            log_prob = val.logpdf(self[key])
-            if not np.isfinite(log_prob):
-                raise RuntimeError(f"{key}'s logpdf evaluated to {log_prob}")
+        priors = self._checked_priors(priors)
 
         def nll(P):
             self.set_param_vector(P)
