@@ -57,17 +57,18 @@ def recover_from_internal(lib, where, count, stacklevel=3):
     lib.sf_persistent_potrf(0)
 
 
-def retry_internal(lib, where, evaluate, count=None):
+def retry_internal(lib, where, evaluate, count=None, stacklevel=4):
     """THE policy for SF_INFO_INTERNAL of the dense path.  ``evaluate(again) -> (result, info)`` runs the call and fetches
     its status codes; ``again`` is False for the first run and True for the one repeat after
     :func:`recover_from_internal` (never a silent -inf: warn, switch the persistent kernel off, evaluate again).  A -5 that
     survives the repeat is never an ordinary per-unit status -- no value of the call is valid: RuntimeError.  ``count``:
-    the units the warning names (default: the -5 entries of ``info``)."""
+    the units the warning names (default: the -5 entries of ``info``); ``stacklevel``: the frame it is attributed to (default:
+    the one that called our caller)."""
     result, info = evaluate(False)
     bad = int(np.count_nonzero(np.asarray(info) == INFO_INTERNAL))
     if not bad:
         return result
-    recover_from_internal(lib, where, bad if count is None else count, stacklevel=4)  # (the frame that called our caller)
+    recover_from_internal(lib, where, bad if count is None else count, stacklevel=stacklevel)
     result, info = evaluate(True)
     if np.any(np.asarray(info) == INFO_INTERNAL):
         raise RuntimeError(INFO_MESSAGES[INFO_INTERNAL])
@@ -429,8 +430,11 @@ class DeviceOrder:
             _lib.check(stride, "sf_param_stride")
         return stride
 
+    def _size_query(self, call, md, *counts):
+        return getattr(self.lib, f"sf_{call}workspace_bytes")(self.ctx, C.byref(md), *(int(v) for v in counts))
+
     def workspace_bytes(self, md, B):
-        return self.lib.sf_workspace_bytes(self.ctx, C.byref(md), int(B))
+        return self._size_query("", md, B)
 
     def max_batch(self, md):
         """Largest batch whose workspace fits the free HBM (leaving a safety margin)."""
@@ -473,7 +477,7 @@ class DeviceOrder:
         return band_halfwidth_bound(self._keep[0], rows, self.P, bool(md.has_global), int(md.n_local), int(md.n_cheb))
 
     def banded_workspace_bytes(self, md, B, halfwidth):
-        return self.lib.sf_banded_workspace_bytes(self.ctx, C.byref(md), int(B), int(halfwidth))
+        return self._size_query("banded_", md, B, halfwidth)
 
     def _work_banded(self, md, B, halfwidth):
         return self._reserve(self.banded_workspace_bytes(md, B, halfwidth))
@@ -486,6 +490,31 @@ class DeviceOrder:
                    ws=self._work_banded(md, B, halfwidth))
 
     # ------------------------------------------------------------------ batched calls
+    def _rows(self, params):
+        """Parameter rows ((B, stride) float64, numpy or tensor) on the order's device."""
+        return params if _torch().is_tensor(params) else to_dev(params, self.dev)
+
+    def _run_chunked(self, name, md, P, max_chunk, workspace_bytes, buffers, args, download):
+        """THE chunk loop of the dense calls ``sf_<name>(ctx, &md, B, P, *args, ws, ...)``: the rows of ``P`` cut into chunks
+        whose workspace (``workspace_bytes(units)``) fits the free HBM, at most ``max_chunk`` each; the results allocated
+        (``buffers()``) and every chunk enqueued on ONE reserved workspace with ``args(bufs, lo, hi)``; ``download(bufs)``, a
+        dict with "info", returned; all of it once more if a status is SF_INFO_INTERNAL (:func:`retry_internal`, whose
+        warning names the frame that called our caller)."""
+        B = int(P.shape[0])
+
+        def run(again):
+            held = self._ws.numel() if self._ws is not None else 0
+            chunk = min(B, max_chunk or B, units_that_fit(self.dev, 0, max(workspace_bytes(1), 1), held))
+            bufs = buffers()
+            ws = self._reserve(workspace_bytes(chunk))
+            for lo in range(0, B, chunk):
+                hi = min(lo + chunk, B)
+                self._call(name, md, hi - lo, P[lo:hi], *args(bufs, lo, hi), ws=ws)
+            res = download(bufs)
+            return res, res["info"]
+
+        return retry_internal(self.lib, "sf_" + name, run, stacklevel=5)
+
     def loglike(self, md, params, want_resid=False, max_chunk=None, solver="dense"):
         """params: (B, stride) float64 (numpy or cuda tensor) in the C-ABI row layout.
         Returns dict of numpy arrays: lnl, logdet, sqmah, log_scale, info (+ resid).
@@ -500,20 +529,16 @@ class DeviceOrder:
         if solver != "dense":
             return self._loglike_structured(md, params, want_resid, max_chunk, solver)
         with torch.cuda.device(self.dev):
-            P = params if torch.is_tensor(params) else to_dev(params, self.dev)
-            B = int(P.shape[0])
+            P = self._rows(params)
 
-            def run(again):
-                chunk = min(B, max_chunk or B, self.max_batch(md))
-                quad, info, resid = result_buffers(B, self.dev, self.n if want_resid else None)
-                for lo in range(0, B, chunk):
-                    hi = min(lo + chunk, B)
-                    self._call("loglike_batch", md, hi - lo, P[lo:hi], quad[0][lo:hi], quad[1][lo:hi], quad[2][lo:hi],
-                               resid[lo:hi] if want_resid else None, quad[3][lo:hi], info[lo:hi])
-                out = fetch_results(quad, info, resid)
-                return out, out["info"]
+            def args(bufs, lo, hi):
+                quad, info, resid = bufs
+                return (quad[0][lo:hi], quad[1][lo:hi], quad[2][lo:hi], resid[lo:hi] if want_resid else None, quad[3][lo:hi],
+                        info[lo:hi])
 
-            return retry_internal(self.lib, "sf_loglike_batch", run)
+            return self._run_chunked("loglike_batch", md, P, max_chunk, lambda units: self.workspace_bytes(md, units),
+                                     lambda: result_buffers(int(P.shape[0]), self.dev, self.n if want_resid else None), args,
+                                     lambda bufs: fetch_results(*bufs))
 
     def _loglike_structured(self, md, params, want_resid, max_chunk, solver):
         return self.structured_collect(md, self.structured_enqueue(md, params, want_resid, max_chunk), solver)
@@ -585,13 +610,16 @@ class DeviceOrder:
         return out
 
     def apply_workspace_bytes(self, md, B, nrhs):
-        return self.lib.sf_apply_workspace_bytes(self.ctx, C.byref(md), int(B), int(nrhs))
+        return self._size_query("apply_", md, B, nrhs)
 
     def decompose_workspace_bytes(self, md, B, nrhs):
-        return self.lib.sf_decompose_workspace_bytes(self.ctx, C.byref(md), int(B), int(nrhs))
+        return self._size_query("decompose_", md, B, nrhs)
 
     def pointwise_workspace_bytes(self, md, B, nrhs):
-        return self.lib.sf_pointwise_workspace_bytes(self.ctx, C.byref(md), int(B), int(nrhs))
+        return self._size_query("pointwise_", md, B, nrhs)
+
+    def loglike_grad_workspace_bytes(self, md, B):
+        return self._size_query("loglike_grad_", md, B)
 
     def _rhs_on_device(self, rhs, B):
         """``rhs`` of :meth:`apply` / :meth:`decompose` as (contiguous device tensor or None, nrhs, per_walker)."""
@@ -606,32 +634,40 @@ class DeviceOrder:
             raise ValueError("rhs holds no right-hand side")
         return R.contiguous(), nrhs, R.dim() == 3
 
-    def _run_applied(self, name, md, P, R, nrhs, per_walker, outputs, want_flux, max_chunk, workspace_bytes, lead=()):
-        """The chunk loop and retry of the calls that apply the factor: ``sf_<name>(ctx, &md, B, P, *lead, rhs, nrhs, ldr,
-        rhs_stride, *outputs, flux, info, ws, ...)``.  ``outputs``: key -> trailing shape of a (B, ...) double result."""
+    def _outputs(self, B, outputs, want_flux):
+        """``buffers`` and ``download`` of :meth:`_run_chunked` for the calls that apply the factor: ``bufs`` = (the (B, ...)
+        double results in the order of ``outputs``, key -> trailing shape; the int32 status; the (B, n) flux or None)."""
         torch = _torch()
-        B = int(P.shape[0])
 
-        def run(again):
-            held = self._ws.numel() if self._ws is not None else 0
-            fit = units_that_fit(self.dev, 0, max(workspace_bytes(md, 1, nrhs), 1), held)
-            chunk = min(B, max_chunk or B, fit)
-            outs = {key: empty((B,) + tuple(shape), self.dev) for key, shape in outputs.items()}
-            info = empty((B,), self.dev, torch.int32)
-            flux = empty((B, self.n), self.dev) if want_flux else None
-            ws = self._reserve(workspace_bytes(md, chunk, nrhs))
-            for lo in range(0, B, chunk):
-                hi = min(lo + chunk, B)
-                self._call(name, md, hi - lo, P[lo:hi], *lead, R[lo:hi] if per_walker else R, nrhs, self.n,
-                           nrhs * self.n if per_walker else 0, *[o[lo:hi] for o in outs.values()],
-                           flux[lo:hi] if want_flux else None, info[lo:hi], ws=ws)
-            res = {key: o.cpu().numpy() for key, o in outs.items()}
+        def buffers():
+            return ([empty((B,) + tuple(shape), self.dev) for shape in outputs.values()], empty((B,), self.dev, torch.int32),
+                    empty((B, self.n), self.dev) if want_flux else None)
+
+        def download(bufs):
+            outs, info, flux = bufs
+            res = {key: o.cpu().numpy() for key, o in zip(outputs, outs)}
             res["info"] = info.cpu().numpy()
             if want_flux:
                 res["flux"] = flux.cpu().numpy()
-            return res, res["info"]
+            return res
 
-        return retry_internal(self.lib, "sf_" + name, run)
+        return buffers, download
+
+    def _run_applied(self, name, md, params, rhs, outputs, want_flux, max_chunk, workspace_bytes, lead=()):
+        """:meth:`_run_chunked` for ``sf_<name>(ctx, &md, B, P, *lead, rhs, nrhs, ldr, rhs_stride, *outputs, flux, info, ws,
+        ...)``.  ``outputs(nrhs)``: key -> trailing shape of a (B, ...) double result."""
+        with _torch().cuda.device(self.dev):
+            P = self._rows(params)
+            R, nrhs, per_walker = self._rhs_on_device(rhs, int(P.shape[0]))
+            buffers, download = self._outputs(int(P.shape[0]), outputs(nrhs), want_flux)
+
+            def args(bufs, lo, hi):
+                outs, info, flux = bufs
+                return (*lead, R[lo:hi] if per_walker else R, nrhs, self.n, nrhs * self.n if per_walker else 0,
+                        *[o[lo:hi] for o in outs], flux[lo:hi] if want_flux else None, info[lo:hi])
+
+            return self._run_chunked(name, md, P, max_chunk, lambda units: workspace_bytes(md, units, nrhs), buffers, args,
+                                     download)
 
     def apply(self, md, params, op, rhs=None, want_flux=False, max_chunk=None):
         """The Cholesky factor of every walker's covariance matrix applied to right-hand sides (sf_apply_batch): ``op`` is
@@ -639,13 +675,9 @@ class DeviceOrder:
         params: (B, stride) rows as for :meth:`loglike`.  rhs: None (each walker's own residual), (nrhs, n) shared by all
         walkers or (B, nrhs, n).  Returns dict of numpy arrays: out (B, nrhs, n), NaN for walkers with info != 0, info
         (the codes of :meth:`loglike`) and, asked for, flux (B, n).  Always the dense factor."""
-        torch = _torch()
         code = APPLY_OPS[op] if isinstance(op, str) else int(op)
-        with torch.cuda.device(self.dev):
-            P = params if torch.is_tensor(params) else to_dev(params, self.dev)
-            R, nrhs, per_walker = self._rhs_on_device(rhs, int(P.shape[0]))
-            return self._run_applied("apply_batch", md, P, R, nrhs, per_walker, {"out": (nrhs, self.n)}, want_flux,
-                                     max_chunk, self.apply_workspace_bytes, lead=(code,))
+        return self._run_applied("apply_batch", md, params, rhs, lambda nrhs: {"out": (nrhs, self.n)}, want_flux, max_chunk,
+                                 self.apply_workspace_bytes, lead=(code,))
 
     def decompose(self, md, params, rhs=None, want_flux=False, max_chunk=None):
         """The right-hand sides split by covariance component (sf_decompose_batch): ``alpha = C^-1 rhs`` as :meth:`apply`
@@ -653,29 +685,18 @@ class DeviceOrder:
         without one), 3 + j local kernel j.  params, rhs: as for :meth:`apply`.  Returns dict of numpy arrays: comp
         (B, 3 + n_local, nrhs, n), alpha (B, nrhs, n), info and, asked for, flux (B, n); NaN rows where info != 0.
         Chunked and retried like :meth:`apply`."""
-        torch = _torch()
-        with torch.cuda.device(self.dev):
-            P = params if torch.is_tensor(params) else to_dev(params, self.dev)
-            R, nrhs, per_walker = self._rhs_on_device(rhs, int(P.shape[0]))
-            outputs = {"comp": (3 + int(md.n_local), nrhs, self.n), "alpha": (nrhs, self.n)}
-            return self._run_applied("decompose_batch", md, P, R, nrhs, per_walker, outputs, want_flux, max_chunk,
-                                     self.decompose_workspace_bytes)
+        outputs = lambda nrhs: {"comp": (3 + int(md.n_local), nrhs, self.n), "alpha": (nrhs, self.n)}  # noqa: E731
+        return self._run_applied("decompose_batch", md, params, rhs, outputs, want_flux, max_chunk,
+                                 self.decompose_workspace_bytes)
 
     def pointwise(self, md, params, rhs=None, want_flux=False, max_chunk=None):
         """What the per-pixel leave-one-out diagnostics need (sf_pointwise_batch): ``alpha = C^-1 rhs`` as :meth:`apply`
         with "Cinv" gives it, ``cinv_diag = diag(C^-1)`` and ``cov_diag = diag(C)``, jitter included, as it was factorised.
         params, rhs: as for :meth:`apply`.  Returns dict of numpy arrays: alpha (B, nrhs, n), cinv_diag (B, n), cov_diag
         (B, n), info and, asked for, flux (B, n); NaN rows where info != 0.  Chunked and retried like :meth:`apply`."""
-        torch = _torch()
-        with torch.cuda.device(self.dev):
-            P = params if torch.is_tensor(params) else to_dev(params, self.dev)
-            R, nrhs, per_walker = self._rhs_on_device(rhs, int(P.shape[0]))
-            outputs = {"alpha": (nrhs, self.n), "cinv_diag": (self.n,), "cov_diag": (self.n,)}
-            return self._run_applied("pointwise_batch", md, P, R, nrhs, per_walker, outputs, want_flux, max_chunk,
-                                     self.pointwise_workspace_bytes)
-
-    def loglike_grad_workspace_bytes(self, md, B):
-        return self.lib.sf_loglike_grad_workspace_bytes(self.ctx, C.byref(md), int(B))
+        outputs = lambda nrhs: {"alpha": (nrhs, self.n), "cinv_diag": (self.n,), "cov_diag": (self.n,)}  # noqa: E731
+        return self._run_applied("pointwise_batch", md, params, rhs, outputs, want_flux, max_chunk,
+                                 self.pointwise_workspace_bytes)
 
     def loglike_grad(self, md, params, want_flux=False, max_chunk=None):
         """The likelihood and its gradient in the covariance hyper-parameters (sf_loglike_grad_batch).  params: (B, stride)
@@ -683,30 +704,23 @@ class DeviceOrder:
         (B, slots) with the slots in parameter-row order (log_amp, log_ls of the global kernel if the model has one, then mu,
         log_amp, log_sigma per local kernel), NaN rows where info != 0, and, asked for, flux (B, n).  Chunked and retried
         like :meth:`apply`."""
-        torch = _torch()
         slots = (2 if md.has_global else 0) + 3 * int(md.n_local)
-        with torch.cuda.device(self.dev):
-            P = params if torch.is_tensor(params) else to_dev(params, self.dev)
-            B = int(P.shape[0])
+        stride = max(slots, 1)
+        with _torch().cuda.device(self.dev):
+            P = self._rows(params)
+            buffers, download = self._outputs(int(P.shape[0]), {"lnl": (), "grad": (stride,)}, want_flux)
 
-            def run(again):
-                held = self._ws.numel() if self._ws is not None else 0
-                fit = units_that_fit(self.dev, 0, max(self.loglike_grad_workspace_bytes(md, 1), 1), held)
-                chunk = min(B, max_chunk or B, fit)
-                lnl, grad = empty((B,), self.dev), empty((B, max(slots, 1)), self.dev)
-                info = empty((B,), self.dev, torch.int32)
-                flux = empty((B, self.n), self.dev) if want_flux else None
-                ws = self._reserve(self.loglike_grad_workspace_bytes(md, chunk))
-                for lo in range(0, B, chunk):
-                    hi = min(lo + chunk, B)
-                    self._call("loglike_grad_batch", md, hi - lo, P[lo:hi], lnl[lo:hi], grad[lo:hi], max(slots, 1),
-                               flux[lo:hi] if want_flux else None, info[lo:hi], ws=ws)
-                res = dict(lnl=lnl.cpu().numpy(), grad=grad.cpu().numpy()[:, :slots], info=info.cpu().numpy())
-                if want_flux:
-                    res["flux"] = flux.cpu().numpy()
-                return res, res["info"]
+            def args(bufs, lo, hi):
+                (lnl, grad), info, flux = bufs
+                return lnl[lo:hi], grad[lo:hi], stride, flux[lo:hi] if want_flux else None, info[lo:hi]
 
-            return retry_internal(self.lib, "sf_loglike_grad_batch", run)
+            def sliced(bufs):
+                res = download(bufs)
+                res["grad"] = res["grad"][:, :slots]
+                return res
+
+            return self._run_chunked("loglike_grad_batch", md, P, max_chunk,
+                                     lambda units: self.loglike_grad_workspace_bytes(md, units), buffers, args, sliced)
 
     def loglike_device(self, md, P_dev, out_lnl, info=None):
         """Enqueue-only variant for bench.py: device tensors in/out, no synchronisation."""
@@ -716,7 +730,7 @@ class DeviceOrder:
         """SpectrumModel.__call__ for B rows: flux (B, n), cov (B, n, n), log_scale, info."""
         torch = _torch()
         with torch.cuda.device(self.dev):
-            P = params if torch.is_tensor(params) else to_dev(params, self.dev)
+            P = self._rows(params)
             B = int(P.shape[0])
             flux = empty((B, self.n), self.dev)
             cov = empty((B, self.n, self.n), self.dev)
@@ -735,7 +749,7 @@ class DeviceOrder:
         last matrix and returns them as a third value (tests: nothing may be written past the caller's array)."""
         torch = _torch()
         with torch.cuda.device(self.dev):
-            P = params if torch.is_tensor(params) else to_dev(params, self.dev)
+            P = self._rows(params)
             B = int(P.shape[0])
             ld = int(ld or self.n)
             buf = torch.zeros((B * self.n * ld + int(guard),), dtype=torch.float64, device=self.dev)
@@ -758,7 +772,7 @@ class DeviceOrder:
     def transform(self, md, params):
         torch = _torch()
         with torch.cuda.device(self.dev):
-            P = params if torch.is_tensor(params) else to_dev(params, self.dev)
+            P = self._rows(params)
             B = int(P.shape[0])
             flux = empty((B, self.n), self.dev)
             X = empty((B, self.m, self.n), self.dev)

@@ -188,9 +188,7 @@ extern "C" size_t sf_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, 
     if (model_ok(c, mdl) || B <= 0) return 0;
     return carve(c, mdl, B, nullptr, 0, true).bytes;
 }
-// Prologue of every single-order entry point: arguments and workspace size checked, the context's device selected,
-// the workspace carved
-static int open_call(const sf_ctx* c, const sf_model_desc* mdl, int B, void* d_work, size_t have, bool need_C, Work* w) {
+int open_call(const sf_ctx* c, const sf_model_desc* mdl, int B, void* d_work, size_t have, bool need_C, Work* w) {
     if (model_ok(c, mdl)) return SF_EINVAL;
     if (B <= 0 || !d_work) {
         sf_set_error("bad batch size / workspace");
@@ -378,257 +376,4 @@ extern "C" int sf_loglike_batch(sf_ctx* c, const sf_model_desc* mdl, int B, cons
     rc = loglike_factor_finish(w, L, fp, B, w.ltbuf, d_lnl, d_info, s, &c->exec);
     if (rc) return rc;
     return export_logdet_sqmah(d_logdet, d_sqmah, w, B, s);
-}
-
-// ----------------------------------------------------------------------------------- the factor applied to right-hand sides
-static int apply_args_ok(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs) {
-    if (model_ok(c, mdl)) return SF_EINVAL;
-    // (the staging and export launches take one grid row per right-hand side and one grid plane per walker)
-    if (B <= 0 || B > 65535 || nrhs < 1 || nrhs > 65535) {
-        sf_set_error("sf_apply_batch: B=%d and nrhs=%d must lie in 1 .. 65535", B, nrhs);
-        return SF_EINVAL;
-    }
-    return SF_OK;
-}
-extern "C" size_t sf_apply_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs) {
-    if (apply_args_ok(c, mdl, B, nrhs)) return 0;
-    return carve_apply(c, B, nrhs, nullptr, 0, carve(c, mdl, B, nullptr, 0, true).bytes).bytes;
-}
-// transform chain, staging, fill, the likelihood's factorisation and `op` on the staging area, in place.  cov_diag (may be
-// NULL): [B][npad], the diagonal of the filled matrices, copied out before the factorisation overwrites it
-static int apply_staged(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int op, const double* d_rhs, int nrhs,
-                        int ldr, int64_t rhs_stride, double* d_flux, const Work& w, const ApplyWork& aw, hipStream_t s,
-                        double* cov_diag = nullptr) {
-    const Layout L = layout_of(c);
-    int rc;
-    {
-        ProfScope ps(s, PS_TRANSFORM);
-        rc = run_transforms(c, mdl, B, d_params, w, d_flux, nullptr, nullptr, nullptr, true, s);
-        if (rc) return rc;
-    }
-    // (before the factorisation: the residual rides through it and comes out as L^-1 R)
-    rc = sf_launch_apply_stage(d_rhs, ldr, rhs_stride, w.resid, c->n, L.npad, nrhs, B, aw.stage, s);
-    if (rc) return rc;
-    const int fp = sf_potrf_front_pad(c->npad, B);  // (once per call: see sf_loglike_batch)
-    {
-        ProfScope ps(s, PS_FILL);
-        rc = sf_launch_fill(loglike_fill_args(c, mdl, d_params, w, L, fp), B, s);
-        if (rc) return rc;
-    }
-    if (cov_diag) SF_CHECK(sf_launch_diag_copy(w.C, L.npad, L.lda, (int64_t)L.npad * L.lda, B, cov_diag, s));
-    // the likelihood's factorisation and status, as sf_loglike_batch reports it
-    rc = loglike_factor_finish(w, L, fp, B, w.ltbuf, aw.lnl, aw.info, s, &c->exec);
-    if (rc) return rc;
-    const int64_t sstride = (int64_t)nrhs * L.npad;
-    return sf_launch_chol_apply(w.C, L.npad, L.lda, (int64_t)L.npad * L.lda, B, op, aw.stage, nrhs, L.npad, sstride, aw.stage,
-                                L.npad, sstride, s);
-}
-extern "C" int sf_apply_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int op, const double* d_rhs,
-                              int nrhs, int ldr, int64_t rhs_stride, double* d_out, double* d_flux, int* d_info, void* d_work,
-                              size_t work_bytes, void* stream) {
-    int rc = apply_args_ok(c, mdl, B, nrhs);
-    if (rc) return rc;
-    if (!d_params || !d_out || op < SF_APPLY_L || op > SF_APPLY_CINV || (d_rhs ? ldr < c->n || rhs_stride < 0 : nrhs != 1)) {
-        sf_set_error("sf_apply_batch: d_params and d_out are required, op is one of SF_APPLY_*, ldr >= n (%d) and rhs_stride >= 0 "
-                     "with d_rhs, nrhs == 1 without", c->n);
-        return SF_EINVAL;
-    }
-    Work w;
-    rc = open_call(c, mdl, B, d_work, work_bytes, true, &w);
-    if (rc) return rc;
-    const ApplyWork aw = carve_apply(c, B, nrhs, d_work, work_bytes, w.bytes);
-    rc = work_fits(work_bytes, aw.bytes);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    rc = apply_staged(c, mdl, B, d_params, op, d_rhs, nrhs, ldr, rhs_stride, d_flux, w, aw, s);
-    if (rc) return rc;
-    rc = sf_launch_apply_export(aw.stage, aw.info, c->n, c->npad, nrhs, B, d_out, s);
-    if (rc) return rc;
-    if (d_info) SF_HIP(hipMemcpyAsync(d_info, aw.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
-    return SF_OK;
-}
-
-// ----------------------------------------------------------------------------------- the residual split by covariance component
-// (sf_decompose_batch, sf_debug_decompose_matvec)  The checks that need no context come first: B, nrhs, the required
-// pointers and the right-hand-side conventions; then the context and the model; then ldr against the order's n.
-static int decompose_counts_ok(int B, int nrhs) {
-    if (B <= 0 || B > 65535 || nrhs < 1 || nrhs > 65535) {
-        sf_set_error("sf_decompose_batch: B=%d and nrhs=%d must lie in 1 .. 65535", B, nrhs);
-        return SF_EINVAL;
-    }
-    return SF_OK;
-}
-static int decompose_args_ok(const sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const double* d_rhs,
-                             int nrhs, int ldr, int64_t rhs_stride, const double* d_comp) {
-    SF_CHECK(decompose_counts_ok(B, nrhs));
-    if (!d_params || !d_comp || (d_rhs ? rhs_stride < 0 : nrhs != 1)) {
-        sf_set_error("sf_decompose_batch: d_params and d_comp are required, rhs_stride >= 0 with d_rhs, nrhs == 1 without");
-        return SF_EINVAL;
-    }
-    SF_CHECK(model_ok(c, mdl));
-    if (d_rhs && ldr < c->n) {
-        sf_set_error("sf_decompose_batch: ldr=%d < n (%d)", ldr, c->n);
-        return SF_EINVAL;
-    }
-    return SF_OK;
-}
-extern "C" size_t sf_decompose_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs) {
-    if (decompose_counts_ok(B, nrhs) || model_ok(c, mdl)) return 0;
-    return carve_decompose(c, B, nrhs, nullptr, 0, carve(c, mdl, B, nullptr, 0, true).bytes).bytes;
-}
-// the workspace of a call whose arguments passed
-static int open_decompose(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs, void* d_work, size_t work_bytes, Work* w,
-                          DecomposeWork* dw) {
-    SF_CHECK(open_call(c, mdl, B, d_work, work_bytes, true, w));
-    *dw = carve_decompose(c, B, nrhs, d_work, work_bytes, w->bytes);
-    return work_fits(work_bytes, dw->bytes);
-}
-// K_k v for the v in the staging area, with the Y the transform chain left (the factorisation only reads it)
-static int decompose_matvec(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int nrhs, const Work& w,
-                            const DecomposeWork& dw, double* d_comp, hipStream_t s) {
-    return sf_launch_cov_matvec(fill_args(c, mdl, d_params, w), c->m, dw.a.stage, c->npad, nrhs, B, dw.yv, dw.a.info, d_comp, s);
-}
-extern "C" int sf_decompose_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const double* d_rhs,
-                                  int nrhs, int ldr, int64_t rhs_stride, double* d_comp, double* d_alpha, double* d_flux,
-                                  int* d_info, void* d_work, size_t work_bytes, void* stream) {
-    SF_CHECK(decompose_args_ok(c, mdl, B, d_params, d_rhs, nrhs, ldr, rhs_stride, d_comp));
-    Work w;
-    DecomposeWork dw;
-    SF_CHECK(open_decompose(c, mdl, B, nrhs, d_work, work_bytes, &w, &dw));
-    hipStream_t s = (hipStream_t)stream;
-    SF_CHECK(apply_staged(c, mdl, B, d_params, SF_APPLY_CINV, d_rhs, nrhs, ldr, rhs_stride, d_flux, w, dw.a, s));
-    SF_CHECK(decompose_matvec(c, mdl, B, d_params, nrhs, w, dw, d_comp, s));
-    if (d_alpha) SF_CHECK(sf_launch_apply_export(dw.a.stage, dw.a.info, c->n, c->npad, nrhs, B, d_alpha, s));
-    if (d_info) SF_HIP(hipMemcpyAsync(d_info, dw.a.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
-    return SF_OK;
-}
-// The last step of sf_decompose_batch alone, on the workspace a call with the same ctx, model, B, nrhs and d_params left
-// (tools/bench_decompose.py times it)
-extern "C" int sf_debug_decompose_matvec(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int nrhs,
-                                         double* d_comp, void* d_work, size_t work_bytes, void* stream) {
-    SF_CHECK(decompose_counts_ok(B, nrhs));
-    if (!d_params || !d_comp) {
-        sf_set_error("sf_debug_decompose_matvec: d_params and d_comp are required");
-        return SF_EINVAL;
-    }
-    SF_CHECK(model_ok(c, mdl));
-    Work w;
-    DecomposeWork dw;
-    SF_CHECK(open_decompose(c, mdl, B, nrhs, d_work, work_bytes, &w, &dw));
-    return decompose_matvec(c, mdl, B, d_params, nrhs, w, dw, d_comp, (hipStream_t)stream);
-}
-
-// ----------------------------------------------------------------------------------- per-pixel leave-one-out diagnostics
-// (sf_pointwise_batch)  The checks that need no context come first, as for sf_decompose_batch.
-static int pointwise_counts_ok(int B, int nrhs) {
-    if (B <= 0 || B > 65535 || nrhs < 1 || nrhs > 65535) {
-        sf_set_error("sf_pointwise_batch: B=%d and nrhs=%d must lie in 1 .. 65535", B, nrhs);
-        return SF_EINVAL;
-    }
-    return SF_OK;
-}
-extern "C" size_t sf_pointwise_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs) {
-    if (pointwise_counts_ok(B, nrhs) || model_ok(c, mdl)) return 0;
-    return carve_pointwise(c, B, nrhs, nullptr, 0, carve(c, mdl, B, nullptr, 0, true).bytes).bytes;
-}
-extern "C" int sf_pointwise_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const double* d_rhs,
-                                  int nrhs, int ldr, int64_t rhs_stride, double* d_alpha, double* d_cinv_diag,
-                                  double* d_cov_diag, double* d_flux, int* d_info, void* d_work, size_t work_bytes,
-                                  void* stream) {
-    SF_CHECK(pointwise_counts_ok(B, nrhs));
-    if (!d_params || !d_alpha || !d_cinv_diag || (d_rhs ? rhs_stride < 0 : nrhs != 1)) {
-        sf_set_error("sf_pointwise_batch: d_params, d_alpha and d_cinv_diag are required, rhs_stride >= 0 with d_rhs, nrhs == 1 "
-                     "without");
-        return SF_EINVAL;
-    }
-    SF_CHECK(model_ok(c, mdl));
-    if (d_rhs && ldr < c->n) {
-        sf_set_error("sf_pointwise_batch: ldr=%d < n (%d)", ldr, c->n);
-        return SF_EINVAL;
-    }
-    Work w;
-    SF_CHECK(open_call(c, mdl, B, d_work, work_bytes, true, &w));
-    const PointwiseWork pw = carve_pointwise(c, B, nrhs, d_work, work_bytes, w.bytes);
-    SF_CHECK(work_fits(work_bytes, pw.bytes));
-    hipStream_t s = (hipStream_t)stream;
-    const Layout L = layout_of(c);
-    SF_CHECK(apply_staged(c, mdl, B, d_params, SF_APPLY_CINV, d_rhs, nrhs, ldr, rhs_stride, d_flux, w, pw.a, s,
-                          d_cov_diag ? pw.cov_diag : nullptr));
-    // (the factor applied first: the inverse's launch takes the strict upper triangle of the matrices as scratch)
-    SF_CHECK(sf_launch_chol_inverse_diag(w.C, L.npad, L.lda, (int64_t)L.npad * L.lda, B, pw.winv, pw.cinv_diag, L.npad, s));
-    SF_CHECK(sf_launch_apply_export(pw.a.stage, pw.a.info, c->n, c->npad, nrhs, B, d_alpha, s));
-    SF_CHECK(sf_launch_apply_export(pw.cinv_diag, pw.a.info, c->n, c->npad, 1, B, d_cinv_diag, s));
-    if (d_cov_diag) SF_CHECK(sf_launch_apply_export(pw.cov_diag, pw.a.info, c->n, c->npad, 1, B, d_cov_diag, s));
-    if (d_info) SF_HIP(hipMemcpyAsync(d_info, pw.a.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
-    return SF_OK;
-}
-
-// ----------------------------------------------------------------------------------- gradient in the covariance hyper-parameters
-// (sf_loglike_grad_batch, sf_debug_loglike_grad_contract)  The checks that need no context come first, as for
-// sf_pointwise_batch.
-static int grad_args_ok(const sf_model_desc* mdl, int B, bool have_pointers, int grad_stride) {
-    if (B <= 0 || B > 65535) {
-        sf_set_error("sf_loglike_grad_batch: B=%d must lie in 1 .. 65535", B);
-        return SF_EINVAL;
-    }
-    if (!have_pointers) {
-        sf_set_error("sf_loglike_grad_batch: d_params, d_lnl and d_grad are required");
-        return SF_EINVAL;
-    }
-    if (!mdl || mdl->n_local < 0 || mdl->n_local > SF_MAX_LOCAL) return SF_OK;  // (model_ok refuses it next)
-    const int slots = sf_cov_grad_slots(mdl->has_global, mdl->n_local);
-    if (slots == 0) {
-        sf_set_error("sf_loglike_grad_batch: nothing to differentiate (no global and no local kernel)");
-        return SF_EINVAL;
-    }
-    if (grad_stride < slots) {
-        sf_set_error("sf_loglike_grad_batch: grad_stride=%d < %d slots", grad_stride, slots);
-        return SF_EINVAL;
-    }
-    return SF_OK;
-}
-extern "C" size_t sf_loglike_grad_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B) {
-    if (B <= 0 || B > 65535 || model_ok(c, mdl) || sf_cov_grad_slots(mdl->has_global, mdl->n_local) == 0) return 0;
-    return carve_grad(c, mdl, B, nullptr, 0, carve(c, mdl, B, nullptr, 0, true).bytes).bytes;
-}
-// the workspace of a call whose arguments passed
-static int open_grad(const sf_ctx* c, const sf_model_desc* mdl, int B, void* d_work, size_t work_bytes, Work* w, GradWork* gw) {
-    SF_CHECK(model_ok(c, mdl));
-    SF_CHECK(open_call(c, mdl, B, d_work, work_bytes, true, w));
-    *gw = carve_grad(c, mdl, B, d_work, work_bytes, w->bytes);
-    return work_fits(work_bytes, gw->bytes);
-}
-// 1/2 sum (alpha alpha^T - C^-1) o dC/dtheta from the alpha in the staging area and the X the inverse's launch left in the matrices
-static int grad_contract(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const Work& w, const GradWork& gw,
-                         double* d_grad, int grad_stride, hipStream_t s) {
-    sf_fill_args f = fill_args(c, mdl, d_params, w);
-    f.C = w.C, f.lda = w.L.lda, f.stride = (int64_t)w.L.npad * w.L.lda, f.lower_only = 1, f.add_jitter = 1;
-    return sf_launch_cov_grad(f, B, gw.winv, gw.a.stage, w.L.npad, gw.a.info, gw.part, d_grad, grad_stride, s);
-}
-extern "C" int sf_loglike_grad_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, double* d_lnl,
-                                     double* d_grad, int grad_stride, double* d_flux, int* d_info, void* d_work,
-                                     size_t work_bytes, void* stream) {
-    SF_CHECK(grad_args_ok(mdl, B, d_params && d_lnl && d_grad, grad_stride));
-    Work w;
-    GradWork gw;
-    SF_CHECK(open_grad(c, mdl, B, d_work, work_bytes, &w, &gw));
-    hipStream_t s = (hipStream_t)stream;
-    const Layout L = layout_of(c);
-    SF_CHECK(apply_staged(c, mdl, B, d_params, SF_APPLY_CINV, nullptr, 1, c->n, 0, d_flux, w, gw.a, s));
-    // (the factor applied first: the inverse's launch takes the strict upper triangle of the matrices as scratch)
-    SF_CHECK(sf_launch_chol_inverse_diag(w.C, L.npad, L.lda, (int64_t)L.npad * L.lda, B, gw.winv, gw.cinv_diag, L.npad, s));
-    SF_CHECK(grad_contract(c, mdl, B, d_params, w, gw, d_grad, grad_stride, s));
-    SF_HIP(hipMemcpyAsync(d_lnl, gw.a.lnl, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, s));
-    if (d_info) SF_HIP(hipMemcpyAsync(d_info, gw.a.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
-    return SF_OK;
-}
-// The contraction launches of sf_loglike_grad_batch alone, on the workspace a call with the same ctx, model, B and d_params
-// left (tools/bench_gradient.py times them)
-extern "C" int sf_debug_loglike_grad_contract(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, double* d_grad,
-                                              int grad_stride, void* d_work, size_t work_bytes, void* stream) {
-    SF_CHECK(grad_args_ok(mdl, B, d_params && d_grad, grad_stride));  // (no d_lnl here)
-    Work w;
-    GradWork gw;
-    SF_CHECK(open_grad(c, mdl, B, d_work, work_bytes, &w, &gw));
-    return grad_contract(c, mdl, B, d_params, w, gw, d_grad, grad_stride, (hipStream_t)stream);
 }

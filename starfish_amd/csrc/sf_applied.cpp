@@ -1,0 +1,240 @@
+// C-ABI host layer: the calls that run the likelihood's sequence and then work on the Cholesky factor (sf_apply_batch,
+// sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch and the two timing aids).  One description per call, one
+// argument check, one workspace layout (carve_applied) and one way to open a call.
+#include "sf_stages.h"
+
+struct AppliedCall {
+    const char* name;      // the entry point, as its messages start
+    const char* required;  // the pointers that must not be NULL, as the message names them
+    unsigned parts;        // of the workspace behind the staging area (AppliedParts)
+    bool rhs;              // takes right-hand sides (d_rhs, ldr, rhs_stride); false: nothing but the walker's own residual
+    bool op;               // takes one of SF_APPLY_*
+};
+static const AppliedCall APPLY = {"sf_apply_batch", "d_params and d_out", 0, true, true};
+static const AppliedCall DECOMPOSE = {"sf_decompose_batch", "d_params and d_comp", AW_YV, true, false};
+static const AppliedCall DECOMPOSE_MATVEC = {"sf_debug_decompose_matvec", "d_params and d_comp", AW_YV, false, false};
+static const AppliedCall POINTWISE = {"sf_pointwise_batch", "d_params, d_alpha and d_cinv_diag", AW_COV_DIAG | AW_INVERSE, true,
+                                      false};
+static const AppliedCall GRAD = {"sf_loglike_grad_batch", "d_params, d_lnl and d_grad", AW_INVERSE | AW_PART, false, false};
+static const AppliedCall GRAD_CONTRACT = {"sf_debug_loglike_grad_contract", "d_params and d_grad", AW_INVERSE | AW_PART, false,
+                                          false};
+// what a call was handed, as far as the check looks at it
+struct AppliedArgs {
+    int B, nrhs;
+    bool required;  // every required pointer is there
+    int op = SF_APPLY_CINV;
+    const double* d_rhs = nullptr;
+    int ldr = 0;
+    int64_t rhs_stride = 0;
+    int grad_stride = 0;
+};
+
+// (the staging and export launches take one grid row per right-hand side and one grid plane per walker)
+static int counts_ok(const AppliedCall& k, int B, int nrhs) {
+    if (B <= 0 || B > 65535 || nrhs < 1 || nrhs > 65535) {
+        sf_set_error("%s: B=%d and nrhs=%d must lie in 1 .. 65535", k.name, B, nrhs);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+// the gradient's own: something to differentiate, and rows that hold it
+static int grad_slots_ok(const AppliedCall& k, const sf_model_desc* mdl, int grad_stride) {
+    if (!mdl || mdl->n_local < 0 || mdl->n_local > SF_MAX_LOCAL) return SF_OK;  // (model_ok refuses it next)
+    const int slots = sf_cov_grad_slots(mdl->has_global, mdl->n_local);
+    if (slots == 0) {
+        sf_set_error("%s: nothing to differentiate (no global and no local kernel)", k.name);
+        return SF_EINVAL;
+    }
+    if (grad_stride < slots) {
+        sf_set_error("%s: grad_stride=%d < %d slots", k.name, grad_stride, slots);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+// The checks that need no context come first: the counts, the required pointers, op and the right-hand-side conventions;
+// then the context and the model; then ldr against the order's n.
+static int args_ok(const AppliedCall& k, const sf_ctx* c, const sf_model_desc* mdl, const AppliedArgs& a) {
+    SF_CHECK(counts_ok(k, a.B, a.nrhs));
+    if (!a.required) {
+        sf_set_error("%s: %s are required", k.name, k.required);
+        return SF_EINVAL;
+    }
+    if (k.op && (a.op < SF_APPLY_L || a.op > SF_APPLY_CINV)) {
+        sf_set_error("%s: op=%d is none of SF_APPLY_*", k.name, a.op);
+        return SF_EINVAL;
+    }
+    if (k.rhs && (a.d_rhs ? a.rhs_stride < 0 : a.nrhs != 1)) {
+        sf_set_error("%s: rhs_stride >= 0 with d_rhs, nrhs == 1 without", k.name);
+        return SF_EINVAL;
+    }
+    if (k.parts & AW_PART) SF_CHECK(grad_slots_ok(k, mdl, a.grad_stride));
+    SF_CHECK(model_ok(c, mdl));
+    if (k.rhs && a.d_rhs && a.ldr < c->n) {
+        sf_set_error("%s: ldr=%d < n (%d)", k.name, a.ldr, c->n);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+static size_t workspace_bytes(const AppliedCall& k, const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs) {
+    if (counts_ok(k, B, nrhs) || model_ok(c, mdl)) return 0;
+    if ((k.parts & AW_PART) && sf_cov_grad_slots(mdl->has_global, mdl->n_local) == 0) return 0;
+    return carve_applied(c, mdl, B, nrhs, k.parts, nullptr, 0, carve(c, mdl, B, nullptr, 0, true).bytes).bytes;
+}
+// the arguments checked, then the workspace of the call
+static int open_applied(const AppliedCall& k, const sf_ctx* c, const sf_model_desc* mdl, const AppliedArgs& a, void* d_work,
+                        size_t work_bytes, Work* w, AppliedWork* aw) {
+    SF_CHECK(args_ok(k, c, mdl, a));
+    SF_CHECK(open_call(c, mdl, a.B, d_work, work_bytes, true, w));
+    *aw = carve_applied(c, mdl, a.B, a.nrhs, k.parts, d_work, work_bytes, w->bytes);
+    return work_fits(work_bytes, aw->bytes);
+}
+static int export_status(int* d_info, const AppliedWork& aw, int B, hipStream_t s) {
+    if (d_info) SF_HIP(hipMemcpyAsync(d_info, aw.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return SF_OK;
+}
+
+// transform chain, staging, fill, the likelihood's factorisation and `op` on the staging area, in place.  cov_diag (may be
+// NULL): [B][npad], the diagonal of the filled matrices, copied out before the factorisation overwrites it
+static int apply_staged(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int op, const double* d_rhs, int nrhs,
+                        int ldr, int64_t rhs_stride, double* d_flux, const Work& w, const AppliedWork& aw, hipStream_t s,
+                        double* cov_diag = nullptr) {
+    const Layout L = layout_of(c);
+    int rc;
+    {
+        ProfScope ps(s, PS_TRANSFORM);
+        rc = run_transforms(c, mdl, B, d_params, w, d_flux, nullptr, nullptr, nullptr, true, s);
+        if (rc) return rc;
+    }
+    // (before the factorisation: the residual rides through it and comes out as L^-1 R)
+    rc = sf_launch_apply_stage(d_rhs, ldr, rhs_stride, w.resid, c->n, L.npad, nrhs, B, aw.stage, s);
+    if (rc) return rc;
+    const int fp = sf_potrf_front_pad(c->npad, B);  // (once per call: see sf_loglike_batch)
+    {
+        ProfScope ps(s, PS_FILL);
+        rc = sf_launch_fill(loglike_fill_args(c, mdl, d_params, w, L, fp), B, s);
+        if (rc) return rc;
+    }
+    if (cov_diag) SF_CHECK(sf_launch_diag_copy(w.C, L.npad, L.lda, (int64_t)L.npad * L.lda, B, cov_diag, s));
+    // the likelihood's factorisation and status, as sf_loglike_batch reports it
+    rc = loglike_factor_finish(w, L, fp, B, w.ltbuf, aw.lnl, aw.info, s, &c->exec);
+    if (rc) return rc;
+    const int64_t sstride = (int64_t)nrhs * L.npad;
+    return sf_launch_chol_apply(w.C, L.npad, L.lda, (int64_t)L.npad * L.lda, B, op, aw.stage, nrhs, L.npad, sstride, aw.stage,
+                                L.npad, sstride, s);
+}
+// alpha = C^-1 rhs in the staging area, then the inverse: its diagonal in aw.cinv_diag, X in the matrices.  (The factor is
+// applied first: the inverse's launch takes the strict upper triangle of the matrices as scratch.)
+static int apply_cinv_and_invert(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const double* d_rhs, int nrhs,
+                                 int ldr, int64_t rhs_stride, double* d_flux, const Work& w, const AppliedWork& aw, hipStream_t s,
+                                 double* cov_diag = nullptr) {
+    const Layout L = layout_of(c);
+    SF_CHECK(apply_staged(c, mdl, B, d_params, SF_APPLY_CINV, d_rhs, nrhs, ldr, rhs_stride, d_flux, w, aw, s, cov_diag));
+    return sf_launch_chol_inverse_diag(w.C, L.npad, L.lda, (int64_t)L.npad * L.lda, B, aw.winv, aw.cinv_diag, L.npad, s);
+}
+
+// ----------------------------------------------------------------------------------- the factor applied to right-hand sides
+extern "C" size_t sf_apply_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs) {
+    return workspace_bytes(APPLY, c, mdl, B, nrhs);
+}
+extern "C" int sf_apply_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int op, const double* d_rhs,
+                              int nrhs, int ldr, int64_t rhs_stride, double* d_out, double* d_flux, int* d_info, void* d_work,
+                              size_t work_bytes, void* stream) {
+    Work w;
+    AppliedWork aw;
+    SF_CHECK(open_applied(APPLY, c, mdl, {B, nrhs, d_params && d_out, op, d_rhs, ldr, rhs_stride}, d_work, work_bytes, &w, &aw));
+    hipStream_t s = (hipStream_t)stream;
+    SF_CHECK(apply_staged(c, mdl, B, d_params, op, d_rhs, nrhs, ldr, rhs_stride, d_flux, w, aw, s));
+    SF_CHECK(sf_launch_apply_export(aw.stage, aw.info, c->n, c->npad, nrhs, B, d_out, s));
+    return export_status(d_info, aw, B, s);
+}
+
+// ----------------------------------------------------------------------------------- the residual split by covariance component
+extern "C" size_t sf_decompose_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs) {
+    return workspace_bytes(DECOMPOSE, c, mdl, B, nrhs);
+}
+// K_k v for the v in the staging area, with the Y the transform chain left (the factorisation only reads it)
+static int decompose_matvec(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int nrhs, const Work& w,
+                            const AppliedWork& aw, double* d_comp, hipStream_t s) {
+    return sf_launch_cov_matvec(fill_args(c, mdl, d_params, w), c->m, aw.stage, c->npad, nrhs, B, aw.yv, aw.info, d_comp, s);
+}
+extern "C" int sf_decompose_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const double* d_rhs,
+                                  int nrhs, int ldr, int64_t rhs_stride, double* d_comp, double* d_alpha, double* d_flux,
+                                  int* d_info, void* d_work, size_t work_bytes, void* stream) {
+    Work w;
+    AppliedWork aw;
+    SF_CHECK(open_applied(DECOMPOSE, c, mdl, {B, nrhs, d_params && d_comp, SF_APPLY_CINV, d_rhs, ldr, rhs_stride}, d_work,
+                          work_bytes, &w, &aw));
+    hipStream_t s = (hipStream_t)stream;
+    SF_CHECK(apply_staged(c, mdl, B, d_params, SF_APPLY_CINV, d_rhs, nrhs, ldr, rhs_stride, d_flux, w, aw, s));
+    SF_CHECK(decompose_matvec(c, mdl, B, d_params, nrhs, w, aw, d_comp, s));
+    if (d_alpha) SF_CHECK(sf_launch_apply_export(aw.stage, aw.info, c->n, c->npad, nrhs, B, d_alpha, s));
+    return export_status(d_info, aw, B, s);
+}
+// The last step of sf_decompose_batch alone, on the workspace a call with the same ctx, model, B, nrhs and d_params left
+// (tools/bench_decompose.py times it)
+extern "C" int sf_debug_decompose_matvec(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int nrhs,
+                                         double* d_comp, void* d_work, size_t work_bytes, void* stream) {
+    Work w;
+    AppliedWork aw;
+    SF_CHECK(open_applied(DECOMPOSE_MATVEC, c, mdl, {B, nrhs, d_params && d_comp}, d_work, work_bytes, &w, &aw));
+    return decompose_matvec(c, mdl, B, d_params, nrhs, w, aw, d_comp, (hipStream_t)stream);
+}
+
+// ----------------------------------------------------------------------------------- per-pixel leave-one-out diagnostics
+extern "C" size_t sf_pointwise_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs) {
+    return workspace_bytes(POINTWISE, c, mdl, B, nrhs);
+}
+extern "C" int sf_pointwise_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const double* d_rhs,
+                                  int nrhs, int ldr, int64_t rhs_stride, double* d_alpha, double* d_cinv_diag,
+                                  double* d_cov_diag, double* d_flux, int* d_info, void* d_work, size_t work_bytes,
+                                  void* stream) {
+    Work w;
+    AppliedWork aw;
+    SF_CHECK(open_applied(POINTWISE, c, mdl, {B, nrhs, d_params && d_alpha && d_cinv_diag, SF_APPLY_CINV, d_rhs, ldr, rhs_stride},
+                          d_work, work_bytes, &w, &aw));
+    hipStream_t s = (hipStream_t)stream;
+    SF_CHECK(apply_cinv_and_invert(c, mdl, B, d_params, d_rhs, nrhs, ldr, rhs_stride, d_flux, w, aw, s,
+                                   d_cov_diag ? aw.cov_diag : nullptr));
+    SF_CHECK(sf_launch_apply_export(aw.stage, aw.info, c->n, c->npad, nrhs, B, d_alpha, s));
+    SF_CHECK(sf_launch_apply_export(aw.cinv_diag, aw.info, c->n, c->npad, 1, B, d_cinv_diag, s));
+    if (d_cov_diag) SF_CHECK(sf_launch_apply_export(aw.cov_diag, aw.info, c->n, c->npad, 1, B, d_cov_diag, s));
+    return export_status(d_info, aw, B, s);
+}
+
+// ----------------------------------------------------------------------------------- gradient in the covariance hyper-parameters
+extern "C" size_t sf_loglike_grad_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B) {
+    return workspace_bytes(GRAD, c, mdl, B, 1);
+}
+// 1/2 sum (alpha alpha^T - C^-1) o dC/dtheta from the alpha in the staging area and the X the inverse's launch left in the matrices
+static int grad_contract(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const Work& w, const AppliedWork& aw,
+                         double* d_grad, int grad_stride, hipStream_t s) {
+    sf_fill_args f = fill_args(c, mdl, d_params, w);
+    f.C = w.C, f.lda = w.L.lda, f.stride = (int64_t)w.L.npad * w.L.lda, f.lower_only = 1, f.add_jitter = 1;
+    return sf_launch_cov_grad(f, B, aw.winv, aw.stage, w.L.npad, aw.info, aw.part, d_grad, grad_stride, s);
+}
+static AppliedArgs grad_args(int B, bool required, int grad_stride) {
+    AppliedArgs a = {B, 1, required};
+    a.grad_stride = grad_stride;
+    return a;
+}
+extern "C" int sf_loglike_grad_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, double* d_lnl,
+                                     double* d_grad, int grad_stride, double* d_flux, int* d_info, void* d_work,
+                                     size_t work_bytes, void* stream) {
+    Work w;
+    AppliedWork aw;
+    SF_CHECK(open_applied(GRAD, c, mdl, grad_args(B, d_params && d_lnl && d_grad, grad_stride), d_work, work_bytes, &w, &aw));
+    hipStream_t s = (hipStream_t)stream;
+    SF_CHECK(apply_cinv_and_invert(c, mdl, B, d_params, nullptr, 1, c->n, 0, d_flux, w, aw, s));
+    SF_CHECK(grad_contract(c, mdl, B, d_params, w, aw, d_grad, grad_stride, s));
+    SF_HIP(hipMemcpyAsync(d_lnl, aw.lnl, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return export_status(d_info, aw, B, s);
+}
+// The contraction launches of sf_loglike_grad_batch alone, on the workspace a call with the same ctx, model, B and d_params
+// left (tools/bench_gradient.py times them)
+extern "C" int sf_debug_loglike_grad_contract(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, double* d_grad,
+                                              int grad_stride, void* d_work, size_t work_bytes, void* stream) {
+    Work w;
+    AppliedWork aw;
+    SF_CHECK(open_applied(GRAD_CONTRACT, c, mdl, grad_args(B, d_params && d_grad, grad_stride), d_work, work_bytes, &w, &aw));
+    return grad_contract(c, mdl, B, d_params, w, aw, d_grad, grad_stride, (hipStream_t)stream);
+}

@@ -246,7 +246,7 @@ extern "C" int sf_potri_diag_batch(double* d_L, int n, int lda, int64_t stride, 
 
 extern "C" size_t sf_potri_blocks_workspace_bytes(int n, int batch) {
     if (n <= 0 || n % SF_LEAF != 0 || batch <= 0) return 0;
-    return carve_potri_blocks(n, batch, nullptr, 0).bytes;
+    return carve_potri(n, batch, nullptr, 0, true).bytes;
 }
 extern "C" int sf_potri_blocks_batch(double* d_L, int n, int lda, int64_t stride, int batch, const int* d_pairs, int npairs,
                                      double* d_out, void* d_work, size_t work_bytes, void* stream) {
@@ -259,7 +259,7 @@ extern "C" int sf_potri_blocks_batch(double* d_L, int n, int lda, int64_t stride
                      SF_LEAF, lda, batch, npairs);
         return SF_EINVAL;
     }
-    const PotriBlocksWork w = carve_potri_blocks(n, batch, d_work, work_bytes);
+    const PotriWork w = carve_potri(n, batch, d_work, work_bytes, true);
     if (work_bytes < w.bytes) {
         sf_set_error("sf_potri_blocks_batch: workspace too small: have %zu, need %zu", work_bytes, w.bytes);
         return SF_EINVAL;

@@ -1,9 +1,13 @@
-// Stages of the likelihood that the single-order, multi-order and banded sequences share (internal; sf_abi.cpp).
+// Stages of the likelihood that the single-order, multi-order, banded and factor-applied sequences share (internal;
+// sf_abi.cpp).
 #pragma once
 #include "sf_prof.h"
 #include "sf_work.h"
 
 #pragma GCC visibility push(hidden)
+// Prologue of every single-order entry point: arguments and workspace size checked, the context's device selected,
+// the workspace carved
+int open_call(const sf_ctx* c, const sf_model_desc* mdl, int B, void* d_work, size_t have, bool need_C, Work* w);
 // emulator + transform chain -> unscaled X / flux, scale, then residual / Y
 int run_transforms(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const Work& w, double* d_flux_out,
                    double* d_X_out, double* d_resid_out, double* d_log_scale, bool want_Y, hipStream_t s);

@@ -1,5 +1,6 @@
 // Workspace layouts of the C-ABI (internal): every caller-provided workspace is carved by ONE function, which the size
-// query runs on a null base and the entry point on the caller's pointer.
+// query runs on a null base and the entry point on the caller's pointer.  (A layout that lies behind the Work of the same
+// call is carved by one function too: it starts its Carve at the Work's size.)
 #pragma once
 #include <type_traits>
 
@@ -7,8 +8,8 @@
 
 struct Carve {
     char* base;
-    size_t off = 0, cap;
-    Carve(void* p, size_t bytes) : base((char*)p), cap(bytes) {}
+    size_t off, cap;
+    Carve(void* p, size_t bytes, size_t start = 0) : base((char*)p), off(start), cap(bytes) {}
     template <typename T>
     T* take(size_t count) {
         off = sf_align_up(off, 256);
@@ -135,8 +136,7 @@ struct BandWork {
     size_t bytes;
 };
 static BandWork carve_band(const sf_ctx* c, int B, int halfwidth, void* p, size_t cap, size_t base_bytes) {
-    Carve k(p, cap);
-    k.off = base_bytes;
+    Carve k(p, cap, base_bytes);
     BandWork w;
     // Half-widths beyond the LDS window are factorised as bordered band matrices on the tile kernels of the dense
     // path (sf_launch_potrf_band); the band fill writes those tiles directly.
@@ -153,104 +153,52 @@ static BandWork carve_band(const sf_ctx* c, int B, int halfwidth, void* p, size_
 }
 
 // ------------------------------------------------------------------- the factor applied to right-hand sides
-// (sf_apply_batch; behind the Work of the same call: base_bytes = its size)  The staging area holds the right-hand sides
-// padded to npad rows; the factor is applied to it in place.  lnl / info: what the likelihood's last step leaves.
-struct ApplyWork {
+// (sf_apply_batch, sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch; behind the Work of the same call:
+// base_bytes = its size)  Every call has the staging area -- the right-hand sides padded to npad rows, the factor is applied
+// to it in place (for all but sf_apply_batch it ends up holding alpha = C^-1 rhs) -- and lnl / info, what the likelihood's
+// last step leaves.  Then, in this order, the parts the call asks for:
+//   AW_YV        yv: t = Y alpha, m doubles per right-hand side (sf_decompose_batch)
+//   AW_COV_DIAG  cov_diag: the diagonal of the matrix that is factorised, npad doubles per walker (sf_pointwise_batch)
+//   AW_INVERSE   cinv_diag: the diagonal of the inverse, npad doubles per walker (the inverse's launch writes it; the
+//                gradient does not read it), and winv: the scratch of that launch (carve_potri)
+//   AW_PART      part: the gradient's partial sums per (walker, block row, slot)
+enum AppliedParts { AW_YV = 1, AW_COV_DIAG = 2, AW_INVERSE = 4, AW_PART = 8 };
+struct AppliedWork {
     double *stage, *lnl;
     int* info;
+    double *yv, *cov_diag, *cinv_diag, *winv, *part;
     size_t bytes;
 };
-static ApplyWork carve_apply(const sf_ctx* c, int B, int nrhs, void* p, size_t cap, size_t base_bytes) {
-    Carve k(p, cap);
-    k.off = base_bytes;
-    ApplyWork w;
+static AppliedWork carve_applied(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs, unsigned parts, void* p, size_t cap,
+                                 size_t base_bytes) {
+    Carve k(p, cap, base_bytes);
+    AppliedWork w{};
     w.stage = k.take<double>((size_t)B * nrhs * c->npad);
     w.lnl = k.take<double>((size_t)B);
     w.info = k.take<int>((size_t)B);
-    w.bytes = sf_align_up(k.off, 256);
-    return w;
-}
-
-// sf_decompose_batch: the layout of sf_apply_batch (the staging area ends up holding alpha = C^-1 rhs), then t = Y alpha,
-// m doubles per right-hand side
-struct DecomposeWork {
-    ApplyWork a;
-    double* yv;
-    size_t bytes;
-};
-static DecomposeWork carve_decompose(const sf_ctx* c, int B, int nrhs, void* p, size_t cap, size_t base_bytes) {
-    DecomposeWork w;
-    w.a = carve_apply(c, B, nrhs, p, cap, base_bytes);
-    Carve k(p, cap);
-    k.off = w.a.bytes;
-    w.yv = k.take<double>((size_t)B * nrhs * c->m);
-    w.bytes = sf_align_up(k.off, 256);
-    return w;
-}
-
-// sf_pointwise_batch: the layout of sf_apply_batch (the staging area ends up holding alpha = C^-1 rhs), then the diagonal
-// of the matrix that is factorised and the diagonal of its inverse, npad doubles per walker each, then the scratch of the
-// inverse's launch (carve_potri)
-struct PointwiseWork {
-    ApplyWork a;
-    double *cov_diag, *cinv_diag, *winv;
-    size_t bytes;
-};
-static PointwiseWork carve_pointwise(const sf_ctx* c, int B, int nrhs, void* p, size_t cap, size_t base_bytes) {
-    PointwiseWork w;
-    w.a = carve_apply(c, B, nrhs, p, cap, base_bytes);
-    Carve k(p, cap);
-    k.off = w.a.bytes;
-    w.cov_diag = k.take<double>((size_t)B * c->npad);
-    w.cinv_diag = k.take<double>((size_t)B * c->npad);
-    w.winv = k.take<double>(sf_chol_inverse_work_doubles(c->npad, B));
-    w.bytes = sf_align_up(k.off, 256);
-    return w;
-}
-
-// sf_loglike_grad_batch: the layout of sf_apply_batch with one right-hand side (the staging area ends up holding alpha =
-// C^-1 r), then the diagonal of the inverse (npad doubles per walker: the inverse's launch writes it, nothing reads it), the
-// scratch of that launch (carve_potri) and the contraction's partial sums per (walker, block row, slot)
-struct GradWork {
-    ApplyWork a;
-    double *cinv_diag, *winv, *part;
-    size_t bytes;
-};
-static GradWork carve_grad(const sf_ctx* c, const sf_model_desc* mdl, int B, void* p, size_t cap, size_t base_bytes) {
-    GradWork w;
-    w.a = carve_apply(c, B, 1, p, cap, base_bytes);
-    Carve k(p, cap);
-    k.off = w.a.bytes;
-    w.cinv_diag = k.take<double>((size_t)B * c->npad);
-    w.winv = k.take<double>(sf_chol_inverse_work_doubles(c->npad, B));
-    w.part = k.take<double>(sf_cov_grad_work_doubles(c->n, mdl->has_global, mdl->n_local, B));
+    if (parts & AW_YV) w.yv = k.take<double>((size_t)B * nrhs * c->m);
+    if (parts & AW_COV_DIAG) w.cov_diag = k.take<double>((size_t)B * c->npad);
+    if (parts & AW_INVERSE) {
+        w.cinv_diag = k.take<double>((size_t)B * c->npad);
+        w.winv = k.take<double>(sf_chol_inverse_work_doubles(c->npad, B));
+    }
+    if (parts & AW_PART) w.part = k.take<double>(sf_cov_grad_work_doubles(c->n, mdl->has_global, mdl->n_local, B));
     w.bytes = sf_align_up(k.off, 256);
     return w;
 }
 
 // ------------------------------------------------------------------- context-free workspaces
-// sf_potri_diag_batch: the transposed inverses of the 64 x 64 diagonal blocks, [batch][n / 64][64][64]
+// sf_potri_diag_batch: the transposed inverses of the 64 x 64 diagonal blocks, [batch][n / 64][64][64]; sf_potri_blocks_batch
+// (with_diag): the same, then the diagonal of the inverse ([batch][n]: the inverse's launch writes it)
 struct PotriWork {
-    double* winv;
-    size_t bytes;
-};
-static PotriWork carve_potri(int n, int batch, void* p, size_t cap) {
-    Carve k(p, cap);
-    PotriWork w;
-    w.winv = k.take<double>(sf_chol_inverse_work_doubles(n, batch));
-    w.bytes = sf_align_up(k.off, 256);
-    return w;
-}
-// sf_potri_blocks_batch: the same, then the diagonal of the inverse ([batch][n]: the inverse's launch writes it)
-struct PotriBlocksWork {
     double *winv, *diag;
     size_t bytes;
 };
-static PotriBlocksWork carve_potri_blocks(int n, int batch, void* p, size_t cap) {
+static PotriWork carve_potri(int n, int batch, void* p, size_t cap, bool with_diag = false) {
     Carve k(p, cap);
-    PotriBlocksWork w;
+    PotriWork w{};
     w.winv = k.take<double>(sf_chol_inverse_work_doubles(n, batch));
-    w.diag = k.take<double>((size_t)n * batch);
+    if (with_diag) w.diag = k.take<double>((size_t)n * batch);
     w.bytes = sf_align_up(k.off, 256);
     return w;
 }

@@ -474,16 +474,27 @@ class SpectrumModel:
             raise ValueError(f"{what} of shape {r.shape}: expected ({len(self.data.wave)},) or (k, {len(self.data.wave)})")
         return np.atleast_2d(r), r.ndim == 1
 
+    def _diagnose(self, call, P, rhs, *args, **kwargs):
+        """``DeviceOrder.<call>`` on the rows of ``P`` (None: the model's own state, one walker) and the right-hand sides
+        ``rhs``, with whatever else the call takes: its result, the model descriptor, ``rhs`` as handed to the device and
+        whether every walker has one vector.  No cache is updated."""
+        if rhs is None:
+            single = True
+        else:
+            rhs, single = self._rhs_block(rhs) if P is None else self._batch_rhs(P, rhs)
+        dev, md, rows = self._pack(P, update_caches=False)
+        return getattr(dev, call)(md, rows, *args, rhs=rhs, **kwargs), md, rhs, single
+
+    def _own(self, out):
+        """The first walker of a device result, or what :meth:`log_likelihood` raises for its status."""
+        self._raise_for_info(out["info"][0])
+        return {key: v[0] for key, v in out.items()}
+
     def _apply_factor(self, op, rhs, want_flux=False):
         """``op`` of :meth:`apply_factor_batch` for the current parameters; raises as :meth:`log_likelihood` does."""
-        single = True
-        if rhs is not None:
-            rhs, single = self._rhs_block(rhs)
-        dev, md, rows = self._pack(update_caches=False)
-        out = dev.apply(md, rows, op, rhs=rhs, want_flux=want_flux)
-        self._raise_for_info(out["info"][0])
-        res = out["out"][0]
-        return (res[0] if single else res), (out["flux"][0] if want_flux else None)
+        out, _, _, single = self._diagnose("apply", None, rhs, op, want_flux=want_flux)
+        out = self._own(out)
+        return (out["out"][0] if single else out["out"]), (out["flux"] if want_flux else None)
 
     def cho_solve(self, rhs=None):
         """``C^-1 rhs`` for the covariance of the current parameters, jitter included (the reference's
@@ -515,18 +526,13 @@ class SpectrumModel:
         ``info`` the codes of :meth:`log_likelihood_batch`.  The model's own state is not modified."""
         if op not in D.APPLY_OPS:
             raise ValueError(f"op must be one of {sorted(D.APPLY_OPS)}")
-        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
-        rhs, single = self._batch_rhs(P, rhs)
-        dev, md, rows = self._pack(P, update_caches=False)
-        out = dev.apply(md, rows, op, rhs=rhs)
+        out, _, _, single = self._diagnose("apply", np.atleast_2d(np.asarray(P, dtype=np.float64)), rhs, op)
         res = out["out"][:, 0] if single else out["out"]
         return (res, out["info"]) if return_info else res
 
     def _batch_rhs(self, P, rhs):
-        """``rhs`` of the batched diagnostics: None, (n,) / (k, n) shared by the walkers, or (B, k, n); and whether every
-        walker has one vector."""
-        if rhs is None:
-            return None, True
+        """``rhs`` of the batched diagnostics: (n,) / (k, n) shared by the walkers, or (B, k, n); and whether every walker
+        has one vector."""
         r = np.asarray(rhs, dtype=np.float64)
         if r.ndim == 3:
             if r.shape[0] != P.shape[0] or r.shape[-1] != len(self.data.wave):
@@ -560,22 +566,15 @@ class SpectrumModel:
         data.flux``; (n,) or (k, n)): dict with "emulator", "noise", "global" (models with ``global_cov``), "local"
         (models with ``local_cov``: one row per kernel, in the order of ``self["local_cov"]``) and "alpha" = ``C^-1 rhs``
         (:meth:`cho_solve`).  The components add up to ``rhs``.  Raises as :meth:`log_likelihood` does."""
-        single = True
-        if rhs is not None:
-            rhs, single = self._rhs_block(rhs)
-        dev, md, rows = self._pack(update_caches=False)
-        out = dev.decompose(md, rows, rhs=rhs)
-        self._raise_for_info(out["info"][0])
-        return self._component_dict(out["comp"][0], out["alpha"][0], bool(md.has_global), int(md.n_local), single)
+        out, md, _, single = self._diagnose("decompose", None, rhs)
+        out = self._own(out)
+        return self._component_dict(out["comp"], out["alpha"], bool(md.has_global), int(md.n_local), single)
 
     def residual_components_batch(self, P, rhs=None, return_info=False):
         """:meth:`residual_components` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device pass:
         the same keys with a leading B axis.  ``rhs`` as for :meth:`apply_factor_batch`; walkers that fail get NaN rows,
         ``info`` their codes.  The model's own state is not modified."""
-        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
-        rhs, single = self._batch_rhs(P, rhs)
-        dev, md, rows = self._pack(P, update_caches=False)
-        out = dev.decompose(md, rows, rhs=rhs)
+        out, md, _, single = self._diagnose("decompose", np.atleast_2d(np.asarray(P, dtype=np.float64)), rhs)
         res = self._component_dict(out["comp"], out["alpha"], bool(md.has_global), int(md.n_local), single)
         return (res, out["info"]) if return_info else res
 
@@ -612,24 +611,18 @@ class SpectrumModel:
         standardised residual "z" = ``alpha / sqrt(d)`` and the per-pixel "log_density" = ``-log(2 pi / d) / 2 - z^2 / 2``,
         whose sum is the leave-one-out pseudo-likelihood.  "marginal_std" and "loo_std" are (n,) whatever ``rhs`` is.
         Raises as :meth:`log_likelihood` does."""
-        single = True
-        if rhs is not None:
-            rhs, single = self._rhs_block(rhs)
-        dev, md, rows = self._pack(update_caches=False)
-        out = dev.pointwise(md, rows, rhs=rhs, want_flux=rhs is None)
-        self._raise_for_info(out["info"][0])
+        out, _, rhs, single = self._diagnose("pointwise", None, rhs, want_flux=rhs is None)
+        out = self._own(out)
         if rhs is None:
-            rhs = (out["flux"][0] - self.data.flux)[None, :]
-        return self._pointwise_dict(rhs, out["alpha"][0], out["cinv_diag"][0], out["cov_diag"][0], single)
+            rhs = (out["flux"] - self.data.flux)[None, :]
+        return self._pointwise_dict(rhs, out["alpha"], out["cinv_diag"], out["cov_diag"], single)
 
     def pointwise_batch(self, P, rhs=None, return_info=False):
         """:meth:`pointwise` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device pass: the same
         keys with a leading B axis.  ``rhs`` as for :meth:`apply_factor_batch`; walkers that fail get NaN rows, ``info``
         their codes.  The model's own state is not modified."""
-        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
-        rhs, single = self._batch_rhs(P, rhs)
-        dev, md, rows = self._pack(P, update_caches=False)
-        out = dev.pointwise(md, rows, rhs=rhs, want_flux=rhs is None)
+        out, _, rhs, single = self._diagnose("pointwise", np.atleast_2d(np.asarray(P, dtype=np.float64)), rhs,
+                                             want_flux=rhs is None)
         if rhs is None:
             rhs = (out["flux"] - self.data.flux)[:, None, :]
         res = self._pointwise_dict(rhs, out["alpha"], out["cinv_diag"], out["cov_diag"], single)
@@ -666,10 +659,8 @@ class SpectrumModel:
         if not labels:
             raise ValueError("no thawed global_cov / local_cov parameter to differentiate in")
         dev, md, rows = self._pack(update_caches=False)
-        out = dev.loglike_grad(md, rows)
-        self._raise_for_info(out["info"][0])
-        g = out["grad"][0, self._gradient_slots(md)]
-        return float(out["lnl"][0]), dict(zip(labels, (float(v) for v in g)))
+        out = self._own(dev.loglike_grad(md, rows))
+        return float(out["lnl"]), dict(zip(labels, (float(v) for v in out["grad"][self._gradient_slots(md)])))
 
     def log_likelihood_gradient_batch(self, P, return_info=False):
         """:meth:`log_likelihood_gradient` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device pass:

@@ -1,5 +1,6 @@
 """sf_potrs_batch / sf_apply_batch without a device: every bad argument is refused with SF_EINVAL and a message before
-any HIP call, and the size queries that need no context.  (A context needs a device: what the size query of
+any HIP call (sf_apply_batch: before the context is looked at, as its siblings do), and the size queries that need no
+context.  (A context needs a device: what the size query of
 sf_apply_batch returns for a real order is checked in tests/test_gpu_apply_factor.py.)"""
 import ctypes as C
 
@@ -58,6 +59,36 @@ def test_apply_ops_are_the_headers():
     got = {name: int(v) for name, v in re.findall(r"#define SF_APPLY_([A-Z]+) (\d)", header)}
     assert got == {"L": 0, "LINV": 1, "LINVT": 2, "CINV": 3}
     assert {k.upper(): v for k, v in D.APPLY_OPS.items()} == got
+
+
+APPLY_GOOD = dict(ctx=None, B=4, params=FAKE, op=3, rhs=FAKE + (1 << 20), nrhs=3, ldr=4096, rhs_stride=3 * 4096,
+                  out=FAKE + (1 << 24), flux=None, info=None, work=FAKE + (1 << 28), work_bytes=1 << 20)
+
+# refused on the counts, the pointers, op and the right-hand-side conventions: before the context is looked at
+APPLY_BAD = {
+    "no walker": dict(B=0),
+    "negative batch": dict(B=-3),
+    "more walkers than a grid plane": dict(B=65536),
+    "no right-hand side": dict(nrhs=0),
+    "more right-hand sides than a grid row": dict(nrhs=65536),
+    "null params": dict(params=None),
+    "null out": dict(out=None),
+    "op below the range": dict(op=-1),
+    "op above the range": dict(op=4),
+    "negative rhs stride": dict(rhs_stride=-1),
+    "the residual as two right-hand sides": dict(rhs=None, nrhs=2),
+}
+
+
+@pytest.mark.parametrize("case", list(APPLY_BAD))
+def test_apply_refuses_bad_arguments_before_it_looks_at_the_context(case):
+    lib = _lib.load()  # loading needs no GPU; a call that reached the HIP runtime here would not return SF_EINVAL
+    a = dict(APPLY_GOOD, **APPLY_BAD[case])
+    rc = lib.sf_apply_batch(a["ctx"], C.byref(_lib.ModelDesc()), a["B"], a["params"], a["op"], a["rhs"], a["nrhs"], a["ldr"],
+                            a["rhs_stride"], a["out"], a["flux"], a["info"], a["work"], a["work_bytes"], None)
+    assert rc == SF_EINVAL, (case, rc)
+    msg = lib.sf_last_error().decode()
+    assert msg.startswith("sf_apply_batch:"), (case, msg)
 
 
 def test_apply_entry_points_refuse_a_missing_context():

@@ -173,10 +173,16 @@ def test_chunked_and_repeated_calls_give_the_same_bits_and_the_workspace_grows_w
     assert do.npad == 192
     sizes = np.array([do.loglike_grad_workspace_bytes(md, B) for B in (1, 2, 3, 64)])
     assert (np.diff(sizes) > 0).all()
+    a256 = lambda x: -(-x // 256) * 256  # noqa: E731
+    slots = (2 if md.has_global else 0) + 3 * int(md.n_local)
+    assert (do.npad // 64, -(-do.n // 64), slots) == (3, 3, 5)
     for B in (1, 3, 64):
-        # the workspace of apply with one right-hand side, a row of npad, the three block inverses, 3 block rows x 5 slots
-        assert do.loglike_grad_workspace_bytes(md, B) >= (do.apply_workspace_bytes(md, B, 1) + 8 * B * do.npad
-                                                          + 8 * B * 3 * 64 * 64 + 8 * B * 3 * 5)
+        # behind sf_apply_batch's layout with one right-hand side: a row of npad per walker, the workspace of the inverse's
+        # launch (the three block inverses), then 3 block rows x 5 slots per walker
+        extra = do.loglike_grad_workspace_bytes(md, B) - do.apply_workspace_bytes(md, B, 1)
+        assert extra == (a256(8 * B * do.npad) + do.lib.sf_potri_diag_workspace_bytes(do.npad, B)
+                         + a256(8 * B * -(-do.n // 64) * slots)), (B, extra)
+        assert do.lib.sf_potri_diag_workspace_bytes(do.npad, B) >= 8 * B * 3 * 64 * 64
     assert do.loglike_grad_workspace_bytes(md, 0) == 0
 
 

@@ -239,6 +239,9 @@ def test_workspace_grows_with_walkers_and_right_hand_sides():
     assert do.npad == 192
     sizes = np.array([[do.pointwise_workspace_bytes(md, B, k) for k in (1, 2, 16, 17)] for B in (1, 2, 3, 64)])
     assert (np.diff(sizes, axis=0) > 0).all() and (np.diff(sizes, axis=1) > 0).all()
+    a256 = lambda x: -(-x // 256) * 256  # noqa: E731
     for B, k in ((1, 1), (3, 17), (64, 2)):
-        assert do.pointwise_workspace_bytes(md, B, k) >= do.apply_workspace_bytes(md, B, k) + 8 * B * 2 * do.npad
+        # behind sf_apply_batch's layout: two rows of npad per walker, then the workspace of the inverse's launch
+        extra = do.pointwise_workspace_bytes(md, B, k) - do.apply_workspace_bytes(md, B, k)
+        assert extra == 2 * a256(8 * B * do.npad) + do.lib.sf_potri_diag_workspace_bytes(do.npad, B), (B, k, extra)
     assert do.pointwise_workspace_bytes(md, 0, 1) == 0 and do.pointwise_workspace_bytes(md, 1, 0) == 0

@@ -466,6 +466,7 @@ def _host_order(monkeypatch, free):
 
     do = D.DeviceOrder.__new__(D.DeviceOrder)
     do.lib, do.dev, do.n, do.ctx, do._ws, do._ws_multi = _RecoveryLib(), torch.device("cpu"), 5, None, None, None
+    do._reserve = lambda need: None  # (the workspace is reserved by the chunk loop, once, not by the _call the tests replace)
     monkeypatch.setattr(torch.cuda, "mem_get_info", lambda dev=None: (free, 2 * free))
     monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
     return do

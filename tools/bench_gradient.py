@@ -4,35 +4,15 @@ Per N in {3008, 4096}, batch 128, a global kernel and 0 or 4 local kernels: ms p
 its contraction launches alone (k_cov_grad and k_cov_grad_sum of sf_cov_grad.h, through sf_debug_loglike_grad_contract on the
 workspace the call left) and, beside them from the same run, of sf_pointwise_batch (the same sequence up to and including the
 inverse's launches) and of sf_loglike_batch (one likelihood evaluation)."""
-import os
-import sys
-
-sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
-sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests"))
 import torch
-from gpu_helpers import device_order, oracle_order, pack_rows
+from _bench_common import arguments, order_and_walkers, timed
+from gpu_helpers import pack_rows
 
 from starfish_amd import _device as D
-from starfish_amd import _lib, synth
+from starfish_amd import _lib
 
-reps = int(sys.argv[1]) if len(sys.argv) > 1 else 3
-B = int(sys.argv[2]) if len(sys.argv) > 2 else 128
-sizes = [int(a) for a in sys.argv[3:]] or [3008, 4096]
+reps, B, sizes = arguments(3)
 lib = _lib.require_gpu()
-
-
-def timed(call):
-    """ms per call (the first call is not timed)."""
-    total = 0.0
-    for it in range(reps + 1):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        call()
-        t1.record()
-        torch.cuda.synchronize()
-        if it:
-            total += t0.elapsed_time(t1)
-    return total / reps
 
 
 def with_local_kernels(o, p, n_local):
@@ -44,9 +24,7 @@ def with_local_kernels(o, p, n_local):
 
 
 for N in sizes:
-    o = synth.make_order(N=N, m=4, seed=5)
-    do = device_order(oracle_order(o))
-    walkers = [synth.vector_to_oracle_params(p) for p in synth.walker_ball(o, B=B)]
+    o, do, walkers = order_and_walkers(N, B)
     for n_local in (0, 4):
         md, rows = pack_rows(do, [with_local_kernels(o, p, n_local) for p in walkers])
         dev, n = do.dev, do.n
@@ -57,11 +35,12 @@ for N in sizes:
             alpha, cinv_diag = D.empty((B, 1, n), dev), D.empty((B, n), dev)
             info = D.empty((B,), dev, torch.int32)
             ws = do._reserve(max(do.loglike_grad_workspace_bytes(md, B), do.pointwise_workspace_bytes(md, B, 1)))
-            pointwise = timed(lambda: do._call("pointwise_batch", md, B, P, None, 1, n, 0, alpha, cinv_diag, None, None, info, ws=ws))
-            loglike = timed(lambda: do._call("loglike_batch", md, B, P, lnl2, None, None, None, None, info, ws=ws))
-            whole = timed(lambda: do._call("loglike_grad_batch", md, B, P, lnl, grad, slots, None, info, ws=ws))
+            pointwise = timed(lambda: do._call("pointwise_batch", md, B, P, None, 1, n, 0, alpha, cinv_diag, None, None, info, ws=ws),
+                              reps)
+            loglike = timed(lambda: do._call("loglike_batch", md, B, P, lnl2, None, None, None, None, info, ws=ws), reps)
+            whole = timed(lambda: do._call("loglike_grad_batch", md, B, P, lnl, grad, slots, None, info, ws=ws), reps)
             assert int(info.abs().max()) == 0 and bool(torch.isfinite(grad).all()) and torch.equal(lnl, lnl2)
-            contract = timed(lambda: do._call("debug_loglike_grad_contract", md, B, P, grad2, slots, ws=ws))
+            contract = timed(lambda: do._call("debug_loglike_grad_contract", md, B, P, grad2, slots, ws=ws), reps)
             assert torch.equal(grad, grad2)
             do.release_workspace()
             del ws
