@@ -482,6 +482,38 @@ int sf_emulator_loglike_batch(const double* d_grid, int M, int P, int m, const d
                               const double* d_iphiphi, const double* d_w_hat, double* d_lnl, double* d_logdet,
                               double* d_sqmah, int* d_info, void* d_work, size_t work_bytes, void* stream);
 
+/* The training likelihood and its gradient in the LOGS of the hyper-parameters, for B hyper-parameter vectors in ONE enqueue:
+ * d lnL / d theta = 1/2 sum_ij (alpha_i alpha_j - (v11^-1)_ij) (d v11 / d theta)_ij (Rasmussen & Williams, Gaussian Processes for
+ * Machine Learning, eq. 5.9), alpha = v11^-1 w_hat, with (row i = component i / M, grid point i % M)
+ *     log lambda_xi:   -iPhiPhi_ij / lambda_xi                                 (every entry of the dense n x n array)
+ *     log variance_c:  K_c[g,h] = variance_c exp(-1/2 sum_p ((x_gp - x_hp) / l_cp)^2)     where i / M == j / M == c, else 0
+ *     log l_cp:        K_c[g,h] ((x_gp - x_hp) / l_cp)^2                                   where i / M == j / M == c, else 0
+ * Sequence: the four stages of sf_emulator_loglike_batch on the same layout (d_lnl and d_info carry ITS BITS for the same
+ * rows), alpha by sf_potrs_batch's SF_APPLY_CINV, X = L^-1 by the launch of sf_potri_diag_batch, every 64 x 64 block of
+ * v11^-1 = X^T X of the lower triangle as sf_potri_blocks_batch forms them, contracted with the analytic entries; a small
+ * fixed-order sum over block rows.  No atomics: a repeated call, and a call on a part of the rows, give the same bits.
+ * d_hyper: raw rows as for sf_emulator_loglike_batch.  d_grad[b*grad_stride + s]: the derivative in the LOG of
+ * hyper-parameter s, in the order of the raw row (lambda_xi, variances[m], lengthscales[m*P]); grad_stride >= 1 + m + m P,
+ * entries beyond the slots are not touched.  Rows with d_info[b] != 0 get lnl = -inf and NaN in every slot.
+ * Error: with u = 2^-53 and |D| the entry derivative taken in absolute value, a slot is within
+ *     1/2 sum_ij (|dalpha|_i |alpha|_j + |alpha|_i |dalpha|_j + |dG|_ij) |D|_ij + (1e-13 + gamma_k) 1/2 sum_ij |A_ij| |D|_ij
+ * of the exact value for the matrix that is factorised, |dalpha| and |dG| being the bounds of sf_potrs_batch and
+ * sf_potri_blocks_batch above with the build's entry error (1e-13 relative) in dC, k the number of non-zero entries of D.
+ * SF_EINVAL before anything is enqueued: a null pointer, M or m not positive, P outside 1 .. 8, hyper_stride or grad_stride
+ * below 1 + m + m P, B outside 1 .. 65535, d_work not 256-byte aligned; SF_ENOMEM for a short workspace.  d_work:
+ * what sf_emulator_loglike_grad_workspace_bytes gives for M, P, m, B (0 for bad arguments): the workspace of sf_emulator_loglike_batch,
+ * then alpha (npad doubles per row), the workspace of sf_potri_blocks_batch and one double per (row, 64-row block, slot).
+ * The call never synchronises. */
+size_t sf_emulator_loglike_grad_workspace_bytes(int M, int P, int m, int B);
+int sf_emulator_loglike_grad_batch(const double* d_grid, int M, int P, int m, const double* d_hyper, int hyper_stride, int B,
+                                   const double* d_iphiphi, const double* d_w_hat, double* d_lnl, double* d_grad,
+                                   int grad_stride, int* d_info, void* d_work, size_t work_bytes, void* stream);
+/* Timing aid (tools/bench_emulator_gradient.py): the contraction launches of sf_emulator_loglike_grad_batch alone, on the
+ * workspace and d_info that a call of it with the same arguments left behind. */
+int sf_debug_emulator_grad_contract(const double* d_grid, int M, int P, int m, const double* d_hyper, int hyper_stride, int B,
+                                    const double* d_iphiphi, double* d_grad, int grad_stride, const int* d_info, void* d_work,
+                                    size_t work_bytes, void* stream);
+
 /* Process-global switch of the persistent-kernel ("dataflow") Cholesky sequence: enable = 0 makes every later factorisation
  * take a launch sequence (kernels without waits inside), 1 restores the default choice, < 0 only queries.  Returns the
  * previous setting.  The recovery path after SF_INFO_INTERNAL.

@@ -103,6 +103,15 @@ SIGNATURES = {
         C.c_int,
         [_VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP],
     ),
+    "sf_emulator_loglike_grad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sf_emulator_loglike_grad_batch": (
+        C.c_int,
+        [_VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP, _VP, _VP, C.c_int, _VP, _VP, C.c_size_t, _VP],
+    ),
+    "sf_debug_emulator_grad_contract": (
+        C.c_int,
+        [_VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_size_t, _VP],
+    ),
     "sf_potrf_batch": (
         C.c_int,
         [_VP, C.c_int, C.c_int, C.c_int64, C.c_int, _VP, _VP, C.c_size_t, _VP],

@@ -163,7 +163,8 @@ int sf_launch_diag_copy(const double* A, int n, int lda, int64_t stride, int bat
 
 int sf_launch_clock_probe(long long* out, long long wall_ticks, hipStream_t s);
 
-// sf_fill.hip (layers: sf_fill_elem.h, sf_fill_band.h, sf_fill_tile.h, sf_fill_dense.h, sf_fill_free.h, sf_cov_matvec.h, sf_cov_grad.h)
+// sf_fill.hip (layers: sf_fill_elem.h, sf_fill_band.h, sf_fill_tile.h, sf_fill_dense.h, sf_fill_free.h, sf_cov_matvec.h, sf_cov_grad.h,
+// sf_emu_grad.h)
 struct sf_fill_args {
     const double* wave;    // [n]
     const double* sigma;   // [n]
@@ -218,6 +219,16 @@ static inline __host__ __device__ int sf_cov_grad_slots(int has_global, int n_lo
 size_t sf_cov_grad_work_doubles(int n, int has_global, int n_local, int batch);
 int sf_launch_cov_grad(const sf_fill_args& f, int batch, const double* winv, const double* alpha, int ld_alpha, const int* info,
                        double* part, double* grad, int grad_stride, hipStream_t s);
+// sf_emu_grad.h: the emulator training likelihood's gradient in the LOGS of its hyper-parameters, contracted from the blocks of
+// v11^-1: grid, hyper (raw rows), iphiphi as sf_launch_v11_build_batch gets them; L: the factored matrices after the inverse's
+// launch; alpha: [batch][ld_alpha] = v11^-1 w_hat; part: sf_emu_grad_work_doubles of scratch; grad[b * grad_stride + slot] in
+// the order of the raw row; NaN where info[b] != 0
+static inline __host__ __device__ int sf_emu_grad_slots(int m, int P) { return 1 + m + m * P; }
+size_t sf_emu_grad_work_doubles(int M, int P, int m, int batch);
+int sf_launch_emu_grad(const double* grid, int M, int P, int m, const double* hyper, int hyper_stride, int batch,
+                       const double* iphiphi, const double* L, int npad, int lda, int64_t stride, const double* winv,
+                       const double* alpha, int ld_alpha, const int* info, double* part, double* grad, int grad_stride,
+                       hipStream_t s);
 // sf_fill_band.h: band storage of the structured part of C (sf_band.hip consumes it); a.npad = rows written (>= a.n)
 int sf_launch_band_fill(const sf_fill_args& a, int B, double* band, int ws, int halfwidth, int ldb, int64_t sband,
                         int* info, double* gtab, hipStream_t s, int tile_wt = -1);  // ws stored diagonals > halfwidth; gtab: B x (ws+1) or NULL

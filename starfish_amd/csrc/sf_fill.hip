@@ -18,6 +18,7 @@
 //   sf_fill_free.h    k_global_cov, k_local_cov, k_stream_write: stand-alone kernels and the write probe
 //   sf_cov_matvec.h   k_cov_yv, k_cov_matvec: the components of C applied to vectors (sf_decompose_batch)
 //   sf_cov_grad.h     k_cinv_blocks, k_cov_grad, k_cov_grad_sum: blocks of C^-1 and the gradient in the covariance hyper-parameters
+//   sf_emu_grad.h     k_emu_grad, k_emu_grad_sum: the emulator training likelihood's gradient in its hyper-parameters
 #include "sf_common.h"
 #include "sf_device.h"
 #include "sf_fill_elem.h"
@@ -27,3 +28,4 @@
 #include "sf_fill_free.h"
 #include "sf_cov_matvec.h"
 #include "sf_cov_grad.h"
+#include "sf_emu_grad.h"

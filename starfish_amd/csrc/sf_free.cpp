@@ -282,6 +282,24 @@ extern "C" int sf_emulator_v11_build_batch(const double* d_grid, int M, int P, i
 
 // The training objective for B hyper-parameter rows (workspace: carve_emu_train)
 extern "C" size_t sf_emulator_loglike_workspace_bytes(int M, int m, int B) { return carve_emu_train(M, m, B, nullptr, 0).bytes; }
+// build (lower triangle, R = w_hat), factorisation, logdet / sqmah, finish: the four stages both calls below run, on one layout
+static int emu_loglike_stages(const EmuTrainWork& w, const double* d_grid, int M, int P, int m, const double* d_hyper,
+                              int hyper_stride, int B, const double* d_iphiphi, const double* d_w_hat, double* d_lnl,
+                              double* d_logdet, double* d_sqmah, int* d_info, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    double* logdet = d_logdet ? d_logdet : w.logdet;
+    double* sqmah = d_sqmah ? d_sqmah : w.sqmah;
+    // (every argument check of the stages is made by the first one before it enqueues anything: P <= 8 is the build's)
+    int rc = sf_launch_v11_build_batch(d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, w.A, w.npad, w.lda, w.stride, 1, d_w_hat,
+                                       w.R, w.npad, s);
+    if (rc) return rc;
+    rc = sf_potrf_batch(w.A, w.npad, w.lda, w.stride, B, w.info_c, w.potrf, w.potrf_bytes, stream);
+    if (rc) return rc;
+    rc = sf_logdet_sqmah_batch(w.A, w.npad, w.lda, w.stride, B, w.R, w.npad, w.potrf, w.potrf_bytes, logdet, sqmah, stream);
+    if (rc) return rc;
+    ProfScope ps(s, PS_SOLVE);
+    return sf_launch_finish(B, logdet, sqmah, w.info_c, nullptr, d_lnl, d_info, s);
+}
 extern "C" int sf_emulator_loglike_batch(const double* d_grid, int M, int P, int m, const double* d_hyper, int hyper_stride,
                                          int B, const double* d_iphiphi, const double* d_w_hat, double* d_lnl, double* d_logdet,
                                          double* d_sqmah, int* d_info, void* d_work, size_t work_bytes, void* stream) {
@@ -296,19 +314,78 @@ extern "C" int sf_emulator_loglike_batch(const double* d_grid, int M, int P, int
         sf_set_error("sf_emulator_loglike_batch: workspace of %zu bytes, %zu needed", work_bytes, w.bytes);
         return SF_ENOMEM;
     }
+    return emu_loglike_stages(w, d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, d_w_hat, d_lnl, d_logdet, d_sqmah, d_info,
+                              stream);
+}
+
+// The training objective and its gradient in the logs of the hyper-parameters (workspace: carve_emu_train with the grid axes)
+static bool emu_grad_counts_ok(int M, int P, int m, int B) {
+    return M > 0 && m > 0 && P >= 1 && P <= 8 && B >= 1 && B <= 65535 && (int64_t)m * M <= (1 << 30) &&
+           (int64_t)m * (P + 1) < (1 << 30);
+}
+extern "C" size_t sf_emulator_loglike_grad_workspace_bytes(int M, int P, int m, int B) {
+    if (!emu_grad_counts_ok(M, P, m, B)) return 0;
+    return carve_emu_train(M, m, B, nullptr, 0, P).bytes;
+}
+// every argument check of both calls below, before any HIP call
+static int emu_grad_open(const char* name, bool required, int M, int P, int m, int hyper_stride, int B, int grad_stride,
+                         void* d_work, size_t work_bytes, EmuTrainWork* w) {
+    if (!required || !d_work) {
+        sf_set_error("%s: a required pointer is NULL", name);
+        return SF_EINVAL;
+    }
+    if (!emu_grad_counts_ok(M, P, m, B)) {
+        sf_set_error("%s: M=%d and m=%d must be positive, P=%d in 1 .. 8, B=%d in 1 .. 65535", name, M, m, P, B);
+        return SF_EINVAL;
+    }
+    const int slots = sf_emu_grad_slots(m, P);
+    if (hyper_stride < slots || grad_stride < slots) {
+        sf_set_error("%s: hyper_stride=%d and grad_stride=%d must be at least 1 + m + m P = %d", name, hyper_stride, grad_stride,
+                     slots);
+        return SF_EINVAL;
+    }
+    if ((uintptr_t)d_work & 255) {
+        sf_set_error("%s: d_work must be 256-byte aligned", name);
+        return SF_EINVAL;
+    }
+    *w = carve_emu_train(M, m, B, d_work, work_bytes, P);
+    if (work_bytes < w->bytes) {
+        sf_set_error("%s: workspace of %zu bytes, %zu needed", name, work_bytes, w->bytes);
+        return SF_ENOMEM;
+    }
+    return SF_OK;
+}
+// 1/2 sum (alpha alpha^T - v11^-1) o dv11/dtheta from the alpha and the X the stages before left in the workspace
+static int emu_grad_contract(const EmuTrainWork& w, const double* d_grid, int M, int P, int m, const double* d_hyper,
+                             int hyper_stride, int B, const double* d_iphiphi, const int* d_info, double* d_grad, int grad_stride,
+                             hipStream_t s) {
+    return sf_launch_emu_grad(d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, w.A, w.npad, w.lda, w.stride, w.winv, w.alpha,
+                              w.npad, d_info, w.part, d_grad, grad_stride, s);
+}
+extern "C" int sf_emulator_loglike_grad_batch(const double* d_grid, int M, int P, int m, const double* d_hyper, int hyper_stride,
+                                              int B, const double* d_iphiphi, const double* d_w_hat, double* d_lnl, double* d_grad,
+                                              int grad_stride, int* d_info, void* d_work, size_t work_bytes, void* stream) {
+    EmuTrainWork w;
+    SF_CHECK(emu_grad_open("sf_emulator_loglike_grad_batch", d_grid && d_hyper && d_iphiphi && d_w_hat && d_lnl && d_grad && d_info,
+                           M, P, m, hyper_stride, B, grad_stride, d_work, work_bytes, &w));
     hipStream_t s = (hipStream_t)stream;
-    double* logdet = d_logdet ? d_logdet : w.logdet;
-    double* sqmah = d_sqmah ? d_sqmah : w.sqmah;
-    // (every argument check of the stages is made by the first one before it enqueues anything: P <= 8 is the build's)
-    int rc = sf_launch_v11_build_batch(d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, w.A, w.npad, w.lda, w.stride, 1, d_w_hat,
-                                       w.R, w.npad, s);
-    if (rc) return rc;
-    rc = sf_potrf_batch(w.A, w.npad, w.lda, w.stride, B, w.info_c, w.potrf, w.potrf_bytes, stream);
-    if (rc) return rc;
-    rc = sf_logdet_sqmah_batch(w.A, w.npad, w.lda, w.stride, B, w.R, w.npad, w.potrf, w.potrf_bytes, logdet, sqmah, stream);
-    if (rc) return rc;
-    ProfScope ps(s, PS_SOLVE);
-    return sf_launch_finish(B, logdet, sqmah, w.info_c, nullptr, d_lnl, d_info, s);
+    SF_CHECK(emu_loglike_stages(w, d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, d_w_hat, d_lnl, nullptr, nullptr, d_info,
+                                stream));
+    // (the factor is applied first: the inverse's launch takes the strict upper triangle of the matrices as scratch)
+    SF_CHECK(sf_launch_chol_apply(w.A, w.npad, w.lda, w.stride, B, SF_APPLY_CINV, w.R, 1, w.npad, w.npad, w.alpha, w.npad, w.npad, s));
+    SF_CHECK(sf_launch_chol_inverse_diag(w.A, w.npad, w.lda, w.stride, B, w.winv, w.cinv_diag, w.npad, s));
+    return emu_grad_contract(w, d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, d_info, d_grad, grad_stride, s);
+}
+// The contraction launches of sf_emulator_loglike_grad_batch alone, on the workspace and d_info a call with the same arguments
+// left (tools/bench_emulator_gradient.py times them)
+extern "C" int sf_debug_emulator_grad_contract(const double* d_grid, int M, int P, int m, const double* d_hyper, int hyper_stride,
+                                               int B, const double* d_iphiphi, double* d_grad, int grad_stride, const int* d_info,
+                                               void* d_work, size_t work_bytes, void* stream) {
+    EmuTrainWork w;
+    SF_CHECK(emu_grad_open("sf_debug_emulator_grad_contract", d_grid && d_hyper && d_iphiphi && d_grad && d_info, M, P, m,
+                           hyper_stride, B, grad_stride, d_work, work_bytes, &w));
+    return emu_grad_contract(w, d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, d_info, d_grad, grad_stride,
+                             (hipStream_t)stream);
 }
 
 // Recovery switch of the callers (process-global): after a batch came back SF_INFO_INTERNAL the host layer turns the

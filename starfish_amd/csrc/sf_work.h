@@ -249,16 +249,20 @@ static ResampleWork carve_resample(int n, int rows, void* p, size_t cap) {
 }
 // The training objective for B hyper-parameter rows: the B matrices (npad = m M rounded up to the Cholesky leaf, row stride
 // npad + 16 as Emulator.log_likelihood lays its one matrix out), the B x npad right-hand sides, logdet / sqmah / the
-// factorisation's info, then the workspace of sf_potrf_batch (carve_potrf).
+// factorisation's info, then the workspace of sf_potrf_batch (carve_potrf).  With grad_P > 0 (grid axes:
+// sf_emulator_loglike_grad_batch), behind all that and so at the same offsets: alpha = v11^-1 w_hat (B x npad), the scratch
+// of the inverse's launch and the row of the inverse's diagonal it writes (carve_potri; the gradient does not read the row),
+// and the gradient's partial sums, one double per (matrix, 64-row block, slot).
 struct EmuTrainWork {
     int npad, lda;
     int64_t stride;
     double *A, *R, *logdet, *sqmah;
     int* info_c;
     char* potrf;
+    double *alpha, *winv, *cinv_diag, *part;
     size_t potrf_bytes, bytes;
 };
-static EmuTrainWork carve_emu_train(int M, int m, int B, void* p, size_t cap) {
+static EmuTrainWork carve_emu_train(int M, int m, int B, void* p, size_t cap, int grad_P = 0) {
     EmuTrainWork w = {};
     if (M <= 0 || m <= 0 || B <= 0 || (int64_t)m * M > (1 << 30)) return w;
     w.npad = (m * M + SF_LEAF - 1) / SF_LEAF * SF_LEAF;
@@ -273,6 +277,14 @@ static EmuTrainWork carve_emu_train(int M, int m, int B, void* p, size_t cap) {
     w.info_c = k.take<int>(b);
     w.potrf_bytes = carve_potrf(w.npad, B, nullptr, 0).bytes;
     w.potrf = k.take<char>(w.potrf_bytes);
+    if (grad_P > 0) {
+        w.alpha = k.take<double>(b * w.npad);
+        const PotriWork pw = carve_potri(w.npad, B, nullptr, 0, true);
+        char* potri = k.take<char>(pw.bytes);
+        const PotriWork pi = carve_potri(w.npad, B, potri, pw.bytes, true);
+        w.winv = pi.winv, w.cinv_diag = pi.diag;
+        w.part = k.take<double>(sf_emu_grad_work_doubles(M, grad_P, m, B));
+    }
     w.bytes = k.off;
     return w;
 }

@@ -431,11 +431,62 @@ class Emulator:
     def _hyper_rows(self, P):
         """Rows in the units of :meth:`get_param_vector` (logs) -> the raw rows {lambda_xi, variances[m], lengthscales[m][P]}
         of the C-ABI, in the order the property getters read ``hyperparams``."""
-        keys = list(self.hyperparams)
-        order = ([keys.index("log_lambda_xi")] + [i for i, k in enumerate(keys) if k.startswith("log_variance:")]
-                 + [i for i, k in enumerate(keys) if k.startswith("log_lengthscale:")])
         with np.errstate(over="ignore"):
-            return np.ascontiguousarray(np.exp(P[:, order]))
+            return np.ascontiguousarray(np.exp(P[:, self._hyper_order()]))
+
+    def _hyper_order(self):
+        """For every slot of the raw row, its column in :meth:`get_param_vector`."""
+        keys = list(self.hyperparams)
+        return ([keys.index("log_lambda_xi")] + [i for i, k in enumerate(keys) if k.startswith("log_variance:")]
+                + [i for i, k in enumerate(keys) if k.startswith("log_lengthscale:")])
+
+    def _hyper_batches(self, where, P, width, workspace_bytes, enqueue):
+        """The rows of ``P`` (logs) through a batched training call: checked, turned into raw rows, cut into chunks that fit the
+        free device memory, run under :func:`D.retry_internal`.  ``workspace_bytes(M, npar, m, nb)`` is the call's size query;
+        ``enqueue(lib, td, (M, npar, m), d_hyper, S, nb, d_out, d_info, ws, stream)`` enqueues it for ``nb`` rows, its
+        ``width * nb`` doubles going to ``d_out``.  Doubles and status codes share one buffer: one download per chunk.
+        Returns the doubles of every chunk in order and ``info (B,)``."""
+        from .. import _lib
+
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        if P.ndim != 2 or P.shape[1] != len(self.hyperparams):
+            raise ValueError("P must be (B, len(get_param_vector()))")
+        if self._v11_assigned:
+            raise ValueError(f"{where}: this emulator's v11 was assigned by hand and has no hyper-parameter row "
+                             "(set_param_vector / set_param_dict make the hyper-parameters rule again)")
+        lib = _lib.require_gpu()
+        torch = D._torch()
+        dev = D.device_of()
+        M, npar = self.grid_points.shape
+        m = self.ncomps
+        td = self._train_resident(lib, dev)
+        hyper = self._hyper_rows(P)
+        B, S = hyper.shape
+
+        def run(again):
+            chunks = []
+            info = np.empty(B, dtype=np.int32)
+            # chunks sized from the free device memory as DeviceOrder.max_batch does; the workspace is a fixed part (the
+            # factorisation's partial-sum regions) plus a part per matrix
+            one, two = (int(workspace_bytes(lib, M, npar, m, b)) for b in (1, 2))
+            if not one:
+                raise ValueError(f"{where}: the device does not take {npar} grid dimensions")
+            held = td["ws_batch"].numel() if td["ws_batch"] is not None else 0
+            cap = D.units_that_fit(dev, 2 * one - two, two - one, held, 65535)
+            s = D.stream_ptr(dev)
+            for lo in range(0, B, cap):
+                nb = min(cap, B - lo)
+                ws = D.grow_workspace(td, "ws_batch", int(workspace_bytes(lib, M, npar, m, nb)), dev)
+                d_hyper = D.to_dev(hyper[lo:lo + nb], dev)
+                out = torch.empty((8 * width + 4) * nb, dtype=torch.uint8, device=dev)  # the doubles, then info[nb]
+                enqueue(lib, td, (M, npar, m), d_hyper, S, nb, C.c_void_p(out.data_ptr()),
+                        C.c_void_p(out.data_ptr() + 8 * width * nb), ws, s)
+                host = out.cpu().numpy()
+                chunks.append(host[:8 * width * nb].view(np.float64))
+                info[lo:lo + nb] = host[8 * width * nb:].view(np.int32)
+            return (chunks, info), info
+
+        return D.retry_internal(lib, f"Emulator.{where}", run, count=B, stacklevel=5)
 
     def log_likelihood_batch(self, P, return_info=False):
         """:meth:`log_likelihood` (Starfish/emulator/emulator.py:602-619) for the ``B`` rows of ``P`` -- hyper-parameter
@@ -447,46 +498,90 @@ class Emulator:
         into chunks."""
         from .. import _lib
 
-        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
-        if P.ndim != 2 or P.shape[1] != len(self.hyperparams):
-            raise ValueError("P must be (B, len(get_param_vector()))")
-        if self._v11_assigned:
-            raise ValueError("log_likelihood_batch: this emulator's v11 was assigned by hand and has no hyper-parameter row "
-                             "(set_param_vector / set_param_dict make the hyper-parameters rule again)")
-        lib = _lib.require_gpu()
-        torch = D._torch()
-        dev = D.device_of()
-        M, npar = self.grid_points.shape
-        m = self.ncomps
-        td = self._train_resident(lib, dev)
-        hyper = self._hyper_rows(P)
-        B = len(hyper)
+        def enqueue(lib, td, shape, d_hyper, S, nb, d_out, d_info, ws, s):
+            M, npar, m = shape
+            _lib.check(lib.sf_emulator_loglike_batch(
+                D.ptr(td["grid"]), M, npar, m, D.ptr(d_hyper), S, nb, D.ptr(td["iphiphi"]), D.ptr(td["w_hat_dev"]), d_out, None,
+                None, d_info, D.ptr(ws), ws.numel(), s), "sf_emulator_loglike_batch")
 
-        def run(again):
-            lnl = np.empty(B)
-            info = np.empty(B, dtype=np.int32)
-            # chunks sized from the free device memory as DeviceOrder.max_batch does; the workspace is a fixed part (the
-            # factorisation's partial-sum regions) plus a part per matrix
-            one, two = (int(lib.sf_emulator_loglike_workspace_bytes(M, m, b)) for b in (1, 2))
-            held = td["ws_batch"].numel() if td["ws_batch"] is not None else 0
-            cap = D.units_that_fit(dev, 2 * one - two, two - one, held, 65535)
-            s = D.stream_ptr(dev)
-            for lo in range(0, B, cap):
-                nb = min(cap, B - lo)
-                ws = D.grow_workspace(td, "ws_batch", int(lib.sf_emulator_loglike_workspace_bytes(M, m, nb)), dev)
-                d_hyper = D.to_dev(hyper[lo:lo + nb], dev)
-                out = torch.empty(12 * nb, dtype=torch.uint8, device=dev)  # lnl[nb] then info[nb]: one download
-                _lib.check(lib.sf_emulator_loglike_batch(
-                    D.ptr(td["grid"]), M, npar, m, D.ptr(d_hyper), hyper.shape[1], nb, D.ptr(td["iphiphi"]),
-                    D.ptr(td["w_hat_dev"]), C.c_void_p(out.data_ptr()), None, None, C.c_void_p(out.data_ptr() + 8 * nb),
-                    D.ptr(ws), ws.numel(), s), "sf_emulator_loglike_batch")
-                host = out.cpu().numpy()
-                lnl[lo:lo + nb] = host[:8 * nb].view(np.float64)
-                info[lo:lo + nb] = host[8 * nb:].view(np.int32)
-            return (lnl, info), info
-
-        lnl, info = D.retry_internal(lib, "Emulator.log_likelihood_batch", run, count=B)
+        chunks, info = self._hyper_batches("log_likelihood_batch", P, 1,
+                                           lambda lib, M, npar, m, b: lib.sf_emulator_loglike_workspace_bytes(M, m, b), enqueue)
+        lnl = np.concatenate(chunks)
         return (lnl, info) if return_info else lnl
+
+    @property
+    def gradient_labels(self):
+        """list of str : the hyper-parameters :meth:`log_likelihood_gradient` differentiates in -- all of them, in the order
+        of :meth:`get_param_vector`."""
+        return list(self.hyperparams)
+
+    def log_likelihood_gradient_batch(self, P, return_info=False):
+        """:meth:`log_likelihood_batch` and its analytic gradient (Rasmussen & Williams, GPML, eq. 5.9) for the ``B`` rows of
+        ``P`` -- hyper-parameter vectors in the units of :meth:`get_param_vector`, i.e. logs -- from ONE factorisation per row
+        (``sf_emulator_loglike_grad_batch``): ``lnl (B,)`` and ``grad (B, len(P[0]))``, the derivative of ``lnl`` in every entry
+        of the row, columns in :attr:`gradient_labels` order.  ``lnl`` has the bits of :meth:`log_likelihood_batch`.  Rows
+        with ``info != 0`` get ``-inf`` and a NaN gradient row; with ``return_info`` ``info`` is returned as well.  The
+        emulator's own hyper-parameters, ``v11`` and ``_trained`` are not touched.  Batches that do not fit the free device
+        memory are cut into chunks."""
+        from .. import _lib
+
+        S = len(self.hyperparams)
+
+        def enqueue(lib, td, shape, d_hyper, S, nb, d_out, d_info, ws, s):  # lnl[nb], then the gradient rows [nb][S]
+            M, npar, m = shape
+            _lib.check(lib.sf_emulator_loglike_grad_batch(
+                D.ptr(td["grid"]), M, npar, m, D.ptr(d_hyper), S, nb, D.ptr(td["iphiphi"]), D.ptr(td["w_hat_dev"]), d_out,
+                C.c_void_p(d_out.value + 8 * nb), S, d_info, D.ptr(ws), ws.numel(), s), "sf_emulator_loglike_grad_batch")
+
+        chunks, info = self._hyper_batches("log_likelihood_gradient_batch", P, 1 + S,
+                                           lambda lib, M, npar, m, b: lib.sf_emulator_loglike_grad_workspace_bytes(M, npar, m, b),
+                                           enqueue)
+        lnl = np.concatenate([c[:len(c) // (1 + S)] for c in chunks])
+        grad = np.concatenate([c[len(c) // (1 + S):].reshape(-1, S) for c in chunks])
+        back = np.argsort(self._hyper_order())  # raw slot of every column of P
+        grad = np.ascontiguousarray(grad[:, back])
+        return (lnl, grad, info) if return_info else (lnl, grad)
+
+    def log_likelihood_gradient(self):
+        """``(lnL, grad)`` of the current hyper-parameters: :meth:`log_likelihood` and its gradient in
+        :meth:`get_param_vector`, entries in :attr:`gradient_labels` order.  Raises ``LinAlgError`` where
+        :meth:`log_likelihood` does."""
+        lnl, grad, info = self.log_likelihood_gradient_batch(self.get_param_vector()[None, :], return_info=True)
+        self._raise_for_info(int(info[0]))
+        return float(lnl[0]), grad[0]
+
+    @staticmethod
+    def _raise_for_info(code):
+        """The scalar path's exception for the status code of one row (nothing for 0)."""
+        if code > 0:
+            raise np.linalg.LinAlgError(f"{code}-th leading minor of the array is not positive definite")
+        if code < 0:
+            raise RuntimeError(D.INFO_MESSAGES.get(code, f"emulator likelihood failed (info {code})"))
+
+    def _lengthscale_bounds(self, bounds=None):
+        """``scipy.optimize.Bounds`` over :meth:`get_param_vector`: ``log_lengthscale:c:p >= log(2 grid_sep[p])`` -- the wall of
+        the Nelder-Mead objective (emulator.py:497-503) as a bound, since an ``inf`` breaks a line search -- intersected with
+        the caller's ``bounds`` (a ``Bounds`` or a sequence of ``(lo, hi)``, None for an open end)."""
+        from scipy.optimize import Bounds
+
+        keys = list(self.hyperparams)
+        lo, hi = np.full(len(keys), -np.inf), np.full(len(keys), np.inf)
+        for i, k in enumerate(keys):
+            if k.startswith("log_lengthscale:"):
+                lo[i] = np.log(2 * self._grid_sep[int(k.split(":")[2])])
+        if bounds is not None:
+            if isinstance(bounds, Bounds):
+                blo, bhi = np.broadcast_to(bounds.lb, lo.shape), np.broadcast_to(bounds.ub, hi.shape)
+            else:
+                pairs = list(bounds)
+                if len(pairs) != len(keys):
+                    raise ValueError("bounds must have one (lo, hi) per entry of get_param_vector()")
+                blo = np.array([-np.inf if a is None else a for a, _ in pairs], dtype=np.float64)
+                bhi = np.array([np.inf if b is None else b for _, b in pairs], dtype=np.float64)
+            lo, hi = np.maximum(lo, blo), np.minimum(hi, bhi)
+            if np.any(lo > hi):
+                raise ValueError("bounds leave no lengthscale of at least twice the grid separation")
+        return Bounds(lo, hi)
 
     def _batched_objective(self, evaluate):
         """The objective of :meth:`train` for the rows of a batch, ``evaluate(X) -> (lnl, info)`` being the batch evaluator
@@ -514,16 +609,13 @@ class Emulator:
             def raiser(i):
                 if info[i] != 0:
                     self.set_param_vector(X[i])  # (where the scalar objective stood when it raised)
-                if info[i] > 0:
-                    raise np.linalg.LinAlgError(f"{int(info[i])}-th leading minor of the array is not positive definite")
-                if info[i] < 0:
-                    raise RuntimeError(D.INFO_MESSAGES.get(int(info[i]), f"emulator likelihood failed (info {int(info[i])})"))
+                self._raise_for_info(int(info[i]))
 
             return vals, raiser
 
         return nll_batch
 
-    def train(self, batch_simplex=False, **opt_kwargs):
+    def train(self, batch_simplex=False, gradient=False, **opt_kwargs):
         """Nelder-Mead over the hyper-parameter vector (Starfish/emulator/emulator.py:484-524); every
         likelihood evaluation factors v11 on the GPU.
 
@@ -532,10 +624,21 @@ class Emulator:
         of the simplex method may ask for go to the device as ONE batch (:mod:`starfish_amd._neldermead`,
         :meth:`log_likelihood_batch`): the initial simplex, the four candidates of an iteration, the vertices of a shrink
         step.  The decisions, ``nit`` / ``nfev`` / ``status`` and the exceptions of used points are scipy's; the result also
-        carries ``nbatches`` and ``nfev_speculative``.  The emulator is left as the reference's loop leaves it."""
+        carries ``nbatches`` and ``nfev_speculative``.  The emulator is left as the reference's loop leaves it.
+
+        With ``gradient=True`` the search uses the analytic gradient (:meth:`log_likelihood_gradient_batch`, one factorisation
+        per evaluation): ``method`` defaults to ``"L-BFGS-B"``, the objective returns ``(-lnL, -grad)`` (``jac=True``), and the
+        reference's wall "a lengthscale below twice the grid separation gives ``inf``" becomes the bound
+        ``log_lengthscale >= log(2 grid_sep)`` per entry, intersected with ``bounds`` of the caller.  A point whose v11 is not
+        positive definite raises the scalar path's ``LinAlgError``.  Not together with ``batch_simplex``."""
         from scipy.optimize import minimize
 
         from .._neldermead import minimize_neldermead_batched, split_minimize_kwargs
+
+        if gradient:
+            if batch_simplex:
+                raise ValueError("Emulator.train: gradient=True and batch_simplex=True exclude each other")
+            return self._finish_training(self._train_gradient(minimize, opt_kwargs))
 
         def nll(P):
             if np.any(~np.isfinite(P)):
@@ -560,6 +663,26 @@ class Emulator:
             soln = minimize_neldermead_batched(objective, self.get_param_vector(), **nm_opts)
             if np.all(np.isfinite(soln.last_x)):
                 self.set_param_vector(soln.last_x)  # where the reference's last objective call left the emulator
+        return self._finish_training(soln)
+
+    def _train_gradient(self, minimize, opt_kwargs):
+        """The ``gradient=True`` search of :meth:`train`: every evaluation leaves the emulator at its point, as the serial
+        objective does."""
+        def objective(x):
+            if np.any(~np.isfinite(x)):
+                raise ValueError("Emulator.train: the optimiser asked for a point that is not finite")
+            self.set_param_vector(x)
+            lnl, grad, info = self.log_likelihood_gradient_batch(x[None, :], return_info=True)
+            self._raise_for_info(int(info[0]))
+            return -float(lnl[0]), -np.asarray(grad[0], dtype=np.float64)
+
+        kwargs = {"method": "L-BFGS-B"}
+        kwargs.update(opt_kwargs)
+        kwargs["jac"] = True
+        kwargs["bounds"] = self._lengthscale_bounds(kwargs.get("bounds"))
+        return minimize(objective, self.get_param_vector(), **kwargs)
+
+    def _finish_training(self, soln):
         if not soln.success:
             self.log.warning("Optimization did not succeed.")
             self.log.info(soln.message)
