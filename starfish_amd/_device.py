@@ -140,6 +140,27 @@ def units_that_fit(dev, fixed_bytes, per_unit_bytes, held_bytes=0, limit=None):
     return cap if limit is None else min(cap, int(limit))
 
 
+def run_chunked(lib, where, dev, slot, key, fixed_bytes, per_unit_bytes, limit, B, max_chunk, reserve, buffers, enqueue, download,
+                count=None):
+    """THE chunk loop of the batched calls: ``B`` units cut into chunks whose workspace fits the free HBM
+    (:func:`units_that_fit` of ``fixed_bytes``, ``per_unit_bytes`` and ``limit``; the buffer ``slot[key]`` counts as free), at
+    most ``max_chunk`` each; the results allocated (``buffers()``) and every chunk enqueued on ONE workspace
+    (``reserve(units)``, which grows ``slot[key]``) with ``enqueue(bufs, lo, hi, ws)``; ``download(bufs)``, a dict with "info",
+    returned; all of it once more if a status is SF_INFO_INTERNAL (:func:`retry_internal` with ``where`` and ``count``; its
+    warning names the frame that called the caller of our caller)."""
+    def run(again):
+        held = slot[key].numel() if slot[key] is not None else 0
+        chunk = min(B, max_chunk or B, units_that_fit(dev, fixed_bytes, per_unit_bytes, held, limit))
+        bufs = buffers()
+        ws = reserve(chunk)
+        for lo in range(0, B, chunk):
+            enqueue(bufs, lo, min(lo + chunk, B), ws)
+        res = download(bufs)
+        return res, res["info"]
+
+    return retry_internal(lib, where, run, count=count, stacklevel=6)
+
+
 def result_buffers(B, dev, resid_cols=None):
     """Device outputs of a likelihood call of ``B`` units: the (4, B) "quad" lnl / logdet / sqmah / log_scale (ONE
     device->host copy for the four double outputs), the int32 ``info`` and, asked for, the (B, resid_cols) residuals."""
@@ -495,25 +516,14 @@ class DeviceOrder:
         return params if _torch().is_tensor(params) else to_dev(params, self.dev)
 
     def _run_chunked(self, name, md, P, max_chunk, workspace_bytes, buffers, args, download):
-        """THE chunk loop of the dense calls ``sf_<name>(ctx, &md, B, P, *args, ws, ...)``: the rows of ``P`` cut into chunks
-        whose workspace (``workspace_bytes(units)``) fits the free HBM, at most ``max_chunk`` each; the results allocated
-        (``buffers()``) and every chunk enqueued on ONE reserved workspace with ``args(bufs, lo, hi)``; ``download(bufs)``, a
-        dict with "info", returned; all of it once more if a status is SF_INFO_INTERNAL (:func:`retry_internal`, whose
-        warning names the frame that called our caller)."""
-        B = int(P.shape[0])
+        """:func:`run_chunked` for the dense calls ``sf_<name>(ctx, &md, B, P, *args(bufs, lo, hi), ws, ...)`` on the order's
+        workspace: nothing fixed, ``workspace_bytes(1)`` per walker."""
+        def enqueue(bufs, lo, hi, ws):
+            self._call(name, md, hi - lo, P[lo:hi], *args(bufs, lo, hi), ws=ws)
 
-        def run(again):
-            held = self._ws.numel() if self._ws is not None else 0
-            chunk = min(B, max_chunk or B, units_that_fit(self.dev, 0, max(workspace_bytes(1), 1), held))
-            bufs = buffers()
-            ws = self._reserve(workspace_bytes(chunk))
-            for lo in range(0, B, chunk):
-                hi = min(lo + chunk, B)
-                self._call(name, md, hi - lo, P[lo:hi], *args(bufs, lo, hi), ws=ws)
-            res = download(bufs)
-            return res, res["info"]
-
-        return retry_internal(self.lib, "sf_" + name, run, stacklevel=5)
+        return run_chunked(self.lib, "sf_" + name, self.dev, vars(self), "_ws", 0, max(workspace_bytes(1), 1), None,
+                           int(P.shape[0]), max_chunk, lambda units: self._reserve(workspace_bytes(units)), buffers, enqueue,
+                           download)
 
     def loglike(self, md, params, want_resid=False, max_chunk=None, solver="dense"):
         """params: (B, stride) float64 (numpy or cuda tensor) in the C-ABI row layout.

@@ -163,8 +163,8 @@ int sf_launch_diag_copy(const double* A, int n, int lda, int64_t stride, int bat
 
 int sf_launch_clock_probe(long long* out, long long wall_ticks, hipStream_t s);
 
-// sf_fill.hip (layers: sf_fill_elem.h, sf_fill_band.h, sf_fill_tile.h, sf_fill_dense.h, sf_fill_free.h, sf_cov_matvec.h, sf_cov_grad.h,
-// sf_emu_grad.h)
+// sf_fill.hip (layers: sf_fill_elem.h, sf_fill_band.h, sf_fill_tile.h, sf_fill_dense.h, sf_fill_free.h, sf_cov_matvec.h, sf_cinv.h,
+// sf_grad_frame.h, sf_cov_grad.h, sf_emu_grad.h)
 struct sf_fill_args {
     const double* wave;    // [n]
     const double* sigma;   // [n]
@@ -207,11 +207,12 @@ int sf_launch_stream_write(double* dst, size_t count, double v, hipStream_t s); 
 // exist; v: [batch][nrhs][ldv]; yv: [batch][nrhs][m] scratch for Y v
 int sf_launch_cov_matvec(const sf_fill_args& f, int m, const double* v, int ldv, int nrhs, int batch, double* yv,
                          const int* info, double* out, hipStream_t s);
-// sf_cov_grad.h: selected 64 x 64 blocks of C^-1 = X^T X from what sf_launch_chol_inverse_diag leaves (X^T above the diagonal,
+// sf_cinv.h: selected 64 x 64 blocks of C^-1 = X^T X from what sf_launch_chol_inverse_diag leaves (X^T above the diagonal,
 // winv); pairs: device [npairs][2] = (I, J), 0 <= J <= I < n / 64 (any other pair: a block of NaN); out: [batch][npairs][64][64]
 int sf_launch_cinv_blocks(const double* L, int n, int lda, int64_t stride, int batch, const double* winv, const int* pairs,
                           int npairs, double* out, hipStream_t s);
-// ... and the likelihood's gradient in the covariance hyper-parameters contracted from them: f as the fill gets it with C = the
+// sf_cov_grad.h: the likelihood's gradient in the covariance hyper-parameters contracted from them (sf_grad_frame.h: the frame it
+// shares with sf_emu_grad.h, the layout of part and the sum over the block rows): f as the fill gets it with C = the
 // factored matrices after the inverse's launch; alpha: [batch][ld_alpha] = C^-1 r; part: sf_cov_grad_work_doubles of scratch;
 // grad[b * grad_stride + slot]: log_amp, log_ls of the global kernel, then mu, log_amp, log_sigma per local kernel; NaN where
 // info[b] != 0

@@ -41,7 +41,7 @@ __device__ __forceinline__ int sf_xcd_remap(int bid, int nblk) {
     return base + slot;
 }
 
-// ---- operands of v_mfma_f64_16x16x4_f64 read k-contiguously (sf_chol_apply.h, sf_chol_inverse.h, sf_cov_grad.h)
+// ---- operands of v_mfma_f64_16x16x4_f64 read k-contiguously (sf_chol_apply.h, sf_chol_inverse.h, sf_cinv.h)
 // four consecutive doubles; al: p is 16-byte aligned
 __device__ __forceinline__ void sf_ap_ld4(const double* p, bool al, double (&v)[4]) {
     if (al) {

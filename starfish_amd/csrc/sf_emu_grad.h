@@ -1,33 +1,24 @@
-// The emulator training likelihood's gradient in its hyper-parameters (Rasmussen & Williams, Gaussian Processes for Machine
-// Learning, eq. 5.9):
-//     d lnL / d theta = 1/2 sum_ij (alpha_i alpha_j - (V^-1)_ij) (dV / d theta)_ij,   alpha = V^-1 w_hat,  V^-1 = X^T X,  X = L^-1
-// for V = v11 = iPhiPhi / lambda_xi + blockdiag_c K_c, K_c[g,h] = variance_c exp(-1/2 sum_p ((x_gp - x_hp) / l_cp)^2)
+// The emulator training likelihood's gradient in its hyper-parameters: the contraction of sf_grad_frame.h with alpha =
+// V^-1 w_hat for V = v11 = iPhiPhi / lambda_xi + blockdiag_c K_c, K_c[g,h] = variance_c exp(-1/2 sum_p ((x_gp - x_hp) / l_cp)^2)
 // (sf_transform_v11.h; row i = component i / M, grid point i % M) and theta the LOGS of lambda_xi, variance_c, l_cp:
 //     log lambda_xi   -iPhiPhi_ij / lambda_xi                         every entry of the dense n x n array
 //     log variance_c  K_c[g,h]                                        where i / M == j / M == c
 //     log l_cp        K_c[g,h] ((x_gp - x_hp) / l_cp)^2               where i / M == j / M == c
-// iPhiPhi is dense to this layer, so every 64 x 64 block of V^-1 of the lower triangle is formed (sf_cinv_tile of
-// sf_cov_grad.h, from the X that sf_launch_chol_inverse_diag leaves).  A layer of sf_fill.hip: it shares sf_cinv_tile and the
-// tile's accumulator layout with sf_cov_grad.h; the scaled coordinates are staged as k_v11_build_batch stages them.
+// iPhiPhi is dense to this layer, so every 64 x 64 block of V^-1 of the lower triangle is formed.  A layer of sf_fill.hip; the
+// scaled coordinates are staged as k_v11_build_batch stages them.
 //
-//   k_emu_grad      one 4-wave workgroup per (matrix, block row I), short I first (their K sums are the long ones), matrix
-//                   fastest.  It walks J = 0 .. I in order.  Per pair: the tile, A_ij = alpha_i alpha_j - G_ij for i, j < n
-//                   (zero beyond), the lambda_xi slot sum A_ij iPhiPhi_ij (the 16 consecutive columns of a quarter-wave are
-//                   one 128-byte segment of a row; the factor -1 / lambda_xi is applied once, to the block row's sum), and,
-//                   where the component ranges of the pair's rows and columns meet (the rbf test of k_v11_build_batch), the
-//                   kernel entries: A_ij variance_c exp(-1/2 d2) once per entry, kept in the tile's registers, then one
-//                   component at a time (M = 27 puts up to four in 64 rows) its sum and its sums weighted with the squared
-//                   scaled differences of each grid axis, the entries of other components masked.  A slot's sum over the pair
-//                   meets by xor shuffles within a wave, then across the four waves in LDS in wave order, and thread 0 adds
-//                   it, weighted 2 for J < I and 1 for J = I (the whole tile is formed there), to the slot's running sum in
-//                   LDS.  Partial sums per (matrix, block row, slot) go to the workspace, zero for the components the block
-//                   row does not hold.
-//   k_emu_grad_sum  one thread per (matrix, slot): the block rows in ascending order, times 1/2; NaN where info != 0.
+//   k_emu_grad      the frame's block-row kernel.  It walks J = 0 .. I in order.  Per pair: the tile, the lambda_xi slot sum
+//                   A_ij iPhiPhi_ij (the 16 consecutive columns of a quarter-wave are one 128-byte segment of a row; the
+//                   factor -1 / lambda_xi is applied once, to the block row's sum), and, where the component ranges of the
+//                   pair's rows and columns meet (the rbf test of k_v11_build_batch), the kernel entries: A_ij variance_c
+//                   exp(-1/2 d2) once per entry, kept in the tile's registers, then one component at a time (M = 27 puts up
+//                   to four in 64 rows) its sum and its sums weighted with the squared scaled differences of each grid axis,
+//                   the entries of other components masked, flushed together.  The partial sums are zero for the components
+//                   the block row does not hold.
 // The tile runs on v_mfma_f64_16x16x4_f64 through sf_inv_sweep: it is a matrix product, n^3 / 3 flops over the lower tiles.
 // The entries run on plain VALU arithmetic: the contraction with dV / d theta is an element-wise product, each entry behind
 // an exp that costs more than the 2 + P multiply-adds it feeds, so the matrix cores would have nothing to do.
-// No atomics, no workgroup waits for another, every sum in a fixed order (a repeated call gives the same bits); nothing of
-// the lower triangle is written; alpha, iPhiPhi and the grid are not read for rows and columns >= n.
+// iPhiPhi and the grid are not read for rows and columns >= n.
 #pragma once
 
 #define SF_EG_PMAX 8                      // grid axes (SF_V11_PMAX of the build)
@@ -46,11 +37,7 @@ struct sf_emu_grad_args {
     const double* winv;     // [batch][npad / 64][64][64]
     const double* alpha;    // [batch][ld_alpha]: V^-1 w_hat
     int ld_alpha;
-    const int* info;        // [batch]: != 0 -> NaN rows, nothing is read
-    double* part;           // [batch][nbr][nslots]
-    int nbr, nslots, batch;
-    double* grad;           // [batch][grad_stride]
-    int grad_stride;
+    sf_grad_out o;
 };
 
 // Row (column) g of v11 staged at slot t of a 64-row block, as k_v11_build_batch stages it: the scaled coordinates
@@ -70,15 +57,6 @@ __device__ __forceinline__ double sf_emu_grad_stage(const sf_emu_grad_args& a, c
     return hb[1 + c];
 }
 
-// red[w][0 .. nv) hold the four waves' sums: thread 0 adds them in wave order, times wgt, to dst[0 .. nv)
-__device__ __forceinline__ void sf_emu_grad_flush(int nv, double wgt, const double* red, double* dst, int tid) {
-    __syncthreads();
-    if (tid == 0)
-        for (int q = 0; q < nv; ++q)
-            dst[q] = dst[q] + wgt * (((red[q] + red[SF_EG_NQ + q]) + red[2 * SF_EG_NQ + q]) + red[3 * SF_EG_NQ + q]);
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(256) void k_emu_grad(const sf_emu_grad_args a) {
     __shared__ double xr[SF_EG_PMAX][SF_LEAF];  // scaled coordinates of the block row's rows
     __shared__ double xc[SF_EG_PMAX][SF_LEAF];  // ... and of the pair's columns
@@ -87,8 +65,9 @@ __global__ __launch_bounds__(256) void k_emu_grad(const sf_emu_grad_args a) {
     __shared__ double s_sum[SF_EG_SUMS];
     __shared__ double s_red[4 * SF_EG_NQ];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, lq = lane >> 4;
-    const int b = blockIdx.x % a.batch, I = blockIdx.x / a.batch, n = a.n, M = a.M, P = a.P;
-    if (a.info[b] != 0) return;  // (k_emu_grad_sum writes NaN and does not read the partial sums)
+    const int n = a.n, M = a.M, P = a.P;
+    int b, I;
+    if (!sf_grad_block(a.o, b, I)) return;
     const double* __restrict__ hb = a.hyper + (int64_t)b * a.hyper_stride;
     const double* __restrict__ al = a.alpha + (int64_t)b * a.ld_alpha;
     const sf_cinv_src src = sf_cinv_source(a.L, a.npad, a.lda, a.stride, a.winv, b);
@@ -97,42 +76,30 @@ __global__ __launch_bounds__(256) void k_emu_grad(const sf_emu_grad_args a) {
     for (int q = tid; q < nsum; q += 256) s_sum[q] = 0.0;
     // the rows are the same for every pair of the block row: staged once
     if (tid < SF_LEAF) vr[tid] = sf_emu_grad_stage(a, hb, R0 + tid, tid, xr, cr);
-    // this thread's rows 16 w + lq + 4 r of block I: alpha, masked beyond n
     double a_r[4];
     bool ok_r[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int i = R0 + 16 * w + lq + 4 * r;
-        ok_r[r] = i < n;
-        a_r[r] = ok_r[r] ? al[i] : 0.0;
-    }
+    sf_grad_rows(al, R0, n, w, lq, a_r, ok_r);
     for (int J = 0; J <= I; ++J) {
         const int C0 = J * SF_LEAF;
-        const double wgt = J < I ? 2.0 : 1.0;
         const int cj0 = C0 / M, cj1 = min(C0 + SF_LEAF - 1, n - 1) / M;
         const bool rbf = ci0 <= cj1 && cj0 <= ci1;  // the component ranges of rows and columns meet
         __syncthreads();  // the last pair's columns are read; the rows and s_sum are in place
         if (rbf && tid < SF_LEAF) sf_emu_grad_stage(a, hb, C0 + tid, tid, xc, cc);
+        const double wgt = sf_grad_weight(I, J);
         sf_d4 A[4];
-        sf_cinv_tile(src, I, J, w, l15, lq, A);
-        // this thread's columns 16 t + l15 of block J; A_ij = alpha_i alpha_j - G_ij, zero beyond n; the lambda_xi slot
-        double v = 0.0;
+        bool ok_c[4];
+        sf_grad_tile(src, al, n, I, J, w, l15, lq, a_r, ok_r, A, ok_c);
+        double v = 0.0;  // the lambda_xi slot
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int j = C0 + 16 * t + l15;
-            const bool ok_c = j < n;
-            const double a_c = ok_c ? al[j] : 0.0;
+        for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const bool ok = ok_r[r] && ok_c;
-                A[t][r] = ok ? a_r[r] * a_c - A[t][r] : 0.0;
-                const double ip = ok ? a.iphiphi[(int64_t)(R0 + 16 * w + lq + 4 * r) * n + j] : 0.0;
+                const int64_t at = (int64_t)(R0 + 16 * w + lq + 4 * r) * n + C0 + 16 * t + l15;
+                const double ip = ok_r[r] && ok_c[t] ? a.iphiphi[at] : 0.0;
                 v = v + A[t][r] * ip;
             }
-        }
-        v = sf_wave_sum(v);
-        if (lane == 0) s_red[w * SF_EG_NQ] = v;
-        sf_emu_grad_flush(1, wgt, s_red, s_sum, tid);  // (its first barrier also publishes the staged columns)
+        sf_grad_put(v, s_red + w * SF_EG_NQ, lane);
+        sf_grad_flush(1, wgt, s_red, SF_EG_NQ, s_sum, tid);  // (its first barrier also publishes the staged columns)
         if (!rbf) continue;  // (the same in every thread)
         // A_ij K_c[g,h] where row and column belong to one component, zero elsewhere: one exp per entry
         int c_r[4];
@@ -170,16 +137,15 @@ __global__ __launch_bounds__(256) void k_emu_grad(const sf_emu_grad_args a) {
                         s = s + A[t][r] * (d * d);
                     }
                 }
-                s = sf_wave_sum(s);
-                if (lane == 0) s_red[w * SF_EG_NQ + q] = s;
+                sf_grad_put(s, s_red + w * SF_EG_NQ + q, lane);
             }
-            sf_emu_grad_flush(nq, wgt, s_red, s_sum + 1 + (c - ci0) * nq, tid);
+            sf_grad_flush(nq, wgt, s_red, SF_EG_NQ, s_sum + 1 + (c - ci0) * nq, tid);
         }
     }
     __syncthreads();
     // slots in the order of the raw row: lambda_xi, variances[m], lengthscales[m][P]
-    double* part = a.part + ((int64_t)b * a.nbr + I) * a.nslots;
-    for (int q = tid; q < a.nslots; q += 256) {
+    double* part = sf_grad_part(a.o, b, I);
+    for (int q = tid; q < a.o.nslots; q += 256) {
         double s;
         if (q == 0) {
             s = -s_sum[0] / hb[0];
@@ -191,22 +157,9 @@ __global__ __launch_bounds__(256) void k_emu_grad(const sf_emu_grad_args a) {
     }
 }
 
-__global__ void k_emu_grad_sum(const sf_emu_grad_args a) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-    if (q >= a.nslots) return;
-    double s = 0.0;
-    if (a.info[b] != 0) {
-        s = __builtin_nan("");
-    } else {
-        for (int I = 0; I < a.nbr; ++I) s = s + a.part[((int64_t)b * a.nbr + I) * a.nslots + q];
-        s = 0.5 * s;
-    }
-    a.grad[(int64_t)b * a.grad_stride + q] = s;
-}
-
 size_t sf_emu_grad_work_doubles(int M, int P, int m, int batch) {
     if (M <= 0 || P <= 0 || m <= 0 || batch <= 0) return 0;
-    return (size_t)batch * (size_t)(((size_t)m * M + SF_LEAF - 1) / SF_LEAF) * (size_t)sf_emu_grad_slots(m, P);
+    return sf_grad_part_doubles((size_t)m * M, sf_emu_grad_slots(m, P), batch);
 }
 // every argument is the caller's to check (sf_emulator_loglike_grad_batch does, before its first launch)
 int sf_launch_emu_grad(const double* grid, int M, int P, int m, const double* hyper, int hyper_stride, int batch,
@@ -215,20 +168,13 @@ int sf_launch_emu_grad(const double* grid, int M, int P, int m, const double* hy
                        hipStream_t s) {
     sf_emu_grad_args a;
     a.grid = grid, a.M = M, a.P = P, a.m = m, a.n = m * M, a.hyper = hyper, a.hyper_stride = hyper_stride, a.iphiphi = iphiphi;
-    a.L = L, a.npad = npad, a.lda = lda, a.stride = stride, a.winv = winv, a.alpha = alpha, a.ld_alpha = ld_alpha, a.info = info;
-    a.part = part, a.grad = grad, a.grad_stride = grad_stride;
-    a.nbr = (a.n + SF_LEAF - 1) / SF_LEAF, a.nslots = sf_emu_grad_slots(m, P), a.batch = batch;
+    a.L = L, a.npad = npad, a.lda = lda, a.stride = stride, a.winv = winv, a.alpha = alpha, a.ld_alpha = ld_alpha;
+    a.o = sf_grad_out{info, part, (a.n + SF_LEAF - 1) / SF_LEAF, sf_emu_grad_slots(m, P), batch, grad, grad_stride};
     if (M <= 0 || m <= 0 || P < 1 || P > SF_EG_PMAX || npad % SF_LEAF != 0 || npad < a.n || lda < npad || ld_alpha < a.n ||
-        grad_stride < a.nslots || hyper_stride < a.nslots || batch < 1 || batch > 65535) {
+        grad_stride < a.o.nslots || hyper_stride < a.o.nslots || batch < 1 || batch > 65535) {
         sf_set_error("emu grad: P in 1 .. %d, npad a multiple of %d >= m M, grad_stride and hyper_stride >= 1 + m + m P, "
                      "ld_alpha >= m M, batch in 1 .. 65535", SF_EG_PMAX, SF_LEAF);
         return SF_EINVAL;
     }
-    const long long nblk = (long long)batch * a.nbr;
-    SF_CHECK(sf_check_fill_grid(nblk));
-    hipLaunchKernelGGL(k_emu_grad, dim3((unsigned)nblk), dim3(256), 0, s, a);
-    SF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_emu_grad_sum, dim3((a.nslots + 63) / 64, batch), dim3(64), 0, s, a);
-    SF_LAUNCH_CHECK();
-    return SF_OK;
+    return sf_launch_grad(k_emu_grad, a, a.o, s);
 }

@@ -280,16 +280,53 @@ extern "C" int sf_emulator_v11_build_batch(const double* d_grid, int M, int P, i
                                      d_w_hat, d_R, ldr, (hipStream_t)stream);
 }
 
-// The training objective for B hyper-parameter rows (workspace: carve_emu_train)
+// The training objective for B hyper-parameter rows, alone or with its gradient in the logs of the hyper-parameters
+// (workspace: carve_emu_train, with the grid axes for the gradient)
+static bool emu_counts_ok(int M, int P, int m, int B) {
+    return M > 0 && m > 0 && P >= 1 && P <= 8 && B >= 1 && B <= 65535 && (int64_t)m * M <= (1 << 30) &&
+           (int64_t)m * (P + 1) < (1 << 30);
+}
 extern "C" size_t sf_emulator_loglike_workspace_bytes(int M, int m, int B) { return carve_emu_train(M, m, B, nullptr, 0).bytes; }
-// build (lower triangle, R = w_hat), factorisation, logdet / sqmah, finish: the four stages both calls below run, on one layout
+extern "C" size_t sf_emulator_loglike_grad_workspace_bytes(int M, int P, int m, int B) {
+    if (!emu_counts_ok(M, P, m, B)) return 0;
+    return carve_emu_train(M, m, B, nullptr, 0, P).bytes;
+}
+// every argument check of the three calls below, before any HIP call, and their workspace.  grad_stride: NULL for a call
+// without a gradient, whose workspace ends behind the factorisation's
+static int emu_open(const char* name, bool required, int M, int P, int m, int hyper_stride, int B, const int* grad_stride,
+                    void* d_work, size_t work_bytes, EmuTrainWork* w) {
+    if (!required || !d_work) {
+        sf_set_error("%s: a required pointer is NULL", name);
+        return SF_EINVAL;
+    }
+    if (!emu_counts_ok(M, P, m, B)) {
+        sf_set_error("%s: M=%d and m=%d must be positive, P=%d in 1 .. 8, B=%d in 1 .. 65535", name, M, m, P, B);
+        return SF_EINVAL;
+    }
+    const int slots = sf_emu_grad_slots(m, P);
+    if (hyper_stride < slots || (grad_stride && *grad_stride < slots)) {
+        sf_set_error("%s: hyper_stride=%d and, with a gradient, grad_stride=%d must be at least 1 + m + m P = %d", name, hyper_stride,
+                     grad_stride ? *grad_stride : 0, slots);
+        return SF_EINVAL;
+    }
+    if ((uintptr_t)d_work & 255) {
+        sf_set_error("%s: d_work must be 256-byte aligned", name);
+        return SF_EINVAL;
+    }
+    *w = carve_emu_train(M, m, B, d_work, work_bytes, grad_stride ? P : 0);
+    if (work_bytes < w->bytes) {
+        sf_set_error("%s: workspace of %zu bytes, %zu needed", name, work_bytes, w->bytes);
+        return SF_ENOMEM;
+    }
+    return SF_OK;
+}
+// build (lower triangle, R = w_hat), factorisation, logdet / sqmah, finish: the four stages of the likelihood
 static int emu_loglike_stages(const EmuTrainWork& w, const double* d_grid, int M, int P, int m, const double* d_hyper,
                               int hyper_stride, int B, const double* d_iphiphi, const double* d_w_hat, double* d_lnl,
                               double* d_logdet, double* d_sqmah, int* d_info, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     double* logdet = d_logdet ? d_logdet : w.logdet;
     double* sqmah = d_sqmah ? d_sqmah : w.sqmah;
-    // (every argument check of the stages is made by the first one before it enqueues anything: P <= 8 is the build's)
     int rc = sf_launch_v11_build_batch(d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, w.A, w.npad, w.lda, w.stride, 1, d_w_hat,
                                        w.R, w.npad, s);
     if (rc) return rc;
@@ -303,57 +340,11 @@ static int emu_loglike_stages(const EmuTrainWork& w, const double* d_grid, int M
 extern "C" int sf_emulator_loglike_batch(const double* d_grid, int M, int P, int m, const double* d_hyper, int hyper_stride,
                                          int B, const double* d_iphiphi, const double* d_w_hat, double* d_lnl, double* d_logdet,
                                          double* d_sqmah, int* d_info, void* d_work, size_t work_bytes, void* stream) {
-    const EmuTrainWork w = carve_emu_train(M, m, B, d_work, work_bytes);
-    if (!w.bytes || !d_grid || !d_hyper || !d_iphiphi || !d_w_hat || !d_lnl || !d_info || !d_work || P <= 0 || B > 65535 ||
-        (int64_t)hyper_stride < 1 + (int64_t)m + (int64_t)m * P || ((uintptr_t)d_work & 255)) {
-        sf_set_error("sf_emulator_loglike_batch: bad argument (d_lnl, d_info and a 256-byte aligned d_work are required, "
-                     "hyper_stride >= 1 + m + m P, B <= 65535)");
-        return SF_EINVAL;
-    }
-    if (work_bytes < w.bytes) {
-        sf_set_error("sf_emulator_loglike_batch: workspace of %zu bytes, %zu needed", work_bytes, w.bytes);
-        return SF_ENOMEM;
-    }
+    EmuTrainWork w;
+    SF_CHECK(emu_open("sf_emulator_loglike_batch", d_grid && d_hyper && d_iphiphi && d_w_hat && d_lnl && d_info, M, P, m,
+                      hyper_stride, B, nullptr, d_work, work_bytes, &w));
     return emu_loglike_stages(w, d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, d_w_hat, d_lnl, d_logdet, d_sqmah, d_info,
                               stream);
-}
-
-// The training objective and its gradient in the logs of the hyper-parameters (workspace: carve_emu_train with the grid axes)
-static bool emu_grad_counts_ok(int M, int P, int m, int B) {
-    return M > 0 && m > 0 && P >= 1 && P <= 8 && B >= 1 && B <= 65535 && (int64_t)m * M <= (1 << 30) &&
-           (int64_t)m * (P + 1) < (1 << 30);
-}
-extern "C" size_t sf_emulator_loglike_grad_workspace_bytes(int M, int P, int m, int B) {
-    if (!emu_grad_counts_ok(M, P, m, B)) return 0;
-    return carve_emu_train(M, m, B, nullptr, 0, P).bytes;
-}
-// every argument check of both calls below, before any HIP call
-static int emu_grad_open(const char* name, bool required, int M, int P, int m, int hyper_stride, int B, int grad_stride,
-                         void* d_work, size_t work_bytes, EmuTrainWork* w) {
-    if (!required || !d_work) {
-        sf_set_error("%s: a required pointer is NULL", name);
-        return SF_EINVAL;
-    }
-    if (!emu_grad_counts_ok(M, P, m, B)) {
-        sf_set_error("%s: M=%d and m=%d must be positive, P=%d in 1 .. 8, B=%d in 1 .. 65535", name, M, m, P, B);
-        return SF_EINVAL;
-    }
-    const int slots = sf_emu_grad_slots(m, P);
-    if (hyper_stride < slots || grad_stride < slots) {
-        sf_set_error("%s: hyper_stride=%d and grad_stride=%d must be at least 1 + m + m P = %d", name, hyper_stride, grad_stride,
-                     slots);
-        return SF_EINVAL;
-    }
-    if ((uintptr_t)d_work & 255) {
-        sf_set_error("%s: d_work must be 256-byte aligned", name);
-        return SF_EINVAL;
-    }
-    *w = carve_emu_train(M, m, B, d_work, work_bytes, P);
-    if (work_bytes < w->bytes) {
-        sf_set_error("%s: workspace of %zu bytes, %zu needed", name, work_bytes, w->bytes);
-        return SF_ENOMEM;
-    }
-    return SF_OK;
 }
 // 1/2 sum (alpha alpha^T - v11^-1) o dv11/dtheta from the alpha and the X the stages before left in the workspace
 static int emu_grad_contract(const EmuTrainWork& w, const double* d_grid, int M, int P, int m, const double* d_hyper,
@@ -366,8 +357,8 @@ extern "C" int sf_emulator_loglike_grad_batch(const double* d_grid, int M, int P
                                               int B, const double* d_iphiphi, const double* d_w_hat, double* d_lnl, double* d_grad,
                                               int grad_stride, int* d_info, void* d_work, size_t work_bytes, void* stream) {
     EmuTrainWork w;
-    SF_CHECK(emu_grad_open("sf_emulator_loglike_grad_batch", d_grid && d_hyper && d_iphiphi && d_w_hat && d_lnl && d_grad && d_info,
-                           M, P, m, hyper_stride, B, grad_stride, d_work, work_bytes, &w));
+    SF_CHECK(emu_open("sf_emulator_loglike_grad_batch", d_grid && d_hyper && d_iphiphi && d_w_hat && d_lnl && d_grad && d_info, M, P, m,
+                      hyper_stride, B, &grad_stride, d_work, work_bytes, &w));
     hipStream_t s = (hipStream_t)stream;
     SF_CHECK(emu_loglike_stages(w, d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, d_w_hat, d_lnl, nullptr, nullptr, d_info,
                                 stream));
@@ -382,8 +373,8 @@ extern "C" int sf_debug_emulator_grad_contract(const double* d_grid, int M, int 
                                                int B, const double* d_iphiphi, double* d_grad, int grad_stride, const int* d_info,
                                                void* d_work, size_t work_bytes, void* stream) {
     EmuTrainWork w;
-    SF_CHECK(emu_grad_open("sf_debug_emulator_grad_contract", d_grid && d_hyper && d_iphiphi && d_grad && d_info, M, P, m,
-                           hyper_stride, B, grad_stride, d_work, work_bytes, &w));
+    SF_CHECK(emu_open("sf_debug_emulator_grad_contract", d_grid && d_hyper && d_iphiphi && d_grad && d_info, M, P, m, hyper_stride, B,
+                      &grad_stride, d_work, work_bytes, &w));
     return emu_grad_contract(w, d_grid, M, P, m, d_hyper, hyper_stride, B, d_iphiphi, d_info, d_grad, grad_stride,
                              (hipStream_t)stream);
 }

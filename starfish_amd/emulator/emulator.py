@@ -440,12 +440,12 @@ class Emulator:
         return ([keys.index("log_lambda_xi")] + [i for i, k in enumerate(keys) if k.startswith("log_variance:")]
                 + [i for i, k in enumerate(keys) if k.startswith("log_lengthscale:")])
 
-    def _hyper_batches(self, where, P, width, workspace_bytes, enqueue):
-        """The rows of ``P`` (logs) through a batched training call: checked, turned into raw rows, cut into chunks that fit the
-        free device memory, run under :func:`D.retry_internal`.  ``workspace_bytes(M, npar, m, nb)`` is the call's size query;
-        ``enqueue(lib, td, (M, npar, m), d_hyper, S, nb, d_out, d_info, ws, stream)`` enqueues it for ``nb`` rows, its
-        ``width * nb`` doubles going to ``d_out``.  Doubles and status codes share one buffer: one download per chunk.
-        Returns the doubles of every chunk in order and ``info (B,)``."""
+    def _hyper_batches(self, where, P, grad):
+        """The rows of ``P`` (logs) through the batched training call, ``sf_emulator_loglike_grad_batch`` with ``grad`` and
+        ``sf_emulator_loglike_batch`` without: checked, turned into raw rows and run by :func:`D.run_chunked` on the workspace ``_train_dev["ws_batch"]``
+        (a fixed part, the factorisation's partial-sum regions, plus a part per matrix; at most 65535 rows a call).  Doubles
+        and status codes share one packed buffer, lnl[B], then the gradient rows [B][S], then info[B]: one download.
+        Returns ``lnl (B,)``, the raw gradient rows ``(B, S)`` (``(B, 0)`` without) and ``info (B,)``."""
         from .. import _lib
 
         P = np.atleast_2d(np.asarray(P, dtype=np.float64))
@@ -462,31 +462,39 @@ class Emulator:
         td = self._train_resident(lib, dev)
         hyper = self._hyper_rows(P)
         B, S = hyper.shape
+        width = 1 + S if grad else 1  # doubles of a row
 
-        def run(again):
-            chunks = []
-            info = np.empty(B, dtype=np.int32)
-            # chunks sized from the free device memory as DeviceOrder.max_batch does; the workspace is a fixed part (the
-            # factorisation's partial-sum regions) plus a part per matrix
-            one, two = (int(workspace_bytes(lib, M, npar, m, b)) for b in (1, 2))
-            if not one:
-                raise ValueError(f"{where}: the device does not take {npar} grid dimensions")
-            held = td["ws_batch"].numel() if td["ws_batch"] is not None else 0
-            cap = D.units_that_fit(dev, 2 * one - two, two - one, held, 65535)
-            s = D.stream_ptr(dev)
-            for lo in range(0, B, cap):
-                nb = min(cap, B - lo)
-                ws = D.grow_workspace(td, "ws_batch", int(workspace_bytes(lib, M, npar, m, nb)), dev)
-                d_hyper = D.to_dev(hyper[lo:lo + nb], dev)
-                out = torch.empty((8 * width + 4) * nb, dtype=torch.uint8, device=dev)  # the doubles, then info[nb]
-                enqueue(lib, td, (M, npar, m), d_hyper, S, nb, C.c_void_p(out.data_ptr()),
-                        C.c_void_p(out.data_ptr() + 8 * width * nb), ws, s)
-                host = out.cpu().numpy()
-                chunks.append(host[:8 * width * nb].view(np.float64))
-                info[lo:lo + nb] = host[8 * width * nb:].view(np.int32)
-            return (chunks, info), info
+        def size(units):
+            if grad:
+                return int(lib.sf_emulator_loglike_grad_workspace_bytes(M, npar, m, units))
+            return int(lib.sf_emulator_loglike_workspace_bytes(M, m, units))
 
-        return D.retry_internal(lib, f"Emulator.{where}", run, count=B, stacklevel=5)
+        one, two = size(1), size(2)
+        if not one:
+            raise ValueError(f"{where}: the device does not take {npar} grid dimensions")
+
+        def buffers():
+            return D.to_dev(hyper, dev), torch.empty((8 * width + 4) * B, dtype=torch.uint8, device=dev)
+
+        def enqueue(bufs, lo, hi, ws):
+            d_hyper, out = bufs
+            at = lambda byte: C.c_void_p(out.data_ptr() + byte)  # noqa: E731
+            head = (D.ptr(td["grid"]), M, npar, m, D.ptr(d_hyper[lo:hi]), S, hi - lo, D.ptr(td["iphiphi"]), D.ptr(td["w_hat_dev"]),
+                    at(8 * lo))
+            tail = (at(8 * width * B + 4 * lo), D.ptr(ws), ws.numel(), D.stream_ptr(dev))
+            if grad:
+                _lib.check(lib.sf_emulator_loglike_grad_batch(*head, at(8 * (B + lo * S)), S, *tail), "sf_emulator_loglike_grad_batch")
+            else:
+                _lib.check(lib.sf_emulator_loglike_batch(*head, None, None, *tail), "sf_emulator_loglike_batch")
+
+        def download(bufs):
+            host = bufs[1].cpu().numpy()
+            doubles = host[:8 * width * B].view(np.float64)
+            return dict(lnl=doubles[:B], grad=doubles[B:].reshape(B, width - 1), info=host[8 * width * B:].view(np.int32))
+
+        res = D.run_chunked(lib, f"Emulator.{where}", dev, td, "ws_batch", 2 * one - two, two - one, 65535, B, None,
+                            lambda units: D.grow_workspace(td, "ws_batch", size(units), dev), buffers, enqueue, download, count=B)
+        return res["lnl"], res["grad"], res["info"]
 
     def log_likelihood_batch(self, P, return_info=False):
         """:meth:`log_likelihood` (Starfish/emulator/emulator.py:602-619) for the ``B`` rows of ``P`` -- hyper-parameter
@@ -496,17 +504,7 @@ class Emulator:
         definite -- where the scalar call raises), and with ``return_info`` also ``info``.  The emulator's own
         hyper-parameters, ``v11`` and ``_trained`` are not touched.  Batches that do not fit the free device memory are cut
         into chunks."""
-        from .. import _lib
-
-        def enqueue(lib, td, shape, d_hyper, S, nb, d_out, d_info, ws, s):
-            M, npar, m = shape
-            _lib.check(lib.sf_emulator_loglike_batch(
-                D.ptr(td["grid"]), M, npar, m, D.ptr(d_hyper), S, nb, D.ptr(td["iphiphi"]), D.ptr(td["w_hat_dev"]), d_out, None,
-                None, d_info, D.ptr(ws), ws.numel(), s), "sf_emulator_loglike_batch")
-
-        chunks, info = self._hyper_batches("log_likelihood_batch", P, 1,
-                                           lambda lib, M, npar, m, b: lib.sf_emulator_loglike_workspace_bytes(M, m, b), enqueue)
-        lnl = np.concatenate(chunks)
+        lnl, _, info = self._hyper_batches("log_likelihood_batch", P, False)
         return (lnl, info) if return_info else lnl
 
     @property
@@ -523,21 +521,7 @@ class Emulator:
         with ``info != 0`` get ``-inf`` and a NaN gradient row; with ``return_info`` ``info`` is returned as well.  The
         emulator's own hyper-parameters, ``v11`` and ``_trained`` are not touched.  Batches that do not fit the free device
         memory are cut into chunks."""
-        from .. import _lib
-
-        S = len(self.hyperparams)
-
-        def enqueue(lib, td, shape, d_hyper, S, nb, d_out, d_info, ws, s):  # lnl[nb], then the gradient rows [nb][S]
-            M, npar, m = shape
-            _lib.check(lib.sf_emulator_loglike_grad_batch(
-                D.ptr(td["grid"]), M, npar, m, D.ptr(d_hyper), S, nb, D.ptr(td["iphiphi"]), D.ptr(td["w_hat_dev"]), d_out,
-                C.c_void_p(d_out.value + 8 * nb), S, d_info, D.ptr(ws), ws.numel(), s), "sf_emulator_loglike_grad_batch")
-
-        chunks, info = self._hyper_batches("log_likelihood_gradient_batch", P, 1 + S,
-                                           lambda lib, M, npar, m, b: lib.sf_emulator_loglike_grad_workspace_bytes(M, npar, m, b),
-                                           enqueue)
-        lnl = np.concatenate([c[:len(c) // (1 + S)] for c in chunks])
-        grad = np.concatenate([c[len(c) // (1 + S):].reshape(-1, S) for c in chunks])
+        lnl, grad, info = self._hyper_batches("log_likelihood_gradient_batch", P, True)
         back = np.argsort(self._hyper_order())  # raw slot of every column of P
         grad = np.ascontiguousarray(grad[:, back])
         return (lnl, grad, info) if return_info else (lnl, grad)

@@ -269,6 +269,53 @@ def test_python_methods_return_the_columns_in_gradient_labels_order():
         emu.log_likelihood_gradient()
 
 
+def test_python_methods_cut_into_chunks_give_the_bits_of_one_call(monkeypatch):
+    """B = 5 rows through Emulator.log_likelihood_batch and log_likelihood_gradient_batch with the chunk size forced to 2
+    (chunks of 2, 2 and 1 on one workspace sized for 2 rows), then as one call: every array equal bit for bit.  Once more
+    with row 2 not positive definite (the raw row of the test above; no vector of logs gives a negative lambda_xi, so the
+    raw rows are handed in behind _hyper_rows): -inf, a NaN gradient row and its info, the neighbours' bits untouched."""
+    from starfish_amd import _device as D
+    from starfish_amd import _lib
+
+    need = _lib.require_gpu().sf_emulator_loglike_grad_workspace_bytes
+    emu = _emulator(2)
+    m, (M, P) = emu.ncomps, emu.grid_points.shape
+    P0 = emu.get_param_vector()
+    X = np.vstack([P0, P0 + np.random.default_rng(5).uniform(-0.2, 0.2, (4, P0.size))])
+    good = emu._hyper_rows(X)
+    bad = good.copy()
+    bad[2] = np.concatenate([[-1.0], np.full(m, 1e-6), emu.lengthscales.ravel()])  # -iPhiPhi + 1e-6 RBF: indefinite
+
+    def both():
+        lnl, info = emu.log_likelihood_batch(X, return_info=True)
+        lnl_g, grad, info_g = emu.log_likelihood_gradient_batch(X, return_info=True)
+        return dict(lnl=lnl, info=info, lnl_g=lnl_g, grad=grad, info_g=info_g)
+
+    results = []
+    for rows in (good, bad):
+        emu._train_dev = None  # (the workspace starts empty: its size tells the chunk it was reserved for)
+        with monkeypatch.context() as mp:
+            mp.setattr(emu, "_hyper_rows", lambda _, rows=rows: rows)
+            with monkeypatch.context() as cut:
+                cut.setattr(D, "units_that_fit", lambda *a, **k: 2)
+                chunked = both()
+                assert emu._train_dev["ws_batch"].numel() == need(M, P, m, 2)
+            whole = both()
+        assert emu._train_dev["ws_batch"].numel() == need(M, P, m, 5)
+        for key, want in whole.items():
+            assert chunked[key].shape == want.shape and chunked[key].dtype == want.dtype, key
+            np.testing.assert_array_equal(chunked[key], want, err_msg=key)  # (NaN equals NaN at the same place)
+        np.testing.assert_array_equal(whole["lnl_g"], whole["lnl"])
+        np.testing.assert_array_equal(whole["info_g"], whole["info"])
+        results.append(whole)
+    clean, mixed = results
+    assert (clean["info"] == 0).all() and np.isfinite(clean["lnl"]).all() and np.isfinite(clean["grad"]).all()
+    assert clean["grad"].shape == (5, P0.size)
+    assert mixed["info"][2] > 0 and mixed["lnl"][2] == -np.inf and np.isnan(mixed["grad"][2]).all()
+    for key in clean:
+        np.testing.assert_array_equal(mixed[key][[0, 1, 3, 4]], clean[key][[0, 1, 3, 4]], err_msg=key)
+
+
 def test_gradient_training_reaches_the_simplex_result_in_fewer_evaluations():
     """m = 2, M = 27 (9 hyper-parameters), from the defaults: the L-BFGS-B run ends no lower than the serial Nelder-Mead run
     minus 1e-6 |lnL| (the slack of Nelder-Mead's own fatol = 1e-4 at |lnL| of a few tens) and asks for fewer objective

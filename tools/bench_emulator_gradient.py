@@ -2,7 +2,7 @@
 hyper-parameters) on synthetic libraries.
     python tools/bench_emulator_gradient.py [reps] [train]
 Per m M in {216 (m = 8, M = 27), 1320 (m = 4, M = 330: the worked example)} and B in {1, 8, 32}: ms per call of the whole
-sf_emulator_loglike_grad_batch, of its contraction launches alone (k_emu_grad and k_emu_grad_sum of sf_emu_grad.h, through
+sf_emulator_loglike_grad_batch, of its contraction launches alone (k_emu_grad of sf_emu_grad.h and k_grad_sum of sf_grad_frame.h, through
 sf_debug_emulator_grad_contract on the workspace the call left) and, beside them from the same run, of
 sf_emulator_loglike_batch (one likelihood evaluation per row); the call's cost in likelihood evaluations is the ratio.
 Second leg (skipped with train = 0): Emulator.train from the defaults three ways -- the serial Nelder-Mead loop,

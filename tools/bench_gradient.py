@@ -1,7 +1,7 @@
 """Stand-alone timing of sf_loglike_grad_batch (likelihood gradient in the covariance hyper-parameters) on synthetic orders.
     python tools/bench_gradient.py [reps] [B] [N ...]
 Per N in {3008, 4096}, batch 128, a global kernel and 0 or 4 local kernels: ms per call of the whole sf_loglike_grad_batch, of
-its contraction launches alone (k_cov_grad and k_cov_grad_sum of sf_cov_grad.h, through sf_debug_loglike_grad_contract on the
+its contraction launches alone (k_cov_grad of sf_cov_grad.h and k_grad_sum of sf_grad_frame.h, through sf_debug_loglike_grad_contract on the
 workspace the call left) and, beside them from the same run, of sf_pointwise_batch (the same sequence up to and including the
 inverse's launches) and of sf_loglike_batch (one likelihood evaluation)."""
 import torch
