@@ -4,8 +4,8 @@
 extern "C" int sf_banded_max_halfwidth(const sf_ctx* c) {
     if (!c || !c->n) return SF_EINVAL;
     if (!c->monotonic) return -1;
-    const int lds_max = sf_band_max_halfwidth(c->m + 1), wide_max = SF_BAND_TILES_MAX_HALFWIDTH;
-    return c->m + 1 <= 48 ? (wide_max > lds_max ? wide_max : lds_max) : lds_max;
+    const bool tiles = sfb_admit(SF_BAND_TILES_MAX_HALFWIDTH, c->m + 1) == SFB_TILES;  // (beyond what the window takes)
+    return tiles ? SF_BAND_TILES_MAX_HALFWIDTH : sf_band_max_halfwidth(c->m + 1);
 }
 extern "C" int sf_banded_window_halfwidth(const sf_ctx* c) {
     if (!c || !c->n) return SF_EINVAL;
@@ -78,17 +78,15 @@ extern "C" int sf_loglike_banded_batch(sf_ctx* c, const sf_model_desc* mdl, int 
     if (sf != s) SF_HIP(hipStreamWaitEvent(s, aux->join, 0));
     {
         ProfScope ps(s, PS_POTRF);
-        const int n16 = (c->n + 15) / 16 * 16;
-        if (bw.tiles)
-            rc = sf_launch_potrf_band(c->n, c->npad, halfwidth, B, w.resid, c->npad, w.Y, c->m + 1, c->npad,
-                                      (int64_t)c->mpad * c->npad, bw.logdet_band, bw.gram, w.info_c, bw.tiles, s);
-        else if (sf_band_twisted_applicable(n16, halfwidth, B))
-            rc = sf_launch_band_forms_twisted(bw.band, n16, halfwidth, bw.ldb, sband, B, w.resid, c->npad, w.Y,
-                                              c->m + 1, c->npad, (int64_t)c->mpad * c->npad, bw.logdet_band,
-                                              bw.gram, w.info_c, bw.twist, s);
-        else
-            rc = sf_launch_band_forms(bw.band, n16, halfwidth, bw.ldb, sband, B, w.resid, c->npad, w.Y, c->m + 1,
-                                      c->npad, (int64_t)c->mpad * c->npad, bw.logdet_band, bw.gram, w.info_c, s);
+        sf_band_call k = {};
+        k.band = bw.band, k.sband = sband, k.ldb = bw.ldb, k.halfwidth = halfwidth;
+        k.n = bw.tiles ? c->n : (c->n + 15) / 16 * 16;  // (the window's band is filled with identity rows up to whole blocks)
+        k.batch = B;
+        k.r = sf_band_rhs{w.Y, (int64_t)c->mpad * c->npad, c->npad, c->m + 1, w.resid, c->npad};
+        k.logdet = bw.logdet_band, k.gram = bw.gram, k.info = w.info_c;
+        if (bw.tiles) rc = sf_launch_potrf_band(k, c->npad, bw.tiles, s);
+        else if (sf_band_twisted_applicable(k.n, halfwidth, B)) rc = sf_launch_band_forms_twisted(k, bw.twist, s);
+        else rc = sf_launch_band_forms(k, s);
         if (rc) return rc;
     }
     {
@@ -110,6 +108,10 @@ extern "C" int sf_band_logdet_gram_batch(const double* d_band, int n, int halfwi
     }
     hipStream_t s = (hipStream_t)stream;
     SF_HIP(hipMemsetAsync(d_info, 0, sizeof(int) * (size_t)batch, s));
-    return sf_launch_band_forms(d_band, n, halfwidth, ldb, stride, batch, nullptr, 0, d_rhs, nrhs, ldr, rhs_stride,
-                                d_logdet, d_gram, d_info, s);
+    sf_band_call k = {};
+    k.band = d_band, k.sband = stride, k.ldb = ldb, k.halfwidth = halfwidth;
+    k.n = n, k.batch = batch;
+    k.r = sf_band_rhs{d_rhs, rhs_stride, ldr, nrhs, nullptr, 0};
+    k.logdet = d_logdet, k.gram = d_gram, k.info = d_info;
+    return sf_launch_band_forms(k, s);
 }

@@ -18,15 +18,11 @@
 // the dense path's rate, spread over the whole chip (round 1's in-place sweep kept one matrix on one CU and streamed
 // its operands from L2: 7.5 / 10.3 / 30.1 ms at W = 241 / 361 / 724 against 5.0 / 6.0 / 11.3 here).  The border rows come out as Z = R L^-T, their diagonal tile as -Z Z^T: the Gram matrix the
 // Woodbury step needs; L_band's diagonal gives logdet(Bd).  The diagonal tile of the border is never factorised.
-// border rows: row 0 <- rhs0 (the residual), rows 1 .. nrhs-1 <- rhs rows, everything else (and the border's own
-// diagonal tile) zero
-__global__ __launch_bounds__(256) void k_band_border_rows(const double* __restrict__ rhs0, int64_t srhs0, const double* __restrict__ rhs,
-                                                          int64_t srhs, int ldr, int nrhs, int n, int nband, double* __restrict__ A,
-                                                          int64_t sA, int lda) {
+// border rows: the right-hand sides (sf_band_rhs), everything else (and the border's own diagonal tile) zero
+__global__ __launch_bounds__(256) void k_band_border_rows(sf_band_rhs rhs, int n, int nband, double* __restrict__ A, int64_t sA, int lda) {
     const int b = blockIdx.z, r = blockIdx.y, col = blockIdx.x * 256 + threadIdx.x;
     if (col >= nband + 64) return;
-    double v = 0.0;
-    if (r < nrhs && col < n) v = r == 0 ? rhs0[(int64_t)b * srhs0 + col] : rhs[(int64_t)b * srhs + (int64_t)(r - 1) * ldr + col];
+    const double v = r < rhs.nrhs && col < n ? rhs.of(b).row(r)[col] : 0.0;
     A[(int64_t)b * sA + (int64_t)(nband + r) * lda + col] = v;
 }
 __global__ __launch_bounds__(256) void k_band_tiles_finish(const double* __restrict__ A, int64_t sA, int lda, int nband, int nrhs,
@@ -57,12 +53,12 @@ size_t sf_band_tiles_doubles(int nband, int batch) {  // the dense-strided array
 
 // The lower 128 x 128 tiles that meet the band are in place at the start of `tiles` (k_band_fill's tile mode: row
 // stride sf_band_tiles_lda(nband), nband + 64 rows per matrix, zeros where the band ends inside a tile, identity
-// padding from n to nband = n rounded up to 64); `tiles` holds sf_band_tiles_doubles(nband, batch) doubles.  rhs0 /
-// rhs: the right-hand sides (row 0 separate, as in sf_launch_band_forms).  Outputs logdet(Bd) and the nrhs x nrhs
+// padding from n to nband = n rounded up to 64); `tiles` holds sf_band_tiles_doubles(nband, batch) doubles.  c.r: the
+// right-hand sides (as for sf_launch_band_forms; c.band is not read).  Outputs logdet(Bd) and the nrhs x nrhs
 // Gram matrix of the solved right-hand sides; info[b] (cleared by the caller) gets the first non-positive pivot.
-int sf_launch_potrf_band(int n, int nband, int halfwidth, int batch, const double* rhs0, int64_t srhs0, const double* rhs,
-                         int nrhs, int ldr, int64_t srhs, double* logdet, double* gram, int* info, double* tiles,
-                         hipStream_t s) {
+int sf_launch_potrf_band(const sf_band_call& c, int nband, double* tiles, hipStream_t s) {
+    const int n = c.n, halfwidth = c.halfwidth, batch = c.batch, nrhs = c.r.nrhs;
+    int* const info = c.info;
     if (nband % SF_LEAF != 0 || nband < n || batch <= 0 || nrhs < 1 || nrhs > 64 || halfwidth < 0 || !tiles) {
         sf_set_error("potrf_band: bad arguments (n=%d nband=%d halfwidth=%d nrhs=%d)", n, nband, halfwidth, nrhs);
         return SF_EINVAL;
@@ -74,8 +70,7 @@ int sf_launch_potrf_band(int n, int nband, int halfwidth, int batch, const doubl
     const int nt = (nband + GT - 1) / GT;
     const int wt = sf_band_tiles_wt(halfwidth);
 
-    hipLaunchKernelGGL(k_band_border_rows, dim3((next + 255) / 256, 64, batch), dim3(256), 0, s, rhs0, srhs0, rhs, srhs, ldr, nrhs, n,
-                       nband, A, sA, lda);
+    hipLaunchKernelGGL(k_band_border_rows, dim3((next + 255) / 256, 64, batch), dim3(256), 0, s, c.r, n, nband, A, sA, lda);
     SF_LAUNCH_CHECK();
 
     const sf_potrf_scratch ws = sf_potrf_scratch_of(work, next, batch);  // (one W buffer is used)
@@ -118,7 +113,7 @@ int sf_launch_potrf_band(int n, int nband, int halfwidth, int batch, const doubl
         const int last = (k + wt < nt - 1) ? k + wt : nt - 1;
         SF_TRY(launch_panel(k0, pw, (k + 1) * GT, last - k, true));
     }
-    hipLaunchKernelGGL(k_band_tiles_finish, dim3(batch), dim3(256), 0, s, A, sA, lda, nband, nrhs, logdet, gram);
+    hipLaunchKernelGGL(k_band_tiles_finish, dim3(batch), dim3(256), 0, s, A, sA, lda, nband, nrhs, c.logdet, c.gram);
     SF_LAUNCH_CHECK();
     return SF_OK;
 }

@@ -134,9 +134,6 @@ int sf_launch_potrf(double* A, int n, int lda, int64_t stride, int batch, int* i
 int sf_band_tiles_lda(int nband);
 size_t sf_band_tiles_doubles(int nband, int batch);
 int sf_band_tiles_wt(int halfwidth);  // tile (i, j) of a bordered band matrix meets the band iff i - j <= wt
-int sf_launch_potrf_band(int n, int nband, int halfwidth, int batch, const double* rhs0, int64_t srhs0, const double* rhs,
-                         int nrhs, int ldr, int64_t srhs, double* logdet, double* gram, int* info, double* tiles,
-                         hipStream_t s);
 int sf_set_persistent_potrf(int enable);  // 0 / 1: the dataflow sequence may be chosen; < 0: query.  Returns the previous value
 int sf_persistent_potrf_read_status(long long* out8);  // sf_persistent_potrf_status (include/starfish_amd.h)
 int sf_set_cholesky_sequence(int mode);  // -1 automatic (by batch size), 0 fused panel kernel, 1 unfused
@@ -237,20 +234,40 @@ int sf_launch_global_cov(const double* wave, int n, double amp, double ls, doubl
 int sf_launch_local_cov(const double* wave, int n, double amp, double mu, double sigma, int accumulate,
                         double* out, hipStream_t s);
 
-// sf_band.hip: banded Cholesky + forward substitution of (1 + m) right-hand sides -> logdet, Gram matrix
-int sf_band_max_halfwidth(int nrhs);
-int sf_launch_band_forms(const double* band, int n, int halfwidth, int ldb, int64_t sband, int batch,
-                         const double* rhs0, int64_t srhs0, const double* rhs, int nrhs, int ldr,
-                         int64_t srhs, double* logdet, double* gram, int* info, hipStream_t s,
-                         const double* logdet_add = nullptr, const double* gram_add = nullptr, int info_off = 0);
-// two half sweeps + separator (halves the sequential chain when 2*batch workgroups fit the chip)
-size_t sf_band_twisted_work_doubles(int halfwidth, int nrhs, int batch);
+// sf_band.hip (layers: sf_band_shape.h, sf_band_window.h, sf_band_sweep.h, sf_band_twist.h, sf_band_woodbury.h): banded
+// Cholesky + forward substitution of (1 + m) right-hand sides -> logdet, Gram matrix
+// The right-hand sides of a batch: row r of matrix b at rhs + b * srhs + r * ldr.  Optional separate source for row 0 (the
+// residual lives in its own buffer in the fused path): when rhs0 is given, rows 1.. come from rhs rows 0..
+struct sf_band_rhs {
+    const double* rhs;
+    int64_t srhs;
+    int ldr, nrhs;
+    const double* rhs0;
+    int64_t srhs0;
+    __device__ sf_band_rhs of(int b) const {  // matrix b alone, as a batch of one
+        return sf_band_rhs{rhs + (int64_t)b * srhs, 0, ldr, nrhs, rhs0 ? rhs0 + (int64_t)b * srhs0 : nullptr, 0};
+    }
+    __device__ const double* row(int r) const {  // row r of the first matrix
+        return rhs0 ? (r == 0 ? rhs0 : rhs + (int64_t)(r - 1) * ldr) : rhs + (int64_t)r * ldr;
+    }
+};
+// One call of the band solver: the band view (band[i*ldb + d] = A[i][i-d], d in [0, halfwidth], matrices sband apart), the
+// order and the batch, the right-hand sides; outputs logdet [batch], gram [batch][nrhs*nrhs], info [batch] (first
+// non-positive pivot, 1-based; left untouched otherwise)
+struct sf_band_call {
+    const double* band;
+    int64_t sband;
+    int ldb, halfwidth, n, batch;
+    sf_band_rhs r;
+    double *logdet, *gram;
+    int* info;
+};
+int sf_launch_band_forms(const sf_band_call& c, hipStream_t s);
+// two half sweeps + separator (halves the sequential chain when 2*batch workgroups fit the chip); work: sfb_twist_carve
 bool sf_band_twisted_applicable(int n, int halfwidth, int batch);
-int sf_launch_band_forms_twisted(const double* band, int n, int halfwidth, int ldb, int64_t sband, int batch,
-                                 const double* rhs0, int64_t srhs0, const double* rhs, int nrhs, int ldr,
-                                 int64_t srhs, double* logdet, double* gram, int* info, double* work,
-                                 hipStream_t s);
+int sf_launch_band_forms_twisted(const sf_band_call& c, double* work, hipStream_t s);
 int sf_launch_woodbury(const double* gram, int nrhs, int batch, const double* logdet_band, double* logdet,
                        double* sqmah, int* info, hipStream_t s);
-// wide bands (beyond the LDS window): bordered band matrices on the fused panel kernel, sf_launch_potrf_band
-#define SF_BAND_TILES_MAX_HALFWIDTH 768
+// sf_chol.hip (sf_chol_band.h): wide bands (beyond the LDS window) as bordered band matrices on the fused panel kernel;
+// c.band is not read: the tiles hold the matrix, nband rows of it
+int sf_launch_potrf_band(const sf_band_call& c, int nband, double* tiles, hipStream_t s);

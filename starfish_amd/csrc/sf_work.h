@@ -4,6 +4,7 @@
 #pragma once
 #include <type_traits>
 
+#include "sf_band_shape.h"
 #include "sf_ctx.h"
 
 struct Carve {
@@ -140,12 +141,12 @@ static BandWork carve_band(const sf_ctx* c, int B, int halfwidth, void* p, size_
     BandWork w;
     // Half-widths beyond the LDS window are factorised as bordered band matrices on the tile kernels of the dense
     // path (sf_launch_potrf_band); the band fill writes those tiles directly.
-    const bool tiles = halfwidth > sf_band_max_halfwidth(c->m + 1);
+    const bool tiles = sfb_admit(halfwidth, c->m + 1) != SFB_WINDOW;
     w.ldb = tiles ? 128 * (sf_band_tiles_wt(halfwidth) + 1) : ((halfwidth + 2) & ~1);
     w.band = tiles ? nullptr : k.take<double>((size_t)B * c->npad * w.ldb);  // (the tiles are filled directly)
     w.gram = k.take<double>((size_t)B * (c->m + 1) * (c->m + 1));
     w.logdet_band = k.take<double>((size_t)B);
-    w.twist = tiles ? nullptr : k.take<double>(sf_band_twisted_work_doubles(halfwidth, c->m + 1, B));
+    w.twist = tiles ? nullptr : k.take<double>(sfb_twist_carve(nullptr, halfwidth, c->m + 1, B).doubles);
     w.gtab = k.take<double>((size_t)B * (w.ldb + 2));
     w.tiles = tiles ? k.take<double>(sf_band_tiles_doubles(c->npad, B)) : nullptr;
     w.bytes = sf_align_up(k.off, 256);

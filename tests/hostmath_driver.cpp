@@ -1,12 +1,14 @@
 // Stand-alone driver of starfish_amd/csrc/sf_hostmath.cpp for tests/test_hostmath.py (host compiler, no HIP).
-// usage: hostmath_driver <lu|inv|emu|ext|tw> with the numbers on stdin (strtod: hex floats are exact); prints
+// usage: hostmath_driver <lu|inv|emu|ext|tw|grid|band> with the numbers on stdin (strtod: hex floats are exact); prints
 // "rc <code>", "err <text of sf_last_error()>", then one "<name> <hex floats...>" line per result.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
+#include "sf_band_shape.h"
 #include "sf_hostmath.h"
 
 static double next_double() {
@@ -95,8 +97,54 @@ int main(int argc, char** argv) {
         done(SF_OK);
         put("min_dv", {min_dv(w.data(), n)});
         put("loguniform", {is_loguniform(w.data(), n) ? 1.0 : 0.0});
+    } else if (cmd == "band") {  // the band solver's shape (sf_band_shape.h) for every half-width 0 .. wmax, nrhs 1 .. nmax
+        const int wmax = (int)next_double(), nmax = (int)next_double(), ncu = (int)next_double();
+        done(SF_OK);
+        std::vector<double> maxhw, shape, lds, workers, twist, carve, pays;
+        for (int nrhs = 1; nrhs <= nmax; ++nrhs) maxhw.push_back(sf_band_max_halfwidth(nrhs));
+        for (int w = 0; w <= wmax; ++w)
+            for (int nrhs = 1; nrhs <= nmax; ++nrhs) {
+                const int nbr = sfb_nbr(w), nrb = sfb_nrb(nrhs), nwaves = sfb_nwaves(nbr);
+                for (int v : {(int)sfb_admit(w, nrhs), nbr, nrb, nwaves, sfb_loader_groups(nwaves)}) shape.push_back(v);
+                const sfb_lds L = sfb_lds_layout(nbr, nrb);  // byte offsets of the regions, then the size
+                for (int off : {L.Wb, L.RH, L.Fb2, L.G, L.pv, L.red, L.sync, L.ptab, L.reserve, L.doubles}) lds.push_back(8.0 * off);
+                lds.push_back((double)L.bytes);
+                for (int wave = 0; wave < 16; ++wave) {  // position and update pairs of every wave (-1: no such wave)
+                    const int pos = wave < nwaves ? sfb_worker_pos(wave, nwaves) : -1;
+                    workers.push_back(pos);
+                    workers.push_back(pos < 0 ? -1 : sfb_worker_pairs(pos, nwaves - 1, nbr - 1 + nrb));
+                }
+                if (sfb_admit(w, nrhs) != SFB_WINDOW) continue;
+                for (int batch = 1; batch <= 3; batch += 2) {  // carved from a real allocation of the counted size
+                    const size_t count = sfb_twist_carve(nullptr, w, nrhs, batch).doubles;
+                    const std::unique_ptr<double[]> buf(new double[count]);
+                    const sfb_twist_work t = sfb_twist_carve(buf.get(), w, nrhs, batch);
+                    for (int v : {w, nrhs, batch}) carve.push_back(v);
+                    for (const double* p : {t.dumpM, t.dumpR, t.dumpG, t.dumpL, t.mband, t.mrhs, t.gadd, t.ladd})
+                        carve.push_back((double)(p - buf.get()));
+                    carve.push_back((double)t.doubles);
+                    carve.push_back((double)count);
+                }
+            }
+        for (int nbr = 3; nbr <= sfb_nbr(wmax); ++nbr)
+            for (int nblk = 6 * nbr; nblk <= 300; ++nblk) {
+                const sfb_twist t = sfb_twist_shape(nblk, nbr);
+                for (int v : {nbr, nblk, t.nm, t.kend0, t.kend1, (int)sfb_twist_fits(nblk, nbr)}) twist.push_back(v);
+            }
+        for (int batch = 1; batch <= 1600; ++batch)  // cfg 2: 256 block columns, nbr = 10
+            pays.push_back(sfb_twist_pays(256, 10, batch, ncu) ? 1.0 : 0.0);
+        pays.push_back(sfb_twist_pays(6 * 10 - 1, 10, 1, ncu) ? 1.0 : 0.0);  // too few block columns for two halves
+        put("consts", {(double)BB, (double)BS, (double)BLD, (double)SFB_PF, (double)SFB_PT, (double)SFB_LDS_MAX,
+                       (double)SF_BAND_TILES_MAX_HALFWIDTH});
+        put("maxhw", maxhw);
+        put("shape", shape);
+        put("lds", lds);
+        put("workers", workers);
+        put("twist", twist);
+        put("carve", carve);
+        put("pays", pays);
     } else {
-        fprintf(stderr, "usage: hostmath_driver <lu|inv|emu|ext|tw|grid> < numbers\n");
+        fprintf(stderr, "usage: hostmath_driver <lu|inv|emu|ext|tw|grid|band> < numbers\n");
         return 2;
     }
     return 0;

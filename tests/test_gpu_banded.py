@@ -155,6 +155,34 @@ def test_banded_batch_matches_reference_and_dense_n1024():
     np.testing.assert_array_equal(b2["lnl"][::-1], band["lnl"])
 
 
+def test_single_and_twisted_sweep_match_dense_n640():
+    """The same four walkers through both forms of the window sweep, at the smallest order that reaches both: N = 640 has
+    40 block columns, enough for two half sweeps up to nbr = 6 (half-widths up to 80).  The walkers are those of
+    walker_ball with half the global kernel's length scale: as they stand their bounds are 108 .. 141 pixels at any N,
+    which takes 60 block columns; halved, 56 .. 71.  Alone the four take two half sweeps, the merge and the separator
+    pass; as the first rows of a batch of 130 they take one sweep each.  Which form runs follows from the rule at the 256
+    compute units of an MI355X, as tests/test_hostmath.py states it (test_band_twisted_shape: batches up to 128 two half
+    sweeps, 129 .. 256 one).  Both are held to the dense factorisation of the same rows."""
+    o = synth.make_order(N=640)
+    oo = oracle_order(o)
+    do = device_order(oo)
+    plist = [synth.vector_to_oracle_params(p) for p in synth.walker_ball(o, B=130)]
+    for p in plist:
+        p["global_cov"] = (p["global_cov"][0], p["global_cov"][1] - np.log(2.0))
+    md, rows = pack_rows(do, plist)
+    hw = do.halfwidth_bound(md, rows)
+    print("half-width bounds:", int(hw.min()), "..", int(hw.max()))
+    assert hw.max() <= 80 and hw.max() <= do.banded_window_halfwidth()
+    dense = do.loglike(md, rows[:4])
+    assert (dense["info"] == 0).all()
+    for batch in (4, 130):
+        band = do.loglike(md, rows[:batch], solver="banded")
+        assert (band["info"] == 0).all()
+        for key, rtol in (("lnl", 1e-11), ("logdet", 1e-12), ("sqmah", 1e-9)):
+            print(batch, key, np.abs(band[key][:4] / dense[key] - 1).max())
+            np.testing.assert_allclose(band[key][:4], dense[key], rtol=rtol)
+
+
 def test_banded_halfwidth_too_small_is_flagged_and_auto_recovers():
     o = synth.make_order(N=1024)
     oo = oracle_order(o)

@@ -210,3 +210,118 @@ def test_twiddles(driver, nf):
     e = np.abs(v["tw"] - want).max()
     print(f"nf={nf}: max |tw - numpy| = {e:.3e}")
     assert len(v["tw"]) == nf and e <= TW_BOUND
+
+
+# ---- the band solver's shape (starfish_amd/csrc/sf_band_shape.h): what the kernel, its launchers and the workspace layout
+# share, for every half-width 0 .. 160 and every number of right-hand sides 1 .. 49.  The sizes below are written out here
+# a second time on purpose (the formulas the launchers used before the header existed): the header has to reproduce them.
+BAND_W, BAND_NRHS, BAND_NCU = 160, 49, 256
+NEITHER, WINDOW, TILES = 0, 1, 2
+BB, BS, PF, PT = 16, 16 * 17, 4, 8
+
+
+@pytest.fixture(scope="module")
+def band(driver):
+    rc, err, v = run(driver, "band", BAND_W, BAND_NRHS, BAND_NCU)
+    assert rc == 0, err
+    assert v["consts"].tolist() == [BB, BS, BB + 1, PF, PT, 160 * 1024, 768]
+    grid = (BAND_W + 1, BAND_NRHS)
+    return {"maxhw": v["maxhw"].astype(int), "shape": v["shape"].astype(int).reshape(*grid, 5),
+            "lds": v["lds"].astype(int).reshape(*grid, 11), "workers": v["workers"].astype(int).reshape(*grid, 16, 2),
+            "twist": v["twist"].astype(int).reshape(-1, 6), "carve": v["carve"].astype(np.int64).reshape(-1, 13),
+            "pays": v["pays"].astype(int)}
+
+
+def lds_bytes_before(nbr, nrb):
+    """The dynamic LDS size the launcher computed before the shape had a header of its own."""
+    nr = nrb * BB
+    return 8 * (nbr * (nbr + 1) // 2 * BS + nrb * nbr * BS + 2 * BS + nr * (nr + 1) + 4 * BB + 16 * PT // 2)
+
+
+def test_band_limits_and_admission(band):
+    """Largest half-width of the window: 144, 128, 112 for up to 16, 32, 48 right-hand sides, none beyond; a half-width is
+    the window's up to that limit, the tiles' up to 768, nobody's with more than 48 right-hand sides."""
+    want = [144 if n <= 16 else 128 if n <= 32 else 112 if n <= 48 else -1 for n in range(1, BAND_NRHS + 1)]
+    assert band["maxhw"].tolist() == want
+    for w in range(BAND_W + 1):
+        for n in range(1, BAND_NRHS + 1):
+            admit, nbr, nrb, nwaves, groups = band["shape"][w, n - 1]
+            assert nbr == max(3, (w + 31) // 16) and nrb == (n + 15) // 16
+            assert nwaves == (8 if nbr <= 4 else 12 if nbr <= 8 else 16) and groups == (nwaves - 4) // 4
+            assert admit == (NEITHER if n > 48 else WINDOW if w <= want[n - 1] else TILES), (w, n)
+            assert (admit == WINDOW) == (n <= 48 and lds_bytes_before(nbr, nrb) <= 160 * 1024)
+
+
+def test_band_lds_layout(band):
+    """The regions lie in order without overlap and end within the byte count, which is the launcher's earlier formula
+    (at most 160 KiB where the window is admitted; 64 bytes of it are a reserve nothing uses)."""
+    for w in range(BAND_W + 1):
+        for n in range(1, BAND_NRHS + 1):
+            admit, nbr, nrb = band["shape"][w, n - 1][:3]
+            off, nbytes = band["lds"][w, n - 1][:10], band["lds"][w, n - 1][10]
+            nr = nrb * BB
+            sizes = [8 * nbr * (nbr + 1) // 2 * BS, 8 * nrb * nbr * BS, 8 * 2 * BS, 8 * nr * (nr + 1), 8 * 2 * BB, 8 * BB,
+                     4 * 16, 4 * 16 * PT, 64]  # Wb, RH, Fb2, G, pv, red, sync, ptab, reserve
+            assert off[0] == 0 and (off[1:] == off[:-1] + sizes).all(), (w, n)  # each region starts where the last ends
+            assert off[9] == nbytes == lds_bytes_before(nbr, nrb)
+            assert off[6] % 4 == 0 and off[7] % 4 == 0 and (off[:6] % 8 == 0).all()
+            if admit == WINDOW:
+                assert nbytes <= 160 * 1024
+    at = {(nbr, nrb): None for nbr, nrb in [(3, 1), (10, 1), (9, 2), (8, 3)]}
+    for w in range(BAND_W + 1):
+        for n in range(1, BAND_NRHS + 1):
+            key = tuple(band["shape"][w, n - 1][1:3])
+            if key in at:
+                at[key] = band["lds"][w, n - 1][10]
+    assert at == {(3, 1): 27136, (10, 1): 148992, (9, 2): 150912, (8, 3): 154752}
+
+
+def test_band_kernel_conditions(band):
+    """What k_band_forms relies on for every shape the window admits (its run-time flags guard the same): the loader groups'
+    registers cover a block row, no worker is dealt more pairs than its table row holds, two row blocks per worker cover
+    the column below wave 0's block, and the workgroup has a thread per element of a right-hand-side column block row."""
+    checked = 0
+    for w in range(BAND_W + 1):
+        for n in range(1, BAND_NRHS + 1):
+            admit, nbr, nrb, nwaves, groups = band["shape"][w, n - 1]
+            if admit != WINDOW:
+                continue
+            checked += 1
+            RB, nworkers = nbr - 1 + nrb, nwaves - 1
+            assert groups * PF >= nbr
+            assert 64 * nwaves >= 16 * RB
+            pos, pairs = band["workers"][w, n - 1][:, 0], band["workers"][w, n - 1][:, 1]
+            assert pos[0] == -1 and (pos[nwaves:] == -1).all()
+            assert sorted(pos[1:nwaves]) == list(range(nworkers))  # every position once
+            assert pairs[1:nwaves].max() <= PT - 1
+            assert pairs[1:nwaves].sum() == RB * (RB + 1) // 2 - 1  # every pair but wave 0's is dealt once
+            for p in pos[1:nwaves]:  # the round robin the kernel walks, counted here again
+                assert pairs[list(pos).index(p)] == len(range(1 + p, RB * (RB + 1) // 2, nworkers))
+            solved = {1 + p + k * nworkers for p in pos[1:nwaves] for k in (0, 1)}
+            assert set(range(1, RB)) <= solved
+    assert checked == 145 * 16 + 129 * 16 + 113 * 16
+
+
+def test_band_twisted_shape(band):
+    """Two half sweeps and the separator make up the matrix; the workspace's regions are disjoint and add up to the count
+    the size query has always given; at 256 compute units batches 1 .. 128 take two half sweeps, 129 .. 256 one, 300 two
+    and 1600 one (the cases the rule's comment quotes)."""
+    tw = band["twist"]
+    assert set(tw[:, 0]) == set(range(3, 12))
+    for nbr in range(3, 12):
+        rows = tw[tw[:, 0] == nbr]
+        assert rows[:, 1].tolist() == list(range(6 * nbr, 301))
+    nbr, nblk, nm, k0, k1, fits = tw.T
+    assert (nm == 16 * (nbr - 1)).all() and (k0 + k1 + nbr - 1 == nblk).all() and (abs(k0 - k1) <= 1).all()
+    assert (np.minimum(k0, k1) >= nbr).all() and fits.all()  # each half sweeps at least a window's length
+    carve = band["carve"]
+    assert len(carve) == 2 * (145 * 16 + 129 * 16 + 113 * 16)
+    for w, n, b, *rest in carve.tolist():
+        off, total, counted = rest[:8], rest[8], rest[9]
+        nm_, nr = 16 * (max(3, (w + 31) // 16) - 1), 16 * ((n + 15) // 16)
+        sizes = [2 * b * nm_ * nm_, 2 * b * nr * nm_, 2 * b * n * n, 2 * b, b * nm_ * nm_, b * nr * nm_, b * n * n, b]
+        assert off[0] == 0 and all(off[i] + sizes[i] <= off[i + 1] for i in range(7)) and off[7] + sizes[7] <= total
+        assert total == counted == 3 * b * (nm_ * nm_ + nr * nm_ + n * n + 1) + 64
+    pays = band["pays"]
+    assert pays[:128].all() and not pays[128:256].any() and pays[300 - 1] == 1 and pays[1600 - 1] == 0
+    assert pays[1600] == 0  # fewer than 6 nbr block columns: never
