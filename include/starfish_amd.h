@@ -376,6 +376,38 @@ int sf_loglike_grad_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const 
 int sf_debug_loglike_grad_contract(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, double* d_grad,
                                    int grad_stride, void* d_work, size_t work_bytes, void* stream);
 
+/* The likelihood and its gradient in the mean-flux parameters: vsini (column 0 of the parameter row), vz (1), log_scale (2), the
+ * emulator grid parameters, the Chebyshev coefficients and Av.  They enter through the flux f, the scaled emulator rows X and
+ * the emulator's weight covariance Sigma_w, not through the structured kernels.  With alpha = C^-1 r, V = C^-1 X^T, a = X alpha,
+ * z_a = Sigma_w^-1 a and G = Sigma_w^-1 X V Sigma_w^-1,
+ *     d lnL = -alpha^T df + sum_ki dX_ki (alpha_i z_a,k - (V Sigma_w^-1)_ik) - 1/2 z_a^T dS z_a + 1/2 tr(dS G),  dS = dSigma_w,
+ * so no inverse is needed: the sequence of sf_apply_batch with SF_APPLY_CINV on the 1 + m right-hand sides [r, X_1 .. X_m]
+ * (same transform chain, fill, factorisation and finish: d_lnl and d_info have sf_loglike_batch's bits, d_flux
+ * sf_apply_batch's), per-walker m x m algebra, one pass over the pixels with the analytic row tangents (transform parameters:
+ * dSigma_w = 0) and one over the rows of the emulator's z = Linv v12 (grid parameters: dX = 0, df = dmu^T X).  At vsini <= 0 the
+ * likelihood is not differentiated: such walkers are flagged as by sf_loglike_batch.  h_slots (HOST): the nslots columns of the
+ * parameter row to differentiate in, 1 <= nslots <= SF_MEAN_GRAD_MAX_SLOTS, no column twice; d_grad[b*grad_stride + j] belongs
+ * to h_slots[j], and a subset of columns gives the bits of those columns of a larger call.  The matrix is the one that is
+ * factorised (jitter included).  d_flux[B*n] and d_info[B] may be NULL.  Walkers with d_info[b] != 0 get NaN in every slot.
+ * Every sum has a fixed order: a repeated call gives the same bits.  SF_EINVAL before anything is enqueued: B outside
+ * 1 .. 65535, null d_params, h_slots, d_lnl or d_grad, nslots outside its range, a repeated column, a column that is none of
+ * the above or that the model does not have (norm, the covariance hyper-parameters), grad_stride < nslots, a model without
+ * log_scale (the renormalising scale is not differentiated), use_sigma_w, a bad context or model.  d_work:
+ * sf_loglike_mean_grad_workspace_bytes(ctx, model, B, nslots) (0 for bad arguments): the workspace of sf_apply_batch with
+ * 1 + m right-hand sides; per walker the m scaled rows, 2 m + 3 m^2 doubles, one double per (256-pixel block, slot), a second
+ * set of spline coefficients if the model has vsini, and m M (m + 1) + m doubles for each of min(nslots, n_grid) grid columns. */
+#define SF_MEAN_GRAD_MAX_SLOTS 16
+size_t sf_loglike_mean_grad_workspace_bytes(const sf_ctx* ctx, const sf_model_desc* model, int B, int nslots);
+int sf_loglike_mean_grad_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, const int* h_slots,
+                               int nslots, double* d_lnl, double* d_grad, int grad_stride, double* d_flux, int* d_info,
+                               void* d_work, size_t work_bytes, void* stream);
+/* Timing aid (tools/bench_mean_gradient.py): the launches of sf_loglike_mean_grad_batch behind the solve alone (moments, pixel
+ * pass, grid slots, sum), on the workspace that a call of sf_loglike_mean_grad_batch with the same ctx, model, B, d_params and slots left
+ * behind. */
+int sf_debug_loglike_mean_grad_contract(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params,
+                                        const int* h_slots, int nslots, double* d_grad, int grad_stride, void* d_work,
+                                        size_t work_bytes, void* stream);
+
 /* ---- multi-order batches (reference: the multi-order container
  * Starfish/spectrum.py:96-115, orders independent docs/intro.rst:71-73, EchelleModel stub
  * Starfish/models/echelle_model.py:1-2) -------------------------------------------------------------

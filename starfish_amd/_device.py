@@ -19,6 +19,7 @@ INFO_MESSAGES = {
     -6: "the log-likelihood evaluated to NaN (non-finite input or intermediate)",
 }
 APPLY_OPS = {"L": 0, "Linv": 1, "LinvT": 2, "Cinv": 3}  # SF_APPLY_* of include/starfish_amd.h
+MEAN_GRAD_MAX_SLOTS = 16  # SF_MEAN_GRAD_MAX_SLOTS of include/starfish_amd.h
 INFO_BANDWIDTH = -4
 INFO_INTERNAL = -5
 C_KMS = 2.99792458e5
@@ -468,11 +469,11 @@ class DeviceOrder:
 
     def _call(self, name, md, B, P, *args, ws=None):
         """Enqueue ``sf_<name>(ctx, &md, B, P, *args, ws, ws_bytes, stream)`` on the current stream and check its return
-        code.  ``args``: integers as they are, tensors (or None) as their device pointers; ``ws``: the order's workspace
+        code.  ``args``: integers and ctypes arrays (host arguments) as they are, tensors (or None) as their device pointers; ``ws``: the order's workspace
         sized for ``(md, B)`` unless the caller reserved another (the banded solver's)."""
         if ws is None:
             ws = self._work(md, B)
-        args = [a if isinstance(a, (int, np.integer)) else ptr(a) for a in args]
+        args = [a if isinstance(a, (int, np.integer, C.Array)) else ptr(a) for a in args]
         rc = getattr(self.lib, "sf_" + name)(self.ctx, C.byref(md), B, ptr(P), *args, ptr(ws), ws.numel(),
                                              stream_ptr(self.dev))
         _lib.check(rc, "sf_" + name)
@@ -731,6 +732,35 @@ class DeviceOrder:
 
             return self._run_chunked("loglike_grad_batch", md, P, max_chunk,
                                      lambda units: self.loglike_grad_workspace_bytes(md, units), buffers, args, sliced)
+
+    def loglike_mean_grad_workspace_bytes(self, md, B, nslots):
+        return self._size_query("loglike_mean_grad_", md, B, nslots)
+
+    def loglike_mean_grad(self, md, params, slots, want_flux=False, max_chunk=None):
+        """The likelihood and its gradient in the mean-flux parameters (sf_loglike_mean_grad_batch).  params: (B, stride) rows
+        as for :meth:`loglike`; slots: the columns of the parameter row to differentiate in (vsini = 0, vz = 1, log_scale = 2,
+        the grid, Chebyshev and Av columns), each at most once, at most MEAN_GRAD_MAX_SLOTS.  Returns dict of
+        numpy arrays: lnl (B,) and info (B,) with :meth:`loglike`'s bits, grad (B, len(slots)) in the order of ``slots``, NaN rows
+        where info != 0, and, asked for, flux (B, n).  Chunked and retried like :meth:`apply`."""
+        slots = [int(v) for v in slots]
+        nslots = len(slots)
+        h_slots = (C.c_int * max(nslots, 1))(*slots)
+        with _torch().cuda.device(self.dev):
+            P = self._rows(params)
+            buffers, download = self._outputs(int(P.shape[0]), {"lnl": (), "grad": (max(nslots, 1),)}, want_flux)
+
+            def args(bufs, lo, hi):
+                (lnl, grad), info, flux = bufs
+                return h_slots, nslots, lnl[lo:hi], grad[lo:hi], max(nslots, 1), flux[lo:hi] if want_flux else None, info[lo:hi]
+
+            def sliced(bufs):
+                res = download(bufs)
+                res["grad"] = res["grad"][:, :nslots]
+                return res
+
+            return self._run_chunked("loglike_mean_grad_batch", md, P, max_chunk,
+                                     lambda units: self.loglike_mean_grad_workspace_bytes(md, units, nslots), buffers, args,
+                                     sliced)
 
     def loglike_device(self, md, P_dev, out_lnl, info=None):
         """Enqueue-only variant for bench.py: device tensors in/out, no synchronisation."""

@@ -161,6 +161,15 @@ SIGNATURES = {
         C.c_int,
         [_VP, C.POINTER(ModelDesc), C.c_int, _VP, _VP, C.c_int, _VP, C.c_size_t, _VP],
     ),
+    "sf_loglike_mean_grad_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int]),
+    "sf_loglike_mean_grad_batch": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, c_int_p, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_size_t, _VP],
+    ),
+    "sf_debug_loglike_mean_grad_contract": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, c_int_p, C.c_int, _VP, C.c_int, _VP, C.c_size_t, _VP],
+    ),
     "sf_debug_decompose_matvec": (
         C.c_int,
         [_VP, C.POINTER(ModelDesc), C.c_int, _VP, C.c_int, _VP, _VP, C.c_size_t, _VP],

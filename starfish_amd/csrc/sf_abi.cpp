@@ -3,8 +3,8 @@
 #include "sf_stages.h"
 
 // ----------------------------------------------------------------------------------- stages
-static sf_emu_args emu_args(sf_ctx* c, const sf_model_desc* mdl, const double* d_params, const Work& w,
-                            double* d_mu, double* d_cov, double* d_Lw, int* d_info) {
+sf_emu_args emu_args(sf_ctx* c, const sf_model_desc* mdl, const double* d_params, const Work& w, double* d_mu, double* d_cov,
+                     double* d_Lw, int* d_info) {
     sf_emu_args e;
     e.params = d_params;
     e.pstride = sf_param_stride(c, mdl);
@@ -49,49 +49,36 @@ static int export_resid(double* d_resid_out, const sf_ctx* c, const Work& w, int
     return SF_OK;
 }
 
-// emulator + transform chain -> unscaled X / flux, scale, then residual / Y
-int run_transforms(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const Work& w, double* d_flux_out,
-                   double* d_X_out, double* d_resid_out, double* d_log_scale, bool want_Y, hipStream_t s) {
-    // (the broadening + spline-fit launches depend on vsini only, not on the emulator; forked onto a stream of their own beside
-    // the emulator's launches and the band fill they do not shorten the banded step: every one of these launches fills the chip
-    // by itself -- with three streams each simply takes longer, profiles/r05_q_banded_step_timelines.txt)
-    const int pstride = sf_param_stride(c, mdl);
-    SF_HIP(hipMemsetAsync(w.info_e, 0, sizeof(int) * (size_t)B, s));
-    int rc = run_emulator(c, mdl, B, d_params, w, w.mu, nullptr, w.Lw, w.info_e, s);
-    if (rc) return rc;
-    const double* coef = c->coef_static.as<double>();
-    if (mdl->has_vsini) {
-        sf_broaden_args a;
-        a.in = nullptr;
-        a.spec = c->spec.as<double2>();
-        a.B = B;
-        a.rows = c->rows;
-        a.nf = c->nf;
-        a.tw = c->tw.as<double2>();
-        a.dv = c->dv;
-        a.kind = 1;
-        a.params = d_params;
-        a.pstride = pstride;
-        a.poff = 0;
-        a.scalar_param = 0.0;
-        a.out = w.ybro;  // [B][rows][nf]: every row contiguous (coalesced stores)
-        a.ob = (int64_t)c->nf * c->rows;
-        a.orow = c->nf;
-        a.oelem = 1;
-        a.gscratch = w.fft;
-        a.mult = w.mult;
-        a.info = w.info_e;
-        rc = sf_launch_broaden(a, s);
-        if (rc) return rc;
-        // spline coefficients of the broadened rows: truncated-inverse band product (fully parallel)
-        rc = sf_launch_spline_apply(w.ybro, w.coef, B, c->rows, c->nf, c->inv_band.as<double>(), s);
-        if (rc) return rc;
-        coef = w.coef;
-    }
+// the rotational broadening of the context's half spectra into w.ybro
+sf_broaden_args broaden_args(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const Work& w) {
+    sf_broaden_args a;
+    a.in = nullptr;
+    a.spec = c->spec.as<double2>();
+    a.B = B;
+    a.rows = c->rows;
+    a.nf = c->nf;
+    a.tw = c->tw.as<double2>();
+    a.dv = c->dv;
+    a.kind = 1;
+    a.params = d_params;
+    a.pstride = sf_param_stride(c, mdl);
+    a.poff = 0;
+    a.scalar_param = 0.0;
+    a.out = w.ybro;  // [B][rows][nf]: every row contiguous (coalesced stores)
+    a.ob = (int64_t)c->nf * c->rows;
+    a.orow = c->nf;
+    a.oelem = 1;
+    a.gscratch = w.fft;
+    a.mult = w.mult;
+    a.info = w.info_e;
+    return a;
+}
+// the per-pixel evaluation's arguments on the workspace w (the coefficients: the walkers' own behind the broadening)
+sf_eval_args eval_args(sf_ctx* c, const sf_model_desc* mdl, const double* d_params, const Work& w) {
     sf_eval_args ev;
     ev.wave = c->wave.as<double>();
     ev.knots = c->knots.as<double>();
-    ev.coef = coef;
+    ev.coef = mdl->has_vsini ? w.coef : c->coef_static.as<double>();
     ev.coef_batched = mdl->has_vsini ? 1 : 0;
     ev.params = d_params;
     ev.mu = w.mu;
@@ -102,13 +89,34 @@ int run_transforms(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_p
     ev.nf = c->nf;
     ev.m = c->m;
     ev.ldx = w.L.npad;
-    ev.pstride = pstride;
+    ev.pstride = sf_param_stride(c, mdl);
     ev.has_vz = mdl->has_vz;
     ev.n_cheb = mdl->n_cheb;
     ev.off_cheb = 6 + c->P;
     ev.has_av = mdl->has_av;
     ev.off_av = 6 + c->P + mdl->n_cheb + 3 * mdl->n_local;
     ev.wave_max = c->wave_max;
+    return ev;
+}
+
+// emulator + transform chain -> unscaled X / flux, scale, then residual / Y
+int run_transforms(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const Work& w, double* d_flux_out,
+                   double* d_X_out, double* d_resid_out, double* d_log_scale, bool want_Y, hipStream_t s) {
+    // (the broadening + spline-fit launches depend on vsini only, not on the emulator; forked onto a stream of their own beside
+    // the emulator's launches and the band fill they do not shorten the banded step: every one of these launches fills the chip
+    // by itself -- with three streams each simply takes longer, profiles/r05_q_banded_step_timelines.txt)
+    const int pstride = sf_param_stride(c, mdl);
+    SF_HIP(hipMemsetAsync(w.info_e, 0, sizeof(int) * (size_t)B, s));
+    int rc = run_emulator(c, mdl, B, d_params, w, w.mu, nullptr, w.Lw, w.info_e, s);
+    if (rc) return rc;
+    if (mdl->has_vsini) {
+        rc = sf_launch_broaden(broaden_args(c, mdl, B, d_params, w), s);
+        if (rc) return rc;
+        // spline coefficients of the broadened rows: truncated-inverse band product (fully parallel)
+        rc = sf_launch_spline_apply(w.ybro, w.coef, B, c->rows, c->nf, c->inv_band.as<double>(), s);
+        if (rc) return rc;
+    }
+    const sf_eval_args ev = eval_args(c, mdl, d_params, w);
     sf_resid_args r;
     r.dflux = c->flux.as<double>();
     r.flux = w.fraw;

@@ -1,6 +1,6 @@
 // C-ABI host layer: the calls that run the likelihood's sequence and then work on the Cholesky factor (sf_apply_batch,
-// sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch and the two timing aids).  One description per call, one
-// argument check, one workspace layout (carve_applied) and one way to open a call.
+// sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch, sf_loglike_mean_grad_batch and the three timing aids).  One
+// description per call, one argument check, one workspace layout (carve_applied) and one way to open a call.
 #include "sf_stages.h"
 
 struct AppliedCall {
@@ -18,6 +18,9 @@ static const AppliedCall POINTWISE = {"sf_pointwise_batch", "d_params, d_alpha a
 static const AppliedCall GRAD = {"sf_loglike_grad_batch", "d_params, d_lnl and d_grad", AW_INVERSE | AW_PART, false, false};
 static const AppliedCall GRAD_CONTRACT = {"sf_debug_loglike_grad_contract", "d_params and d_grad", AW_INVERSE | AW_PART, false,
                                           false};
+static const AppliedCall MEAN_GRAD = {"sf_loglike_mean_grad_batch", "d_params, h_slots, d_lnl and d_grad", AW_MEAN, false, false};
+static const AppliedCall MEAN_GRAD_CONTRACT = {"sf_debug_loglike_mean_grad_contract", "d_params, h_slots and d_grad", AW_MEAN,
+                                               false, false};
 // what a call was handed, as far as the check looks at it
 struct AppliedArgs {
     int B, nrhs;
@@ -27,6 +30,8 @@ struct AppliedArgs {
     int ldr = 0;
     int64_t rhs_stride = 0;
     int grad_stride = 0;
+    const int* h_slots = nullptr;  // (AW_MEAN)
+    int nslots = 0;
 };
 
 // (the staging and export launches take one grid row per right-hand side and one grid plane per walker)
@@ -51,6 +56,38 @@ static int grad_slots_ok(const AppliedCall& k, const sf_model_desc* mdl, int gra
     }
     return SF_OK;
 }
+// the mean gradient's own (behind model_ok): a model it differentiates, and columns that are mean-flux parameters of it
+static int mean_slots_ok(const AppliedCall& k, const sf_ctx* c, const sf_model_desc* mdl, const AppliedArgs& a) {
+    if (!mdl->has_log_scale || mdl->use_sigma_w) {
+        sf_set_error("%s: %s", k.name, mdl->use_sigma_w ? "use_sigma_w (the paper's form of the emulator term) is not differentiated"
+                                                        : "a model without log_scale (the renormalising scale) is not differentiated");
+        return SF_EINVAL;
+    }
+    if (a.nslots < 1 || a.nslots > SF_MEAN_GRAD_MAX_SLOTS) {
+        sf_set_error("%s: nslots=%d must lie in 1 .. %d", k.name, a.nslots, SF_MEAN_GRAD_MAX_SLOTS);
+        return SF_EINVAL;
+    }
+    if (a.grad_stride < a.nslots) {
+        sf_set_error("%s: grad_stride=%d < %d slots", k.name, a.grad_stride, a.nslots);
+        return SF_EINVAL;
+    }
+    const int off_cheb = 6 + c->P, off_av = off_cheb + mdl->n_cheb + 3 * mdl->n_local;
+    for (int j = 0; j < a.nslots; ++j) {
+        const int col = a.h_slots[j];
+        for (int i = 0; i < j; ++i)
+            if (a.h_slots[i] == col) {
+                sf_set_error("%s: column %d is listed twice", k.name, col);
+                return SF_EINVAL;
+            }
+        const bool ok = (col == 0 && mdl->has_vsini) || (col == 1 && mdl->has_vz) || col == 2 || (col >= 6 && col < off_av) ||
+                        (col == off_av && mdl->has_av);
+        if (ok && !(col >= off_cheb + mdl->n_cheb && col < off_av)) continue;
+        sf_set_error("%s: column %d is not a differentiable mean parameter of this model (vsini, vz, log_scale, grid, cheb, Av)",
+                     k.name, col);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
 // The checks that need no context come first: the counts, the required pointers, op and the right-hand-side conventions;
 // then the context and the model; then ldr against the order's n.
 static int args_ok(const AppliedCall& k, const sf_ctx* c, const sf_model_desc* mdl, const AppliedArgs& a) {
@@ -69,23 +106,24 @@ static int args_ok(const AppliedCall& k, const sf_ctx* c, const sf_model_desc* m
     }
     if (k.parts & AW_PART) SF_CHECK(grad_slots_ok(k, mdl, a.grad_stride));
     SF_CHECK(model_ok(c, mdl));
+    if (k.parts & AW_MEAN) SF_CHECK(mean_slots_ok(k, c, mdl, a));
     if (k.rhs && a.d_rhs && a.ldr < c->n) {
         sf_set_error("%s: ldr=%d < n (%d)", k.name, a.ldr, c->n);
         return SF_EINVAL;
     }
     return SF_OK;
 }
-static size_t workspace_bytes(const AppliedCall& k, const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs) {
+static size_t workspace_bytes(const AppliedCall& k, const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs, int nslots = 0) {
     if (counts_ok(k, B, nrhs) || model_ok(c, mdl)) return 0;
     if ((k.parts & AW_PART) && sf_cov_grad_slots(mdl->has_global, mdl->n_local) == 0) return 0;
-    return carve_applied(c, mdl, B, nrhs, k.parts, nullptr, 0, carve(c, mdl, B, nullptr, 0, true).bytes).bytes;
+    return carve_applied(c, mdl, B, nrhs, k.parts, nullptr, 0, carve(c, mdl, B, nullptr, 0, true).bytes, nslots).bytes;
 }
 // the arguments checked, then the workspace of the call
 static int open_applied(const AppliedCall& k, const sf_ctx* c, const sf_model_desc* mdl, const AppliedArgs& a, void* d_work,
                         size_t work_bytes, Work* w, AppliedWork* aw) {
     SF_CHECK(args_ok(k, c, mdl, a));
     SF_CHECK(open_call(c, mdl, a.B, d_work, work_bytes, true, w));
-    *aw = carve_applied(c, mdl, a.B, a.nrhs, k.parts, d_work, work_bytes, w->bytes);
+    *aw = carve_applied(c, mdl, a.B, a.nrhs, k.parts, d_work, work_bytes, w->bytes, a.nslots);
     return work_fits(work_bytes, aw->bytes);
 }
 static int export_status(int* d_info, const AppliedWork& aw, int B, hipStream_t s) {
@@ -94,19 +132,21 @@ static int export_status(int* d_info, const AppliedWork& aw, int B, hipStream_t 
 }
 
 // transform chain, staging, fill, the likelihood's factorisation and `op` on the staging area, in place.  cov_diag (may be
-// NULL): [B][npad], the diagonal of the filled matrices, copied out before the factorisation overwrites it
+// NULL): [B][npad], the diagonal of the filled matrices, copied out before the factorisation overwrites it.  xs (may be NULL;
+// nrhs = 1 + m, no d_rhs): the transform chain leaves the scaled rows X there and [r, X_1 .. X_m] are the right-hand sides
 static int apply_staged(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int op, const double* d_rhs, int nrhs,
                         int ldr, int64_t rhs_stride, double* d_flux, const Work& w, const AppliedWork& aw, hipStream_t s,
-                        double* cov_diag = nullptr) {
+                        double* cov_diag = nullptr, double* xs = nullptr) {
     const Layout L = layout_of(c);
     int rc;
     {
         ProfScope ps(s, PS_TRANSFORM);
-        rc = run_transforms(c, mdl, B, d_params, w, d_flux, nullptr, nullptr, nullptr, true, s);
+        rc = run_transforms(c, mdl, B, d_params, w, d_flux, xs, nullptr, nullptr, true, s);
         if (rc) return rc;
     }
     // (before the factorisation: the residual rides through it and comes out as L^-1 R)
-    rc = sf_launch_apply_stage(d_rhs, ldr, rhs_stride, w.resid, c->n, L.npad, nrhs, B, aw.stage, s);
+    rc = xs ? sf_launch_mean_stage(w.resid, xs, w.info_e, c->n, L.npad, c->m, B, aw.stage, s)
+            : sf_launch_apply_stage(d_rhs, ldr, rhs_stride, w.resid, c->n, L.npad, nrhs, B, aw.stage, s);
     if (rc) return rc;
     const int fp = sf_potrf_front_pad(c->npad, B);  // (once per call: see sf_loglike_batch)
     {
@@ -237,4 +277,66 @@ extern "C" int sf_debug_loglike_grad_contract(sf_ctx* c, const sf_model_desc* md
     AppliedWork aw;
     SF_CHECK(open_applied(GRAD_CONTRACT, c, mdl, grad_args(B, d_params && d_grad, grad_stride), d_work, work_bytes, &w, &aw));
     return grad_contract(c, mdl, B, d_params, w, aw, d_grad, grad_stride, (hipStream_t)stream);
+}
+
+// ----------------------------------------------------------------------------------- gradient in the mean-flux parameters
+extern "C" size_t sf_loglike_mean_grad_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int nslots) {
+    if (model_ok(c, mdl) || nslots < 1 || nslots > SF_MEAN_GRAD_MAX_SLOTS) return 0;
+    return workspace_bytes(MEAN_GRAD, c, mdl, B, 1 + c->m, nslots);
+}
+static sf_mean_grad_args mean_grad_kernel_args(const sf_ctx* c, const int* h_slots, int nslots, const Work& w, const AppliedWork& aw,
+                                               double* d_grad, int grad_stride) {
+    sf_mean_grad_args a;
+    a.stage = aw.stage, a.Xs = aw.xs, a.Lw = w.Lw, a.mu = w.mu, a.scale = w.scale, a.info = aw.info;
+    a.fin = aw.fin, a.part = aw.mpart, a.grad = d_grad;
+    a.dcoef = aw.dcoef, a.kdot = aw.kdot, a.mudot = aw.mudot, a.zdot = aw.zdot;
+    a.n = c->n, a.npad = w.L.npad, a.m = c->m, a.nslots = nslots, a.grad_stride = grad_stride;
+    a.want_vz = a.want_vsini = a.ng = 0;
+    for (int j = 0; j < SF_MEAN_GRAD_MAX_SLOTS; ++j) {
+        a.slots[j] = j < nslots ? h_slots[j] : -1;
+        a.gcols[j] = -1;
+        if (a.slots[j] == 0) a.want_vsini = 1;
+        if (a.slots[j] == 1) a.want_vz = 1;
+        if (a.slots[j] >= 6 && a.slots[j] < 6 + c->P) a.gcols[a.ng++] = a.slots[j];
+    }
+    return a;
+}
+// the moments, the pixel pass, the grid slots and the sum over the blocks, from alpha and V = C^-1 X^T in the staging area
+static int mean_grad_contract(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const int* h_slots, int nslots,
+                              const Work& w, const AppliedWork& aw, double* d_grad, int grad_stride, hipStream_t s) {
+    return sf_launch_mean_grad(eval_args(c, mdl, d_params, w), mean_grad_kernel_args(c, h_slots, nslots, w, aw, d_grad, grad_stride),
+                               w.zs, c->m * c->M, B, s);
+}
+static AppliedArgs mean_grad_args(const sf_ctx* c, int B, bool required, const int* h_slots, int nslots, int grad_stride) {
+    AppliedArgs a = {B, c ? 1 + c->m : 1, required};
+    a.grad_stride = grad_stride, a.h_slots = h_slots, a.nslots = nslots;
+    return a;
+}
+extern "C" int sf_loglike_mean_grad_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const int* h_slots,
+                                          int nslots, double* d_lnl, double* d_grad, int grad_stride, double* d_flux, int* d_info,
+                                          void* d_work, size_t work_bytes, void* stream) {
+    Work w;
+    AppliedWork aw;
+    SF_CHECK(open_applied(MEAN_GRAD, c, mdl, mean_grad_args(c, B, d_params && h_slots && d_lnl && d_grad, h_slots, nslots, grad_stride),
+                          d_work, work_bytes, &w, &aw));
+    hipStream_t s = (hipStream_t)stream;
+    SF_CHECK(apply_staged(c, mdl, B, d_params, SF_APPLY_CINV, nullptr, 1 + c->m, c->n, 0, d_flux, w, aw, s, nullptr, aw.xs));
+    // (behind the transform chain: its broadened rows, multiplier table and FFT scratch are free again)
+    SF_CHECK(sf_launch_mean_tangents(broaden_args(c, mdl, B, d_params, w), c->inv_band.as<double>(),
+                                     emu_args(c, mdl, d_params, w, w.mu, nullptr, w.Lw, w.info_e),
+                                     mean_grad_kernel_args(c, h_slots, nslots, w, aw, d_grad, grad_stride), B, s));
+    SF_CHECK(mean_grad_contract(c, mdl, B, d_params, h_slots, nslots, w, aw, d_grad, grad_stride, s));
+    SF_HIP(hipMemcpyAsync(d_lnl, aw.lnl, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return export_status(d_info, aw, B, s);
+}
+// The launches of sf_loglike_mean_grad_batch behind the solve alone, on the workspace a call with the same ctx, model, B,
+// d_params and slots left (tools/bench_mean_gradient.py times them)
+extern "C" int sf_debug_loglike_mean_grad_contract(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params,
+                                                   const int* h_slots, int nslots, double* d_grad, int grad_stride, void* d_work,
+                                                   size_t work_bytes, void* stream) {
+    Work w;
+    AppliedWork aw;
+    SF_CHECK(open_applied(MEAN_GRAD_CONTRACT, c, mdl, mean_grad_args(c, B, d_params && h_slots && d_grad, h_slots, nslots, grad_stride),
+                          d_work, work_bytes, &w, &aw));
+    return mean_grad_contract(c, mdl, B, d_params, h_slots, nslots, w, aw, d_grad, grad_stride, (hipStream_t)stream);
 }

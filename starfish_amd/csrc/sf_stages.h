@@ -11,6 +11,12 @@ int open_call(const sf_ctx* c, const sf_model_desc* mdl, int B, void* d_work, si
 // emulator + transform chain -> unscaled X / flux, scale, then residual / Y
 int run_transforms(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const Work& w, double* d_flux_out,
                    double* d_X_out, double* d_resid_out, double* d_log_scale, bool want_Y, hipStream_t s);
+// the arguments of the emulator's, the broadening's and the per-pixel evaluation's launches on the workspace w, as
+// run_transforms hands them to its kernels
+sf_emu_args emu_args(sf_ctx* c, const sf_model_desc* mdl, const double* d_params, const Work& w, double* d_mu, double* d_cov,
+                     double* d_Lw, int* d_info);
+sf_broaden_args broaden_args(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const Work& w);
+sf_eval_args eval_args(sf_ctx* c, const sf_model_desc* mdl, const double* d_params, const Work& w);
 sf_fill_args fill_args(sf_ctx* c, const sf_model_desc* mdl, const double* d_params, const Work& w);
 // The likelihood's fill of the workspace matrices of layout L (lower tiles, identity padding, jitter), in the frame fp of
 // the factorisation: only the tiles that carry more than the rank-m term are materialised (tile map and list)

@@ -81,6 +81,39 @@ int sf_launch_resid_y(const sf_resid_args& a, int B, hipStream_t s);
 int sf_launch_eval_resid_y(const sf_eval_args& e, const sf_resid_args& r, double* scale_out, double* log_scale_out, int B,
                            hipStream_t s);
 
+// sf_mean_grad.h: the likelihood's gradient in the mean-flux parameters, contracted from alpha = C^-1 r and
+// V = C^-1 X^T (the staging area after SF_APPLY_CINV on the 1 + m right-hand sides sf_launch_mean_stage put there)
+struct sf_emu_args;
+struct sf_mean_grad_args {
+    const double* stage;   // [B][1 + m][npad]: alpha, V_1 .. V_m
+    const double* Xs;      // [B][m][n] scaled rows (sf_resid_args::X_out)
+    const double* Lw;      // [B][m][m]
+    const double* mu;      // [B][m]
+    const double* scale;   // [B]
+    const int* info;       // [B]: != 0 -> NaN row, nothing of the walker is read
+    double* fin;           // [B][sf_mean_fin_doubles(m)]: z_a, Sigma_w^-1, Q, a, H
+    double* part;          // sf_mean_grad_part_doubles(n, nslots, B)
+    double* grad;          // [B][grad_stride]
+    double* dcoef;         // [B][nf][m + 2]: spline coefficients of the d / d vsini rows (want_vsini)
+    double* kdot;          // [ng][B][m M]: d v12 per grid column asked for
+    double* mudot;         // [ng][B][m]
+    double* zdot;          // [ng][B][m M][m]: Linv d v12
+    int n, npad, m, nslots, grad_stride, want_vz, want_vsini, ng;
+    int slots[SF_MEAN_GRAD_MAX_SLOTS];  // columns of the parameter row: 0 vsini, 1 vz, 2 log_scale, grid, cheb, Av
+    int gcols[SF_MEAN_GRAD_MAX_SLOTS];  // the ng grid columns among them, in their order
+};
+static inline __host__ __device__ size_t sf_mean_fin_doubles(int m) { return 2 * (size_t)m + 3 * (size_t)m * m; }
+size_t sf_mean_grad_part_doubles(int n, int nslots, int batch);
+int sf_launch_mean_stage(const double* resid, const double* Xs, const int* info, int n, int npad, int m, int batch, double* stage,
+                         hipStream_t s);
+// the tangents that need no solve: a.dcoef (bro: the broadening's arguments as run_transforms fills them; its ybro, mult and FFT
+// scratch are used once more) and a.kdot, a.mudot, a.zdot (e: the emulator's arguments)
+int sf_launch_mean_tangents(const sf_broaden_args& bro, const double* inv_band, const sf_emu_args& e, const sf_mean_grad_args& a,
+                            int B, hipStream_t s);
+// the moments, the pixel pass, the grid slots (z: the emulator's [B][mM][m]) and the sum over the blocks; e: the evaluation's
+// arguments as run_transforms fills them
+int sf_launch_mean_grad(const sf_eval_args& e, const sf_mean_grad_args& a, const double* z, int mM, int batch, hipStream_t s);
+
 int sf_launch_extinct_rows(const double* wave, int n, const double* flux, int rows, double Av, double Rv, int law,
                            double* out, hipStream_t s);  // law: 0 ccm89, 1 odonnell94, 2 calzetti00
 int sf_launch_extinct_spline_rows(const double* wave, int n, const double* flux, int rows, double Av, double Rv,

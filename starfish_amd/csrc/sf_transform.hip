@@ -15,6 +15,7 @@
 //   sf_transform_eval.h     Chebyshev, extinction laws, sf_eval_pixel, k_eval_rows, k_scale, k_resid_y, k_eval_resid_y
 //   sf_transform_emu.h      k_emu_prep/z/post, k_emu_joint, k_finish
 //   sf_transform_v11.h      k_v11_build, k_v11_build_batch
+//   sf_mean_grad.h          the gradient in the mean-flux parameters: k_mean_stage, k_mean_finish, k_mean_pixel, k_mean_sum
 #include "sf_common.h"
 #include "sf_device.h"
 #include "sf_transform.h"
@@ -23,3 +24,4 @@
 #include "sf_transform_eval.h"
 #include "sf_transform_emu.h"
 #include "sf_transform_v11.h"
+#include "sf_mean_grad.h"

@@ -296,12 +296,8 @@ __global__ __launch_bounds__(256) void k_broaden_half(const double2* __restrict_
     }
 }
 
-static int launch_broaden_half(const sf_broaden_args& a, hipStream_t s) {
-    const int nh1 = a.nf / 2 + 1;
-    const double val = 1.0 / (a.nf * a.dv);  // numpy.fft.rfftfreq
-    hipLaunchKernelGGL(k_kernel_mult, dim3((nh1 + 255) / 256, a.B), dim3(256), 0, s, a.mult, nh1, val, a.kind,
-                       a.params, a.pstride, a.poff, a.scalar_param, a.info);
-    SF_LAUNCH_CHECK();
+// the rows' launch of the hot path: a.mult holds the walkers' multiplier tables
+static int launch_broaden_half_rows(const sf_broaden_args& a, hipStream_t s) {
     static sf_dev_once attr_once;  // devices whose function attributes are set
     size_t shm;
     SF_CHECK(sf_fft_place("broaden", a.nf / 2, a.nf, a.gscratch, &attr_once, {(const void*)k_broaden_half<true>}, &shm));
@@ -316,6 +312,14 @@ static int launch_broaden_half(const sf_broaden_args& a, hipStream_t s) {
     }
     SF_LAUNCH_CHECK();
     return SF_OK;
+}
+static int launch_broaden_half(const sf_broaden_args& a, hipStream_t s) {
+    const int nh1 = a.nf / 2 + 1;
+    const double val = 1.0 / (a.nf * a.dv);  // numpy.fft.rfftfreq
+    hipLaunchKernelGGL(k_kernel_mult, dim3((nh1 + 255) / 256, a.B), dim3(256), 0, s, a.mult, nh1, val, a.kind,
+                       a.params, a.pstride, a.poff, a.scalar_param, a.info);
+    SF_LAUNCH_CHECK();
+    return launch_broaden_half_rows(a, s);
 }
 
 int sf_launch_broaden(const sf_broaden_args& a, hipStream_t s) {

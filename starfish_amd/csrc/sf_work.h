@@ -154,7 +154,7 @@ static BandWork carve_band(const sf_ctx* c, int B, int halfwidth, void* p, size_
 }
 
 // ------------------------------------------------------------------- the factor applied to right-hand sides
-// (sf_apply_batch, sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch; behind the Work of the same call:
+// (sf_apply_batch, sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch, sf_loglike_mean_grad_batch; behind the Work of the same call:
 // base_bytes = its size)  Every call has the staging area -- the right-hand sides padded to npad rows, the factor is applied
 // to it in place (for all but sf_apply_batch it ends up holding alpha = C^-1 rhs) -- and lnl / info, what the likelihood's
 // last step leaves.  Then, in this order, the parts the call asks for:
@@ -163,15 +163,19 @@ static BandWork carve_band(const sf_ctx* c, int B, int halfwidth, void* p, size_
 //   AW_INVERSE   cinv_diag: the diagonal of the inverse, npad doubles per walker (the inverse's launch writes it; the
 //                gradient does not read it), and winv: the scratch of that launch (carve_potri)
 //   AW_PART      part: the gradient's partial sums per (walker, block row, slot)
-enum AppliedParts { AW_YV = 1, AW_COV_DIAG = 2, AW_INVERSE = 4, AW_PART = 8 };
+//   AW_MEAN      (sf_loglike_mean_grad_batch, nslots slots) xs: the m scaled rows X of every walker, n doubles each; fin: its
+//                moments (sf_mean_fin_doubles); mpart: the partial sums per (walker, 256-pixel block, slot); dcoef: the spline
+//                coefficients of the d / d vsini rows (models with vsini); kdot, mudot, zdot: d v12, d mu and Linv d v12 for
+//                min(nslots, P) grid columns
+enum AppliedParts { AW_YV = 1, AW_COV_DIAG = 2, AW_INVERSE = 4, AW_PART = 8, AW_MEAN = 16 };
 struct AppliedWork {
     double *stage, *lnl;
     int* info;
-    double *yv, *cov_diag, *cinv_diag, *winv, *part;
+    double *yv, *cov_diag, *cinv_diag, *winv, *part, *xs, *fin, *mpart, *dcoef, *kdot, *mudot, *zdot;
     size_t bytes;
 };
 static AppliedWork carve_applied(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs, unsigned parts, void* p, size_t cap,
-                                 size_t base_bytes) {
+                                 size_t base_bytes, int nslots = 0) {
     Carve k(p, cap, base_bytes);
     AppliedWork w{};
     w.stage = k.take<double>((size_t)B * nrhs * c->npad);
@@ -184,6 +188,16 @@ static AppliedWork carve_applied(const sf_ctx* c, const sf_model_desc* mdl, int 
         w.winv = k.take<double>(sf_chol_inverse_work_doubles(c->npad, B));
     }
     if (parts & AW_PART) w.part = k.take<double>(sf_cov_grad_work_doubles(c->n, mdl->has_global, mdl->n_local, B));
+    if (parts & AW_MEAN) {
+        w.xs = k.take<double>((size_t)B * c->m * c->n);
+        w.fin = k.take<double>((size_t)B * sf_mean_fin_doubles(c->m));
+        w.mpart = k.take<double>(sf_mean_grad_part_doubles(c->n, nslots, B));
+        if (mdl->has_vsini) w.dcoef = k.take<double>((size_t)B * c->nf * c->rows);
+        const size_t ng = (size_t)(nslots < c->P ? nslots : c->P), mM = (size_t)c->m * c->M;
+        w.kdot = k.take<double>(ng * B * mM);
+        w.mudot = k.take<double>(ng * B * c->m);
+        w.zdot = k.take<double>(ng * B * mM * c->m);
+    }
     w.bytes = sf_align_up(k.off, 256);
     return w;
 }

@@ -714,6 +714,66 @@ class SpectrumModel:
             self.set_param_dict(dict(zip(glabels, soln.x)))
         return soln
 
+    # ------------------------------------------------------------------ gradient in the mean-flux parameters
+    @property
+    def mean_gradient_labels(self):
+        """tuple of str : the thawed labels that are not under ``global_cov:`` / ``local_cov:``, in :attr:`labels` order: the
+        parameters :meth:`log_likelihood_mean_gradient` differentiates in.  ``Rv`` is left out: it is never passed on."""
+        return tuple(key for key in self.labels if not key.startswith(("global_cov:", "local_cov:")) and key != "Rv")
+
+    def _mean_gradient_columns(self, dev, md):
+        """For every label of :attr:`mean_gradient_labels`, its column of the C-ABI parameter row; raises ``ValueError`` for a
+        model the device does not differentiate."""
+        labels = self.mean_gradient_labels
+        if not labels:
+            raise ValueError("no thawed mean-flux parameter to differentiate in")
+        if "log_scale" not in self.params:
+            raise ValueError("the mean gradient needs log_scale: the renormalising scale is not differentiated")
+        if self.emulator_cov == "paper":
+            raise ValueError('the mean gradient covers emulator_cov="code" only, not the form of the paper (emulator_cov="paper")')
+        if self.norm and any(key in self.emulator.param_names for key in labels):
+            raise ValueError("norm=True with a thawed grid parameter: the derivative of the host's norm-factor interpolant is "
+                             "not built; freeze the grid parameters")
+        slots = self._slot_of(dev, md)
+        return [slots[key] for key in labels]
+
+    def log_likelihood_mean_gradient(self):
+        """``(lnL, {label: d lnL / d label})`` of the current state for the labels of :attr:`mean_gradient_labels`: the analytic
+        gradient of :meth:`log_likelihood` (no priors) in vsini, vz, log_scale, Av, the Chebyshev coefficients and the grid
+        parameters, from the likelihood's factorisation and one solve with 1 + m right-hand sides.  Raises as
+        :meth:`log_likelihood` does; the model's state is not modified."""
+        dev, md, rows = self._pack(update_caches=False)
+        out = self._own(dev.loglike_mean_grad(md, rows, self._mean_gradient_columns(dev, md)))
+        return float(out["lnl"]), dict(zip(self.mean_gradient_labels, (float(v) for v in out["grad"])))
+
+    def log_likelihood_mean_gradient_batch(self, P, return_info=False):
+        """:meth:`log_likelihood_mean_gradient` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device
+        pass: ``(lnL (B,), grad (B, len(mean_gradient_labels)))``.  Walkers that fail get ``-inf`` and a NaN row, ``info`` their
+        codes.  The model's own state is not modified."""
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        dev, md, rows = self._pack(P, update_caches=False)
+        out = dev.loglike_mean_grad(md, rows, self._mean_gradient_columns(dev, md))
+        lnl = np.where(out["info"] == 0, out["lnl"], -np.inf)
+        return (lnl, out["grad"], out["info"]) if return_info else (lnl, out["grad"])
+
+    def log_likelihood_full_gradient_batch(self, P, return_info=False):
+        """``(lnL (B,), grad (B, len(labels)))``: the gradient in every thawed label, columns in :attr:`labels` order -- the mean
+        call's columns and, where covariance labels are thawed, :meth:`log_likelihood_gradient_batch`'s (two device calls).  A
+        thawed ``Rv`` gets a zero column: it is never passed on."""
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        labels = self.labels
+        grad = np.zeros((P.shape[0], len(labels)))
+        lnl = info = None
+        if self.mean_gradient_labels:
+            lnl, g, info = self.log_likelihood_mean_gradient_batch(P, return_info=True)
+            grad[:, [labels.index(key) for key in self.mean_gradient_labels]] = g
+        if self.gradient_labels:
+            lnl, g, info = self.log_likelihood_gradient_batch(P, return_info=True)
+            grad[:, [labels.index(key) for key in self.gradient_labels]] = g
+        if lnl is None:
+            raise ValueError("no thawed parameter to differentiate in")
+        return (lnl, grad, info) if return_info else (lnl, grad)
+
     def _checked_priors(self, priors):
         """``priors`` ({} for None) after the checks of :meth:`train` (spectrum_model.py:655-668)."""
         priors = {} if priors is None else priors
@@ -727,9 +787,15 @@ class SpectrumModel:
                 raise RuntimeError(f"{key}'s logpdf evaluated to {log_prob}")
         return priors
 
-    def train(self, priors=None, batch_simplex=True, **kwargs):
+    def train(self, priors=None, batch_simplex=True, gradient=False, **kwargs):
         """MAP estimate by Nelder-Mead over :meth:`log_likelihood` (spectrum_model.py:635-696).  ``kwargs`` go to
         ``scipy.optimize.minimize`` as in the reference.
+
+        With ``gradient=True`` the search is ``minimize(method="L-BFGS-B", jac=True)`` over all of :attr:`labels` on the analytic
+        gradient of :meth:`log_likelihood_full_gradient_batch`; priors and their slopes are handled as in
+        :meth:`train_covariance`, a point the device flags raises as :meth:`log_likelihood` does, every evaluation leaves the
+        model at its point, a run that succeeds or stops at its iteration limit at ``soln.x``; ``batch_simplex`` plays no part then.  Without it the path below is
+        unchanged.
 
         The reference's loop is ~10^3 SERIAL scalar evaluations.  Here (``batch_simplex=True``, a plain Nelder-Mead run:
         no other ``method``, no bounds) the candidate points of every simplex iteration -- reflection, expansion, both
@@ -743,6 +809,8 @@ class SpectrumModel:
         from .._neldermead import minimize_neldermead_batched, split_minimize_kwargs
 
         priors = self._checked_priors(priors)
+        if gradient:
+            return self._train_gradient(minimize, priors, kwargs)
 
         def nll(P):
             self.set_param_vector(P)
@@ -768,6 +836,34 @@ class SpectrumModel:
             # residual deque, _lnprob): ONE scalar evaluation at that point
             nll(soln.last_x)
         if soln.success:
+            self.set_param_vector(soln.x)
+        return soln
+
+    def _train_gradient(self, minimize, priors, kwargs):
+        """The ``gradient=True`` search of :meth:`train`."""
+        labels = self.labels
+        const_lp = sum(prior.logpdf(self[key]) for key, prior in priors.items() if key in self.params and key not in labels)
+        h0 = np.finfo(np.float64).eps ** (1.0 / 3.0)
+
+        def objective(x):
+            if np.any(~np.isfinite(x)):
+                raise ValueError("SpectrumModel.train: the optimiser asked for a point that is not finite")
+            self.set_param_vector(x)
+            lnl, grad, info = self.log_likelihood_full_gradient_batch(x[None, :], return_info=True)
+            self._raise_for_info(info[0])
+            value, slope = float(lnl[0]) + const_lp, grad[0].copy()
+            for i, key in enumerate(labels):
+                if key in priors:
+                    h = h0 * max(1.0, abs(x[i]))
+                    value += priors[key].logpdf(x[i])
+                    slope[i] += (priors[key].logpdf(x[i] + h) - priors[key].logpdf(x[i] - h)) / (2 * h)
+            return -value, -slope
+
+        opts = {"method": "L-BFGS-B"}
+        opts.update(kwargs)
+        opts["jac"] = True
+        soln = minimize(objective, self.get_param_vector().astype(np.float64), **opts)
+        if soln.success or soln.status == 1:  # (1: the iteration / evaluation limit; soln.x is the best point so far)
             self.set_param_vector(soln.x)
         return soln
 

@@ -1,5 +1,5 @@
 """What the stand-alone timers of the calls on the Cholesky factor share (bench_potrs.py, bench_decompose.py,
-bench_pointwise.py, bench_gradient.py): the argv convention ``[reps] [B] [N ...]``, the event timing, the synthetic order with
+bench_pointwise.py, bench_gradient.py, bench_mean_gradient.py): the argv convention ``[reps] [B] [N ...]``, the event timing, the synthetic order with
 its walkers and the synthetic factor."""
 import os
 import sys
