@@ -441,6 +441,50 @@ int sf_loglike_multi_batch_md(const sf_segment* segs, int nseg, const sf_model_d
                               double* d_lnl, double* d_logdet, double* d_sqmah, double* d_log_scale,
                               int* d_info, void* d_work, size_t work_bytes, void* stream);
 
+/* The likelihood of the units of several orders AND its gradient, from ONE factorisation per unit: the sequence of
+ * sf_loglike_multi_batch_md (same chunks, lanes and frame; d_lnl, d_log_scale and d_info have its bits for the same segments)
+ * with the right-hand sides [r, X_1 .. X_m] of sf_loglike_mean_grad_batch (r alone in a call without mean slots) staged
+ * behind every order's transform chain, SF_APPLY_CINV applied to the staging area of a whole chunk in one launch, the inverse
+ * factor of sf_loglike_grad_batch formed for the chunks in which a segment wants covariance slots, and then per segment the
+ * two contractions of the single-order calls: both need only alpha = C^-1 r, V = C^-1 X^T and X = L^-1 of the same factor.
+ * requests[i] says what segment i is differentiated in: h_mean_slots (HOST) / n_mean_slots as sf_loglike_mean_grad_batch's
+ * h_slots / nslots, except that 0 slots ask for none; want_cov != 0 for the covariance slots of models[i] in
+ * sf_loglike_grad_batch's order.  d_grad[u * grad_stride + j], u = sum_{j<i} B_j + b: the row of a unit of segment i holds that
+ * segment's mean slots in request order, then its covariance slots; entries of the row beyond them are not touched; a segment
+ * that requests nothing gets lnl only.  Orders shorter than the group's common npad are padded with an identity block: every
+ * contraction masks at the order's own n.  A subset of slots gives the bits of those slots of a larger request.  Units with
+ * d_info[u] != 0 get NaN in every slot of theirs.  Every sum has a fixed order: a repeated call gives the same bits.
+ * d_log_scale may be NULL.  SF_EINVAL before anything is enqueued, the message naming the segment: whatever
+ * sf_loglike_multi_batch_md refuses; null requests, d_lnl, d_info or d_grad; a segment with more than 65535 units that requests
+ * something; for a segment with mean slots whatever sf_loglike_mean_grad_batch refuses (a model without log_scale,
+ * use_sigma_w, more than SF_MEAN_GRAD_MAX_SLOTS columns, a repeated or foreign column); want_cov on a model without global
+ * and local kernels; a row shorter than a segment's slots; a call in which no segment requests anything ("nothing to
+ * differentiate").  d_work: sf_multi_grad_workspace_bytes_md(...) (0 for bad arguments): the workspace of
+ * sf_loglike_multi_batch_md, 1 + m (1 without mean slots) rows of the common npad doubles per unit, with covariance slots a
+ * further row and the scratch of sf_potri_diag_batch per unit, and per segment what the single-order calls keep per walker
+ * (sf_loglike_mean_grad_workspace_bytes, sf_loglike_grad_workspace_bytes) plus, with mean slots and vsini, a third set of
+ * spline coefficients. */
+typedef struct sf_grad_request {
+    const int32_t* h_mean_slots; /* HOST: columns of the parameter row */
+    int32_t n_mean_slots;        /* 0 .. SF_MEAN_GRAD_MAX_SLOTS */
+    int32_t want_cov;            /* 1: the covariance slots of models[i], in sf_loglike_grad_batch's order */
+} sf_grad_request;
+size_t sf_multi_grad_workspace_bytes_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                        const sf_grad_request* requests, int grad_stride);
+int sf_loglike_multi_grad_batch_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                   const sf_grad_request* requests, double* d_lnl, double* d_log_scale, int* d_info,
+                                   double* d_grad, int grad_stride, void* d_work, size_t work_bytes, void* stream);
+/* The sum over the orders of what the call above leaves, for nseg segments of W walkers each (unit = i * W + w): per walker
+ * d_lnl[w] = ((lnl_0 + lnl_1) + ...) in ascending order index, d_info[w] = the first non-zero unit code in that order, and
+ * d_grad[w * out_stride + j], j < ncols, the same fixed-order sum of the unit slots that column j's list names:
+ * d_col_src[2 q], d_col_src[2 q + 1] = (segment, slot) for d_col_ptr[j] <= q < d_col_ptr[j + 1] (DEVICE, int32, ascending in the
+ * segment within a column); a column without a source is 0.0.  Where d_info[w] != 0, d_lnl[w] = -inf and every column is NaN.
+ * Plain adds, no atomics: a repeated call gives the same bits.  A source outside the unit rows is not read (NaN).  SF_EINVAL: a
+ * null pointer, nseg < 1, W outside 1 .. 65535, ncols < 0, grad_stride < 1, out_stride < ncols. */
+int sf_multi_grad_reduce(int nseg, int W, const double* d_unit_lnl, const int* d_unit_info, const double* d_unit_grad,
+                         int grad_stride, const int32_t* d_col_ptr, const int32_t* d_col_src, int ncols, double* d_lnl,
+                         double* d_grad, int out_stride, int* d_info, void* stream);
+
 /* ---- structure-exploiting solver -----------------------------------
  * Same value as sf_loglike_batch, computed without ever forming the N x N matrix: the covariance of
  * spectrum_model.py:334-363 is  C = Bd + Y^T Y  with Bd = sigma^2 + K_global + K_local + jitter

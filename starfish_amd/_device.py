@@ -357,6 +357,148 @@ def loglike_multi(orders, md, rows_list, max_units=None, sync=True):
     return plan.collect() if sync else plan
 
 
+class MultiGradPlan(MultiPlan):
+    """Device-resident state of a repeated multi-order likelihood-and-gradient evaluation (sf_loglike_multi_grad_batch_md):
+    one factorisation per (order x walker) unit gives the likelihood and the gradient in every requested slot.  ``mds``: one
+    ModelDesc per order; ``requests[i]`` = ``(mean_columns, want_cov)``: the columns of order i's parameter row to
+    differentiate in (as :meth:`DeviceOrder.loglike_mean_grad` takes them; may be empty) and whether its covariance slots
+    (in :meth:`DeviceOrder.loglike_grad`'s order) are wanted.  The gradient row of a unit holds its order's mean slots in
+    request order, then its covariance slots.  Buffers are allocated once; unit lists that do not fit the free HBM (or
+    ``max_units``) are cut into several calls, a piece in which no order requests anything is a plain likelihood call."""
+
+    def __init__(self, orders, mds, rows_list, requests, max_units=None):
+        if len(requests) != len(orders):
+            raise ValueError(f"multi-order gradient: {len(requests)} requests for {len(orders)} orders")
+        self.requests = [([int(c) for c in cols], bool(cov)) for cols, cov in requests]
+        self.slots = [len(cols) + (((2 if md.has_global else 0) + 3 * int(md.n_local)) if cov else 0)
+                      for (cols, cov), md in zip(self.requests, mds)]
+        if not any(self.slots):
+            raise ValueError("multi-order gradient: nothing to differentiate (no order requests a slot)")
+        self.stride = max(self.slots)
+        self._slot_arrays = [(C.c_int32 * max(len(cols), 1))(*cols) for cols, _ in self.requests]
+        super().__init__(orders, list(mds), rows_list, max_units=max_units)
+        with _torch().cuda.device(self.dev):
+            self.grad = _torch().zeros((self.units, self.stride), dtype=_torch().float64, device=self.dev)
+
+    def _requests_array(self, idxs):
+        """``const sf_grad_request*`` of the given orders (the array keeps the column lists alive)."""
+        arr = (_lib.GradRequest * len(idxs))()
+        for k, i in enumerate(idxs):
+            cols, cov = self.requests[i]
+            arr[k] = _lib.GradRequest(self._slot_arrays[i], len(cols), int(cov))
+        arr._keep = self._slot_arrays
+        return arr
+
+    def _workspace_bytes(self, segs, nseg, models):
+        """The gradient call's workspace for these segments; they are matched to their orders by context."""
+        by_ctx = {int(o.ctx): i for i, o in enumerate(self.orders)}
+        items = [segs[k] for k in range(nseg)] if isinstance(segs, C.Array) else [segs._obj]  # (an array, or byref of one)
+        idxs = [by_ctx[int(seg.ctx)] for seg in items]
+        if not any(self.slots[i] for i in idxs):
+            return self.lib.sf_multi_workspace_bytes_md(segs, nseg, models)
+        return self.lib.sf_multi_grad_workspace_bytes_md(segs, nseg, models, self._requests_array(idxs), self.stride)
+
+    def enqueue(self):
+        """Launch only: results land in ``self.quad`` (rows 0 lnl, 3 log_scale), ``self.info`` and ``self.grad`` once the
+        device's current stream is done."""
+        torch = _torch()
+        with torch.cuda.device(self.dev):
+            s = stream_ptr(self.dev)
+            q = self.quad
+            for (segs, nseg, u0, n, models), piece in zip(self.calls, self.pieces):
+                idxs = [i for i, _, _ in piece]
+                if not any(self.slots[i] for i in idxs):
+                    rc = self.lib.sf_loglike_multi_batch_md(segs, nseg, models, ptr(q[0][u0:u0 + n]), None, None,
+                                                            ptr(q[3][u0:u0 + n]), ptr(self.info[u0:u0 + n]), ptr(self.ws),
+                                                            self.ws.numel(), s)
+                    _lib.check(rc, "sf_loglike_multi_batch_md")
+                    continue
+                rc = self.lib.sf_loglike_multi_grad_batch_md(
+                    segs, nseg, models, self._requests_array(idxs), ptr(q[0][u0:u0 + n]), ptr(q[3][u0:u0 + n]),
+                    ptr(self.info[u0:u0 + n]), ptr(self.grad[u0:u0 + n]), self.stride, ptr(self.ws), self.ws.numel(), s)
+                _lib.check(rc, "sf_loglike_multi_grad_batch_md")
+
+    def collect(self):
+        """Per order a dict of numpy arrays: lnl (B,), grad (B, slots of the order), log_scale (B,), info (B,); NaN rows
+        where info != 0.  After SF_INFO_INTERNAL the whole batch is run once more (:func:`retry_internal`)."""
+        def fetch(again):  # (the first run was enqueued by the caller)
+            if again:
+                self.enqueue()
+            lnl, log_scale = self.quad[0].cpu().numpy(), self.quad[3].cpu().numpy()
+            info, grad = self.info.cpu().numpy(), self.grad.cpu().numpy()
+            ends = np.cumsum(self.sizes)
+            out = [dict(lnl=lnl[hi - n:hi], grad=grad[hi - n:hi, :k], log_scale=log_scale[hi - n:hi], info=info[hi - n:hi])
+                   for n, hi, k in zip(self.sizes, ends, self.slots)]
+            return out, info
+
+        return retry_internal(self.lib, "sf_loglike_multi_grad_batch_md", fetch)
+
+    def reduce(self, sources):
+        """The sum over the orders on the device (sf_multi_grad_reduce), of what a finished call left in the plan's buffers:
+        ``sources[j]`` lists the ``(order, slot)`` pairs whose unit slots column j adds, ascending in the order.  Every
+        order must have the same number of walkers W.  Returns numpy ``lnl (W,)``, ``grad (W, len(sources))``, ``info (W,)``."""
+        torch = _torch()
+        if len(set(self.sizes)) != 1:
+            raise ValueError(f"sf_multi_grad_reduce: the orders have {sorted(set(self.sizes))} walkers")
+        W, ncols = self.sizes[0], len(sources)
+        col_ptr, col_src = column_map_csr(sources)
+        with torch.cuda.device(self.dev):
+            d_ptr, d_src = torch.from_numpy(col_ptr).to(self.dev), torch.from_numpy(col_src).to(self.dev)
+            lnl, grad = empty((W,), self.dev), empty((W, max(ncols, 1)), self.dev)
+            info = empty((W,), self.dev, torch.int32)
+            rc = self.lib.sf_multi_grad_reduce(len(self.sizes), W, ptr(self.quad[0]), ptr(self.info), ptr(self.grad), self.stride,
+                                               ptr(d_ptr), ptr(d_src), ncols, ptr(lnl), ptr(grad), max(ncols, 1), ptr(info),
+                                               stream_ptr(self.dev))
+            _lib.check(rc, "sf_multi_grad_reduce")
+            return lnl.cpu().numpy(), grad.cpu().numpy()[:, :ncols], info.cpu().numpy()
+
+
+def column_map_csr(sources):
+    """``sources[j]`` = [(order, slot), ...] -> the int32 arrays ``col_ptr (ncols + 1,)`` and ``col_src (nnz, 2)`` of
+    sf_multi_grad_reduce, the pairs of every column ascending in the order."""
+    col_ptr = np.zeros(len(sources) + 1, dtype=np.int32)
+    pairs = []
+    for j, src in enumerate(sources):
+        pairs += sorted((int(i), int(slot)) for i, slot in src)
+        col_ptr[j + 1] = len(pairs)
+    col_src = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    if not len(pairs):
+        col_src = np.zeros((1, 2), dtype=np.int32)
+    return col_ptr, np.ascontiguousarray(col_src)
+
+
+def reduce_orders_host(lnl, info, grads, sources):
+    """sf_multi_grad_reduce's rule on the host, for per-unit results that live on several devices: ``lnl``, ``info``
+    (n_orders, W), ``grads[i]`` (W, slots of order i).  Every sum runs over the orders in ascending index, ``s = g0;
+    s = s + g1; ...``; a column without a source is 0.0; ``info`` is the first non-zero code in that order, and a walker
+    that has one gets ``-inf`` and a NaN row."""
+    lnl, info = np.asarray(lnl, dtype=np.float64), np.asarray(info, dtype=np.int32)
+    W = lnl.shape[1]
+    total = lnl[0].copy()
+    for i in range(1, lnl.shape[0]):
+        total = total + lnl[i]
+    code = np.zeros(W, dtype=np.int32)
+    for i in range(info.shape[0]):
+        code = np.where(code == 0, info[i], code)
+    grad = np.zeros((W, len(sources)))
+    for j, src in enumerate(sources):
+        for q, (i, slot) in enumerate(sorted((int(i), int(slot)) for i, slot in src)):
+            grad[:, j] = grads[i][:, slot] if q == 0 else grad[:, j] + grads[i][:, slot]
+    bad = code != 0
+    total[bad] = -np.inf
+    grad[bad] = np.nan
+    return total, grad, code
+
+
+def loglike_multi_grad(orders, mds, rows_list, requests, max_units=None, sync=True):
+    """The likelihood and its gradient for the (order x walker) units of several orders of ONE device, one factorisation per
+    unit, in one enqueue and one host synchronisation (see :class:`MultiGradPlan` for ``mds`` and ``requests``).  Returns
+    a list of dicts (lnl, grad, log_scale, info) per order; with ``sync=False`` the un-synchronised plan."""
+    plan = MultiGradPlan(orders, mds, rows_list, requests, max_units=max_units)
+    plan.enqueue()
+    return plan.collect() if sync else plan
+
+
 def collect_multi(quad, info, sizes):
     host = fetch_results(quad, info)
     ends = np.cumsum(sizes)

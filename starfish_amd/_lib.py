@@ -63,6 +63,12 @@ class Segment(C.Structure):
     _fields_ = [("ctx", C.c_void_p), ("d_params", C.c_void_p), ("B", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GradRequest(C.Structure):
+    """``sf_grad_request``: what one segment of sf_loglike_multi_grad_batch_md is differentiated in."""
+
+    _fields_ = [("h_mean_slots", C.POINTER(C.c_int32)), ("n_mean_slots", C.c_int32), ("want_cov", C.c_int32)]
+
+
 # name -> (restype, argtypes); kept in one table so the CPU test-suite can check that every symbol
 # declared in include/starfish_amd.h is exported.
 _VP = C.c_void_p
@@ -213,6 +219,19 @@ SIGNATURES = {
     "sf_loglike_multi_batch_md": (
         C.c_int,
         [C.POINTER(Segment), C.c_int, C.POINTER(C.POINTER(ModelDesc)), _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP],
+    ),
+    "sf_multi_grad_workspace_bytes_md": (
+        C.c_size_t,
+        [C.POINTER(Segment), C.c_int, C.POINTER(C.POINTER(ModelDesc)), C.POINTER(GradRequest), C.c_int],
+    ),
+    "sf_loglike_multi_grad_batch_md": (
+        C.c_int,
+        [C.POINTER(Segment), C.c_int, C.POINTER(C.POINTER(ModelDesc)), C.POINTER(GradRequest), _VP, _VP, _VP, _VP, C.c_int, _VP,
+         C.c_size_t, _VP],
+    ),
+    "sf_multi_grad_reduce": (
+        C.c_int,
+        [C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP],
     ),
     "sf_banded_max_halfwidth": (C.c_int, [_VP]),
     "sf_banded_window_halfwidth": (C.c_int, [_VP]),

@@ -57,33 +57,34 @@ static int grad_slots_ok(const AppliedCall& k, const sf_model_desc* mdl, int gra
     return SF_OK;
 }
 // the mean gradient's own (behind model_ok): a model it differentiates, and columns that are mean-flux parameters of it
-static int mean_slots_ok(const AppliedCall& k, const sf_ctx* c, const sf_model_desc* mdl, const AppliedArgs& a) {
+// (shared with the multi-order gradient call: sf_stages.h)
+int mean_slots_ok(const char* who, const sf_ctx* c, const sf_model_desc* mdl, const int* h_slots, int nslots, int grad_stride) {
     if (!mdl->has_log_scale || mdl->use_sigma_w) {
-        sf_set_error("%s: %s", k.name, mdl->use_sigma_w ? "use_sigma_w (the paper's form of the emulator term) is not differentiated"
-                                                        : "a model without log_scale (the renormalising scale) is not differentiated");
+        sf_set_error("%s: %s", who, mdl->use_sigma_w ? "use_sigma_w (the paper's form of the emulator term) is not differentiated"
+                                                     : "a model without log_scale (the renormalising scale) is not differentiated");
         return SF_EINVAL;
     }
-    if (a.nslots < 1 || a.nslots > SF_MEAN_GRAD_MAX_SLOTS) {
-        sf_set_error("%s: nslots=%d must lie in 1 .. %d", k.name, a.nslots, SF_MEAN_GRAD_MAX_SLOTS);
+    if (nslots < 1 || nslots > SF_MEAN_GRAD_MAX_SLOTS) {
+        sf_set_error("%s: nslots=%d must lie in 1 .. %d", who, nslots, SF_MEAN_GRAD_MAX_SLOTS);
         return SF_EINVAL;
     }
-    if (a.grad_stride < a.nslots) {
-        sf_set_error("%s: grad_stride=%d < %d slots", k.name, a.grad_stride, a.nslots);
+    if (grad_stride < nslots) {
+        sf_set_error("%s: grad_stride=%d < %d slots", who, grad_stride, nslots);
         return SF_EINVAL;
     }
     const int off_cheb = 6 + c->P, off_av = off_cheb + mdl->n_cheb + 3 * mdl->n_local;
-    for (int j = 0; j < a.nslots; ++j) {
-        const int col = a.h_slots[j];
+    for (int j = 0; j < nslots; ++j) {
+        const int col = h_slots[j];
         for (int i = 0; i < j; ++i)
-            if (a.h_slots[i] == col) {
-                sf_set_error("%s: column %d is listed twice", k.name, col);
+            if (h_slots[i] == col) {
+                sf_set_error("%s: column %d is listed twice", who, col);
                 return SF_EINVAL;
             }
         const bool ok = (col == 0 && mdl->has_vsini) || (col == 1 && mdl->has_vz) || col == 2 || (col >= 6 && col < off_av) ||
                         (col == off_av && mdl->has_av);
         if (ok && !(col >= off_cheb + mdl->n_cheb && col < off_av)) continue;
         sf_set_error("%s: column %d is not a differentiable mean parameter of this model (vsini, vz, log_scale, grid, cheb, Av)",
-                     k.name, col);
+                     who, col);
         return SF_EINVAL;
     }
     return SF_OK;
@@ -106,7 +107,7 @@ static int args_ok(const AppliedCall& k, const sf_ctx* c, const sf_model_desc* m
     }
     if (k.parts & AW_PART) SF_CHECK(grad_slots_ok(k, mdl, a.grad_stride));
     SF_CHECK(model_ok(c, mdl));
-    if (k.parts & AW_MEAN) SF_CHECK(mean_slots_ok(k, c, mdl, a));
+    if (k.parts & AW_MEAN) SF_CHECK(mean_slots_ok(k.name, c, mdl, a.h_slots, a.nslots, a.grad_stride));
     if (k.rhs && a.d_rhs && a.ldr < c->n) {
         sf_set_error("%s: ldr=%d < n (%d)", k.name, a.ldr, c->n);
         return SF_EINVAL;
@@ -284,8 +285,8 @@ extern "C" size_t sf_loglike_mean_grad_workspace_bytes(const sf_ctx* c, const sf
     if (model_ok(c, mdl) || nslots < 1 || nslots > SF_MEAN_GRAD_MAX_SLOTS) return 0;
     return workspace_bytes(MEAN_GRAD, c, mdl, B, 1 + c->m, nslots);
 }
-static sf_mean_grad_args mean_grad_kernel_args(const sf_ctx* c, const int* h_slots, int nslots, const Work& w, const AppliedWork& aw,
-                                               double* d_grad, int grad_stride) {
+sf_mean_grad_args mean_grad_kernel_args(const sf_ctx* c, const int* h_slots, int nslots, const Work& w, const AppliedWork& aw,
+                                        double* d_grad, int grad_stride) {
     sf_mean_grad_args a;
     a.stage = aw.stage, a.Xs = aw.xs, a.Lw = w.Lw, a.mu = w.mu, a.scale = w.scale, a.info = aw.info;
     a.fin = aw.fin, a.part = aw.mpart, a.grad = d_grad;

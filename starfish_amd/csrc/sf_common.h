@@ -217,6 +217,19 @@ static inline __host__ __device__ int sf_cov_grad_slots(int has_global, int n_lo
 size_t sf_cov_grad_work_doubles(int n, int has_global, int n_local, int batch);
 int sf_launch_cov_grad(const sf_fill_args& f, int batch, const double* winv, const double* alpha, int ld_alpha, const int* info,
                        double* part, double* grad, int grad_stride, hipStream_t s);
+// sf_grad_frame.h: the sum over the orders of a multi-order gradient (sf_multi_grad_reduce)
+struct sf_multi_reduce_args {
+    const double* unit_lnl;   // [nseg * W]
+    const int* unit_info;     // [nseg * W]
+    const double* unit_grad;  // [nseg * W][grad_stride]
+    const int* col_ptr;       // [ncols + 1]
+    const int* col_src;       // [col_ptr[ncols]][2]: (segment, slot)
+    int nseg, W, grad_stride, ncols, out_stride;
+    double* lnl;   // [W]
+    double* grad;  // [W][out_stride]
+    int* info;     // [W]
+};
+int sf_launch_multi_grad_reduce(const sf_multi_reduce_args& a, hipStream_t s);
 // sf_emu_grad.h: the emulator training likelihood's gradient in the LOGS of its hyper-parameters, contracted from the blocks of
 // v11^-1: grid, hyper (raw rows), iphiphi as sf_launch_v11_build_batch gets them; L: the factored matrices after the inverse's
 // launch; alpha: [batch][ld_alpha] = v11^-1 w_hat; part: sf_emu_grad_work_doubles of scratch; grad[b * grad_stride + slot] in

@@ -18,7 +18,7 @@
 //   sf_fill_free.h    k_global_cov, k_local_cov, k_stream_write: stand-alone kernels and the write probe
 //   sf_cov_matvec.h   k_cov_yv, k_cov_matvec: the components of C applied to vectors (sf_decompose_batch)
 //   sf_cinv.h         sf_cinv_tile, k_cinv_blocks: 64 x 64 blocks of C^-1 from the inverse factor
-//   sf_grad_frame.h   sf_grad_tile, sf_grad_flush, k_grad_sum, sf_launch_grad: what the two likelihood gradients share
+//   sf_grad_frame.h   sf_grad_tile, sf_grad_flush, k_grad_sum, sf_launch_grad: what the two likelihood gradients share; k_multi_grad_reduce
 //   sf_cov_grad.h     k_cov_grad: the likelihood's gradient in the covariance hyper-parameters
 //   sf_emu_grad.h     k_emu_grad: the emulator training likelihood's gradient in its hyper-parameters
 #include "sf_common.h"

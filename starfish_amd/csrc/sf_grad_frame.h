@@ -11,6 +11,7 @@
 //                    J < I, 1 for J == I, where the whole tile is formed), to the slot's running sum in LDS.
 // Partial sums per (matrix, block row, slot) go to the workspace (sf_grad_part), and
 //   k_grad_sum       one thread per (matrix, slot) adds the block rows in ascending order, times 1/2; NaN where info != 0.
+//   k_multi_grad_reduce  the sum over the orders of a multi-order gradient, per (walker, column), in ascending order index.
 // No atomics, no workgroup waits for another, every sum in a fixed order (a repeated call gives the same bits); nothing of
 // the lower triangle is written; rows and columns >= n are not read as data (their alpha and entries are masked) and
 // nothing is written for them.
@@ -88,6 +89,48 @@ __global__ void k_grad_sum(const sf_grad_out o) {
     }
     o.grad[(int64_t)b * o.grad_stride + q] = s;
 }
+// The sum over the orders of a multi-order gradient (sf_multi_grad_reduce): per-unit results stored order-major
+// (unit = i * W + w), one thread per (walker, column).  Column j < ncols adds the unit slots its CSR list names, ascending in
+// the segment: s = g0; s = s + g1; ... (0.0 without a source); column ncols is the walker's lnl, the same fixed-order sum over
+// all the orders, and its status, the first non-zero unit code in ascending order.  A walker with a non-zero status gets
+// lnl = -inf and NaN in every column.  A source outside the unit rows is not read: the column comes out NaN.
+__global__ void k_multi_grad_reduce(const sf_multi_reduce_args a) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, w = blockIdx.y;
+    if (j > a.ncols) return;
+    int code = 0;
+    for (int i = 0; i < a.nseg && code == 0; ++i) code = a.unit_info[(int64_t)i * a.W + w];
+    if (j == a.ncols) {
+        double s = a.unit_lnl[w];
+        for (int i = 1; i < a.nseg; ++i) s = s + a.unit_lnl[(int64_t)i * a.W + w];
+        a.lnl[w] = code != 0 ? -__builtin_inf() : s;
+        a.info[w] = code;
+        return;
+    }
+    double s = 0.0;
+    if (code != 0) {
+        s = __builtin_nan("");
+    } else {
+        const int lo = a.col_ptr[j], hi = a.col_ptr[j + 1];
+        for (int q = lo; q < hi; ++q) {
+            const int i = a.col_src[2 * q], slot = a.col_src[2 * q + 1];
+            double g = __builtin_nan("");
+            if (i >= 0 && i < a.nseg && slot >= 0 && slot < a.grad_stride)
+                g = a.unit_grad[((int64_t)i * a.W + w) * a.grad_stride + slot];
+            s = q == lo ? g : s + g;
+        }
+    }
+    a.grad[(int64_t)w * a.out_stride + j] = s;
+}
+int sf_launch_multi_grad_reduce(const sf_multi_reduce_args& a, hipStream_t s) {
+    if (a.nseg < 1 || a.W < 1 || a.W > 65535 || a.ncols < 0 || a.grad_stride < 1 || a.out_stride < a.ncols) {
+        sf_set_error("sf_multi_grad_reduce: nseg >= 1, W in 1 .. 65535, ncols >= 0, grad_stride >= 1 and out_stride >= ncols");
+        return SF_EINVAL;
+    }
+    hipLaunchKernelGGL(k_multi_grad_reduce, dim3((a.ncols + 1 + 63) / 64, a.W), dim3(64), 0, s, a);
+    SF_LAUNCH_CHECK();
+    return SF_OK;
+}
+
 // the launch tail of a contraction: its block-row kernel over (matrix, block row), then the sum over the block rows
 template <class Args>
 static int sf_launch_grad(void (*kernel)(const Args), const Args& a, const sf_grad_out& o, hipStream_t s) {

@@ -4,6 +4,9 @@
 // and covariance fill into its slice of a common [units][npad][lda] array, padded (identity block) to the largest
 // order of the group; the Cholesky, which is where the time goes, then sees sum(B_i) matrices in one launch
 // sequence instead of nseg half-filled ones, and the host synchronises once.
+// sf_loglike_multi_grad_batch_md is the same sequence with a gradient part (MultiGradCall): right-hand sides staged behind
+// every order's chain, the factor applied to a whole chunk's staging area at once, and per segment the contractions of the
+// two single-order gradient calls -- one factorisation per unit for the likelihood and its gradient.
 #include <algorithm>
 #include <cstdio>
 #include <string>
@@ -91,20 +94,146 @@ extern "C" size_t sf_multi_workspace_bytes(const sf_segment* segs, int nseg, con
 extern "C" size_t sf_multi_workspace_bytes_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models) {
     return multi_workspace_bytes(segs, nseg, models);
 }
+// ---- the gradient's part of a multi-order call (sf_loglike_multi_grad_batch_md)
+#define MULTI_GRAD "sf_loglike_multi_grad_batch_md"
+struct MultiGradCall {
+    const sf_grad_request* reqs;
+    double* d_grad;
+    int grad_stride;
+    MultiGradWork G;  // carved by loglike_multi behind the Work of the call
+};
+// every per-segment requirement of the two single-order gradient calls, for the segment that requests the part (behind
+// multi_layout: contexts and models are good)
+static int multi_grad_requests_ok(const sf_segment* segs, int nseg, const sf_model_desc* const* models, const sf_grad_request* reqs,
+                                  int grad_stride) {
+    if (!reqs) {
+        sf_set_error(MULTI_GRAD ": requests are required");
+        return SF_EINVAL;
+    }
+    bool any = false;
+    for (int i = 0; i < nseg; ++i) {
+        const sf_grad_request& r = reqs[i];
+        char who[96];
+        snprintf(who, sizeof who, MULTI_GRAD ": segment %d", i);
+        int slots = 0;
+        if (r.n_mean_slots != 0) {
+            if (r.n_mean_slots < 0 || !r.h_mean_slots) {
+                sf_set_error("%s: n_mean_slots=%d without columns", who, r.n_mean_slots);
+                return SF_EINVAL;
+            }
+            SF_CHECK(mean_slots_ok(who, segs[i].ctx, models[i], r.h_mean_slots, r.n_mean_slots, grad_stride));
+            slots += r.n_mean_slots;
+        }
+        if (r.want_cov) {
+            const int cov = sf_cov_grad_slots(models[i]->has_global, models[i]->n_local);
+            if (cov == 0) {
+                sf_set_error("%s: nothing to differentiate (no global and no local kernel)", who);
+                return SF_EINVAL;
+            }
+            slots += cov;
+        }
+        if (slots > grad_stride) {
+            sf_set_error("%s: grad_stride=%d < %d slots", who, grad_stride, slots);
+            return SF_EINVAL;
+        }
+        if (slots > 0 && segs[i].B > 65535) {  // (the staging and contraction launches take one grid plane per unit)
+            sf_set_error("%s: B=%d must lie in 1 .. 65535", who, (int)segs[i].B);
+            return SF_EINVAL;
+        }
+        any |= slots > 0;
+    }
+    if (!any) {
+        sf_set_error(MULTI_GRAD ": nothing to differentiate (no segment requests a slot)");
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_multi_grad_workspace_bytes_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                                   const sf_grad_request* reqs, int grad_stride) {
+    Layout L;
+    sf_model_desc uni;
+    int U = 0, bmax = 0;
+    if (multi_layout(segs, nseg, models, &L, &U, &bmax, &uni)) return 0;
+    if (multi_grad_requests_ok(segs, nseg, models, reqs, grad_stride)) return 0;
+    return carve_multi_grad(segs, nseg, models, reqs, L, U, nullptr, 0, carve_multi(L, uni, U, bmax, nullptr, 0).bytes).bytes;
+}
+// On segment i's lane, between its transform chain and its fill: the right-hand sides into the staging area.  The residual
+// is read before the factorisation turns it into L^-1 r.
+static int multi_grad_stage(const MultiGradCall& g, int i, const sf_ctx* c, int B, const Work& w, const Layout& L, hipStream_t sp) {
+    const AppliedWork& aw = g.G.seg[i];
+    if (g.reqs[i].n_mean_slots > 0) return sf_launch_mean_stage(w.resid, aw.xs, w.info_e, c->n, L.npad, c->m, B, aw.stage, sp);
+    if (g.G.nrhs == 1) return sf_launch_apply_stage(nullptr, c->n, 0, w.resid, c->n, L.npad, 1, B, aw.stage, sp);
+    // r alone among units of 1 + m rows: the residual's n data rows into row 0, zero everywhere else
+    const size_t unit = sizeof(double) * (size_t)g.G.nrhs * L.npad;
+    SF_HIP(hipMemsetAsync(aw.stage, 0, unit * (size_t)B, sp));
+    SF_HIP(hipMemcpy2DAsync(aw.stage, unit, w.resid, sizeof(double) * (size_t)L.npad, sizeof(double) * (size_t)c->n, B,
+                            hipMemcpyDeviceToDevice, sp));
+    return SF_OK;
+}
+// On segment i's lane behind its own chain: the row tangents read the chain's transient buffers (broadened rows, multiplier
+// table, FFT scratch), which the lane's next segment overwrites; they leave per-unit data only (dcoef, kdot, mudot, zdot)
+static int multi_grad_tangents(const MultiGradCall& g, int i, sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params,
+                               const Work& w, hipStream_t sp) {
+    const sf_grad_request& r = g.reqs[i];
+    if (r.n_mean_slots <= 0) return SF_OK;
+    return sf_launch_mean_tangents(broaden_args(c, mdl, B, d_params, w), c->inv_band.as<double>(),
+                                   emu_args(c, mdl, d_params, w, w.mu, nullptr, w.Lw, w.info_e),
+                                   mean_grad_kernel_args(c, r.h_mean_slots, r.n_mean_slots, w, g.G.seg[i], nullptr, g.grad_stride), B, sp);
+}
+// Behind a chunk's factorisation and finish, on the caller's stream: alpha (and V) for the whole chunk in one launch, X = L^-1
+// if a segment of the chunk wants covariance slots, then every segment's contractions.  seg_u0[i]: segment i's first unit
+static int multi_grad_chunk(const MultiGradCall& g, const sf_segment* segs, const sf_model_desc* const* models, const Work& W,
+                            const Layout& L, const int* seg_u0, int s0, int s1, int* d_info, hipStream_t s) {
+    const int u0 = seg_u0[s0], units = seg_u0[s1 - 1] + segs[s1 - 1].B - u0;
+    const int64_t stride = (int64_t)L.npad * L.lda, sstride = (int64_t)g.G.nrhs * L.npad;
+    const Work wc = slice(W, u0);
+    double* stage = g.G.seg[s0].stage;
+    SF_CHECK(sf_launch_chol_apply(wc.C, L.npad, L.lda, stride, units, SF_APPLY_CINV, stage, g.G.nrhs, L.npad, sstride, stage, L.npad,
+                                  sstride, s));
+    bool cov = false;
+    for (int i = s0; i < s1; ++i) cov |= g.reqs[i].want_cov != 0;
+    // (the factor is applied first: the inverse's launch takes the strict upper triangle of the matrices as scratch)
+    if (cov)
+        SF_CHECK(sf_launch_chol_inverse_diag(wc.C, L.npad, L.lda, stride, units, g.G.seg[s0].winv, g.G.seg[s0].cinv_diag, L.npad, s));
+    for (int i = s0; i < s1; ++i) {
+        const sf_grad_request& r = g.reqs[i];
+        sf_ctx* c = segs[i].ctx;
+        const int B = segs[i].B;
+        AppliedWork aw = g.G.seg[i];
+        aw.info = d_info + seg_u0[i];
+        Work w = slice(W, seg_u0[i]);
+        if (aw.coef) w.coef = aw.coef;
+        double* grad = g.d_grad + (int64_t)seg_u0[i] * g.grad_stride;
+        if (r.want_cov) {
+            sf_fill_args f = fill_args(c, models[i], segs[i].d_params, w);
+            f.C = w.C, f.lda = L.lda, f.stride = stride, f.lower_only = 1, f.add_jitter = 1;
+            SF_CHECK(sf_launch_cov_grad(f, B, aw.winv, aw.stage, (int)sstride, aw.info, aw.part, grad + r.n_mean_slots, g.grad_stride, s));
+        }
+        if (r.n_mean_slots > 0)
+            SF_CHECK(sf_launch_mean_grad(eval_args(c, models[i], segs[i].d_params, w),
+                                         mean_grad_kernel_args(c, r.h_mean_slots, r.n_mean_slots, w, aw, grad, g.grad_stride), w.zs,
+                                         c->m * c->M, B, s));
+    }
+    return SF_OK;
+}
+
+// g (gradient calls): what the segments are differentiated in; its workspace lies behind the likelihood's
 static int loglike_multi(const char* who, const sf_segment* segs, int nseg, const sf_model_desc* const* models,
                          double* d_lnl, double* d_logdet, double* d_sqmah, double* d_log_scale, int* d_info,
-                         void* d_work, size_t work_bytes, void* stream) {
+                         void* d_work, size_t work_bytes, void* stream, MultiGradCall* g = nullptr) {
     Layout L;
     sf_model_desc uni;
     int U = 0, bmax = 0;
     int rc = multi_layout(segs, nseg, models, &L, &U, &bmax, &uni);
     if (rc) return rc;
-    if (!d_lnl || !d_work) {
-        sf_set_error("%s: d_lnl and a workspace are required", who);
+    if (g) SF_CHECK(multi_grad_requests_ok(segs, nseg, models, g->reqs, g->grad_stride));
+    if (!d_lnl || !d_work || (g && (!d_info || !g->d_grad))) {
+        sf_set_error(g ? "%s: d_lnl, d_info, d_grad and a workspace are required" : "%s: d_lnl and a workspace are required", who);
         return SF_EINVAL;
     }
     Work W = carve_multi(L, uni, U, bmax, d_work, work_bytes);
-    rc = work_fits(work_bytes, W.bytes);
+    if (g) g->G = carve_multi_grad(segs, nseg, models, g->reqs, L, U, d_work, work_bytes, W.bytes);
+    rc = work_fits(work_bytes, g ? g->G.bytes : W.bytes);
     if (rc) return rc;
     sf_ctx* c0 = segs[0].ctx;
     if (use_device(c0)) return SF_EHIP;
@@ -129,31 +258,38 @@ static int loglike_multi(const char* who, const sf_segment* segs, int nseg, cons
     struct Chunk {
         int u0, units;
         hipEvent_t filled[SF_MULTI_LANES];
+        int s0, s1;  // its segments [s0, s1)
     };
     std::vector<Chunk> chunks;
+    std::vector<int> seg_u0(nseg);
     bool lane_used[SF_MULTI_LANES] = {};
-    int u0 = 0, cu0 = 0;
+    int u0 = 0, cu0 = 0, cs0 = 0;
     for (int i = 0; i < nseg; ++i) {
         sf_ctx* c = segs[i].ctx;
         const int B = segs[i].B;
         const int lane = i % SF_MULTI_LANES;
         hipStream_t sp = lane_stream[lane];
         lane_used[lane] = true;
+        seg_u0[i] = u0;
         Work w = with_trans_set(slice(W, u0), lane);
+        if (g && g->G.seg[i].coef) w.coef = g->G.seg[i].coef;  // (the contraction reads them behind the factorisation)
         {
             ProfScope ps(sp, PS_TRANSFORM);
-            rc = run_transforms(c, models[i], B, segs[i].d_params, w, nullptr, nullptr, nullptr,
+            rc = run_transforms(c, models[i], B, segs[i].d_params, w, nullptr, g ? g->G.seg[i].xs : nullptr, nullptr,
                                 d_log_scale ? d_log_scale + u0 : nullptr, true, sp);
             if (rc) return rc;
         }
+        if (g) SF_CHECK(multi_grad_stage(*g, i, c, B, w, L, sp));
         {
             ProfScope ps(sp, PS_FILL);
             rc = sf_launch_fill(loglike_fill_args(c, models[i], segs[i].d_params, w, L, fp), B, sp);
             if (rc) return rc;
         }
+        if (g) SF_CHECK(multi_grad_tangents(*g, i, c, models[i], B, segs[i].d_params, w, sp));
         u0 += B;
         if ((chunks.empty() && u0 - cu0 >= first_units) || i == nseg - 1) {
-            Chunk ch{cu0, u0 - cu0, {}};
+            Chunk ch{cu0, u0 - cu0, {}, cs0, i + 1};
+            cs0 = i + 1;
             for (int l = 0; l < SF_MULTI_LANES; ++l) {
                 if (!lane_used[l]) continue;
                 rc = sf_exec_event(ex, &ch.filled[l]);
@@ -174,6 +310,7 @@ static int loglike_multi(const char* who, const sf_segment* segs, int nseg, cons
         rc = loglike_factor_finish(slice(W, ch.u0), L, fp, ch.units, W.ltbuf, d_lnl + ch.u0, d_info ? d_info + ch.u0 : nullptr, s,
                                    &c0->exec_potrf);
         if (rc) return rc;
+        if (g) SF_CHECK(multi_grad_chunk(*g, segs, models, W, L, seg_u0.data(), ch.s0, ch.s1, d_info, s));
     }
     return export_logdet_sqmah(d_logdet, d_sqmah, W, U, s);
 }
@@ -192,4 +329,23 @@ extern "C" int sf_loglike_multi_batch_md(const sf_segment* segs, int nseg, const
                                          int* d_info, void* d_work, size_t work_bytes, void* stream) {
     return loglike_multi("sf_loglike_multi_batch_md", segs, nseg, models, d_lnl, d_logdet, d_sqmah, d_log_scale,
                          d_info, d_work, work_bytes, stream);
+}
+extern "C" int sf_loglike_multi_grad_batch_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                              const sf_grad_request* reqs, double* d_lnl, double* d_log_scale, int* d_info,
+                                              double* d_grad, int grad_stride, void* d_work, size_t work_bytes, void* stream) {
+    MultiGradCall g{reqs, d_grad, grad_stride, {}};
+    return loglike_multi(MULTI_GRAD, segs, nseg, models, d_lnl, nullptr, nullptr, d_log_scale, d_info, d_work, work_bytes, stream, &g);
+}
+extern "C" int sf_multi_grad_reduce(int nseg, int W, const double* d_unit_lnl, const int* d_unit_info, const double* d_unit_grad,
+                                    int grad_stride, const int32_t* d_col_ptr, const int32_t* d_col_src, int ncols, double* d_lnl,
+                                    double* d_grad, int out_stride, int* d_info, void* stream) {
+    if (!d_unit_lnl || !d_unit_info || !d_unit_grad || !d_col_ptr || !d_lnl || !d_grad || !d_info || (!d_col_src && ncols > 0)) {
+        sf_set_error("sf_multi_grad_reduce: the unit results, the column map and the outputs are required");
+        return SF_EINVAL;
+    }
+    sf_multi_reduce_args a;
+    a.unit_lnl = d_unit_lnl, a.unit_info = d_unit_info, a.unit_grad = d_unit_grad, a.col_ptr = d_col_ptr, a.col_src = d_col_src;
+    a.nseg = nseg, a.W = W, a.grad_stride = grad_stride, a.ncols = ncols, a.out_stride = out_stride;
+    a.lnl = d_lnl, a.grad = d_grad, a.info = d_info;
+    return sf_launch_multi_grad_reduce(a, (hipStream_t)stream);
 }

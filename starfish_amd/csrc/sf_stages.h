@@ -29,4 +29,11 @@ int loglike_factor_finish(const Work& w, const Layout& L, int fp, int units, dou
 // optional results of `units` units, copied out of the workspace behind everything enqueued on s
 int export_info(int* d_info, const Work& w, int units, hipStream_t s);
 int export_logdet_sqmah(double* d_logdet, double* d_sqmah, const Work& w, int units, hipStream_t s);
+// The mean gradient's own checks of one request (behind model_ok): a model it differentiates, 1 .. SF_MEAN_GRAD_MAX_SLOTS columns
+// that are mean-flux parameters of it, none twice, and rows that hold them.  who: how the message starts
+int mean_slots_ok(const char* who, const sf_ctx* c, const sf_model_desc* mdl, const int* h_slots, int nslots, int grad_stride);
+// the arguments of the mean gradient's launches: the staging area, moments, partial sums and tangents of aw on the workspace w
+// (rows of w.L.npad doubles), nslots columns into d_grad
+sf_mean_grad_args mean_grad_kernel_args(const sf_ctx* c, const int* h_slots, int nslots, const Work& w, const AppliedWork& aw,
+                                        double* d_grad, int grad_stride);
 #pragma GCC visibility pop

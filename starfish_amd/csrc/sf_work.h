@@ -3,6 +3,7 @@
 // call is carved by one function too: it starts its Carve at the Work's size.)
 #pragma once
 #include <type_traits>
+#include <vector>
 
 #include "sf_band_shape.h"
 #include "sf_ctx.h"
@@ -172,6 +173,7 @@ struct AppliedWork {
     double *stage, *lnl;
     int* info;
     double *yv, *cov_diag, *cinv_diag, *winv, *part, *xs, *fin, *mpart, *dcoef, *kdot, *mudot, *zdot;
+    double* coef;  // (carve_multi_grad only) the segment's own spline coefficients, which a single-order call keeps in its Work
     size_t bytes;
 };
 static AppliedWork carve_applied(const sf_ctx* c, const sf_model_desc* mdl, int B, int nrhs, unsigned parts, void* p, size_t cap,
@@ -200,6 +202,69 @@ static AppliedWork carve_applied(const sf_ctx* c, const sf_model_desc* mdl, int 
     }
     w.bytes = sf_align_up(k.off, 256);
     return w;
+}
+
+// ------------------------------------------------------------------- multi-order gradient
+// (sf_loglike_multi_grad_batch_md; behind the Work of the same call: base_bytes = its size)  Rows are laid out with the
+// group's common npad (L.npad), not an order's own.  For all U units: the staging area, nrhs right-hand sides of npad doubles
+// per unit -- nrhs = 1 + m if any segment asks for mean slots, else 1 -- so that one launch applies the factor to a whole
+// chunk; then, if any segment asks for covariance slots, cinv_diag (npad per unit) and winv (the inverse's scratch, per unit).
+// Then per segment, in segment order, the per-unit data of the parts it asks for, as carve_applied lays them out for a
+// single-order call (AW_MEAN with the order's own n: xs, fin, mpart, dcoef, kdot, mudot, zdot; AW_PART: part) and, for a
+// segment with mean slots and vsini, coef: the walkers' spline coefficients (in a multi-order call the Work's are one set per
+// lane, which the lane's next segment overwrites before the contraction reads them).  seg[i].stage / cinv_diag / winv point at
+// the segment's units in the shared arrays.
+struct MultiGradWork {
+    int nrhs;
+    bool any_cov;
+    double *stage, *cinv_diag, *winv;
+    std::vector<AppliedWork> seg;
+    size_t bytes;
+};
+static MultiGradWork carve_multi_grad(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                      const sf_grad_request* reqs, const Layout& L, int U, void* p, size_t cap, size_t base_bytes) {
+    Carve k(p, cap, base_bytes);
+    MultiGradWork g{};
+    bool any_mean = false;
+    for (int i = 0; i < nseg; ++i) any_mean |= reqs[i].n_mean_slots > 0, g.any_cov |= reqs[i].want_cov != 0;
+    g.nrhs = any_mean ? 1 + L.m : 1;
+    const size_t npad = (size_t)L.npad, winv1 = sf_chol_inverse_work_doubles(L.npad, 1);
+    g.stage = k.take<double>((size_t)U * g.nrhs * npad);
+    if (g.any_cov) {
+        g.cinv_diag = k.take<double>((size_t)U * npad);
+        g.winv = k.take<double>((size_t)U * winv1);
+    }
+    g.seg.assign(nseg, AppliedWork{});
+    size_t u0 = 0;
+    for (int i = 0; i < nseg; ++i) {
+        const sf_ctx* c = segs[i].ctx;
+        const sf_model_desc* mdl = models[i];
+        const size_t B = (size_t)segs[i].B;
+        const int nslots = reqs[i].n_mean_slots;
+        AppliedWork& w = g.seg[i];
+        w.stage = g.stage ? g.stage + u0 * g.nrhs * npad : nullptr;
+        if (g.any_cov) {
+            w.cinv_diag = g.cinv_diag ? g.cinv_diag + u0 * npad : nullptr;
+            w.winv = g.winv ? g.winv + u0 * winv1 : nullptr;
+        }
+        if (nslots > 0) {
+            w.xs = k.take<double>(B * c->m * c->n);
+            w.fin = k.take<double>(B * sf_mean_fin_doubles(c->m));
+            w.mpart = k.take<double>(sf_mean_grad_part_doubles(c->n, nslots, (int)B));
+            if (mdl->has_vsini) {
+                w.dcoef = k.take<double>(B * c->nf * c->rows);
+                w.coef = k.take<double>(B * c->nf * c->rows);
+            }
+            const size_t ng = (size_t)(nslots < c->P ? nslots : c->P), mM = (size_t)c->m * c->M;
+            w.kdot = k.take<double>(ng * B * mM);
+            w.mudot = k.take<double>(ng * B * c->m);
+            w.zdot = k.take<double>(ng * B * mM * c->m);
+        }
+        if (reqs[i].want_cov) w.part = k.take<double>(sf_cov_grad_work_doubles(c->n, mdl->has_global, mdl->n_local, (int)B));
+        u0 += B;
+    }
+    g.bytes = sf_align_up(k.off, 256);
+    return g;
 }
 
 // ------------------------------------------------------------------- context-free workspaces

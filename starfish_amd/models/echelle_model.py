@@ -326,3 +326,138 @@ class EchelleModel:
         if return_orders:
             out += (per_order,)
         return out if len(out) > 1 else lnl
+
+    # ------------------------------------------------------------------ likelihood gradient of all orders in one pass
+    def _gradient_layout(self):
+        """Host logic of the gradient, no device: ``(labels, cols, requests, sources)``.  ``cols[i]``: the columns of a
+        parameter vector that hold order i's own labels; ``requests[i] = (mean_columns, want_cov)``: what order i asks the
+        device for (:class:`starfish_amd._device.MultiGradPlan`); ``sources[j]``: the ``(order, slot)`` pairs of the
+        per-unit gradient rows that label j adds up, ascending in the order -- a unit's row holds its order's mean slots in
+        :attr:`SpectrumModel.mean_gradient_labels` order, then all covariance slots of its descriptor.  A shared label has a
+        source in every order, an ``order{i}:`` label one, ``Rv`` none.  Raises ``ValueError``, naming the order, for what
+        the device does not differentiate."""
+        from .. import _device as D
+
+        if self.per_order is None:
+            labels = tuple(self.orders[0].labels)
+            cols = [np.arange(len(labels), dtype=np.intp)] * len(self.orders)
+        else:
+            labels, cols = self._layout()
+        if not labels:
+            raise ValueError("no thawed parameter to differentiate in")
+        requests, sources = [], [[] for _ in labels]
+        for i, m in enumerate(self.orders):
+            if m.solver != "dense":
+                raise ValueError(f"order {i}: the gradient runs on the dense solver only, not solver={m.solver!r}")
+            md = m._model_desc(None)
+            own, mean, cov = list(m.labels), m.mean_gradient_labels, m.gradient_labels
+            try:
+                columns = m._mean_gradient_columns(None, md) if mean else []
+            except ValueError as e:
+                raise ValueError(f"order {i}: {e}") from None
+            if len(columns) > D.MEAN_GRAD_MAX_SLOTS:
+                raise ValueError(f"order {i}: {len(columns)} thawed mean-flux parameters, the device differentiates in at most "
+                                 f"{D.MEAN_GRAD_MAX_SLOTS} per order")
+            requests.append((columns, bool(cov)))
+            for k, key in enumerate(mean):
+                sources[cols[i][own.index(key)]].append((i, k))
+            for key, slot in zip(cov, m._gradient_slots(md)):
+                sources[cols[i][own.index(key)]].append((i, len(columns) + slot))
+        return labels, cols, requests, sources
+
+    def log_likelihood_gradient_batch(self, P, return_info=False, return_orders=False):
+        """``(lnL (B,), grad (B, len(labels)))`` for B parameter vectors (rows of ``P`` in :attr:`labels` order), no priors:
+        the sum of the per-order likelihoods and its analytic gradient in every thawed label, from ONE factorisation per
+        (order x walker) unit and one enqueue per device (``sf_loglike_multi_grad_batch_md``).  A shared label receives the
+        sum over the orders that have it, an ``order{i}:`` label order i's column, a thawed ``Rv`` a zero column.  The sum over
+        the orders runs in ascending order index -- on the device (``sf_multi_grad_reduce``) when all orders share one
+        call, on the host by the same rule when they live on several devices.  Walkers that fail in any order get
+        ``-inf`` and a NaN row; ``info`` is the first non-zero per-order code.  With ``return_orders`` the (n_orders, B)
+        per-order likelihoods are returned too.  The model's own state is not modified."""
+        from .. import _device as D
+
+        labels, cols, requests, sources = self._gradient_layout()
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        if P.shape[1] != len(labels):
+            raise ValueError("Param Vector does not match length of thawed parameters")
+        B = P.shape[0]
+        packed = [m._pack(P[:, cols[i]], update_caches=False) for i, m in enumerate(self.orders)]
+        groups = {}
+        for idx, (dev, md, rows) in enumerate(packed):
+            groups.setdefault((str(dev.dev), dev.m, dev.P), []).append(idx)
+        pending = []
+        for idxs in groups.values():  # enqueue everything first, synchronise afterwards
+            if not any(requests[i][0] or requests[i][1] for i in idxs):  # nothing thawed in these orders: lnl only
+                pending.append((idxs, D.loglike_multi([packed[i][0] for i in idxs], [packed[i][1] for i in idxs],
+                                                      [packed[i][2] for i in idxs], sync=False)))
+                continue
+            pending.append((idxs, D.loglike_multi_grad([packed[i][0] for i in idxs], [packed[i][1] for i in idxs],
+                                                       [packed[i][2] for i in idxs], [requests[i] for i in idxs], sync=False)))
+        unit_lnl = np.full((len(self.orders), B), -np.inf)
+        unit_info = np.zeros((len(self.orders), B), dtype=np.int32)
+        unit_grad = [np.zeros((B, 0))] * len(self.orders)
+        for idxs, plan in pending:
+            for i, out in zip(idxs, plan.collect()):
+                unit_lnl[i], unit_info[i] = out["lnl"], out["info"]
+                unit_grad[i] = out.get("grad", unit_grad[i])
+        if len(pending) == 1 and isinstance(pending[0][1], D.MultiGradPlan):
+            lnl, grad, info = pending[0][1].reduce(sources)
+        else:
+            lnl, grad, info = D.reduce_orders_host(unit_lnl, unit_info, unit_grad, sources)
+        self.last_info = info
+        out = (lnl, grad)
+        if return_info:
+            out += (info,)
+        if return_orders:
+            out += (np.where(unit_info == 0, unit_lnl, -np.inf),)
+        return out
+
+    def log_likelihood_gradient(self):
+        """``(lnL, {label: d lnL / d label})`` of the current state, no priors.  Raises as
+        :meth:`SpectrumModel.log_likelihood` does for a point the device flags; the model's state is not modified."""
+        lnl, grad, info = self.log_likelihood_gradient_batch(self.get_param_vector()[None, :], return_info=True)
+        SpectrumModel._raise_for_info(info[0])
+        return float(lnl[0]), dict(zip(self.labels, (float(v) for v in grad[0])))
+
+    def train(self, priors=None, **kwargs):
+        """MAP estimate over :attr:`labels`: ``scipy.optimize.minimize(method="L-BFGS-B", jac=True)`` on the analytic gradient
+        of :meth:`log_likelihood_gradient_batch` -- a per-order fit has a few hundred parameters, which a simplex search
+        cannot handle.  ``priors`` are looked up as :meth:`log_likelihood` does (a bare per-order key counts once per order);
+        a prior on an optimised label adds its ``logpdf`` and the slope of it by a central difference with step
+        ``eps^(1/3) max(1, |x|)``, priors on other parameters a constant.  A point the device flags raises as
+        :meth:`SpectrumModel.log_likelihood` does.  ``kwargs`` go to ``minimize``.  Every evaluation leaves the model at its
+        point; a run that succeeds or stops at its iteration limit leaves it at ``soln.x``."""
+        from scipy.optimize import minimize
+
+        labels, cols, _requests, _sources = self._gradient_layout()  # (refusals before any device work)
+        for key, prior in (priors or {}).items():
+            if not callable(getattr(prior, "logpdf", None)):
+                raise ValueError(f"Invalid priors. {key} does not have a `logpdf` method")
+        terms = self._prior_terms(priors)
+        h0 = np.finfo(np.float64).eps ** (1.0 / 3.0)
+
+        def objective(x):
+            if np.any(~np.isfinite(x)):
+                raise ValueError("EchelleModel.train: the optimiser asked for a point that is not finite")
+            self.set_param_vector(x)
+            lnl, grad, info = self.log_likelihood_gradient_batch(x[None, :], return_info=True)
+            SpectrumModel._raise_for_info(info[0])
+            value, slope = float(lnl[0]), grad[0].copy()
+            for prior, i, key in terms:
+                own = self.orders[i].labels
+                if key not in own:
+                    value += prior.logpdf(self.orders[i][key])
+                    continue
+                j = cols[i][own.index(key)]
+                h = h0 * max(1.0, abs(x[j]))
+                value += prior.logpdf(x[j])
+                slope[j] += (prior.logpdf(x[j] + h) - prior.logpdf(x[j] - h)) / (2 * h)
+            return -value, -slope
+
+        opts = {"method": "L-BFGS-B"}
+        opts.update(kwargs)
+        opts["jac"] = True
+        soln = minimize(objective, self.get_param_vector().astype(np.float64), **opts)
+        if soln.success or soln.status == 1:  # (1: the iteration / evaluation limit; soln.x is the best point so far)
+            self.set_param_vector(soln.x)
+        return soln

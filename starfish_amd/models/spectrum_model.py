@@ -319,17 +319,20 @@ class SpectrumModel:
 
     # ------------------------------------------------------------------ packing for the C-ABI
     def _model_desc(self, dev):
+        """The C-ABI descriptor of the model's parameter rows.  ``dev`` None: built on the host, without a device."""
         n_local = len(self._local_kernels()) if "local_cov" in self.params else 0
         n_cheb = len(self.params["cheb"]) if "cheb" in self.params else 0
-        return dev.model_desc(
+        make = dev.model_desc if dev is not None else (lambda *a, **k: D.DeviceOrder.model_desc(None, *a, **k))
+        return make(
             "vsini" in self.params, "vz" in self.params, "log_scale" in self.params,
             "global_cov" in self.params, n_local, n_cheb, use_sigma_w=self.emulator_cov == "paper",
             has_av="Av" in self.params,
         )
 
     def _slot_of(self, dev, md):
-        """flat parameter key -> column of the C-ABI parameter row (None: not used on the device)."""
-        P = dev.P
+        """flat parameter key -> column of the C-ABI parameter row (None: not used on the device).  ``dev`` None: the grid
+        dimensions are the emulator's."""
+        P = dev.P if dev is not None else len(self.emulator.param_names)
         slots = {"vsini": 0, "vz": 1, "log_scale": 2, "global_cov:log_amp": 4, "global_cov:log_ls": 5}
         for i, key in enumerate(self.emulator.param_names):
             slots[key] = 6 + i
@@ -756,14 +759,29 @@ class SpectrumModel:
         lnl = np.where(out["info"] == 0, out["lnl"], -np.inf)
         return (lnl, out["grad"], out["info"]) if return_info else (lnl, out["grad"])
 
-    def log_likelihood_full_gradient_batch(self, P, return_info=False):
+    def log_likelihood_full_gradient_batch(self, P, return_info=False, one_pass=False):
         """``(lnL (B,), grad (B, len(labels)))``: the gradient in every thawed label, columns in :attr:`labels` order -- the mean
         call's columns and, where covariance labels are thawed, :meth:`log_likelihood_gradient_batch`'s (two device calls).  A
-        thawed ``Rv`` gets a zero column: it is never passed on."""
+        thawed ``Rv`` gets a zero column: it is never passed on.
+
+        ``one_pass=True``: both parts from ONE factorisation per walker (sf_loglike_multi_grad_batch_md with one segment)
+        instead of one per call; the values agree with the default's to rounding, not bit for bit."""
         P = np.atleast_2d(np.asarray(P, dtype=np.float64))
         labels = self.labels
         grad = np.zeros((P.shape[0], len(labels)))
         lnl = info = None
+        if one_pass:
+            mean, cov = self.mean_gradient_labels, self.gradient_labels
+            if not mean and not cov:
+                raise ValueError("no thawed parameter to differentiate in")
+            dev, md, rows = self._pack(P, update_caches=False)
+            columns = self._mean_gradient_columns(dev, md) if mean else []
+            out = D.loglike_multi_grad([dev], [md], [rows], [(columns, bool(cov))])[0]
+            grad[:, [labels.index(key) for key in mean]] = out["grad"][:, :len(columns)]
+            if cov:
+                grad[:, [labels.index(key) for key in cov]] = out["grad"][:, [len(columns) + s for s in self._gradient_slots(md)]]
+            lnl, info = np.where(out["info"] == 0, out["lnl"], -np.inf), out["info"]
+            return (lnl, grad, info) if return_info else (lnl, grad)
         if self.mean_gradient_labels:
             lnl, g, info = self.log_likelihood_mean_gradient_batch(P, return_info=True)
             grad[:, [labels.index(key) for key in self.mean_gradient_labels]] = g
