@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import _rows as R
 
 INFO_MESSAGES = {
     -1: "Querying emulator outside of original parameter range.",
@@ -182,7 +183,7 @@ def band_halfwidth_bound(wave, rows, n_grid, has_global, n_local, n_cheb):
     """Per-walker upper bound on max|i-j| over the non-zero entries of the structured part of the
     covariance (global Matern taper r0 = 6 ls, Starfish/models/kernels.py:29; local patches r0 = 4 sigma,
     kernels.py:73), from host copies of the wavelength grid and of the C-ABI parameter rows
-    (include/starfish_amd.h: [4] log_amp, [5] log_ls, locals after the grid and Chebyshev entries).
+    (layout: :mod:`starfish_amd._rows`).
     Conservative: uses the smallest pixel spacing.  Pure host logic (numpy)."""
     w = np.asarray(wave, dtype=np.float64)
     rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
@@ -194,12 +195,12 @@ def band_halfwidth_bound(wave, rows, n_grid, has_global, n_local, n_cheb):
         # metric of the global kernel (kernels.py:27): r = c/2 |wi - wj| / (wi + wj), a quarter of the
         # velocity separation; r(i, i+d) >= d * dv * (1 - O(r0/c)) (slightly sub-additive)
         dv = float(np.min(C_KMS / 2 * (w[1:] - w[:-1]) / (w[1:] + w[:-1])))
-        r0 = 6 * np.exp(rows[:, 5])
+        r0 = 6 * np.exp(rows[:, R.GLOBAL_LOG_LS])
         hw = np.maximum(hw, np.floor(r0 / dv * (1 + 4 * r0 / C_KMS + 1e-9)) + 1)
-    off = 6 + n_grid + n_cheb
+    lay = R.RowLayout(n_grid, R.model_desc(0, 0, 0, has_global, n_local, n_cheb))
     for k in range(n_local):
-        mu = rows[:, off + 3 * k]
-        r0 = 4 * np.exp(rows[:, off + 3 * k + 2])
+        mu, _log_amp, log_sigma = rows[:, lay.local_of(k)].T
+        r0 = 4 * np.exp(log_sigma)
         # metric d_i = c/mu |w_i - mu| (kernels.py:69): patch = pixels with d_i <= r0; its extent in
         # pixels is at most 2 r0 / (smallest step of d), step of d >= (c/mu) * min(diff(w))
         step = C_KMS / np.abs(mu) * float(np.min(np.diff(w)))
@@ -370,8 +371,7 @@ class MultiGradPlan(MultiPlan):
         if len(requests) != len(orders):
             raise ValueError(f"multi-order gradient: {len(requests)} requests for {len(orders)} orders")
         self.requests = [([int(c) for c in cols], bool(cov)) for cols, cov in requests]
-        self.slots = [len(cols) + (((2 if md.has_global else 0) + 3 * int(md.n_local)) if cov else 0)
-                      for (cols, cov), md in zip(self.requests, mds)]
+        self.slots = [len(cols) + (R.cov_grad_slots(md) if cov else 0) for (cols, cov), md in zip(self.requests, mds)]
         if not any(self.slots):
             raise ValueError("multi-order gradient: nothing to differentiate (no order requests a slot)")
         self.stride = max(self.slots)
@@ -579,14 +579,8 @@ class DeviceOrder:
             pass
 
     # ------------------------------------------------------------------ helpers
-    def model_desc(self, has_vsini, has_vz, has_log_scale, has_global, n_local, n_cheb, use_sigma_w=False,
-                   has_av=False):
-        md = _lib.ModelDesc()
-        md.has_vsini, md.has_vz = int(has_vsini), int(has_vz)
-        md.has_log_scale, md.has_global = int(has_log_scale), int(has_global)
-        md.n_local, md.n_cheb, md.use_sigma_w = int(n_local), int(n_cheb), int(use_sigma_w)
-        md.has_av = int(has_av)
-        return md
+    def model_desc(self, *args, **kwargs):
+        return R.model_desc(*args, **kwargs)
 
     def param_stride(self, md):
         stride = self.lib.sf_param_stride(self.ctx, C.byref(md))
@@ -851,13 +845,10 @@ class DeviceOrder:
         return self._run_applied("pointwise_batch", md, params, rhs, outputs, want_flux, max_chunk,
                                  self.pointwise_workspace_bytes)
 
-    def loglike_grad(self, md, params, want_flux=False, max_chunk=None):
-        """The likelihood and its gradient in the covariance hyper-parameters (sf_loglike_grad_batch).  params: (B, stride)
-        rows as for :meth:`loglike`.  Returns dict of numpy arrays: lnl (B,) and info (B,) with :meth:`loglike`'s bits, grad
-        (B, slots) with the slots in parameter-row order (log_amp, log_ls of the global kernel if the model has one, then mu,
-        log_amp, log_sigma per local kernel), NaN rows where info != 0, and, asked for, flux (B, n).  Chunked and retried
-        like :meth:`apply`."""
-        slots = (2 if md.has_global else 0) + 3 * int(md.n_local)
+    def _run_grad(self, name, md, params, lead, slots, workspace_bytes, want_flux, max_chunk):
+        """:meth:`_run_chunked` for ``sf_<name>(ctx, &md, B, P, *lead, lnl, grad, grad_stride, flux, info, ws, ...)``: the two
+        likelihood-and-gradient calls.  ``lead``: the host arguments in front; ``slots``: the gradient columns wanted (the
+        buffer has at least one); ``workspace_bytes(units)``: the call's size query."""
         stride = max(slots, 1)
         with _torch().cuda.device(self.dev):
             P = self._rows(params)
@@ -865,15 +856,23 @@ class DeviceOrder:
 
             def args(bufs, lo, hi):
                 (lnl, grad), info, flux = bufs
-                return lnl[lo:hi], grad[lo:hi], stride, flux[lo:hi] if want_flux else None, info[lo:hi]
+                return (*lead, lnl[lo:hi], grad[lo:hi], stride, flux[lo:hi] if want_flux else None, info[lo:hi])
 
             def sliced(bufs):
                 res = download(bufs)
                 res["grad"] = res["grad"][:, :slots]
                 return res
 
-            return self._run_chunked("loglike_grad_batch", md, P, max_chunk,
-                                     lambda units: self.loglike_grad_workspace_bytes(md, units), buffers, args, sliced)
+            return self._run_chunked(name, md, P, max_chunk, workspace_bytes, buffers, args, sliced)
+
+    def loglike_grad(self, md, params, want_flux=False, max_chunk=None):
+        """The likelihood and its gradient in the covariance hyper-parameters (sf_loglike_grad_batch).  params: (B, stride)
+        rows as for :meth:`loglike`.  Returns dict of numpy arrays: lnl (B,) and info (B,) with :meth:`loglike`'s bits, grad
+        (B, slots) with the slots in parameter-row order (log_amp, log_ls of the global kernel if the model has one, then mu,
+        log_amp, log_sigma per local kernel), NaN rows where info != 0, and, asked for, flux (B, n).  Chunked and retried
+        like :meth:`apply`."""
+        return self._run_grad("loglike_grad_batch", md, params, (), R.cov_grad_slots(md),
+                              lambda units: self.loglike_grad_workspace_bytes(md, units), want_flux, max_chunk)
 
     def loglike_mean_grad_workspace_bytes(self, md, B, nslots):
         return self._size_query("loglike_mean_grad_", md, B, nslots)
@@ -887,22 +886,8 @@ class DeviceOrder:
         slots = [int(v) for v in slots]
         nslots = len(slots)
         h_slots = (C.c_int * max(nslots, 1))(*slots)
-        with _torch().cuda.device(self.dev):
-            P = self._rows(params)
-            buffers, download = self._outputs(int(P.shape[0]), {"lnl": (), "grad": (max(nslots, 1),)}, want_flux)
-
-            def args(bufs, lo, hi):
-                (lnl, grad), info, flux = bufs
-                return h_slots, nslots, lnl[lo:hi], grad[lo:hi], max(nslots, 1), flux[lo:hi] if want_flux else None, info[lo:hi]
-
-            def sliced(bufs):
-                res = download(bufs)
-                res["grad"] = res["grad"][:, :nslots]
-                return res
-
-            return self._run_chunked("loglike_mean_grad_batch", md, P, max_chunk,
-                                     lambda units: self.loglike_mean_grad_workspace_bytes(md, units, nslots), buffers, args,
-                                     sliced)
+        return self._run_grad("loglike_mean_grad_batch", md, params, (h_slots, nslots), nslots,
+                              lambda units: self.loglike_mean_grad_workspace_bytes(md, units, nslots), want_flux, max_chunk)
 
     def loglike_device(self, md, P_dev, out_lnl, info=None):
         """Enqueue-only variant for bench.py: device tensors in/out, no synchronisation."""
@@ -972,8 +957,8 @@ class DeviceOrder:
         gp = np.atleast_2d(np.asarray(grid_params, dtype=np.float64))
         md = self.model_desc(0, 0, 1, 0, 0, 0)
         rows = np.zeros((gp.shape[0], self.param_stride(md)))
-        rows[:, 3] = 1.0
-        rows[:, 6 : 6 + self.P] = gp
+        rows[:, R.NORM] = 1.0
+        rows[:, R.RowLayout(self.P, md).grid] = gp
         return md, rows
 
     def emulator_query(self, grid_params):

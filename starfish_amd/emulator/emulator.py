@@ -622,7 +622,7 @@ class Emulator:
         if gradient:
             if batch_simplex:
                 raise ValueError("Emulator.train: gradient=True and batch_simplex=True exclude each other")
-            return self._finish_training(self._train_gradient(minimize, opt_kwargs))
+            return self._finish_training(self._train_gradient(opt_kwargs))
 
         def nll(P):
             if np.any(~np.isfinite(P)):
@@ -649,22 +649,19 @@ class Emulator:
                 self.set_param_vector(soln.last_x)  # where the reference's last objective call left the emulator
         return self._finish_training(soln)
 
-    def _train_gradient(self, minimize, opt_kwargs):
-        """The ``gradient=True`` search of :meth:`train`: every evaluation leaves the emulator at its point, as the serial
-        objective does."""
-        def objective(x):
-            if np.any(~np.isfinite(x)):
-                raise ValueError("Emulator.train: the optimiser asked for a point that is not finite")
+    def _train_gradient(self, opt_kwargs):
+        """The ``gradient=True`` search of :meth:`train` (no priors): every evaluation leaves the emulator at its point, as
+        the serial objective does."""
+        from .._map import minimize_lbfgsb
+
+        def evaluate(x):
             self.set_param_vector(x)
             lnl, grad, info = self.log_likelihood_gradient_batch(x[None, :], return_info=True)
             self._raise_for_info(int(info[0]))
-            return -float(lnl[0]), -np.asarray(grad[0], dtype=np.float64)
+            return lnl[0], grad[0]
 
-        kwargs = {"method": "L-BFGS-B"}
-        kwargs.update(opt_kwargs)
-        kwargs["jac"] = True
-        kwargs["bounds"] = self._lengthscale_bounds(kwargs.get("bounds"))
-        return minimize(objective, self.get_param_vector(), **kwargs)
+        kwargs = dict(opt_kwargs, bounds=self._lengthscale_bounds(opt_kwargs.get("bounds")))
+        return minimize_lbfgsb(evaluate, self.get_param_vector(), [], None, kwargs, finite_for="Emulator.train")
 
     def _finish_training(self, soln):
         if not soln.success:

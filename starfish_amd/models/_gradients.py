@@ -1,0 +1,169 @@
+"""The analytic likelihood gradients of :class:`SpectrumModel` -- in the covariance hyper-parameters, in the mean-flux
+parameters, in every thawed label -- and the two L-BFGS-B searches on them (:mod:`starfish_amd._map`)."""
+import numpy as np
+
+from .. import _device as D
+from .. import _map
+from .. import _rows as R
+
+
+class Gradients:
+    # ------------------------------------------------------------------ gradient in the covariance hyper-parameters
+    @property
+    def gradient_labels(self):
+        """tuple of str : the thawed labels under ``global_cov:`` / ``local_cov:``, in :attr:`labels` order: the parameters
+        :meth:`log_likelihood_gradient` differentiates in."""
+        return tuple(key for key in self.labels if key.startswith(("global_cov:", "local_cov:")))
+
+    def _gradient_slots(self, md):
+        """For every label of :attr:`gradient_labels`, its slot in the device's gradient row
+        (:func:`starfish_amd._rows.cov_grad_slot`)."""
+        return [R.cov_grad_slot(md, key) for key in self.gradient_labels]
+
+    def log_likelihood_gradient(self):
+        """``(lnL, {label: d lnL / d label})`` of the current state for the labels of :attr:`gradient_labels`: the analytic
+        gradient of :meth:`log_likelihood` (no priors) in the covariance hyper-parameters, from one factorisation
+        (Rasmussen & Williams, GPML, eq. 5.9).  In ``mu`` of a local kernel it is the almost-everywhere derivative: the
+        likelihood has a kink wherever two pixels of the patch are equidistant from ``mu``.  Raises as
+        :meth:`log_likelihood` does; the model's state is not modified."""
+        labels = self.gradient_labels
+        if not labels:
+            raise ValueError("no thawed global_cov / local_cov parameter to differentiate in")
+        dev, md, rows = self._pack(update_caches=False)
+        out = self._own(dev.loglike_grad(md, rows))
+        return float(out["lnl"]), dict(zip(labels, (float(v) for v in out["grad"][self._gradient_slots(md)])))
+
+    def log_likelihood_gradient_batch(self, P, return_info=False):
+        """:meth:`log_likelihood_gradient` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device pass:
+        ``(lnL (B,), grad (B, len(gradient_labels)))``.  Walkers that fail get ``-inf`` and a NaN row, ``info`` their codes.
+        The model's own state is not modified."""
+        if not self.gradient_labels:
+            raise ValueError("no thawed global_cov / local_cov parameter to differentiate in")
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        dev, md, rows = self._pack(P, update_caches=False)
+        out = dev.loglike_grad(md, rows)
+        lnl = np.where(out["info"] == 0, out["lnl"], -np.inf)
+        grad = out["grad"][:, self._gradient_slots(md)]
+        return (lnl, grad, out["info"]) if return_info else (lnl, grad)
+
+    def _prior_split(self, priors, labels):
+        """``(sampled, const_lp)`` of :func:`starfish_amd._map.minimize_lbfgsb` for the optimised ``labels``: a prior on
+        one of them with its position, in ``labels`` order; priors on other parameters a constant."""
+        const_lp = sum(prior.logpdf(self[key]) for key, prior in priors.items() if key in self.params and key not in labels)
+        return [(i, priors[key]) for i, key in enumerate(labels) if key in priors], const_lp
+
+    def train_covariance(self, priors=None, **kwargs):
+        """MAP estimate of the covariance hyper-parameters alone: ``scipy.optimize.minimize(method="L-BFGS-B", jac=True)``
+        over :attr:`gradient_labels` with the analytic gradient of :meth:`log_likelihood_gradient_batch`; every other
+        parameter keeps its value.  ``priors`` are checked as :meth:`train` checks them; a prior on an optimised label adds
+        its ``logpdf`` and the slope of it by a central difference with step ``eps^(1/3) max(1, |x|)`` (scipy's frozen
+        distributions expose no derivative), priors on other parameters a constant.  ``kwargs`` go to ``minimize``.  On
+        success the model is left at ``soln.x``."""
+        priors = self._checked_priors(priors)
+        glabels = self.gradient_labels
+        if not glabels:
+            raise ValueError("no thawed global_cov / local_cov parameter to optimise")
+        labels = self.labels
+        cols = [labels.index(key) for key in glabels]
+        x_all = self.get_param_vector().astype(np.float64)
+
+        def evaluate(x):  # (the model's state is not touched: x goes into a copy of the full vector)
+            row = x_all.copy()
+            row[cols] = x
+            lnl, grad, info = self.log_likelihood_gradient_batch(row[None, :], return_info=True)
+            self._raise_for_info(info[0])
+            return lnl[0], grad[0]
+
+        soln = _map.minimize_lbfgsb(evaluate, x_all[cols], *self._prior_split(priors, glabels), kwargs, force_jac=False)
+        if soln.success:
+            self.set_param_dict(dict(zip(glabels, soln.x)))
+        return soln
+
+    # ------------------------------------------------------------------ gradient in the mean-flux parameters
+    @property
+    def mean_gradient_labels(self):
+        """tuple of str : the thawed labels that are not under ``global_cov:`` / ``local_cov:``, in :attr:`labels` order: the
+        parameters :meth:`log_likelihood_mean_gradient` differentiates in.  ``Rv`` is left out: it is never passed on."""
+        return tuple(key for key in self.labels if not key.startswith(("global_cov:", "local_cov:")) and key != "Rv")
+
+    def _mean_gradient_columns(self, dev, md):
+        """For every label of :attr:`mean_gradient_labels`, its column of the C-ABI parameter row; raises ``ValueError`` for a
+        model the device does not differentiate."""
+        labels = self.mean_gradient_labels
+        if not labels:
+            raise ValueError("no thawed mean-flux parameter to differentiate in")
+        if "log_scale" not in self.params:
+            raise ValueError("the mean gradient needs log_scale: the renormalising scale is not differentiated")
+        if self.emulator_cov == "paper":
+            raise ValueError('the mean gradient covers emulator_cov="code" only, not the form of the paper (emulator_cov="paper")')
+        if self.norm and any(key in self.emulator.param_names for key in labels):
+            raise ValueError("norm=True with a thawed grid parameter: the derivative of the host's norm-factor interpolant is "
+                             "not built; freeze the grid parameters")
+        slots = self._slot_of(dev, md)
+        return [slots[key] for key in labels]
+
+    def log_likelihood_mean_gradient(self):
+        """``(lnL, {label: d lnL / d label})`` of the current state for the labels of :attr:`mean_gradient_labels`: the analytic
+        gradient of :meth:`log_likelihood` (no priors) in vsini, vz, log_scale, Av, the Chebyshev coefficients and the grid
+        parameters, from the likelihood's factorisation and one solve with 1 + m right-hand sides.  Raises as
+        :meth:`log_likelihood` does; the model's state is not modified."""
+        dev, md, rows = self._pack(update_caches=False)
+        out = self._own(dev.loglike_mean_grad(md, rows, self._mean_gradient_columns(dev, md)))
+        return float(out["lnl"]), dict(zip(self.mean_gradient_labels, (float(v) for v in out["grad"])))
+
+    def log_likelihood_mean_gradient_batch(self, P, return_info=False):
+        """:meth:`log_likelihood_mean_gradient` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device
+        pass: ``(lnL (B,), grad (B, len(mean_gradient_labels)))``.  Walkers that fail get ``-inf`` and a NaN row, ``info`` their
+        codes.  The model's own state is not modified."""
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        dev, md, rows = self._pack(P, update_caches=False)
+        out = dev.loglike_mean_grad(md, rows, self._mean_gradient_columns(dev, md))
+        lnl = np.where(out["info"] == 0, out["lnl"], -np.inf)
+        return (lnl, out["grad"], out["info"]) if return_info else (lnl, out["grad"])
+
+    def log_likelihood_full_gradient_batch(self, P, return_info=False, one_pass=False):
+        """``(lnL (B,), grad (B, len(labels)))``: the gradient in every thawed label, columns in :attr:`labels` order -- the mean
+        call's columns and, where covariance labels are thawed, :meth:`log_likelihood_gradient_batch`'s (two device calls).  A
+        thawed ``Rv`` gets a zero column: it is never passed on.
+
+        ``one_pass=True``: both parts from ONE factorisation per walker (sf_loglike_multi_grad_batch_md with one segment)
+        instead of one per call; the values agree with the default's to rounding, not bit for bit."""
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        labels = self.labels
+        grad = np.zeros((P.shape[0], len(labels)))
+        lnl = info = None
+        if one_pass:
+            mean, cov = self.mean_gradient_labels, self.gradient_labels
+            if not mean and not cov:
+                raise ValueError("no thawed parameter to differentiate in")
+            dev, md, rows = self._pack(P, update_caches=False)
+            columns = self._mean_gradient_columns(dev, md) if mean else []
+            out = D.loglike_multi_grad([dev], [md], [rows], [(columns, bool(cov))])[0]
+            grad[:, [labels.index(key) for key in mean]] = out["grad"][:, :len(columns)]
+            if cov:
+                grad[:, [labels.index(key) for key in cov]] = out["grad"][:, [len(columns) + s for s in self._gradient_slots(md)]]
+            lnl, info = np.where(out["info"] == 0, out["lnl"], -np.inf), out["info"]
+            return (lnl, grad, info) if return_info else (lnl, grad)
+        if self.mean_gradient_labels:
+            lnl, g, info = self.log_likelihood_mean_gradient_batch(P, return_info=True)
+            grad[:, [labels.index(key) for key in self.mean_gradient_labels]] = g
+        if self.gradient_labels:
+            lnl, g, info = self.log_likelihood_gradient_batch(P, return_info=True)
+            grad[:, [labels.index(key) for key in self.gradient_labels]] = g
+        if lnl is None:
+            raise ValueError("no thawed parameter to differentiate in")
+        return (lnl, grad, info) if return_info else (lnl, grad)
+
+    def _train_gradient(self, priors, kwargs):
+        """The ``gradient=True`` search of :meth:`train`."""
+        def evaluate(x):
+            self.set_param_vector(x)
+            lnl, grad, info = self.log_likelihood_full_gradient_batch(x[None, :], return_info=True)
+            self._raise_for_info(info[0])
+            return lnl[0], grad[0]
+
+        soln = _map.minimize_lbfgsb(evaluate, self.get_param_vector().astype(np.float64),
+                                    *self._prior_split(priors, self.labels), kwargs, finite_for="SpectrumModel.train")
+        if soln.success or soln.status == 1:  # (1: the iteration / evaluation limit; soln.x is the best point so far)
+            self.set_param_vector(soln.x)
+        return soln

@@ -90,7 +90,11 @@ class EchelleModel:
 
     def _layout(self):
         """(labels, cols): the model's labels, and for every order the columns of a parameter vector that hold
-        that order's own labels (shared labels first, then each order's per-order labels, prefixed)."""
+        that order's own labels (shared labels first, then each order's per-order labels, prefixed).  Without
+        ``per_order``: order 0's labels and every column for every order, whatever the other orders' labels are."""
+        if self.per_order is None:
+            labels = tuple(self.orders[0].labels)
+            return labels, [np.arange(len(labels), dtype=np.intp)] * len(self.orders)
         shared = [k for k in self.orders[0].labels if not self._is_per_order(k)]
         labels, cols = list(shared), []
         for i, m in enumerate(self.orders):
@@ -225,6 +229,15 @@ class EchelleModel:
                 lp += prior.logpdf(self.orders[i][key])
         return lp
 
+    @staticmethod
+    def _by_device(packed):
+        """The orders of ``packed`` (``_pack`` results) that may share one multi-order call: lists of indices, one per
+        device and emulator shape."""
+        groups = {}
+        for idx, (dev, _md, _rows) in enumerate(packed):
+            groups.setdefault((str(dev.dev), dev.m, dev.P), []).append(idx)
+        return list(groups.values())
+
     def log_likelihood(self, priors=None):
         """Sum of the per-order likelihoods; the prior is counted once (per order for a per-order parameter)."""
         if self.per_order is None:
@@ -251,15 +264,11 @@ class EchelleModel:
 
         P = np.atleast_2d(np.asarray(P, dtype=np.float64))
         B = P.shape[0]
-        if self.per_order is None:
-            order_P = [P] * len(self.orders)
-            prior_lp = self.orders[0]._batch_prior(P, priors)
-        else:
-            labels, cols = self._layout()
-            if P.shape[1] != len(labels):
-                raise ValueError("Param Vector does not match length of thawed parameters")
-            order_P = [P[:, c] for c in cols]
-            prior_lp = self._batch_prior(P, priors, cols)
+        labels, cols = self._layout()
+        if P.shape[1] != len(labels):
+            raise ValueError("Param Vector does not match length of thawed parameters")
+        order_P = [P[:, c] for c in cols]
+        prior_lp = self._batch_prior(P, priors, cols)
         finite = np.isfinite(prior_lp)
         lnl = np.full(B, -np.inf)
         info = np.zeros(B, dtype=np.int32)
@@ -304,11 +313,8 @@ class EchelleModel:
             packed = [m._pack(order_P[i][finite], update_caches=False) for i, m in enumerate(self.orders)]
             # one multi-order call per device (and emulator shape): orders whose row layouts differ -- per-order
             # Chebyshev terms, another number of local kernels, ... -- pass one descriptor each
-            groups = {}
-            for idx, (dev, md, rows) in enumerate(packed):
-                groups.setdefault((str(dev.dev), dev.m, dev.P), []).append(idx)
             pending = []
-            for idxs in groups.values():  # enqueue everything first, synchronise afterwards
+            for idxs in self._by_device(packed):  # enqueue everything first, synchronise afterwards
                 devs = [packed[i][0] for i in idxs]
                 mds = [packed[i][1] for i in idxs]
                 same = all(D.model_desc_key(m) == D.model_desc_key(mds[0]) for m in mds)
@@ -338,11 +344,7 @@ class EchelleModel:
         the device does not differentiate."""
         from .. import _device as D
 
-        if self.per_order is None:
-            labels = tuple(self.orders[0].labels)
-            cols = [np.arange(len(labels), dtype=np.intp)] * len(self.orders)
-        else:
-            labels, cols = self._layout()
+        labels, cols = self._layout()
         if not labels:
             raise ValueError("no thawed parameter to differentiate in")
         requests, sources = [], [[] for _ in labels]
@@ -382,11 +384,8 @@ class EchelleModel:
             raise ValueError("Param Vector does not match length of thawed parameters")
         B = P.shape[0]
         packed = [m._pack(P[:, cols[i]], update_caches=False) for i, m in enumerate(self.orders)]
-        groups = {}
-        for idx, (dev, md, rows) in enumerate(packed):
-            groups.setdefault((str(dev.dev), dev.m, dev.P), []).append(idx)
         pending = []
-        for idxs in groups.values():  # enqueue everything first, synchronise afterwards
+        for idxs in self._by_device(packed):  # enqueue everything first, synchronise afterwards
             if not any(requests[i][0] or requests[i][1] for i in idxs):  # nothing thawed in these orders: lnl only
                 pending.append((idxs, D.loglike_multi([packed[i][0] for i in idxs], [packed[i][1] for i in idxs],
                                                       [packed[i][2] for i in idxs], sync=False)))
@@ -427,21 +426,19 @@ class EchelleModel:
         ``eps^(1/3) max(1, |x|)``, priors on other parameters a constant.  A point the device flags raises as
         :meth:`SpectrumModel.log_likelihood` does.  ``kwargs`` go to ``minimize``.  Every evaluation leaves the model at its
         point; a run that succeeds or stops at its iteration limit leaves it at ``soln.x``."""
-        from scipy.optimize import minimize
+        from .. import _map
 
         labels, cols, _requests, _sources = self._gradient_layout()  # (refusals before any device work)
         for key, prior in (priors or {}).items():
             if not callable(getattr(prior, "logpdf", None)):
                 raise ValueError(f"Invalid priors. {key} does not have a `logpdf` method")
         terms = self._prior_terms(priors)
-        h0 = np.finfo(np.float64).eps ** (1.0 / 3.0)
 
-        def objective(x):
-            if np.any(~np.isfinite(x)):
-                raise ValueError("EchelleModel.train: the optimiser asked for a point that is not finite")
+        def evaluate(x):
             self.set_param_vector(x)
             lnl, grad, info = self.log_likelihood_gradient_batch(x[None, :], return_info=True)
             SpectrumModel._raise_for_info(info[0])
+            # the priors are added here, not by _map: constant and sampled terms alternate in the order of ``terms``
             value, slope = float(lnl[0]), grad[0].copy()
             for prior, i, key in terms:
                 own = self.orders[i].labels
@@ -449,15 +446,13 @@ class EchelleModel:
                     value += prior.logpdf(self.orders[i][key])
                     continue
                 j = cols[i][own.index(key)]
-                h = h0 * max(1.0, abs(x[j]))
-                value += prior.logpdf(x[j])
-                slope[j] += (prior.logpdf(x[j] + h) - prior.logpdf(x[j] - h)) / (2 * h)
-            return -value, -slope
+                v, s = _map.prior_value_and_slope(prior, x[j])
+                value += v
+                slope[j] += s
+            return value, slope
 
-        opts = {"method": "L-BFGS-B"}
-        opts.update(kwargs)
-        opts["jac"] = True
-        soln = minimize(objective, self.get_param_vector().astype(np.float64), **opts)
+        soln = _map.minimize_lbfgsb(evaluate, self.get_param_vector().astype(np.float64), [], None, kwargs,
+                                    finite_for="EchelleModel.train")
         if soln.success or soln.status == 1:  # (1: the iteration / evaluation limit; soln.x is the best point so far)
             self.set_param_vector(soln.x)
         return soln

@@ -12,6 +12,8 @@ from oracle import sf_oracle as O
 from starfish_amd import _lib, synth
 from starfish_amd.models import SpectrumModel
 
+import stand_in
+
 SF_EINVAL = -1
 FAKE = 0x10000  # a non-null "device pointer": a refused call never touches it
 U = 2.0 ** -53
@@ -70,20 +72,8 @@ def test_decompose_entry_points_refuse_a_missing_context_or_model():
 
 
 # ------------------------------------------------------------------ the model methods over a stand-in DeviceOrder
-class StandIn:
+class StandIn(stand_in.StandIn):
     """What SpectrumModel asks of a DeviceOrder here; decompose returns numbers that name their own index."""
-
-    def __init__(self, n, info=0):
-        self.n, self.P, self.info, self.calls = n, 3, info, []
-
-    def model_desc(self, has_vsini, has_vz, has_log_scale, has_global, n_local, n_cheb, use_sigma_w=False, has_av=False):
-        md = _lib.ModelDesc()
-        md.has_vsini, md.has_vz, md.has_log_scale, md.has_global = int(has_vsini), int(has_vz), int(has_log_scale), int(has_global)
-        md.n_local, md.n_cheb, md.use_sigma_w, md.has_av = int(n_local), int(n_cheb), int(use_sigma_w), int(has_av)
-        return md
-
-    def param_stride(self, md):
-        return 6 + self.P + md.n_cheb + 3 * md.n_local + md.has_av
 
     def decompose(self, md, rows, rhs=None, want_flux=False, max_chunk=None):
         B, nrhs = rows.shape[0], 1 if rhs is None else rhs.shape[-2]
@@ -94,17 +84,16 @@ class StandIn:
 
 
 def model_with(n_local, has_global, N=64):
-    o = synth.make_order(N=N, m=3, seed=9)
-    p = dict(synth.centre_params(o))
-    p["local_cov"] = [dict(mu=float(o["wave"][5 + 7 * j]), log_amp=-8.0 - j, log_sigma=2.5) for j in range(n_local)]
-    if not n_local:
-        del p["local_cov"]
-    if not has_global:
-        del p["global_cov"]
-    model = synth.build_model(o, params=p)
-    standin = StandIn(N)
-    model._device = lambda: standin
-    return model, standin
+    def params(o):
+        p = dict(synth.centre_params(o))
+        p["local_cov"] = [dict(mu=float(o["wave"][5 + 7 * j]), log_amp=-8.0 - j, log_sigma=2.5) for j in range(n_local)]
+        if not n_local:
+            del p["local_cov"]
+        if not has_global:
+            del p["global_cov"]
+        return p
+
+    return stand_in.model_on_a_stand_in(StandIn, N=N, params=params)
 
 
 @pytest.mark.parametrize("n_local", [0, 1, 3])

@@ -12,6 +12,7 @@ from oracle import sf_oracle as O
 from starfish_amd import _lib, synth
 
 import cov_derivatives as CD
+from stand_in import StandIn as HostStandIn, model_on_a_stand_in, state_of
 
 SF_EINVAL = -1
 FAKE = 0x10000  # a non-null "device pointer": a refused call never touches it
@@ -198,20 +199,8 @@ def test_potri_blocks_refuses_bad_arguments_before_any_device_call(case):
 
 
 # ------------------------------------------------------------------ (d) the model methods over a stand-in DeviceOrder
-class StandIn:
+class StandIn(HostStandIn):
     """What SpectrumModel asks of a DeviceOrder here; loglike_grad returns numbers that name their walker and slot."""
-
-    def __init__(self, n, info=0):
-        self.n, self.P, self.info, self.calls = n, 3, info, []
-
-    def model_desc(self, has_vsini, has_vz, has_log_scale, has_global, n_local, n_cheb, use_sigma_w=False, has_av=False):
-        md = _lib.ModelDesc()
-        md.has_vsini, md.has_vz, md.has_log_scale, md.has_global = int(has_vsini), int(has_vz), int(has_log_scale), int(has_global)
-        md.n_local, md.n_cheb, md.use_sigma_w, md.has_av = int(n_local), int(n_cheb), int(use_sigma_w), int(has_av)
-        return md
-
-    def param_stride(self, md):
-        return 6 + self.P + md.n_cheb + 3 * md.n_local + md.has_av
 
     def loglike_grad(self, md, rows, want_flux=False, max_chunk=None):
         B, slots = rows.shape[0], (2 if md.has_global else 0) + 3 * md.n_local
@@ -220,25 +209,14 @@ class StandIn:
         return dict(lnl=-100.0 - np.arange(B), grad=10.0 * b + s + 0.25, info=np.full(B, self.info, dtype=np.int32))
 
 
-def model_on_a_stand_in(two_local=False):
-    o = synth.make_order(N=64, m=3, seed=9)
-    params = None
-    if two_local:
-        params = synth.centre_params(o)
-        params["local_cov"] = params["local_cov"] + [dict(mu=float(o["wave"][40]), log_amp=-8.5, log_sigma=2.5)]
-    model = synth.build_model(o, params=params)
-    standin = StandIn(64)
-    model._device = lambda: standin
-    return model, standin
-
-
-def state_of(model):
-    return (len(model.residuals), model._lnprob, model._log_scale, model._glob_snapshot, model._loc_snapshot,
-            tuple(model.get_param_vector()), tuple(model.frozen))
+def two_local(o):
+    params = synth.centre_params(o)
+    params["local_cov"] = params["local_cov"] + [dict(mu=float(o["wave"][40]), log_amp=-8.5, log_sigma=2.5)]
+    return params
 
 
 def test_gradient_labels_follow_what_is_thawed():
-    model, dev = model_on_a_stand_in(two_local=True)
+    model, dev = model_on_a_stand_in(StandIn, params=two_local)
     every = ("global_cov:log_amp", "global_cov:log_ls", "local_cov:0:mu", "local_cov:0:log_amp", "local_cov:0:log_sigma",
              "local_cov:1:mu", "local_cov:1:log_amp", "local_cov:1:log_sigma")
     assert model.gradient_labels == every
@@ -273,7 +251,7 @@ def test_gradient_labels_follow_what_is_thawed():
 
 
 def test_nothing_thawed_is_a_value_error_and_failures_raise_as_the_likelihood_does():
-    model, dev = model_on_a_stand_in()
+    model, dev = model_on_a_stand_in(StandIn)
     P = np.tile(model.get_param_vector(), (3, 1))
     with pytest.raises(ValueError):
         model.log_likelihood_gradient_batch(P[:, :-1])
@@ -299,7 +277,7 @@ def test_nothing_thawed_is_a_value_error_and_failures_raise_as_the_likelihood_do
 
 
 def test_train_covariance_checks_its_priors_as_train_does():
-    model, dev = model_on_a_stand_in()
+    model, dev = model_on_a_stand_in(StandIn)
 
     class Flat:
         def logpdf(self, x):

@@ -20,6 +20,7 @@ from starfish_amd import _lib, synth
 
 import mean_derivatives as MD
 from gpu_helpers import oracle_order
+from stand_in import StandIn as HostStandIn, model_on_a_stand_in, state_of
 
 SF_EINVAL = -1
 FAKE = 0x10000
@@ -184,20 +185,8 @@ def test_mean_grad_entry_points_are_present():
     assert lib.sf_loglike_mean_grad_workspace_bytes(None, C.byref(md), 4, 2) == 0
 
 
-class StandIn:
+class StandIn(HostStandIn):
     """What SpectrumModel asks of a DeviceOrder here; the gradients name their walker and their slot (covariance) or column."""
-
-    def __init__(self, n, info=0):
-        self.n, self.P, self.info, self.calls = n, 3, info, []
-
-    def model_desc(self, has_vsini, has_vz, has_log_scale, has_global, n_local, n_cheb, use_sigma_w=False, has_av=False):
-        md = _lib.ModelDesc()
-        md.has_vsini, md.has_vz, md.has_log_scale, md.has_global = int(has_vsini), int(has_vz), int(has_log_scale), int(has_global)
-        md.n_local, md.n_cheb, md.use_sigma_w, md.has_av = int(n_local), int(n_cheb), int(use_sigma_w), int(has_av)
-        return md
-
-    def param_stride(self, md):
-        return 6 + self.P + md.n_cheb + 3 * md.n_local + md.has_av
 
     def loglike_grad(self, md, rows, want_flux=False, max_chunk=None):
         B, slots = rows.shape[0], (2 if md.has_global else 0) + 3 * md.n_local
@@ -215,22 +204,8 @@ class StandIn:
                     info=np.full(B, self.info, dtype=np.int32))
 
 
-def model_on_a_stand_in(**kw):
-    o = synth.make_order(N=64, m=3, seed=9)
-    params = dict(synth.centre_params(o), **kw.pop("params", {}))
-    model = synth.build_model(o, params=params, **kw)
-    standin = StandIn(64)
-    model._device = lambda: standin
-    return model, standin
-
-
-def state_of(model):
-    return (len(model.residuals), model._lnprob, model._log_scale, model._glob_snapshot, model._loc_snapshot,
-            tuple(model.get_param_vector()), tuple(model.frozen))
-
-
 def test_mean_gradient_labels_and_columns_follow_what_is_thawed():
-    model, dev = model_on_a_stand_in(params=dict(Av=0.2, Rv=3.1))
+    model, dev = model_on_a_stand_in(StandIn, params=dict(Av=0.2, Rv=3.1))
     assert model.labels[:3] == ("vz", "vsini", "log_scale") and "Rv" in model.labels and "Av" in model.labels
     every = tuple(k for k in model.labels if not k.startswith(("global_cov", "local_cov")) and k != "Rv")
     assert model.mean_gradient_labels == every and set(every) == set(MEAN) | {"Av"}
@@ -273,12 +248,12 @@ def test_models_the_device_does_not_differentiate_are_refused_with_a_reason():
     model._device = lambda: StandIn(64)
     with pytest.raises(ValueError, match="log_scale"):
         model.log_likelihood_mean_gradient()
-    model, dev = model_on_a_stand_in(emulator_cov="paper")
+    model, dev = model_on_a_stand_in(StandIn, emulator_cov="paper")
     with pytest.raises(ValueError, match="paper"):
         model.log_likelihood_mean_gradient_batch(np.tile(model.get_param_vector(), (2, 1)))
     with pytest.raises(ValueError, match="paper"):
         model.train(gradient=True)
-    model, dev = model_on_a_stand_in()
+    model, dev = model_on_a_stand_in(StandIn)
     model.norm = True
     with pytest.raises(ValueError, match="norm=True"):
         model.log_likelihood_mean_gradient()
@@ -296,7 +271,7 @@ def test_models_the_device_does_not_differentiate_are_refused_with_a_reason():
 
 
 def test_train_gradient_runs_lbfgsb_over_all_labels_and_leaves_the_model_at_the_solution():
-    model, dev = model_on_a_stand_in(freeze=("global_cov", "local_cov"))
+    model, dev = model_on_a_stand_in(StandIn, freeze=("global_cov", "local_cov"))
     labels = model.labels
     assert labels == model.mean_gradient_labels and len(labels) == 8
 
@@ -318,5 +293,5 @@ def test_train_gradient_runs_lbfgsb_over_all_labels_and_leaves_the_model_at_the_
     np.testing.assert_array_equal(model.get_param_vector(), soln.x)
     assert all(call[0] == "mean" and call[1] == 1 for call in dev.calls)
     # the default path is the Nelder-Mead loop as before: it never asks for a gradient
-    model2, dev2 = model_on_a_stand_in()
+    model2, dev2 = model_on_a_stand_in(StandIn)
     assert model2.train.__defaults__ == (None, True, False)

@@ -11,6 +11,8 @@ from oracle import sf_oracle as O
 from starfish_amd import _lib, synth
 from starfish_amd.models import SpectrumModel
 
+from stand_in import StandIn as HostStandIn, model_on_a_stand_in
+
 SF_EINVAL = -1
 FAKE = 0x10000  # a non-null "device pointer": a refused call never touches it
 U = 2.0 ** -53
@@ -98,20 +100,8 @@ def test_potri_diag_refuses_bad_arguments_before_any_device_call(case):
 
 
 # ------------------------------------------------------------------ the model methods over a stand-in DeviceOrder
-class StandIn:
+class StandIn(HostStandIn):
     """What SpectrumModel asks of a DeviceOrder here; pointwise returns numbers that name their own index."""
-
-    def __init__(self, n, info=0):
-        self.n, self.P, self.info, self.calls = n, 3, info, []
-
-    def model_desc(self, has_vsini, has_vz, has_log_scale, has_global, n_local, n_cheb, use_sigma_w=False, has_av=False):
-        md = _lib.ModelDesc()
-        md.has_vsini, md.has_vz, md.has_log_scale, md.has_global = int(has_vsini), int(has_vz), int(has_log_scale), int(has_global)
-        md.n_local, md.n_cheb, md.use_sigma_w, md.has_av = int(n_local), int(n_cheb), int(use_sigma_w), int(has_av)
-        return md
-
-    def param_stride(self, md):
-        return 6 + self.P + md.n_cheb + 3 * md.n_local + md.has_av
 
     def pointwise(self, md, rows, rhs=None, want_flux=False, max_chunk=None):
         B, nrhs = rows.shape[0], 1 if rhs is None else rhs.shape[-2]
@@ -122,14 +112,6 @@ class StandIn:
         if want_flux:
             out["flux"] = 7.0 * (b[:, 0] + 1) + i[:, 0]
         return out
-
-
-def model_on_a_stand_in(N=64):
-    o = synth.make_order(N=N, m=3, seed=9)
-    model = synth.build_model(o)
-    standin = StandIn(N)
-    model._device = lambda: standin
-    return model, standin
 
 
 def expected(model, B, rhs, N=64):
@@ -144,7 +126,7 @@ def expected(model, B, rhs, N=64):
 
 
 def test_keys_shapes_and_formulas_of_the_model_methods():
-    model, dev = model_on_a_stand_in()
+    model, dev = model_on_a_stand_in(StandIn)
     N = 64
     state = (len(model.residuals), model._lnprob, model._log_scale, model._glob_snapshot, model._loc_snapshot)
     rng = np.random.default_rng(0)
@@ -176,7 +158,7 @@ def test_keys_shapes_and_formulas_of_the_model_methods():
 
 
 def test_shapes_are_checked_and_failures_raise_as_the_likelihood_does():
-    model, dev = model_on_a_stand_in()
+    model, dev = model_on_a_stand_in(StandIn)
     P = np.tile(model.get_param_vector(), (3, 1))
     for bad in (np.zeros(63), np.zeros((2, 65)), np.zeros((1, 2, 64)), 1.0):
         with pytest.raises(ValueError):
