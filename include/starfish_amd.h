@@ -517,6 +517,33 @@ int sf_band_logdet_gram_batch(const double* d_band, int n, int halfwidth, int ld
                               int batch, const double* d_rhs, int nrhs, int ldr, int64_t rhs_stride,
                               double* d_logdet, double* d_gram, int* d_info, void* stream);
 
+/* Stand-alone banded solve, the counterpart of sf_band_logdet_gram_batch that keeps the factor: for the same band matrices
+ * and right-hand sides (nrhs in 1 .. 48) returns d_x[b*x_stride + r*ldx + i] = (A^-1 rhs_r)_i, i < n  (scipy.linalg.
+ * cholesky_banded + cho_solve_banded), d_logdet[b] and, if d_gram is not NULL, the same Gram matrix.  d_band is not
+ * modified: the factor goes to the workspace (sf_band_solve_workspace_bytes; 0 for arguments the call refuses), about
+ * n (halfwidth + 32 + nrhs) doubles per matrix.  d_info[b] (zeroed by the call) = 1-based column of the first non-positive
+ * pivot; such a matrix gets NaN in every entry of its x.  Only half-widths the LDS window takes (144 for nrhs <= 16, 128 for
+ * nrhs <= 32, 112 beyond); ldx >= n.  SF_EINVAL, before anything is enqueued, for a null pointer, such a half-width or
+ * nrhs outside 1 .. 48; SF_ENOMEM for a short workspace.  Never synchronises. */
+size_t sf_band_solve_workspace_bytes(int n, int halfwidth, int batch, int nrhs);
+int sf_band_solve_batch(const double* d_band, int n, int halfwidth, int ldb, int64_t stride, int batch, const double* d_rhs,
+                        int nrhs, int ldr, int64_t rhs_stride, double* d_x, int ldx, int64_t x_stride, double* d_logdet,
+                        double* d_gram, int* d_info, void* d_work, size_t work_bytes, void* stream);
+
+/* The mean-flux gradient of sf_loglike_mean_grad_batch (same h_slots, d_grad rows, refusals and NaN rows) on the band +
+ * Woodbury solver: band fill and transforms as sf_loglike_banded_batch, the band sweep keeping its factor, the capacitance
+ * step (d_lnl, d_info as sf_loglike_banded_batch reports them), a backward sweep giving T = Bd^-1 [r, Y^T], the mix
+ * [alpha, V] = T M with the (1 + m) x (1 + m) matrix M of the Woodbury identity, then the dense call's contraction.
+ * d_resid (may be NULL): [B][n], model flux minus data flux.  halfwidth as for sf_loglike_banded_batch but at most
+ * sf_banded_window_halfwidth(ctx) -- beyond it SF_EINVAL (use sf_loglike_mean_grad_batch); a walker whose support is wider
+ * than halfwidth gets SF_INFO_BANDWIDTH, -inf and a NaN row.  Values agree with the dense call to rounding, not bit for bit;
+ * a repeated call, a call on a sub-batch and a call with a subset of the slots give the same bits.  Never synchronises. */
+size_t sf_loglike_banded_mean_grad_workspace_bytes(const sf_ctx* ctx, const sf_model_desc* model, int B, int halfwidth,
+                                                   int nslots);
+int sf_loglike_banded_mean_grad_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, int halfwidth,
+                                      const int* h_slots, int nslots, double* d_lnl, double* d_grad, int grad_stride,
+                                      double* d_resid, int* d_info, void* d_work, size_t work_bytes, void* stream);
+
 /* Timing hooks for bench.py (process-global, not thread-safe): when enabled, the batched calls
  * record HIP events on the caller's stream around each stage and around every MFMA update launch.
  * sf_profile_read synchronises those events, returns the milliseconds accumulated since the last

@@ -877,17 +877,68 @@ class DeviceOrder:
     def loglike_mean_grad_workspace_bytes(self, md, B, nslots):
         return self._size_query("loglike_mean_grad_", md, B, nslots)
 
-    def loglike_mean_grad(self, md, params, slots, want_flux=False, max_chunk=None):
+    def loglike_banded_mean_grad_workspace_bytes(self, md, B, halfwidth, nslots):
+        return self._size_query("loglike_banded_mean_grad_", md, B, halfwidth, nslots)
+
+    def loglike_mean_grad(self, md, params, slots, want_flux=False, max_chunk=None, solver="dense"):
         """The likelihood and its gradient in the mean-flux parameters (sf_loglike_mean_grad_batch).  params: (B, stride) rows
         as for :meth:`loglike`; slots: the columns of the parameter row to differentiate in (vsini = 0, vz = 1, log_scale = 2,
         the grid, Chebyshev and Av columns), each at most once, at most MEAN_GRAD_MAX_SLOTS.  Returns dict of
         numpy arrays: lnl (B,) and info (B,) with :meth:`loglike`'s bits, grad (B, len(slots)) in the order of ``slots``, NaN rows
-        where info != 0, and, asked for, flux (B, n).  Chunked and retried like :meth:`apply`."""
+        where info != 0, and, asked for, flux (B, n).  Chunked and retried like :meth:`apply`.
+
+        solver: "dense"  -- the dense factor (sf_loglike_mean_grad_batch);
+                "banded" -- band + rank-m Woodbury solve with a backward sweep (sf_loglike_banded_mean_grad_batch): lnl and
+                            grad agree with the dense call to rounding, not bit for bit;
+                            walkers whose covariance support exceeds the LDS window come back with info = -4;
+                "auto"   -- banded for the walkers whose half-width bound fits the window, dense for the rest."""
+        if solver not in ("dense", "banded", "auto"):
+            raise ValueError("solver must be 'dense', 'banded' or 'auto'")
         slots = [int(v) for v in slots]
         nslots = len(slots)
         h_slots = (C.c_int * max(nslots, 1))(*slots)
+        if solver != "dense":
+            return self._mean_grad_structured(md, params, slots, h_slots, want_flux, max_chunk, solver)
         return self._run_grad("loglike_mean_grad_batch", md, params, (h_slots, nslots), nslots,
                               lambda units: self.loglike_mean_grad_workspace_bytes(md, units, nslots), want_flux, max_chunk)
+
+    def _mean_grad_structured(self, md, params, slots, h_slots, want_flux, max_chunk, solver):
+        """:meth:`loglike_mean_grad` on the band solver: the walkers whose host half-width bound fits the LDS window in one
+        group with the group's largest bound (so that chunks of it give the same bits); the rest, and walkers with the
+        internal status, through the dense call under "auto" (the internal status under "banded" too)."""
+        torch = _torch()
+        rows = params.cpu().numpy() if torch.is_tensor(params) else np.asarray(params, dtype=np.float64)
+        rows = np.atleast_2d(rows)
+        B, nslots = rows.shape[0], len(slots)
+        hw = self.halfwidth_bound(md, rows)
+        fits = hw <= self.banded_window_halfwidth()
+        out = dict(lnl=np.full(B, -np.inf), grad=np.full((B, nslots), np.nan), info=np.full(B, INFO_BANDWIDTH, dtype=np.int32))
+        if want_flux:
+            out["flux"] = np.full((B, self.n), np.nan)
+        idx = np.nonzero(fits)[0]
+        if idx.size:
+            W = int(hw[idx].max())
+            got = self._run_grad("loglike_banded_mean_grad_batch", md, rows[idx], (W, h_slots, nslots), nslots,
+                                 lambda units: self.loglike_banded_mean_grad_workspace_bytes(md, units, W, nslots), want_flux,
+                                 max_chunk)
+            if want_flux:  # (the call returns the residual: model minus data)
+                got["flux"] = got["flux"] + self._keep[1][None, :]
+            for key, v in got.items():
+                out[key][idx] = v
+        internal = out["info"] == INFO_INTERNAL
+        if internal.any():
+            import warnings
+
+            warnings.warn(f"banded solver: internal status -5 for {int(internal.sum())} walker(s); recomputed densely",
+                          RuntimeWarning)
+        rest = np.nonzero(internal)[0]
+        if solver == "auto":  # too wide for the window -> dense
+            rest = np.nonzero(~fits | (out["info"] == INFO_BANDWIDTH) | internal)[0]
+        if rest.size:
+            dense = self.loglike_mean_grad(md, rows[rest], slots, want_flux=want_flux, max_chunk=max_chunk, solver="dense")
+            for key in out:
+                out[key][rest] = dense[key]
+        return out
 
     def loglike_device(self, md, P_dev, out_lnl, info=None):
         """Enqueue-only variant for bench.py: device tensors in/out, no synchronisation."""

@@ -43,9 +43,11 @@
 //   sf_band_shape.h     the window's shape without HIP: constants, nbr / nrb / waves, the LDS layout, which solver takes a
 //                       half-width, the workers' positions, the twisted sweep's shape and workspace, when it pays
 //   sf_band_window.h    sf_band_args, sfb_pair, sfb_gram, sfb_fetch (the right-hand sides and the call: sf_band_rhs, sf_band_call, sf_common.h)
-//   sf_band_sweep.h     k_band_forms, launch_forms_kernel, sf_launch_band_forms
+//   sf_band_sweep.h     k_band_forms (its text: sf_band_sweep_body.h), launch_forms_kernel, sf_launch_band_forms
 //   sf_band_twist.h     k_band_merge, sf_band_twisted_applicable, sf_launch_band_forms_twisted
 //   sf_band_woodbury.h  k_woodbury, sf_launch_woodbury
+//   sf_band_solve.h     the full solve x = A^-1 rhs for the mean-flux gradient: k_band_keep (the sweep, which then also stores
+//                       the factor), k_band_back (backward sweep), k_band_mix_matrix / k_band_mix (Woodbury mix), their launchers
 #include "sf_common.h"
 #include "sf_device.h"
 #include "sf_band_shape.h"
@@ -53,3 +55,4 @@
 #include "sf_band_sweep.h"
 #include "sf_band_twist.h"
 #include "sf_band_woodbury.h"
+#include "sf_band_solve.h"

@@ -119,3 +119,33 @@ SFB_HD bool sfb_twist_pays(int nblk, int nbr, int batch, int ncu) {
     const int rounds1 = (batch + ncu - 1) / ncu, rounds2 = (2 * batch + ncu - 1) / ncu;
     return 0.5 * rounds2 + 0.12 * rounds1 < (double)rounds1;
 }
+
+// ---- the full solve x = A^-1 rhs (sf_band_solve.h): what the keeping sweep stores, and the backward sweep's LDS
+// Per block column k the keeping sweep writes one record of nbr + nrb row-major 16 x 16 blocks (no row padding):
+//   [0] F_k = L_kk^-1    [1 + I] L_{k+1+I,k}, I < nbr - 1    [nbr + rb] block rb of the forward-substituted right-hand
+//   sides (L^-1 rhs)_k, transposed: rows = right-hand sides, columns = the 16 pixels of the column
+SFB_HD int sfb_keep_column_blocks(int nbr, int nrb) { return nbr + nrb; }
+SFB_HD size_t sfb_keep_block(int kb, int j, int nbr, int nrb) {  // offset of block j of column kb's record, in doubles
+    return ((size_t)kb * sfb_keep_column_blocks(nbr, nrb) + j) * (BB * BB);
+}
+SFB_HD size_t sfb_keep_doubles(int n, int nbr, int nrb) {  // stored factor + right-hand sides of one matrix: ~ n (W + 16 + nrhs)
+    return sfb_keep_block((n + BB - 1) / BB, 0, nbr, nrb);
+}
+// The backward sweep k_band_back<NRB>: SFB_BACK_SPLIT waves per block of right-hand sides share the sum over a column's
+// blocks.  Its dynamic LDS, offsets in doubles (blocks of BS doubles, row stride 17):
+//   T     [nrb][nbr] ring of the solved blocks, slot = block column % nbr
+//   part  [nrb][SFB_BACK_SPLIT] partial sums of the step
+#define SFB_BACK_SPLIT 4
+struct sfb_back_lds {
+    int T, part, doubles;
+    size_t bytes;
+};
+SFB_HD sfb_back_lds sfb_back_lds_layout(int nbr, int nrb) {
+    sfb_back_lds L;
+    L.T = 0, L.part = L.T + nrb * nbr * BS, L.doubles = L.part + nrb * SFB_BACK_SPLIT * BS;
+    L.bytes = sizeof(double) * (size_t)L.doubles;
+    return L;
+}
+SFB_HD int sfb_back_nwaves(int nrb) { return SFB_BACK_SPLIT * nrb; }
+SFB_HD int sfb_back_blocks_per_wave(int nbr) { return (nbr - 1 + SFB_BACK_SPLIT - 1) / SFB_BACK_SPLIT; }  // factor blocks a wave holds
+#define SFB_BACK_MAX_BLOCKS 3  // ... at the widest window the LDS admits (nbr = 10)

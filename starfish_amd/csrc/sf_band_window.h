@@ -31,6 +31,13 @@ struct sf_band_args {
     double* dumpL;             // [batch][2]          partial log-determinants
 };
 
+// Where the keeping sweep (k_band_keep, sf_band_solve.h) stores what it eliminates: per block column one record of
+// sfb_keep_column_blocks blocks (sfb_keep_block)
+struct sf_band_keep {
+    double* fac;   // [batch] x sfac
+    int64_t sfac;
+};
+
 __device__ __forceinline__ int sfb_pair(int a, int b) {  // slot of the unordered pair {a, b}
     return a >= b ? a * (a + 1) / 2 + b : b * (b + 1) / 2 + a;
 }

@@ -115,3 +115,140 @@ extern "C" int sf_band_logdet_gram_batch(const double* d_band, int n, int halfwi
     k.logdet = d_logdet, k.gram = d_gram, k.info = d_info;
     return sf_launch_band_forms(k, s);
 }
+
+// ----------------------------------------------------------------------------------- the full banded solve
+// what sf_band_solve_batch refuses before it touches the device; who == NULL: silently (the size query)
+static int band_solve_shape_ok(const char* who, int n, int halfwidth, int batch, int nrhs) {
+    if (n <= 0 || batch <= 0 || halfwidth < 0 || nrhs < 1 || nrhs > 48) {
+        if (who) sf_set_error("%s: n=%d, batch=%d must be positive, halfwidth=%d >= 0, nrhs=%d in 1 .. 48", who, n, batch, halfwidth, nrhs);
+        return SF_EINVAL;
+    }
+    if (sfb_admit(halfwidth, nrhs) != SFB_WINDOW) {
+        if (who)
+            sf_set_error("%s: half-width %d with %d right-hand sides exceeds the LDS window (max %d)", who, halfwidth, nrhs,
+                         sf_band_max_halfwidth(nrhs));
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_band_solve_workspace_bytes(int n, int halfwidth, int batch, int nrhs) {
+    if (band_solve_shape_ok(nullptr, n, halfwidth, batch, nrhs)) return 0;
+    return carve_band_solve(n, halfwidth, batch, nrhs, nullptr, 0).bytes;
+}
+extern "C" int sf_band_solve_batch(const double* d_band, int n, int halfwidth, int ldb, int64_t stride, int batch,
+                                   const double* d_rhs, int nrhs, int ldr, int64_t rhs_stride, double* d_x, int ldx,
+                                   int64_t x_stride, double* d_logdet, double* d_gram, int* d_info, void* d_work, size_t work_bytes,
+                                   void* stream) {
+    if (!d_band || !d_rhs || !d_x || !d_logdet || !d_info || !d_work) {
+        sf_set_error("sf_band_solve_batch: null pointer");
+        return SF_EINVAL;
+    }
+    SF_CHECK(band_solve_shape_ok("sf_band_solve_batch", n, halfwidth, batch, nrhs));
+    if (ldb < halfwidth + 1 || ldr < n || ldx < n) {
+        sf_set_error("sf_band_solve_batch: ldb=%d < halfwidth + 1, or ldr=%d / ldx=%d < n (%d)", ldb, ldr, ldx, n);
+        return SF_EINVAL;
+    }
+    const BandSolveWork bs = carve_band_solve(n, halfwidth, batch, nrhs, d_work, work_bytes);
+    SF_CHECK(work_fits(work_bytes, bs.bytes));
+    hipStream_t s = (hipStream_t)stream;
+    SF_HIP(hipMemsetAsync(d_info, 0, sizeof(int) * (size_t)batch, s));
+    sf_band_call k = {};
+    k.band = d_band, k.sband = stride, k.ldb = ldb, k.halfwidth = halfwidth;
+    k.n = n, k.batch = batch;
+    k.r = sf_band_rhs{d_rhs, rhs_stride, ldr, nrhs, nullptr, 0};
+    k.logdet = d_logdet, k.gram = d_gram ? d_gram : bs.gram, k.info = d_info;
+    SF_CHECK(sf_launch_band_keep(k, bs.fac, s));
+    return sf_launch_band_back(bs.fac, n, halfwidth, batch, nrhs, d_info, d_x, ldx, x_stride, s);
+}
+
+// ----------------------------------------------------------------------------------- mean-flux gradient on the band solver
+static int banded_mean_grad_counts_ok(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth, bool say) {
+    if (model_ok(c, mdl)) return SF_EINVAL;
+    if (B <= 0 || B > 65535) {
+        if (say) sf_set_error("sf_loglike_banded_mean_grad_batch: B=%d must lie in 1 .. 65535", B);
+        return SF_EINVAL;
+    }
+    const int wmax = sf_banded_window_halfwidth(c);
+    if (halfwidth < 0 || halfwidth > wmax) {
+        if (say)
+            sf_set_error("sf_loglike_banded_mean_grad_batch: half-width %d outside [0, %d], the LDS window (use sf_loglike_mean_grad_batch)",
+                         halfwidth, wmax);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_loglike_banded_mean_grad_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth,
+                                                              int nslots) {
+    if (banded_mean_grad_counts_ok(c, mdl, B, halfwidth, false) || nslots < 1 || nslots > SF_MEAN_GRAD_MAX_SLOTS) return 0;
+    return carve_band_grad(c, mdl, B, halfwidth, nslots, nullptr, 0, carve(c, mdl, B, nullptr, 0, false).bytes).bytes;
+}
+extern "C" int sf_loglike_banded_mean_grad_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int halfwidth,
+                                                 const int* h_slots, int nslots, double* d_lnl, double* d_grad, int grad_stride,
+                                                 double* d_resid, int* d_info, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_params || !h_slots || !d_lnl || !d_grad || !d_work) {
+        sf_set_error("sf_loglike_banded_mean_grad_batch: d_params, h_slots, d_lnl, d_grad and d_work are required");
+        return SF_EINVAL;
+    }
+    SF_CHECK(banded_mean_grad_counts_ok(c, mdl, B, halfwidth, true));
+    SF_CHECK(mean_slots_ok("sf_loglike_banded_mean_grad_batch", c, mdl, h_slots, nslots, grad_stride));
+    const Work w = carve(c, mdl, B, d_work, work_bytes, false);
+    const BandGradWork g = carve_band_grad(c, mdl, B, halfwidth, nslots, d_work, work_bytes, w.bytes);
+    const BandWork& bw = g.bw;
+    const AppliedWork& aw = g.aw;
+    SF_CHECK(work_fits(work_bytes, g.bytes));
+    hipStream_t s = (hipStream_t)stream;
+    if (use_device(c)) return SF_EHIP;
+    prof_count_call();
+    // band fill and transforms side by side, as in sf_loglike_banded_batch
+    sf_exec* aux = &c->exec;
+    SF_CHECK(sf_exec_prepare(aux));
+    hipStream_t sf = aux->aux;
+    if (sf != s) {
+        SF_HIP(hipEventRecord(aux->fork, s));
+        SF_HIP(hipStreamWaitEvent(sf, aux->fork, 0));
+    }
+    const int n16 = (c->n + 15) / 16 * 16, nrhs = c->m + 1;  // (the window's band is filled with identity rows up to whole blocks)
+    const int64_t sband = (int64_t)c->npad * bw.ldb;
+    {
+        ProfScope ps(sf, PS_FILL);
+        SF_HIP(hipMemsetAsync(w.info_c, 0, sizeof(int) * (size_t)B, sf));
+        sf_fill_args f = fill_args(c, mdl, d_params, w);
+        f.C = nullptr;
+        f.lda = 0;
+        f.stride = 0;
+        f.lower_only = 1;
+        f.add_jitter = 1;
+        f.npad = n16;
+        SF_CHECK(sf_launch_band_fill(f, B, bw.band, halfwidth + 1, halfwidth, bw.ldb, sband, w.info_c, bw.gtab, sf));
+    }
+    if (sf != s) SF_HIP(hipEventRecord(aux->join, sf));
+    {
+        ProfScope ps(s, PS_TRANSFORM);
+        SF_CHECK(run_transforms(c, mdl, B, d_params, w, nullptr, aw.xs, d_resid, nullptr, true, s));
+    }
+    if (sf != s) SF_HIP(hipStreamWaitEvent(s, aux->join, 0));
+    {
+        ProfScope ps(s, PS_POTRF);
+        sf_band_call k = {};
+        k.band = bw.band, k.sband = sband, k.ldb = bw.ldb, k.halfwidth = halfwidth;
+        k.n = n16, k.batch = B;
+        k.r = sf_band_rhs{w.Y, (int64_t)c->mpad * c->npad, c->npad, nrhs, w.resid, c->npad};
+        k.logdet = bw.logdet_band, k.gram = bw.gram, k.info = w.info_c;
+        SF_CHECK(sf_launch_band_keep(k, g.fac, s));
+    }
+    {
+        ProfScope ps(s, PS_SOLVE);
+        SF_CHECK(sf_launch_woodbury(bw.gram, nrhs, B, bw.logdet_band, w.logdet, w.sqmah, w.info_c, s));
+        SF_CHECK(sf_launch_finish(B, w.logdet, w.sqmah, w.info_e, w.info_c, aw.lnl, aw.info, s));
+        // T = Bd^-1 [r, Y^T], then [alpha, V] = T M in the staging area
+        SF_CHECK(sf_launch_band_back(g.fac, n16, halfwidth, B, nrhs, aw.info, g.T, c->npad, (int64_t)nrhs * c->npad, s));
+        SF_CHECK(sf_launch_band_mix(bw.gram, w.Lw, c->m, aw.info, g.T, c->n, c->npad, B, g.M, aw.stage, s));
+    }
+    const sf_mean_grad_args ma = mean_grad_kernel_args(c, h_slots, nslots, w, aw, d_grad, grad_stride);
+    SF_CHECK(sf_launch_mean_tangents(broaden_args(c, mdl, B, d_params, w), c->inv_band.as<double>(),
+                                     emu_args(c, mdl, d_params, w, w.mu, nullptr, w.Lw, w.info_e), ma, B, s));
+    SF_CHECK(sf_launch_mean_grad(eval_args(c, mdl, d_params, w), ma, w.zs, c->m * c->M, B, s));
+    SF_HIP(hipMemcpyAsync(d_lnl, aw.lnl, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    if (d_info) SF_HIP(hipMemcpyAsync(d_info, aw.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return SF_OK;
+}

@@ -247,7 +247,7 @@ int sf_launch_global_cov(const double* wave, int n, double amp, double ls, doubl
 int sf_launch_local_cov(const double* wave, int n, double amp, double mu, double sigma, int accumulate,
                         double* out, hipStream_t s);
 
-// sf_band.hip (layers: sf_band_shape.h, sf_band_window.h, sf_band_sweep.h, sf_band_twist.h, sf_band_woodbury.h): banded
+// sf_band.hip (layers: sf_band_shape.h, sf_band_window.h, sf_band_sweep.h, sf_band_twist.h, sf_band_woodbury.h, sf_band_solve.h): banded
 // Cholesky + forward substitution of (1 + m) right-hand sides -> logdet, Gram matrix
 // The right-hand sides of a batch: row r of matrix b at rhs + b * srhs + r * ldr.  Optional separate source for row 0 (the
 // residual lives in its own buffer in the fused path): when rhs0 is given, rows 1.. come from rhs rows 0..
@@ -281,6 +281,16 @@ bool sf_band_twisted_applicable(int n, int halfwidth, int batch);
 int sf_launch_band_forms_twisted(const sf_band_call& c, double* work, hipStream_t s);
 int sf_launch_woodbury(const double* gram, int nrhs, int batch, const double* logdet_band, double* logdet,
                        double* sqmah, int* info, hipStream_t s);
+// sf_band_solve.h: the full solve on the LDS window (sfb_admit(...) == SFB_WINDOW only).  The keeping sweep is
+// sf_launch_band_forms' single sweep, which also stores the factor and the forward-substituted right-hand sides in fac
+// (sfb_keep_doubles(n, nbr, nrb) doubles per matrix); the backward sweep turns them into x[b * sx + r * ldx + i] = (A^-1 rhs_r)_i
+// (NaN where info[b] != 0); the mix forms [alpha, V] = C^-1 [r, X^T] = T M in the mean gradient's staging layout
+// [batch][1 + m][npad] from T = Bd^-1 [r, Y^T] (same layout), the sweep's Gram matrix and Lw (Mwork: [batch][(1 + m)^2])
+int sf_launch_band_keep(const sf_band_call& c, double* fac, hipStream_t s);
+int sf_launch_band_back(const double* fac, int n, int halfwidth, int batch, int nrhs, const int* info, double* x, int ldx, int64_t sx,
+                        hipStream_t s);
+int sf_launch_band_mix(const double* gram, const double* Lw, int m, const int* info, const double* T, int n, int npad, int batch,
+                       double* Mwork, double* stage, hipStream_t s);
 // sf_chol.hip (sf_chol_band.h): wide bands (beyond the LDS window) as bordered band matrices on the fused panel kernel;
 // c.band is not read: the tiles hold the matrix, nband rows of it
 int sf_launch_potrf_band(const sf_band_call& c, int nband, double* tiles, hipStream_t s);

@@ -204,6 +204,44 @@ static AppliedWork carve_applied(const sf_ctx* c, const sf_model_desc* mdl, int 
     return w;
 }
 
+// ------------------------------------------------------------------- the full banded solve
+// sf_band_solve_batch: what the keeping sweep stores (sfb_keep_doubles per matrix), then the Gram matrices of a call that
+// asks for none
+struct BandSolveWork {
+    double *fac, *gram;
+    size_t bytes;
+};
+static BandSolveWork carve_band_solve(int n, int halfwidth, int batch, int nrhs, void* p, size_t cap) {
+    Carve k(p, cap);
+    BandSolveWork w;
+    w.fac = k.take<double>((size_t)batch * sfb_keep_doubles(n, sfb_nbr(halfwidth), sfb_nrb(nrhs)));
+    w.gram = k.take<double>((size_t)batch * nrhs * nrhs);
+    w.bytes = sf_align_up(k.off, 256);
+    return w;
+}
+// sf_loglike_banded_mean_grad_batch, behind the Work of the same call: the band solver's buffers (carve_band), the mean
+// gradient's (carve_applied with AW_MEAN: the staging area [alpha, V], lnl, info, xs, fin, ...), then fac: the kept factor of
+// the sweep over n16 = n rounded up to whole blocks; T: [B][1 + m][npad] = Bd^-1 [r, Y^T]; M: [B][(1 + m)^2] mix matrices
+struct BandGradWork {
+    BandWork bw;
+    AppliedWork aw;
+    double *fac, *T, *M;
+    size_t bytes;
+};
+static BandGradWork carve_band_grad(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth, int nslots, void* p, size_t cap,
+                                    size_t base_bytes) {
+    BandGradWork g;
+    const int nrhs = c->m + 1, n16 = (c->n + 15) / 16 * 16;
+    g.bw = carve_band(c, B, halfwidth, p, cap, base_bytes);
+    g.aw = carve_applied(c, mdl, B, nrhs, AW_MEAN, p, cap, g.bw.bytes, nslots);
+    Carve k(p, cap, g.aw.bytes);
+    g.fac = k.take<double>((size_t)B * sfb_keep_doubles(n16, sfb_nbr(halfwidth), sfb_nrb(nrhs)));
+    g.T = k.take<double>((size_t)B * nrhs * c->npad);
+    g.M = k.take<double>((size_t)B * nrhs * nrhs);
+    g.bytes = sf_align_up(k.off, 256);
+    return g;
+}
+
 // ------------------------------------------------------------------- multi-order gradient
 // (sf_loglike_multi_grad_batch_md; behind the Work of the same call: base_bytes = its size)  Rows are laid out with the
 // group's common npad (L.npad), not an order's own.  For all U units: the staging area, nrhs right-hand sides of npad doubles

@@ -102,32 +102,59 @@ class Gradients:
         slots = self._slot_of(dev, md)
         return [slots[key] for key in labels]
 
-    def log_likelihood_mean_gradient(self):
+    @staticmethod
+    def _gradient_solver(solver):
+        """``solver`` of the mean-gradient methods as :meth:`DeviceOrder.loglike_mean_grad` takes it.  ``None`` is "dense",
+        whatever the model's own ``solver`` is: a model built with ``solver="auto"`` keeps the dense gradient's bits unless the
+        caller asks for the band solver."""
+        solver = "dense" if solver is None else solver
+        if solver not in ("dense", "banded", "auto"):
+            raise ValueError("solver must be None, 'dense', 'banded' or 'auto'")
+        return solver
+
+    def _mean_grad_call(self, dev, md, rows, solver):
+        """The device call of the mean gradient; "dense" is the call as it always was."""
+        columns = self._mean_gradient_columns(dev, md)
+        if solver == "dense":
+            return dev.loglike_mean_grad(md, rows, columns)
+        return dev.loglike_mean_grad(md, rows, columns, solver=solver)
+
+    def log_likelihood_mean_gradient(self, solver=None):
         """``(lnL, {label: d lnL / d label})`` of the current state for the labels of :attr:`mean_gradient_labels`: the analytic
         gradient of :meth:`log_likelihood` (no priors) in vsini, vz, log_scale, Av, the Chebyshev coefficients and the grid
         parameters, from the likelihood's factorisation and one solve with 1 + m right-hand sides.  Raises as
-        :meth:`log_likelihood` does; the model's state is not modified."""
+        :meth:`log_likelihood` does; the model's state is not modified.  ``solver``: ``None`` / "dense" the dense factor, "banded" /
+        "auto" the band + Woodbury solver with a backward sweep (:meth:`DeviceOrder.loglike_mean_grad`)."""
+        solver = self._gradient_solver(solver)
         dev, md, rows = self._pack(update_caches=False)
-        out = self._own(dev.loglike_mean_grad(md, rows, self._mean_gradient_columns(dev, md)))
+        out = self._own(self._mean_grad_call(dev, md, rows, solver))
         return float(out["lnl"]), dict(zip(self.mean_gradient_labels, (float(v) for v in out["grad"])))
 
-    def log_likelihood_mean_gradient_batch(self, P, return_info=False):
+    def log_likelihood_mean_gradient_batch(self, P, return_info=False, solver=None):
         """:meth:`log_likelihood_mean_gradient` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device
         pass: ``(lnL (B,), grad (B, len(mean_gradient_labels)))``.  Walkers that fail get ``-inf`` and a NaN row, ``info`` their
-        codes.  The model's own state is not modified."""
+        codes.  The model's own state is not modified.  ``solver``: as for :meth:`log_likelihood_mean_gradient`."""
+        solver = self._gradient_solver(solver)
         P = np.atleast_2d(np.asarray(P, dtype=np.float64))
         dev, md, rows = self._pack(P, update_caches=False)
-        out = dev.loglike_mean_grad(md, rows, self._mean_gradient_columns(dev, md))
+        out = self._mean_grad_call(dev, md, rows, solver)
         lnl = np.where(out["info"] == 0, out["lnl"], -np.inf)
         return (lnl, out["grad"], out["info"]) if return_info else (lnl, out["grad"])
 
-    def log_likelihood_full_gradient_batch(self, P, return_info=False, one_pass=False):
+    def log_likelihood_full_gradient_batch(self, P, return_info=False, one_pass=False, solver=None):
         """``(lnL (B,), grad (B, len(labels)))``: the gradient in every thawed label, columns in :attr:`labels` order -- the mean
         call's columns and, where covariance labels are thawed, :meth:`log_likelihood_gradient_batch`'s (two device calls).  A
         thawed ``Rv`` gets a zero column: it is never passed on.
 
         ``one_pass=True``: both parts from ONE factorisation per walker (sf_loglike_multi_grad_batch_md with one segment)
-        instead of one per call; the values agree with the default's to rounding, not bit for bit."""
+        instead of one per call; the values agree with the default's to rounding, not bit for bit.
+
+        ``solver``: as for :meth:`log_likelihood_mean_gradient`, for the mean columns; the covariance columns always come from the
+        dense factor (and with them ``lnL``, where covariance labels are thawed).  ``one_pass=True`` is the dense factor's: with
+        another solver it raises ``ValueError``."""
+        solver = self._gradient_solver(solver)
+        if one_pass and solver != "dense":
+            raise ValueError('one_pass=True shares ONE dense factorisation: it takes solver=None or "dense" only')
         P = np.atleast_2d(np.asarray(P, dtype=np.float64))
         labels = self.labels
         grad = np.zeros((P.shape[0], len(labels)))
@@ -145,7 +172,7 @@ class Gradients:
             lnl, info = np.where(out["info"] == 0, out["lnl"], -np.inf), out["info"]
             return (lnl, grad, info) if return_info else (lnl, grad)
         if self.mean_gradient_labels:
-            lnl, g, info = self.log_likelihood_mean_gradient_batch(P, return_info=True)
+            lnl, g, info = self.log_likelihood_mean_gradient_batch(P, return_info=True, solver=solver)
             grad[:, [labels.index(key) for key in self.mean_gradient_labels]] = g
         if self.gradient_labels:
             lnl, g, info = self.log_likelihood_gradient_batch(P, return_info=True)
@@ -154,11 +181,13 @@ class Gradients:
             raise ValueError("no thawed parameter to differentiate in")
         return (lnl, grad, info) if return_info else (lnl, grad)
 
-    def _train_gradient(self, priors, kwargs):
-        """The ``gradient=True`` search of :meth:`train`."""
+    def _train_gradient(self, priors, kwargs, solver=None):
+        """The ``gradient=True`` search of :meth:`train`; ``solver``: of the mean columns (``gradient_solver``)."""
+        solver = self._gradient_solver(solver)
+
         def evaluate(x):
             self.set_param_vector(x)
-            lnl, grad, info = self.log_likelihood_full_gradient_batch(x[None, :], return_info=True)
+            lnl, grad, info = self.log_likelihood_full_gradient_batch(x[None, :], return_info=True, solver=solver)
             self._raise_for_info(info[0])
             return lnl[0], grad[0]
 

@@ -341,7 +341,7 @@ class SpectrumModel(ParameterBook, Diagnostics, Gradients):
                 raise RuntimeError(f"{key}'s logpdf evaluated to {log_prob}")
         return priors
 
-    def train(self, priors=None, batch_simplex=True, gradient=False, **kwargs):
+    def train(self, priors=None, batch_simplex=True, gradient=False, *, gradient_solver=None, **kwargs):
         """MAP estimate by Nelder-Mead over :meth:`log_likelihood` (spectrum_model.py:635-696).  ``kwargs`` go to
         ``scipy.optimize.minimize`` as in the reference.
 
@@ -349,7 +349,8 @@ class SpectrumModel(ParameterBook, Diagnostics, Gradients):
         gradient of :meth:`log_likelihood_full_gradient_batch`; priors and their slopes are handled as in
         :meth:`train_covariance`, a point the device flags raises as :meth:`log_likelihood` does, every evaluation leaves the
         model at its point, a run that succeeds or stops at its iteration limit at ``soln.x``; ``batch_simplex`` plays no part then.  Without it the path below is
-        unchanged.
+        unchanged.  ``gradient_solver`` (keyword only, like everything behind it): the solver of the gradient's mean columns (``None`` / "dense", "banded", "auto", as
+        :meth:`log_likelihood_full_gradient_batch` takes it); ``None`` is the dense factor whatever the model's ``solver`` is.
 
         The reference's loop is ~10^3 SERIAL scalar evaluations.  Here (``batch_simplex=True``, a plain Nelder-Mead run:
         no other ``method``, no bounds) the candidate points of every simplex iteration -- reflection, expansion, both
@@ -364,7 +365,7 @@ class SpectrumModel(ParameterBook, Diagnostics, Gradients):
 
         priors = self._checked_priors(priors)
         if gradient:
-            return self._train_gradient(priors, kwargs)
+            return self._train_gradient(priors, kwargs, gradient_solver)
 
         def nll(P):
             self.set_param_vector(P)
