@@ -544,6 +544,38 @@ int sf_loglike_banded_mean_grad_batch(sf_ctx* ctx, const sf_model_desc* model, i
                                       const int* h_slots, int nslots, double* d_lnl, double* d_grad, int grad_stride,
                                       double* d_resid, int* d_info, void* d_work, size_t work_bytes, void* stream);
 
+/* Stand-alone selected inversion, the counterpart of sf_band_solve_batch for the inverse itself: for the same band matrices
+ * returns the entries of Sigma = A^-1 inside the band, d_out[b*out_stride + i*ldo + d] = Sigma[i][i-d] for
+ * 0 <= d <= min(i, halfwidth), i < n (the band storage of d_band; nothing else of d_out is written), and d_logdet[b], by
+ * the keeping sweep and Takahashi's recurrence over its factor, backwards: O(n halfwidth^2) per matrix, exact on the band.
+ * The keeping sweep needs at least one right-hand side: the call feeds it one row of n zeros from the workspace, shared by the
+ * batch, so d_logdet has the bits sf_band_solve_batch gives for these matrices.  d_band is not modified; the workspace
+ * (sf_band_selinv_workspace_bytes; 0 for arguments the call refuses) holds the factor, about n (halfwidth + 48) doubles per
+ * matrix.  d_info[b] (zeroed by the call) = 1-based column of the first non-positive pivot; such a matrix gets NaN in every
+ * entry of its band.  Every half-width the LDS window takes (up to 144).  SF_EINVAL, before anything is enqueued, for a null
+ * pointer, a half-width outside the window or ldb / ldo < halfwidth + 1; SF_ENOMEM for a short workspace.  Never synchronises. */
+size_t sf_band_selinv_workspace_bytes(int n, int halfwidth, int batch);
+int sf_band_selinv_batch(const double* d_band, int n, int halfwidth, int ldb, int64_t stride, int batch, double* d_out, int ldo,
+                         int64_t out_stride, double* d_logdet, int* d_info, void* d_work, size_t work_bytes, void* stream);
+
+/* The likelihood gradient on the band + Woodbury solver in one call: one band fill, one keeping sweep, the capacitance step
+ * and one backward sweep; then the nslots mean-flux columns exactly as sf_loglike_banded_mean_grad_batch makes them (nslots
+ * may be 0, h_slots then NULL) and behind them, with want_cov, the covariance slots of sf_loglike_grad_batch in its order
+ * (log_amp, log_ls of the global kernel if present, then mu, log_amp, log_sigma per local kernel):
+ *     d lnL / d theta = 1/2 sum_{ij on the band} (alpha_i alpha_j - Sigma_ij + (Vs Vs^T)_ij) (dC / d theta)_ij,
+ * C^-1 = Sigma - Vs Vs^T with Sigma = Bd^-1 on the band by selected inversion and Vs = Bd^-1 Y^T L_S^-T; dC / d theta has the
+ * support of the kernel, which lies inside the band.  d_grad[b*grad_stride + j]: j < nslots the mean columns, nslots + q the
+ * covariance slot q.  d_lnl, d_info, d_resid, refusals, SF_INFO_BANDWIDTH and NaN rows as in the mean call;
+ * nslots == 0 without want_cov is SF_EINVAL; beyond sf_banded_window_halfwidth(ctx) SF_EINVAL (use sf_loglike_grad_batch).
+ * Values agree with the dense calls to rounding, not bit for bit; the mean columns, d_lnl and d_info have the bits of
+ * sf_loglike_banded_mean_grad_batch, the covariance columns the same bits whatever mean slots are asked for.  Never
+ * synchronises. */
+size_t sf_loglike_banded_grad_workspace_bytes(const sf_ctx* ctx, const sf_model_desc* model, int B, int halfwidth, int nslots,
+                                              int want_cov);
+int sf_loglike_banded_grad_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, int halfwidth,
+                                 const int* h_slots, int nslots, int want_cov, double* d_lnl, double* d_grad, int grad_stride,
+                                 double* d_resid, int* d_info, void* d_work, size_t work_bytes, void* stream);
+
 /* Timing hooks for bench.py (process-global, not thread-safe): when enabled, the batched calls
  * record HIP events on the caller's stream around each stage and around every MFMA update launch.
  * sf_profile_read synchronises those events, returns the milliseconds accumulated since the last

@@ -865,14 +865,59 @@ class DeviceOrder:
 
             return self._run_chunked(name, md, P, max_chunk, workspace_bytes, buffers, args, sliced)
 
-    def loglike_grad(self, md, params, want_flux=False, max_chunk=None):
+    def loglike_grad(self, md, params, want_flux=False, max_chunk=None, solver="dense"):
         """The likelihood and its gradient in the covariance hyper-parameters (sf_loglike_grad_batch).  params: (B, stride)
         rows as for :meth:`loglike`.  Returns dict of numpy arrays: lnl (B,) and info (B,) with :meth:`loglike`'s bits, grad
         (B, slots) with the slots in parameter-row order (log_amp, log_ls of the global kernel if the model has one, then mu,
         log_amp, log_sigma per local kernel), NaN rows where info != 0, and, asked for, flux (B, n).  Chunked and retried
-        like :meth:`apply`."""
+        like :meth:`apply`.
+
+        solver: "dense"  -- the dense factor and the support blocks of its inverse (sf_loglike_grad_batch);
+                "banded" -- band + rank-m Woodbury solve, the band of Bd^-1 by selected inversion and the contraction over
+                            the band (sf_loglike_banded_grad_batch without mean slots): lnl and info as
+                            :meth:`loglike_mean_grad` gives them under "banded", grad agrees with the dense call to rounding;
+                            walkers whose covariance support exceeds the LDS window come back with info = -4;
+                "auto"   -- banded for the walkers whose half-width bound fits the window, dense for the rest."""
+        if solver not in ("dense", "banded", "auto"):
+            raise ValueError("solver must be 'dense', 'banded' or 'auto'")
+        if solver != "dense":
+            return self.loglike_banded_grad(md, params, (), True, want_flux=want_flux, max_chunk=max_chunk, solver=solver)
         return self._run_grad("loglike_grad_batch", md, params, (), R.cov_grad_slots(md),
                               lambda units: self.loglike_grad_workspace_bytes(md, units), want_flux, max_chunk)
+
+    def loglike_banded_grad_workspace_bytes(self, md, B, halfwidth, nslots, want_cov):
+        return self._size_query("loglike_banded_grad_", md, B, halfwidth, nslots, int(bool(want_cov)))
+
+    def loglike_banded_grad(self, md, params, slots, want_cov, want_flux=False, max_chunk=None, solver="banded"):
+        """The likelihood and its gradient on the band solver in one call (sf_loglike_banded_grad_batch): the mean-flux
+        columns ``slots`` as :meth:`loglike_mean_grad` gives them under the same solver (same bits), and behind them, with
+        ``want_cov``, the covariance slots of :meth:`loglike_grad`.  solver: "banded" or "auto", as for
+        :meth:`loglike_mean_grad`; under "auto" the walkers the window does not take go through the two dense calls."""
+        if solver not in ("banded", "auto"):
+            raise ValueError("solver must be 'banded' or 'auto'")
+        slots = [int(v) for v in slots]
+        nslots, want_cov = len(slots), bool(want_cov)
+        if nslots == 0 and not want_cov:
+            raise ValueError("nothing to differentiate: no mean slots and want_cov is false")
+        ncols = nslots + (R.cov_grad_slots(md) if want_cov else 0)
+        h_slots = (C.c_int * max(nslots, 1))(*slots)
+
+        def banded(rows, W):
+            return self._run_grad("loglike_banded_grad_batch", md, rows, (W, h_slots, nslots, int(want_cov)), ncols,
+                                  lambda units: self.loglike_banded_grad_workspace_bytes(md, units, W, nslots, want_cov), want_flux,
+                                  max_chunk)
+
+        def dense(rows):
+            parts = []
+            if nslots:
+                parts.append(self.loglike_mean_grad(md, rows, slots, want_flux=want_flux, max_chunk=max_chunk, solver="dense"))
+            if want_cov:
+                parts.append(self.loglike_grad(md, rows, want_flux=want_flux, max_chunk=max_chunk, solver="dense"))
+            res = dict(parts[0])
+            res["grad"] = np.concatenate([q["grad"] for q in parts], axis=1)
+            return res
+
+        return self._grad_structured(md, params, ncols, banded, dense, want_flux, solver)
 
     def loglike_mean_grad_workspace_bytes(self, md, B, nslots):
         return self._size_query("loglike_mean_grad_", md, B, nslots)
@@ -903,24 +948,37 @@ class DeviceOrder:
                               lambda units: self.loglike_mean_grad_workspace_bytes(md, units, nslots), want_flux, max_chunk)
 
     def _mean_grad_structured(self, md, params, slots, h_slots, want_flux, max_chunk, solver):
-        """:meth:`loglike_mean_grad` on the band solver: the walkers whose host half-width bound fits the LDS window in one
-        group with the group's largest bound (so that chunks of it give the same bits); the rest, and walkers with the
-        internal status, through the dense call under "auto" (the internal status under "banded" too)."""
+        """:meth:`loglike_mean_grad` on the band solver (:meth:`_grad_structured`)."""
+        nslots = len(slots)
+
+        def banded(rows, W):
+            return self._run_grad("loglike_banded_mean_grad_batch", md, rows, (W, h_slots, nslots), nslots,
+                                  lambda units: self.loglike_banded_mean_grad_workspace_bytes(md, units, W, nslots), want_flux,
+                                  max_chunk)
+
+        def dense(rows):
+            return self.loglike_mean_grad(md, rows, slots, want_flux=want_flux, max_chunk=max_chunk, solver="dense")
+
+        return self._grad_structured(md, params, nslots, banded, dense, want_flux, solver)
+
+    def _grad_structured(self, md, params, ncols, banded, dense, want_flux, solver):
+        """A likelihood-and-gradient call on the band solver: the walkers whose host half-width bound fits the LDS window in
+        one group with the group's largest bound (so that chunks of it give the same bits) through ``banded(rows, W)``; the
+        rest, and walkers with the internal status, through ``dense(rows)`` under "auto" (the internal status under "banded"
+        too).  Both return the dict of :meth:`_run_grad` with ``ncols`` gradient columns."""
         torch = _torch()
         rows = params.cpu().numpy() if torch.is_tensor(params) else np.asarray(params, dtype=np.float64)
         rows = np.atleast_2d(rows)
-        B, nslots = rows.shape[0], len(slots)
+        B = rows.shape[0]
         hw = self.halfwidth_bound(md, rows)
         fits = hw <= self.banded_window_halfwidth()
-        out = dict(lnl=np.full(B, -np.inf), grad=np.full((B, nslots), np.nan), info=np.full(B, INFO_BANDWIDTH, dtype=np.int32))
+        out = dict(lnl=np.full(B, -np.inf), grad=np.full((B, ncols), np.nan), info=np.full(B, INFO_BANDWIDTH, dtype=np.int32))
         if want_flux:
             out["flux"] = np.full((B, self.n), np.nan)
         idx = np.nonzero(fits)[0]
         if idx.size:
             W = int(hw[idx].max())
-            got = self._run_grad("loglike_banded_mean_grad_batch", md, rows[idx], (W, h_slots, nslots), nslots,
-                                 lambda units: self.loglike_banded_mean_grad_workspace_bytes(md, units, W, nslots), want_flux,
-                                 max_chunk)
+            got = banded(rows[idx], W)
             if want_flux:  # (the call returns the residual: model minus data)
                 got["flux"] = got["flux"] + self._keep[1][None, :]
             for key, v in got.items():
@@ -935,9 +993,9 @@ class DeviceOrder:
         if solver == "auto":  # too wide for the window -> dense
             rest = np.nonzero(~fits | (out["info"] == INFO_BANDWIDTH) | internal)[0]
         if rest.size:
-            dense = self.loglike_mean_grad(md, rows[rest], slots, want_flux=want_flux, max_chunk=max_chunk, solver="dense")
+            got = dense(rows[rest])
             for key in out:
-                out[key][rest] = dense[key]
+                out[key][rest] = got[key]
         return out
 
     def loglike_device(self, md, P_dev, out_lnl, info=None):

@@ -255,6 +255,17 @@ SIGNATURES = {
         C.c_int,
         [_VP, C.POINTER(ModelDesc), C.c_int, _VP, C.c_int, c_int_p, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_size_t, _VP],
     ),
+    "sf_band_selinv_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sf_band_selinv_batch": (
+        C.c_int,
+        [_VP, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, _VP, C.c_int, C.c_int64, _VP, _VP, _VP, C.c_size_t, _VP],
+    ),
+    "sf_loglike_banded_grad_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sf_loglike_banded_grad_batch": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, C.c_int, c_int_p, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_size_t,
+         _VP],
+    ),
     "sf_debug_clock_probe": (C.c_int, [_VP, C.c_longlong, _VP]),
     "sf_debug_stream_write": (C.c_int, [_VP, C.c_size_t, C.c_double, _VP]),
     "sf_debug_cholesky_sequence": (C.c_int, [C.c_int]),

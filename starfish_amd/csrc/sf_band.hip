@@ -48,6 +48,9 @@
 //   sf_band_woodbury.h  k_woodbury, sf_launch_woodbury
 //   sf_band_solve.h     the full solve x = A^-1 rhs for the mean-flux gradient: k_band_keep (the sweep, which then also stores
 //                       the factor), k_band_back (backward sweep), k_band_mix_matrix / k_band_mix (Woodbury mix), their launchers
+//   sf_band_selinv.h    for the covariance gradient on the band: k_band_selinv (selected inversion: the band of Bd^-1 from the
+//                       kept factor), k_band_vs_matrix (Vs of C^-1 = Bd^-1 - Vs Vs^T through k_band_mix), their launchers (the
+//                       contraction with dC / d theta over the band is sf_fill.hip's, beside the derivative formulas)
 #include "sf_common.h"
 #include "sf_device.h"
 #include "sf_band_shape.h"
@@ -56,3 +59,4 @@
 #include "sf_band_twist.h"
 #include "sf_band_woodbury.h"
 #include "sf_band_solve.h"
+#include "sf_band_selinv.h"

@@ -149,3 +149,28 @@ SFB_HD sfb_back_lds sfb_back_lds_layout(int nbr, int nrb) {
 SFB_HD int sfb_back_nwaves(int nrb) { return SFB_BACK_SPLIT * nrb; }
 SFB_HD int sfb_back_blocks_per_wave(int nbr) { return (nbr - 1 + SFB_BACK_SPLIT - 1) / SFB_BACK_SPLIT; }  // factor blocks a wave holds
 #define SFB_BACK_MAX_BLOCKS 3  // ... at the widest window the LDS admits (nbr = 10)
+
+// ---- selected inversion (sf_band_selinv.h): the band of Sigma = A^-1 from the kept factor, block columns from the last to
+// the first.  k_band_selinv runs one wave per block below the diagonal of a block column (nbr - 1 waves).  Its dynamic LDS,
+// offsets in doubles (blocks of BS doubles, row stride 17):
+//   S  nbr (nbr + 1) / 2 blocks of Sigma, the lower triangle of the window, addressed by the unordered pair of ring slots
+//      {row block % nbr, column block % nbr} as the forward sweep's window (the full square does not fit: the upper half is
+//      read transposed)
+//   G  [nbr - 1] the step's G_I = L_{k+1+I,k} F_k          P  [nbr - 1] the step's products G_I^T Sigma_{k+1+I,k}
+// 158848 bytes at nbr = 10: every half-width the window admits with one block of right-hand sides (144) fits.
+struct sfb_selinv_lds {
+    int S, G, P, doubles;
+    size_t bytes;
+};
+SFB_HD sfb_selinv_lds sfb_selinv_lds_layout(int nbr) {
+    sfb_selinv_lds L;
+    L.S = 0, L.G = L.S + (nbr * (nbr + 1) / 2) * BS, L.P = L.G + (nbr - 1) * BS, L.doubles = L.P + (nbr - 1) * BS;
+    L.bytes = sizeof(double) * (size_t)L.doubles;
+    return L;
+}
+SFB_HD int sfb_selinv_nwaves(int nbr) { return nbr - 1; }
+#define SFB_SELINV_MAX_WAVES 9  // ... at nbr = 10
+SFB_HD bool sfb_selinv_admits(int halfwidth) {  // every half-width of the window: sfb_admit(halfwidth, 1) == SFB_WINDOW
+    return sfb_admit(halfwidth, 1) == SFB_WINDOW && sfb_selinv_lds_layout(sfb_nbr(halfwidth)).bytes <= SFB_LDS_MAX &&
+           sfb_selinv_nwaves(sfb_nbr(halfwidth)) <= SFB_SELINV_MAX_WAVES;
+}

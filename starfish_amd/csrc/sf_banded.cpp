@@ -161,42 +161,71 @@ extern "C" int sf_band_solve_batch(const double* d_band, int n, int halfwidth, i
     return sf_launch_band_back(bs.fac, n, halfwidth, batch, nrhs, d_info, d_x, ldx, x_stride, s);
 }
 
-// ----------------------------------------------------------------------------------- mean-flux gradient on the band solver
-static int banded_mean_grad_counts_ok(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth, bool say) {
-    if (model_ok(c, mdl)) return SF_EINVAL;
-    if (B <= 0 || B > 65535) {
-        if (say) sf_set_error("sf_loglike_banded_mean_grad_batch: B=%d must lie in 1 .. 65535", B);
+// ----------------------------------------------------------------------------------- the stand-alone selected inversion
+static int band_selinv_shape_ok(const char* who, int n, int halfwidth, int batch) {
+    if (n <= 0 || batch <= 0 || halfwidth < 0) {
+        if (who) sf_set_error("%s: n=%d, batch=%d must be positive, halfwidth=%d >= 0", who, n, batch, halfwidth);
         return SF_EINVAL;
     }
-    const int wmax = sf_banded_window_halfwidth(c);
-    if (halfwidth < 0 || halfwidth > wmax) {
-        if (say)
-            sf_set_error("sf_loglike_banded_mean_grad_batch: half-width %d outside [0, %d], the LDS window (use sf_loglike_mean_grad_batch)",
-                         halfwidth, wmax);
+    if (!sfb_selinv_admits(halfwidth)) {
+        if (who) sf_set_error("%s: half-width %d exceeds the LDS window (max %d)", who, halfwidth, sf_band_max_halfwidth(1));
         return SF_EINVAL;
     }
     return SF_OK;
 }
-extern "C" size_t sf_loglike_banded_mean_grad_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth,
-                                                              int nslots) {
-    if (banded_mean_grad_counts_ok(c, mdl, B, halfwidth, false) || nslots < 1 || nslots > SF_MEAN_GRAD_MAX_SLOTS) return 0;
-    return carve_band_grad(c, mdl, B, halfwidth, nslots, nullptr, 0, carve(c, mdl, B, nullptr, 0, false).bytes).bytes;
+extern "C" size_t sf_band_selinv_workspace_bytes(int n, int halfwidth, int batch) {
+    if (band_selinv_shape_ok(nullptr, n, halfwidth, batch)) return 0;
+    return carve_band_selinv(n, halfwidth, batch, nullptr, 0).bytes;
 }
-extern "C" int sf_loglike_banded_mean_grad_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int halfwidth,
-                                                 const int* h_slots, int nslots, double* d_lnl, double* d_grad, int grad_stride,
-                                                 double* d_resid, int* d_info, void* d_work, size_t work_bytes, void* stream) {
-    if (!d_params || !h_slots || !d_lnl || !d_grad || !d_work) {
-        sf_set_error("sf_loglike_banded_mean_grad_batch: d_params, h_slots, d_lnl, d_grad and d_work are required");
+extern "C" int sf_band_selinv_batch(const double* d_band, int n, int halfwidth, int ldb, int64_t stride, int batch, double* d_out, int ldo,
+                                    int64_t out_stride, double* d_logdet, int* d_info, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_band || !d_out || !d_logdet || !d_info || !d_work) {
+        sf_set_error("sf_band_selinv_batch: null pointer");
         return SF_EINVAL;
     }
-    SF_CHECK(banded_mean_grad_counts_ok(c, mdl, B, halfwidth, true));
-    SF_CHECK(mean_slots_ok("sf_loglike_banded_mean_grad_batch", c, mdl, h_slots, nslots, grad_stride));
-    const Work w = carve(c, mdl, B, d_work, work_bytes, false);
-    const BandGradWork g = carve_band_grad(c, mdl, B, halfwidth, nslots, d_work, work_bytes, w.bytes);
+    SF_CHECK(band_selinv_shape_ok("sf_band_selinv_batch", n, halfwidth, batch));
+    if (ldb < halfwidth + 1 || ldo < halfwidth + 1) {
+        sf_set_error("sf_band_selinv_batch: ldb=%d or ldo=%d < halfwidth + 1 (%d)", ldb, ldo, halfwidth + 1);
+        return SF_EINVAL;
+    }
+    const BandSelinvWork bs = carve_band_selinv(n, halfwidth, batch, d_work, work_bytes);
+    SF_CHECK(work_fits(work_bytes, bs.bytes));
+    hipStream_t s = (hipStream_t)stream;
+    SF_HIP(hipMemsetAsync(d_info, 0, sizeof(int) * (size_t)batch, s));
+    SF_HIP(hipMemsetAsync(bs.zero, 0, sizeof(double) * (size_t)n, s));  // the sweep's one right-hand side, shared by the batch
+    sf_band_call k = {};
+    k.band = d_band, k.sband = stride, k.ldb = ldb, k.halfwidth = halfwidth;
+    k.n = n, k.batch = batch;
+    k.r = sf_band_rhs{bs.zero, 0, n, 1, nullptr, 0};
+    k.logdet = d_logdet, k.gram = bs.gram, k.info = d_info;
+    SF_CHECK(sf_launch_band_keep(k, bs.fac, s));
+    return sf_launch_band_selinv(bs.fac, n, halfwidth, batch, 1, d_info, d_out, ldo, out_stride, s);
+}
+
+// ----------------------------------------------------------------------------------- likelihood gradient on the band solver
+// (the mean-flux columns: sf_loglike_banded_mean_grad_batch; with the covariance columns behind them: sf_loglike_banded_grad_batch)
+static int banded_grad_counts_ok(const char* who, const char* dense, const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth,
+                                 bool say) {
+    // (no context is needed to refuse what no window takes; with one, the limit is that of its 1 + m right-hand sides)
+    const int wmax = c && c->n ? sf_banded_window_halfwidth(c) : sf_band_max_halfwidth(1);
+    if (halfwidth < 0 || halfwidth > wmax) {
+        if (say) sf_set_error("%s: half-width %d outside [0, %d], the LDS window (use %s)", who, halfwidth, wmax, dense);
+        return SF_EINVAL;
+    }
+    if (model_ok(c, mdl)) return SF_EINVAL;
+    if (B <= 0 || B > 65535) {
+        if (say) sf_set_error("%s: B=%d must lie in 1 .. 65535", who, B);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+// One band fill, one keeping sweep, the capacitance step and the backward sweep; then the mean columns (nslots > 0) and,
+// behind them, the covariance columns (cv != NULL) of every walker's row of d_grad
+static int banded_grad_run(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int halfwidth, const int* h_slots,
+                           int nslots, const Work& w, const BandGradWork& g, const BandCovGradWork* cv, double* d_lnl, double* d_grad,
+                           int grad_stride, double* d_resid, int* d_info, hipStream_t s) {
     const BandWork& bw = g.bw;
     const AppliedWork& aw = g.aw;
-    SF_CHECK(work_fits(work_bytes, g.bytes));
-    hipStream_t s = (hipStream_t)stream;
     if (use_device(c)) return SF_EHIP;
     prof_count_call();
     // band fill and transforms side by side, as in sf_loglike_banded_batch
@@ -236,19 +265,95 @@ extern "C" int sf_loglike_banded_mean_grad_batch(sf_ctx* c, const sf_model_desc*
         k.logdet = bw.logdet_band, k.gram = bw.gram, k.info = w.info_c;
         SF_CHECK(sf_launch_band_keep(k, g.fac, s));
     }
+    const int64_t sstage = (int64_t)nrhs * c->npad;
     {
         ProfScope ps(s, PS_SOLVE);
         SF_CHECK(sf_launch_woodbury(bw.gram, nrhs, B, bw.logdet_band, w.logdet, w.sqmah, w.info_c, s));
         SF_CHECK(sf_launch_finish(B, w.logdet, w.sqmah, w.info_e, w.info_c, aw.lnl, aw.info, s));
         // T = Bd^-1 [r, Y^T], then [alpha, V] = T M in the staging area
-        SF_CHECK(sf_launch_band_back(g.fac, n16, halfwidth, B, nrhs, aw.info, g.T, c->npad, (int64_t)nrhs * c->npad, s));
+        SF_CHECK(sf_launch_band_back(g.fac, n16, halfwidth, B, nrhs, aw.info, g.T, c->npad, sstage, s));
         SF_CHECK(sf_launch_band_mix(bw.gram, w.Lw, c->m, aw.info, g.T, c->n, c->npad, B, g.M, aw.stage, s));
     }
-    const sf_mean_grad_args ma = mean_grad_kernel_args(c, h_slots, nslots, w, aw, d_grad, grad_stride);
-    SF_CHECK(sf_launch_mean_tangents(broaden_args(c, mdl, B, d_params, w), c->inv_band.as<double>(),
-                                     emu_args(c, mdl, d_params, w, w.mu, nullptr, w.Lw, w.info_e), ma, B, s));
-    SF_CHECK(sf_launch_mean_grad(eval_args(c, mdl, d_params, w), ma, w.zs, c->m * c->M, B, s));
+    if (nslots > 0) {
+        const sf_mean_grad_args ma = mean_grad_kernel_args(c, h_slots, nslots, w, aw, d_grad, grad_stride);
+        SF_CHECK(sf_launch_mean_tangents(broaden_args(c, mdl, B, d_params, w), c->inv_band.as<double>(),
+                                         emu_args(c, mdl, d_params, w, w.mu, nullptr, w.Lw, w.info_e), ma, B, s));
+        SF_CHECK(sf_launch_mean_grad(eval_args(c, mdl, d_params, w), ma, w.zs, c->m * c->M, B, s));
+    }
+    if (cv) {
+        // the band of Sigma = Bd^-1 and Vs of C^-1 = Sigma - Vs Vs^T, then the contraction with dC / d theta over the band
+        SF_CHECK(sf_launch_band_selinv(g.fac, n16, halfwidth, B, nrhs, aw.info, cv->sigma, bw.ldb, (int64_t)n16 * bw.ldb, s));
+        SF_CHECK(sf_launch_band_vs(bw.gram, c->m, aw.info, g.T, c->n, c->npad, B, cv->M2, cv->stage2, s));
+        SF_CHECK(sf_launch_band_cov_grad(fill_args(c, mdl, d_params, w), B, cv->sigma, bw.ldb, (int64_t)n16 * bw.ldb, halfwidth, aw.stage,
+                                         cv->stage2 + c->npad, c->npad, sstage, c->m, aw.info, cv->part, d_grad + nslots, grad_stride, s));
+    }
     SF_HIP(hipMemcpyAsync(d_lnl, aw.lnl, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, s));
     if (d_info) SF_HIP(hipMemcpyAsync(d_info, aw.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
     return SF_OK;
+}
+
+static const char MEAN_NAME[] = "sf_loglike_banded_mean_grad_batch", MEAN_DENSE[] = "sf_loglike_mean_grad_batch";
+extern "C" size_t sf_loglike_banded_mean_grad_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth,
+                                                              int nslots) {
+    if (banded_grad_counts_ok(MEAN_NAME, MEAN_DENSE, c, mdl, B, halfwidth, false) || nslots < 1 || nslots > SF_MEAN_GRAD_MAX_SLOTS)
+        return 0;
+    return carve_band_grad(c, mdl, B, halfwidth, nslots, nullptr, 0, carve(c, mdl, B, nullptr, 0, false).bytes).bytes;
+}
+extern "C" int sf_loglike_banded_mean_grad_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int halfwidth,
+                                                 const int* h_slots, int nslots, double* d_lnl, double* d_grad, int grad_stride,
+                                                 double* d_resid, int* d_info, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_params || !h_slots || !d_lnl || !d_grad || !d_work) {
+        sf_set_error("sf_loglike_banded_mean_grad_batch: d_params, h_slots, d_lnl, d_grad and d_work are required");
+        return SF_EINVAL;
+    }
+    SF_CHECK(banded_grad_counts_ok(MEAN_NAME, MEAN_DENSE, c, mdl, B, halfwidth, true));
+    SF_CHECK(mean_slots_ok(MEAN_NAME, c, mdl, h_slots, nslots, grad_stride));
+    const Work w = carve(c, mdl, B, d_work, work_bytes, false);
+    const BandGradWork g = carve_band_grad(c, mdl, B, halfwidth, nslots, d_work, work_bytes, w.bytes);
+    SF_CHECK(work_fits(work_bytes, g.bytes));
+    return banded_grad_run(c, mdl, B, d_params, halfwidth, h_slots, nslots, w, g, nullptr, d_lnl, d_grad, grad_stride, d_resid, d_info,
+                           (hipStream_t)stream);
+}
+
+static const char GRAD_NAME[] = "sf_loglike_banded_grad_batch", GRAD_DENSE[] = "sf_loglike_grad_batch";
+// what the counts of the combined call must satisfy beyond banded_grad_counts_ok; say == false: silently (the size query)
+static int banded_grad_slots_ok(const sf_model_desc* mdl, int nslots, int want_cov, bool say) {
+    if (nslots < 0 || nslots > SF_MEAN_GRAD_MAX_SLOTS || (nslots == 0 && !want_cov)) {
+        if (say) sf_set_error("%s: nothing to differentiate (nslots=%d must lie in 0 .. %d, and be positive without want_cov)", GRAD_NAME,
+                              nslots, SF_MEAN_GRAD_MAX_SLOTS);
+        return SF_EINVAL;
+    }
+    if (want_cov && sf_cov_grad_slots(mdl->has_global, mdl->n_local) == 0) {
+        if (say) sf_set_error("%s: nothing to differentiate (no global and no local kernel)", GRAD_NAME);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_loglike_banded_grad_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth, int nslots,
+                                                         int want_cov) {
+    if (banded_grad_counts_ok(GRAD_NAME, GRAD_DENSE, c, mdl, B, halfwidth, false) || banded_grad_slots_ok(mdl, nslots, want_cov, false))
+        return 0;
+    return carve_band_cov_grad(c, mdl, B, halfwidth, nslots, want_cov != 0, nullptr, 0, carve(c, mdl, B, nullptr, 0, false).bytes).bytes;
+}
+extern "C" int sf_loglike_banded_grad_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int halfwidth,
+                                            const int* h_slots, int nslots, int want_cov, double* d_lnl, double* d_grad, int grad_stride,
+                                            double* d_resid, int* d_info, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_params || (!h_slots && nslots > 0) || !d_lnl || !d_grad || !d_work) {
+        sf_set_error("sf_loglike_banded_grad_batch: d_params, h_slots (with nslots > 0), d_lnl, d_grad and d_work are required");
+        return SF_EINVAL;
+    }
+    if (nslots == 0 && !want_cov) return banded_grad_slots_ok(nullptr, nslots, want_cov, true);  // (before the context is looked at)
+    SF_CHECK(banded_grad_counts_ok(GRAD_NAME, GRAD_DENSE, c, mdl, B, halfwidth, true));
+    SF_CHECK(banded_grad_slots_ok(mdl, nslots, want_cov, true));
+    if (nslots > 0) SF_CHECK(mean_slots_ok(GRAD_NAME, c, mdl, h_slots, nslots, grad_stride));
+    const int ncols = nslots + (want_cov ? sf_cov_grad_slots(mdl->has_global, mdl->n_local) : 0);
+    if (grad_stride < ncols) {
+        sf_set_error("%s: grad_stride=%d < %d columns", GRAD_NAME, grad_stride, ncols);
+        return SF_EINVAL;
+    }
+    const Work w = carve(c, mdl, B, d_work, work_bytes, false);
+    const BandCovGradWork cv = carve_band_cov_grad(c, mdl, B, halfwidth, nslots, want_cov != 0, d_work, work_bytes, w.bytes);
+    SF_CHECK(work_fits(work_bytes, cv.bytes));
+    return banded_grad_run(c, mdl, B, d_params, halfwidth, h_slots, nslots, w, cv.g, want_cov ? &cv : nullptr, d_lnl, d_grad,
+                           grad_stride, d_resid, d_info, (hipStream_t)stream);
 }

@@ -247,7 +247,7 @@ int sf_launch_global_cov(const double* wave, int n, double amp, double ls, doubl
 int sf_launch_local_cov(const double* wave, int n, double amp, double mu, double sigma, int accumulate,
                         double* out, hipStream_t s);
 
-// sf_band.hip (layers: sf_band_shape.h, sf_band_window.h, sf_band_sweep.h, sf_band_twist.h, sf_band_woodbury.h, sf_band_solve.h): banded
+// sf_band.hip (layers: sf_band_shape.h, sf_band_window.h, sf_band_sweep.h, sf_band_twist.h, sf_band_woodbury.h, sf_band_solve.h, sf_band_selinv.h): banded
 // Cholesky + forward substitution of (1 + m) right-hand sides -> logdet, Gram matrix
 // The right-hand sides of a batch: row r of matrix b at rhs + b * srhs + r * ldr.  Optional separate source for row 0 (the
 // residual lives in its own buffer in the fused path): when rhs0 is given, rows 1.. come from rhs rows 0..
@@ -291,6 +291,18 @@ int sf_launch_band_back(const double* fac, int n, int halfwidth, int batch, int 
                         hipStream_t s);
 int sf_launch_band_mix(const double* gram, const double* Lw, int m, const int* info, const double* T, int n, int npad, int batch,
                        double* Mwork, double* stage, hipStream_t s);
+// sf_band_selinv.h: the band of Sigma = A^-1 from the records of sf_launch_band_keep (same n, halfwidth, nrhs), by selected
+// inversion: out[b * sout + i * ldo + d] = Sigma[i][i - d], 0 <= d <= min(i, halfwidth), i < n (NaN where info[b] != 0); and
+// Vs = T_Y L_S^-T of C^-1 = Sigma - Vs Vs^T in rows 1 .. m of stage2 (the staging layout of sf_launch_band_mix; row 0 is zero)
+int sf_launch_band_selinv(const double* fac, int n, int halfwidth, int batch, int nrhs, const int* info, double* out, int ldo,
+                          int64_t sout, hipStream_t s);
+int sf_launch_band_vs(const double* gram, int m, const int* info, const double* T, int n, int npad, int batch, double* Mwork,
+                      double* stage2, hipStream_t s);
+// sf_fill.hip (sf_band_cov_grad.h): the covariance gradient contracted over the band, slots and part as sf_launch_cov_grad;
+// sigma: the band of Bd^-1 (lds doubles per row, ssigma per matrix); alpha[b * sstage + i]; vs[b * sstage + c * ldv + i], c < m
+int sf_launch_band_cov_grad(const sf_fill_args& f, int batch, const double* sigma, int lds, int64_t ssigma, int halfwidth,
+                            const double* alpha, const double* vs, int ldv, int64_t sstage, int m, const int* info, double* part,
+                            double* grad, int grad_stride, hipStream_t s);
 // sf_chol.hip (sf_chol_band.h): wide bands (beyond the LDS window) as bordered band matrices on the fused panel kernel;
 // c.band is not read: the tiles hold the matrix, nband rows of it
 int sf_launch_potrf_band(const sf_band_call& c, int nband, double* tiles, hipStream_t s);

@@ -219,6 +219,21 @@ static BandSolveWork carve_band_solve(int n, int halfwidth, int batch, int nrhs,
     w.bytes = sf_align_up(k.off, 256);
     return w;
 }
+// sf_band_selinv_batch: the keeping sweep's records for one right-hand side, that right-hand side (n zeros, shared by the batch)
+// and its Gram matrices (one double per matrix)
+struct BandSelinvWork {
+    double *fac, *gram, *zero;
+    size_t bytes;
+};
+static BandSelinvWork carve_band_selinv(int n, int halfwidth, int batch, void* p, size_t cap) {
+    Carve k(p, cap);
+    BandSelinvWork w;
+    w.fac = k.take<double>((size_t)batch * sfb_keep_doubles(n, sfb_nbr(halfwidth), 1));
+    w.gram = k.take<double>((size_t)batch);
+    w.zero = k.take<double>((size_t)n);
+    w.bytes = sf_align_up(k.off, 256);
+    return w;
+}
 // sf_loglike_banded_mean_grad_batch, behind the Work of the same call: the band solver's buffers (carve_band), the mean
 // gradient's (carve_applied with AW_MEAN: the staging area [alpha, V], lnl, info, xs, fin, ...), then fac: the kept factor of
 // the sweep over n16 = n rounded up to whole blocks; T: [B][1 + m][npad] = Bd^-1 [r, Y^T]; M: [B][(1 + m)^2] mix matrices
@@ -240,6 +255,30 @@ static BandGradWork carve_band_grad(const sf_ctx* c, const sf_model_desc* mdl, i
     g.M = k.take<double>((size_t)B * nrhs * nrhs);
     g.bytes = sf_align_up(k.off, 256);
     return g;
+}
+
+// sf_loglike_banded_grad_batch: carve_band_grad's layout, and behind it, for a call that wants the covariance slots, sigma:
+// the band of Bd^-1, [B][n16][bw.ldb]; M2, stage2: the mix matrix of Vs and [0, Vs] in the staging layout [B][1 + m][npad];
+// part: the contraction's partial sums (sf_cov_grad_work_doubles)
+struct BandCovGradWork {
+    BandGradWork g;
+    double *sigma, *M2, *stage2, *part;
+    size_t bytes;
+};
+static BandCovGradWork carve_band_cov_grad(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth, int nslots, bool want_cov,
+                                           void* p, size_t cap, size_t base_bytes) {
+    BandCovGradWork w{};
+    const int nrhs = c->m + 1, n16 = (c->n + 15) / 16 * 16;
+    w.g = carve_band_grad(c, mdl, B, halfwidth, nslots, p, cap, base_bytes);
+    Carve k(p, cap, w.g.bytes);
+    if (want_cov) {
+        w.sigma = k.take<double>((size_t)B * n16 * w.g.bw.ldb);
+        w.M2 = k.take<double>((size_t)B * nrhs * nrhs);
+        w.stage2 = k.take<double>((size_t)B * nrhs * c->npad);
+        w.part = k.take<double>(sf_cov_grad_work_doubles(c->n, mdl->has_global, mdl->n_local, B));
+    }
+    w.bytes = sf_align_up(k.off, 256);
+    return w;
 }
 
 // ------------------------------------------------------------------- multi-order gradient

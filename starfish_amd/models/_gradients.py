@@ -20,28 +20,38 @@ class Gradients:
         (:func:`starfish_amd._rows.cov_grad_slot`)."""
         return [R.cov_grad_slot(md, key) for key in self.gradient_labels]
 
-    def log_likelihood_gradient(self):
+    def _cov_grad_call(self, dev, md, rows, solver):
+        """The device call of the covariance gradient; "dense" is the call as it always was."""
+        if solver == "dense":
+            return dev.loglike_grad(md, rows)
+        return dev.loglike_grad(md, rows, solver=solver)
+
+    def log_likelihood_gradient(self, solver=None):
         """``(lnL, {label: d lnL / d label})`` of the current state for the labels of :attr:`gradient_labels`: the analytic
         gradient of :meth:`log_likelihood` (no priors) in the covariance hyper-parameters, from one factorisation
         (Rasmussen & Williams, GPML, eq. 5.9).  In ``mu`` of a local kernel it is the almost-everywhere derivative: the
         likelihood has a kink wherever two pixels of the patch are equidistant from ``mu``.  Raises as
-        :meth:`log_likelihood` does; the model's state is not modified."""
+        :meth:`log_likelihood` does; the model's state is not modified.  ``solver``: ``None`` / "dense" the dense factor and the
+        support blocks of its inverse, whatever the model's own ``solver`` is; "banded" / "auto" the band + Woodbury solver
+        with the band of the inverse by selected inversion (:meth:`DeviceOrder.loglike_grad`)."""
+        solver = self._gradient_solver(solver)
         labels = self.gradient_labels
         if not labels:
             raise ValueError("no thawed global_cov / local_cov parameter to differentiate in")
         dev, md, rows = self._pack(update_caches=False)
-        out = self._own(dev.loglike_grad(md, rows))
+        out = self._own(self._cov_grad_call(dev, md, rows, solver))
         return float(out["lnl"]), dict(zip(labels, (float(v) for v in out["grad"][self._gradient_slots(md)])))
 
-    def log_likelihood_gradient_batch(self, P, return_info=False):
+    def log_likelihood_gradient_batch(self, P, return_info=False, solver=None):
         """:meth:`log_likelihood_gradient` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device pass:
         ``(lnL (B,), grad (B, len(gradient_labels)))``.  Walkers that fail get ``-inf`` and a NaN row, ``info`` their codes.
-        The model's own state is not modified."""
+        The model's own state is not modified.  ``solver``: as for :meth:`log_likelihood_gradient`."""
+        solver = self._gradient_solver(solver)
         if not self.gradient_labels:
             raise ValueError("no thawed global_cov / local_cov parameter to differentiate in")
         P = np.atleast_2d(np.asarray(P, dtype=np.float64))
         dev, md, rows = self._pack(P, update_caches=False)
-        out = dev.loglike_grad(md, rows)
+        out = self._cov_grad_call(dev, md, rows, solver)
         lnl = np.where(out["info"] == 0, out["lnl"], -np.inf)
         grad = out["grad"][:, self._gradient_slots(md)]
         return (lnl, grad, out["info"]) if return_info else (lnl, grad)
@@ -52,13 +62,14 @@ class Gradients:
         const_lp = sum(prior.logpdf(self[key]) for key, prior in priors.items() if key in self.params and key not in labels)
         return [(i, priors[key]) for i, key in enumerate(labels) if key in priors], const_lp
 
-    def train_covariance(self, priors=None, **kwargs):
+    def train_covariance(self, priors=None, *, gradient_solver=None, **kwargs):
         """MAP estimate of the covariance hyper-parameters alone: ``scipy.optimize.minimize(method="L-BFGS-B", jac=True)``
         over :attr:`gradient_labels` with the analytic gradient of :meth:`log_likelihood_gradient_batch`; every other
         parameter keeps its value.  ``priors`` are checked as :meth:`train` checks them; a prior on an optimised label adds
         its ``logpdf`` and the slope of it by a central difference with step ``eps^(1/3) max(1, |x|)`` (scipy's frozen
-        distributions expose no derivative), priors on other parameters a constant.  ``kwargs`` go to ``minimize``.  On
-        success the model is left at ``soln.x``."""
+        distributions expose no derivative), priors on other parameters a constant.  ``gradient_solver``: ``solver`` of
+        :meth:`log_likelihood_gradient_batch`.  ``kwargs`` go to ``minimize``.  On success the model is left at ``soln.x``."""
+        gradient_solver = self._gradient_solver(gradient_solver)
         priors = self._checked_priors(priors)
         glabels = self.gradient_labels
         if not glabels:
@@ -70,7 +81,7 @@ class Gradients:
         def evaluate(x):  # (the model's state is not touched: x goes into a copy of the full vector)
             row = x_all.copy()
             row[cols] = x
-            lnl, grad, info = self.log_likelihood_gradient_batch(row[None, :], return_info=True)
+            lnl, grad, info = self.log_likelihood_gradient_batch(row[None, :], return_info=True, solver=gradient_solver)
             self._raise_for_info(info[0])
             return lnl[0], grad[0]
 
@@ -104,7 +115,7 @@ class Gradients:
 
     @staticmethod
     def _gradient_solver(solver):
-        """``solver`` of the mean-gradient methods as :meth:`DeviceOrder.loglike_mean_grad` takes it.  ``None`` is "dense",
+        """``solver`` of the gradient methods as :meth:`DeviceOrder.loglike_mean_grad` / ``loglike_grad`` take it.  ``None`` is "dense",
         whatever the model's own ``solver`` is: a model built with ``solver="auto"`` keeps the dense gradient's bits unless the
         caller asks for the band solver."""
         solver = "dense" if solver is None else solver
@@ -141,7 +152,7 @@ class Gradients:
         lnl = np.where(out["info"] == 0, out["lnl"], -np.inf)
         return (lnl, out["grad"], out["info"]) if return_info else (lnl, out["grad"])
 
-    def log_likelihood_full_gradient_batch(self, P, return_info=False, one_pass=False, solver=None):
+    def log_likelihood_full_gradient_batch(self, P, return_info=False, one_pass=False, solver=None, covariance_solver=None):
         """``(lnL (B,), grad (B, len(labels)))``: the gradient in every thawed label, columns in :attr:`labels` order -- the mean
         call's columns and, where covariance labels are thawed, :meth:`log_likelihood_gradient_batch`'s (two device calls).  A
         thawed ``Rv`` gets a zero column: it is never passed on.
@@ -149,12 +160,15 @@ class Gradients:
         ``one_pass=True``: both parts from ONE factorisation per walker (sf_loglike_multi_grad_batch_md with one segment)
         instead of one per call; the values agree with the default's to rounding, not bit for bit.
 
-        ``solver``: as for :meth:`log_likelihood_mean_gradient`, for the mean columns; the covariance columns always come from the
-        dense factor (and with them ``lnL``, where covariance labels are thawed).  ``one_pass=True`` is the dense factor's: with
-        another solver it raises ``ValueError``."""
+        ``solver``: as for :meth:`log_likelihood_mean_gradient`, for the mean columns.  ``covariance_solver``: as for
+        :meth:`log_likelihood_gradient`, for the covariance columns (and with them ``lnL``, where covariance labels are
+        thawed); ``None`` is the dense factor whatever ``solver`` is.  Where both are "banded" or both "auto" and both kinds of
+        label are thawed, everything comes from ONE device call on the band solver (sf_loglike_banded_grad_batch), with the
+        bits of the two separate calls.  ``one_pass=True`` is the dense factor's: with another solver it raises ``ValueError``."""
         solver = self._gradient_solver(solver)
-        if one_pass and solver != "dense":
-            raise ValueError('one_pass=True shares ONE dense factorisation: it takes solver=None or "dense" only')
+        covariance_solver = self._gradient_solver(covariance_solver)
+        if one_pass and (solver != "dense" or covariance_solver != "dense"):
+            raise ValueError('one_pass=True shares ONE dense factorisation: it takes solver / covariance_solver None or "dense" only')
         P = np.atleast_2d(np.asarray(P, dtype=np.float64))
         labels = self.labels
         grad = np.zeros((P.shape[0], len(labels)))
@@ -171,23 +185,34 @@ class Gradients:
                 grad[:, [labels.index(key) for key in cov]] = out["grad"][:, [len(columns) + s for s in self._gradient_slots(md)]]
             lnl, info = np.where(out["info"] == 0, out["lnl"], -np.inf), out["info"]
             return (lnl, grad, info) if return_info else (lnl, grad)
+        if solver == covariance_solver != "dense" and self.mean_gradient_labels and self.gradient_labels:
+            mean, cov = self.mean_gradient_labels, self.gradient_labels
+            dev, md, rows = self._pack(P, update_caches=False)
+            columns = self._mean_gradient_columns(dev, md)
+            out = dev.loglike_banded_grad(md, rows, columns, True, solver=solver)
+            grad[:, [labels.index(key) for key in mean]] = out["grad"][:, :len(columns)]
+            grad[:, [labels.index(key) for key in cov]] = out["grad"][:, [len(columns) + s for s in self._gradient_slots(md)]]
+            lnl, info = np.where(out["info"] == 0, out["lnl"], -np.inf), out["info"]
+            return (lnl, grad, info) if return_info else (lnl, grad)
         if self.mean_gradient_labels:
             lnl, g, info = self.log_likelihood_mean_gradient_batch(P, return_info=True, solver=solver)
             grad[:, [labels.index(key) for key in self.mean_gradient_labels]] = g
         if self.gradient_labels:
-            lnl, g, info = self.log_likelihood_gradient_batch(P, return_info=True)
+            lnl, g, info = self.log_likelihood_gradient_batch(P, return_info=True, solver=covariance_solver)
             grad[:, [labels.index(key) for key in self.gradient_labels]] = g
         if lnl is None:
             raise ValueError("no thawed parameter to differentiate in")
         return (lnl, grad, info) if return_info else (lnl, grad)
 
-    def _train_gradient(self, priors, kwargs, solver=None):
-        """The ``gradient=True`` search of :meth:`train`; ``solver``: of the mean columns (``gradient_solver``)."""
-        solver = self._gradient_solver(solver)
+    def _train_gradient(self, priors, kwargs, solver=None, covariance_solver=None):
+        """The ``gradient=True`` search of :meth:`train`; ``solver``: of the mean columns (``gradient_solver``),
+        ``covariance_solver``: of the covariance columns."""
+        solver, covariance_solver = self._gradient_solver(solver), self._gradient_solver(covariance_solver)
 
         def evaluate(x):
             self.set_param_vector(x)
-            lnl, grad, info = self.log_likelihood_full_gradient_batch(x[None, :], return_info=True, solver=solver)
+            lnl, grad, info = self.log_likelihood_full_gradient_batch(x[None, :], return_info=True, solver=solver,
+                                                                       covariance_solver=covariance_solver)
             self._raise_for_info(info[0])
             return lnl[0], grad[0]
 

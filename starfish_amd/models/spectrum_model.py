@@ -341,7 +341,7 @@ class SpectrumModel(ParameterBook, Diagnostics, Gradients):
                 raise RuntimeError(f"{key}'s logpdf evaluated to {log_prob}")
         return priors
 
-    def train(self, priors=None, batch_simplex=True, gradient=False, *, gradient_solver=None, **kwargs):
+    def train(self, priors=None, batch_simplex=True, gradient=False, *, gradient_solver=None, covariance_solver=None, **kwargs):
         """MAP estimate by Nelder-Mead over :meth:`log_likelihood` (spectrum_model.py:635-696).  ``kwargs`` go to
         ``scipy.optimize.minimize`` as in the reference.
 
@@ -351,6 +351,7 @@ class SpectrumModel(ParameterBook, Diagnostics, Gradients):
         model at its point, a run that succeeds or stops at its iteration limit at ``soln.x``; ``batch_simplex`` plays no part then.  Without it the path below is
         unchanged.  ``gradient_solver`` (keyword only, like everything behind it): the solver of the gradient's mean columns (``None`` / "dense", "banded", "auto", as
         :meth:`log_likelihood_full_gradient_batch` takes it); ``None`` is the dense factor whatever the model's ``solver`` is.
+        ``covariance_solver``: the same for the gradient's covariance columns (its ``covariance_solver``).
 
         The reference's loop is ~10^3 SERIAL scalar evaluations.  Here (``batch_simplex=True``, a plain Nelder-Mead run:
         no other ``method``, no bounds) the candidate points of every simplex iteration -- reflection, expansion, both
@@ -365,7 +366,7 @@ class SpectrumModel(ParameterBook, Diagnostics, Gradients):
 
         priors = self._checked_priors(priors)
         if gradient:
-            return self._train_gradient(priors, kwargs, gradient_solver)
+            return self._train_gradient(priors, kwargs, gradient_solver, covariance_solver)
 
         def nll(P):
             self.set_param_vector(P)
