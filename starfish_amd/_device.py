@@ -208,6 +208,45 @@ def band_halfwidth_bound(wave, rows, n_grid, has_global, n_local, n_cheb):
     return np.minimum(hw, big).astype(np.int64)
 
 
+def check_solver(solver, choices=("dense", "banded", "auto"), or_none=False):
+    """``ValueError`` unless ``solver`` is one of ``choices`` (``or_none``: the message offers None too, which the caller has
+    already replaced by its default)."""
+    if solver not in choices:
+        names = ["None"] * or_none + [repr(c) for c in choices]
+        raise ValueError(f"solver must be {', '.join(names[:-1])} or {names[-1]}")
+
+
+def refused_output(B, shapes):
+    """What the band solver's dispatchers start from: every one of ``B`` walkers refused with INFO_BANDWIDTH -- ``lnl`` -inf,
+    ``info`` -4, NaN in every other result (``shapes``: key -> trailing shape)."""
+    out = dict(lnl=np.full(B, -np.inf))
+    out.update({key: np.full((B,) + tuple(shape), np.nan) for key, shape in shapes.items()})
+    out["info"] = np.full(B, INFO_BANDWIDTH, dtype=np.int32)
+    return out
+
+
+def finish_structured(out, fits, solver, dense):
+    """THE tail of the band solver's dispatchers, once the banded groups' results are in ``out`` (:func:`refused_output`
+    elsewhere).  An internal wait timeout of the sweep (-5, not expected: the bound keeps a logic error from hanging the GPU) is
+    recomputed by the dense solver -- under "banded" too -- instead of silently turning into a rejected walker; under "auto" so
+    are the walkers whose bound does not fit (``~fits``) and those the kernels flagged with -4.  ``dense(rest)`` gets their
+    ascending indices, once, and returns the keys of ``out`` for them.  The warning names the caller's frame."""
+    internal = out["info"] == INFO_INTERNAL
+    if internal.any():
+        import warnings
+
+        warnings.warn(f"banded solver: internal status -5 for {int(internal.sum())} walker(s); recomputed densely",
+                      RuntimeWarning, stacklevel=2)
+    rest = np.nonzero(internal)[0]
+    if solver == "auto":  # too wide for the banded kernels -> dense
+        rest = np.nonzero(~fits | (out["info"] == INFO_BANDWIDTH) | internal)[0]
+    if rest.size:
+        got = dense(rest)
+        for key in out:
+            out[key][rest] = got[key]
+    return out
+
+
 def factor_v11(v11, w_hat):
     """Init-time constants of the emulator conditional (the reference solves with the constant v11 on every call,
     emulator.py:387-388): Linv = inverse of the lower Cholesky factor of v11 and alpha = v11^-1 w_hat, by LAPACK on
@@ -648,6 +687,12 @@ class DeviceOrder:
                    ws=self._work_banded(md, B, halfwidth))
 
     # ------------------------------------------------------------------ batched calls
+    def _host_rows_and_bound(self, md, params):
+        """Parameter rows (numpy or tensor) as a (B, stride) float64 host array, and :meth:`halfwidth_bound` of them."""
+        rows = params.cpu().numpy() if _torch().is_tensor(params) else np.asarray(params, dtype=np.float64)
+        rows = np.atleast_2d(rows)
+        return rows, self.halfwidth_bound(md, rows)
+
     def _rows(self, params):
         """Parameter rows ((B, stride) float64, numpy or tensor) on the order's device."""
         return params if _torch().is_tensor(params) else to_dev(params, self.dev)
@@ -671,8 +716,7 @@ class DeviceOrder:
                             covariance support exceeds the window come back with info = -4;
                 "auto"   -- banded for the walkers whose half-width bound fits, dense for the rest."""
         torch = _torch()
-        if solver not in ("dense", "banded", "auto"):
-            raise ValueError("solver must be 'dense', 'banded' or 'auto'")
+        check_solver(solver)
         if solver != "dense":
             return self._loglike_structured(md, params, want_resid, max_chunk, solver)
         with torch.cuda.device(self.dev):
@@ -695,18 +739,10 @@ class DeviceOrder:
         banded calls on the current stream -- no host synchronisation.  :meth:`structured_collect` (after the stream
         is done) fetches the results; callers with several orders enqueue them all first (EchelleModel)."""
         torch = _torch()
-        rows = params.cpu().numpy() if torch.is_tensor(params) else np.asarray(params, dtype=np.float64)
-        rows = np.atleast_2d(rows)
-        B = rows.shape[0]
-        wmax = self.banded_max_halfwidth()
-        hw = self.halfwidth_bound(md, rows)
-        fits = hw <= wmax  # (solver="banded": the walkers that do not fit are reported with info = -4)
-        out = dict(
-            lnl=np.full(B, -np.inf), logdet=np.full(B, np.nan), sqmah=np.full(B, np.nan),
-            log_scale=np.full(B, np.nan), info=np.full(B, INFO_BANDWIDTH, dtype=np.int32),
-        )
-        if want_resid:
-            out["resid"] = np.full((B, self.n), np.nan)
+        rows, hw = self._host_rows_and_bound(md, params)
+        fits = hw <= self.banded_max_halfwidth()  # (solver="banded": the walkers that do not fit are reported with info = -4)
+        shapes = dict(logdet=(), sqmah=(), log_scale=(), **({"resid": (self.n,)} if want_resid else {}))
+        out = refused_output(rows.shape[0], shapes)
         groups = []
         # two groups: the cost of the wide-band factorisation grows with the half-width, so the walkers that fit the
         # LDS window are not dragged along with the wide ones
@@ -735,26 +771,12 @@ class DeviceOrder:
         return dict(out=out, groups=groups, fits=fits, rows=rows, want_resid=want_resid, max_chunk=max_chunk)
 
     def structured_collect(self, md, pend, solver):
-        out, rows, fits, want_resid = pend["out"], pend["rows"], pend["fits"], pend["want_resid"]
+        out, rows = pend["out"], pend["rows"]
         for idx, quad, info, resid, _ in pend["groups"]:
             for key, v in fetch_results(quad, info, resid).items():
                 out[key][idx] = v
-        # an internal wait timeout of the sweep (-5, not expected: the bound keeps a logic error from hanging the GPU) is
-        # recomputed by the dense solver -- under "banded" too -- instead of silently turning into a rejected walker
-        internal = out["info"] == INFO_INTERNAL
-        if internal.any():
-            import warnings
-
-            warnings.warn(f"banded solver: internal status -5 for {int(internal.sum())} walker(s); recomputed densely",
-                          RuntimeWarning)
-        rest = np.nonzero(internal)[0]
-        if solver == "auto":  # too wide for the banded kernels -> dense
-            rest = np.nonzero(~fits | (out["info"] == INFO_BANDWIDTH) | internal)[0]
-        if rest.size:
-            dense = self.loglike(md, rows[rest], want_resid=want_resid, max_chunk=pend["max_chunk"], solver="dense")
-            for key in out:
-                out[key][rest] = dense[key]
-        return out
+        return finish_structured(out, pend["fits"], solver, lambda rest: self.loglike(
+            md, rows[rest], want_resid=pend["want_resid"], max_chunk=pend["max_chunk"], solver="dense"))
 
     def apply_workspace_bytes(self, md, B, nrhs):
         return self._size_query("apply_", md, B, nrhs)
@@ -878,8 +900,7 @@ class DeviceOrder:
                             :meth:`loglike_mean_grad` gives them under "banded", grad agrees with the dense call to rounding;
                             walkers whose covariance support exceeds the LDS window come back with info = -4;
                 "auto"   -- banded for the walkers whose half-width bound fits the window, dense for the rest."""
-        if solver not in ("dense", "banded", "auto"):
-            raise ValueError("solver must be 'dense', 'banded' or 'auto'")
+        check_solver(solver)
         if solver != "dense":
             return self.loglike_banded_grad(md, params, (), True, want_flux=want_flux, max_chunk=max_chunk, solver=solver)
         return self._run_grad("loglike_grad_batch", md, params, (), R.cov_grad_slots(md),
@@ -893,31 +914,11 @@ class DeviceOrder:
         columns ``slots`` as :meth:`loglike_mean_grad` gives them under the same solver (same bits), and behind them, with
         ``want_cov``, the covariance slots of :meth:`loglike_grad`.  solver: "banded" or "auto", as for
         :meth:`loglike_mean_grad`; under "auto" the walkers the window does not take go through the two dense calls."""
-        if solver not in ("banded", "auto"):
-            raise ValueError("solver must be 'banded' or 'auto'")
+        check_solver(solver, ("banded", "auto"))
         slots = [int(v) for v in slots]
-        nslots, want_cov = len(slots), bool(want_cov)
-        if nslots == 0 and not want_cov:
+        if not slots and not want_cov:
             raise ValueError("nothing to differentiate: no mean slots and want_cov is false")
-        ncols = nslots + (R.cov_grad_slots(md) if want_cov else 0)
-        h_slots = (C.c_int * max(nslots, 1))(*slots)
-
-        def banded(rows, W):
-            return self._run_grad("loglike_banded_grad_batch", md, rows, (W, h_slots, nslots, int(want_cov)), ncols,
-                                  lambda units: self.loglike_banded_grad_workspace_bytes(md, units, W, nslots, want_cov), want_flux,
-                                  max_chunk)
-
-        def dense(rows):
-            parts = []
-            if nslots:
-                parts.append(self.loglike_mean_grad(md, rows, slots, want_flux=want_flux, max_chunk=max_chunk, solver="dense"))
-            if want_cov:
-                parts.append(self.loglike_grad(md, rows, want_flux=want_flux, max_chunk=max_chunk, solver="dense"))
-            res = dict(parts[0])
-            res["grad"] = np.concatenate([q["grad"] for q in parts], axis=1)
-            return res
-
-        return self._grad_structured(md, params, ncols, banded, dense, want_flux, solver)
+        return self._banded_grad(md, params, slots, want_cov, want_flux, max_chunk, solver)
 
     def loglike_mean_grad_workspace_bytes(self, md, B, nslots):
         return self._size_query("loglike_mean_grad_", md, B, nslots)
@@ -937,66 +938,58 @@ class DeviceOrder:
                             grad agree with the dense call to rounding, not bit for bit;
                             walkers whose covariance support exceeds the LDS window come back with info = -4;
                 "auto"   -- banded for the walkers whose half-width bound fits the window, dense for the rest."""
-        if solver not in ("dense", "banded", "auto"):
-            raise ValueError("solver must be 'dense', 'banded' or 'auto'")
+        check_solver(solver)
+        if solver != "dense":
+            return self._banded_grad(md, params, slots, False, want_flux, max_chunk, solver)
         slots = [int(v) for v in slots]
         nslots = len(slots)
         h_slots = (C.c_int * max(nslots, 1))(*slots)
-        if solver != "dense":
-            return self._mean_grad_structured(md, params, slots, h_slots, want_flux, max_chunk, solver)
         return self._run_grad("loglike_mean_grad_batch", md, params, (h_slots, nslots), nslots,
                               lambda units: self.loglike_mean_grad_workspace_bytes(md, units, nslots), want_flux, max_chunk)
 
-    def _mean_grad_structured(self, md, params, slots, h_slots, want_flux, max_chunk, solver):
-        """:meth:`loglike_mean_grad` on the band solver (:meth:`_grad_structured`)."""
-        nslots = len(slots)
+    def _banded_grad(self, md, params, slots, want_cov, want_flux, max_chunk, solver):
+        """The mean columns ``slots`` and, with ``want_cov``, the covariance slots behind them on the band solver
+        (:meth:`_grad_structured`): a mean-only request is sf_loglike_banded_mean_grad_batch, one with covariance columns
+        sf_loglike_banded_grad_batch; the walkers that go to the dense solver go through its two calls."""
+        slots = [int(v) for v in slots]
+        nslots, want_cov = len(slots), bool(want_cov)
+        ncols = nslots + (R.cov_grad_slots(md) if want_cov else 0)
+        h_slots = (C.c_int * max(nslots, 1))(*slots)
+        call, tail = ("loglike_banded_grad_", (1,)) if want_cov else ("loglike_banded_mean_grad_", ())
+        size_query = getattr(self, call + "workspace_bytes")
 
         def banded(rows, W):
-            return self._run_grad("loglike_banded_mean_grad_batch", md, rows, (W, h_slots, nslots), nslots,
-                                  lambda units: self.loglike_banded_mean_grad_workspace_bytes(md, units, W, nslots), want_flux,
-                                  max_chunk)
+            return self._run_grad(call + "batch", md, rows, (W, h_slots, nslots, *tail), ncols,
+                                  lambda units: size_query(md, units, W, nslots, *tail), want_flux, max_chunk)
 
         def dense(rows):
-            return self.loglike_mean_grad(md, rows, slots, want_flux=want_flux, max_chunk=max_chunk, solver="dense")
+            parts = []
+            if nslots:
+                parts.append(self.loglike_mean_grad(md, rows, slots, want_flux=want_flux, max_chunk=max_chunk, solver="dense"))
+            if want_cov:
+                parts.append(self.loglike_grad(md, rows, want_flux=want_flux, max_chunk=max_chunk, solver="dense"))
+            res = dict(parts[0])
+            res["grad"] = np.concatenate([q["grad"] for q in parts], axis=1)
+            return res
 
-        return self._grad_structured(md, params, nslots, banded, dense, want_flux, solver)
+        return self._grad_structured(md, params, ncols, banded, dense, want_flux, solver)
 
     def _grad_structured(self, md, params, ncols, banded, dense, want_flux, solver):
         """A likelihood-and-gradient call on the band solver: the walkers whose host half-width bound fits the LDS window in
         one group with the group's largest bound (so that chunks of it give the same bits) through ``banded(rows, W)``; the
         rest, and walkers with the internal status, through ``dense(rows)`` under "auto" (the internal status under "banded"
-        too).  Both return the dict of :meth:`_run_grad` with ``ncols`` gradient columns."""
-        torch = _torch()
-        rows = params.cpu().numpy() if torch.is_tensor(params) else np.asarray(params, dtype=np.float64)
-        rows = np.atleast_2d(rows)
-        B = rows.shape[0]
-        hw = self.halfwidth_bound(md, rows)
+        too: :func:`finish_structured`).  Both return the dict of :meth:`_run_grad` with ``ncols`` gradient columns."""
+        rows, hw = self._host_rows_and_bound(md, params)
         fits = hw <= self.banded_window_halfwidth()
-        out = dict(lnl=np.full(B, -np.inf), grad=np.full((B, ncols), np.nan), info=np.full(B, INFO_BANDWIDTH, dtype=np.int32))
-        if want_flux:
-            out["flux"] = np.full((B, self.n), np.nan)
+        out = refused_output(rows.shape[0], dict(grad=(ncols,), **({"flux": (self.n,)} if want_flux else {})))
         idx = np.nonzero(fits)[0]
         if idx.size:
-            W = int(hw[idx].max())
-            got = banded(rows[idx], W)
+            got = banded(rows[idx], int(hw[idx].max()))
             if want_flux:  # (the call returns the residual: model minus data)
                 got["flux"] = got["flux"] + self._keep[1][None, :]
             for key, v in got.items():
                 out[key][idx] = v
-        internal = out["info"] == INFO_INTERNAL
-        if internal.any():
-            import warnings
-
-            warnings.warn(f"banded solver: internal status -5 for {int(internal.sum())} walker(s); recomputed densely",
-                          RuntimeWarning)
-        rest = np.nonzero(internal)[0]
-        if solver == "auto":  # too wide for the window -> dense
-            rest = np.nonzero(~fits | (out["info"] == INFO_BANDWIDTH) | internal)[0]
-        if rest.size:
-            got = dense(rows[rest])
-            for key in out:
-                out[key][rest] = got[key]
-        return out
+        return finish_structured(out, fits, solver, lambda rest: dense(rows[rest]))
 
     def loglike_device(self, md, P_dev, out_lnl, info=None):
         """Enqueue-only variant for bench.py: device tensors in/out, no synchronisation."""

@@ -234,18 +234,22 @@ static BandSelinvWork carve_band_selinv(int n, int halfwidth, int batch, void* p
     w.bytes = sf_align_up(k.off, 256);
     return w;
 }
-// sf_loglike_banded_mean_grad_batch, behind the Work of the same call: the band solver's buffers (carve_band), the mean
-// gradient's (carve_applied with AW_MEAN: the staging area [alpha, V], lnl, info, xs, fin, ...), then fac: the kept factor of
-// the sweep over n16 = n rounded up to whole blocks; T: [B][1 + m][npad] = Bd^-1 [r, Y^T]; M: [B][(1 + m)^2] mix matrices
+// sf_loglike_banded_mean_grad_batch and sf_loglike_banded_grad_batch, behind the Work of the same call: the band solver's
+// buffers (carve_band), the mean gradient's (carve_applied with AW_MEAN: the staging area [alpha, V], lnl, info, xs, fin, ...),
+// then fac: the kept factor of the sweep over n16 = n rounded up to whole blocks; T: [B][1 + m][npad] = Bd^-1 [r, Y^T]; M:
+// [B][(1 + m)^2] mix matrices.  Behind them, for a call that wants the covariance slots (NULL otherwise), sigma: the band of
+// Bd^-1, [B][n16][bw.ldb]; M2, stage2: the mix matrix of Vs and [0, Vs] in the staging layout [B][1 + m][npad]; part: the
+// contraction's partial sums (sf_cov_grad_work_doubles)
 struct BandGradWork {
     BandWork bw;
     AppliedWork aw;
     double *fac, *T, *M;
+    double *sigma, *M2, *stage2, *part;
     size_t bytes;
 };
-static BandGradWork carve_band_grad(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth, int nslots, void* p, size_t cap,
-                                    size_t base_bytes) {
-    BandGradWork g;
+static BandGradWork carve_band_grad(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth, int nslots, bool want_cov, void* p,
+                                    size_t cap, size_t base_bytes) {
+    BandGradWork g{};
     const int nrhs = c->m + 1, n16 = (c->n + 15) / 16 * 16;
     g.bw = carve_band(c, B, halfwidth, p, cap, base_bytes);
     g.aw = carve_applied(c, mdl, B, nrhs, AW_MEAN, p, cap, g.bw.bytes, nslots);
@@ -253,32 +257,14 @@ static BandGradWork carve_band_grad(const sf_ctx* c, const sf_model_desc* mdl, i
     g.fac = k.take<double>((size_t)B * sfb_keep_doubles(n16, sfb_nbr(halfwidth), sfb_nrb(nrhs)));
     g.T = k.take<double>((size_t)B * nrhs * c->npad);
     g.M = k.take<double>((size_t)B * nrhs * nrhs);
+    if (want_cov) {
+        g.sigma = k.take<double>((size_t)B * n16 * g.bw.ldb);
+        g.M2 = k.take<double>((size_t)B * nrhs * nrhs);
+        g.stage2 = k.take<double>((size_t)B * nrhs * c->npad);
+        g.part = k.take<double>(sf_cov_grad_work_doubles(c->n, mdl->has_global, mdl->n_local, B));
+    }
     g.bytes = sf_align_up(k.off, 256);
     return g;
-}
-
-// sf_loglike_banded_grad_batch: carve_band_grad's layout, and behind it, for a call that wants the covariance slots, sigma:
-// the band of Bd^-1, [B][n16][bw.ldb]; M2, stage2: the mix matrix of Vs and [0, Vs] in the staging layout [B][1 + m][npad];
-// part: the contraction's partial sums (sf_cov_grad_work_doubles)
-struct BandCovGradWork {
-    BandGradWork g;
-    double *sigma, *M2, *stage2, *part;
-    size_t bytes;
-};
-static BandCovGradWork carve_band_cov_grad(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth, int nslots, bool want_cov,
-                                           void* p, size_t cap, size_t base_bytes) {
-    BandCovGradWork w{};
-    const int nrhs = c->m + 1, n16 = (c->n + 15) / 16 * 16;
-    w.g = carve_band_grad(c, mdl, B, halfwidth, nslots, p, cap, base_bytes);
-    Carve k(p, cap, w.g.bytes);
-    if (want_cov) {
-        w.sigma = k.take<double>((size_t)B * n16 * w.g.bw.ldb);
-        w.M2 = k.take<double>((size_t)B * nrhs * nrhs);
-        w.stage2 = k.take<double>((size_t)B * nrhs * c->npad);
-        w.part = k.take<double>(sf_cov_grad_work_doubles(c->n, mdl->has_global, mdl->n_local, B));
-    }
-    w.bytes = sf_align_up(k.off, 256);
-    return w;
 }
 
 // ------------------------------------------------------------------- multi-order gradient

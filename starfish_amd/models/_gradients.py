@@ -119,8 +119,7 @@ class Gradients:
         whatever the model's own ``solver`` is: a model built with ``solver="auto"`` keeps the dense gradient's bits unless the
         caller asks for the band solver."""
         solver = "dense" if solver is None else solver
-        if solver not in ("dense", "banded", "auto"):
-            raise ValueError("solver must be None, 'dense', 'banded' or 'auto'")
+        D.check_solver(solver, or_none=True)
         return solver
 
     def _mean_grad_call(self, dev, md, rows, solver):
@@ -152,6 +151,17 @@ class Gradients:
         lnl = np.where(out["info"] == 0, out["lnl"], -np.inf)
         return (lnl, out["grad"], out["info"]) if return_info else (lnl, out["grad"])
 
+    def _scatter_combined(self, grad, md, out, columns):
+        """A combined device result -- the mean ``columns`` in request order (none: ``[]``), then, where covariance labels are
+        thawed, the covariance slots -- into the :attr:`labels`-ordered ``grad``; returns ``(lnl, info)`` with ``-inf`` for the
+        walkers that failed."""
+        labels, ncols = self.labels, len(columns)
+        if columns:
+            grad[:, [labels.index(key) for key in self.mean_gradient_labels]] = out["grad"][:, :ncols]
+        if self.gradient_labels:
+            grad[:, [labels.index(key) for key in self.gradient_labels]] = out["grad"][:, [ncols + s for s in self._gradient_slots(md)]]
+        return np.where(out["info"] == 0, out["lnl"], -np.inf), out["info"]
+
     def log_likelihood_full_gradient_batch(self, P, return_info=False, one_pass=False, solver=None, covariance_solver=None):
         """``(lnL (B,), grad (B, len(labels)))``: the gradient in every thawed label, columns in :attr:`labels` order -- the mean
         call's columns and, where covariance labels are thawed, :meth:`log_likelihood_gradient_batch`'s (two device calls).  A
@@ -179,20 +189,12 @@ class Gradients:
                 raise ValueError("no thawed parameter to differentiate in")
             dev, md, rows = self._pack(P, update_caches=False)
             columns = self._mean_gradient_columns(dev, md) if mean else []
-            out = D.loglike_multi_grad([dev], [md], [rows], [(columns, bool(cov))])[0]
-            grad[:, [labels.index(key) for key in mean]] = out["grad"][:, :len(columns)]
-            if cov:
-                grad[:, [labels.index(key) for key in cov]] = out["grad"][:, [len(columns) + s for s in self._gradient_slots(md)]]
-            lnl, info = np.where(out["info"] == 0, out["lnl"], -np.inf), out["info"]
+            lnl, info = self._scatter_combined(grad, md, D.loglike_multi_grad([dev], [md], [rows], [(columns, bool(cov))])[0], columns)
             return (lnl, grad, info) if return_info else (lnl, grad)
         if solver == covariance_solver != "dense" and self.mean_gradient_labels and self.gradient_labels:
-            mean, cov = self.mean_gradient_labels, self.gradient_labels
             dev, md, rows = self._pack(P, update_caches=False)
             columns = self._mean_gradient_columns(dev, md)
-            out = dev.loglike_banded_grad(md, rows, columns, True, solver=solver)
-            grad[:, [labels.index(key) for key in mean]] = out["grad"][:, :len(columns)]
-            grad[:, [labels.index(key) for key in cov]] = out["grad"][:, [len(columns) + s for s in self._gradient_slots(md)]]
-            lnl, info = np.where(out["info"] == 0, out["lnl"], -np.inf), out["info"]
+            lnl, info = self._scatter_combined(grad, md, dev.loglike_banded_grad(md, rows, columns, True, solver=solver), columns)
             return (lnl, grad, info) if return_info else (lnl, grad)
         if self.mean_gradient_labels:
             lnl, g, info = self.log_likelihood_mean_gradient_batch(P, return_info=True, solver=solver)

@@ -457,6 +457,59 @@ def test_retry_internal_runs_once_when_clean_twice_after_an_abort_and_raises_whe
     assert seen == [False, True] and lib.switched == [0]
 
 
+def test_structured_tail_keeps_the_banded_values_and_sends_the_rest_to_dense_once_in_index_order(recwarn):
+    """finish_structured, the tail the likelihood's and the gradients' band dispatchers share, on stub callbacks: eight walkers,
+    0 2 4 7 served by the banded calls, 1 not fitting (still as refused_output made it), 3 flagged -4 by a kernel, 5 and 6 with
+    the internal status."""
+    from starfish_amd import _device as D
+
+    fits = np.array([True, False, True, True, True, True, True, True])
+    codes = np.array([0, D.INFO_BANDWIDTH, 0, D.INFO_BANDWIDTH, 0, D.INFO_INTERNAL, D.INFO_INTERNAL, -2], dtype=np.int32)
+    rng = np.random.default_rng(8)
+
+    def banded_results():
+        out = D.refused_output(8, dict(grad=(3,), flux=(5,)))
+        assert list(out) == ["lnl", "grad", "flux", "info"] and out["info"].dtype == np.int32 and out["grad"].shape == (8, 3)
+        assert (out["info"] == D.INFO_BANDWIDTH).all() and np.isneginf(out["lnl"]).all()
+        assert np.isnan(out["grad"]).all() and np.isnan(out["flux"]).all()
+        served = np.nonzero(fits)[0]
+        out["lnl"][served], out["grad"][served], out["flux"][served] = rng.random(7), rng.random((7, 3)), rng.random((7, 5))
+        out["info"][:] = codes
+        out["lnl"][3], out["grad"][3] = -np.inf, np.nan
+        return out
+
+    def dense_stub(seen):
+        def dense(rest):
+            seen.append(rest.tolist())
+            return dict(lnl=100.0 + rest, grad=np.repeat(200.0 + rest, 3).reshape(-1, 3), flux=np.repeat(300.0 + rest, 5).reshape(-1, 5),
+                        info=np.zeros(rest.size, dtype=np.int32))
+
+        return dense
+
+    for solver, redone in (("banded", [5, 6]), ("auto", [1, 3, 5, 6])):
+        before, seen = banded_results(), []
+        want = {key: v.copy() for key, v in before.items()}
+        with pytest.warns(RuntimeWarning, match=r"banded solver: internal status -5 for 2 walker\(s\); recomputed densely") as caught:
+            out = D.finish_structured(before, fits, solver, dense_stub(seen))
+        assert len(caught) == 1 and os.path.samefile(caught[0].filename, __file__)  # attributed to the dispatcher that called
+        assert seen == [redone] and out is before
+        kept = np.setdiff1d(np.arange(8), redone)
+        for key in want:  # bit for bit, the NaN and -inf of the refused walkers included
+            assert out[key][kept].tobytes() == want[key][kept].tobytes(), (solver, key)
+        assert out["info"][redone].tolist() == [0] * len(redone) and out["lnl"][redone].tolist() == [100.0 + i for i in redone]
+        assert (out["grad"][redone] == 200.0 + np.array(redone)[:, None]).all()
+        assert (out["flux"][redone] == 300.0 + np.array(redone)[:, None]).all()
+        if solver == "banded":
+            assert out["info"][[1, 3]].tolist() == [D.INFO_BANDWIDTH] * 2 and np.isneginf(out["lnl"][[1, 3]]).all()
+    # nothing to redo: no warning, no dense call
+    clean = D.refused_output(3, dict(logdet=()))
+    clean["info"][:], clean["lnl"][:] = 0, 1.0
+    D.finish_structured(clean, np.ones(3, dtype=bool), "auto", lambda rest: pytest.fail("dense was called"))
+    refused = D.refused_output(3, dict(logdet=()))
+    D.finish_structured(refused, np.zeros(3, dtype=bool), "banded", lambda rest: pytest.fail("dense was called"))
+    assert (refused["info"] == D.INFO_BANDWIDTH).all() and len(recwarn) == 0
+
+
 def _host_order(monkeypatch, free):
     """A DeviceOrder without a device: ``__new__``, host tensors, and ``free`` bytes reported as free HBM."""
     import contextlib
