@@ -484,6 +484,33 @@ int sf_loglike_multi_grad_batch_md(const sf_segment* segs, int nseg, const sf_mo
 int sf_multi_grad_reduce(int nseg, int W, const double* d_unit_lnl, const int* d_unit_info, const double* d_unit_grad,
                          int grad_stride, const int32_t* d_col_ptr, const int32_t* d_col_src, int ncols, double* d_lnl,
                          double* d_grad, int out_stride, int* d_info, void* stream);
+/* sf_loglike_multi_grad_batch_md on the band + Woodbury solver (see the structure-exploiting solver below and
+ * sf_loglike_banded_grad_batch): segs, models, requests, d_lnl, d_log_scale, d_info, d_grad and grad_stride mean exactly what
+ * they mean there -- units in segment order, a unit's row its order's mean slots in request order and then all covariance slots
+ * of its descriptor, NaN rows where d_info[u] != 0, a segment without a request gets lnl / info / log_scale only and its rows
+ * of d_grad are not written.  h_halfwidth (HOST, one int per segment): the band half-width the caller vouches for per segment;
+ * a unit whose support is wider gets d_info[u] = SF_INFO_BANDWIDTH.  No N x N matrix is formed.  Per segment, on the streams
+ * sf_loglike_multi_batch_md runs its chains on: band fill, transform chain, row tangents; once per chunk of segments, over all
+ * its units in one launch each: keeping sweep, capacitance step, backward sweep, mix, and with covariance slots selected
+ * inversion and Vs; then per segment the contractions of sf_loglike_banded_grad_batch with the order's own n.  All units share
+ * ONE frame taken from the whole call (never from a chunk, so a unit's bits do not depend on how a caller cuts its unit list
+ * as long as the frame is the same): the largest n rounded up to 16 rows (shorter orders: identity rows, zero right-hand
+ * sides), the largest npad, the largest half-width (a wider band than a unit needs holds zeros: exact).  A half-width may
+ * exceed an order's length.  lnl and the slots agree with the dense call to rounding, not bit for bit; d_log_scale has its
+ * bits.  Fixed summation order, no atomics in any sum: a repeated call gives the same bits.  The call never synchronises.
+ * SF_EINVAL before anything is enqueued: whatever sf_loglike_multi_grad_batch_md refuses; a null h_halfwidth; a segment whose
+ * wavelength grid is not strictly increasing; a half-width outside [0, sf_banded_window_halfwidth(ctx)] of its segment (the
+ * bordered-tile path has no backward sweep: the message names sf_loglike_multi_grad_batch_md); a segment with more than 65535
+ * units.  SF_ENOMEM: the workspace is too small.  d_work: sf_banded_multi_grad_workspace_bytes_md(...) (0 for bad
+ * arguments): the workspace of sf_loglike_multi_batch_md without its matrices; per unit, in the common frame, the band, the
+ * kept factor (~ n16 (W + 16 + 16) doubles), T and two staging areas of 1 + m rows, and with covariance slots the band of
+ * Bd^-1; per segment what sf_loglike_multi_grad_batch_md keeps per segment. */
+size_t sf_banded_multi_grad_workspace_bytes_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                               const sf_grad_request* requests, const int* h_halfwidth, int grad_stride);
+int sf_loglike_banded_multi_grad_batch_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                          const sf_grad_request* requests, const int* h_halfwidth, double* d_lnl,
+                                          double* d_log_scale, int* d_info, double* d_grad, int grad_stride, void* d_work,
+                                          size_t work_bytes, void* stream);
 
 /* ---- structure-exploiting solver -----------------------------------
  * Same value as sf_loglike_batch, computed without ever forming the N x N matrix: the covariance of

@@ -428,11 +428,15 @@ class MultiGradPlan(MultiPlan):
         arr._keep = self._slot_arrays
         return arr
 
-    def _workspace_bytes(self, segs, nseg, models):
-        """The gradient call's workspace for these segments; they are matched to their orders by context."""
+    def _orders_of(self, segs, nseg):
+        """The orders of these segments, matched by context."""
         by_ctx = {int(o.ctx): i for i, o in enumerate(self.orders)}
         items = [segs[k] for k in range(nseg)] if isinstance(segs, C.Array) else [segs._obj]  # (an array, or byref of one)
-        idxs = [by_ctx[int(seg.ctx)] for seg in items]
+        return [by_ctx[int(seg.ctx)] for seg in items]
+
+    def _workspace_bytes(self, segs, nseg, models):
+        """The gradient call's workspace for these segments."""
+        idxs = self._orders_of(segs, nseg)
         if not any(self.slots[i] for i in idxs):
             return self.lib.sf_multi_workspace_bytes_md(segs, nseg, models)
         return self.lib.sf_multi_grad_workspace_bytes_md(segs, nseg, models, self._requests_array(idxs), self.stride)
@@ -534,6 +538,192 @@ def loglike_multi_grad(orders, mds, rows_list, requests, max_units=None, sync=Tr
     unit, in one enqueue and one host synchronisation (see :class:`MultiGradPlan` for ``mds`` and ``requests``).  Returns
     a list of dicts (lnl, grad, log_scale, info) per order; with ``sync=False`` the un-synchronised plan."""
     plan = MultiGradPlan(orders, mds, rows_list, requests, max_units=max_units)
+    plan.enqueue()
+    return plan.collect() if sync else plan
+
+
+def banded_units(bounds, windows):
+    """Which units of a multi-order gradient the band kernels take: ``bounds[i]`` (B_i,) the half-width bounds of order i's
+    units, ``windows[i]`` its LDS window.  Returns ``fits``, one boolean array per order.  Pure host logic."""
+    return [np.asarray(b) <= int(w) for b, w in zip(bounds, windows)]
+
+
+def rerouted_units(fits, infos, solver):
+    """The rule of :func:`finish_structured` per (order x walker) unit: ``infos[i]`` (B_i,) are the codes the band kernels
+    left (INFO_BANDWIDTH where ``fits[i]`` is false: those units never ran).  Returns per order the ascending walker indices
+    that go through the dense call: units with the internal status -5 under either solver; under "auto" also the units whose
+    bound does not fit and those the kernels flagged -4.  Under "banded" the latter two stay refused.  Pure host logic."""
+    check_solver(solver, ("banded", "auto"))
+    out = []
+    for f, info in zip(fits, infos):
+        info = np.asarray(info)
+        rest = info == INFO_INTERNAL
+        if solver == "auto":
+            rest = rest | ~np.asarray(f) | (info == INFO_BANDWIDTH)
+        out.append(np.nonzero(rest)[0])
+    return out
+
+
+def merge_units(outs, rest, dense):
+    """Put the dense results back by (order, walker): ``outs[i]`` the per-order dicts, ``rest[i]`` the walker indices of order
+    i that were re-routed, ``dense`` the dicts of the dense call for the orders that have any, in order.  In place."""
+    got = iter(dense)
+    for out, idx in zip(outs, rest):
+        if not len(idx):
+            continue
+        res = next(got)
+        for key in out:
+            out[key][idx] = res[key]
+    return outs
+
+
+class _BandedUnits(MultiGradPlan):
+    """The device side of :class:`BandedMultiGradPlan`: the units the band kernels take, every segment with the half-width
+    ``halfwidth`` (sf_loglike_banded_multi_grad_batch_md).  A piece of a cut unit list in which no order requests anything is
+    the plain (dense) multi-order likelihood, as in :class:`MultiGradPlan`."""
+
+    def __init__(self, orders, mds, rows_list, requests, halfwidth, max_units=None):
+        self.halfwidth = int(halfwidth)
+        super().__init__(orders, mds, rows_list, requests, max_units=max_units)
+
+    def _halfwidths(self, nseg):
+        return (C.c_int * nseg)(*([self.halfwidth] * nseg))
+
+    def _workspace_bytes(self, segs, nseg, models):
+        idxs = self._orders_of(segs, nseg)
+        if not any(self.slots[i] for i in idxs):
+            return self.lib.sf_multi_workspace_bytes_md(segs, nseg, models)
+        return self.lib.sf_banded_multi_grad_workspace_bytes_md(segs, nseg, models, self._requests_array(idxs),
+                                                                self._halfwidths(nseg), self.stride)
+
+    def enqueue(self):
+        torch = _torch()
+        with torch.cuda.device(self.dev):
+            s = stream_ptr(self.dev)
+            q = self.quad
+            for (segs, nseg, u0, n, models), piece in zip(self.calls, self.pieces):
+                idxs = [i for i, _, _ in piece]
+                if not any(self.slots[i] for i in idxs):
+                    rc = self.lib.sf_loglike_multi_batch_md(segs, nseg, models, ptr(q[0][u0:u0 + n]), None, None,
+                                                            ptr(q[3][u0:u0 + n]), ptr(self.info[u0:u0 + n]), ptr(self.ws),
+                                                            self.ws.numel(), s)
+                    _lib.check(rc, "sf_loglike_multi_batch_md")
+                    continue
+                rc = self.lib.sf_loglike_banded_multi_grad_batch_md(
+                    segs, nseg, models, self._requests_array(idxs), self._halfwidths(nseg), ptr(q[0][u0:u0 + n]),
+                    ptr(q[3][u0:u0 + n]), ptr(self.info[u0:u0 + n]), ptr(self.grad[u0:u0 + n]), self.stride, ptr(self.ws),
+                    self.ws.numel(), s)
+                _lib.check(rc, "sf_loglike_banded_multi_grad_batch_md")
+
+    def collect(self):
+        """As :meth:`MultiGradPlan.collect`, without its retry: the band sweep's internal status is recomputed densely per
+        unit (:func:`rerouted_units`), not by a second run of the batch."""
+        lnl, log_scale = self.quad[0].cpu().numpy(), self.quad[3].cpu().numpy()
+        info, grad = self.info.cpu().numpy(), self.grad.cpu().numpy()
+        ends = np.cumsum(self.sizes)
+        return [dict(lnl=lnl[hi - n:hi], grad=grad[hi - n:hi, :k], log_scale=log_scale[hi - n:hi], info=info[hi - n:hi])
+                for n, hi, k in zip(self.sizes, ends, self.slots)]
+
+
+class BandedMultiGradPlan:
+    """:class:`MultiGradPlan` on the band + Woodbury solver: the likelihood of every (order x walker) unit and its gradient
+    in every requested slot from one keeping sweep per unit, all units of the device in one launch sequence
+    (sf_loglike_banded_multi_grad_batch_md).  ``orders``, ``mds``, ``rows_list`` (host rows or tensors) and ``requests`` as
+    for :class:`MultiGradPlan`; :meth:`collect` returns the same per-order dicts and :meth:`reduce` the same order sum.
+
+    Every unit's half-width bound is computed on the host (:meth:`DeviceOrder.halfwidth_bound`); the units whose bound fits
+    their order's LDS window form one group, and every segment is given the group's largest bound, so that a unit's bits do
+    not depend on how the unit list is cut.  solver: "banded" -- the other units are refused with INFO_BANDWIDTH (-inf and a
+    NaN row); "auto" -- they, the units the kernels flag -4 and units with the internal status -5 go through the dense
+    :func:`loglike_multi_grad` with just those rows and are merged back by (order, walker).  Status -5 is recomputed densely
+    under "banded" too, with the warning of :func:`finish_structured`."""
+
+    def __init__(self, orders, mds, rows_list, requests, solver="banded", max_units=None):
+        check_solver(solver, ("banded", "auto"))
+        if len(requests) != len(orders):
+            raise ValueError(f"multi-order gradient: {len(requests)} requests for {len(orders)} orders")
+        torch = _torch()
+        self.orders, self.mds, self.solver, self.max_units = list(orders), list(mds), solver, max_units
+        self.requests = [([int(c) for c in cols], bool(cov)) for cols, cov in requests]
+        self.slots = [len(cols) + (R.cov_grad_slots(md) if cov else 0) for (cols, cov), md in zip(self.requests, self.mds)]
+        if not any(self.slots):
+            raise ValueError("multi-order gradient: nothing to differentiate (no order requests a slot)")
+        self.rows = [np.atleast_2d(r.cpu().numpy() if torch.is_tensor(r) else np.asarray(r, dtype=np.float64)) for r in rows_list]
+        self.sizes = [int(r.shape[0]) for r in self.rows]
+        self.bounds = [o.halfwidth_bound(md, r) for o, md, r in zip(self.orders, self.mds, self.rows)]
+        self.fits = banded_units(self.bounds, [o.banded_window_halfwidth() for o in self.orders])
+        self.idx = [np.nonzero(f)[0] for f in self.fits]
+        self.on_device = [i for i, idx in enumerate(self.idx) if idx.size]  # the orders that have a unit for the band kernels
+        self.halfwidth = max((int(self.bounds[i][self.idx[i]].max()) for i in self.on_device), default=0)
+        self.plan = None
+        # (a group in which no order requests a slot has nothing for the gradient call: its units are refused or go dense)
+        if self.on_device and any(self.slots[i] for i in self.on_device):
+            self.plan = _BandedUnits([self.orders[i] for i in self.on_device], [self.mds[i] for i in self.on_device],
+                                     [self.rows[i][self.idx[i]] for i in self.on_device],
+                                     [self.requests[i] for i in self.on_device], self.halfwidth, max_units=max_units)
+        else:
+            self.fits = [np.zeros(n, dtype=bool) for n in self.sizes]
+            self.idx, self.on_device = [np.zeros(0, dtype=np.int64)] * len(self.sizes), []
+        self.complete = all(f.all() for f in self.fits)  # every unit is in the device plan, in unit order
+        self.rerouted = None
+        self._out = None
+
+    @property
+    def units(self):
+        return sum(self.sizes)
+
+    def enqueue(self):
+        """Launch only (no host synchronisation)."""
+        if self.plan is not None:
+            self.plan.enqueue()
+
+    def collect(self):
+        """Per order a dict of numpy arrays: lnl (B,), grad (B, slots of the order), log_scale (B,), info (B,), as
+        :meth:`MultiGradPlan.collect`; refused units have ``-inf``, NaN and INFO_BANDWIDTH."""
+        outs = []
+        for n, k in zip(self.sizes, self.slots):
+            outs.append(refused_output(n, dict(grad=(k,), log_scale=())))
+        if self.plan is not None:
+            for i, got in zip(self.on_device, self.plan.collect()):
+                for key, v in got.items():
+                    outs[i][key][self.idx[i]] = v
+        internal = sum(int(np.count_nonzero(o["info"] == INFO_INTERNAL)) for o in outs)
+        if internal:
+            import warnings
+
+            warnings.warn(f"banded solver: internal status -5 for {internal} unit(s); recomputed densely", RuntimeWarning,
+                          stacklevel=2)
+        rest = rerouted_units(self.fits, [o["info"] for o in outs], self.solver)
+        which = [i for i, idx in enumerate(rest) if len(idx)]
+        self.rerouted = sum(len(idx) for idx in rest)
+        if which:
+            sub = ([self.orders[i] for i in which], [self.mds[i] for i in which], [self.rows[i][rest[i]] for i in which])
+            if any(self.slots[i] for i in which):
+                dense = loglike_multi_grad(*sub, [self.requests[i] for i in which], max_units=self.max_units)
+            else:
+                dense = [dict(o, grad=np.zeros((len(o["lnl"]), 0))) for o in loglike_multi(*sub, max_units=self.max_units)]
+            dense = [{key: d[key] for key in ("lnl", "grad", "log_scale", "info")} for d in dense]
+            merge_units(outs, rest, dense)
+        self._out = outs
+        return outs
+
+    def reduce(self, sources):
+        """The sum over the orders of a collected call, as :meth:`MultiGradPlan.reduce`: on the device
+        (sf_multi_grad_reduce) when every unit ran on the band kernels and none was re-routed, else by
+        :func:`reduce_orders_host` of the collected units -- the same rule, the same bits."""
+        if self._out is None:
+            raise RuntimeError("BandedMultiGradPlan.reduce: collect() first")
+        if len(set(self.sizes)) != 1:
+            raise ValueError(f"sf_multi_grad_reduce: the orders have {sorted(set(self.sizes))} walkers")
+        if self.complete and not self.rerouted:
+            return self.plan.reduce(sources)
+        return reduce_orders_host(np.stack([o["lnl"] for o in self._out]), np.stack([o["info"] for o in self._out]),
+                                  [o["grad"] for o in self._out], sources)
+
+
+def loglike_banded_multi_grad(orders, mds, rows_list, requests, solver="banded", max_units=None, sync=True):
+    """:func:`loglike_multi_grad` on the band solver (:class:`BandedMultiGradPlan`; ``solver``: "banded" or "auto")."""
+    plan = BandedMultiGradPlan(orders, mds, rows_list, requests, solver=solver, max_units=max_units)
     plan.enqueue()
     return plan.collect() if sync else plan
 

@@ -229,6 +229,15 @@ SIGNATURES = {
         [C.POINTER(Segment), C.c_int, C.POINTER(C.POINTER(ModelDesc)), C.POINTER(GradRequest), _VP, _VP, _VP, _VP, C.c_int, _VP,
          C.c_size_t, _VP],
     ),
+    "sf_banded_multi_grad_workspace_bytes_md": (
+        C.c_size_t,
+        [C.POINTER(Segment), C.c_int, C.POINTER(C.POINTER(ModelDesc)), C.POINTER(GradRequest), C.POINTER(C.c_int), C.c_int],
+    ),
+    "sf_loglike_banded_multi_grad_batch_md": (
+        C.c_int,
+        [C.POINTER(Segment), C.c_int, C.POINTER(C.POINTER(ModelDesc)), C.POINTER(GradRequest), C.POINTER(C.c_int), _VP, _VP, _VP,
+         _VP, C.c_int, _VP, C.c_size_t, _VP],
+    ),
     "sf_multi_grad_reduce": (
         C.c_int,
         [C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP],

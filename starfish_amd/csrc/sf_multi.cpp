@@ -7,6 +7,8 @@
 // sf_loglike_multi_grad_batch_md is the same sequence with a gradient part (MultiGradCall): right-hand sides staged behind
 // every order's chain, the factor applied to a whole chunk's staging area at once, and per segment the contractions of the
 // two single-order gradient calls -- one factorisation per unit for the likelihood and its gradient.
+// sf_loglike_banded_multi_grad_batch_md (at the end) is that call on the band + Woodbury solver: no matrices, one launch of
+// each band sweep over all units of a chunk.
 #include <algorithm>
 #include <cstdio>
 #include <string>
@@ -104,17 +106,18 @@ struct MultiGradCall {
 };
 // every per-segment requirement of the two single-order gradient calls, for the segment that requests the part (behind
 // multi_layout: contexts and models are good)
+// call: the entry point the messages name
 static int multi_grad_requests_ok(const sf_segment* segs, int nseg, const sf_model_desc* const* models, const sf_grad_request* reqs,
-                                  int grad_stride) {
+                                  int grad_stride, const char* call = MULTI_GRAD) {
     if (!reqs) {
-        sf_set_error(MULTI_GRAD ": requests are required");
+        sf_set_error("%s: requests are required", call);
         return SF_EINVAL;
     }
     bool any = false;
     for (int i = 0; i < nseg; ++i) {
         const sf_grad_request& r = reqs[i];
         char who[96];
-        snprintf(who, sizeof who, MULTI_GRAD ": segment %d", i);
+        snprintf(who, sizeof who, "%s: segment %d", call, i);
         int slots = 0;
         if (r.n_mean_slots != 0) {
             if (r.n_mean_slots < 0 || !r.h_mean_slots) {
@@ -143,7 +146,7 @@ static int multi_grad_requests_ok(const sf_segment* segs, int nseg, const sf_mod
         any |= slots > 0;
     }
     if (!any) {
-        sf_set_error(MULTI_GRAD ": nothing to differentiate (no segment requests a slot)");
+        sf_set_error("%s: nothing to differentiate (no segment requests a slot)", call);
         return SF_EINVAL;
     }
     return SF_OK;
@@ -348,4 +351,215 @@ extern "C" int sf_multi_grad_reduce(int nseg, int W, const double* d_unit_lnl, c
     a.nseg = nseg, a.W = W, a.grad_stride = grad_stride, a.ncols = ncols, a.out_stride = out_stride;
     a.lnl = d_lnl, a.grad = d_grad, a.info = d_info;
     return sf_launch_multi_grad_reduce(a, (hipStream_t)stream);
+}
+
+// ----------------------------------------------------------------------------------- multi-order gradient on the band solver
+// sf_loglike_banded_multi_grad_batch_md: the launch structure of banded_grad_call (sf_banded.cpp), regrouped as loglike_multi
+// regroups the dense call.  Per segment on its lane: band fill, transform chain, row tangents, into the segment's slice of
+// per-unit arrays with ONE frame (BandMultiFrame); per chunk on the caller's stream, over all its units at once: the keeping
+// sweep, the capacitance step and lnl / info, the backward sweep, the mix and, with covariance slots, the selected inversion
+// and Vs; then per segment the two contractions with the order's own n.
+// The frame is taken from the whole call -- the largest n16, npad and half-width of its segments -- never from a chunk: a
+// shorter order's rows n .. n16 are identity rows of the band (the fill's npad argument) with zero right-hand sides (the
+// transform chain pads its rows to the layout's npad), which add 0 to the log-determinant and the Gram matrix and come out
+// of the backward sweep as zeros; a wider window than a unit needs holds zeros of the band.  No device code of its own.
+#define BANDED_MULTI_GRAD "sf_loglike_banded_multi_grad_batch_md"
+struct BandMultiFrame {
+    Layout L;
+    sf_model_desc uni;
+    int U, bmax, n16, halfwidth;
+};
+static int banded_multi_frame(const sf_segment* segs, int nseg, const sf_model_desc* const* models, const sf_grad_request* reqs,
+                              const int* h_halfwidth, int grad_stride, BandMultiFrame* F) {
+    if (segs && nseg > 0 && models) {
+        if (!h_halfwidth) {
+            sf_set_error(BANDED_MULTI_GRAD ": h_halfwidth (one half-width per segment) is required");
+            return SF_EINVAL;
+        }
+        // (no context is needed to refuse what no window takes; with one, the limit is that of its 1 + m right-hand sides)
+        for (int i = 0; i < nseg; ++i) {
+            const sf_ctx* c = segs[i].ctx;
+            const bool have = c && c->n;
+            if (have && !c->monotonic) {
+                sf_set_error(BANDED_MULTI_GRAD ": segment %d: the banded solver needs a strictly increasing wavelength grid (use %s)",
+                             i, MULTI_GRAD);
+                return SF_EINVAL;
+            }
+            const int wmax = have ? sf_banded_window_halfwidth(c) : sf_band_max_halfwidth(1);
+            if (h_halfwidth[i] < 0 || h_halfwidth[i] > wmax) {
+                sf_set_error(BANDED_MULTI_GRAD ": segment %d: half-width %d outside [0, %d], the LDS window (use %s)", i,
+                             h_halfwidth[i], wmax, MULTI_GRAD);
+                return SF_EINVAL;
+            }
+        }
+    }
+    SF_CHECK(multi_layout(segs, nseg, models, &F->L, &F->U, &F->bmax, &F->uni));
+    SF_CHECK(multi_grad_requests_ok(segs, nseg, models, reqs, grad_stride, BANDED_MULTI_GRAD));
+    F->n16 = 0, F->halfwidth = 0;
+    for (int i = 0; i < nseg; ++i) {
+        if (segs[i].B > 65535) {  // (the fill and the tangents take one grid plane per unit)
+            sf_set_error(BANDED_MULTI_GRAD ": segment %d: B=%d must lie in 1 .. 65535", i, (int)segs[i].B);
+            return SF_EINVAL;
+        }
+        F->n16 = std::max(F->n16, (segs[i].ctx->n + 15) / 16 * 16);
+        F->halfwidth = std::max(F->halfwidth, h_halfwidth[i]);
+    }
+    return SF_OK;
+}
+// the likelihood's workspace without matrices, then the band solver's
+static Work carve_banded_multi(const BandMultiFrame& F, void* p, size_t cap) {
+    return carve(F.L, &F.uni, F.U, F.bmax, p, cap, false, 0, SF_MULTI_LANES);
+}
+extern "C" size_t sf_banded_multi_grad_workspace_bytes_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                                          const sf_grad_request* reqs, const int* h_halfwidth, int grad_stride) {
+    BandMultiFrame F;
+    if (banded_multi_frame(segs, nseg, models, reqs, h_halfwidth, grad_stride, &F)) return 0;
+    return carve_band_multi_grad(segs, nseg, models, reqs, F.L, F.n16, F.halfwidth, F.U, nullptr, 0,
+                                 carve_banded_multi(F, nullptr, 0).bytes).bytes;
+}
+// k_band_mix takes one grid plane per unit: the mix (and Vs) of `units` units in slices of at most 65535
+static int banded_multi_mix(const BandMultiGradWork& G, const Work& wc, const Layout& L, int u0, int units, const int* info, bool vs,
+                            hipStream_t s) {
+    const size_t ng = (size_t)G.nrhs * G.nrhs, unit = (size_t)G.nrhs * L.npad;
+    for (int lo = 0; lo < units; lo += 65535) {
+        const int nb = std::min(units - lo, 65535);
+        const size_t u = (size_t)u0 + lo;
+        if (!vs)
+            SF_CHECK(sf_launch_band_mix(G.gram + u * ng, wc.Lw + (size_t)lo * L.m * L.m, L.m, info + lo, G.T + u * unit, G.n16, L.npad, nb,
+                                        G.M + u * ng, G.stage + u * unit, s));
+        else
+            SF_CHECK(sf_launch_band_vs(G.gram + u * ng, L.m, info + lo, G.T + u * unit, G.n16, L.npad, nb, G.M2 + u * ng,
+                                       G.stage2 + u * unit, s));
+    }
+    return SF_OK;
+}
+extern "C" int sf_loglike_banded_multi_grad_batch_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                                     const sf_grad_request* reqs, const int* h_halfwidth, double* d_lnl,
+                                                     double* d_log_scale, int* d_info, double* d_grad, int grad_stride, void* d_work,
+                                                     size_t work_bytes, void* stream) {
+    BandMultiFrame F;
+    SF_CHECK(banded_multi_frame(segs, nseg, models, reqs, h_halfwidth, grad_stride, &F));
+    if (!d_lnl || !d_info || !d_grad || !d_work) {
+        sf_set_error(BANDED_MULTI_GRAD ": d_lnl, d_info, d_grad and a workspace are required");
+        return SF_EINVAL;
+    }
+    const Layout& L = F.L;
+    const Work W = carve_banded_multi(F, d_work, work_bytes);
+    const BandMultiGradWork G = carve_band_multi_grad(segs, nseg, models, reqs, L, F.n16, F.halfwidth, F.U, d_work, work_bytes, W.bytes);
+    SF_CHECK(work_fits(work_bytes, G.bytes));
+    sf_ctx* c0 = segs[0].ctx;
+    if (use_device(c0)) return SF_EHIP;
+    hipStream_t s = (hipStream_t)stream;
+    prof_count_call();
+    sf_exec* ex = &c0->exec;
+    SF_CHECK(sf_exec_prepare(ex));
+    hipStream_t lane_stream[SF_MULTI_LANES] = {ex->aux, ex->side, ex->grp[0]};
+    const int H = G.halfwidth, n16 = G.n16, nrhs = G.nrhs, first_units = multi_first_units(F.U);
+    const int64_t sband = (int64_t)n16 * G.ldb, sstage = (int64_t)nrhs * L.npad;
+    const size_t ng = (size_t)nrhs * nrhs;
+    SF_HIP(hipEventRecord(ex->fork, s));
+    for (int l = 0; l < SF_MULTI_LANES; ++l) SF_HIP(hipStreamWaitEvent(lane_stream[l], ex->fork, 0));
+    struct Chunk {
+        int u0, units;
+        hipEvent_t filled[SF_MULTI_LANES];
+        int s0, s1;  // its segments [s0, s1)
+    };
+    std::vector<Chunk> chunks;
+    std::vector<int> seg_u0(nseg);
+    bool lane_used[SF_MULTI_LANES] = {};
+    int u0 = 0, cu0 = 0, cs0 = 0;
+    for (int i = 0; i < nseg; ++i) {
+        sf_ctx* c = segs[i].ctx;
+        const int B = segs[i].B;
+        const int lane = i % SF_MULTI_LANES;
+        hipStream_t sp = lane_stream[lane];
+        lane_used[lane] = true;
+        seg_u0[i] = u0;
+        Work w = with_trans_set(slice(W, u0), lane);
+        if (G.seg[i].coef) w.coef = G.seg[i].coef;  // (the contraction reads them behind the sweeps)
+        {
+            ProfScope ps(sp, PS_FILL);
+            SF_HIP(hipMemsetAsync(w.info_c, 0, sizeof(int) * (size_t)B, sp));
+            sf_fill_args f = fill_args(c, models[i], segs[i].d_params, w);
+            f.C = nullptr, f.lda = 0, f.stride = 0, f.lower_only = 1, f.add_jitter = 1;
+            f.npad = n16;  // (identity rows up to the frame's row count)
+            SF_CHECK(sf_launch_band_fill(f, B, G.band + (size_t)u0 * sband, H + 1, H, G.ldb, sband, w.info_c,
+                                         G.gtab + (size_t)u0 * (G.ldb + 2), sp));
+        }
+        {
+            ProfScope ps(sp, PS_TRANSFORM);
+            SF_CHECK(run_transforms(c, models[i], B, segs[i].d_params, w, nullptr, G.seg[i].xs, nullptr,
+                                    d_log_scale ? d_log_scale + u0 : nullptr, true, sp));
+        }
+        const sf_grad_request& r = reqs[i];
+        if (r.n_mean_slots > 0)
+            SF_CHECK(sf_launch_mean_tangents(broaden_args(c, models[i], B, segs[i].d_params, w), c->inv_band.as<double>(),
+                                             emu_args(c, models[i], segs[i].d_params, w, w.mu, nullptr, w.Lw, w.info_e),
+                                             mean_grad_kernel_args(c, r.h_mean_slots, r.n_mean_slots, w, G.seg[i], nullptr, grad_stride),
+                                             B, sp));
+        u0 += B;
+        // (loglike_multi's chunks; a chunk every 256 units instead: 51.7 against 51.2 ms of device time at 25 x 3000 x 64)
+        if ((chunks.empty() && u0 - cu0 >= first_units) || i == nseg - 1) {
+            Chunk ch{cu0, u0 - cu0, {}, cs0, i + 1};
+            cs0 = i + 1;
+            for (int l = 0; l < SF_MULTI_LANES; ++l) {
+                if (!lane_used[l]) continue;
+                SF_CHECK(sf_exec_event(ex, &ch.filled[l]));
+                SF_HIP(hipEventRecord(ch.filled[l], lane_stream[l]));
+                lane_used[l] = false;
+            }
+            chunks.push_back(ch);
+            cu0 = u0;
+        }
+    }
+    for (const Chunk& ch : chunks) {
+        for (int l = 0; l < SF_MULTI_LANES; ++l)
+            if (ch.filled[l]) SF_HIP(hipStreamWaitEvent(s, ch.filled[l], 0));
+        const Work wc = slice(W, ch.u0);
+        const size_t u = (size_t)ch.u0;
+        int* info = d_info + ch.u0;
+        bool cov = false;
+        for (int i = ch.s0; i < ch.s1; ++i) cov |= reqs[i].want_cov != 0;
+        {
+            ProfScope ps(s, PS_POTRF);
+            sf_band_call k = {};
+            k.band = G.band + u * sband, k.sband = sband, k.ldb = G.ldb, k.halfwidth = H;
+            k.n = n16, k.batch = ch.units;
+            k.r = sf_band_rhs{wc.Y, (int64_t)L.mpad * L.npad, L.npad, nrhs, wc.resid, L.npad};
+            k.logdet = G.logdet_band + u, k.gram = G.gram + u * ng, k.info = wc.info_c;
+            SF_CHECK(sf_launch_band_keep(k, G.fac + u * G.sfac, s));
+        }
+        {
+            ProfScope ps(s, PS_SOLVE);
+            SF_CHECK(sf_launch_woodbury(G.gram + u * ng, nrhs, ch.units, G.logdet_band + u, wc.logdet, wc.sqmah, wc.info_c, s));
+            SF_CHECK(sf_launch_finish(ch.units, wc.logdet, wc.sqmah, wc.info_e, wc.info_c, d_lnl + ch.u0, info, s));
+            // T = Bd^-1 [r, Y^T], then [alpha, V] = T M in the staging area
+            SF_CHECK(sf_launch_band_back(G.fac + u * G.sfac, n16, H, ch.units, nrhs, info, G.T + u * sstage, L.npad, sstage, s));
+            SF_CHECK(banded_multi_mix(G, wc, L, ch.u0, ch.units, info, false, s));
+            if (cov) {
+                SF_CHECK(sf_launch_band_selinv(G.fac + u * G.sfac, n16, H, ch.units, nrhs, info, G.sigma + u * sband, G.ldb, sband, s));
+                SF_CHECK(banded_multi_mix(G, wc, L, ch.u0, ch.units, info, true, s));
+            }
+        }
+        for (int i = ch.s0; i < ch.s1; ++i) {
+            const sf_grad_request& r = reqs[i];
+            sf_ctx* c = segs[i].ctx;
+            const int B = segs[i].B;
+            const size_t su = (size_t)seg_u0[i];
+            AppliedWork aw = G.seg[i];
+            aw.info = d_info + seg_u0[i];
+            Work w = slice(W, seg_u0[i]);
+            if (aw.coef) w.coef = aw.coef;
+            double* grad = d_grad + (int64_t)seg_u0[i] * grad_stride;
+            if (r.n_mean_slots > 0)
+                SF_CHECK(sf_launch_mean_grad(eval_args(c, models[i], segs[i].d_params, w),
+                                             mean_grad_kernel_args(c, r.h_mean_slots, r.n_mean_slots, w, aw, grad, grad_stride), w.zs,
+                                             c->m * c->M, B, s));
+            if (r.want_cov)
+                SF_CHECK(sf_launch_band_cov_grad(fill_args(c, models[i], segs[i].d_params, w), B, G.sigma + su * sband, G.ldb, sband, H,
+                                                 aw.stage, G.stage2 + su * sstage + L.npad, L.npad, sstage, c->m, aw.info, aw.part,
+                                                 grad + r.n_mean_slots, grad_stride, s));
+        }
+    }
+    return SF_OK;
 }

@@ -330,6 +330,74 @@ static MultiGradWork carve_multi_grad(const sf_segment* segs, int nseg, const sf
     return g;
 }
 
+// ------------------------------------------------------------------- multi-order gradient on the band solver
+// (sf_loglike_banded_multi_grad_batch_md; behind the Work of the same call, which has no matrices: base_bytes = its size)  One
+// common frame for all U units: n16 rows of the sweep (the group's largest order rounded up to whole blocks), rows of npad
+// doubles (L.npad), the half-width `halfwidth` (the largest of the call) and its ldb.  For all U units, as carve_band and
+// carve_band_grad lay them out for one order: band [U][n16][ldb], gram, logdet_band, gtab, the staging area [U][1 + m][npad],
+// fac (the kept factor of a sweep over n16 rows), T, M; with covariance slots in any segment sigma [U][n16][ldb], M2, stage2.
+// Then per segment, in segment order, the per-unit data of the parts it asks for with the order's own n (AW_MEAN: xs, fin,
+// mpart, dcoef, kdot, mudot, zdot; part) and, for a segment with mean slots and vsini, coef, for the reason carve_multi_grad
+// gives.  seg[i].stage points at the segment's units in the shared staging area.
+struct BandMultiGradWork {
+    int nrhs, n16, halfwidth, ldb;
+    bool any_cov;
+    double *band, *gram, *logdet_band, *gtab, *stage, *fac, *T, *M, *sigma, *M2, *stage2;
+    size_t sfac;  // doubles of one unit's kept factor
+    std::vector<AppliedWork> seg;
+    size_t bytes;
+};
+static BandMultiGradWork carve_band_multi_grad(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                               const sf_grad_request* reqs, const Layout& L, int n16, int halfwidth, int U, void* p,
+                                               size_t cap, size_t base_bytes) {
+    Carve k(p, cap, base_bytes);
+    BandMultiGradWork g{};
+    for (int i = 0; i < nseg; ++i) g.any_cov |= reqs[i].want_cov != 0;
+    g.nrhs = 1 + L.m, g.n16 = n16, g.halfwidth = halfwidth, g.ldb = (halfwidth + 2) & ~1;
+    g.sfac = sfb_keep_doubles(n16, sfb_nbr(halfwidth), sfb_nrb(g.nrhs));
+    const size_t u = (size_t)U, npad = (size_t)L.npad, ng = (size_t)g.nrhs * g.nrhs, unit = (size_t)g.nrhs * npad;
+    g.band = k.take<double>(u * n16 * g.ldb);
+    g.gram = k.take<double>(u * ng);
+    g.logdet_band = k.take<double>(u);
+    g.gtab = k.take<double>(u * (g.ldb + 2));
+    g.stage = k.take<double>(u * unit);
+    g.fac = k.take<double>(u * g.sfac);
+    g.T = k.take<double>(u * unit);
+    g.M = k.take<double>(u * ng);
+    if (g.any_cov) {
+        g.sigma = k.take<double>(u * n16 * g.ldb);
+        g.M2 = k.take<double>(u * ng);
+        g.stage2 = k.take<double>(u * unit);
+    }
+    g.seg.assign(nseg, AppliedWork{});
+    size_t u0 = 0;
+    for (int i = 0; i < nseg; ++i) {
+        const sf_ctx* c = segs[i].ctx;
+        const sf_model_desc* mdl = models[i];
+        const size_t B = (size_t)segs[i].B;
+        const int nslots = reqs[i].n_mean_slots;
+        AppliedWork& w = g.seg[i];
+        w.stage = g.stage ? g.stage + u0 * unit : nullptr;
+        if (nslots > 0) {
+            w.xs = k.take<double>(B * c->m * c->n);
+            w.fin = k.take<double>(B * sf_mean_fin_doubles(c->m));
+            w.mpart = k.take<double>(sf_mean_grad_part_doubles(c->n, nslots, (int)B));
+            if (mdl->has_vsini) {
+                w.dcoef = k.take<double>(B * c->nf * c->rows);
+                w.coef = k.take<double>(B * c->nf * c->rows);
+            }
+            const size_t ngrid = (size_t)(nslots < c->P ? nslots : c->P), mM = (size_t)c->m * c->M;
+            w.kdot = k.take<double>(ngrid * B * mM);
+            w.mudot = k.take<double>(ngrid * B * c->m);
+            w.zdot = k.take<double>(ngrid * B * mM * c->m);
+        }
+        if (reqs[i].want_cov) w.part = k.take<double>(sf_cov_grad_work_doubles(c->n, mdl->has_global, mdl->n_local, (int)B));
+        u0 += B;
+    }
+    g.bytes = sf_align_up(k.off, 256);
+    return g;
+}
+
 // ------------------------------------------------------------------- context-free workspaces
 // sf_potri_diag_batch: the transposed inverses of the 64 x 64 diagonal blocks, [batch][n / 64][64][64]; sf_potri_blocks_batch
 // (with_diag): the same, then the diagonal of the inverse ([batch][n]: the inverse's launch writes it)

@@ -334,8 +334,10 @@ class EchelleModel:
         return out if len(out) > 1 else lnl
 
     # ------------------------------------------------------------------ likelihood gradient of all orders in one pass
-    def _gradient_layout(self):
-        """Host logic of the gradient, no device: ``(labels, cols, requests, sources)``.  ``cols[i]``: the columns of a
+    def _gradient_layout(self, solver=None):
+        """Host logic of the gradient, no device: ``(labels, cols, requests, sources)``.  ``solver``: None -- every order's
+        own ``solver`` must be "dense"; "dense", "banded" or "auto" -- the solver of the gradient call, whatever the orders'
+        own is (anything else: the ``ValueError`` of :func:`starfish_amd._device.check_solver`).  ``cols[i]``: the columns of a
         parameter vector that hold order i's own labels; ``requests[i] = (mean_columns, want_cov)``: what order i asks the
         device for (:class:`starfish_amd._device.MultiGradPlan`); ``sources[j]``: the ``(order, slot)`` pairs of the
         per-unit gradient rows that label j adds up, ascending in the order -- a unit's row holds its order's mean slots in
@@ -344,12 +346,14 @@ class EchelleModel:
         the device does not differentiate."""
         from .. import _device as D
 
+        if solver is not None:
+            D.check_solver(solver, or_none=True)
         labels, cols = self._layout()
         if not labels:
             raise ValueError("no thawed parameter to differentiate in")
         requests, sources = [], [[] for _ in labels]
         for i, m in enumerate(self.orders):
-            if m.solver != "dense":
+            if solver is None and m.solver != "dense":
                 raise ValueError(f"order {i}: the gradient runs on the dense solver only, not solver={m.solver!r}")
             md = m._model_desc(None)
             own, mean, cov = list(m.labels), m.mean_gradient_labels, m.gradient_labels
@@ -367,7 +371,7 @@ class EchelleModel:
                 sources[cols[i][own.index(key)]].append((i, len(columns) + slot))
         return labels, cols, requests, sources
 
-    def log_likelihood_gradient_batch(self, P, return_info=False, return_orders=False):
+    def log_likelihood_gradient_batch(self, P, return_info=False, return_orders=False, solver=None):
         """``(lnL (B,), grad (B, len(labels)))`` for B parameter vectors (rows of ``P`` in :attr:`labels` order), no priors:
         the sum of the per-order likelihoods and its analytic gradient in every thawed label, from ONE factorisation per
         (order x walker) unit and one enqueue per device (``sf_loglike_multi_grad_batch_md``).  A shared label receives the
@@ -375,10 +379,19 @@ class EchelleModel:
         the orders runs in ascending order index -- on the device (``sf_multi_grad_reduce``) when all orders share one
         call, on the host by the same rule when they live on several devices.  Walkers that fail in any order get
         ``-inf`` and a NaN row; ``info`` is the first non-zero per-order code.  With ``return_orders`` the (n_orders, B)
-        per-order likelihoods are returned too.  The model's own state is not modified."""
+        per-order likelihoods are returned too.  The model's own state is not modified.
+
+        solver: None    -- the dense call above; every order's own ``solver`` must be "dense";
+                "dense" -- the same call, whatever the orders' own ``solver`` is;
+                "banded" -- the band + Woodbury solver, all units of a device in one launch sequence
+                            (``sf_loglike_banded_multi_grad_batch_md``): agrees with the dense call to rounding, not bit for
+                            bit; a walker with a unit whose covariance support exceeds the LDS window gets ``-inf``, a NaN
+                            row and info = -4;
+                "auto"  -- banded for the units whose half-width bound fits the window, the dense call for the rest."""
         from .. import _device as D
 
-        labels, cols, requests, sources = self._gradient_layout()
+        labels, cols, requests, sources = self._gradient_layout(solver)
+        banded = solver in ("banded", "auto")
         P = np.atleast_2d(np.asarray(P, dtype=np.float64))
         if P.shape[1] != len(labels):
             raise ValueError("Param Vector does not match length of thawed parameters")
@@ -390,8 +403,9 @@ class EchelleModel:
                 pending.append((idxs, D.loglike_multi([packed[i][0] for i in idxs], [packed[i][1] for i in idxs],
                                                       [packed[i][2] for i in idxs], sync=False)))
                 continue
-            pending.append((idxs, D.loglike_multi_grad([packed[i][0] for i in idxs], [packed[i][1] for i in idxs],
-                                                       [packed[i][2] for i in idxs], [requests[i] for i in idxs], sync=False)))
+            call, kw = (D.loglike_banded_multi_grad, dict(solver=solver)) if banded else (D.loglike_multi_grad, {})
+            pending.append((idxs, call([packed[i][0] for i in idxs], [packed[i][1] for i in idxs],
+                                       [packed[i][2] for i in idxs], [requests[i] for i in idxs], sync=False, **kw)))
         unit_lnl = np.full((len(self.orders), B), -np.inf)
         unit_info = np.zeros((len(self.orders), B), dtype=np.int32)
         unit_grad = [np.zeros((B, 0))] * len(self.orders)
@@ -399,7 +413,7 @@ class EchelleModel:
             for i, out in zip(idxs, plan.collect()):
                 unit_lnl[i], unit_info[i] = out["lnl"], out["info"]
                 unit_grad[i] = out.get("grad", unit_grad[i])
-        if len(pending) == 1 and isinstance(pending[0][1], D.MultiGradPlan):
+        if len(pending) == 1 and isinstance(pending[0][1], (D.MultiGradPlan, D.BandedMultiGradPlan)):
             lnl, grad, info = pending[0][1].reduce(sources)
         else:
             lnl, grad, info = D.reduce_orders_host(unit_lnl, unit_info, unit_grad, sources)
@@ -411,24 +425,28 @@ class EchelleModel:
             out += (np.where(unit_info == 0, unit_lnl, -np.inf),)
         return out
 
-    def log_likelihood_gradient(self):
+    def log_likelihood_gradient(self, solver=None):
         """``(lnL, {label: d lnL / d label})`` of the current state, no priors.  Raises as
-        :meth:`SpectrumModel.log_likelihood` does for a point the device flags; the model's state is not modified."""
-        lnl, grad, info = self.log_likelihood_gradient_batch(self.get_param_vector()[None, :], return_info=True)
+        :meth:`SpectrumModel.log_likelihood` does for a point the device flags; the model's state is not modified.
+        ``solver`` as for :meth:`log_likelihood_gradient_batch`."""
+        extra = {} if solver is None else dict(solver=solver)
+        lnl, grad, info = self.log_likelihood_gradient_batch(self.get_param_vector()[None, :], return_info=True, **extra)
         SpectrumModel._raise_for_info(info[0])
         return float(lnl[0]), dict(zip(self.labels, (float(v) for v in grad[0])))
 
-    def train(self, priors=None, **kwargs):
+    def train(self, priors=None, *, gradient_solver=None, **kwargs):
         """MAP estimate over :attr:`labels`: ``scipy.optimize.minimize(method="L-BFGS-B", jac=True)`` on the analytic gradient
         of :meth:`log_likelihood_gradient_batch` -- a per-order fit has a few hundred parameters, which a simplex search
         cannot handle.  ``priors`` are looked up as :meth:`log_likelihood` does (a bare per-order key counts once per order);
         a prior on an optimised label adds its ``logpdf`` and the slope of it by a central difference with step
         ``eps^(1/3) max(1, |x|)``, priors on other parameters a constant.  A point the device flags raises as
         :meth:`SpectrumModel.log_likelihood` does.  ``kwargs`` go to ``minimize``.  Every evaluation leaves the model at its
-        point; a run that succeeds or stops at its iteration limit leaves it at ``soln.x``."""
+        point; a run that succeeds or stops at its iteration limit leaves it at ``soln.x``.  ``gradient_solver``: the
+        ``solver`` of :meth:`log_likelihood_gradient_batch` for every evaluation."""
         from .. import _map
 
-        labels, cols, _requests, _sources = self._gradient_layout()  # (refusals before any device work)
+        labels, cols, _requests, _sources = self._gradient_layout(gradient_solver)  # (refusals before any device work)
+        extra = {} if gradient_solver is None else dict(solver=gradient_solver)
         for key, prior in (priors or {}).items():
             if not callable(getattr(prior, "logpdf", None)):
                 raise ValueError(f"Invalid priors. {key} does not have a `logpdf` method")
@@ -436,7 +454,7 @@ class EchelleModel:
 
         def evaluate(x):
             self.set_param_vector(x)
-            lnl, grad, info = self.log_likelihood_gradient_batch(x[None, :], return_info=True)
+            lnl, grad, info = self.log_likelihood_gradient_batch(x[None, :], return_info=True, **extra)
             SpectrumModel._raise_for_info(info[0])
             # the priors are added here, not by _map: constant and sampled terms alternate in the order of ``terms``
             value, slope = float(lnl[0]), grad[0].copy()
