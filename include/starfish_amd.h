@@ -603,6 +603,38 @@ int sf_loglike_banded_grad_batch(sf_ctx* ctx, const sf_model_desc* model, int B,
                                  const int* h_slots, int nslots, int want_cov, double* d_lnl, double* d_grad, int grad_stride,
                                  double* d_resid, int* d_info, void* d_work, size_t work_bytes, void* stream);
 
+/* The residual diagnostics on the band + Woodbury solver: what sf_apply_batch with SF_APPLY_CINV, sf_pointwise_batch and
+ * sf_decompose_batch give from the dense factor, from one band fill, one keeping sweep and one backward sweep.  d_rhs, nrhs,
+ * ldr, rhs_stride as for sf_apply_batch (NULL: each walker's own residual, nrhs == 1; rhs_stride == 0: one block shared by the
+ * walkers).  With k = nrhs right-hand sides the sweep carries the k + m rows [R; Y] (NULL: the gradient call's [r; Y]) and
+ *     alpha_j = T_rj - T_Y S^-1 G_Y,rj,   T = Bd^-1 [R^T, Y^T],  G the sweep's Gram matrix,  S = I + G_YY = L_S L_S^T
+ * goes to d_alpha[B][nrhs][n] (required).  Optional, not computed when NULL: d_cinv_diag[B][n] = diag(C^-1) = diag(Sigma) -
+ * rowsum(Vs^2), Sigma = Bd^-1 on the band by selected inversion and Vs = T_Y L_S^-T (the sum over the m columns ascending);
+ * d_cov_diag[B][n] = diag(C) of the matrix that is factorised, jitter included: the filled band's diagonal plus colsum(Y^2);
+ * d_comp[B][3 + n_local][nrhs][n] = K_k alpha in the component order of sf_decompose_batch, by the same launches.  d_flux
+ * [B][n] and d_info [B] may be NULL; d_info has the codes of sf_loglike_banded_batch, SF_INFO_BANDWIDTH included (with caller
+ * right-hand sides there is no residual to be NaN: SF_INFO_NAN then says that logdet(Bd) is).  A walker with info != 0 gets NaN
+ * in every row of every output.
+ * The call takes every nrhs for which m + nrhs rows fit the LDS window at this half-width: at most 48 rows in all, the widest
+ * half-width falling from 144 to 128 to 112 as the 16-row blocks of right-hand sides grow.  sf_diagnose_banded_max_nrhs: the
+ * largest such nrhs, 0 if not even one fits (or the grid is not strictly increasing), SF_EINVAL for a bad context; more
+ * right-hand sides go in several calls.  SF_EINVAL, before anything is enqueued, for B outside 1 .. 65535, nrhs < 1, m + nrhs
+ * beyond the window (use sf_diagnose_banded_max_nrhs, or sf_pointwise_batch / sf_decompose_batch), a null d_params, d_alpha or
+ * d_work, rhs_stride < 0, nrhs != 1 without d_rhs, ldr < n, a grid that is not strictly increasing, a bad context or model;
+ * SF_ENOMEM for a short workspace (sf_diagnose_banded_workspace_bytes: 0 for whatever the call refuses).  Values agree with
+ * the dense calls to rounding, not bit for bit; every sum has a fixed order, so a repeated call and a call on a sub-batch of
+ * the walkers at the same halfwidth and nrhs give the same bits; the two diagonals do not depend on the right-hand sides.
+ * The band is filled entry by entry (the likelihood calls tabulate the global kernel per diagonal on a log-uniform grid, which
+ * is off by the rounding of the grid: inside the likelihood's tolerance, not inside the bound diag(C^-1) is held to).  Never
+ * synchronises. */
+int sf_diagnose_banded_max_nrhs(const sf_ctx* ctx, int halfwidth);
+size_t sf_diagnose_banded_workspace_bytes(const sf_ctx* ctx, const sf_model_desc* model, int B, int halfwidth, int nrhs,
+                                          int want_cinv_diag, int want_comp);
+int sf_diagnose_banded_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, int halfwidth,
+                             const double* d_rhs, int nrhs, int ldr, int64_t rhs_stride, double* d_alpha, double* d_cinv_diag,
+                             double* d_cov_diag, double* d_comp, double* d_flux, int* d_info, void* d_work, size_t work_bytes,
+                             void* stream);
+
 /* Timing hooks for bench.py (process-global, not thread-safe): when enabled, the batched calls
  * record HIP events on the caller's stream around each stage and around every MFMA update launch.
  * sf_profile_read synchronises those events, returns the milliseconds accumulated since the last

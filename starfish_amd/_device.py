@@ -247,6 +247,29 @@ def finish_structured(out, fits, solver, dense):
     return out
 
 
+DIAGNOSE_WANTS = ("alpha", "cinv_diag", "cov_diag", "comp")
+
+
+def diagnose_wants(want):
+    """``want`` of :meth:`DeviceOrder.diagnose_banded` in the order of DIAGNOSE_WANTS, "alpha" always among them."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    unknown = [w for w in want if w not in DIAGNOSE_WANTS]
+    if unknown:
+        raise ValueError(f"want holds {unknown}: expected some of {list(DIAGNOSE_WANTS)}")
+    return tuple(w for w in DIAGNOSE_WANTS if w == "alpha" or w in want)
+
+
+def rhs_groups(nrhs, max_nrhs):
+    """``nrhs`` right-hand sides cut into consecutive groups of at most ``max_nrhs`` (sf_diagnose_banded_max_nrhs), one call of
+    the band solver each: the list of ``(lo, hi)``.  Pure host logic."""
+    nrhs, max_nrhs = int(nrhs), int(max_nrhs)
+    if nrhs < 1:
+        raise ValueError("rhs holds no right-hand side")
+    if max_nrhs < 1:
+        raise ValueError("the band solver takes no right-hand side at this half-width")
+    return [(lo, min(lo + max_nrhs, nrhs)) for lo in range(0, nrhs, max_nrhs)]
+
+
 def factor_v11(v11, w_hat):
     """Init-time constants of the emulator conditional (the reference solves with the constant v11 on every call,
     emulator.py:387-388): Linv = inverse of the lower Cholesky factor of v11 and alpha = v11^-1 w_hat, by LAPACK on
@@ -1028,34 +1051,157 @@ class DeviceOrder:
             return self._run_chunked(name, md, P, max_chunk, lambda units: workspace_bytes(md, units, nrhs), buffers, args,
                                      download)
 
-    def apply(self, md, params, op, rhs=None, want_flux=False, max_chunk=None):
+    def apply(self, md, params, op, rhs=None, want_flux=False, max_chunk=None, solver="dense"):
         """The Cholesky factor of every walker's covariance matrix applied to right-hand sides (sf_apply_batch): ``op`` is
         "L" (L z), "Linv" (L^-1 b), "LinvT" (L^-T b) or "Cinv" (C^-1 b = cho_solve), or its SF_APPLY_* number.
         params: (B, stride) rows as for :meth:`loglike`.  rhs: None (each walker's own residual), (nrhs, n) shared by all
         walkers or (B, nrhs, n).  Returns dict of numpy arrays: out (B, nrhs, n), NaN for walkers with info != 0, info
-        (the codes of :meth:`loglike`) and, asked for, flux (B, n).  Always the dense factor."""
+        (the codes of :meth:`loglike`) and, asked for, flux (B, n).
+
+        solver: "dense" -- the dense factor (sf_apply_batch); "banded" / "auto" -- :meth:`diagnose_banded`, for "Cinv" only:
+        the band solver has no triangular factor of C, so "L", "Linv" and "LinvT" with it are a ``ValueError``."""
         code = APPLY_OPS[op] if isinstance(op, str) else int(op)
+        check_solver(solver)
+        if solver != "dense":
+            if code != APPLY_OPS["Cinv"]:
+                raise ValueError(f'op {op!r} needs the dense factor: solver={solver!r} has no triangular factor of C ("Cinv" only)')
+            res = self.diagnose_banded(md, params, rhs, ("alpha",), want_flux=want_flux, max_chunk=max_chunk, solver=solver)
+            res["out"] = res.pop("alpha")
+            return res
         return self._run_applied("apply_batch", md, params, rhs, lambda nrhs: {"out": (nrhs, self.n)}, want_flux, max_chunk,
                                  self.apply_workspace_bytes, lead=(code,))
 
-    def decompose(self, md, params, rhs=None, want_flux=False, max_chunk=None):
+    def decompose(self, md, params, rhs=None, want_flux=False, max_chunk=None, solver="dense"):
         """The right-hand sides split by covariance component (sf_decompose_batch): ``alpha = C^-1 rhs`` as :meth:`apply`
         with "Cinv" gives it, and ``comp[b, k] = K_k alpha`` for k = 0 emulator, 1 noise (jitter included), 2 global (zeros
         without one), 3 + j local kernel j.  params, rhs: as for :meth:`apply`.  Returns dict of numpy arrays: comp
         (B, 3 + n_local, nrhs, n), alpha (B, nrhs, n), info and, asked for, flux (B, n); NaN rows where info != 0.
-        Chunked and retried like :meth:`apply`."""
+        Chunked and retried like :meth:`apply`.  solver: "dense" (sf_decompose_batch), or "banded" / "auto":
+        :meth:`diagnose_banded`."""
+        check_solver(solver)
+        if solver != "dense":
+            return self.diagnose_banded(md, params, rhs, ("alpha", "comp"), want_flux=want_flux, max_chunk=max_chunk, solver=solver)
         outputs = lambda nrhs: {"comp": (3 + int(md.n_local), nrhs, self.n), "alpha": (nrhs, self.n)}  # noqa: E731
         return self._run_applied("decompose_batch", md, params, rhs, outputs, want_flux, max_chunk,
                                  self.decompose_workspace_bytes)
 
-    def pointwise(self, md, params, rhs=None, want_flux=False, max_chunk=None):
+    def pointwise(self, md, params, rhs=None, want_flux=False, max_chunk=None, solver="dense"):
         """What the per-pixel leave-one-out diagnostics need (sf_pointwise_batch): ``alpha = C^-1 rhs`` as :meth:`apply`
         with "Cinv" gives it, ``cinv_diag = diag(C^-1)`` and ``cov_diag = diag(C)``, jitter included, as it was factorised.
         params, rhs: as for :meth:`apply`.  Returns dict of numpy arrays: alpha (B, nrhs, n), cinv_diag (B, n), cov_diag
-        (B, n), info and, asked for, flux (B, n); NaN rows where info != 0.  Chunked and retried like :meth:`apply`."""
+        (B, n), info and, asked for, flux (B, n); NaN rows where info != 0.  Chunked and retried like :meth:`apply`.
+        solver: "dense" (sf_pointwise_batch), or "banded" / "auto": :meth:`diagnose_banded`."""
+        check_solver(solver)
+        if solver != "dense":
+            return self.diagnose_banded(md, params, rhs, ("alpha", "cinv_diag", "cov_diag"), want_flux=want_flux,
+                                        max_chunk=max_chunk, solver=solver)
         outputs = lambda nrhs: {"alpha": (nrhs, self.n), "cinv_diag": (self.n,), "cov_diag": (self.n,)}  # noqa: E731
         return self._run_applied("pointwise_batch", md, params, rhs, outputs, want_flux, max_chunk,
                                  self.pointwise_workspace_bytes)
+
+    # ------------------------------------------------------------------ residual diagnostics on the band solver
+    def diagnose_banded_max_nrhs(self, halfwidth):
+        """Most right-hand sides one sf_diagnose_banded_batch call takes at this half-width (0: none)."""
+        return max(int(self.lib.sf_diagnose_banded_max_nrhs(self.ctx, int(halfwidth))), 0) if self.n else 0
+
+    def diagnose_banded_workspace_bytes(self, md, B, halfwidth, nrhs, want_cinv_diag=False, want_comp=False):
+        return self._size_query("diagnose_banded_", md, B, halfwidth, nrhs, int(bool(want_cinv_diag)), int(bool(want_comp)))
+
+    def _diagnose_shapes(self, md, want, nrhs, want_flux):
+        """key -> trailing shape of the results of :meth:`diagnose_banded` (without info)."""
+        shapes = {"alpha": (nrhs, self.n), "cinv_diag": (self.n,), "cov_diag": (self.n,),
+                  "comp": (3 + int(md.n_local), nrhs, self.n)}
+        shapes = {key: shapes[key] for key in want}
+        if want_flux:
+            shapes["flux"] = (self.n,)
+        return shapes
+
+    def _diagnose_banded_group(self, md, rows, W, R, per_walker, cols, want, want_flux, max_chunk):
+        """One sf_diagnose_banded_batch per chunk of ``rows`` at the half-width ``W`` for the right-hand sides ``cols`` =
+        (lo, hi) of ``R`` (None: the walkers' own residuals): the dict of the results in ``want`` (+ flux, info)."""
+        torch = _torch()
+        lo_r, hi_r = cols
+        k = hi_r - lo_r
+        with torch.cuda.device(self.dev):
+            P = self._rows(rows)
+            B = int(P.shape[0])
+            buffers, download = self._outputs(B, self._diagnose_shapes(md, want, k, False), want_flux)
+            ktot = int(R.shape[-2]) if R is not None else 1
+
+            def args(bufs, lo, hi):
+                outs, info, flux = bufs
+                by_key = {key: o[lo:hi] for key, o in zip(want, outs)}
+                rhs = None if R is None else (R[lo:hi, lo_r:hi_r] if per_walker else R[lo_r:hi_r])
+                return (W, rhs, k, self.n, ktot * self.n if per_walker else 0, by_key["alpha"], by_key.get("cinv_diag"),
+                        by_key.get("cov_diag"), by_key.get("comp"), flux[lo:hi] if want_flux else None, info[lo:hi])
+
+            size = lambda units: self.diagnose_banded_workspace_bytes(md, units, W, k, "cinv_diag" in want, "comp" in want)  # noqa: E731
+            return self._run_chunked("diagnose_banded_batch", md, P, max_chunk, size, buffers, args, download)
+
+    def _diagnose_dense(self, md, rows, rhs, want, want_flux, max_chunk):
+        """The results of :meth:`diagnose_banded` from the dense calls, each as its own call gives it."""
+        res = {}
+        if "comp" in want:
+            res.update(self.decompose(md, rows, rhs, want_flux=want_flux, max_chunk=max_chunk))
+        if "cinv_diag" in want or "cov_diag" in want:
+            res.update(self.pointwise(md, rows, rhs, want_flux=want_flux, max_chunk=max_chunk))
+        if not res:
+            res = self.apply(md, rows, "Cinv", rhs, want_flux=want_flux, max_chunk=max_chunk)
+            res["alpha"] = res.pop("out")
+        return res
+
+    def diagnose_banded(self, md, params, rhs=None, want=("alpha",), want_flux=False, max_chunk=None, solver="banded"):
+        """The residual diagnostics on the band + Woodbury solver (sf_diagnose_banded_batch): what :meth:`apply` with "Cinv",
+        :meth:`pointwise` and :meth:`decompose` give from the dense factor, from one keeping sweep per walker.  params, rhs:
+        as for :meth:`apply`.  want: some of "alpha" (B, nrhs, n; always returned), "cinv_diag" (B, n), "cov_diag" (B, n),
+        "comp" (B, 3 + n_local, nrhs, n).  Returns dict of numpy arrays: those, info and, asked for, flux (B, n); NaN rows
+        where info != 0.  Values agree with the dense calls to rounding, not bit for bit.
+
+        The walkers whose host half-width bound fits the LDS window go in one group at the group's largest bound (so that
+        chunks and sub-batches of it give the same bits).  More right-hand sides than the window takes at that half-width
+        (:meth:`diagnose_banded_max_nrhs`) are cut into groups of that size (:func:`rhs_groups`), one call each; the two
+        diagonals are taken from the first.  solver: "banded" -- the other walkers come back with info = -4 and NaN rows;
+        "auto" -- they, and walkers with the internal status -5, go through the dense calls (:func:`finish_structured`)."""
+        torch = _torch()
+        check_solver(solver, ("banded", "auto"))
+        want = diagnose_wants(want)
+        rows, hw = self._host_rows_and_bound(md, params)
+        B = rows.shape[0]
+        with torch.cuda.device(self.dev):
+            R, nrhs, per_walker = self._rhs_on_device(rhs, B)
+        fits = hw <= self.banded_window_halfwidth()
+        out = refused_output(B, self._diagnose_shapes(md, want, nrhs, want_flux))
+        del out["lnl"]  # (no likelihood here)
+        idx = np.nonzero(fits)[0]
+        if idx.size:
+            W = int(hw[idx].max())
+            with torch.cuda.device(self.dev):
+                Rg = R[torch.from_numpy(idx).to(self.dev)] if per_walker else R
+            for g, cols in enumerate(rhs_groups(nrhs, self.diagnose_banded_max_nrhs(W))):
+                # (the diagonals, the flux and the status do not depend on the right-hand sides: the first group's)
+                first = g == 0
+                got = self._diagnose_banded_group(md, rows[idx], W, Rg, per_walker, cols,
+                                                  want if first else tuple(w for w in want if w in ("alpha", "comp")),
+                                                  want_flux and first, max_chunk)
+                for key, v in got.items():
+                    if key in ("alpha", "comp"):
+                        out[key][idx, ..., cols[0]:cols[1], :] = v
+                    elif first:
+                        out[key][idx] = v
+                    elif key == "info":  # (a later group's status counts where the first had none)
+                        out[key][idx] = np.where(out[key][idx] == 0, v, out[key][idx])
+            bad = out["info"][idx] != 0  # (every row of a failed walker is NaN, whichever group reported it)
+            for key in out:
+                if key not in ("info", "flux") and bad.any():
+                    out[key][idx[bad]] = np.nan
+
+        def dense(rest):
+            sub = rhs
+            if per_walker:
+                sub = R[torch.from_numpy(rest).to(self.dev)]
+            return self._diagnose_dense(md, rows[rest], sub, want, want_flux, max_chunk)
+
+        return finish_structured(out, fits, solver, dense)
 
     def _run_grad(self, name, md, params, lead, slots, workspace_bytes, want_flux, max_chunk):
         """:meth:`_run_chunked` for ``sf_<name>(ctx, &md, B, P, *lead, lnl, grad, grad_stride, flux, info, ws, ...)``: the two

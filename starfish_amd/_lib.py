@@ -275,6 +275,16 @@ SIGNATURES = {
         [_VP, C.POINTER(ModelDesc), C.c_int, _VP, C.c_int, c_int_p, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_size_t,
          _VP],
     ),
+    "sf_diagnose_banded_max_nrhs": (C.c_int, [_VP, C.c_int]),
+    "sf_diagnose_banded_workspace_bytes": (
+        C.c_size_t,
+        [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    ),
+    "sf_diagnose_banded_batch": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+         C.c_size_t, _VP],
+    ),
     "sf_debug_clock_probe": (C.c_int, [_VP, C.c_longlong, _VP]),
     "sf_debug_stream_write": (C.c_int, [_VP, C.c_size_t, C.c_double, _VP]),
     "sf_debug_cholesky_sequence": (C.c_int, [C.c_int]),

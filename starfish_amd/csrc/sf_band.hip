@@ -51,6 +51,9 @@
 //   sf_band_selinv.h    for the covariance gradient on the band: k_band_selinv (selected inversion: the band of Bd^-1 from the
 //                       kept factor), k_band_vs_matrix (Vs of C^-1 = Bd^-1 - Vs Vs^T through k_band_mix), their launchers (the
 //                       contraction with dC / d theta over the band is sf_fill.hip's, beside the derivative formulas)
+//   sf_band_diag.h      for the residual diagnostics on the band: k_band_diag_stage (the sweep's rows [R; Y] for caller
+//                       right-hand sides), k_band_cinv_diag (diag(C^-1) = diag(Sigma) - rowsum(Vs^2)), k_band_cov_diag, their
+//                       launchers (the split by covariance component is sf_fill.hip's sf_launch_cov_matvec)
 #include "sf_common.h"
 #include "sf_device.h"
 #include "sf_band_shape.h"
@@ -60,3 +63,4 @@
 #include "sf_band_woodbury.h"
 #include "sf_band_solve.h"
 #include "sf_band_selinv.h"
+#include "sf_band_diag.h"

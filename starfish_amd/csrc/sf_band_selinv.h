@@ -144,13 +144,13 @@ int sf_launch_band_selinv(const double* fac, int n, int halfwidth, int batch, in
     return SF_OK;
 }
 
-// The capacitance matrix S = I + G of one walker (G = gram[1:,1:]) into S[r * 33 + c], and its factor S = L_S L_S^T in place
-// (lower; the diagonal holds 1 / l_jj), one wave.  The steps of k_band_mix_matrix, whose own text stays as it is.
-__device__ __forceinline__ void sfb_capacitance_factor(const double* g, int m, int lane, double* S) {
-    const int nrhs = m + 1;
+// The capacitance matrix S = I + G of one walker (G = gram[kr:, kr:] of the sweep over kr + m rows) into S[r * 33 + c], and its
+// factor S = L_S L_S^T in place (lower; the diagonal holds 1 / l_jj), one wave.  The steps of k_band_mix_matrix.
+__device__ __forceinline__ void sfb_capacitance_factor(const double* g, int kr, int m, int lane, double* S) {
+    const int nrhs = kr + m;
     for (int e = lane; e < m * m; e += 64) {
         const int r = e / m, c = e - r * m;
-        S[r * 33 + c] = g[(r + 1) * nrhs + (c + 1)] + (r == c ? 1.0 : 0.0);
+        S[r * 33 + c] = g[(r + kr) * nrhs + (c + kr)] + (r == c ? 1.0 : 0.0);
     }
     __syncthreads();
     for (int j = 0; j < m; ++j) {
@@ -168,17 +168,22 @@ __device__ __forceinline__ void sfb_capacitance_factor(const double* g, int m, i
         __syncthreads();
     }
 }
-// C^-1 = Sigma - Vs Vs^T with Vs = T_Y L_S^-T (n x m): Vs = T M2 through k_band_mix, where row 0 and column 0 of M2 are zero
-// and M2[1 + j][1 + c] = (L_S^-1)[c][j].  One wave per walker; lane c solves L_S z = e_c, column c of L_S^-1, which is row
-// 1 + c of M2.  A walker with info != 0 is not read.
-__global__ __launch_bounds__(64) void k_band_vs_matrix(const double* __restrict__ gram, int m, const int* __restrict__ info,
-                                                       double* __restrict__ M2) {
+// C^-1 = Sigma - Vs Vs^T with Vs = T_Y L_S^-T (n x m): Vs = T M2 through k_band_mix.  T has kr rows in front of the m rows of
+// Y; M2 is (kr + m) x (co + m): its first kr rows and first co columns are zero and M2[kr + j][co + c] = (L_S^-1)[c][j].  The
+// gradient keeps the staging layout of its mix (kr = co = 1: row 0 of the product is zero), the diagnostics ask for the m
+// columns alone (co = 0).  One wave per walker; lane c solves L_S z = e_c, column c of L_S^-1, which is row kr + c of M2.  A
+// walker with info != 0 is not read.
+__global__ __launch_bounds__(64) void k_band_vs_matrix(const double* __restrict__ gram, int kr, int m, int co,
+                                                       const int* __restrict__ info, double* __restrict__ M2) {
     __shared__ double S[33 * 33];
-    const int b = blockIdx.x, lane = threadIdx.x, nrhs = m + 1;
+    const int b = blockIdx.x, lane = threadIdx.x, nin = kr + m, nout = co + m;
     if (info[b] != 0) return;
-    sfb_capacitance_factor(gram + (int64_t)b * nrhs * nrhs, m, lane, S);
-    double* Mb = M2 + (int64_t)b * nrhs * nrhs;
-    if (lane < nrhs) Mb[lane] = 0.0, Mb[lane * nrhs] = 0.0;
+    sfb_capacitance_factor(gram + (int64_t)b * nin * nin, kr, m, lane, S);
+    double* Mb = M2 + (int64_t)b * nin * nout;
+    if (lane < nout)
+        for (int r = 0; r < kr; ++r) Mb[r * nout + lane] = 0.0;
+    if (lane < nin)
+        for (int c = 0; c < co; ++c) Mb[lane * nout + c] = 0.0;
     if (lane < m) {
         const int c = lane;
         double z[32];
@@ -194,19 +199,22 @@ __global__ __launch_bounds__(64) void k_band_vs_matrix(const double* __restrict_
         }
 #pragma unroll
         for (int j = 0; j < 32; ++j)
-            if (j < m) Mb[(1 + c) * nrhs + 1 + j] = z[j];
+            if (j < m) Mb[(kr + c) * nout + co + j] = z[j];
     }
 }
-// stage2[b][0] = 0, stage2[b][1 + c] = column c of Vs, in the staging layout [batch][1 + m][npad] of sf_launch_band_mix
-int sf_launch_band_vs(const double* gram, int m, const int* info, const double* T, int n, int npad, int batch, double* Mwork,
-                      double* stage2, hipStream_t s) {
-    if (m < 1 || m > 32 || batch <= 0 || batch > 65535 || n <= 0 || npad < n) {
-        sf_set_error("band_vs: 1 .. 32 low-rank rows, 1 .. 65535 walkers");
+// stage2[b][co + c] = column c of Vs (rows < co are zero), [batch][co + m][npad]: with kr = co = 1 the staging layout of the
+// gradient's sf_launch_band_mix
+int sf_launch_band_vs(const double* gram, int kr, int m, int co, const int* info, const double* T, int n, int npad, int batch,
+                      double* Mwork, double* stage2, hipStream_t s) {
+    if (m < 1 || m > 32 || kr < 1 || kr + m > SFB_MIX_MAX || (co != 0 && co != kr) || co + m > SFB_MIX_MAX || batch <= 0 ||
+        batch > 65535 || n <= 0 || npad < n) {
+        sf_set_error("band_vs: 1 .. 32 low-rank rows, at most %d rows of right-hand sides in all, 1 .. 65535 walkers", SFB_MIX_MAX);
         return SF_EINVAL;
     }
-    hipLaunchKernelGGL(k_band_vs_matrix, dim3(batch), dim3(64), 0, s, gram, m, info, Mwork);
+    hipLaunchKernelGGL(k_band_vs_matrix, dim3(batch), dim3(64), 0, s, gram, kr, m, co, info, Mwork);
     SF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_band_mix, dim3((npad + 255) / 256, batch), dim3(256), 0, s, T, Mwork, info, m + 1, n, npad, stage2);
+    hipLaunchKernelGGL(k_band_mix, dim3((npad + 255) / 256, batch), dim3(256), 0, s, T, Mwork, info, kr + m, kr, co, co + m, n, npad,
+                       stage2);
     SF_LAUNCH_CHECK();
     return SF_OK;
 }

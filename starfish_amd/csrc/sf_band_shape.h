@@ -23,6 +23,7 @@ SFB_HD int sfb_nbr(int halfwidth) {  // window blocks per side: window rows >= W
     return nbr < 3 ? 3 : nbr;
 }
 SFB_HD int sfb_nrb(int nrhs) { return (nrhs + BB - 1) / BB; }  // 16-row blocks of right-hand sides
+#define SFB_MIX_MAX_ROWS 48  // right-hand sides of a sweep in all: three blocks (sfb_admit)
 // Waves 4.. prefetch the band rows in groups of 256 threads (one 16 x 16 block per group and register): enough groups
 // for SFB_PF registers to cover the nbr blocks of a block row
 SFB_HD int sfb_nwaves(int nbr) { return nbr <= SFB_PF ? 8 : nbr <= 2 * SFB_PF ? 12 : 16; }

@@ -4,7 +4,8 @@
 //   forward   k_band_keep<NRB>: k_band_forms' sweep (sf_band_sweep_body.h with SFB_SWEEP_KEEP), which besides logdet and the Gram matrix
 //             stores per block column F_k = L_kk^-1, the blocks L_{k+1+I,k} and W_k = (L^-1 rhs)_k  (sfb_keep_block)
 //   backward  k_band_back<NRB>: T_k^T = ( W_k^T - sum_I T_{k+1+I}^T L_{k+1+I,k} ) F_k, block columns from the last to the first
-//   mix       k_band_mix_matrix: M from the Gram matrix and Lw;  k_band_mix: stage = T M per pixel
+//   mix       k_band_mix_matrix: M from the Gram matrix and Lw;  k_band_mix: stage = T M per pixel (any number of leading
+//             right-hand sides in front of Y: the gradient's one residual, the diagnostics' k)
 #pragma once
 #include "sf_band_sweep.h"
 
@@ -177,29 +178,38 @@ int sf_launch_band_back(const double* fac, int n, int halfwidth, int batch, int 
     return SF_OK;
 }
 
-// The mix matrix of the Woodbury identity, one wave per walker.  With g = gram[1:,0], G = gram[1:,1:], S = I + G = L_S L_S^T:
-//   alpha = t_r - T_Y S^-1 g,   V = C^-1 X^T = T_Y S^-1 Lw^T      (X^T = Y^T Lw^T)
-// so [alpha, V] = T M with M[0][0] = 1, M[0][k] = 0, M[1 + j][0] = -(S^-1 g)_j, M[1 + j][1 + k] = (S^-1 Lw^T)_jk.
-// Lane c solves column c of S Z = [g, Lw^T].  A walker with info != 0 is not read.
-__global__ __launch_bounds__(64) void k_band_mix_matrix(const double* __restrict__ gram, const double* __restrict__ Lw, int m,
-                                                        const int* __restrict__ info, double* __restrict__ M) {
+// The mix matrix of the Woodbury identity, one wave per walker, for kr leading right-hand sides R in front of the m rows of Y
+// (the sweep's rows are [R; Y], nin = kr + m of them; the gradient's [r; Y] is kr = 1).  With g_c = gram[kr:, c],
+// G = gram[kr:, kr:], S = I + G = L_S L_S^T:
+//   alpha_c = t_c - T_Y S^-1 g_c  (c < kr),   V = C^-1 X^T = T_Y S^-1 Lw^T      (X^T = Y^T Lw^T; nv = m columns, or nv = 0: none)
+// so [alpha, V] = T M with the nin x nout matrix M, nout = kr + nv: M[r][c] = (r == c) for r < kr, M[kr + j][c] = -(S^-1 g_c)_j
+// for c < kr, M[kr + j][kr + k] = (S^-1 Lw^T)_jk.  Lane c solves column c of S Z = [g_0 .. g_{kr-1}, Lw^T].  A walker with
+// info != 0 is not read.  flag (may be NULL; the walkers' status, where k_woodbury has not looked at S): a non-positive pivot
+// of S sets SF_INFO_BAD_WEIGHT_COV there.
+#define SFB_MIX_MAX SFB_MIX_MAX_ROWS  // rows and columns of M: what three blocks of right-hand sides hold
+#define SFB_MIX_LD 49
+__global__ __launch_bounds__(64) void k_band_mix_matrix(const double* __restrict__ gram, const double* __restrict__ Lw, int kr, int m,
+                                                        int nv, const int* info, int* flag, double* __restrict__ M) {
     __shared__ double S[33 * 33];
-    __shared__ double Z[33 * 33];  // Z[j * 33 + c]
-    const int b = blockIdx.x, lane = threadIdx.x, nrhs = m + 1;
+    __shared__ double Z[32 * SFB_MIX_LD];  // Z[j * SFB_MIX_LD + c]
+    const int b = blockIdx.x, lane = threadIdx.x, nin = kr + m, nout = kr + nv;
     if (info[b] != 0) return;
-    const double* g = gram + (int64_t)b * nrhs * nrhs;
+    const double* g = gram + (int64_t)b * nin * nin;
     const double* lw = Lw + (int64_t)b * m * m;
     for (int e = lane; e < m * m; e += 64) {
         const int r = e / m, c = e - r * m;
-        S[r * 33 + c] = g[(r + 1) * nrhs + (c + 1)] + (r == c ? 1.0 : 0.0);
+        S[r * 33 + c] = g[(r + kr) * nin + (c + kr)] + (r == c ? 1.0 : 0.0);
     }
-    for (int e = lane; e < m * nrhs; e += 64) {
-        const int j = e / nrhs, c = e - j * nrhs;
-        Z[j * 33 + c] = c == 0 ? g[(j + 1) * nrhs] : (j <= c - 1 ? lw[(c - 1) * m + j] : 0.0);  // Lw^T[j][c - 1]
+    for (int e = lane; e < m * nout; e += 64) {
+        const int j = e / nout, c = e - j * nout;
+        Z[j * SFB_MIX_LD + c] = c < kr ? g[(j + kr) * nin + c] : (j <= c - kr ? lw[(c - kr) * m + j] : 0.0);  // Lw^T[j][c - kr]
     }
     __syncthreads();
+    int bad = 0;
     for (int j = 0; j < m; ++j) {  // S = L_S L_S^T in place (lower), as k_woodbury
-        const double rs = 1.0 / sqrt(S[j * 33 + j]);
+        const double p = S[j * 33 + j];
+        if (!(p > 0.0)) bad = 1;
+        const double rs = 1.0 / sqrt(p);
         __syncthreads();
         double lij = 0.0;
         if (lane > j && lane < m) {
@@ -212,51 +222,59 @@ __global__ __launch_bounds__(64) void k_band_mix_matrix(const double* __restrict
             for (int c = j + 1; c <= lane; ++c) S[lane * 33 + c] -= lij * S[c * 33 + j];
         __syncthreads();
     }
-    if (lane < nrhs) {
+    if (lane < nout) {
         const int c = lane;
         for (int j = 0; j < m; ++j) {  // L_S z = rhs
-            double v = Z[j * 33 + c];
-            for (int i = 0; i < j; ++i) v -= S[j * 33 + i] * Z[i * 33 + c];
-            Z[j * 33 + c] = v * S[j * 33 + j];
+            double v = Z[j * SFB_MIX_LD + c];
+            for (int i = 0; i < j; ++i) v -= S[j * 33 + i] * Z[i * SFB_MIX_LD + c];
+            Z[j * SFB_MIX_LD + c] = v * S[j * 33 + j];
         }
         for (int j = m - 1; j >= 0; --j) {  // L_S^T y = z
-            double v = Z[j * 33 + c];
-            for (int i = j + 1; i < m; ++i) v -= S[i * 33 + j] * Z[i * 33 + c];
-            Z[j * 33 + c] = v * S[j * 33 + j];
+            double v = Z[j * SFB_MIX_LD + c];
+            for (int i = j + 1; i < m; ++i) v -= S[i * 33 + j] * Z[i * SFB_MIX_LD + c];
+            Z[j * SFB_MIX_LD + c] = v * S[j * 33 + j];
         }
-        double* Mb = M + (int64_t)b * nrhs * nrhs;
-        Mb[c] = c == 0 ? 1.0 : 0.0;
-        for (int j = 0; j < m; ++j) Mb[(1 + j) * nrhs + c] = c == 0 ? -Z[j * 33 + c] : Z[j * 33 + c];
+        double* Mb = M + (int64_t)b * nin * nout;
+        for (int r = 0; r < kr; ++r) Mb[r * nout + c] = r == c ? 1.0 : 0.0;
+        for (int j = 0; j < m; ++j) Mb[(kr + j) * nout + c] = c < kr ? -Z[j * SFB_MIX_LD + c] : Z[j * SFB_MIX_LD + c];
     }
+    if (flag && bad && lane == 0) flag[b] = SF_INFO_BAD_WEIGHT_COV;  // (info[b] was 0)
 }
-// stage[b][k][i] = sum_j T[b][j][i] M[b][j][k], j ascending; pixels n .. npad - 1 are zero.  One thread per pixel.
+// stage[b][c][i] = (c < nself ? T[b][c][i] M[b][c][c] : 0) + sum_{j >= lead} T[b][j][i] M[b][j][c], j ascending, for the nin rows
+// of T and the nin x nout matrix M (the rows j < lead of a column hold its own unit entry or zeros: they are not multiplied
+// out); pixels n .. npad - 1 are zero.  One thread per pixel.
 __global__ __launch_bounds__(256) void k_band_mix(const double* __restrict__ T, const double* __restrict__ M, const int* __restrict__ info,
-                                                  int nrhs, int n, int npad, double* __restrict__ stage) {
-    __shared__ double Ms[33 * 33];
+                                                  int nin, int lead, int nself, int nout, int n, int npad, double* __restrict__ stage) {
+    __shared__ double Ms[SFB_MIX_MAX * SFB_MIX_MAX];
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (info[b] != 0) return;
-    for (int e = threadIdx.x; e < nrhs * nrhs; e += 256) Ms[e] = M[(int64_t)b * nrhs * nrhs + e];
+    for (int e = threadIdx.x; e < nin * nout; e += 256) Ms[e] = M[(int64_t)b * nin * nout + e];
     __syncthreads();
     if (i >= npad) return;
-    const double* Tb = T + (int64_t)b * nrhs * npad;
-    double* sb = stage + (int64_t)b * nrhs * npad;
-    for (int k = 0; k < nrhs; ++k) {
+    const double* Tb = T + (int64_t)b * nin * npad;
+    double* sb = stage + (int64_t)b * nout * npad;
+    for (int c = 0; c < nout; ++c) {
         double v = 0.0;
-        if (i < n)
-            for (int j = 0; j < nrhs; ++j) v += Tb[(int64_t)j * npad + i] * Ms[j * nrhs + k];
-        sb[(int64_t)k * npad + i] = v;
+        if (i < n) {
+            if (c < nself) v += Tb[(int64_t)c * npad + i] * Ms[c * nout + c];
+            for (int j = lead; j < nin; ++j) v += Tb[(int64_t)j * npad + i] * Ms[j * nout + c];
+        }
+        sb[(int64_t)c * npad + i] = v;
     }
 }
-// gram: [batch][(1 + m)^2] of the sweep; Lw: [batch][m][m]; T: [batch][1 + m][npad] of the backward sweep; Mwork: [batch][(1 + m)^2]
-int sf_launch_band_mix(const double* gram, const double* Lw, int m, const int* info, const double* T, int n, int npad, int batch,
-                       double* Mwork, double* stage, hipStream_t s) {
-    if (m < 1 || m > 32 || batch <= 0 || batch > 65535 || n <= 0 || npad < n) {
-        sf_set_error("band_mix: 1 .. 32 low-rank rows, 1 .. 65535 walkers");
+// gram: [batch][(kr + m)^2] of the sweep over [R; Y]; Lw: [batch][m][m] (not read with nv = 0); T: [batch][kr + m][npad] of the
+// backward sweep; Mwork: [batch][(kr + m)(kr + nv)]; stage: [batch][kr + nv][npad]; flag: see k_band_mix_matrix
+int sf_launch_band_mix(const double* gram, const double* Lw, int kr, int m, int nv, const int* info, int* flag, const double* T, int n,
+                       int npad, int batch, double* Mwork, double* stage, hipStream_t s) {
+    if (m < 1 || m > 32 || kr < 1 || kr + m > SFB_MIX_MAX || (nv != 0 && nv != m) || kr + nv > SFB_MIX_MAX || batch <= 0 ||
+        batch > 65535 || n <= 0 || npad < n) {
+        sf_set_error("band_mix: 1 .. 32 low-rank rows, at most %d rows of right-hand sides in all, 1 .. 65535 walkers", SFB_MIX_MAX);
         return SF_EINVAL;
     }
-    hipLaunchKernelGGL(k_band_mix_matrix, dim3(batch), dim3(64), 0, s, gram, Lw, m, info, Mwork);
+    hipLaunchKernelGGL(k_band_mix_matrix, dim3(batch), dim3(64), 0, s, gram, Lw, kr, m, nv, info, flag, Mwork);
     SF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_band_mix, dim3((npad + 255) / 256, batch), dim3(256), 0, s, T, Mwork, info, m + 1, n, npad, stage);
+    hipLaunchKernelGGL(k_band_mix, dim3((npad + 255) / 256, batch), dim3(256), 0, s, T, Mwork, info, kr + m, kr, kr, kr + nv, n, npad,
+                       stage);
     SF_LAUNCH_CHECK();
     return SF_OK;
 }

@@ -27,11 +27,23 @@ static sf_band_call band_call(const double* band, int64_t sband, int ldb, int ha
     return k;
 }
 // What the calls that share the likelihood's head differ in, beyond the layout (tiles or window) that the BandWork says
+// Caller right-hand sides R in place of the walker's own residual (sf_diagnose_banded_batch): the sweep then runs over the k + m
+// rows [R; Y] staged in buf, its Gram matrix goes to gram, and the capacitance step is left to the mix (sf_launch_band_mix with
+// flag): there is no squared distance, lnl is -logdet(Bd) / 2 (not a likelihood) and info what fill, emulator and sweep reported
+struct BandHeadRhs {
+    const double* d_rhs;
+    int k, ldr;
+    int64_t rhs_stride;
+    double *buf, *gram, *zero;  // (carve_band_diag: rhs, gram, zero)
+};
 struct BandHead {
     double* fac;                              // the sweep keeps its factor here (window only); NULL: it keeps nothing
     double *d_X, *d_resid, *d_log_scale;      // optional outputs of run_transforms
     double* lnl;                              // where sf_launch_finish leaves lnl / info
     int* info;
+    double* d_flux = nullptr;                 // one more of them
+    const BandHeadRhs* rhs = nullptr;         // NULL: the walker's own residual, [r; Y]
+    bool per_entry_fill = false;              // true: every entry of the band from its own pixel pair, no table per diagonal
 };
 // The head of the likelihood on the band solver: band fill, transforms, sweep, capacitance step, lnl / info.
 // The band fill depends on the covariance hyper-parameters only, the transforms on the stellar ones: the two run side by
@@ -66,19 +78,27 @@ static int banded_head(sf_ctx* c, const sf_model_desc* mdl, int B, const double*
             SF_CHECK(sf_launch_band_fill(f, B, bw.tiles, bw.ldb, halfwidth, lda_t, (int64_t)(c->npad + 64) * lda_t, w.info_c, bw.gtab, sf,
                                          sf_band_tiles_wt(halfwidth)));
         } else
-            SF_CHECK(sf_launch_band_fill(f, B, bw.band, halfwidth + 1, halfwidth, bw.ldb, sband, w.info_c, bw.gtab, sf));
+            SF_CHECK(sf_launch_band_fill(f, B, bw.band, halfwidth + 1, halfwidth, bw.ldb, sband, w.info_c,
+                                         h.per_entry_fill ? nullptr : bw.gtab, sf));
     }
     if (sf != s) SF_HIP(hipEventRecord(aux->join, sf));
     {
         ProfScope ps(s, PS_TRANSFORM);
-        SF_CHECK(run_transforms(c, mdl, B, d_params, w, nullptr, h.d_X, h.d_resid, h.d_log_scale, true, s));
+        SF_CHECK(run_transforms(c, mdl, B, d_params, w, h.d_flux, h.d_X, h.d_resid, h.d_log_scale, true, s));
+    }
+    sf_band_rhs rhs = {w.Y, (int64_t)c->mpad * c->npad, c->npad, c->m + 1, w.resid, c->npad};
+    if (h.rhs) {
+        const BandHeadRhs& r = *h.rhs;
+        SF_CHECK(sf_launch_band_diag_stage(r.d_rhs, r.ldr, r.rhs_stride, w.Y, (int64_t)c->mpad * c->npad, c->n, c->npad, r.k, c->m, B,
+                                           r.buf, s));
+        SF_HIP(hipMemsetAsync(r.zero, 0, sizeof(double) * (size_t)B, s));
+        rhs = sf_band_rhs{r.buf, (int64_t)(r.k + c->m) * c->npad, c->npad, r.k + c->m, nullptr, 0};
     }
     if (sf != s) SF_HIP(hipStreamWaitEvent(s, aux->join, 0));
     {
         ProfScope ps(s, PS_POTRF);
-        const sf_band_call k = band_call(bw.band, sband, bw.ldb, halfwidth, bw.tiles ? c->n : n16, B,
-                                         sf_band_rhs{w.Y, (int64_t)c->mpad * c->npad, c->npad, c->m + 1, w.resid, c->npad},
-                                         bw.logdet_band, bw.gram, w.info_c);
+        const sf_band_call k = band_call(bw.band, sband, bw.ldb, halfwidth, bw.tiles ? c->n : n16, B, rhs, bw.logdet_band,
+                                         h.rhs ? h.rhs->gram : bw.gram, w.info_c);
         if (bw.tiles) SF_CHECK(sf_launch_potrf_band(k, c->npad, bw.tiles, s));
         else if (h.fac) SF_CHECK(sf_launch_band_keep(k, h.fac, s));
         else if (sf_band_twisted_applicable(k.n, halfwidth, B)) SF_CHECK(sf_launch_band_forms_twisted(k, bw.twist, s));
@@ -86,6 +106,7 @@ static int banded_head(sf_ctx* c, const sf_model_desc* mdl, int B, const double*
     }
     {
         ProfScope ps(s, PS_SOLVE);
+        if (h.rhs) return sf_launch_finish(B, bw.logdet_band, h.rhs->zero, w.info_e, w.info_c, h.lnl, h.info, s);
         SF_CHECK(sf_launch_woodbury(bw.gram, c->m + 1, B, bw.logdet_band, w.logdet, w.sqmah, w.info_c, s));
         SF_CHECK(sf_launch_finish(B, w.logdet, w.sqmah, w.info_e, w.info_c, h.lnl, h.info, s));
     }
@@ -281,7 +302,7 @@ static int banded_grad_call(const BandGradCall& k, sf_ctx* c, const sf_model_des
         ProfScope ps(s, PS_SOLVE);
         // T = Bd^-1 [r, Y^T], then [alpha, V] = T M in the staging area
         SF_CHECK(sf_launch_band_back(g.fac, n16, halfwidth, B, nrhs, aw.info, g.T, c->npad, sstage, s));
-        SF_CHECK(sf_launch_band_mix(bw.gram, w.Lw, c->m, aw.info, g.T, c->n, c->npad, B, g.M, aw.stage, s));
+        SF_CHECK(sf_launch_band_mix(bw.gram, w.Lw, 1, c->m, c->m, aw.info, nullptr, g.T, c->n, c->npad, B, g.M, aw.stage, s));
     }
     if (nslots > 0) {
         const sf_mean_grad_args ma = mean_grad_kernel_args(c, h_slots, nslots, w, aw, d_grad, grad_stride);
@@ -292,7 +313,7 @@ static int banded_grad_call(const BandGradCall& k, sf_ctx* c, const sf_model_des
     if (want_cov) {
         // the band of Sigma = Bd^-1 and Vs of C^-1 = Sigma - Vs Vs^T, then the contraction with dC / d theta over the band
         SF_CHECK(sf_launch_band_selinv(g.fac, n16, halfwidth, B, nrhs, aw.info, g.sigma, bw.ldb, (int64_t)n16 * bw.ldb, s));
-        SF_CHECK(sf_launch_band_vs(bw.gram, c->m, aw.info, g.T, c->n, c->npad, B, g.M2, g.stage2, s));
+        SF_CHECK(sf_launch_band_vs(bw.gram, 1, c->m, 1, aw.info, g.T, c->n, c->npad, B, g.M2, g.stage2, s));
         SF_CHECK(sf_launch_band_cov_grad(fill_args(c, mdl, d_params, w), B, g.sigma, bw.ldb, (int64_t)n16 * bw.ldb, halfwidth, aw.stage,
                                          g.stage2 + c->npad, c->npad, sstage, c->m, aw.info, g.part, d_grad + nslots, grad_stride, s));
     }
@@ -320,4 +341,98 @@ extern "C" int sf_loglike_banded_grad_batch(sf_ctx* c, const sf_model_desc* mdl,
                                             double* d_resid, int* d_info, void* d_work, size_t work_bytes, void* stream) {
     return banded_grad_call(GRAD_CALL, c, mdl, B, d_params, halfwidth, h_slots, nslots, want_cov, d_lnl, d_grad, grad_stride, d_resid,
                             d_info, d_work, work_bytes, (hipStream_t)stream);
+}
+
+// ----------------------------------------------------------------------------------- residual diagnostics on the band solver
+static const char* const DIAGNOSE = "sf_diagnose_banded_batch";
+extern "C" int sf_diagnose_banded_max_nrhs(const sf_ctx* c, int halfwidth) {
+    if (!c || !c->n) return SF_EINVAL;
+    if (!c->monotonic) return 0;
+    for (int k = SFB_MIX_MAX_ROWS - c->m; k >= 1; --k)
+        if (sfb_admit(halfwidth, c->m + k) == SFB_WINDOW) return k;
+    return 0;
+}
+// what the call refuses on its counts, context and model; say == false: silently (the size query)
+static int diagnose_counts_ok(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth, int nrhs, bool say) {
+    if (B <= 0 || B > 65535 || nrhs < 1) {
+        if (say) sf_set_error("%s: B=%d must lie in 1 .. 65535 and nrhs=%d be positive", DIAGNOSE, B, nrhs);
+        return SF_EINVAL;
+    }
+    if (model_ok(c, mdl)) return SF_EINVAL;
+    if (!c->n || !c->monotonic) {
+        if (say) sf_set_error("%s: the band solver needs a strictly increasing wavelength grid (use sf_pointwise_batch / sf_decompose_batch)",
+                              DIAGNOSE);
+        return SF_EINVAL;
+    }
+    if (c->m < 1 || c->m > 32 || halfwidth < 0 || nrhs > SFB_MIX_MAX_ROWS || sfb_admit(halfwidth, c->m + nrhs) != SFB_WINDOW) {
+        if (say)
+            sf_set_error("%s: %d low-rank rows + %d right-hand sides at half-width %d exceed the LDS window (at most "
+                         "sf_diagnose_banded_max_nrhs = %d per call; or use sf_pointwise_batch / sf_decompose_batch)",
+                         DIAGNOSE, c->m, nrhs, halfwidth, halfwidth < 0 ? 0 : sf_diagnose_banded_max_nrhs(c, halfwidth));
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_diagnose_banded_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth, int nrhs,
+                                                     int want_cinv_diag, int want_comp) {
+    if (diagnose_counts_ok(c, mdl, B, halfwidth, nrhs, false)) return 0;
+    return carve_band_diag(c, mdl, B, halfwidth, nrhs, want_cinv_diag != 0, want_comp != 0, nullptr, 0,
+                           carve(c, mdl, B, nullptr, 0, false).bytes).bytes;
+}
+// The likelihood's head with a keeping sweep over [R; Y] (or the gradient call's [r; Y]), the backward sweep and the mix for
+// k right-hand sides: alpha.  The band is filled entry by entry: on a log-uniform grid the likelihood's table of the global
+// kernel per diagonal (k_band_gtab) is off by the rounding of the grid, ~3e-11 in r, which a narrow kernel turns into element
+// errors far beyond the 1e-13 that diag(C^-1) is held to against the oracle's matrix; the likelihood's 1e-10 does not notice.  Then what is asked for: the selected inversion, Vs and the read-out of diag(C^-1); the diagonal
+// of C; the split of alpha by covariance component
+extern "C" int sf_diagnose_banded_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int halfwidth,
+                                        const double* d_rhs, int nrhs, int ldr, int64_t rhs_stride, double* d_alpha,
+                                        double* d_cinv_diag, double* d_cov_diag, double* d_comp, double* d_flux, int* d_info,
+                                        void* d_work, size_t work_bytes, void* stream) {
+    if (!d_params || !d_alpha || !d_work) {
+        sf_set_error("%s: d_params, d_alpha and d_work are required", DIAGNOSE);
+        return SF_EINVAL;
+    }
+    if (d_rhs ? rhs_stride < 0 : nrhs != 1) {
+        sf_set_error("%s: rhs_stride >= 0 with d_rhs, nrhs == 1 without", DIAGNOSE);
+        return SF_EINVAL;
+    }
+    SF_CHECK(diagnose_counts_ok(c, mdl, B, halfwidth, nrhs, true));
+    if (d_rhs && ldr < c->n) {
+        sf_set_error("%s: ldr=%d < n (%d)", DIAGNOSE, ldr, c->n);
+        return SF_EINVAL;
+    }
+    const Work w = carve(c, mdl, B, d_work, work_bytes, false);
+    const BandDiagWork g = carve_band_diag(c, mdl, B, halfwidth, nrhs, d_cinv_diag != nullptr, d_comp != nullptr, d_work, work_bytes,
+                                           w.bytes);
+    SF_CHECK(work_fits(work_bytes, g.bytes));
+    const BandWork& bw = g.bw;
+    const AppliedWork& aw = g.aw;
+    hipStream_t s = (hipStream_t)stream;
+    const BandHeadRhs own = {d_rhs, nrhs, ldr, rhs_stride, g.rhs, g.gram, g.zero};
+    SF_CHECK(banded_head(c, mdl, B, d_params, halfwidth, w, bw,
+                         BandHead{g.fac, nullptr, nullptr, nullptr, aw.lnl, aw.info, d_flux, d_rhs ? &own : nullptr, true}, s));
+    const int n16 = (c->n + 15) / 16 * 16, m = c->m, nin = nrhs + m;  // (the sweep's order: whole blocks)
+    const double* gram = d_rhs ? g.gram : bw.gram;
+    {
+        ProfScope ps(s, PS_SOLVE);
+        // T = Bd^-1 [R^T, Y^T], then alpha = T M in the staging area (with caller right-hand sides the mix is the first to
+        // look at the capacitance matrix: it completes the status)
+        SF_CHECK(sf_launch_band_back(g.fac, n16, halfwidth, B, nin, aw.info, g.T, c->npad, (int64_t)nin * c->npad, s));
+        SF_CHECK(sf_launch_band_mix(gram, w.Lw, nrhs, m, 0, aw.info, d_rhs ? aw.info : nullptr, g.T, c->n, c->npad, B, g.M, aw.stage, s));
+    }
+    SF_CHECK(sf_launch_apply_export(aw.stage, aw.info, c->n, c->npad, nrhs, B, d_alpha, s));
+    if (d_cinv_diag) {
+        // the band of Sigma = Bd^-1 and Vs of C^-1 = Sigma - Vs Vs^T
+        SF_CHECK(sf_launch_band_selinv(g.fac, n16, halfwidth, B, nin, aw.info, g.sigma, bw.ldb, (int64_t)n16 * bw.ldb, s));
+        SF_CHECK(sf_launch_band_vs(gram, nrhs, m, 0, aw.info, g.T, c->n, c->npad, B, g.M2, g.vs, s));
+        SF_CHECK(sf_launch_band_cinv_diag(g.sigma, bw.ldb, (int64_t)n16 * bw.ldb, g.vs, c->npad, (int64_t)m * c->npad, m, aw.info, c->n,
+                                          B, d_cinv_diag, s));
+    }
+    if (d_cov_diag)
+        SF_CHECK(sf_launch_band_cov_diag(bw.band, bw.ldb, (int64_t)c->npad * bw.ldb, w.Y, c->npad, (int64_t)c->mpad * c->npad, m,
+                                         aw.info, c->n, B, d_cov_diag, s));
+    if (d_comp)  // K_k alpha with the Y, parameter rows and sigma the head's transform chain and fill worked on
+        SF_CHECK(sf_launch_cov_matvec(fill_args(c, mdl, d_params, w), m, aw.stage, c->npad, nrhs, B, aw.yv, aw.info, d_comp, s));
+    if (d_info) SF_HIP(hipMemcpyAsync(d_info, aw.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return SF_OK;
 }

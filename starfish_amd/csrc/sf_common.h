@@ -247,7 +247,7 @@ int sf_launch_global_cov(const double* wave, int n, double amp, double ls, doubl
 int sf_launch_local_cov(const double* wave, int n, double amp, double mu, double sigma, int accumulate,
                         double* out, hipStream_t s);
 
-// sf_band.hip (layers: sf_band_shape.h, sf_band_window.h, sf_band_sweep.h, sf_band_twist.h, sf_band_woodbury.h, sf_band_solve.h, sf_band_selinv.h): banded
+// sf_band.hip (layers: sf_band_shape.h, sf_band_window.h, sf_band_sweep.h, sf_band_twist.h, sf_band_woodbury.h, sf_band_solve.h, sf_band_selinv.h, sf_band_diag.h): banded
 // Cholesky + forward substitution of (1 + m) right-hand sides -> logdet, Gram matrix
 // The right-hand sides of a batch: row r of matrix b at rhs + b * srhs + r * ldr.  Optional separate source for row 0 (the
 // residual lives in its own buffer in the fused path): when rhs0 is given, rows 1.. come from rhs rows 0..
@@ -284,20 +284,34 @@ int sf_launch_woodbury(const double* gram, int nrhs, int batch, const double* lo
 // sf_band_solve.h: the full solve on the LDS window (sfb_admit(...) == SFB_WINDOW only).  The keeping sweep is
 // sf_launch_band_forms' single sweep, which also stores the factor and the forward-substituted right-hand sides in fac
 // (sfb_keep_doubles(n, nbr, nrb) doubles per matrix); the backward sweep turns them into x[b * sx + r * ldx + i] = (A^-1 rhs_r)_i
-// (NaN where info[b] != 0); the mix forms [alpha, V] = C^-1 [r, X^T] = T M in the mean gradient's staging layout
-// [batch][1 + m][npad] from T = Bd^-1 [r, Y^T] (same layout), the sweep's Gram matrix and Lw (Mwork: [batch][(1 + m)^2])
+// (NaN where info[b] != 0); the mix forms [alpha, V] = C^-1 [R^T, X^T] = T M in the staging layout [batch][kr + nv][npad] from
+// T = Bd^-1 [R^T, Y^T] ([batch][kr + m][npad]: kr right-hand sides in front of Y; the mean gradient's residual is kr = 1), the
+// sweep's Gram matrix and Lw (nv = m: with V; nv = 0: alpha alone, Lw not read).  Mwork: [batch][(kr + m)(kr + nv)]; flag: NULL,
+// or the walkers' status, which a non-positive pivot of the capacitance matrix sets to SF_INFO_BAD_WEIGHT_COV
 int sf_launch_band_keep(const sf_band_call& c, double* fac, hipStream_t s);
 int sf_launch_band_back(const double* fac, int n, int halfwidth, int batch, int nrhs, const int* info, double* x, int ldx, int64_t sx,
                         hipStream_t s);
-int sf_launch_band_mix(const double* gram, const double* Lw, int m, const int* info, const double* T, int n, int npad, int batch,
-                       double* Mwork, double* stage, hipStream_t s);
+int sf_launch_band_mix(const double* gram, const double* Lw, int kr, int m, int nv, const int* info, int* flag, const double* T, int n,
+                       int npad, int batch, double* Mwork, double* stage, hipStream_t s);
 // sf_band_selinv.h: the band of Sigma = A^-1 from the records of sf_launch_band_keep (same n, halfwidth, nrhs), by selected
 // inversion: out[b * sout + i * ldo + d] = Sigma[i][i - d], 0 <= d <= min(i, halfwidth), i < n (NaN where info[b] != 0); and
-// Vs = T_Y L_S^-T of C^-1 = Sigma - Vs Vs^T in rows 1 .. m of stage2 (the staging layout of sf_launch_band_mix; row 0 is zero)
+// Vs = T_Y L_S^-T of C^-1 = Sigma - Vs Vs^T in rows co .. co + m - 1 of stage2 ([batch][co + m][npad]; co = kr = 1: the staging
+// layout of the gradient's sf_launch_band_mix, row 0 zero; co = 0: the m columns alone), Mwork: [batch][(kr + m)(co + m)]
 int sf_launch_band_selinv(const double* fac, int n, int halfwidth, int batch, int nrhs, const int* info, double* out, int ldo,
                           int64_t sout, hipStream_t s);
-int sf_launch_band_vs(const double* gram, int m, const int* info, const double* T, int n, int npad, int batch, double* Mwork,
-                      double* stage2, hipStream_t s);
+int sf_launch_band_vs(const double* gram, int kr, int m, int co, const int* info, const double* T, int n, int npad, int batch,
+                      double* Mwork, double* stage2, hipStream_t s);
+// sf_band_diag.h: what the diagnostics on the band solver add.  The rows [R; Y] of a sweep with caller right-hand sides:
+// buf[b][r] = rhs[b * rhs_stride + r * ldr + 0:n) padded with zeros to npad for r < kr, then the m rows of Y
+// (Y[b * sy + j * npad + 0:npad)).  cinv_diag[b][i] = sigma[b * ssigma + i * lds] - sum_c vs[b * svs + c * ldv + i]^2, c
+// ascending; cov_diag[b][i] = band[b * sband + i * ldb] + sum_j Y[b * sy + j * ldy + i]^2, j ascending: the diagonal of
+// C = Bd + Y^T Y as it is factorised; both [batch][n], NaN where info[b] != 0
+int sf_launch_band_diag_stage(const double* rhs, int ldr, int64_t rhs_stride, const double* Y, int64_t sy, int n, int npad, int kr,
+                              int m, int batch, double* buf, hipStream_t s);
+int sf_launch_band_cinv_diag(const double* sigma, int lds, int64_t ssigma, const double* vs, int ldv, int64_t svs, int m,
+                             const int* info, int n, int batch, double* cinv_diag, hipStream_t s);
+int sf_launch_band_cov_diag(const double* band, int ldb, int64_t sband, const double* Y, int ldy, int64_t sy, int m, const int* info,
+                            int n, int batch, double* cov_diag, hipStream_t s);
 // sf_fill.hip (sf_band_cov_grad.h): the covariance gradient contracted over the band, slots and part as sf_launch_cov_grad;
 // sigma: the band of Bd^-1 (lds doubles per row, ssigma per matrix); alpha[b * sstage + i]; vs[b * sstage + c * ldv + i], c < m
 int sf_launch_band_cov_grad(const sf_fill_args& f, int batch, const double* sigma, int lds, int64_t ssigma, int halfwidth,

@@ -425,10 +425,10 @@ static int banded_multi_mix(const BandMultiGradWork& G, const Work& wc, const La
         const int nb = std::min(units - lo, 65535);
         const size_t u = (size_t)u0 + lo;
         if (!vs)
-            SF_CHECK(sf_launch_band_mix(G.gram + u * ng, wc.Lw + (size_t)lo * L.m * L.m, L.m, info + lo, G.T + u * unit, G.n16, L.npad, nb,
+            SF_CHECK(sf_launch_band_mix(G.gram + u * ng, wc.Lw + (size_t)lo * L.m * L.m, 1, L.m, L.m, info + lo, nullptr, G.T + u * unit, G.n16, L.npad, nb,
                                         G.M + u * ng, G.stage + u * unit, s));
         else
-            SF_CHECK(sf_launch_band_vs(G.gram + u * ng, L.m, info + lo, G.T + u * unit, G.n16, L.npad, nb, G.M2 + u * ng,
+            SF_CHECK(sf_launch_band_vs(G.gram + u * ng, 1, L.m, 1, info + lo, G.T + u * unit, G.n16, L.npad, nb, G.M2 + u * ng,
                                        G.stage2 + u * unit, s));
     }
     return SF_OK;

@@ -267,6 +267,43 @@ static BandGradWork carve_band_grad(const sf_ctx* c, const sf_model_desc* mdl, i
     return g;
 }
 
+// sf_diagnose_banded_batch with k = nrhs right-hand sides, behind the Work of the same call: the band solver's buffers
+// (carve_band), the applied layout (carve_applied: the staging area [B][k][npad] that ends up holding alpha, lnl, info and, with
+// want_comp, yv), then the pieces of carve_band_grad for a sweep over k + m rows: fac, T: [B][k + m][npad] = Bd^-1 [R^T, Y^T],
+// M: [B][(k + m) k].  Then what caller right-hand sides need (the size query does not know whether there are any): rhs:
+// [B][k + m][npad], the sweep's rows [R; Y]; gram: [B][(k + m)^2]; zero: [B] zeros (the squared distance of a call that has no
+// residual of its own).  Behind them, with want_cinv_diag (NULL otherwise), sigma: the band of Bd^-1, [B][n16][bw.ldb]; M2:
+// [B][(k + m) m]; vs: [B][m][npad], the columns of Vs
+struct BandDiagWork {
+    BandWork bw;
+    AppliedWork aw;
+    double *fac, *T, *M;
+    double *rhs, *gram, *zero;
+    double *sigma, *M2, *vs;
+    size_t bytes;
+};
+static BandDiagWork carve_band_diag(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth, int k, bool want_cinv_diag,
+                                    bool want_comp, void* p, size_t cap, size_t base_bytes) {
+    BandDiagWork g{};
+    const int nin = k + c->m, n16 = (c->n + 15) / 16 * 16;
+    g.bw = carve_band(c, B, halfwidth, p, cap, base_bytes);
+    g.aw = carve_applied(c, mdl, B, k, want_comp ? AW_YV : 0, p, cap, g.bw.bytes);
+    Carve w(p, cap, g.aw.bytes);
+    g.fac = w.take<double>((size_t)B * sfb_keep_doubles(n16, sfb_nbr(halfwidth), sfb_nrb(nin)));
+    g.T = w.take<double>((size_t)B * nin * c->npad);
+    g.M = w.take<double>((size_t)B * nin * k);
+    g.rhs = w.take<double>((size_t)B * nin * c->npad);
+    g.gram = w.take<double>((size_t)B * nin * nin);
+    g.zero = w.take<double>((size_t)B);
+    if (want_cinv_diag) {
+        g.sigma = w.take<double>((size_t)B * n16 * g.bw.ldb);
+        g.M2 = w.take<double>((size_t)B * nin * c->m);
+        g.vs = w.take<double>((size_t)B * c->m * c->npad);
+    }
+    g.bytes = sf_align_up(w.off, 256);
+    return g;
+}
+
 // ------------------------------------------------------------------- multi-order gradient
 // (sf_loglike_multi_grad_batch_md; behind the Work of the same call: base_bytes = its size)  Rows are laid out with the
 // group's common npad (L.npad), not an order's own.  For all U units: the staging area, nrhs right-hand sides of npad doubles
