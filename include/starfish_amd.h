@@ -408,6 +408,27 @@ int sf_debug_loglike_mean_grad_contract(sf_ctx* ctx, const sf_model_desc* model,
                                         const int* h_slots, int nslots, double* d_grad, int grad_stride, void* d_work,
                                         size_t work_bytes, void* stream);
 
+/* The Fisher information of the mean-flux parameters at fixed covariance,
+ *     F_ij = fdot_i^T C^-1 fdot_j,   fdot_j = d f / d theta_j,
+ * for the columns h_slots of sf_loglike_mean_grad_batch (same columns, same slot checks): the inverse of F is the Laplace
+ * covariance of vsini, vz, log_scale, Av, cheb:k and the grid parameters; the mean / covariance cross block of a Gaussian's
+ * Fisher matrix is zero.  This is the Gauss-Newton, fixed-covariance matrix: the term 1/2 tr(C^-1 dC_i C^-1 dC_j) that a grid
+ * parameter has because X sits inside the emulator's covariance is left out, and so is the block of the covariance
+ * hyper-parameters.  One pixel pass writes the tangent columns J (the row tangents of the gradient's pixel pass; a grid column
+ * is dmu^T X; zero for a walker the transform chain flagged) as the right-hand sides of the likelihood's sequence,
+ * SF_APPLY_LINV turns them into Z = L^-1 J, and F = Z^T Z is summed per 256-pixel block and then over the blocks in ascending
+ * order, without atomics.  d_fisher[b*fisher_stride + i*nslots + j], fisher_stride >= nslots^2; the lower triangle is computed
+ * and mirrored, so F_ij and F_ji are the same bits.  d_lnl and d_info (may be NULL) have sf_loglike_batch's bits; a walker with
+ * info != 0 gets a NaN matrix.  A repeated call and a call on a sub-batch give the same bits; a subset of the slots agrees to
+ * rounding, bit equality is not promised there.  SF_EINVAL before anything is enqueued for what sf_loglike_mean_grad_batch
+ * refuses and for fisher_stride < nslots^2; sf_fisher_mean_workspace_bytes is 0 for the counts and models the call refuses.
+ * The workspace is that of sf_loglike_mean_grad_batch with nslots right-hand sides plus one double per (256-pixel block, pair
+ * of slots).  Never synchronises. */
+size_t sf_fisher_mean_workspace_bytes(const sf_ctx* ctx, const sf_model_desc* model, int B, int nslots);
+int sf_fisher_mean_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, const int* h_slots, int nslots,
+                         double* d_lnl, double* d_fisher, int fisher_stride, int* d_info, void* d_work, size_t work_bytes,
+                         void* stream);
+
 /* ---- multi-order batches (reference: the multi-order container
  * Starfish/spectrum.py:96-115, orders independent docs/intro.rst:71-73, EchelleModel stub
  * Starfish/models/echelle_model.py:1-2) -------------------------------------------------------------
@@ -634,6 +655,27 @@ int sf_diagnose_banded_batch(sf_ctx* ctx, const sf_model_desc* model, int B, con
                              const double* d_rhs, int nrhs, int ldr, int64_t rhs_stride, double* d_alpha, double* d_cinv_diag,
                              double* d_cov_diag, double* d_comp, double* d_flux, int* d_info, void* d_work, size_t work_bytes,
                              void* stream);
+
+/* The Fisher matrix of sf_fisher_mean_batch (same h_slots, d_fisher layout, slot checks and NaN matrices) on the band + Woodbury
+ * solver, from ONE sweep: band fill and transforms as sf_loglike_banded_batch, then the sweep -- the likelihood's, not the keeping
+ * one, twisted where that pays -- over the 1 + m + nslots rows [r; Y; J].  With its Gram matrix G and S = I + G_YY = L_S L_S^T,
+ *     F = G_JJ - U^T U,   U = L_S^-1 G_YJ   (the sum over the m rows of U ascending),
+ * so there is no kept factor, no backward sweep and no N x N matrix.  d_lnl and d_info come from the leading (1 + m)^2 block of
+ * the same Gram matrix through the capacitance step of sf_loglike_banded_batch; d_resid (may be NULL): [B][n], model minus data.
+ * halfwidth: at most what the LDS window takes with 1 + m + nslots rows (144 up to 16 rows, 128 up to 32, 112 up to 48) --
+ * beyond it SF_EINVAL (use sf_fisher_mean_batch; the bordered-tile path of wide bands has no Fisher call); a walker whose
+ * support is wider than halfwidth gets SF_INFO_BANDWIDTH, -inf and a NaN matrix.  sf_fisher_banded_max_slots: the largest nslots
+ * (at most SF_MEAN_GRAD_MAX_SLOTS) whose rows fit the window at this half-width, 0 if none does, SF_EINVAL for a bad context.
+ * Values agree with the dense call to rounding, not bit for bit.  A repeated call and a call on a sub-batch at the same
+ * half-width and slots give the same bits.  A SUBSET OF THE SLOTS AGREES TO ROUNDING ONLY: the number of 16-row blocks picks
+ * another instantiation of the sweep, so bit equality is not promised there.  SF_EINVAL before anything is enqueued as for the
+ * dense call, for a null d_work, a grid that is not strictly increasing and a half-width outside the window;
+ * sf_fisher_banded_mean_workspace_bytes is 0 for the same counts.  Never synchronises. */
+int sf_fisher_banded_max_slots(const sf_ctx* ctx, int halfwidth);
+size_t sf_fisher_banded_mean_workspace_bytes(const sf_ctx* ctx, const sf_model_desc* model, int B, int halfwidth, int nslots);
+int sf_fisher_banded_mean_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, int halfwidth,
+                                const int* h_slots, int nslots, double* d_lnl, double* d_fisher, int fisher_stride,
+                                double* d_resid, int* d_info, void* d_work, size_t work_bytes, void* stream);
 
 /* Timing hooks for bench.py (process-global, not thread-safe): when enabled, the batched calls
  * record HIP events on the caller's stream around each stage and around every MFMA update launch.

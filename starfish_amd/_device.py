@@ -1327,6 +1327,77 @@ class DeviceOrder:
                 out[key][idx] = v
         return finish_structured(out, fits, solver, lambda rest: dense(rows[rest]))
 
+    # ------------------------------------------------------------------ Fisher information in the mean-flux parameters
+    def fisher_mean_workspace_bytes(self, md, B, nslots):
+        return self._size_query("fisher_mean_", md, B, nslots)
+
+    def fisher_banded_mean_workspace_bytes(self, md, B, halfwidth, nslots):
+        return self._size_query("fisher_banded_mean_", md, B, halfwidth, nslots)
+
+    def fisher_banded_max_slots(self, halfwidth):
+        """Most columns one sf_fisher_banded_mean_batch call takes at this half-width (0: none)."""
+        return max(int(self.lib.sf_fisher_banded_max_slots(self.ctx, int(halfwidth))), 0) if self.n else 0
+
+    def _run_fisher(self, name, md, params, lead, nslots, resid, workspace_bytes, max_chunk):
+        """:meth:`_run_chunked` for ``sf_<name>(ctx, &md, B, P, *lead, lnl, fisher, nslots^2, [resid,] info, ws, ...)``.
+        ``resid``: None -- the call has no such argument (the dense one); False -- NULL; True -- a (B, n) buffer, returned
+        under "resid" (model minus data)."""
+        with _torch().cuda.device(self.dev):
+            P = self._rows(params)
+            buffers, download = self._outputs(int(P.shape[0]), {"lnl": (), "fisher": (nslots, nslots)}, bool(resid))
+
+            def args(bufs, lo, hi):
+                (lnl, fisher), info, flux = bufs
+                tail = () if resid is None else (flux[lo:hi] if resid else None,)
+                return (*lead, lnl[lo:hi], fisher[lo:hi], nslots * nslots, *tail, info[lo:hi])
+
+            def named(bufs):
+                res = download(bufs)
+                if resid:
+                    res["resid"] = res.pop("flux")
+                return res
+
+            # (a size of 0: the call refuses its arguments and says why -- it gets a workspace that is not NULL to say it)
+            return self._run_chunked(name, md, P, max_chunk, lambda units: max(workspace_bytes(units), 256), buffers, args, named)
+
+    def fisher_mean(self, md, params, slots, solver="dense", max_chunk=None):
+        """The likelihood and the Fisher information of the mean-flux parameters at fixed covariance, ``F_ij = fdot_i^T C^-1
+        fdot_j`` with ``fdot_j = d f / d theta_j`` (sf_fisher_mean_batch).  This is the Gauss-Newton matrix: the term
+        ``1/2 tr(C^-1 dC_i C^-1 dC_j)`` of a grid parameter (X sits inside the emulator's covariance) is left out.  params, slots:
+        as for :meth:`loglike_mean_grad`.  Returns dict of numpy arrays: lnl (B,), fisher (B, p, p) in the order of ``slots``,
+        bit-symmetric, NaN where info != 0, and info (B,).  Chunked and retried like :meth:`loglike_mean_grad`.
+
+        solver: "dense"  -- the dense factor, ``F = Z^T Z`` with ``Z = L^-1 J`` (lnl and info with :meth:`loglike`'s bits);
+                "banded" -- ONE sweep of the band + Woodbury solver over the rows [r; Y; J] (sf_fisher_banded_mean_batch), one
+                            half-width for every chunk; agrees with the dense call to rounding.  Walkers whose covariance
+                            support exceeds the LDS window at this row count come back with info = -4;
+                "auto"   -- banded for the walkers whose half-width bound fits that window, dense for the rest and for
+                            walkers with the internal status, merged by row."""
+        check_solver(solver)
+        slots = [int(v) for v in slots]
+        nslots = len(slots)
+        if not nslots:
+            raise ValueError("no column to take the Fisher information in")
+        h_slots = (C.c_int * nslots)(*slots)
+        if solver == "dense":
+            return self._run_fisher("fisher_mean_batch", md, params, (h_slots, nslots), nslots, None,
+                                    lambda units: self.fisher_mean_workspace_bytes(md, units, nslots), max_chunk)
+        rows, hw = self._host_rows_and_bound(md, params)
+        # "banded": every walker the window of the likelihood's 1 + m rows takes, at the group's largest bound -- the library
+        # refuses the call (ValueError) if that lies beyond the window at 1 + m + p rows; "auto": only the walkers that fit there
+        fits = hw <= self.banded_window_halfwidth()
+        if solver == "auto":
+            fits = np.array([self.fisher_banded_max_slots(int(v)) >= nslots for v in hw], dtype=bool)
+        out = refused_output(rows.shape[0], dict(fisher=(nslots, nslots)))
+        idx = np.nonzero(fits)[0]
+        if idx.size:
+            W = int(hw[idx].max())
+            got = self._run_fisher("fisher_banded_mean_batch", md, rows[idx], (W, h_slots, nslots), nslots, False,
+                                   lambda units: self.fisher_banded_mean_workspace_bytes(md, units, W, nslots), max_chunk)
+            for key, v in got.items():
+                out[key][idx] = v
+        return finish_structured(out, fits, solver, lambda rest: self.fisher_mean(md, rows[rest], slots, "dense", max_chunk))
+
     def loglike_device(self, md, P_dev, out_lnl, info=None):
         """Enqueue-only variant for bench.py: device tensors in/out, no synchronisation."""
         self._call("loglike_batch", md, int(P_dev.shape[0]), P_dev, out_lnl, None, None, None, None, info)

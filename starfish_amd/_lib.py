@@ -176,6 +176,17 @@ SIGNATURES = {
         C.c_int,
         [_VP, C.POINTER(ModelDesc), C.c_int, _VP, c_int_p, C.c_int, _VP, C.c_int, _VP, C.c_size_t, _VP],
     ),
+    "sf_fisher_mean_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int]),
+    "sf_fisher_mean_batch": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, c_int_p, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_size_t, _VP],
+    ),
+    "sf_fisher_banded_max_slots": (C.c_int, [_VP, C.c_int]),
+    "sf_fisher_banded_mean_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int, C.c_int]),
+    "sf_fisher_banded_mean_batch": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, C.c_int, c_int_p, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_size_t, _VP],
+    ),
     "sf_debug_decompose_matvec": (
         C.c_int,
         [_VP, C.POINTER(ModelDesc), C.c_int, _VP, C.c_int, _VP, _VP, C.c_size_t, _VP],

@@ -1,6 +1,6 @@
 // C-ABI host layer: the calls that run the likelihood's sequence and then work on the Cholesky factor (sf_apply_batch,
-// sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch, sf_loglike_mean_grad_batch and the three timing aids).  One
-// description per call, one argument check, one workspace layout (carve_applied) and one way to open a call.
+// sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch, sf_loglike_mean_grad_batch, sf_fisher_mean_batch and the three
+// timing aids).  One description per call, one argument check, one workspace layout (carve_applied) and one way to open a call.
 #include "sf_stages.h"
 
 struct AppliedCall {
@@ -21,6 +21,7 @@ static const AppliedCall GRAD_CONTRACT = {"sf_debug_loglike_grad_contract", "d_p
 static const AppliedCall MEAN_GRAD = {"sf_loglike_mean_grad_batch", "d_params, h_slots, d_lnl and d_grad", AW_MEAN, false, false};
 static const AppliedCall MEAN_GRAD_CONTRACT = {"sf_debug_loglike_mean_grad_contract", "d_params, h_slots and d_grad", AW_MEAN,
                                                false, false};
+static const AppliedCall FISHER = {"sf_fisher_mean_batch", "d_params, h_slots, d_lnl and d_fisher", AW_MEAN | AW_FISHER, false, false};
 // what a call was handed, as far as the check looks at it
 struct AppliedArgs {
     int B, nrhs;
@@ -29,7 +30,7 @@ struct AppliedArgs {
     const double* d_rhs = nullptr;
     int ldr = 0;
     int64_t rhs_stride = 0;
-    int grad_stride = 0;
+    int grad_stride = 0;           // (AW_FISHER: the stride of a walker's matrix)
     const int* h_slots = nullptr;  // (AW_MEAN)
     int nslots = 0;
 };
@@ -58,14 +59,15 @@ static int grad_slots_ok(const AppliedCall& k, const sf_model_desc* mdl, int gra
 }
 // the mean gradient's own (behind model_ok): a model it differentiates, and columns that are mean-flux parameters of it
 // (shared with the multi-order gradient call: sf_stages.h)
+bool mean_counts_ok(const sf_model_desc* mdl, int nslots) {
+    return mdl->has_log_scale && !mdl->use_sigma_w && nslots >= 1 && nslots <= SF_MEAN_GRAD_MAX_SLOTS;
+}
 int mean_slots_ok(const char* who, const sf_ctx* c, const sf_model_desc* mdl, const int* h_slots, int nslots, int grad_stride) {
-    if (!mdl->has_log_scale || mdl->use_sigma_w) {
-        sf_set_error("%s: %s", who, mdl->use_sigma_w ? "use_sigma_w (the paper's form of the emulator term) is not differentiated"
-                                                     : "a model without log_scale (the renormalising scale) is not differentiated");
-        return SF_EINVAL;
-    }
-    if (nslots < 1 || nslots > SF_MEAN_GRAD_MAX_SLOTS) {
-        sf_set_error("%s: nslots=%d must lie in 1 .. %d", who, nslots, SF_MEAN_GRAD_MAX_SLOTS);
+    if (!mean_counts_ok(mdl, nslots)) {  // (says which)
+        if (!mdl->has_log_scale || mdl->use_sigma_w)
+            sf_set_error("%s: %s", who, mdl->use_sigma_w ? "use_sigma_w (the paper's form of the emulator term) is not differentiated"
+                                                         : "a model without log_scale (the renormalising scale) is not differentiated");
+        else sf_set_error("%s: nslots=%d must lie in 1 .. %d", who, nslots, SF_MEAN_GRAD_MAX_SLOTS);
         return SF_EINVAL;
     }
     if (grad_stride < nslots) {
@@ -107,7 +109,9 @@ static int args_ok(const AppliedCall& k, const sf_ctx* c, const sf_model_desc* m
     }
     if (k.parts & AW_PART) SF_CHECK(grad_slots_ok(k, mdl, a.grad_stride));
     SF_CHECK(model_ok(c, mdl));
-    if (k.parts & AW_MEAN) SF_CHECK(mean_slots_ok(k.name, c, mdl, a.h_slots, a.nslots, a.grad_stride));
+    // (AW_FISHER: the stride holds a matrix, not a row, and fisher_counts_ok has looked at it)
+    const int row_stride = (k.parts & AW_FISHER) ? a.nslots : a.grad_stride;
+    if (k.parts & AW_MEAN) SF_CHECK(mean_slots_ok(k.name, c, mdl, a.h_slots, a.nslots, row_stride));
     if (k.rhs && a.d_rhs && a.ldr < c->n) {
         sf_set_error("%s: ldr=%d < n (%d)", k.name, a.ldr, c->n);
         return SF_EINVAL;
@@ -134,10 +138,11 @@ static int export_status(int* d_info, const AppliedWork& aw, int B, hipStream_t 
 
 // transform chain, staging, fill, the likelihood's factorisation and `op` on the staging area, in place.  cov_diag (may be
 // NULL): [B][npad], the diagonal of the filled matrices, copied out before the factorisation overwrites it.  xs (may be NULL;
-// nrhs = 1 + m, no d_rhs): the transform chain leaves the scaled rows X there and [r, X_1 .. X_m] are the right-hand sides
+// nrhs = 1 + m, no d_rhs): the transform chain leaves the scaled rows X there and [r, X_1 .. X_m] are the right-hand sides.
+// cols (may be NULL; with xs, nrhs = its slots): the right-hand sides are the tangent columns d f / d theta of its slots instead
 static int apply_staged(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int op, const double* d_rhs, int nrhs,
                         int ldr, int64_t rhs_stride, double* d_flux, const Work& w, const AppliedWork& aw, hipStream_t s,
-                        double* cov_diag = nullptr, double* xs = nullptr) {
+                        double* cov_diag = nullptr, double* xs = nullptr, const sf_mean_grad_args* cols = nullptr) {
     const Layout L = layout_of(c);
     int rc;
     {
@@ -146,8 +151,13 @@ static int apply_staged(sf_ctx* c, const sf_model_desc* mdl, int B, const double
         if (rc) return rc;
     }
     // (before the factorisation: the residual rides through it and comes out as L^-1 R)
-    rc = xs ? sf_launch_mean_stage(w.resid, xs, w.info_e, c->n, L.npad, c->m, B, aw.stage, s)
-            : sf_launch_apply_stage(d_rhs, ldr, rhs_stride, w.resid, c->n, L.npad, nrhs, B, aw.stage, s);
+    if (cols) {  // (behind the transform chain: its broadened rows, multiplier table and FFT scratch are free again)
+        SF_CHECK(sf_launch_mean_tangents(broaden_args(c, mdl, B, d_params, w), c->inv_band.as<double>(),
+                                         emu_args(c, mdl, d_params, w, w.mu, nullptr, w.Lw, w.info_e), *cols, B, s, false));
+        rc = sf_launch_fisher_tangents(eval_args(c, mdl, d_params, w), *cols, aw.stage, (int64_t)nrhs * L.npad, B, s);
+    } else
+        rc = xs ? sf_launch_mean_stage(w.resid, xs, w.info_e, c->n, L.npad, c->m, B, aw.stage, s)
+                : sf_launch_apply_stage(d_rhs, ldr, rhs_stride, w.resid, c->n, L.npad, nrhs, B, aw.stage, s);
     if (rc) return rc;
     const int fp = sf_potrf_front_pad(c->npad, B);  // (once per call: see sf_loglike_batch)
     {
@@ -340,4 +350,44 @@ extern "C" int sf_debug_loglike_mean_grad_contract(sf_ctx* c, const sf_model_des
     SF_CHECK(open_applied(MEAN_GRAD_CONTRACT, c, mdl, mean_grad_args(c, B, d_params && h_slots && d_grad, h_slots, nslots, grad_stride),
                           d_work, work_bytes, &w, &aw));
     return mean_grad_contract(c, mdl, B, d_params, h_slots, nslots, w, aw, d_grad, grad_stride, (hipStream_t)stream);
+}
+
+// ----------------------------------------------------------------------------------- Fisher information in the mean-flux parameters
+// what both Fisher calls refuse before they look at the context (shared with sf_banded.cpp: sf_stages.h)
+int fisher_counts_ok(const char* who, bool required, int nslots, int fisher_stride) {
+    if (!required) {
+        sf_set_error("%s: d_params, h_slots, d_lnl, d_fisher and d_work are required", who);
+        return SF_EINVAL;
+    }
+    if (nslots < 1 || nslots > SF_MEAN_GRAD_MAX_SLOTS) {
+        sf_set_error("%s: nslots=%d must lie in 1 .. %d", who, nslots, SF_MEAN_GRAD_MAX_SLOTS);
+        return SF_EINVAL;
+    }
+    if (fisher_stride < nslots * nslots) {
+        sf_set_error("%s: fisher_stride=%d < nslots^2 = %d", who, fisher_stride, nslots * nslots);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_fisher_mean_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int nslots) {
+    if (model_ok(c, mdl) || !mean_counts_ok(mdl, nslots)) return 0;
+    return workspace_bytes(FISHER, c, mdl, B, nslots, nslots);
+}
+// The likelihood's sequence with the tangent columns J as right-hand sides, Z = L^-1 J in the staging area, F = Z^T Z
+extern "C" int sf_fisher_mean_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const int* h_slots, int nslots,
+                                    double* d_lnl, double* d_fisher, int fisher_stride, int* d_info, void* d_work,
+                                    size_t work_bytes, void* stream) {
+    Work w;
+    AppliedWork aw;
+    SF_CHECK(fisher_counts_ok(FISHER.name, d_params && h_slots && d_lnl && d_fisher && d_work, nslots, fisher_stride));
+    AppliedArgs a = {B, nslots, true};
+    a.grad_stride = fisher_stride, a.h_slots = h_slots, a.nslots = nslots;
+    SF_CHECK(open_applied(FISHER, c, mdl, a, d_work, work_bytes, &w, &aw));
+    hipStream_t s = (hipStream_t)stream;
+    sf_mean_grad_args cols = mean_grad_kernel_args(c, h_slots, nslots, w, aw, nullptr, 0);
+    cols.info = w.info_e;  // (the columns are staged before the factorisation: the transform chain's status)
+    SF_CHECK(apply_staged(c, mdl, B, d_params, SF_APPLY_LINV, nullptr, nslots, c->n, 0, nullptr, w, aw, s, nullptr, aw.xs, &cols));
+    SF_CHECK(sf_launch_fisher_ztz(aw.stage, c->n, c->npad, nslots, B, aw.info, aw.fpart, d_fisher, fisher_stride, s));
+    SF_HIP(hipMemcpyAsync(d_lnl, aw.lnl, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return export_status(d_info, aw, B, s);
 }

@@ -36,6 +36,17 @@ struct BandHeadRhs {
     int64_t rhs_stride;
     double *buf, *gram, *zero;  // (carve_band_diag: rhs, gram, zero)
 };
+// The tangent columns J = d f / d theta behind the walker's own rows (sf_fisher_banded_mean_batch): the sweep -- not a keeping
+// one -- runs over the 1 + m + p rows [r; Y; J] staged in buf, its Gram matrix goes to gram and its leading (1 + m)^2 block to
+// the capacitance step as ever; behind the status, F = G_JJ - U^T U
+struct BandHeadFisher {
+    const int* h_slots;
+    int nslots;
+    const AppliedWork* aw;                    // xs and the tangents' buffers
+    double *buf, *gram, *twist;               // (carve_band_fisher: aw.stage, gram, twist)
+    double* d_fisher;
+    int fisher_stride;
+};
 struct BandHead {
     double* fac;                              // the sweep keeps its factor here (window only); NULL: it keeps nothing
     double *d_X, *d_resid, *d_log_scale;      // optional outputs of run_transforms
@@ -44,6 +55,7 @@ struct BandHead {
     double* d_flux = nullptr;                 // one more of them
     const BandHeadRhs* rhs = nullptr;         // NULL: the walker's own residual, [r; Y]
     bool per_entry_fill = false;              // true: every entry of the band from its own pixel pair, no table per diagonal
+    const BandHeadFisher* fisher = nullptr;   // NULL: no columns behind [r; Y]
 };
 // The head of the likelihood on the band solver: band fill, transforms, sweep, capacitance step, lnl / info.
 // The band fill depends on the covariance hyper-parameters only, the transforms on the stellar ones: the two run side by
@@ -94,21 +106,39 @@ static int banded_head(sf_ctx* c, const sf_model_desc* mdl, int B, const double*
         SF_HIP(hipMemsetAsync(r.zero, 0, sizeof(double) * (size_t)B, s));
         rhs = sf_band_rhs{r.buf, (int64_t)(r.k + c->m) * c->npad, c->npad, r.k + c->m, nullptr, 0};
     }
+    const int nin = h.fisher ? 1 + c->m + h.fisher->nslots : 0;
+    if (h.fisher) {
+        const BandHeadFisher& f = *h.fisher;
+        sf_mean_grad_args cols = mean_grad_kernel_args(c, f.h_slots, f.nslots, w, *f.aw, nullptr, 0);
+        cols.info = w.info_e;  // (before the sweep: the transform chain's status)
+        // (behind the transform chain: its broadened rows, multiplier table and FFT scratch are free again)
+        SF_CHECK(sf_launch_mean_tangents(broaden_args(c, mdl, B, d_params, w), c->inv_band.as<double>(),
+                                         emu_args(c, mdl, d_params, w, w.mu, nullptr, w.Lw, w.info_e), cols, B, s, false));
+        SF_CHECK(sf_launch_fisher_rows(w.resid, w.Y, (int64_t)c->mpad * c->npad, c->n, c->npad, c->m, nin, B, f.buf, s));
+        SF_CHECK(sf_launch_fisher_tangents(eval_args(c, mdl, d_params, w), cols, f.buf + (int64_t)(1 + c->m) * c->npad,
+                                           (int64_t)nin * c->npad, B, s));
+        rhs = sf_band_rhs{f.buf, (int64_t)nin * c->npad, c->npad, nin, nullptr, 0};
+    }
     if (sf != s) SF_HIP(hipStreamWaitEvent(s, aux->join, 0));
     {
         ProfScope ps(s, PS_POTRF);
         const sf_band_call k = band_call(bw.band, sband, bw.ldb, halfwidth, bw.tiles ? c->n : n16, B, rhs, bw.logdet_band,
-                                         h.rhs ? h.rhs->gram : bw.gram, w.info_c);
+                                         h.rhs ? h.rhs->gram : h.fisher ? h.fisher->gram : bw.gram, w.info_c);
         if (bw.tiles) SF_CHECK(sf_launch_potrf_band(k, c->npad, bw.tiles, s));
         else if (h.fac) SF_CHECK(sf_launch_band_keep(k, h.fac, s));
-        else if (sf_band_twisted_applicable(k.n, halfwidth, B)) SF_CHECK(sf_launch_band_forms_twisted(k, bw.twist, s));
+        else if (sf_band_twisted_applicable(k.n, halfwidth, B))
+            SF_CHECK(sf_launch_band_forms_twisted(k, h.fisher ? h.fisher->twist : bw.twist, s));
         else SF_CHECK(sf_launch_band_forms(k, s));
     }
     {
         ProfScope ps(s, PS_SOLVE);
         if (h.rhs) return sf_launch_finish(B, bw.logdet_band, h.rhs->zero, w.info_e, w.info_c, h.lnl, h.info, s);
+        if (h.fisher) SF_CHECK(sf_launch_fisher_lead(h.fisher->gram, nin, c->m + 1, B, bw.gram, s));
         SF_CHECK(sf_launch_woodbury(bw.gram, c->m + 1, B, bw.logdet_band, w.logdet, w.sqmah, w.info_c, s));
         SF_CHECK(sf_launch_finish(B, w.logdet, w.sqmah, w.info_e, w.info_c, h.lnl, h.info, s));
+        if (h.fisher)
+            SF_CHECK(sf_launch_fisher_band(h.fisher->gram, c->m, h.fisher->nslots, B, h.info, h.fisher->d_fisher,
+                                           h.fisher->fisher_stride, s));
     }
     return SF_OK;
 }
@@ -341,6 +371,64 @@ extern "C" int sf_loglike_banded_grad_batch(sf_ctx* c, const sf_model_desc* mdl,
                                             double* d_resid, int* d_info, void* d_work, size_t work_bytes, void* stream) {
     return banded_grad_call(GRAD_CALL, c, mdl, B, d_params, halfwidth, h_slots, nslots, want_cov, d_lnl, d_grad, grad_stride, d_resid,
                             d_info, d_work, work_bytes, (hipStream_t)stream);
+}
+
+// ----------------------------------------------------------------------------------- Fisher information on the band solver
+static const char* const FISHER = "sf_fisher_banded_mean_batch";
+extern "C" int sf_fisher_banded_max_slots(const sf_ctx* c, int halfwidth) {
+    if (!c || !c->n) return SF_EINVAL;
+    if (!c->monotonic || c->m < 1 || c->m > 32) return 0;
+    for (int k = SF_MEAN_GRAD_MAX_SLOTS; k >= 1; --k)
+        if (sfb_admit(halfwidth, 1 + c->m + k) == SFB_WINDOW) return k;
+    return 0;
+}
+// The window's limit, stated once: 1 + m + nslots rows at this half-width.  Without a context (the call looks at it next) m is the
+// one low-rank row every order has at least: what no window takes is refused before it.  say == false: silently (the size query)
+static int fisher_window_ok(const sf_ctx* c, int halfwidth, int nslots, bool say) {
+    const int m = c && c->n ? c->m : 1;
+    if (m < 1 || m > 32 || halfwidth < 0 || sfb_admit(halfwidth, 1 + m + nslots) != SFB_WINDOW) {
+        if (say)
+            sf_set_error("%s: half-width %d with 1 + %d + %d rows lies outside the LDS window (at most %d at this row count; use "
+                         "sf_fisher_mean_batch)", FISHER, halfwidth, m, nslots, sf_band_max_halfwidth(1 + m + nslots));
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+// the batch, the context and model, and a grid the band solver takes; say == false: silently
+static int fisher_banded_ctx_ok(const sf_ctx* c, const sf_model_desc* mdl, int B, bool say) {
+    if (B <= 0 || B > 65535) {
+        if (say) sf_set_error("%s: B=%d must lie in 1 .. 65535", FISHER, B);
+        return SF_EINVAL;
+    }
+    if (model_ok(c, mdl)) return SF_EINVAL;
+    if (!c->n || !c->monotonic) {
+        if (say) sf_set_error("%s: the band solver needs a strictly increasing wavelength grid (use sf_fisher_mean_batch)", FISHER);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_fisher_banded_mean_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth, int nslots) {
+    if (fisher_window_ok(c, halfwidth, nslots, false) || fisher_banded_ctx_ok(c, mdl, B, false)) return 0;
+    if (!mean_counts_ok(mdl, nslots)) return 0;
+    return carve_band_fisher(c, mdl, B, halfwidth, nslots, nullptr, 0, carve(c, mdl, B, nullptr, 0, false).bytes).bytes;
+}
+// The likelihood's head over the rows [r; Y; J]: one sweep with nslots more rows, no kept factor, no backward sweep
+extern "C" int sf_fisher_banded_mean_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int halfwidth,
+                                           const int* h_slots, int nslots, double* d_lnl, double* d_fisher, int fisher_stride,
+                                           double* d_resid, int* d_info, void* d_work, size_t work_bytes, void* stream) {
+    SF_CHECK(fisher_counts_ok(FISHER, d_params && h_slots && d_lnl && d_fisher && d_work, nslots, fisher_stride));
+    SF_CHECK(fisher_window_ok(c, halfwidth, nslots, true));
+    SF_CHECK(fisher_banded_ctx_ok(c, mdl, B, true));
+    SF_CHECK(mean_slots_ok(FISHER, c, mdl, h_slots, nslots, nslots));
+    const Work w = carve(c, mdl, B, d_work, work_bytes, false);
+    const BandFisherWork g = carve_band_fisher(c, mdl, B, halfwidth, nslots, d_work, work_bytes, w.bytes);
+    SF_CHECK(work_fits(work_bytes, g.bytes));
+    hipStream_t s = (hipStream_t)stream;
+    const BandHeadFisher f = {h_slots, nslots, &g.aw, g.aw.stage, g.gram, g.twist, d_fisher, fisher_stride};
+    SF_CHECK(banded_head(c, mdl, B, d_params, halfwidth, w, g.bw,
+                         BandHead{nullptr, g.aw.xs, d_resid, nullptr, d_lnl, g.aw.info, nullptr, nullptr, false, &f}, s));
+    if (d_info) SF_HIP(hipMemcpyAsync(d_info, g.aw.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return SF_OK;
 }
 
 // ----------------------------------------------------------------------------------- residual diagnostics on the band solver

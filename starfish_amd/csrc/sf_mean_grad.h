@@ -142,10 +142,11 @@ __global__ __launch_bounds__(256) void k_mean_emu_dk(const sf_emu_args e, const 
     }
 }
 
-// the launches that need no solve: a.dcoef (want_vsini) and a.kdot / a.mudot / a.zdot (ng grid columns).  bro: the broadening's
+// the launches that need no solve: a.dcoef (want_vsini) and a.kdot / a.mudot / a.zdot (ng grid columns; a.zdot only with want_zdot:
+// the Fisher columns read d mu alone).  bro: the broadening's
 // arguments as run_transforms filled them (its ybro, mult and FFT scratch are free again and are used once more)
 int sf_launch_mean_tangents(const sf_broaden_args& bro, const double* inv_band, const sf_emu_args& e, const sf_mean_grad_args& a,
-                            int B, hipStream_t s) {
+                            int B, hipStream_t s, bool want_zdot) {
     if (a.want_vsini) {
         const int nh1 = bro.nf / 2 + 1;
         hipLaunchKernelGGL(k_rot_dmult, dim3((nh1 + 255) / 256, B), dim3(256), 0, s, bro.mult, nh1, 1.0 / (bro.nf * bro.dv), bro.params,
@@ -158,7 +159,7 @@ int sf_launch_mean_tangents(const sf_broaden_args& bro, const double* inv_band, 
         hipLaunchKernelGGL(k_mean_emu_dk, dim3(B, a.ng), dim3(256), 0, s, e, a, B);
         SF_LAUNCH_CHECK();
         const int mM = e.m * e.M;
-        for (int g = 0; g < a.ng; ++g) {  // d z = Linv d v12: the emulator's own product on the tangent blocks
+        for (int g = 0; want_zdot && g < a.ng; ++g) {  // d z = Linv d v12: the emulator's own product on the tangent blocks
             sf_emu_args t = e;
             t.kbuf = a.kdot + (int64_t)g * B * mM;
             t.zscratch = a.zdot + (int64_t)g * B * mM * e.m;

@@ -31,7 +31,11 @@ int export_info(int* d_info, const Work& w, int units, hipStream_t s);
 int export_logdet_sqmah(double* d_logdet, double* d_sqmah, const Work& w, int units, hipStream_t s);
 // The mean gradient's own checks of one request (behind model_ok): a model it differentiates, 1 .. SF_MEAN_GRAD_MAX_SLOTS columns
 // that are mean-flux parameters of it, none twice, and rows that hold them.  who: how the message starts
+bool mean_counts_ok(const sf_model_desc* mdl, int nslots);  // its model and slot-count conditions alone, silently (size queries)
 int mean_slots_ok(const char* who, const sf_ctx* c, const sf_model_desc* mdl, const int* h_slots, int nslots, int grad_stride);
+// What sf_fisher_mean_batch and sf_fisher_banded_mean_batch refuse before they look at the context: a required pointer that is
+// NULL (required == false), nslots outside 1 .. SF_MEAN_GRAD_MAX_SLOTS, fisher_stride < nslots^2
+int fisher_counts_ok(const char* who, bool required, int nslots, int fisher_stride);
 // the arguments of the mean gradient's launches: the staging area, moments, partial sums and tangents of aw on the workspace w
 // (rows of w.L.npad doubles), nslots columns into d_grad
 sf_mean_grad_args mean_grad_kernel_args(const sf_ctx* c, const int* h_slots, int nslots, const Work& w, const AppliedWork& aw,

@@ -107,12 +107,29 @@ size_t sf_mean_grad_part_doubles(int n, int nslots, int batch);
 int sf_launch_mean_stage(const double* resid, const double* Xs, const int* info, int n, int npad, int m, int batch, double* stage,
                          hipStream_t s);
 // the tangents that need no solve: a.dcoef (bro: the broadening's arguments as run_transforms fills them; its ybro, mult and FFT
-// scratch are used once more) and a.kdot, a.mudot, a.zdot (e: the emulator's arguments)
+// scratch are used once more) and a.kdot, a.mudot, a.zdot (e: the emulator's arguments); want_zdot == false leaves a.zdot alone
 int sf_launch_mean_tangents(const sf_broaden_args& bro, const double* inv_band, const sf_emu_args& e, const sf_mean_grad_args& a,
-                            int B, hipStream_t s);
+                            int B, hipStream_t s, bool want_zdot = true);
 // the moments, the pixel pass, the grid slots (z: the emulator's [B][mM][m]) and the sum over the blocks; e: the evaluation's
 // arguments as run_transforms fills them
 int sf_launch_mean_grad(const sf_eval_args& e, const sf_mean_grad_args& a, const double* z, int mM, int batch, hipStream_t s);
+
+// sf_fisher.h: the Fisher information of the mean-flux parameters, F = J^T C^-1 J with the tangent columns J = d f / d theta.
+// The columns of a's slots into rows[b * rstride + j * npad + i] (zero on the padding and where a.info[b] != 0; a.info: the
+// transform chain's status), behind sf_launch_mean_tangents; of a only Xs, mu, scale, info, dcoef, mudot and the counts are read
+int sf_launch_fisher_tangents(const sf_eval_args& e, const sf_mean_grad_args& a, double* rows, int64_t rstride, int batch,
+                              hipStream_t s);
+// band solver: [r; Y] into the first 1 + m of the nin rows of buf[b] (the columns follow); the leading nl x nl block of the
+// nin x nin Gram matrices, compact; F = G_JJ - U^T U from the Gram matrix of [r; Y; J] (info: the final status, != 0 -> NaN)
+int sf_launch_fisher_rows(const double* resid, const double* Y, int64_t sy, int n, int npad, int m, int nin, int batch, double* buf,
+                          hipStream_t s);
+int sf_launch_fisher_lead(const double* gram, int nin, int nl, int batch, double* lead, hipStream_t s);
+int sf_launch_fisher_band(const double* gram, int m, int p, int batch, const int* info, double* fisher, int64_t fstride,
+                          hipStream_t s);
+// dense factor: F = Z^T Z for Z = L^-1 J, [B][p][npad]; part: sf_fisher_part_doubles(n, p, B)
+size_t sf_fisher_part_doubles(int n, int nslots, int batch);
+int sf_launch_fisher_ztz(const double* Z, int n, int npad, int p, int batch, const int* info, double* part, double* fisher,
+                         int64_t fstride, hipStream_t s);
 
 int sf_launch_extinct_rows(const double* wave, int n, const double* flux, int rows, double Av, double Rv, int law,
                            double* out, hipStream_t s);  // law: 0 ccm89, 1 odonnell94, 2 calzetti00

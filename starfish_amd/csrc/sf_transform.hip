@@ -16,6 +16,7 @@
 //   sf_transform_emu.h      k_emu_prep/z/post, k_emu_joint, k_finish
 //   sf_transform_v11.h      k_v11_build, k_v11_build_batch
 //   sf_mean_grad.h          the gradient in the mean-flux parameters: k_mean_stage, k_mean_finish, k_mean_pixel, k_mean_sum
+//   sf_fisher.h             the Fisher information of the mean-flux parameters: k_fisher_tangent, k_fisher_band, k_fisher_ztz
 #include "sf_common.h"
 #include "sf_device.h"
 #include "sf_transform.h"
@@ -25,3 +26,4 @@
 #include "sf_transform_emu.h"
 #include "sf_transform_v11.h"
 #include "sf_mean_grad.h"
+#include "sf_fisher.h"

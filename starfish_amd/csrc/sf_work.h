@@ -168,11 +168,12 @@ static BandWork carve_band(const sf_ctx* c, int B, int halfwidth, void* p, size_
 //                moments (sf_mean_fin_doubles); mpart: the partial sums per (walker, 256-pixel block, slot); dcoef: the spline
 //                coefficients of the d / d vsini rows (models with vsini); kdot, mudot, zdot: d v12, d mu and Linv d v12 for
 //                min(nslots, P) grid columns
-enum AppliedParts { AW_YV = 1, AW_COV_DIAG = 2, AW_INVERSE = 4, AW_PART = 8, AW_MEAN = 16 };
+//   AW_FISHER    (sf_fisher_mean_batch, with AW_MEAN) fpart: the partial sums of Z^T Z per (walker, 256-pixel block, pair of slots)
+enum AppliedParts { AW_YV = 1, AW_COV_DIAG = 2, AW_INVERSE = 4, AW_PART = 8, AW_MEAN = 16, AW_FISHER = 32 };
 struct AppliedWork {
     double *stage, *lnl;
     int* info;
-    double *yv, *cov_diag, *cinv_diag, *winv, *part, *xs, *fin, *mpart, *dcoef, *kdot, *mudot, *zdot;
+    double *yv, *cov_diag, *cinv_diag, *winv, *part, *xs, *fin, *mpart, *dcoef, *kdot, *mudot, *zdot, *fpart;
     double* coef;  // (carve_multi_grad only) the segment's own spline coefficients, which a single-order call keeps in its Work
     size_t bytes;
 };
@@ -200,6 +201,7 @@ static AppliedWork carve_applied(const sf_ctx* c, const sf_model_desc* mdl, int 
         w.mudot = k.take<double>(ng * B * c->m);
         w.zdot = k.take<double>(ng * B * mM * c->m);
     }
+    if (parts & AW_FISHER) w.fpart = k.take<double>(sf_fisher_part_doubles(c->n, nslots, B));
     w.bytes = sf_align_up(k.off, 256);
     return w;
 }
@@ -301,6 +303,29 @@ static BandDiagWork carve_band_diag(const sf_ctx* c, const sf_model_desc* mdl, i
         g.vs = w.take<double>((size_t)B * c->m * c->npad);
     }
     g.bytes = sf_align_up(w.off, 256);
+    return g;
+}
+
+// sf_fisher_banded_mean_batch with p = nslots columns, behind the Work of the same call: the band solver's buffers (carve_band;
+// its gram takes the leading (1 + m)^2 block for the capacitance step), the applied layout with nin = 1 + m + p rows per walker
+// (carve_applied with AW_MEAN: the staging area holds the sweep's rows [r; Y; J]; lnl, info, xs and the tangents' buffers), then
+// gram: [B][nin^2], the sweep's Gram matrices, and twist: the two half sweeps' workspace for nin rows
+struct BandFisherWork {
+    BandWork bw;
+    AppliedWork aw;
+    double *gram, *twist;
+    size_t bytes;
+};
+static BandFisherWork carve_band_fisher(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth, int nslots, void* p,
+                                        size_t cap, size_t base_bytes) {
+    BandFisherWork g{};
+    const int nin = 1 + c->m + nslots;
+    g.bw = carve_band(c, B, halfwidth, p, cap, base_bytes);
+    g.aw = carve_applied(c, mdl, B, nin, AW_MEAN, p, cap, g.bw.bytes, nslots);
+    Carve k(p, cap, g.aw.bytes);
+    g.gram = k.take<double>((size_t)B * nin * nin);
+    g.twist = k.take<double>(sfb_twist_carve(nullptr, halfwidth, nin, B).doubles);
+    g.bytes = sf_align_up(k.off, 256);
     return g;
 }
 

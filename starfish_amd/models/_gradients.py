@@ -151,6 +151,63 @@ class Gradients:
         lnl = np.where(out["info"] == 0, out["lnl"], -np.inf)
         return (lnl, out["grad"], out["info"]) if return_info else (lnl, out["grad"])
 
+    # ------------------------------------------------------------------ Fisher information in the mean-flux parameters
+    def _fisher_call(self, dev, md, rows, solver):
+        """The device call of the Fisher matrix in the columns of :meth:`_mean_gradient_columns` (and so with its refusals)."""
+        return dev.fisher_mean(md, rows, self._mean_gradient_columns(dev, md), solver=solver)
+
+    def fisher_information(self, solver=None):
+        """The Fisher information of the mean-flux parameters at the current state and at fixed covariance, ``F_ij = fdot_i^T
+        C^-1 fdot_j`` with ``fdot_j = d flux / d label_j``: a ``(p, p)`` array in :attr:`mean_gradient_labels` order, symmetric
+        bit for bit.  This is the Gauss-Newton, fixed-covariance matrix: the term ``1/2 tr(C^-1 dC_i C^-1 dC_j)`` that a grid
+        parameter has because the emulator's rows sit inside the covariance is left out, and so is the block of the covariance
+        hyper-parameters (the mean / covariance cross block of a Gaussian's Fisher matrix is zero).  Raises as
+        :meth:`log_likelihood` does and refuses what :meth:`log_likelihood_mean_gradient` refuses; the model's state is not
+        modified.  ``solver``: ``None`` / "dense" the dense factor, "banded" / "auto" one sweep of the band + Woodbury solver
+        (:meth:`DeviceOrder.fisher_mean`)."""
+        solver = self._gradient_solver(solver)
+        dev, md, rows = self._pack(update_caches=False)
+        return self._own(self._fisher_call(dev, md, rows, solver))["fisher"]
+
+    def fisher_information_batch(self, P, return_info=False, solver=None):
+        """:meth:`fisher_information` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device pass:
+        ``(B, p, p)``, a NaN matrix for a walker that fails; with ``return_info`` ``(fisher, info)``.  The model's own state is
+        not modified."""
+        solver = self._gradient_solver(solver)
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        dev, md, rows = self._pack(P, update_caches=False)
+        out = self._fisher_call(dev, md, rows, solver)
+        return (out["fisher"], out["info"]) if return_info else out["fisher"]
+
+    def parameter_covariance(self, priors=None, solver=None):
+        """The Laplace covariance of the labels of :attr:`mean_gradient_labels` at the current state (the point :meth:`train`
+        found): the inverse of :meth:`fisher_information` plus, for every prior on one of these labels,
+        ``-d^2 logpdf / d label^2`` by a central second difference with the step of the trainers' prior slopes,
+        ``eps^(1/3) max(1, |x|)``.  The covariance hyper-parameters are held fixed; see :meth:`fisher_information` for what
+        the matrix leaves out.  The inverse is formed in normalised form, ``D^-1 (D^-1 F D^-1)^-1 D^-1`` with ``D =
+        sqrt(diag(F))``, by Cholesky; a matrix that is not positive definite (parameters the data do not separate) raises
+        ``np.linalg.LinAlgError`` naming the labels.  ``priors`` are checked as :meth:`train` checks them."""
+        priors = self._checked_priors(priors)
+        labels = self.mean_gradient_labels
+        F = np.array(self.fisher_information(solver=solver), dtype=np.float64)
+        for i, key in enumerate(labels):
+            if key in priors:
+                x = float(self[key])
+                h = _map._H0 * max(1.0, abs(x))
+                lp = priors[key].logpdf
+                F[i, i] -= (lp(x + h) - 2.0 * lp(x) + lp(x - h)) / (h * h)
+        d = np.sqrt(np.diag(F))
+        if not (np.all(np.isfinite(F)) and np.all(d > 0)):
+            raise np.linalg.LinAlgError(f"the Fisher matrix of {list(labels)} has a diagonal entry that is not positive or an "
+                                        "entry that is not finite")
+        try:
+            L = np.linalg.cholesky(F / np.outer(d, d))
+        except np.linalg.LinAlgError:
+            raise np.linalg.LinAlgError(f"the Fisher matrix of {list(labels)} is not positive definite: the data (and priors) do "
+                                        "not separate these parameters; freeze some of them or add priors") from None
+        Li = np.linalg.solve(L, np.eye(len(labels)))
+        return (Li.T @ Li) / np.outer(d, d)
+
     def _scatter_combined(self, grad, md, out, columns):
         """A combined device result -- the mean ``columns`` in request order (none: ``[]``), then, where covariance labels are
         thawed, the covariance slots -- into the :attr:`labels`-ordered ``grad``; returns ``(lnl, info)`` with ``-inf`` for the

@@ -73,3 +73,23 @@ class EnsembleSampler:
     def get_log_prob(self, discard=0, flat=False):
         lp = self.log_prob[discard:]
         return lp.reshape(-1) if flat else lp
+
+
+def gaussian_ball(x, cov, nwalkers, seed=None):
+    """An initial ensemble for :class:`EnsembleSampler`: ``nwalkers`` draws from the normal distribution with mean ``x`` (ndim,)
+    and covariance ``cov`` (ndim, ndim), e.g. the Laplace covariance of ``SpectrumModel.parameter_covariance`` at the point
+    ``train`` found, as an (nwalkers, ndim) array.  The draws are ``x + D L z`` with ``D = sqrt(diag(cov))`` and ``L`` the
+    Cholesky factor of the correlation matrix, so parameters of very different scales do not cost digits; a covariance that
+    is not positive definite raises ``np.linalg.LinAlgError``."""
+    x = np.asarray(x, dtype=np.float64)
+    cov = np.asarray(cov, dtype=np.float64)
+    if x.ndim != 1 or cov.shape != (x.size, x.size):
+        raise ValueError(f"x of shape {x.shape} and cov of shape {cov.shape}: expected (ndim,) and (ndim, ndim)")
+    if int(nwalkers) < 1:
+        raise ValueError("nwalkers must be positive")
+    d = np.sqrt(np.diag(cov))
+    if not np.all(d > 0) or not np.all(np.isfinite(cov)):
+        raise np.linalg.LinAlgError("cov is not positive definite: a diagonal entry is not positive (or an entry not finite)")
+    L = np.linalg.cholesky(cov / np.outer(d, d))
+    z = np.random.default_rng(seed).standard_normal((int(nwalkers), x.size))
+    return x[None, :] + (z @ L.T) * d[None, :]
