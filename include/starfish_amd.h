@@ -533,6 +533,52 @@ int sf_loglike_banded_multi_grad_batch_md(const sf_segment* segs, int nseg, cons
                                           double* d_log_scale, int* d_info, double* d_grad, int grad_stride, void* d_work,
                                           size_t work_bytes, void* stream);
 
+/* The Fisher information of the mean-flux parameters (sf_fisher_banded_mean_batch: F = G_JJ - U^T U at fixed covariance, the
+ * Gauss-Newton block) for the units of several orders in one pass on the band + Woodbury solver.  segs, models and h_halfwidth
+ * are exactly as for sf_loglike_banded_multi_grad_batch_md; requests[i].h_mean_slots / n_mean_slots are the tangent columns of
+ * order i (p_i of them, 1 .. SF_MEAN_GRAD_MAX_SLOTS) and want_cov must be 0 (the covariance block is not computed).  Units in
+ * segment order, u = sum_{j<i} B_j + b.  For a unit with d_info[u] == 0 the leading p_i x p_i block of
+ * d_fisher[u * fisher_stride + a * fisher_ld + b] holds F of that unit in request order; only the lower triangle is computed
+ * and it is mirrored, so F_ab and F_ba are the same bits; the block is NaN where d_info[u] != 0.  fisher_ld >= max p_i and
+ * fisher_stride >= fisher_ld^2; outside the leading block the contents are unspecified.  d_lnl, d_info and d_log_scale (may be
+ * NULL) are as for the gradient call.  Per segment, on the streams sf_loglike_multi_batch_md runs its chains on: band fill,
+ * transform chain, row tangents and the sweep's rows [r; Y; J] into the segment's slice of a per-unit row buffer; once per
+ * chunk of segments, over all its units in one launch each: ONE sweep (the likelihood's, not a keeping one; two half sweeps
+ * where they pay for the frame), the capacitance step, lnl / info and F.  No kept factor, no backward sweep, no N x N matrix.
+ * All units share ONE frame taken from the whole call, never from a chunk: the largest n rounded up to 16 rows (shorter
+ * orders: identity rows, zero right-hand sides), the largest npad, the largest half-width and the largest row count
+ * 1 + m + max p_i -- an order with fewer columns carries zero rows behind its own, which add exact zeros to the Gram matrix
+ * and leave its p_i x p_i block what it is alone.  The row count 1 + m + max p_i picks the LDS window: half-widths up to
+ * 144 with at most 16 rows, 128 with at most 32, 112 with at most 48.  A unit whose support is wider than its segment's half-width gets
+ * SF_INFO_BANDWIDTH, -inf and a NaN block.  A unit's values agree with sf_fisher_banded_mean_batch on the same order to
+ * rounding, not bit for bit (another frame picks another instantiation of the sweep).  The call never synchronises and uses no
+ * atomics: a repeated call gives the same bits.  SF_EINVAL before anything is enqueued: whatever
+ * sf_loglike_banded_multi_grad_batch_md refuses; want_cov != 0; a segment without mean slots; the call's largest half-width
+ * beyond the window at the call's row count (the message names sf_fisher_mean_batch); null d_lnl, d_info or d_fisher;
+ * fisher_ld < max p_i; fisher_stride < fisher_ld^2.  SF_ENOMEM: the workspace is too small.  d_work:
+ * sf_fisher_banded_multi_workspace_bytes_md(...) (0 for what the call refuses on these arguments): the workspace of
+ * sf_loglike_multi_batch_md without its matrices; per unit, in the common frame, the band, 1 + m + max p_i rows of npad
+ * doubles, two Gram matrices and a compact block; the half sweeps' scratch; per segment what the tangent columns keep per
+ * walker. */
+size_t sf_fisher_banded_multi_workspace_bytes_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                                 const sf_grad_request* requests, const int* h_halfwidth);
+int sf_fisher_banded_multi_batch_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                    const sf_grad_request* requests, const int* h_halfwidth, double* d_lnl, double* d_log_scale,
+                                    int* d_info, double* d_fisher, int fisher_ld, int fisher_stride, void* d_work,
+                                    size_t work_bytes, void* stream);
+/* The sum over the orders of what the call above leaves, for nseg segments of W walkers each (unit = i * W + w), through the
+ * column map of sf_multi_grad_reduce unchanged: d_col_ptr / d_col_src list, per label, its (segment, slot) sources ascending in
+ * the segment, at most one per segment.  Entry (a, b) of walker w is the sum, over the segments that appear in BOTH labels'
+ * lists and in ascending segment index, of that unit's F[slot_a][slot_b] = d_unit_fisher[u * fisher_stride + slot_a * fisher_ld
+ * + slot_b], written s = f_0; s = s + f_1; ...; a pair with no common segment (two labels of different orders, a label without
+ * a source) is exactly 0.0.  a >= b is computed and mirrored into d_fisher[w * out_stride + a * ncols + b].  d_lnl and d_info
+ * follow sf_multi_grad_reduce's rule; where d_info[w] != 0, d_lnl[w] = -inf and the matrix is NaN.  Plain adds, no atomics: a
+ * repeated call gives the same bits.  A source outside the unit block is not read (NaN).  SF_EINVAL: a null pointer, nseg < 1,
+ * W outside 1 .. 65535, ncols outside 0 .. 32768, fisher_ld < 1, fisher_stride < fisher_ld^2, out_stride < ncols^2. */
+int sf_multi_fisher_reduce(int nseg, int W, const double* d_unit_lnl, const int* d_unit_info, const double* d_unit_fisher,
+                           int fisher_ld, int fisher_stride, const int32_t* d_col_ptr, const int32_t* d_col_src, int ncols,
+                           double* d_lnl, double* d_fisher, int out_stride, int* d_info, void* stream);
+
 /* ---- structure-exploiting solver -----------------------------------
  * Same value as sf_loglike_batch, computed without ever forming the N x N matrix: the covariance of
  * spectrum_model.py:334-363 is  C = Bd + Y^T Y  with Bd = sigma^2 + K_global + K_local + jitter

@@ -674,22 +674,42 @@ class BandedMultiGradPlan:
         self.rows = [np.atleast_2d(r.cpu().numpy() if torch.is_tensor(r) else np.asarray(r, dtype=np.float64)) for r in rows_list]
         self.sizes = [int(r.shape[0]) for r in self.rows]
         self.bounds = [o.halfwidth_bound(md, r) for o, md, r in zip(self.orders, self.mds, self.rows)]
-        self.fits = banded_units(self.bounds, [o.banded_window_halfwidth() for o in self.orders])
+        self.fits = banded_units(self.bounds, self._windows())
         self.idx = [np.nonzero(f)[0] for f in self.fits]
         self.on_device = [i for i, idx in enumerate(self.idx) if idx.size]  # the orders that have a unit for the band kernels
         self.halfwidth = max((int(self.bounds[i][self.idx[i]].max()) for i in self.on_device), default=0)
         self.plan = None
         # (a group in which no order requests a slot has nothing for the gradient call: its units are refused or go dense)
         if self.on_device and any(self.slots[i] for i in self.on_device):
-            self.plan = _BandedUnits([self.orders[i] for i in self.on_device], [self.mds[i] for i in self.on_device],
-                                     [self.rows[i][self.idx[i]] for i in self.on_device],
-                                     [self.requests[i] for i in self.on_device], self.halfwidth, max_units=max_units)
+            self.plan = self._units([self.orders[i] for i in self.on_device], [self.mds[i] for i in self.on_device],
+                                    [self.rows[i][self.idx[i]] for i in self.on_device],
+                                    [self.requests[i] for i in self.on_device], self.halfwidth, max_units=max_units)
         else:
             self.fits = [np.zeros(n, dtype=bool) for n in self.sizes]
             self.idx, self.on_device = [np.zeros(0, dtype=np.int64)] * len(self.sizes), []
         self.complete = all(f.all() for f in self.fits)  # every unit is in the device plan, in unit order
         self.rerouted = None
         self._out = None
+
+    # what a plan on other band kernels (:class:`BandedMultiFisherPlan`) states anew: the device side, the window its units must
+    # fit, a refused order's results and the dense call of the re-routed units
+    _units = _BandedUnits
+
+    def _windows(self):
+        """Per order, the largest half-width bound the band kernels of this plan take."""
+        return [o.banded_window_halfwidth() for o in self.orders]
+
+    def _refused(self, n, k):
+        return refused_output(n, dict(grad=(k,), log_scale=()))
+
+    def _dense(self, which, rest):
+        """The dense results of the walkers ``rest[i]`` of the orders ``which``, one dict with the keys of :meth:`_refused` each."""
+        sub = ([self.orders[i] for i in which], [self.mds[i] for i in which], [self.rows[i][rest[i]] for i in which])
+        if any(self.slots[i] for i in which):
+            dense = loglike_multi_grad(*sub, [self.requests[i] for i in which], max_units=self.max_units)
+        else:
+            dense = [dict(o, grad=np.zeros((len(o["lnl"]), 0))) for o in loglike_multi(*sub, max_units=self.max_units)]
+        return [{key: d[key] for key in ("lnl", "grad", "log_scale", "info")} for d in dense]
 
     @property
     def units(self):
@@ -705,7 +725,7 @@ class BandedMultiGradPlan:
         :meth:`MultiGradPlan.collect`; refused units have ``-inf``, NaN and INFO_BANDWIDTH."""
         outs = []
         for n, k in zip(self.sizes, self.slots):
-            outs.append(refused_output(n, dict(grad=(k,), log_scale=())))
+            outs.append(self._refused(n, k))
         if self.plan is not None:
             for i, got in zip(self.on_device, self.plan.collect()):
                 for key, v in got.items():
@@ -720,13 +740,7 @@ class BandedMultiGradPlan:
         which = [i for i, idx in enumerate(rest) if len(idx)]
         self.rerouted = sum(len(idx) for idx in rest)
         if which:
-            sub = ([self.orders[i] for i in which], [self.mds[i] for i in which], [self.rows[i][rest[i]] for i in which])
-            if any(self.slots[i] for i in which):
-                dense = loglike_multi_grad(*sub, [self.requests[i] for i in which], max_units=self.max_units)
-            else:
-                dense = [dict(o, grad=np.zeros((len(o["lnl"]), 0))) for o in loglike_multi(*sub, max_units=self.max_units)]
-            dense = [{key: d[key] for key in ("lnl", "grad", "log_scale", "info")} for d in dense]
-            merge_units(outs, rest, dense)
+            merge_units(outs, rest, self._dense(which, rest))
         self._out = outs
         return outs
 
@@ -747,6 +761,144 @@ class BandedMultiGradPlan:
 def loglike_banded_multi_grad(orders, mds, rows_list, requests, solver="banded", max_units=None, sync=True):
     """:func:`loglike_multi_grad` on the band solver (:class:`BandedMultiGradPlan`; ``solver``: "banded" or "auto")."""
     plan = BandedMultiGradPlan(orders, mds, rows_list, requests, solver=solver, max_units=max_units)
+    plan.enqueue()
+    return plan.collect() if sync else plan
+
+
+class _BandedFisherUnits(_BandedUnits):
+    """The device side of :class:`BandedMultiFisherPlan`: the units the band kernels take, every segment with the half-width
+    ``halfwidth`` (sf_fisher_banded_multi_batch_md).  ``self.fisher``: (units, pmax, pmax), a unit's matrix in its leading
+    p_i x p_i block."""
+
+    def __init__(self, orders, mds, rows_list, requests, halfwidth, max_units=None):
+        super().__init__(orders, mds, rows_list, requests, halfwidth, max_units=max_units)
+        with _torch().cuda.device(self.dev):  # (the base class's gradient rows, units x pmax doubles, stay unused)
+            self.fisher = empty((self.units, self.stride, self.stride), self.dev)
+
+    def _workspace_bytes(self, segs, nseg, models):
+        idxs = self._orders_of(segs, nseg)
+        return self.lib.sf_fisher_banded_multi_workspace_bytes_md(segs, nseg, models, self._requests_array(idxs),
+                                                                  self._halfwidths(nseg))
+
+    def enqueue(self):
+        torch = _torch()
+        with torch.cuda.device(self.dev):
+            s = stream_ptr(self.dev)
+            q, ld = self.quad, self.stride
+            for (segs, nseg, u0, n, models), piece in zip(self.calls, self.pieces):
+                rc = self.lib.sf_fisher_banded_multi_batch_md(
+                    segs, nseg, models, self._requests_array([i for i, _, _ in piece]), self._halfwidths(nseg),
+                    ptr(q[0][u0:u0 + n]), ptr(q[3][u0:u0 + n]), ptr(self.info[u0:u0 + n]), ptr(self.fisher[u0:u0 + n]), ld, ld * ld,
+                    ptr(self.ws), self.ws.numel(), s)
+                _lib.check(rc, "sf_fisher_banded_multi_batch_md")
+
+    def collect(self):
+        """Per order a dict of numpy arrays: lnl (B,), fisher (B, p_i, p_i), info (B,).  No retry, as :meth:`_BandedUnits.collect`."""
+        lnl, info, fisher = self.quad[0].cpu().numpy(), self.info.cpu().numpy(), self.fisher.cpu().numpy()
+        ends = np.cumsum(self.sizes)
+        return [dict(lnl=lnl[hi - n:hi], fisher=np.ascontiguousarray(fisher[hi - n:hi, :k, :k]), info=info[hi - n:hi])
+                for n, hi, k in zip(self.sizes, ends, self.slots)]
+
+    def reduce(self, sources):
+        """The sum of the unit matrices over the orders on the device (sf_multi_fisher_reduce), of what a finished call left in
+        the plan's buffers; ``sources`` as for :meth:`MultiGradPlan.reduce`.  Returns numpy ``lnl (W,)``,
+        ``fisher (W, len(sources), len(sources))``, ``info (W,)``."""
+        torch = _torch()
+        if len(set(self.sizes)) != 1:
+            raise ValueError(f"sf_multi_fisher_reduce: the orders have {sorted(set(self.sizes))} walkers")
+        W, ncols, ld = self.sizes[0], len(sources), self.stride
+        col_ptr, col_src = column_map_csr(sources)
+        with torch.cuda.device(self.dev):
+            d_ptr, d_src = torch.from_numpy(col_ptr).to(self.dev), torch.from_numpy(col_src).to(self.dev)
+            lnl, fisher = empty((W,), self.dev), empty((W, max(ncols * ncols, 1)), self.dev)
+            info = empty((W,), self.dev, torch.int32)
+            rc = self.lib.sf_multi_fisher_reduce(len(self.sizes), W, ptr(self.quad[0]), ptr(self.info), ptr(self.fisher), ld, ld * ld,
+                                                 ptr(d_ptr), ptr(d_src), ncols, ptr(lnl), ptr(fisher), max(ncols * ncols, 1),
+                                                 ptr(info), stream_ptr(self.dev))
+            _lib.check(rc, "sf_multi_fisher_reduce")
+            return lnl.cpu().numpy(), fisher.cpu().numpy()[:, :ncols * ncols].reshape(W, ncols, ncols), info.cpu().numpy()
+
+
+def reduce_fisher_host(lnl, info, fishers, sources):
+    """sf_multi_fisher_reduce's rule on the host: ``lnl``, ``info`` (n_orders, W), ``fishers[i]`` (W, p_i, p_i) the unit matrices
+    of order i, ``sources[j]`` the ``(order, slot)`` pairs of label j (at most one per order).  Entry ``(a, b)``, ``a >= b``, is
+    the sum of ``fishers[i][:, slot_a, slot_b]`` over the orders i that appear in both labels' lists, ascending, ``s = f0; s = s +
+    f1; ...``, exactly 0.0 without a common order, and is mirrored; ``lnl`` and ``info`` as :func:`reduce_orders_host`; a walker
+    with a non-zero code gets ``-inf`` and a NaN matrix.  The same adds in the same order as the device: the same bits."""
+    total, _none, code = reduce_orders_host(lnl, info, [], [])
+    W, p = total.shape[0], len(sources)
+    per_order = {}
+    for j, src in enumerate(sources):
+        for i, slot in src:
+            labels, slots = per_order.setdefault(int(i), ([], []))
+            if j in labels:
+                raise ValueError(f"label {j} has two sources in order {int(i)}")
+            labels.append(j)
+            slots.append(int(slot))
+    F, seen = np.zeros((W, p, p)), np.zeros((p, p), dtype=bool)
+    for i in sorted(per_order):
+        la, sl = (np.asarray(v, dtype=np.intp) for v in per_order[i])
+        block = np.asarray(fishers[i], dtype=np.float64)[:, sl[:, None], sl[None, :]]
+        ix = np.ix_(la, la)
+        F[:, la[:, None], la[None, :]] = np.where(seen[ix], F[:, la[:, None], la[None, :]] + block, block)
+        seen[ix] = True
+    lower = np.tril_indices(p, -1)
+    F[:, lower[1], lower[0]] = F[:, lower[0], lower[1]]
+    bad = code != 0
+    F[bad] = np.nan
+    return total, F, code
+
+
+class BandedMultiFisherPlan(BandedMultiGradPlan):
+    """The Fisher information of the mean-flux parameters (:meth:`DeviceOrder.fisher_mean`) of every (order x walker) unit of
+    ONE device from one sweep per unit, all units in one launch sequence (sf_fisher_banded_multi_batch_md).  ``columns[i]``: the
+    columns of order i's parameter row (1 .. MEAN_GRAD_MAX_SLOTS).  The rules of :class:`BandedMultiGradPlan`, shared with it
+    -- half-width bounds on the host, one group at the group's largest bound, :func:`rerouted_units`, :func:`merge_units` --
+    with the window at the CALL's row count ``1 + m + max p_i``: the units that fit it go to the band kernels; under "banded" the
+    others are refused (INFO_BANDWIDTH, NaN), under "auto" they, the units flagged -4 and those with status -5 go, per order,
+    through the dense ``fisher_mean`` and are merged back by (order, walker); -5 is recomputed densely under "banded" too.
+    :meth:`collect`: per order a dict lnl (B,), fisher (B, p_i, p_i), info (B,)."""
+
+    _units = _BandedFisherUnits
+
+    def __init__(self, orders, mds, rows_list, columns, solver="banded", max_units=None):
+        columns = [[int(c) for c in cols] for cols in columns]
+        for i, cols in enumerate(columns):
+            if not 1 <= len(cols) <= MEAN_GRAD_MAX_SLOTS:
+                raise ValueError(f"multi-order Fisher information: order {i} has {len(cols)} columns, not 1 .. {MEAN_GRAD_MAX_SLOTS}")
+        self.pmax = max((len(cols) for cols in columns), default=0)
+        super().__init__(orders, mds, rows_list, [(cols, False) for cols in columns], solver=solver, max_units=max_units)
+
+    def _windows(self):
+        """The bound of a unit fits where the window takes this plan's largest column count (sf_fisher_banded_max_slots)."""
+        return [max((w for w in range(0, o.banded_window_halfwidth() + 1, 16) if o.fisher_banded_max_slots(w) >= self.pmax),
+                    default=-1) for o in self.orders]
+
+    def _refused(self, n, k):
+        return refused_output(n, dict(fisher=(k, k)))
+
+    def _dense(self, which, rest):
+        return [self.orders[i].fisher_mean(self.mds[i], self.rows[i][rest[i]], self.requests[i][0], "dense", self.max_units)
+                for i in which]
+
+    def reduce(self, sources):
+        """The sum of the unit matrices over the orders of a collected call: on the device (sf_multi_fisher_reduce) when every
+        unit ran on the band kernels and none was re-routed, else by :func:`reduce_fisher_host` -- the same rule, the same bits."""
+        if self._out is None:
+            raise RuntimeError("BandedMultiFisherPlan.reduce: collect() first")
+        if len(set(self.sizes)) != 1:
+            raise ValueError(f"sf_multi_fisher_reduce: the orders have {sorted(set(self.sizes))} walkers")
+        if self.complete and not self.rerouted:
+            return self.plan.reduce(sources)
+        return reduce_fisher_host(np.stack([o["lnl"] for o in self._out]), np.stack([o["info"] for o in self._out]),
+                                  [o["fisher"] for o in self._out], sources)
+
+
+def fisher_banded_multi(orders, mds, rows_list, columns, solver="banded", max_units=None, sync=True):
+    """The likelihood and the Fisher information of the mean-flux parameters for the (order x walker) units of several orders of
+    ONE device on the band solver (:class:`BandedMultiFisherPlan`; ``solver``: "banded" or "auto").  Returns its per-order
+    dicts; with ``sync=False`` the un-synchronised plan."""
+    plan = BandedMultiFisherPlan(orders, mds, rows_list, columns, solver=solver, max_units=max_units)
     plan.enqueue()
     return plan.collect() if sync else plan
 

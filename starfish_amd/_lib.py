@@ -253,6 +253,19 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP],
     ),
+    "sf_fisher_banded_multi_workspace_bytes_md": (
+        C.c_size_t,
+        [C.POINTER(Segment), C.c_int, C.POINTER(C.POINTER(ModelDesc)), C.POINTER(GradRequest), C.POINTER(C.c_int)],
+    ),
+    "sf_fisher_banded_multi_batch_md": (
+        C.c_int,
+        [C.POINTER(Segment), C.c_int, C.POINTER(C.POINTER(ModelDesc)), C.POINTER(GradRequest), C.POINTER(C.c_int), _VP, _VP, _VP,
+         _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP],
+    ),
+    "sf_multi_fisher_reduce": (
+        C.c_int,
+        [C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP],
+    ),
     "sf_banded_max_halfwidth": (C.c_int, [_VP]),
     "sf_banded_window_halfwidth": (C.c_int, [_VP]),
     "sf_banded_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int]),

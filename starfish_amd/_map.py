@@ -43,3 +43,28 @@ def minimize_lbfgsb(evaluate, x0, sampled, const_lp, kwargs, finite_for=None, fo
     if force_jac:
         opts["jac"] = True
     return minimize(objective, x0, **opts)
+
+
+def laplace_covariance(fisher, labels, terms):
+    """The Laplace covariance of ``labels`` from their Fisher matrix: ``terms`` lists ``(position, prior, x)`` for every prior on
+    one of the labels, and each adds ``-d^2 logpdf / d x^2`` at ``x`` to its diagonal entry by a central second difference with
+    the step of :func:`prior_value_and_slope`, in the order given.  The inverse is formed in normalised form, ``D^-1 (D^-1 F
+    D^-1)^-1 D^-1`` with ``D = sqrt(diag(F))``, by Cholesky; a matrix that is not positive definite (parameters the data do not
+    separate) raises ``np.linalg.LinAlgError`` naming the labels."""
+    F = np.array(fisher, dtype=np.float64)
+    for i, prior, x in terms:
+        h = _H0 * max(1.0, abs(x))
+        lp = prior.logpdf
+        F[i, i] -= (lp(x + h) - 2.0 * lp(x) + lp(x - h)) / (h * h)
+    with np.errstate(invalid="ignore"):  # (a negative diagonal entry: NaN, refused below)
+        d = np.sqrt(np.diag(F))
+    if not (np.all(np.isfinite(F)) and np.all(d > 0)):
+        raise np.linalg.LinAlgError(f"the Fisher matrix of {list(labels)} has a diagonal entry that is not positive or an "
+                                    "entry that is not finite")
+    try:
+        L = np.linalg.cholesky(F / np.outer(d, d))
+    except np.linalg.LinAlgError:
+        raise np.linalg.LinAlgError(f"the Fisher matrix of {list(labels)} is not positive definite: the data (and priors) do "
+                                    "not separate these parameters; freeze some of them or add priors") from None
+    Li = np.linalg.solve(L, np.eye(len(labels)))
+    return (Li.T @ Li) / np.outer(d, d)

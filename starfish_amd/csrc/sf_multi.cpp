@@ -8,7 +8,8 @@
 // every order's chain, the factor applied to a whole chunk's staging area at once, and per segment the contractions of the
 // two single-order gradient calls -- one factorisation per unit for the likelihood and its gradient.
 // sf_loglike_banded_multi_grad_batch_md (at the end) is that call on the band + Woodbury solver: no matrices, one launch of
-// each band sweep over all units of a chunk.
+// each band sweep over all units of a chunk.  sf_fisher_banded_multi_batch_md is its regrouping for the Fisher information of the
+// mean-flux parameters (one plain sweep over [r; Y; J] per unit), sf_multi_fisher_reduce the sum of the unit matrices.
 #include <algorithm>
 #include <cstdio>
 #include <string>
@@ -369,11 +370,13 @@ struct BandMultiFrame {
     sf_model_desc uni;
     int U, bmax, n16, halfwidth;
 };
+// who: the entry point the messages name; dense: the call they point to for what the window does not take
 static int banded_multi_frame(const sf_segment* segs, int nseg, const sf_model_desc* const* models, const sf_grad_request* reqs,
-                              const int* h_halfwidth, int grad_stride, BandMultiFrame* F) {
+                              const int* h_halfwidth, int grad_stride, BandMultiFrame* F, const char* who = BANDED_MULTI_GRAD,
+                              const char* dense = MULTI_GRAD) {
     if (segs && nseg > 0 && models) {
         if (!h_halfwidth) {
-            sf_set_error(BANDED_MULTI_GRAD ": h_halfwidth (one half-width per segment) is required");
+            sf_set_error("%s: h_halfwidth (one half-width per segment) is required", who);
             return SF_EINVAL;
         }
         // (no context is needed to refuse what no window takes; with one, the limit is that of its 1 + m right-hand sides)
@@ -381,24 +384,23 @@ static int banded_multi_frame(const sf_segment* segs, int nseg, const sf_model_d
             const sf_ctx* c = segs[i].ctx;
             const bool have = c && c->n;
             if (have && !c->monotonic) {
-                sf_set_error(BANDED_MULTI_GRAD ": segment %d: the banded solver needs a strictly increasing wavelength grid (use %s)",
-                             i, MULTI_GRAD);
+                sf_set_error("%s: segment %d: the banded solver needs a strictly increasing wavelength grid (use %s)", who, i, dense);
                 return SF_EINVAL;
             }
             const int wmax = have ? sf_banded_window_halfwidth(c) : sf_band_max_halfwidth(1);
             if (h_halfwidth[i] < 0 || h_halfwidth[i] > wmax) {
-                sf_set_error(BANDED_MULTI_GRAD ": segment %d: half-width %d outside [0, %d], the LDS window (use %s)", i,
-                             h_halfwidth[i], wmax, MULTI_GRAD);
+                sf_set_error("%s: segment %d: half-width %d outside [0, %d], the LDS window (use %s)", who, i, h_halfwidth[i], wmax,
+                             dense);
                 return SF_EINVAL;
             }
         }
     }
     SF_CHECK(multi_layout(segs, nseg, models, &F->L, &F->U, &F->bmax, &F->uni));
-    SF_CHECK(multi_grad_requests_ok(segs, nseg, models, reqs, grad_stride, BANDED_MULTI_GRAD));
+    SF_CHECK(multi_grad_requests_ok(segs, nseg, models, reqs, grad_stride, who));
     F->n16 = 0, F->halfwidth = 0;
     for (int i = 0; i < nseg; ++i) {
         if (segs[i].B > 65535) {  // (the fill and the tangents take one grid plane per unit)
-            sf_set_error(BANDED_MULTI_GRAD ": segment %d: B=%d must lie in 1 .. 65535", i, (int)segs[i].B);
+            sf_set_error("%s: segment %d: B=%d must lie in 1 .. 65535", who, i, (int)segs[i].B);
             return SF_EINVAL;
         }
         F->n16 = std::max(F->n16, (segs[i].ctx->n + 15) / 16 * 16);
@@ -562,4 +564,182 @@ extern "C" int sf_loglike_banded_multi_grad_batch_md(const sf_segment* segs, int
         }
     }
     return SF_OK;
+}
+
+// ----------------------------------------------------------------------------------- multi-order Fisher information on the band solver
+// sf_fisher_banded_multi_batch_md: the launch structure above with the head of sf_fisher_banded_mean_batch (banded_head,
+// sf_banded.cpp) in place of the gradient's.  Per segment on its lane: band fill, transform chain, row tangents, then the sweep's
+// rows [r; Y; J] into the segment's slice of one per-unit row buffer; per chunk on the caller's stream, over all its units at
+// once: ONE sweep -- the likelihood's, not a keeping one -- the capacitance step, lnl / info and F = G_JJ - U^T U.  The frame is
+// BandMultiFrame's with the largest row count 1 + m + max p_i: an order with fewer columns carries zero rows behind its own.
+#define BANDED_MULTI_FISHER "sf_fisher_banded_multi_batch_md"
+struct BandMultiFisherFrame {
+    BandMultiFrame F;
+    int pmax;
+};
+// what the call refuses before anything is enqueued, and its frame
+static int banded_multi_fisher_frame(const sf_segment* segs, int nseg, const sf_model_desc* const* models, const sf_grad_request* reqs,
+                                     const int* h_halfwidth, BandMultiFisherFrame* X) {
+    if (!reqs) {
+        sf_set_error(BANDED_MULTI_FISHER ": requests are required");
+        return SF_EINVAL;
+    }
+    X->pmax = 0;
+    for (int i = 0; i < nseg; ++i) {
+        if (reqs[i].want_cov) {
+            sf_set_error(BANDED_MULTI_FISHER ": segment %d: want_cov must be 0 (the covariance block is not computed)", i);
+            return SF_EINVAL;
+        }
+        if (reqs[i].n_mean_slots < 1) {
+            sf_set_error(BANDED_MULTI_FISHER ": segment %d: no mean slot to take the Fisher information in", i);
+            return SF_EINVAL;
+        }
+        X->pmax = std::max(X->pmax, (int)reqs[i].n_mean_slots);
+    }
+    SF_CHECK(banded_multi_frame(segs, nseg, models, reqs, h_halfwidth, SF_MEAN_GRAD_MAX_SLOTS, &X->F, BANDED_MULTI_FISHER,
+                                "sf_fisher_mean_batch"));
+    // the window's limit at the CALL's row count (fisher_window_ok's, sf_banded.cpp, for the frame)
+    const int m = X->F.L.m, nin = 1 + m + X->pmax;
+    if (m < 1 || m > 32 || sfb_admit(X->F.halfwidth, nin) != SFB_WINDOW) {
+        sf_set_error(BANDED_MULTI_FISHER ": half-width %d with 1 + %d + %d rows lies outside the LDS window (at most %d at this row "
+                     "count; use sf_fisher_mean_batch)", X->F.halfwidth, m, X->pmax, sf_band_max_halfwidth(nin));
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_fisher_banded_multi_workspace_bytes_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                                            const sf_grad_request* reqs, const int* h_halfwidth) {
+    BandMultiFisherFrame X;
+    if (banded_multi_fisher_frame(segs, nseg, models, reqs, h_halfwidth, &X)) return 0;
+    const BandMultiFrame& F = X.F;
+    return carve_band_multi_fisher(segs, nseg, models, reqs, F.L, F.n16, F.halfwidth, X.pmax, F.U, nullptr, 0,
+                                   carve_banded_multi(F, nullptr, 0).bytes).bytes;
+}
+extern "C" int sf_fisher_banded_multi_batch_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                               const sf_grad_request* reqs, const int* h_halfwidth, double* d_lnl, double* d_log_scale,
+                                               int* d_info, double* d_fisher, int fisher_ld, int fisher_stride, void* d_work,
+                                               size_t work_bytes, void* stream) {
+    BandMultiFisherFrame X;
+    SF_CHECK(banded_multi_fisher_frame(segs, nseg, models, reqs, h_halfwidth, &X));
+    if (!d_lnl || !d_info || !d_fisher || !d_work) {
+        sf_set_error(BANDED_MULTI_FISHER ": d_lnl, d_info, d_fisher and a workspace are required");
+        return SF_EINVAL;
+    }
+    if (fisher_ld < X.pmax || (int64_t)fisher_stride < (int64_t)fisher_ld * fisher_ld) {
+        sf_set_error(BANDED_MULTI_FISHER ": fisher_ld=%d < %d columns or fisher_stride=%d < fisher_ld^2", fisher_ld, X.pmax,
+                     fisher_stride);
+        return SF_EINVAL;
+    }
+    const BandMultiFrame& F = X.F;
+    const Layout& L = F.L;
+    const Work W = carve_banded_multi(F, d_work, work_bytes);
+    const BandMultiFisherWork G = carve_band_multi_fisher(segs, nseg, models, reqs, L, F.n16, F.halfwidth, X.pmax, F.U, d_work,
+                                                          work_bytes, W.bytes);
+    SF_CHECK(work_fits(work_bytes, G.bytes));
+    sf_ctx* c0 = segs[0].ctx;
+    if (use_device(c0)) return SF_EHIP;
+    hipStream_t s = (hipStream_t)stream;
+    prof_count_call();
+    sf_exec* ex = &c0->exec;
+    SF_CHECK(sf_exec_prepare(ex));
+    hipStream_t lane_stream[SF_MULTI_LANES] = {ex->aux, ex->side, ex->grp[0]};
+    const int H = G.halfwidth, n16 = G.n16, nin = G.nin, pmax = G.pmax, m = L.m, first_units = multi_first_units(F.U);
+    const int64_t sband = (int64_t)n16 * G.ldb, sbuf = (int64_t)nin * L.npad;
+    const size_t ng = (size_t)nin * nin, nl = (size_t)(1 + m) * (1 + m);
+    SF_HIP(hipEventRecord(ex->fork, s));
+    for (int l = 0; l < SF_MULTI_LANES; ++l) SF_HIP(hipStreamWaitEvent(lane_stream[l], ex->fork, 0));
+    struct Chunk {
+        int u0, units;
+        hipEvent_t filled[SF_MULTI_LANES];
+    };
+    std::vector<Chunk> chunks;
+    bool lane_used[SF_MULTI_LANES] = {};
+    int u0 = 0, cu0 = 0;
+    for (int i = 0; i < nseg; ++i) {
+        sf_ctx* c = segs[i].ctx;
+        const int B = segs[i].B, p = reqs[i].n_mean_slots;
+        const int lane = i % SF_MULTI_LANES;
+        hipStream_t sp = lane_stream[lane];
+        lane_used[lane] = true;
+        const Work w = with_trans_set(slice(W, u0), lane);
+        const AppliedWork& aw = G.seg[i];
+        {
+            ProfScope ps(sp, PS_FILL);
+            SF_HIP(hipMemsetAsync(w.info_c, 0, sizeof(int) * (size_t)B, sp));
+            sf_fill_args f = fill_args(c, models[i], segs[i].d_params, w);
+            f.C = nullptr, f.lda = 0, f.stride = 0, f.lower_only = 1, f.add_jitter = 1;
+            f.npad = n16;  // (identity rows up to the frame's row count)
+            SF_CHECK(sf_launch_band_fill(f, B, G.band + (size_t)u0 * sband, H + 1, H, G.ldb, sband, w.info_c,
+                                         G.gtab + (size_t)u0 * (G.ldb + 2), sp));
+        }
+        {
+            ProfScope ps(sp, PS_TRANSFORM);
+            SF_CHECK(run_transforms(c, models[i], B, segs[i].d_params, w, nullptr, aw.xs, nullptr, d_log_scale ? d_log_scale + u0 : nullptr,
+                                    true, sp));
+        }
+        sf_mean_grad_args cols = mean_grad_kernel_args(c, reqs[i].h_mean_slots, p, w, aw, nullptr, 0);
+        cols.info = w.info_e;  // (before the sweep: the transform chain's status)
+        SF_CHECK(sf_launch_mean_tangents(broaden_args(c, models[i], B, segs[i].d_params, w), c->inv_band.as<double>(),
+                                         emu_args(c, models[i], segs[i].d_params, w, w.mu, nullptr, w.Lw, w.info_e), cols, B, sp, false));
+        // the unit's rows: [r; Y] (zero right-hand sides on a shorter order's padding), its p columns, zero rows up to the frame's
+        SF_CHECK(sf_launch_fisher_rows(w.resid, w.Y, (int64_t)L.mpad * L.npad, c->n, L.npad, m, nin, B, aw.stage, sp));
+        SF_CHECK(sf_launch_fisher_tangents(eval_args(c, models[i], segs[i].d_params, w), cols, aw.stage + (int64_t)(1 + m) * L.npad, sbuf, B,
+                                           sp));
+        if (p < pmax)
+            SF_HIP(hipMemset2DAsync(aw.stage + (int64_t)(1 + m + p) * L.npad, sizeof(double) * (size_t)sbuf, 0,
+                                    sizeof(double) * (size_t)(pmax - p) * L.npad, B, sp));
+        u0 += B;
+        if ((chunks.empty() && u0 - cu0 >= first_units) || i == nseg - 1) {  // (the gradient call's chunks)
+            Chunk ch{cu0, u0 - cu0, {}};
+            for (int l = 0; l < SF_MULTI_LANES; ++l) {
+                if (!lane_used[l]) continue;
+                SF_CHECK(sf_exec_event(ex, &ch.filled[l]));
+                SF_HIP(hipEventRecord(ch.filled[l], lane_stream[l]));
+                lane_used[l] = false;
+            }
+            chunks.push_back(ch);
+            cu0 = u0;
+        }
+    }
+    for (const Chunk& ch : chunks) {
+        for (int l = 0; l < SF_MULTI_LANES; ++l)
+            if (ch.filled[l]) SF_HIP(hipStreamWaitEvent(s, ch.filled[l], 0));
+        const Work wc = slice(W, ch.u0);
+        const size_t u = (size_t)ch.u0;
+        int* info = d_info + ch.u0;
+        {
+            ProfScope ps(s, PS_POTRF);
+            sf_band_call k = {};
+            k.band = G.band + u * sband, k.sband = sband, k.ldb = G.ldb, k.halfwidth = H;
+            k.n = n16, k.batch = ch.units;
+            k.r = sf_band_rhs{G.buf + u * sbuf, sbuf, L.npad, nin, nullptr, 0};
+            k.logdet = G.logdet_band + u, k.gram = G.gram + u * ng, k.info = wc.info_c;
+            if (sf_band_twisted_applicable(n16, H, ch.units)) SF_CHECK(sf_launch_band_forms_twisted(k, G.twist, s));
+            else SF_CHECK(sf_launch_band_forms(k, s));
+        }
+        {
+            ProfScope ps(s, PS_SOLVE);
+            SF_CHECK(sf_launch_fisher_lead(G.gram + u * ng, nin, m + 1, ch.units, G.lead + u * nl, s));
+            SF_CHECK(sf_launch_woodbury(G.lead + u * nl, m + 1, ch.units, G.logdet_band + u, wc.logdet, wc.sqmah, wc.info_c, s));
+            SF_CHECK(sf_launch_finish(ch.units, wc.logdet, wc.sqmah, wc.info_e, wc.info_c, d_lnl + ch.u0, info, s));
+            // (k_fisher_band's leading dimension is its column count: compact pmax x pmax blocks, then the caller's layout)
+            SF_CHECK(sf_launch_fisher_band(G.gram + u * ng, m, pmax, ch.units, info, G.fcomp + u * pmax * pmax, (int64_t)pmax * pmax, s));
+            SF_CHECK(sf_launch_fisher_spread(G.fcomp + u * pmax * pmax, pmax, ch.units, d_fisher + (int64_t)ch.u0 * fisher_stride, fisher_ld,
+                                             fisher_stride, s));
+        }
+    }
+    return SF_OK;
+}
+extern "C" int sf_multi_fisher_reduce(int nseg, int W, const double* d_unit_lnl, const int* d_unit_info, const double* d_unit_fisher,
+                                      int fisher_ld, int fisher_stride, const int32_t* d_col_ptr, const int32_t* d_col_src, int ncols,
+                                      double* d_lnl, double* d_fisher, int out_stride, int* d_info, void* stream) {
+    if (!d_unit_lnl || !d_unit_info || !d_unit_fisher || !d_col_ptr || !d_lnl || !d_fisher || !d_info || (!d_col_src && ncols > 0)) {
+        sf_set_error("sf_multi_fisher_reduce: the unit results, the column map and the outputs are required");
+        return SF_EINVAL;
+    }
+    sf_multi_fisher_reduce_args a;
+    a.unit_lnl = d_unit_lnl, a.unit_info = d_unit_info, a.unit_fisher = d_unit_fisher, a.col_ptr = d_col_ptr, a.col_src = d_col_src;
+    a.nseg = nseg, a.W = W, a.fisher_ld = fisher_ld, a.ncols = ncols, a.fisher_stride = fisher_stride, a.out_stride = out_stride;
+    a.lnl = d_lnl, a.fisher = d_fisher, a.info = d_info;
+    return sf_launch_multi_fisher_reduce(a, (hipStream_t)stream);
 }

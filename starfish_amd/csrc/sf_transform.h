@@ -130,6 +130,22 @@ int sf_launch_fisher_band(const double* gram, int m, int p, int batch, const int
 size_t sf_fisher_part_doubles(int n, int nslots, int batch);
 int sf_launch_fisher_ztz(const double* Z, int n, int npad, int p, int batch, const int* info, double* part, double* fisher,
                          int64_t fstride, hipStream_t s);
+// sf_fisher_multi.h: all orders of a multi-order call.  The compact p x p blocks sf_launch_fisher_band leaves (fstride = p^2)
+// into fisher[u * fstride + a * ld + b]; and the sum of the unit matrices over the orders (sf_multi_fisher_reduce)
+int sf_launch_fisher_spread(const double* comp, int p, int batch, double* fisher, int ld, int64_t fstride, hipStream_t s);
+struct sf_multi_fisher_reduce_args {
+    const double* unit_lnl;     // [nseg * W]
+    const int* unit_info;       // [nseg * W]
+    const double* unit_fisher;  // [nseg * W][fisher_stride], rows of fisher_ld
+    const int* col_ptr;         // [ncols + 1]
+    const int* col_src;         // [col_ptr[ncols]][2]: (segment, slot), ascending in the segment within a column
+    int nseg, W, fisher_ld, ncols;
+    int64_t fisher_stride, out_stride;
+    double* lnl;     // [W]
+    double* fisher;  // [W][out_stride], rows of ncols
+    int* info;       // [W]
+};
+int sf_launch_multi_fisher_reduce(const sf_multi_fisher_reduce_args& a, hipStream_t s);
 
 int sf_launch_extinct_rows(const double* wave, int n, const double* flux, int rows, double Av, double Rv, int law,
                            double* out, hipStream_t s);  // law: 0 ccm89, 1 odonnell94, 2 calzetti00

@@ -17,6 +17,7 @@
 //   sf_transform_v11.h      k_v11_build, k_v11_build_batch
 //   sf_mean_grad.h          the gradient in the mean-flux parameters: k_mean_stage, k_mean_finish, k_mean_pixel, k_mean_sum
 //   sf_fisher.h             the Fisher information of the mean-flux parameters: k_fisher_tangent, k_fisher_band, k_fisher_ztz
+//   sf_fisher_multi.h       the Fisher matrices of a multi-order call: k_fisher_spread, k_multi_fisher_reduce
 #include "sf_common.h"
 #include "sf_device.h"
 #include "sf_transform.h"
@@ -27,3 +28,4 @@
 #include "sf_transform_v11.h"
 #include "sf_mean_grad.h"
 #include "sf_fisher.h"
+#include "sf_fisher_multi.h"

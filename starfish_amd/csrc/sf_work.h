@@ -460,6 +460,55 @@ static BandMultiGradWork carve_band_multi_grad(const sf_segment* segs, int nseg,
     return g;
 }
 
+// ------------------------------------------------------------------- multi-order Fisher information on the band solver
+// (sf_fisher_banded_multi_batch_md; behind the Work of the same call, which has no matrices: base_bytes = its size)  The common
+// frame of carve_band_multi_grad with nin = 1 + m + pmax rows per unit, pmax the largest column count of a segment.  For all U
+// units, as carve_band and carve_band_fisher lay them out for one order: band [U][n16][ldb], lead [U][(1 + m)^2] (the Gram
+// matrices' leading blocks, for the capacitance step), logdet_band, gtab, buf [U][nin][npad] (the sweep's rows [r; Y; J; 0]),
+// gram [U][nin^2], twist (the two half sweeps' workspace for nin rows and U units; the chunks run one after the other and
+// share it) and fcomp [U][pmax^2], the compact blocks of k_fisher_band.  Then per segment, in segment order, what the tangent
+// columns read per unit with the order's own n: xs, dcoef (vsini), kdot, mudot.  (No coef of its own: the columns are written on
+// the segment's lane, behind its chain, before the lane's next segment overwrites the Work's.)
+struct BandMultiFisherWork {
+    int nin, pmax, n16, halfwidth, ldb;
+    double *band, *lead, *logdet_band, *gtab, *buf, *gram, *twist, *fcomp;
+    std::vector<AppliedWork> seg;
+    size_t bytes;
+};
+static BandMultiFisherWork carve_band_multi_fisher(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                                   const sf_grad_request* reqs, const Layout& L, int n16, int halfwidth, int pmax, int U,
+                                                   void* p, size_t cap, size_t base_bytes) {
+    Carve k(p, cap, base_bytes);
+    BandMultiFisherWork g{};
+    g.pmax = pmax, g.nin = 1 + L.m + pmax, g.n16 = n16, g.halfwidth = halfwidth, g.ldb = (halfwidth + 2) & ~1;
+    const size_t u = (size_t)U, npad = (size_t)L.npad, nl = (size_t)(1 + L.m) * (1 + L.m), ng = (size_t)g.nin * g.nin;
+    g.band = k.take<double>(u * n16 * g.ldb);
+    g.lead = k.take<double>(u * nl);
+    g.logdet_band = k.take<double>(u);
+    g.gtab = k.take<double>(u * (g.ldb + 2));
+    g.buf = k.take<double>(u * g.nin * npad);
+    g.gram = k.take<double>(u * ng);
+    g.twist = k.take<double>(sfb_twist_carve(nullptr, halfwidth, g.nin, U).doubles);
+    g.fcomp = k.take<double>(u * pmax * pmax);
+    g.seg.assign(nseg, AppliedWork{});
+    size_t u0 = 0;
+    for (int i = 0; i < nseg; ++i) {
+        const sf_ctx* c = segs[i].ctx;
+        const size_t B = (size_t)segs[i].B;
+        const int nslots = reqs[i].n_mean_slots;
+        AppliedWork& w = g.seg[i];
+        w.stage = g.buf ? g.buf + u0 * g.nin * npad : nullptr;
+        w.xs = k.take<double>(B * c->m * c->n);
+        if (models[i]->has_vsini) w.dcoef = k.take<double>(B * c->nf * c->rows);
+        const size_t ngrid = (size_t)(nslots < c->P ? nslots : c->P), mM = (size_t)c->m * c->M;
+        w.kdot = k.take<double>(ngrid * B * mM);
+        w.mudot = k.take<double>(ngrid * B * c->m);
+        u0 += B;
+    }
+    g.bytes = sf_align_up(k.off, 256);
+    return g;
+}
+
 // ------------------------------------------------------------------- context-free workspaces
 // sf_potri_diag_batch: the transposed inverses of the 64 x 64 diagonal blocks, [batch][n / 64][64][64]; sf_potri_blocks_batch
 // (with_diag): the same, then the diagonal of the inverse ([batch][n]: the inverse's launch writes it)

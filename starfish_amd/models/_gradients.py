@@ -186,27 +186,12 @@ class Gradients:
         ``eps^(1/3) max(1, |x|)``.  The covariance hyper-parameters are held fixed; see :meth:`fisher_information` for what
         the matrix leaves out.  The inverse is formed in normalised form, ``D^-1 (D^-1 F D^-1)^-1 D^-1`` with ``D =
         sqrt(diag(F))``, by Cholesky; a matrix that is not positive definite (parameters the data do not separate) raises
-        ``np.linalg.LinAlgError`` naming the labels.  ``priors`` are checked as :meth:`train` checks them."""
+        ``np.linalg.LinAlgError`` naming the labels (:func:`starfish_amd._map.laplace_covariance`).  ``priors`` are checked as
+        :meth:`train` checks them."""
         priors = self._checked_priors(priors)
         labels = self.mean_gradient_labels
-        F = np.array(self.fisher_information(solver=solver), dtype=np.float64)
-        for i, key in enumerate(labels):
-            if key in priors:
-                x = float(self[key])
-                h = _map._H0 * max(1.0, abs(x))
-                lp = priors[key].logpdf
-                F[i, i] -= (lp(x + h) - 2.0 * lp(x) + lp(x - h)) / (h * h)
-        d = np.sqrt(np.diag(F))
-        if not (np.all(np.isfinite(F)) and np.all(d > 0)):
-            raise np.linalg.LinAlgError(f"the Fisher matrix of {list(labels)} has a diagonal entry that is not positive or an "
-                                        "entry that is not finite")
-        try:
-            L = np.linalg.cholesky(F / np.outer(d, d))
-        except np.linalg.LinAlgError:
-            raise np.linalg.LinAlgError(f"the Fisher matrix of {list(labels)} is not positive definite: the data (and priors) do "
-                                        "not separate these parameters; freeze some of them or add priors") from None
-        Li = np.linalg.solve(L, np.eye(len(labels)))
-        return (Li.T @ Li) / np.outer(d, d)
+        terms = [(i, priors[key], float(self[key])) for i, key in enumerate(labels) if key in priors]
+        return _map.laplace_covariance(self.fisher_information(solver=solver), labels, terms)
 
     def _scatter_combined(self, grad, md, out, columns):
         """A combined device result -- the mean ``columns`` in request order (none: ``[]``), then, where covariance labels are

@@ -434,6 +434,135 @@ class EchelleModel:
         SpectrumModel._raise_for_info(info[0])
         return float(lnl[0]), dict(zip(self.labels, (float(v) for v in grad[0])))
 
+    # ------------------------------------------------------------------ Fisher information of all orders in one pass
+    @property
+    def mean_gradient_labels(self):
+        """tuple of str : the labels of :attr:`labels` that are not under ``global_cov:`` / ``local_cov:`` (bare or behind
+        ``order{i}:``) and are not ``Rv``, in :attr:`labels` order: the parameters of :meth:`fisher_information`."""
+        def bare(key):
+            hit = _PREFIXED.match(key)
+            return hit.group(2) if hit else key
+
+        return tuple(key for key in self.labels if not bare(key).startswith(("global_cov:", "local_cov:")) and bare(key) != "Rv")
+
+    def _fisher_layout(self, solver=None):
+        """Host logic of the Fisher matrix, no device, in the manner of :meth:`_gradient_layout`: ``(labels, cols, columns,
+        sources)``.  ``solver`` as there.  ``columns[i]``: the columns of order i's C-ABI parameter row that hold its mean-flux
+        labels (:attr:`SpectrumModel.mean_gradient_labels` order); ``sources[j]``: the ``(order, slot)`` pairs of the unit
+        matrices that label j of :attr:`mean_gradient_labels` adds up, ascending in the order -- a shared label has a source in
+        every order, an ``order{i}:`` label one.  Raises ``ValueError``, naming the order, for what the device does not
+        differentiate, for more than ``MEAN_GRAD_MAX_SLOTS`` columns in one order and, with ``solver=None``, for an order whose
+        own solver is not "dense"."""
+        from .. import _device as D
+
+        if solver is not None:
+            D.check_solver(solver, or_none=True)
+        labels, cols = self._layout()
+        mean = self.mean_gradient_labels
+        if not mean:
+            raise ValueError("no thawed mean-flux parameter to take the Fisher information in")
+        position = {labels.index(key): j for j, key in enumerate(mean)}
+        columns, sources = [], [[] for _ in mean]
+        for i, m in enumerate(self.orders):
+            if solver is None and m.solver != "dense":
+                raise ValueError(f"order {i}: solver=None runs the Fisher information on the dense solver only, not "
+                                 f"solver={m.solver!r}; pass solver=")
+            own = list(m.labels)
+            try:
+                c = m._mean_gradient_columns(None, m._model_desc(None))
+            except ValueError as e:
+                raise ValueError(f"order {i}: {e}") from None
+            if len(c) > D.MEAN_GRAD_MAX_SLOTS:
+                raise ValueError(f"order {i}: {len(c)} thawed mean-flux parameters, the device takes the Fisher information in at "
+                                 f"most {D.MEAN_GRAD_MAX_SLOTS} per order")
+            columns.append(c)
+            for k, key in enumerate(m.mean_gradient_labels):
+                sources[position[int(cols[i][own.index(key)])]].append((i, k))
+        return labels, cols, columns, sources
+
+    def fisher_information_batch(self, P, return_info=False, return_orders=False, solver=None):
+        """The Fisher information of the mean-flux parameters at fixed covariance for B parameter vectors (rows of ``P`` in
+        :attr:`labels` order; covariance labels take their values from ``P``): ``(B, p, p)`` in :attr:`mean_gradient_labels`
+        order, symmetric bit for bit -- the sum over the orders of every order's ``F_ij = fdot_i^T C^-1 fdot_j``
+        (:meth:`SpectrumModel.fisher_information`), embedded by the labels: a shared label adds up all orders, the entry between
+        labels of two different orders is exactly 0.  This is the Gauss-Newton, fixed-covariance matrix: the term ``1/2 tr(C^-1
+        dC_i C^-1 dC_j)`` that a grid parameter has because the emulator's rows sit inside the covariance is left out, and so is
+        the block of the covariance hyper-parameters (the mean / covariance cross block of a Gaussian's Fisher matrix is zero).
+        A walker that fails in any order gets a NaN matrix; with ``return_info`` ``(fisher, info)``, ``info`` the first non-zero
+        per-order code; with ``return_orders`` also the list of the per-order unit matrices ``(B, p_i, p_i)``.  The model's
+        state is not modified.
+
+        solver: None / "dense" -- every order's dense ``fisher_mean`` call (None: every order's own ``solver`` must be "dense");
+                "banded" -- the band + Woodbury solver, ONE sweep per (order x walker) unit and all units of a device in one
+                            launch sequence (``sf_fisher_banded_multi_batch_md``); a walker with a unit whose covariance
+                            support exceeds the LDS window at the call's row count gets a NaN matrix and info = -4;
+                "auto"  -- banded for the units whose half-width bound fits that window, the dense call for the rest.
+        The sum over the orders runs in ascending order index, on the device (``sf_multi_fisher_reduce``) when one band call
+        held every unit, else on the host by the same rule (:func:`starfish_amd._device.reduce_fisher_host`)."""
+        from .. import _device as D
+
+        labels, cols, columns, sources = self._fisher_layout(solver)
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        if P.shape[1] != len(labels):
+            raise ValueError("Param Vector does not match length of thawed parameters")
+        packed = [m._pack(P[:, cols[i]], update_caches=False) for i, m in enumerate(self.orders)]
+        pending = []
+        for idxs in self._by_device(packed):  # enqueue everything first, synchronise afterwards
+            plan = None
+            if solver in ("banded", "auto"):
+                plan = D.fisher_banded_multi([packed[i][0] for i in idxs], [packed[i][1] for i in idxs],
+                                             [packed[i][2] for i in idxs], [columns[i] for i in idxs], solver=solver, sync=False)
+            pending.append((idxs, plan))
+        unit = [None] * len(self.orders)
+        for idxs, plan in pending:
+            outs = plan.collect() if plan is not None else [packed[i][0].fisher_mean(packed[i][1], packed[i][2], columns[i])
+                                                            for i in idxs]
+            for i, out in zip(idxs, outs):
+                unit[i] = out
+        if len(pending) == 1 and pending[0][1] is not None:
+            _lnl, fisher, info = pending[0][1].reduce(sources)
+        else:
+            _lnl, fisher, info = D.reduce_fisher_host(np.stack([u["lnl"] for u in unit]), np.stack([u["info"] for u in unit]),
+                                                      [u["fisher"] for u in unit], sources)
+        self.last_info = info
+        out = (fisher,)
+        if return_info:
+            out += (info,)
+        if return_orders:
+            out += ([u["fisher"] for u in unit],)
+        return out if len(out) > 1 else fisher
+
+    def fisher_information(self, solver=None):
+        """:meth:`fisher_information_batch` at the current state: ``(p, p)`` in :attr:`mean_gradient_labels` order -- the
+        Gauss-Newton, fixed-covariance matrix, without the ``1/2 tr(C^-1 dC_i C^-1 dC_j)`` term of the grid parameters and without
+        the block of the covariance hyper-parameters.  Raises as :meth:`log_likelihood` does for a point the device flags; the
+        model's state is not modified."""
+        fisher, info = self.fisher_information_batch(self.get_param_vector()[None, :], return_info=True, solver=solver)
+        SpectrumModel._raise_for_info(info[0])
+        return fisher[0]
+
+    def parameter_covariance(self, priors=None, solver=None):
+        """The Laplace covariance of the labels of :attr:`mean_gradient_labels` at the current state (the point :meth:`train`
+        found): the inverse of :meth:`fisher_information` plus, for every prior on one of these labels, ``-d^2 logpdf / d
+        label^2`` by a central second difference with step ``eps^(1/3) max(1, |x|)``.  ``priors`` are looked up as :meth:`train`
+        does: a bare per-order key counts once per order, on that order's own label.  The covariance hyper-parameters are held
+        fixed; see :meth:`fisher_information_batch` for what the matrix leaves out.  Inverted in normalised form by Cholesky; a
+        matrix that is not positive definite raises ``np.linalg.LinAlgError`` naming the labels
+        (:func:`starfish_amd._map.laplace_covariance`)."""
+        from .. import _map
+
+        for key, prior in (priors or {}).items():
+            if not callable(getattr(prior, "logpdf", None)):
+                raise ValueError(f"Invalid priors. {key} does not have a `logpdf` method")
+        labels, cols = self._layout()
+        mean = self.mean_gradient_labels
+        terms = []
+        for prior, i, key in self._prior_terms(priors):
+            own = self.orders[i].labels
+            if key in own and labels[cols[i][own.index(key)]] in mean:
+                terms.append((mean.index(labels[cols[i][own.index(key)]]), prior, float(self.orders[i][key])))
+        return _map.laplace_covariance(self.fisher_information(solver=solver), mean, terms)
+
     def train(self, priors=None, *, gradient_solver=None, **kwargs):
         """MAP estimate over :attr:`labels`: ``scipy.optimize.minimize(method="L-BFGS-B", jac=True)`` on the analytic gradient
         of :meth:`log_likelihood_gradient_batch` -- a per-order fit has a few hundred parameters, which a simplex search
