@@ -132,7 +132,16 @@ int sf_extinct(const double* d_wave, int n, const double* d_flux, int rows, doub
 /* scipy.linalg.cho_factor call site Starfish/models/spectrum_model.py:400 (LAPACK dpotrf).
  * In-place batched lower Cholesky of `batch` matrices, matrix b at d_A + b*stride (doubles),
  * n must be a multiple of 64 (callers pad with an identity block), row stride lda.
- * d_work: sf_potrf_workspace_bytes(n, batch).  d_info[batch]: 0, or the 1-based index of the first non-positive pivot. */
+ * Layout contract: d_A 16-byte aligned, lda >= n and even, stride even (every matrix base is then 16-byte aligned: the
+ * panel kernels fetch 16-byte granules) and stride >= (n - 1) lda + n (the matrices are factorised concurrently in place,
+ * so no two may share an element; stride = n lda is the usual choice, a larger one leaves a gap).  Only the lower triangle
+ * (diagonal included) is read; the strict upper triangle is undefined afterwards; the columns n .. lda of a row, the gaps
+ * between matrices and everything outside [d_A, d_A + (batch - 1) stride + (n - 1) lda + n) are neither read into a result
+ * nor written.  The workspace needs no initialisation and may be reused from call to call.
+ * d_work: sf_potrf_workspace_bytes(n, batch).  d_info[batch]: 0, or the 1-based index of the first non-positive pivot; the
+ * factor's columns left of that pivot are those of the successful factorisation.
+ * SF_EINVAL before anything is enqueued: a null d_A, d_info or d_work, n not a positive multiple of 64, lda < n or odd,
+ * batch < 1, stride odd or below (n - 1) lda + n, work_bytes below sf_potrf_workspace_bytes(n, batch). */
 int sf_potrf_batch(double* d_A, int n, int lda, int64_t stride, int batch, int* d_info,
                    void* d_work, size_t work_bytes, void* stream);
 size_t sf_potrf_workspace_bytes(int n, int batch);
@@ -140,7 +149,10 @@ size_t sf_potrf_workspace_bytes(int n, int batch);
 /* Starfish/models/spectrum_model.py:401-404: logdet = 2 sum log L_ii and sqmah = R^T C^-1 R
  * = |L^-1 R|^2 (one forward substitution; the reference's cho_solve does two).
  * d_L as left by sf_potrf_batch; d_R: batch x ldr (ldr >= n, padded entries zero);
- * d_work: sf_potrf_workspace_bytes(n, batch) (only touched when n*8 bytes exceed the LDS). */
+ * d_work: sf_potrf_workspace_bytes(n, batch) (only touched when n*8 bytes exceed the LDS: from n = 16256 on, where a
+ * missing or short workspace is refused with SF_ENOMEM; below that d_work may be NULL).  Only the lower triangle of d_L is
+ * read.  SF_EINVAL before anything is enqueued: a null d_L, d_R, d_logdet or d_sqmah, n not a multiple of 64, batch < 1,
+ * ldr < n. */
 int sf_logdet_sqmah_batch(const double* d_L, int n, int lda, int64_t stride, int batch,
                           const double* d_R, int ldr, void* d_work, size_t work_bytes,
                           double* d_logdet, double* d_sqmah, void* stream);

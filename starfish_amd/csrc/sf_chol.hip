@@ -114,8 +114,16 @@ int sf_potrf_front_pad(int n, int batch) {
 
 int sf_launch_potrf(double* A, int n, int lda, int64_t stride, int batch, int* info, double* work,
                     double* rhs, int ldr, hipStream_t s, const sf_gen_args* gen, sf_exec* ex) {
-    if (n % SF_LEAF != 0 || lda < n || batch <= 0 || (lda & 1) || !work) {
+    if (n <= 0 || n % SF_LEAF != 0 || lda < n || batch <= 0 || (lda & 1) || !work) {
         sf_set_error("potrf: n must be a positive multiple of %d, lda >= n and even, workspace required", SF_LEAF);
+        return SF_EINVAL;
+    }
+    // every matrix base must be 16-byte aligned like the first (the panel kernels fetch operands as 16-byte granules:
+    // global_load_lds_dwordx4 in the K loops, double2 loads of the L slab and of the partial sums), and the matrices are
+    // factorised in place concurrently, so no two may share an element
+    if ((stride & 1) || stride < (int64_t)(n - 1) * lda + n) {
+        sf_set_error("potrf: stride=%lld must be even and at least (n - 1) lda + n = %lld", (long long)stride,
+                     (long long)((int64_t)(n - 1) * lda + n));
         return SF_EINVAL;
     }
     const sf_potrf_scratch ws = sf_potrf_scratch_of(work, n, batch);
