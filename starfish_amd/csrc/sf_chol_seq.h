@@ -129,6 +129,15 @@ static void sf_wide_stamps_report(sf_wide_stamps& w, hipStream_t s) {
         for (auto& sg : seg) fprintf(stderr, " %7.1f |", (t[sg[1]] - t[sg[0]]) / 100.0);
         fprintf(stderr, " %7.1f\n", (t[8] - t[0]) / 100.0);
     }
+    // the interval 6 -> 7 of the same launches, per half (panel k, panel k + 1) of step 4
+    fprintf(stderr, "step 4 of the same launches: k nslab | half 0: dump | wait for S | MFMA | half 1: dump | wait for S | MFMA (us)\n");
+    for (int i = 0; i < w.n; ++i) {
+        const long long* t = w.t + 16 * i;
+        fprintf(stderr, "%2d %2d |", w.k[i] / 1000, w.k[i] % 1000);
+        const int seg[6][2] = {{6, 9}, {9, 10}, {10, 11}, {11, 12}, {12, 13}, {13, 14}};
+        for (auto& sg : seg) fprintf(stderr, " %7.2f |", (t[sg[1]] - t[sg[0]]) / 100.0);
+        fprintf(stderr, "\n");
+    }
     (void)hipHostFree(w.t);
 }
 #else

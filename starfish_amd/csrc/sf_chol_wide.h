@@ -20,7 +20,7 @@
 //                              k_chol_panel: a wave dumps its T blocks when its registers become the L accumulators)
 //   2b T2 -= L1 L21^T         (L21 = L[panel k+1 rows, panel k columns], left in place by the chain's narrow step)
 //   2c L2 = T2 W_k+1
-//   3  L -> C in place, rhs[slab] -= L1 z_k + L2 z_k+1
+//   3  L -> C in place (the stores are issued under the MFMAs of step 4), rhs[slab] -= L1 z_k + L2 z_k+1
 //   4  S  = C[slab, slab] - L L^T (K = 256): L goes from the accumulators into one 128 x 128 LDS image per panel; the 36
 //         lower blocks of the tile are spread over the 16 waves (9 per SIMD) and accumulate over both panels in registers
 // Same arithmetic as two consecutive k_chol_panel steps; the summation order of 2b differs (natural k order instead
@@ -240,91 +240,118 @@ __device__ __forceinline__ void sf_panelw_body(const sf_panelw_args& g, const in
     }
 
     // ---------------------------------------------------------------- 2: triangular solves through LDS
-    // (round 6: the chunk buffers alternate -- a chunk is dumped while the previous one is still being read, so the barrier
-    // that used to stand in front of every dump is gone: 12 of the epilogue's ~36 workgroup-wide barriers)
+    // (round 6: the chunk buffers alternate -- a chunk is dumped while the previous one is still being read, so no barrier
+    // stands in front of a dump)
     double* Ach0 = smw;                         // [2][128][CLD] chunks of the A operand (accumulator -> operand layout)
-    double* Bs = smw + 2 * GT * CLD;            // [2][128][GLD] 16-column blocks of W  /  [2][128][CLD] chunks of L21
-    const int lr = tid >> 3, lc = (tid & 7) * 2;  // staging: 128 rows x 8 threads
-    // L = T W on the blocks NB, NB + 1 of every wave (NB = 0: panel k, NB = 2: panel k + 1), K blocks in descending order
-    // (rw: the K block 7 of W, requested by the caller ahead of the phase that precedes the solve: every global round trip of
-    // the epilogue -- W, L21, z, the diagonal tile -- is in flight before the phase that needs it: with one workgroup per CU
-    // nothing else hides them; 78 -> ~66 us of fixed cost per task, profiles/r05_e_wide_kernel_phases_*.txt)
-    auto w_rows = [&](const double* Wt) { return Wt + (int64_t)b * g.sW + (int64_t)lr * SF_LDT + lc; };
-    auto solve = [&](const double* Wt, double2 rw, auto nbtag) {
+    double* Bs = smw + 2 * GT * CLD;            // [2][128][CLD] chunks of W  /  of L21
+    const int lr = tid >> 3, lc = (tid & 7) * 2;  // staging: 128 rows x 8 threads, four doubles each
+    // L = T W on the blocks NB, NB + 1 of every wave (NB = 0: panel k, NB = 2: panel k + 1), K blocks in descending order.
+    // W is staged in 32-row chunks like T and L21 (the K blocks 2 c + 1 and 2 c meet at ONE barrier), and chunk c - 1 is
+    // dumped and staged AHEAD of the MFMAs of chunk c: the T blocks its owners hand over are untouched until then, and its
+    // buffers ((c - 1) & 1) were last read two chunks ago.  12 barriers in the phases 2a / 2b / 2c instead of 22; per task
+    // 10.7 -> 9.3 us (2a), 17.2 -> 16.2 (2b), 12.4 -> 12.0 (2c): profiles/r07_a_wide_fixed_part_ab.txt.
+    // (rw[0..1] / rw[2..3]: the chunks 3 and 2 of W, requested by the caller ahead of the phase that precedes the solve: every
+    // global round trip of the epilogue -- W, L21, z, the diagonal tile -- is in flight before the phase that needs it: with one
+    // workgroup per CU nothing else hides them; 78 -> ~66 us of fixed cost per task, profiles/r05_e_wide_kernel_phases_*.txt)
+    auto w_rows = [&](const double* Wt) { return Wt + (int64_t)b * g.sW + (int64_t)lr * SF_LDT + 2 * lc; };
+    auto w_chunk = [&](const double* Wp, int c, double2& r0, double2& r1) {
+        r0 = *(const double2*)(Wp + c * 32);
+        r1 = *(const double2*)(Wp + c * 32 + 2);
+    };
+    auto stage4 = [&](double* pb, double2 r0, double2 r1) {  // the thread's four doubles of a 128 x 32 chunk (row stride CLD)
+        pb[0] = r0.x;
+        pb[1] = r0.y;
+        pb[2] = r1.x;
+        pb[3] = r1.y;
+    };
+    auto solve = [&](const double* Wt, double2 (&rw)[4], auto nbtag, auto&& ahead) {
         constexpr int NB = decltype(nbtag)::value;
         const double* Wp = w_rows(Wt);
-        int buf = 0;
+        auto stage = [&](int c, double2 r0, double2 r1) {
+            double* Ach = Ach0 + (c & 1) * (GT * CLD);
+            if (wn == c) {  // the chunk's owner waves hand their T blocks over
 #pragma unroll
-        for (int sbi = 0; sbi < 8; ++sbi) {
-            const int sb = 7 - sbi;
-            double* Ach = Ach0 + ((sb >> 1) & 1) * (GT * CLD);  // (chunk sb / 2: its buffer was last read two chunks = four barriers ago)
-            // (the phase before the second solve -- step 2b -- reads the same buffers: one barrier in front of its first dump)
-            if (sb == 7 && NB != 0) __syncthreads();
-            if (sb & 1) {  // first block of chunk sb / 2: its owner waves hand their T blocks over
-                if (wn == (sb >> 1)) {
+                for (int nn = 0; nn < 2; ++nn)
 #pragma unroll
-                    for (int nn = 0; nn < 2; ++nn)
+                    for (int mi = 0; mi < TM; ++mi) {
 #pragma unroll
-                        for (int mi = 0; mi < TM; ++mi) {
-#pragma unroll
-                            for (int r = 0; r < 4; ++r)
-                                Ach[(wm * 32 + mi * 16 + lq + 4 * r) * CLD + nn * 16 + l15] = acc[mi][NB + nn][r];
-                            acc[mi][NB + nn] = (sf_d4){0.0, 0.0, 0.0, 0.0};
-                        }
-                }
+                        for (int r = 0; r < 4; ++r)
+                            Ach[(wm * 32 + mi * 16 + lq + 4 * r) * CLD + nn * 16 + l15] = acc[mi][NB + nn][r];
+                        acc[mi][NB + nn] = (sf_d4){0.0, 0.0, 0.0, 0.0};
+                    }
             }
-            {
-                double* pb = Bs + buf * (GT * GLD) + lr * GLD + lc;
-                pb[0] = rw.x;
-                pb[1] = rw.y;
-            }
+            stage4(Bs + (c & 1) * (GT * CLD) + lr * CLD + 2 * lc, r0, r1);
+        };
+        // (the phase before this one read the buffers of the other parity last: no barrier in front of the first dump)
+        stage(3, rw[0], rw[1]);
+        w_chunk(Wp, 1, rw[0], rw[1]);  // (a chunk is requested as soon as its registers are free: two chunks ahead)
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) {
+            const int c = 3 - ci;
             __syncthreads();
-            if (sb > 0) rw = *(const double2*)(Wp + (sb - 1) * 16);
-            // W[k][c] = 0 for k > c: the wave's columns (blocks 2 wn, 2 wn + 1 of the panel) need K blocks <= 2 wn + 1
-            if (sb <= 2 * wn + 1 && wave_live) {
-                const double* Ab = Ach + (wm * 32 + l15) * CLD + (sb & 1) * 16 + lq;
-                const double* Bb = Bs + buf * (GT * GLD) + (wn * 32 + l15) * GLD + lq;
+            if (c == 3) {
+                stage(2, rw[2], rw[3]);
+                w_chunk(Wp, 0, rw[2], rw[3]);
+            }
+            if (c == 2) stage(1, rw[0], rw[1]);
+            if (c == 1) {
+                stage(0, rw[2], rw[3]);
+            }
+            if (c <= 1) ahead(c);  // (the caller's requests for the next phase: the W registers are free from here on)
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    double a[TM], bb[2];
+            for (int sb = 2 * c + 1; sb >= 2 * c; --sb) {
+                // W[k][c] = 0 for k > c: the wave's columns (blocks 2 wn, 2 wn + 1 of the panel) need K blocks <= 2 wn + 1
+                if (sb <= 2 * wn + 1 && wave_live) {
+                    const double* Ab = Ach0 + (c & 1) * (GT * CLD) + (wm * 32 + l15) * CLD + (sb & 1) * 16 + lq;
+                    const double* Bb = Bs + (c & 1) * (GT * CLD) + (wn * 32 + l15) * CLD + (sb & 1) * 16 + lq;
 #pragma unroll
-                    for (int i = 0; i < TM; ++i) a[i] = Ab[i * 16 * CLD + ks * 4];
+                    for (int ks = 0; ks < 4; ++ks) {
+                        double a[TM], bb[2];
 #pragma unroll
-                    for (int i = 0; i < 2; ++i) bb[i] = Bb[i * 16 * GLD + ks * 4];
+                        for (int i = 0; i < TM; ++i) a[i] = Ab[i * 16 * CLD + ks * 4];
 #pragma unroll
-                    for (int mi = 0; mi < TM; ++mi)
+                        for (int i = 0; i < 2; ++i) bb[i] = Bb[i * 16 * CLD + ks * 4];
 #pragma unroll
-                        for (int nn = 0; nn < 2; ++nn)
-                            acc[mi][NB + nn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], bb[nn], acc[mi][NB + nn], 0, 0, 0);
+                        for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+                            for (int nn = 0; nn < 2; ++nn)
+                                acc[mi][NB + nn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], bb[nn], acc[mi][NB + nn], 0, 0, 0);
+                    }
                 }
             }
-            buf ^= 1;
         }
     };
-    // ---- requested now, used later: first rows of W_k
-    double2 rw0 = *(const double2*)(w_rows(g.Wt0) + 7 * 16);
+    // ---- requested now, used later: the first two chunks of W_k
+    double2 rw[4];
+    w_chunk(w_rows(g.Wt0), 3, rw[0], rw[1]);
+    w_chunk(w_rows(g.Wt0), 2, rw[2], rw[3]);
     __syncthreads();  // (the main loop's last reads of the ring are done)
     SF_W_STAMP(2);
-    solve(g.Wt0, rw0, std::integral_constant<int, 0>());
+    // 2b's L21 chunks: [128][CLD] beside the A chunk of the OTHER parity ((q & 1) ^ 1: the solves on either side of 2b end and
+    // begin with the buffers 0 and 1, so neither phase change needs a barrier of its own)
+    const double* L21 = Cb + (int64_t)(k0 + GT + lr) * g.lda + k0 + 2 * lc;
+    auto l21 = [&](int q, double2& l0, double2& l1) {
+        const bool real = 2 * lc + q * 32 >= cfp;
+        l0 = real ? *(const double2*)(L21 + q * 32) : make_double2(0.0, 0.0);
+        l1 = real ? *(const double2*)(L21 + q * 32 + 2) : make_double2(0.0, 0.0);
+    };
+    double2 n0 = make_double2(0.0, 0.0), n1 = n0;
+    auto stage_l21 = [&](int q, double2 r0, double2 r1) { stage4(Bs + ((q & 1) ^ 1) * (GT * CLD) + lr * CLD + 2 * lc, r0, r1); };
+    solve(g.Wt0, rw, std::integral_constant<int, 0>(), [&](int c) {
+        if (c == 1) {
+            l21(0, n0, n1);  // (in flight during a chunk of the solve)
+        } else {
+            stage_l21(0, n0, n1);  // (its buffer was last read by chunk 1 of the solve)
+            l21(1, n0, n1);
+        }
+    });
     SF_W_STAMP(3);
-    double2 rw1 = *(const double2*)(w_rows(g.Wt1) + 7 * 16);  // (in flight during step 2b)
 
     // 2b: T2 -= L1 L21^T, 32 columns of L1 at a time (chunk q = the blocks of the waves wn == q)
+    // (chunk q + 1 is dumped and staged ahead of chunk q's MFMAs, like the solves' chunks)
     {
-        const double* L21 = Cb + (int64_t)(k0 + GT + lr) * g.lda + k0 + (tid & 7) * 4;
-        auto l21 = [&](int q, double2& l0, double2& l1) {
-            const bool real = (tid & 7) * 4 + q * 32 >= cfp;
-            l0 = real ? *(const double2*)(L21 + q * 32) : make_double2(0.0, 0.0);
-            l1 = real ? *(const double2*)(L21 + q * 32 + 2) : make_double2(0.0, 0.0);
-        };
-        double2 l0, l1, n0 = make_double2(0.0, 0.0), n1 = n0;
-        l21(0, l0, l1);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (q + 1 < 4) l21(q + 1, n0, n1);  // (the next chunk is in flight under this chunk's MFMAs)
-            double* Ach = Ach0 + (q & 1) * (GT * CLD);
-            double* Bc = Bs + (q & 1) * (GT * CLD);  // [128][CLD]
-            if (q == 0) __syncthreads();  // the first solve's last reads of the buffers are done
+        auto dump = [&](int q) {  // the owner waves of chunk q hand their L1 blocks over
+            double* Ach = Ach0 + ((q & 1) ^ 1) * (GT * CLD);
             if (wn == q) {
 #pragma unroll
                 for (int nn = 0; nn < 2; ++nn)
@@ -334,17 +361,22 @@ __device__ __forceinline__ void sf_panelw_body(const sf_panelw_args& g, const in
                         for (int r = 0; r < 4; ++r)
                             Ach[(wm * 32 + mi * 16 + lq + 4 * r) * CLD + nn * 16 + l15] = acc[mi][nn][r];
             }
-            {
-                double* pb = Bc + lr * CLD + (tid & 7) * 4;
-                pb[0] = l0.x;
-                pb[1] = l0.y;
-                pb[2] = l1.x;
-                pb[3] = l1.y;
-            }
+        };
+        dump(0);  // (its L21 chunk went in ahead of the solve's last chunk)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
             __syncthreads();
+            if (q + 1 < 4) {
+                dump(q + 1);
+                stage_l21(q + 1, n0, n1);
+                if (q + 2 < 4) l21(q + 2, n0, n1);  // (in flight under this chunk's MFMAs)
+            }
+            // (the second solve's first chunks of W, a chunk of MFMAs or more ahead of their use, once registers are free)
+            if (q == 2) w_chunk(w_rows(g.Wt1), 3, rw[0], rw[1]);
+            if (q == 3) w_chunk(w_rows(g.Wt1), 2, rw[2], rw[3]);
             if (wave_live) {
-                const double* Ab = Ach + (wm * 32 + l15) * CLD + lq;
-                const double* Bb = Bc + (wn * 32 + l15) * CLD + lq;
+                const double* Ab = Ach0 + ((q & 1) ^ 1) * (GT * CLD) + (wm * 32 + l15) * CLD + lq;
+                const double* Bb = Bs + ((q & 1) ^ 1) * (GT * CLD) + (wn * 32 + l15) * CLD + lq;
 #pragma unroll
                 for (int ks = 0; ks < 8; ++ks) {
                     double a[TM], bb[2];
@@ -359,12 +391,10 @@ __device__ __forceinline__ void sf_panelw_body(const sf_panelw_args& g, const in
                             acc[mi][2 + nn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], bb[nn], acc[mi][2 + nn], 0, 0, 1);  // neg
                 }
             }
-            l0 = n0;
-            l1 = n1;
         }
     }
     SF_W_STAMP(4);
-    solve(g.Wt1, rw1, std::integral_constant<int, 2>());
+    solve(g.Wt1, rw, std::integral_constant<int, 2>(), [](int) {});
     SF_W_STAMP(5);
     // ---- the slab's diagonal tile (step 4) is requested before the stores of step 3
     constexpr int TLD = 130;
@@ -407,19 +437,19 @@ __device__ __forceinline__ void sf_panelw_body(const sf_panelw_args& g, const in
     }
 
     // ---------------------------------------------------------------- 3: L in place, rhs -= L z
+    // (the stores of L themselves are issued under the MFMAs of step 4, two per group of eight, each panel's under its own
+    // half: the CU's store path takes ~9 us for the 256 KB of a task, and in front of step 4 every wave waited at its first
+    // barrier for the last store to be ISSUED -- 5-6 us in the phase stamps; store + step 4 per task 30 -> 23 us,
+    // profiles/r07_a_wide_fixed_part_ab.txt.  The MFMA part of a half is at its MFMA time, 8.1 us, with the blocks as they
+    // are: no new split of the 36 blocks was built.  Spreading panel k's stores over step 2b, or moving the sums of L z
+    // behind the first half's MFMAs, costs registers the compiler takes from scratch: not built.)
+    double* Lout = Cb + (int64_t)row0 * g.lda + k0;
+    auto store_L = [&](int half, int s) {  // store s = 0 .. 15 of the wave's two blocks of panel k + half
+        const int mi = s >> 3, ni = 2 * half + ((s >> 2) & 1), r = s & 3;
+        const int row = wm * 32 + mi * 16 + lq + 4 * r, col = WBC(ni) + l15;
+        if (row < rows_here && col >= cfp) Lout[(int64_t)row * g.lda + col] = acc[mi][ni][r];
+    };
     {
-        double* Lout = Cb + (int64_t)row0 * g.lda + k0;
-#pragma unroll
-        for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < TN; ++ni) {
-                const int col = WBC(ni) + l15;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = wm * 32 + mi * 16 + lq + 4 * r;
-                    if (row < rows_here && col >= cfp) Lout[(int64_t)row * g.lda + col] = acc[mi][ni][r];
-                }
-            }
         if (RHS && g.rhs) {
 #pragma unroll
             for (int mi = 0; mi < TM; ++mi)
@@ -457,15 +487,34 @@ __device__ __forceinline__ void sf_panelw_body(const sf_panelw_args& g, const in
                     for (int r = 0; r < 4; ++r)
                         Ts[(wm * 32 + mi * 16 + lq + 4 * r) * TLD + wn * 32 + nn * 16 + l15] = acc[mi][2 * half + nn][r];
             __syncthreads();
+#ifdef SF_TUNING
+            if (g.stamps) {  // stamps 9 + 3 half ..: dump done | diagonal-tile loads landed | MFMA part done
+                SF_W_STAMP(9 + 3 * half);
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(acc2[j][r]));
+                SF_W_STAMP(10 + 3 * half);
+            }
+#endif
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 if (j >= nsb) continue;
                 const double* Pa = Ts + (sbi[j] * 16 + l15) * TLD + lq;
                 const double* Pb = Ts + (sbj[j] * 16 + l15) * TLD + lq;
-#pragma unroll 8
-                for (int ks = 0; ks < GT / 4; ++ks)
-                    acc2[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(Pa[ks * 4], Pb[ks * 4], acc2[j], 0, 0, 1);  // neg:[1,0,0]
+#pragma unroll
+                for (int u = 0; u < GT / 32; ++u) {
+#pragma unroll
+                    for (int ks = 8 * u; ks < 8 * u + 8; ++ks)
+                        acc2[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(Pa[ks * 4], Pb[ks * 4], acc2[j], 0, 0, 1);  // neg:[1,0,0]
+                    if (4 * j + u < 8) {  // (every wave has two blocks at least: eight groups per half, sixteen stores)
+                        store_L(half, 2 * (4 * j + u));
+                        store_L(half, 2 * (4 * j + u) + 1);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
+            SF_W_STAMP(11 + 3 * half);
         }
         SF_W_STAMP(7);
         const bool parked = g.Sout && sl == 0;  // (only the first slab of a launch is the next diagonal tile)
