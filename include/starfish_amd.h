@@ -388,6 +388,31 @@ int sf_loglike_grad_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const 
 int sf_debug_loglike_grad_contract(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, double* d_grad,
                                    int grad_stride, void* d_work, size_t work_bytes, void* stream);
 
+/* The Fisher information of the covariance hyper-parameters,
+ *     F_ij = 1/2 tr(C^-1 dC/dtheta_i C^-1 dC/dtheta_j),
+ * in the slots of sf_loglike_grad_batch (s = 2 with a global kernel + 3 per local kernel, same order): its inverse is the
+ * Laplace covariance of the fitted noise model.  The head is sf_loglike_grad_batch's (factor and inverse factor on the
+ * walker's own residual: d_lnl and d_info, both may be NULL, have sf_loglike_batch's bits).  Then every 64 x 64 tile of
+ * W = C^-1 is formed once per walker, and per slot j the product T_j = W dC_j (the derivative tiles generated from the entry
+ * formulas on the kernel's support), the tiles of S_j = T_j W on the kernels' support, both on the fp64 matrix cores, and the
+ * block-row contraction F_ij = 1/2 sum (dC_i)_ab (S_j)_ab for i >= j.  d_fisher[b*fisher_stride + i*s + j], fisher_stride >=
+ * s*s; the upper triangle is the mirror image: F_ij and F_ji are the same bits.  The matrix is the one that is factorised
+ * (jitter included); the derivative in mu is the almost-everywhere one.  A walker with d_info[b] != 0 gets a NaN matrix.
+ * Every sum has a fixed order that does not depend on the batch: a repeated call and a call on a sub-batch give the same
+ * bits.  Dense factor only (the band of Bd^-1 does not hold C^-1 dC_i C^-1 off the band).  SF_EINVAL, the message starting
+ * with the call's name, before anything is enqueued and before the context is looked at: B outside 1 .. 65535, null
+ * d_params or d_fisher, a model without global and local kernels ("nothing to differentiate"), fisher_stride < s*s; then a
+ * bad context or model.  d_work: sf_fisher_cov_workspace_bytes(ctx, model, B) (0 for what the call refuses): the workspace
+ * of sf_loglike_grad_batch plus, per walker, two matrices of ld x ld doubles, ld = 64 ceil(n / 64) (all of W; one T_j): the
+ * slots are worked through one at a time, so the size does not grow with s.  Never synchronises. */
+size_t sf_fisher_cov_workspace_bytes(const sf_ctx* ctx, const sf_model_desc* model, int B);
+int sf_fisher_cov_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, double* d_lnl, double* d_fisher,
+                        int fisher_stride, int* d_info, void* d_work, size_t work_bytes, void* stream);
+/* Timing aid (tools/bench_cov_fisher.py): the launches of sf_fisher_cov_batch behind the inverse alone, on the workspace that
+ * a call of sf_fisher_cov_batch with the same ctx, model, B and d_params left behind. */
+int sf_debug_fisher_cov_contract(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, double* d_fisher,
+                                 int fisher_stride, void* d_work, size_t work_bytes, void* stream);
+
 /* The likelihood and its gradient in the mean-flux parameters: vsini (column 0 of the parameter row), vz (1), log_scale (2), the
  * emulator grid parameters, the Chebyshev coefficients and Av.  They enter through the flux f, the scaled emulator rows X and
  * the emulator's weight covariance Sigma_w, not through the structured kernels.  With alpha = C^-1 r, V = C^-1 X^T, a = X alpha,
@@ -425,8 +450,8 @@ int sf_debug_loglike_mean_grad_contract(sf_ctx* ctx, const sf_model_desc* model,
  * for the columns h_slots of sf_loglike_mean_grad_batch (same columns, same slot checks): the inverse of F is the Laplace
  * covariance of vsini, vz, log_scale, Av, cheb:k and the grid parameters; the mean / covariance cross block of a Gaussian's
  * Fisher matrix is zero.  This is the Gauss-Newton, fixed-covariance matrix: the term 1/2 tr(C^-1 dC_i C^-1 dC_j) that a grid
- * parameter has because X sits inside the emulator's covariance is left out, and so is the block of the covariance
- * hyper-parameters.  One pixel pass writes the tangent columns J (the row tangents of the gradient's pixel pass; a grid column
+ * parameter has because X sits inside the emulator's covariance is left out; the block of the covariance
+ * hyper-parameters is sf_fisher_cov_batch's.  One pixel pass writes the tangent columns J (the row tangents of the gradient's pixel pass; a grid column
  * is dmu^T X; zero for a walker the transform chain flagged) as the right-hand sides of the likelihood's sequence,
  * SF_APPLY_LINV turns them into Z = L^-1 J, and F = Z^T Z is summed per 256-pixel block and then over the blocks in ascending
  * order, without atomics.  d_fisher[b*fisher_stride + i*nslots + j], fisher_stride >= nslots^2; the lower triangle is computed

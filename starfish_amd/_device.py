@@ -6,6 +6,9 @@ by the HIP kernels behind the C-ABI (``_lib``).  Nothing here computes on the CP
 import ctypes as C
 
 import numpy as np
+# (at import, not inside factor_v11: there the import's cost -- a quarter of a second warm, more from a cold disk -- was part of
+# a model's first likelihood call, which it outweighed several times)
+from scipy.linalg import cho_solve, cholesky, solve_triangular
 
 from . import _lib
 from . import _rows as R
@@ -274,8 +277,6 @@ def factor_v11(v11, w_hat):
     """Init-time constants of the emulator conditional (the reference solves with the constant v11 on every call,
     emulator.py:387-388): Linv = inverse of the lower Cholesky factor of v11 and alpha = v11^-1 w_hat, by LAPACK on
     the host, once per hyper-parameter set -- every order context of the emulator receives the same arrays."""
-    from scipy.linalg import cho_solve, cholesky, solve_triangular
-
     try:
         L = cholesky(np.asarray(v11, dtype=np.float64), lower=True)
     except np.linalg.LinAlgError as e:  # the library's documented status for this case (SF_INFO_EMULATOR_NOT_PD)
@@ -1515,8 +1516,8 @@ class DeviceOrder:
     def fisher_mean(self, md, params, slots, solver="dense", max_chunk=None):
         """The likelihood and the Fisher information of the mean-flux parameters at fixed covariance, ``F_ij = fdot_i^T C^-1
         fdot_j`` with ``fdot_j = d f / d theta_j`` (sf_fisher_mean_batch).  This is the Gauss-Newton matrix: the term
-        ``1/2 tr(C^-1 dC_i C^-1 dC_j)`` of a grid parameter (X sits inside the emulator's covariance) is left out.  params, slots:
-        as for :meth:`loglike_mean_grad`.  Returns dict of numpy arrays: lnl (B,), fisher (B, p, p) in the order of ``slots``,
+        ``1/2 tr(C^-1 dC_i C^-1 dC_j)`` of a grid parameter (X sits inside the emulator's covariance) is left out (the
+        covariance hyper-parameters' block: :meth:`fisher_cov`).  params, slots: as for :meth:`loglike_mean_grad`.  Returns dict of numpy arrays: lnl (B,), fisher (B, p, p) in the order of ``slots``,
         bit-symmetric, NaN where info != 0, and info (B,).  Chunked and retried like :meth:`loglike_mean_grad`.
 
         solver: "dense"  -- the dense factor, ``F = Z^T Z`` with ``Z = L^-1 J`` (lnl and info with :meth:`loglike`'s bits);
@@ -1549,6 +1550,22 @@ class DeviceOrder:
             for key, v in got.items():
                 out[key][idx] = v
         return finish_structured(out, fits, solver, lambda rest: self.fisher_mean(md, rows[rest], slots, "dense", max_chunk))
+
+    # ------------------------------------------------------------------ Fisher information in the covariance hyper-parameters
+    def fisher_cov_workspace_bytes(self, md, B):
+        return self._size_query("fisher_cov_", md, B)
+
+    def fisher_cov(self, md, params, max_chunk=None):
+        """The likelihood and the Fisher information of the covariance hyper-parameters, ``F_ij = 1/2 tr(C^-1 dC_i C^-1
+        dC_j)`` (sf_fisher_cov_batch), in the slots of :meth:`loglike_grad`: log_amp, log_ls of the global kernel if the model has
+        one, then mu, log_amp, log_sigma per local kernel.  params: (B, stride) rows as for :meth:`loglike`.  Returns dict of
+        numpy arrays: lnl (B,) and info (B,) with :meth:`loglike`'s bits, fisher (B, s, s), bit-symmetric, NaN where info != 0.
+        The dense factor only.  Chunked and retried like :meth:`loglike_grad`; a chunked call gives the same bits."""
+        s = R.cov_grad_slots(md)
+        if not s:
+            raise ValueError("nothing to differentiate: the model has no global and no local kernel")
+        return self._run_fisher("fisher_cov_batch", md, params, (), s, None, lambda units: self.fisher_cov_workspace_bytes(md, units),
+                                max_chunk)
 
     def loglike_device(self, md, P_dev, out_lnl, info=None):
         """Enqueue-only variant for bench.py: device tensors in/out, no synchronisation."""

@@ -1,6 +1,7 @@
 // C-ABI host layer: the calls that run the likelihood's sequence and then work on the Cholesky factor (sf_apply_batch,
-// sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch, sf_loglike_mean_grad_batch, sf_fisher_mean_batch and the three
-// timing aids).  One description per call, one argument check, one workspace layout (carve_applied) and one way to open a call.
+// sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch, sf_fisher_cov_batch, sf_loglike_mean_grad_batch,
+// sf_fisher_mean_batch and the four timing aids).  One description per call, one argument check, one workspace layout
+// (carve_applied) and one way to open a call.
 #include "sf_stages.h"
 
 struct AppliedCall {
@@ -22,6 +23,9 @@ static const AppliedCall MEAN_GRAD = {"sf_loglike_mean_grad_batch", "d_params, h
 static const AppliedCall MEAN_GRAD_CONTRACT = {"sf_debug_loglike_mean_grad_contract", "d_params, h_slots and d_grad", AW_MEAN,
                                                false, false};
 static const AppliedCall FISHER = {"sf_fisher_mean_batch", "d_params, h_slots, d_lnl and d_fisher", AW_MEAN | AW_FISHER, false, false};
+static const AppliedCall FISHER_COV = {"sf_fisher_cov_batch", "d_params and d_fisher", AW_INVERSE | AW_PART | AW_FISHER_COV, false, false};
+static const AppliedCall FISHER_COV_CONTRACT = {"sf_debug_fisher_cov_contract", "d_params and d_fisher",
+                                                AW_INVERSE | AW_PART | AW_FISHER_COV, false, false};
 // what a call was handed, as far as the check looks at it
 struct AppliedArgs {
     int B, nrhs;
@@ -50,6 +54,13 @@ static int grad_slots_ok(const AppliedCall& k, const sf_model_desc* mdl, int gra
     if (slots == 0) {
         sf_set_error("%s: nothing to differentiate (no global and no local kernel)", k.name);
         return SF_EINVAL;
+    }
+    if (k.parts & AW_FISHER_COV) {  // (the stride holds a matrix)
+        if (grad_stride < slots * slots) {
+            sf_set_error("%s: fisher_stride=%d < slots^2 = %d", k.name, grad_stride, slots * slots);
+            return SF_EINVAL;
+        }
+        return SF_OK;
     }
     if (grad_stride < slots) {
         sf_set_error("%s: grad_stride=%d < %d slots", k.name, grad_stride, slots);
@@ -288,6 +299,38 @@ extern "C" int sf_debug_loglike_grad_contract(sf_ctx* c, const sf_model_desc* md
     AppliedWork aw;
     SF_CHECK(open_applied(GRAD_CONTRACT, c, mdl, grad_args(B, d_params && d_grad, grad_stride), d_work, work_bytes, &w, &aw));
     return grad_contract(c, mdl, B, d_params, w, aw, d_grad, grad_stride, (hipStream_t)stream);
+}
+
+// ----------------------------------------------------------------------------------- Fisher information in the covariance hyper-parameters
+extern "C" size_t sf_fisher_cov_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B) {
+    return workspace_bytes(FISHER_COV, c, mdl, B, 1);
+}
+// all of W = C^-1 from the X the inverse's launch left in the matrices, then per slot T_j = W dC_j and 1/2 sum dC_i o (T_j W)
+static int fisher_cov_contract(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const Work& w, const AppliedWork& aw,
+                               double* d_fisher, int fisher_stride, hipStream_t s) {
+    sf_fill_args f = fill_args(c, mdl, d_params, w);
+    f.C = w.C, f.lda = w.L.lda, f.stride = (int64_t)w.L.npad * w.L.lda, f.lower_only = 1, f.add_jitter = 1;
+    return sf_launch_fisher_cov(f, B, aw.winv, aw.info, aw.wfull, aw.tj, aw.part, d_fisher, fisher_stride, s);
+}
+extern "C" int sf_fisher_cov_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, double* d_lnl, double* d_fisher,
+                                   int fisher_stride, int* d_info, void* d_work, size_t work_bytes, void* stream) {
+    Work w;
+    AppliedWork aw;
+    SF_CHECK(open_applied(FISHER_COV, c, mdl, grad_args(B, d_params && d_fisher, fisher_stride), d_work, work_bytes, &w, &aw));
+    hipStream_t s = (hipStream_t)stream;
+    SF_CHECK(apply_cinv_and_invert(c, mdl, B, d_params, nullptr, 1, c->n, 0, nullptr, w, aw, s));
+    SF_CHECK(fisher_cov_contract(c, mdl, B, d_params, w, aw, d_fisher, fisher_stride, s));
+    if (d_lnl) SF_HIP(hipMemcpyAsync(d_lnl, aw.lnl, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return export_status(d_info, aw, B, s);
+}
+// The launches of sf_fisher_cov_batch behind the inverse alone, on the workspace a call with the same ctx, model, B and d_params
+// left (tools/bench_cov_fisher.py times them)
+extern "C" int sf_debug_fisher_cov_contract(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, double* d_fisher,
+                                            int fisher_stride, void* d_work, size_t work_bytes, void* stream) {
+    Work w;
+    AppliedWork aw;
+    SF_CHECK(open_applied(FISHER_COV_CONTRACT, c, mdl, grad_args(B, d_params && d_fisher, fisher_stride), d_work, work_bytes, &w, &aw));
+    return fisher_cov_contract(c, mdl, B, d_params, w, aw, d_fisher, fisher_stride, (hipStream_t)stream);
 }
 
 // ----------------------------------------------------------------------------------- gradient in the mean-flux parameters

@@ -161,7 +161,7 @@ int sf_launch_diag_copy(const double* A, int n, int lda, int64_t stride, int bat
 int sf_launch_clock_probe(long long* out, long long wall_ticks, hipStream_t s);
 
 // sf_fill.hip (layers: sf_fill_elem.h, sf_fill_band.h, sf_fill_tile.h, sf_fill_dense.h, sf_fill_free.h, sf_cov_matvec.h, sf_cinv.h,
-// sf_grad_frame.h, sf_cov_grad.h, sf_emu_grad.h)
+// sf_grad_frame.h, sf_cov_grad.h, sf_fisher_cov.h, sf_emu_grad.h)
 struct sf_fill_args {
     const double* wave;    // [n]
     const double* sigma;   // [n]
@@ -217,6 +217,13 @@ static inline __host__ __device__ int sf_cov_grad_slots(int has_global, int n_lo
 size_t sf_cov_grad_work_doubles(int n, int has_global, int n_local, int batch);
 int sf_launch_cov_grad(const sf_fill_args& f, int batch, const double* winv, const double* alpha, int ld_alpha, const int* info,
                        double* part, double* grad, int grad_stride, hipStream_t s);
+// sf_fisher_cov.h: the Fisher information of the covariance hyper-parameters, F_ij = 1/2 tr(C^-1 dC_i C^-1 dC_j), in the slots
+// of sf_launch_cov_grad: f, winv, info as sf_launch_cov_grad gets them; wf, tj: [batch][ld][ld] doubles of scratch each,
+// ld = sf_fisher_cov_ld(n) (all of C^-1 and one T_j = C^-1 dC_j); part: sf_cov_grad_work_doubles of scratch;
+// fisher[b * fisher_stride + i * slots + j], bit-symmetric, NaN where info[b] != 0
+static inline __host__ __device__ int sf_fisher_cov_ld(int n) { return (n + SF_LEAF - 1) / SF_LEAF * SF_LEAF; }
+int sf_launch_fisher_cov(const sf_fill_args& f, int batch, const double* winv, const int* info, double* wf, double* tj, double* part,
+                         double* fisher, int fisher_stride, hipStream_t s);
 // sf_grad_frame.h: the sum over the orders of a multi-order gradient (sf_multi_grad_reduce)
 struct sf_multi_reduce_args {
     const double* unit_lnl;   // [nseg * W]

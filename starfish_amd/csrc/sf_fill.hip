@@ -20,6 +20,7 @@
 //   sf_cinv.h         sf_cinv_tile, k_cinv_blocks: 64 x 64 blocks of C^-1 from the inverse factor
 //   sf_grad_frame.h   sf_grad_tile, sf_grad_flush, k_grad_sum, sf_launch_grad: what the two likelihood gradients share; k_multi_grad_reduce
 //   sf_cov_grad.h     k_cov_grad: the likelihood's gradient in the covariance hyper-parameters
+//   sf_fisher_cov.h   k_fc_winv, k_fc_left, k_fc_contract, k_fc_sum: the Fisher information of those hyper-parameters
 //   sf_band_cov_grad.h  k_band_cov_grad: the same gradient contracted over the band of Bd^-1 and the low-rank correction
 //   sf_emu_grad.h     k_emu_grad: the emulator training likelihood's gradient in its hyper-parameters
 #include "sf_common.h"
@@ -33,5 +34,6 @@
 #include "sf_cinv.h"
 #include "sf_grad_frame.h"
 #include "sf_cov_grad.h"
+#include "sf_fisher_cov.h"
 #include "sf_band_cov_grad.h"
 #include "sf_emu_grad.h"

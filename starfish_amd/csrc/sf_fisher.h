@@ -1,5 +1,6 @@
 // The Fisher information of the mean-flux parameters at fixed covariance, F_ij = fdot_i^T C^-1 fdot_j, fdot_j = d f / d theta_j
-// (the Gauss-Newton block: the term 1/2 tr(C^-1 dC_i C^-1 dC_j) that arises because X sits inside C_emu is left out).
+// (the Gauss-Newton block: the term 1/2 tr(C^-1 dC_i C^-1 dC_j) that arises because X sits inside C_emu is left out; the block
+// of the covariance hyper-parameters, where that term is all there is, is sf_fisher_cov.h's).
 // A layer of sf_transform.hip ("Fisher information in the mean-flux parameters"):
 //   columns    k_fisher_tangent: one thread per pixel writes fdot_j(i) of every requested slot into rows of npad doubles, zero
 //              on the padding and for a walker the transform chain flagged.  The formulas are k_mean_pixel's with omega = 0 and

@@ -155,8 +155,8 @@ static BandWork carve_band(const sf_ctx* c, int B, int halfwidth, void* p, size_
 }
 
 // ------------------------------------------------------------------- the factor applied to right-hand sides
-// (sf_apply_batch, sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch, sf_loglike_mean_grad_batch; behind the Work of the same call:
-// base_bytes = its size)  Every call has the staging area -- the right-hand sides padded to npad rows, the factor is applied
+// (sf_apply_batch, sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch, sf_fisher_cov_batch,
+// sf_loglike_mean_grad_batch; behind the Work of the same call: base_bytes = its size)  Every call has the staging area -- the right-hand sides padded to npad rows, the factor is applied
 // to it in place (for all but sf_apply_batch it ends up holding alpha = C^-1 rhs) -- and lnl / info, what the likelihood's
 // last step leaves.  Then, in this order, the parts the call asks for:
 //   AW_YV        yv: t = Y alpha, m doubles per right-hand side (sf_decompose_batch)
@@ -169,11 +169,14 @@ static BandWork carve_band(const sf_ctx* c, int B, int halfwidth, void* p, size_
 //                coefficients of the d / d vsini rows (models with vsini); kdot, mudot, zdot: d v12, d mu and Linv d v12 for
 //                min(nslots, P) grid columns
 //   AW_FISHER    (sf_fisher_mean_batch, with AW_MEAN) fpart: the partial sums of Z^T Z per (walker, 256-pixel block, pair of slots)
-enum AppliedParts { AW_YV = 1, AW_COV_DIAG = 2, AW_INVERSE = 4, AW_PART = 8, AW_MEAN = 16, AW_FISHER = 32 };
+//   AW_FISHER_COV  (sf_fisher_cov_batch, with AW_INVERSE and AW_PART) wfull: every tile of W = C^-1, both triangles, and tj: one
+//                T_j = W dC_j, ld x ld doubles per walker each with ld = sf_fisher_cov_ld(n) <= npad -- the same for every number
+//                of slots: the slots are worked through one at a time, and part holds the sums of the slot at hand
+enum AppliedParts { AW_YV = 1, AW_COV_DIAG = 2, AW_INVERSE = 4, AW_PART = 8, AW_MEAN = 16, AW_FISHER = 32, AW_FISHER_COV = 64 };
 struct AppliedWork {
     double *stage, *lnl;
     int* info;
-    double *yv, *cov_diag, *cinv_diag, *winv, *part, *xs, *fin, *mpart, *dcoef, *kdot, *mudot, *zdot, *fpart;
+    double *yv, *cov_diag, *cinv_diag, *winv, *part, *xs, *fin, *mpart, *dcoef, *kdot, *mudot, *zdot, *fpart, *wfull, *tj;
     double* coef;  // (carve_multi_grad only) the segment's own spline coefficients, which a single-order call keeps in its Work
     size_t bytes;
 };
@@ -202,6 +205,11 @@ static AppliedWork carve_applied(const sf_ctx* c, const sf_model_desc* mdl, int 
         w.zdot = k.take<double>(ng * B * mM * c->m);
     }
     if (parts & AW_FISHER) w.fpart = k.take<double>(sf_fisher_part_doubles(c->n, nslots, B));
+    if (parts & AW_FISHER_COV) {
+        const size_t ld = (size_t)sf_fisher_cov_ld(c->n);
+        w.wfull = k.take<double>((size_t)B * ld * ld);
+        w.tj = k.take<double>((size_t)B * ld * ld);
+    }
     w.bytes = sf_align_up(k.off, 256);
     return w;
 }

@@ -160,8 +160,9 @@ class Gradients:
         """The Fisher information of the mean-flux parameters at the current state and at fixed covariance, ``F_ij = fdot_i^T
         C^-1 fdot_j`` with ``fdot_j = d flux / d label_j``: a ``(p, p)`` array in :attr:`mean_gradient_labels` order, symmetric
         bit for bit.  This is the Gauss-Newton, fixed-covariance matrix: the term ``1/2 tr(C^-1 dC_i C^-1 dC_j)`` that a grid
-        parameter has because the emulator's rows sit inside the covariance is left out, and so is the block of the covariance
-        hyper-parameters (the mean / covariance cross block of a Gaussian's Fisher matrix is zero).  Raises as
+        parameter has because the emulator's rows sit inside the covariance is left out; the block of the covariance
+        hyper-parameters is :meth:`covariance_fisher_information` (the mean / covariance cross block of a Gaussian's Fisher matrix
+        is zero).  Raises as
         :meth:`log_likelihood` does and refuses what :meth:`log_likelihood_mean_gradient` refuses; the model's state is not
         modified.  ``solver``: ``None`` / "dense" the dense factor, "banded" / "auto" one sweep of the band + Woodbury solver
         (:meth:`DeviceOrder.fisher_mean`)."""
@@ -179,7 +180,43 @@ class Gradients:
         out = self._fisher_call(dev, md, rows, solver)
         return (out["fisher"], out["info"]) if return_info else out["fisher"]
 
-    def parameter_covariance(self, priors=None, solver=None):
+    # ------------------------------------------------------------------ Fisher information in the covariance hyper-parameters
+    def _cov_fisher(self, out, md):
+        """The rows and columns of :attr:`gradient_labels` of the device's matrices (the last two axes of ``out["fisher"]``)."""
+        slots = self._gradient_slots(md)
+        return out["fisher"][..., slots, :][..., :, slots]
+
+    def covariance_fisher_information(self):
+        """The Fisher information of the covariance hyper-parameters at the current state, ``F_ij = 1/2 tr(C^-1 dC_i C^-1
+        dC_j)`` with ``dC_i = d C / d label_i``: a ``(q, q)`` array in :attr:`gradient_labels` order, symmetric bit for bit
+        (sf_fisher_cov_batch).  The device differentiates in every slot; frozen labels drop their rows and columns.  In ``mu`` of
+        a local kernel the derivative is the almost-everywhere one, as for :meth:`log_likelihood_gradient`.  Always the dense
+        factor, whatever the model's ``solver`` is: the band of the inverse does not hold ``C^-1 dC_i C^-1``.  Raises
+        ``ValueError`` if no covariance label is thawed, and as :meth:`log_likelihood` does; the model's state is not modified."""
+        if not self.gradient_labels:
+            raise ValueError("no thawed global_cov / local_cov parameter to take the Fisher information in")
+        dev, md, rows = self._pack(update_caches=False)
+        return self._cov_fisher(self._own(dev.fisher_cov(md, rows)), md)
+
+    def covariance_fisher_information_batch(self, P, return_info=False):
+        """:meth:`covariance_fisher_information` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device
+        pass: ``(B, q, q)``, a NaN matrix for a walker that fails; with ``return_info`` ``(fisher, info)``.  The model's own state
+        is not modified."""
+        if not self.gradient_labels:
+            raise ValueError("no thawed global_cov / local_cov parameter to take the Fisher information in")
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        dev, md, rows = self._pack(P, update_caches=False)
+        out = dev.fisher_cov(md, rows)
+        fisher = self._cov_fisher(out, md)
+        return (fisher, out["info"]) if return_info else fisher
+
+    @property
+    def fisher_labels(self):
+        """tuple of str : the thawed labels in :attr:`labels` order without ``Rv``: the labels of
+        ``parameter_covariance(include_covariance=True)``."""
+        return tuple(key for key in self.labels if key != "Rv")
+
+    def parameter_covariance(self, priors=None, solver=None, include_covariance=False):
         """The Laplace covariance of the labels of :attr:`mean_gradient_labels` at the current state (the point :meth:`train`
         found): the inverse of :meth:`fisher_information` plus, for every prior on one of these labels,
         ``-d^2 logpdf / d label^2`` by a central second difference with the step of the trainers' prior slopes,
@@ -187,11 +224,31 @@ class Gradients:
         the matrix leaves out.  The inverse is formed in normalised form, ``D^-1 (D^-1 F D^-1)^-1 D^-1`` with ``D =
         sqrt(diag(F))``, by Cholesky; a matrix that is not positive definite (parameters the data do not separate) raises
         ``np.linalg.LinAlgError`` naming the labels (:func:`starfish_amd._map.laplace_covariance`).  ``priors`` are checked as
-        :meth:`train` checks them."""
+        :meth:`train` checks them.
+
+        ``include_covariance=True``: the Laplace covariance of :attr:`fisher_labels`, the thawed covariance hyper-parameters
+        included.  The assembled Fisher matrix has :meth:`fisher_information` (``solver``) in the mean-flux labels,
+        :meth:`covariance_fisher_information` in the covariance labels and a zero cross block, and goes once through the same
+        inversion, with priors on either kind of label; either block may be empty.  This is an approximation: the grid
+        parameters and ``log_scale`` also sit inside ``C`` through the emulator term, and their ``1/2 tr(C^-1 dC_i C^-1 dC_j)``
+        terms, with each other and with the hyper-parameters, are left out of both blocks and of the cross block."""
         priors = self._checked_priors(priors)
-        labels = self.mean_gradient_labels
+        if not include_covariance:
+            labels = self.mean_gradient_labels
+            terms = [(i, priors[key], float(self[key])) for i, key in enumerate(labels) if key in priors]
+            return _map.laplace_covariance(self.fisher_information(solver=solver), labels, terms)
+        labels = self.fisher_labels
+        if not labels:
+            raise ValueError("no thawed parameter to take the covariance of")
+        F = np.zeros((len(labels), len(labels)))
+        mean = [labels.index(key) for key in self.mean_gradient_labels]
+        cov = [labels.index(key) for key in self.gradient_labels]
+        if mean:
+            F[np.ix_(mean, mean)] = self.fisher_information(solver=solver)
+        if cov:
+            F[np.ix_(cov, cov)] = self.covariance_fisher_information()
         terms = [(i, priors[key], float(self[key])) for i, key in enumerate(labels) if key in priors]
-        return _map.laplace_covariance(self.fisher_information(solver=solver), labels, terms)
+        return _map.laplace_covariance(F, labels, terms)
 
     def _scatter_combined(self, grad, md, out, columns):
         """A combined device result -- the mean ``columns`` in request order (none: ``[]``), then, where covariance labels are

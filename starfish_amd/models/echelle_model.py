@@ -487,7 +487,8 @@ class EchelleModel:
         (:meth:`SpectrumModel.fisher_information`), embedded by the labels: a shared label adds up all orders, the entry between
         labels of two different orders is exactly 0.  This is the Gauss-Newton, fixed-covariance matrix: the term ``1/2 tr(C^-1
         dC_i C^-1 dC_j)`` that a grid parameter has because the emulator's rows sit inside the covariance is left out, and so is
-        the block of the covariance hyper-parameters (the mean / covariance cross block of a Gaussian's Fisher matrix is zero).
+        the block of the covariance hyper-parameters (the mean / covariance cross block of a Gaussian's Fisher matrix is zero):
+        a single order has it from :meth:`SpectrumModel.covariance_fisher_information`, a one-pass multi-order call does not exist.
         A walker that fails in any order gets a NaN matrix; with ``return_info`` ``(fisher, info)``, ``info`` the first non-zero
         per-order code; with ``return_orders`` also the list of the per-order unit matrices ``(B, p_i, p_i)``.  The model's
         state is not modified.
