@@ -413,6 +413,34 @@ int sf_fisher_cov_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const do
 int sf_debug_fisher_cov_contract(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, double* d_fisher,
                                  int fisher_stride, void* d_work, size_t work_bytes, void* stream);
 
+/* The score (Lagrange-multiplier) scan for a NEW local kernel: where does one belong, and how wide?  For every candidate (mu,
+ * sigma in km/s) and every walker, with k(mu, sigma) the matrix the fill would add for a local kernel of that centre and width
+ * at amplitude 1 (the reference's local_covariance_matrix, cut off at 4 sigma), alpha = C^-1 r and W = C^-1 of the walker's
+ * covariance as it stands (every kernel the model has included),
+ *     quad = alpha^T k alpha,    trace = tr(W k),    fisher = 1/2 tr(W k W k),
+ * d_out[(b*ncand + q)*3 + 0 .. 2].  The derivative of lnL in the new kernel's amplitude A at A = 0 is U = 1/2 (quad - trace), its
+ * information is fisher: z = U / sqrt(fisher) is the score statistic and U / fisher one Newton step in A.  d_cand[q*2 + 0 .. 1] =
+ * mu, sigma is shared by the batch.  The head is sf_pointwise_batch's (factor and inverse factor on the walker's own residual:
+ * d_lnl and d_info, both may be NULL, have sf_loglike_batch's bits).  k lives on the pixels within 4 sigma (1 + 1e-9) of mu, a
+ * contiguous patch of the grid, so only the 64 x 64 tiles of W within 4 blocks of the diagonal are formed (once per walker, with
+ * their mirror images); per (walker, candidate) one workgroup generates the tiles of k from the fill's element formulas and
+ * forms the products W k on the fp64 matrix cores.  A candidate's numbers do not depend on the other candidates, the batch or
+ * the chunk (same bits).  A candidate with no pixel in reach gets exactly 0, 0, 0; one whose patch is wider than
+ * SF_LOCAL_SCAN_MAX_PATCH pixels, or whose mu or sigma is not positive and finite, gets NaN in all three for every walker; a
+ * walker with d_info[b] != 0 gets NaN rows.  The model may have no global and no local kernel at all.  Dense factor only.
+ * SF_EINVAL, the message starting with the call's name, before anything is enqueued: B or ncand outside 1 .. 65535, null
+ * d_params, d_cand or d_out; then a bad context or model; then a wavelength grid that is not monotonic.  d_work:
+ * sf_local_scan_workspace_bytes(ctx, model, B, ncand) (0 for what the call refuses): the workspace of sf_pointwise_batch's
+ * inverse, two ints per candidate and, per walker, ceil(n / 64) * 9 tiles of 64 x 64 doubles -- linear in n.  Never synchronises. */
+#define SF_LOCAL_SCAN_MAX_PATCH 256
+size_t sf_local_scan_workspace_bytes(const sf_ctx* ctx, const sf_model_desc* model, int B, int ncand);
+int sf_local_scan_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, const double* d_cand, int ncand,
+                        double* d_out, double* d_lnl, int* d_info, void* d_work, size_t work_bytes, void* stream);
+/* Timing aid (tools/bench_local_scan.py): the launches of sf_local_scan_batch behind the inverse alone, on the workspace that
+ * a call of sf_local_scan_batch with the same ctx, model, B, d_params and ncand left behind. */
+int sf_debug_local_scan_contract(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, const double* d_cand,
+                                 int ncand, double* d_out, void* d_work, size_t work_bytes, void* stream);
+
 /* The likelihood and its gradient in the mean-flux parameters: vsini (column 0 of the parameter row), vz (1), log_scale (2), the
  * emulator grid parameters, the Chebyshev coefficients and Av.  They enter through the flux f, the scaled emulator rows X and
  * the emulator's weight covariance Sigma_w, not through the structured kernels.  With alpha = C^-1 r, V = C^-1 X^T, a = X alpha,

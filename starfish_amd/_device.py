@@ -24,6 +24,8 @@ INFO_MESSAGES = {
 }
 APPLY_OPS = {"L": 0, "Linv": 1, "LinvT": 2, "Cinv": 3}  # SF_APPLY_* of include/starfish_amd.h
 MEAN_GRAD_MAX_SLOTS = 16  # SF_MEAN_GRAD_MAX_SLOTS of include/starfish_amd.h
+MAX_LOCAL = 32  # SF_MAX_LOCAL of csrc/sf_common.h: local kernels per model
+LOCAL_SCAN_MAX_PATCH = 256  # SF_LOCAL_SCAN_MAX_PATCH of include/starfish_amd.h
 INFO_BANDWIDTH = -4
 INFO_INTERNAL = -5
 C_KMS = 2.99792458e5
@@ -180,6 +182,30 @@ def fetch_results(quad, info, resid=None):
     if resid is not None:
         out["resid"] = resid.cpu().numpy()
     return out
+
+
+def local_scan_patches(wave, cand):
+    """The patch of every candidate of :meth:`DeviceOrder.local_scan` as the device finds it: ``cand`` (ncand, 2) = mu, sigma in
+    km/s -> (lo, hi), the first and last pixel with ``c / mu |w - mu| <= 4 sigma (1 + 1e-9)`` on the sorted grid ``wave``;
+    ``hi < lo`` (0, -1) where no pixel is in reach.  Pure host logic (numpy), the device's operations in the device's order."""
+    w = np.asarray(wave, dtype=np.float64)
+    cand = np.asarray(cand, dtype=np.float64).reshape(-1, 2)
+    lo = np.zeros(len(cand), dtype=np.int64)
+    hi = np.full(len(cand), -1, dtype=np.int64)
+    n = w.size
+    # (a sorted grid: the device's test is evaluated on a window around the interval a search gives, two pixels to spare)
+    ordered = n > 1 and bool(np.all(np.diff(w) > 0))
+    for q, (mu, sg) in enumerate(cand):
+        r0 = 4 * sg
+        a, b = 0, n
+        if ordered and np.isfinite(mu) and np.isfinite(sg) and mu > 0:
+            d = abs(r0) * mu / C_KMS
+            a = max(int(np.searchsorted(w, mu - d, "left")) - 2, 0)
+            b = min(int(np.searchsorted(w, mu + d, "right")) + 2, n)
+        idx = np.nonzero(C_KMS / mu * np.abs(w[a:b] - mu) <= r0 * (1 + 1e-9))[0]
+        if idx.size:
+            lo[q], hi[q] = a + idx[0], a + idx[-1]
+    return lo, hi
 
 
 def band_halfwidth_bound(wave, rows, n_grid, has_global, n_local, n_cheb):
@@ -1566,6 +1592,44 @@ class DeviceOrder:
             raise ValueError("nothing to differentiate: the model has no global and no local kernel")
         return self._run_fisher("fisher_cov_batch", md, params, (), s, None, lambda units: self.fisher_cov_workspace_bytes(md, units),
                                 max_chunk)
+
+    # ------------------------------------------------------------------ score scan for a new local kernel
+    def local_scan_workspace_bytes(self, md, B, ncand):
+        return self._size_query("local_scan_", md, B, ncand)
+
+    def local_scan(self, md, params, cand, max_chunk=None):
+        """The score scan for a NEW local kernel at amplitude 0 (sf_local_scan_batch): for every walker and every candidate
+        ``cand[q] = (mu, sigma in km/s)``, shared by the walkers, ``quad = alpha^T k alpha``, ``trace = tr(C^-1 k)`` and ``fisher =
+        1/2 tr(C^-1 k C^-1 k)`` with ``k`` the matrix a local kernel of that centre and width adds at amplitude 1 and ``alpha = C^-1
+        r``: ``1/2 (quad - trace)`` is the derivative of lnL in the new amplitude, ``fisher`` its information.  params: (B,
+        stride) rows as for :meth:`loglike`; the model may have no structured kernel at all.  Returns dict of numpy arrays: quad,
+        trace, fisher (B, ncand) -- zeros for a candidate with no pixel in reach, NaN for one whose patch is wider than
+        LOCAL_SCAN_MAX_PATCH pixels and for walkers with info != 0 --, lnl (B,) and info (B,) with :meth:`loglike`'s bits.  The
+        dense factor only.  Chunked and retried like :meth:`loglike_grad`; a candidate's numbers are the same bits whatever the
+        chunk, the batch and the other candidates are."""
+        torch = _torch()
+        cand = np.ascontiguousarray(np.asarray(cand, dtype=np.float64))
+        if cand.ndim != 2 or cand.shape[1] != 2 or not cand.shape[0]:
+            raise ValueError(f"cand of shape {cand.shape}: expected (ncand, 2) rows of mu, sigma with ncand >= 1")
+        ncand = int(cand.shape[0])
+        with torch.cuda.device(self.dev):
+            P = self._rows(params)
+            Cd = to_dev(cand, self.dev)
+            buffers, download = self._outputs(int(P.shape[0]), {"out": (ncand, 3), "lnl": ()}, False)
+
+            def args(bufs, lo, hi):
+                (out, lnl), info, _ = bufs
+                return (Cd, ncand, out[lo:hi], lnl[lo:hi], info[lo:hi])
+
+            def named(bufs):
+                res = download(bufs)
+                out = res.pop("out")
+                res.update(quad=out[:, :, 0].copy(), trace=out[:, :, 1].copy(), fisher=out[:, :, 2].copy())
+                return res
+
+            # (a size of 0: the call refuses its arguments and says why -- it gets a workspace that is not NULL to say it)
+            size = lambda units: max(self.local_scan_workspace_bytes(md, units, ncand), 256)  # noqa: E731
+            return self._run_chunked("local_scan_batch", md, P, max_chunk, size, buffers, args, named)
 
     def loglike_device(self, md, P_dev, out_lnl, info=None):
         """Enqueue-only variant for bench.py: device tensors in/out, no synchronisation."""

@@ -176,6 +176,15 @@ SIGNATURES = {
         C.c_int,
         [_VP, C.POINTER(ModelDesc), C.c_int, _VP, _VP, C.c_int, _VP, C.c_size_t, _VP],
     ),
+    "sf_local_scan_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int]),
+    "sf_local_scan_batch": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP, _VP, C.c_size_t, _VP],
+    ),
+    "sf_debug_local_scan_contract": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_size_t, _VP],
+    ),
     "sf_loglike_mean_grad_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int]),
     "sf_loglike_mean_grad_batch": (
         C.c_int,

@@ -1,6 +1,6 @@
 // C-ABI host layer: the calls that run the likelihood's sequence and then work on the Cholesky factor (sf_apply_batch,
-// sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch, sf_fisher_cov_batch, sf_loglike_mean_grad_batch,
-// sf_fisher_mean_batch and the four timing aids).  One description per call, one argument check, one workspace layout
+// sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch, sf_fisher_cov_batch, sf_local_scan_batch,
+// sf_loglike_mean_grad_batch, sf_fisher_mean_batch and the five timing aids).  One description per call, one argument check, one workspace layout
 // (carve_applied) and one way to open a call.
 #include "sf_stages.h"
 
@@ -26,6 +26,9 @@ static const AppliedCall FISHER = {"sf_fisher_mean_batch", "d_params, h_slots, d
 static const AppliedCall FISHER_COV = {"sf_fisher_cov_batch", "d_params and d_fisher", AW_INVERSE | AW_PART | AW_FISHER_COV, false, false};
 static const AppliedCall FISHER_COV_CONTRACT = {"sf_debug_fisher_cov_contract", "d_params and d_fisher",
                                                 AW_INVERSE | AW_PART | AW_FISHER_COV, false, false};
+static const AppliedCall LOCAL_SCAN = {"sf_local_scan_batch", "d_params, d_cand and d_out", AW_INVERSE | AW_LOCAL_SCAN, false, false};
+static const AppliedCall LOCAL_SCAN_CONTRACT = {"sf_debug_local_scan_contract", "d_params, d_cand and d_out",
+                                                AW_INVERSE | AW_LOCAL_SCAN, false, false};
 // what a call was handed, as far as the check looks at it
 struct AppliedArgs {
     int B, nrhs;
@@ -331,6 +334,74 @@ extern "C" int sf_debug_fisher_cov_contract(sf_ctx* c, const sf_model_desc* mdl,
     AppliedWork aw;
     SF_CHECK(open_applied(FISHER_COV_CONTRACT, c, mdl, grad_args(B, d_params && d_fisher, fisher_stride), d_work, work_bytes, &w, &aw));
     return fisher_cov_contract(c, mdl, B, d_params, w, aw, d_fisher, fisher_stride, (hipStream_t)stream);
+}
+
+// ----------------------------------------------------------------------------------- score scan for a new local kernel
+// the call's own refusals, before the context is looked at: the counts (with the candidates named) and the required pointers
+static int local_scan_counts_ok(const AppliedCall& k, int B, int ncand, bool required) {
+    if (B <= 0 || B > 65535 || ncand < 1 || ncand > 65535) {
+        sf_set_error("%s: B=%d and ncand=%d must lie in 1 .. 65535", k.name, B, ncand);
+        return SF_EINVAL;
+    }
+    if (!required) {
+        sf_set_error("%s: %s are required", k.name, k.required);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+// behind model_ok: the patch of a candidate is contiguous on a sorted grid only
+static int local_scan_grid_ok(const AppliedCall& k, const sf_ctx* c) {
+    if (!c->monotonic) {
+        sf_set_error("%s: the wavelength grid is not monotonic (a candidate's pixels are no contiguous patch)", k.name);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_local_scan_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int ncand) {
+    if (ncand < 1 || ncand > 65535 || counts_ok(LOCAL_SCAN, B, 1) || model_ok(c, mdl) || !c->monotonic) return 0;
+    return workspace_bytes(LOCAL_SCAN, c, mdl, B, 1, ncand);
+}
+// the band of W = C^-1 from the X the inverse's launch left in the matrices, the candidates' patches, then per (walker,
+// candidate) the three contractions with the alpha in the staging area
+static int local_scan_contract(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const double* d_cand, int ncand,
+                               const Work& w, const AppliedWork& aw, double* d_out, hipStream_t s) {
+    sf_fill_args f = fill_args(c, mdl, d_params, w);
+    f.C = w.C, f.lda = w.L.lda, f.stride = (int64_t)w.L.npad * w.L.lda, f.lower_only = 1, f.add_jitter = 1;
+    return sf_launch_local_scan(f, B, aw.winv, aw.stage, w.L.npad, aw.info, d_cand, ncand, aw.patch, aw.wband, d_out, s);
+}
+static int open_local_scan(const AppliedCall& k, const sf_ctx* c, const sf_model_desc* mdl, int B, int ncand, bool required,
+                           void* d_work, size_t work_bytes, Work* w, AppliedWork* aw) {
+    SF_CHECK(local_scan_counts_ok(k, B, ncand, required));
+    SF_CHECK(model_ok(c, mdl));
+    SF_CHECK(local_scan_grid_ok(k, c));
+    const size_t need = workspace_bytes(LOCAL_SCAN, c, mdl, B, 1, ncand);
+    if (!d_work || work_bytes < need) {  // (said here, so that the message names the call)
+        sf_set_error("%s: workspace too small: have %zu, need %zu", k.name, d_work ? work_bytes : (size_t)0, need);
+        return SF_ENOMEM;
+    }
+    AppliedArgs a = {B, 1, true};
+    a.nslots = ncand;
+    return open_applied(k, c, mdl, a, d_work, work_bytes, w, aw);
+}
+extern "C" int sf_local_scan_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const double* d_cand, int ncand,
+                                   double* d_out, double* d_lnl, int* d_info, void* d_work, size_t work_bytes, void* stream) {
+    Work w;
+    AppliedWork aw;
+    SF_CHECK(open_local_scan(LOCAL_SCAN, c, mdl, B, ncand, d_params && d_cand && d_out, d_work, work_bytes, &w, &aw));
+    hipStream_t s = (hipStream_t)stream;
+    SF_CHECK(apply_cinv_and_invert(c, mdl, B, d_params, nullptr, 1, c->n, 0, nullptr, w, aw, s));
+    SF_CHECK(local_scan_contract(c, mdl, B, d_params, d_cand, ncand, w, aw, d_out, s));
+    if (d_lnl) SF_HIP(hipMemcpyAsync(d_lnl, aw.lnl, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return export_status(d_info, aw, B, s);
+}
+// The launches of sf_local_scan_batch behind the inverse alone, on the workspace a call with the same ctx, model, B, d_params
+// and ncand left (tools/bench_local_scan.py times them)
+extern "C" int sf_debug_local_scan_contract(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const double* d_cand,
+                                            int ncand, double* d_out, void* d_work, size_t work_bytes, void* stream) {
+    Work w;
+    AppliedWork aw;
+    SF_CHECK(open_local_scan(LOCAL_SCAN_CONTRACT, c, mdl, B, ncand, d_params && d_cand && d_out, d_work, work_bytes, &w, &aw));
+    return local_scan_contract(c, mdl, B, d_params, d_cand, ncand, w, aw, d_out, (hipStream_t)stream);
 }
 
 // ----------------------------------------------------------------------------------- gradient in the mean-flux parameters

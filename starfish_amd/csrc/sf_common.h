@@ -11,6 +11,7 @@
 
 #define SF_LEAF 64        // Cholesky leaf block (potrf / trsm granularity); matrices padded to it
 #define SF_NB 256         // outer left-looking panel width
+#define SF_LS_MAXP SF_LOCAL_SCAN_MAX_PATCH  // widest patch of a local-scan candidate in pixels (sf_local_scan.h)
 #define SF_MAX_LOCAL 32   // local kernels per model (sf_fill_elem.h: 32-bit masks of the fill tiles, per-block tables)
 #define SF_NF_MIN_VSINI 16     // FFT lengths of a model with vsini: k_spline_apply takes whole 16-point blocks,
 #define SF_NF_MAX_VSINI 65536  // sf_launch_broaden transforms at most 65536 points
@@ -161,7 +162,7 @@ int sf_launch_diag_copy(const double* A, int n, int lda, int64_t stride, int bat
 int sf_launch_clock_probe(long long* out, long long wall_ticks, hipStream_t s);
 
 // sf_fill.hip (layers: sf_fill_elem.h, sf_fill_band.h, sf_fill_tile.h, sf_fill_dense.h, sf_fill_free.h, sf_cov_matvec.h, sf_cinv.h,
-// sf_grad_frame.h, sf_cov_grad.h, sf_fisher_cov.h, sf_emu_grad.h)
+// sf_grad_frame.h, sf_cov_grad.h, sf_fisher_cov.h, sf_local_scan.h, sf_emu_grad.h)
 struct sf_fill_args {
     const double* wave;    // [n]
     const double* sigma;   // [n]
@@ -224,6 +225,14 @@ int sf_launch_cov_grad(const sf_fill_args& f, int batch, const double* winv, con
 static inline __host__ __device__ int sf_fisher_cov_ld(int n) { return (n + SF_LEAF - 1) / SF_LEAF * SF_LEAF; }
 int sf_launch_fisher_cov(const sf_fill_args& f, int batch, const double* winv, const int* info, double* wf, double* tj, double* part,
                          double* fisher, int fisher_stride, hipStream_t s);
+// sf_local_scan.h: the score scan for a new local kernel at amplitude 0: f, winv, alpha, ld_alpha, info as sf_launch_cov_grad gets
+// them on a monotonic grid; cand: [ncand][2] = mu, sigma (km/s), shared by the batch; patch: [ncand][2] ints and wband:
+// sf_local_scan_band_doubles(n, batch) doubles of scratch (the patches; the block band of C^-1 with its mirror images);
+// out[b][q][3] = alpha^T k alpha, tr(C^-1 k), 1/2 tr(C^-1 k C^-1 k): zeros for a candidate with no pixel in reach, NaN for one
+// whose patch is wider than SF_LS_MAXP pixels and where info[b] != 0
+size_t sf_local_scan_band_doubles(int n, int batch);
+int sf_launch_local_scan(const sf_fill_args& f, int batch, const double* winv, const double* alpha, int ld_alpha, const int* info,
+                         const double* cand, int ncand, int* patch, double* wband, double* out, hipStream_t s);
 // sf_grad_frame.h: the sum over the orders of a multi-order gradient (sf_multi_grad_reduce)
 struct sf_multi_reduce_args {
     const double* unit_lnl;   // [nseg * W]

@@ -156,7 +156,7 @@ static BandWork carve_band(const sf_ctx* c, int B, int halfwidth, void* p, size_
 
 // ------------------------------------------------------------------- the factor applied to right-hand sides
 // (sf_apply_batch, sf_decompose_batch, sf_pointwise_batch, sf_loglike_grad_batch, sf_fisher_cov_batch,
-// sf_loglike_mean_grad_batch; behind the Work of the same call: base_bytes = its size)  Every call has the staging area -- the right-hand sides padded to npad rows, the factor is applied
+// sf_loglike_mean_grad_batch, sf_local_scan_batch; behind the Work of the same call: base_bytes = its size)  Every call has the staging area -- the right-hand sides padded to npad rows, the factor is applied
 // to it in place (for all but sf_apply_batch it ends up holding alpha = C^-1 rhs) -- and lnl / info, what the likelihood's
 // last step leaves.  Then, in this order, the parts the call asks for:
 //   AW_YV        yv: t = Y alpha, m doubles per right-hand side (sf_decompose_batch)
@@ -172,11 +172,18 @@ static BandWork carve_band(const sf_ctx* c, int B, int halfwidth, void* p, size_
 //   AW_FISHER_COV  (sf_fisher_cov_batch, with AW_INVERSE and AW_PART) wfull: every tile of W = C^-1, both triangles, and tj: one
 //                T_j = W dC_j, ld x ld doubles per walker each with ld = sf_fisher_cov_ld(n) <= npad -- the same for every number
 //                of slots: the slots are worked through one at a time, and part holds the sums of the slot at hand
-enum AppliedParts { AW_YV = 1, AW_COV_DIAG = 2, AW_INVERSE = 4, AW_PART = 8, AW_MEAN = 16, AW_FISHER = 32, AW_FISHER_COV = 64 };
+//   AW_LOCAL_SCAN  (sf_local_scan_batch, with AW_INVERSE; nslots = its candidates) patch: two ints per candidate, the first and
+//                last pixel in its reach; wband: per walker and 64-row block A the 64 x 64 tiles (A, K) of W = C^-1 for |A - K| <=
+//                reach = min(blocks - 1, 4), [B][blocks][2 reach + 1][64][64] doubles (sf_local_scan_band_doubles) -- linear in n
+enum AppliedParts {
+    AW_YV = 1, AW_COV_DIAG = 2, AW_INVERSE = 4, AW_PART = 8, AW_MEAN = 16, AW_FISHER = 32, AW_FISHER_COV = 64, AW_LOCAL_SCAN = 128
+};
 struct AppliedWork {
     double *stage, *lnl;
     int* info;
     double *yv, *cov_diag, *cinv_diag, *winv, *part, *xs, *fin, *mpart, *dcoef, *kdot, *mudot, *zdot, *fpart, *wfull, *tj;
+    int* patch;    // (AW_LOCAL_SCAN)
+    double* wband;
     double* coef;  // (carve_multi_grad only) the segment's own spline coefficients, which a single-order call keeps in its Work
     size_t bytes;
 };
@@ -209,6 +216,10 @@ static AppliedWork carve_applied(const sf_ctx* c, const sf_model_desc* mdl, int 
         const size_t ld = (size_t)sf_fisher_cov_ld(c->n);
         w.wfull = k.take<double>((size_t)B * ld * ld);
         w.tj = k.take<double>((size_t)B * ld * ld);
+    }
+    if (parts & AW_LOCAL_SCAN) {
+        w.patch = k.take<int>(2 * (size_t)nslots);
+        w.wband = k.take<double>(sf_local_scan_band_doubles(c->n, B));
     }
     w.bytes = sf_align_up(k.off, 256);
     return w;

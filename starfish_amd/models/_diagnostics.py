@@ -1,6 +1,6 @@
 """The factor-applied diagnostics of :class:`SpectrumModel`: the Cholesky factor of the covariance applied to right-hand
-sides, the residual split by covariance component, the per-pixel leave-one-out predictive.  Not likelihood evaluations: none
-of them touches residuals, _lnprob, _log_scale or the covariance caches.
+sides, the residual split by covariance component, the per-pixel leave-one-out predictive, the score scan for new local
+kernels.  Not likelihood evaluations: none of them touches residuals, _lnprob, _log_scale or the covariance caches.
 
 ``solver`` (cho_solve, apply_factor_batch with "Cinv", residual_components, pointwise and their batch forms): None is the dense
 factor whatever the model's own ``solver`` is, so that every call keeps its bits; "banded" / "auto" take the band + Woodbury solver
@@ -8,6 +8,39 @@ as the gradient methods do (:meth:`DeviceOrder.diagnose_banded`)."""
 import numpy as np
 
 from .. import _device as D
+
+DEFAULT_SCAN_SIGMAS = (8.0, 15.0, 30.0)  # km/s
+
+
+def pick_local_kernels(z, amp, mus, sigmas, threshold=4.0, buffer=None, max_kernels=None):
+    """The peak picking of :meth:`Diagnostics.propose_local_kernels` as a pure function.  ``z`` and ``amp``: (len(sigmas),
+    len(mus)) score statistics and Newton amplitudes; ``mus`` in the units of the wavelengths, ``sigmas`` in km/s.
+
+    Per centre the width with the largest ``z`` (the first of equal ones; NaN entries do not count, a centre with nothing but NaN
+    is left out).  Centres with ``z > threshold`` and a positive amplitude are walked from the largest ``z`` down (equal ``z``:
+    the smaller ``mu`` first); one that lies within ``buffer`` of a kept centre is dropped -- ``buffer`` None: within the kept
+    kernel's own reach ``4 sigma mu / c``.  At most ``max_kernels`` are kept (None: no limit).  Returns the list, sorted by
+    ``mu``, of ``{"mu", "log_amp", "log_sigma"}``."""
+    z, amp = np.atleast_2d(np.asarray(z, dtype=np.float64)), np.atleast_2d(np.asarray(amp, dtype=np.float64))
+    mus, sigmas = np.atleast_1d(np.asarray(mus, dtype=np.float64)), np.atleast_1d(np.asarray(sigmas, dtype=np.float64))
+    if z.shape != (len(sigmas), len(mus)) or amp.shape != z.shape:
+        raise ValueError(f"z of shape {z.shape} and amp of shape {amp.shape}: expected ({len(sigmas)}, {len(mus)})")
+    if max_kernels is not None and max_kernels <= 0:
+        return []
+    cols = np.nonzero(~np.isnan(z).all(axis=0))[0]
+    best = np.argmax(np.where(np.isnan(z[:, cols]), -np.inf, z[:, cols]), axis=0)
+    zbest, abest = z[best, cols], amp[best, cols]
+    ok = (zbest > threshold) & (abest > 0) & np.isfinite(abest)
+    cols, best, zbest, abest = cols[ok], best[ok], zbest[ok], abest[ok]
+    kept = []
+    for i in np.lexsort((mus[cols], -zbest)):
+        mu, sg = float(mus[cols[i]]), float(sigmas[best[i]])
+        if any(abs(mu - k["mu"]) <= (k["reach"] if buffer is None else buffer) for k in kept):
+            continue
+        kept.append({"mu": mu, "log_amp": float(np.log(abest[i])), "log_sigma": float(np.log(sg)), "reach": 4 * sg * mu / D.C_KMS})
+        if max_kernels is not None and len(kept) >= max_kernels:
+            break
+    return [{key: k[key] for key in ("mu", "log_amp", "log_sigma")} for k in sorted(kept, key=lambda k: k["mu"])]
 
 
 class Diagnostics:
@@ -183,3 +216,95 @@ class Diagnostics:
             rhs = (out["flux"] - self.data.flux)[:, None, :]
         res = self._pointwise_dict(rhs, out["alpha"], out["cinv_diag"], out["cov_diag"], single)
         return (res, out["info"]) if return_info else res
+
+    # ------------------------------------------------------------------ where does a new local kernel belong?
+    # The score (Lagrange-multiplier) test for adding a local kernel of centre mu and width sigma at amplitude A = 0 to the
+    # covariance as it stands: with k the matrix the kernel adds at amplitude 1, alpha = C^-1 r and W = C^-1,
+    # U = d lnL / dA = 1/2 (alpha^T k alpha - tr(W k)), its information I = 1/2 tr(W k W k), z = U / sqrt(I), A = U / I.
+    def _scan_candidates(self, mus, sigmas, wl_range):
+        """The centres and widths of a scan, checked on the host: (mus, sigmas, (len(sigmas) * len(mus), 2) candidate rows,
+        width-major)."""
+        wave = np.asarray(self.data.wave, dtype=np.float64)
+        mus = wave.copy() if mus is None else np.atleast_1d(np.asarray(mus, dtype=np.float64)).copy()
+        if wl_range is not None:
+            lo, hi = wl_range
+            mus = mus[(mus >= lo) & (mus <= hi)]
+        sigmas = np.atleast_1d(np.asarray(sigmas, dtype=np.float64))
+        if mus.ndim != 1 or sigmas.ndim != 1 or not mus.size or not sigmas.size:
+            raise ValueError("the scan needs at least one centre and one width")
+        if not (np.isfinite(mus).all() and (mus > 0).all() and np.isfinite(sigmas).all() and (sigmas > 0).all()):
+            raise ValueError("the centres (wavelengths) and the widths (km/s) of the scan must be positive and finite")
+        cand = np.stack([np.tile(mus, len(sigmas)), np.repeat(sigmas, len(mus))], axis=1)
+        lo, hi = D.local_scan_patches(wave, cand)
+        wide = np.nonzero(hi - lo + 1 > D.LOCAL_SCAN_MAX_PATCH)[0]
+        if wide.size:
+            q = int(wide[0])
+            raise ValueError(f"candidate mu={float(cand[q, 0])!r}, sigma={float(cand[q, 1])!r} km/s reaches {int(hi[q] - lo[q] + 1)} pixels: the "
+                             f"device scans patches of at most {D.LOCAL_SCAN_MAX_PATCH} pixels")
+        return mus, sigmas, cand
+
+    def _local_scan(self, P, mus, sigmas, wl_range):
+        """The scan of the rows of ``P`` (None: the model's own state): the result dict with a leading walker axis, the status,
+        the centres and the widths.  No cache is updated."""
+        mus, sigmas, cand = self._scan_candidates(mus, DEFAULT_SCAN_SIGMAS if sigmas is None else sigmas, wl_range)
+        dev, md, rows = self._pack(P, update_caches=False)
+        step = 65535  # (candidates per device call)
+        parts = [dev.local_scan(md, rows, cand[q:q + step]) for q in range(0, len(cand), step)]
+        shape = (rows.shape[0], len(sigmas), len(mus))
+        quad, trace, fisher = (np.concatenate([p[key] for p in parts], axis=1).reshape(shape) for key in ("quad", "trace", "fisher"))
+        score = 0.5 * (quad - trace)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            z = np.where(fisher == 0, np.nan, score / np.sqrt(fisher))
+            amp = np.where(fisher == 0, np.nan, score / fisher)
+        res = {"score": score, "information": fisher, "z": z, "amp": amp, "quad": quad, "trace": trace}
+        return res, parts[0]["info"], mus, sigmas
+
+    def local_kernel_scan(self, mus=None, sigmas=None, wl_range=None):
+        """The score test for one more local kernel, for every centre in ``mus`` (None: every pixel's wavelength; ``wl_range`` =
+        (lo, hi) keeps the centres inside it) and every width in ``sigmas`` (km/s; None: 8, 15, 30), at the current parameters
+        and with every kernel the model already has in the covariance (sf_local_scan_batch): dict of arrays of shape
+        (len(sigmas), len(mus)) with "score" = ``d lnL / dA`` at amplitude A = 0, "information" = its Fisher information, "z" =
+        ``score / sqrt(information)``, "amp" = ``score / information`` (one Newton step in A), and the pieces "quad" = ``alpha^T k
+        alpha`` and "trace" = ``tr(C^-1 k)``.  "z" and "amp" are NaN where the information is 0 (no pixel within 4 sigma of the
+        centre).  A candidate that reaches more pixels than the device scans is a ``ValueError`` before any device call.  Raises
+        as :meth:`log_likelihood` does; the model's state is not modified."""
+        res, info, _, _ = self._local_scan(None, mus, sigmas, wl_range)
+        self._raise_for_info(info[0])
+        return {key: v[0] for key, v in res.items()}
+
+    def local_kernel_scan_batch(self, P, mus=None, sigmas=None, wl_range=None, return_info=False):
+        """:meth:`local_kernel_scan` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device pass: the same
+        keys with a leading B axis.  Walkers that fail get NaN rows, ``info`` their codes (those of
+        :meth:`log_likelihood_batch`).  The model's own state is not modified."""
+        res, info, _, _ = self._local_scan(np.atleast_2d(np.asarray(P, dtype=np.float64)), mus, sigmas, wl_range)
+        return (res, info) if return_info else res
+
+    def propose_local_kernels(self, threshold=4.0, buffer=None, max_kernels=None, sigmas=None, mus=None, wl_range=None, P=None):
+        """Where the residual asks for local kernels: :meth:`local_kernel_scan` (with ``P``: :meth:`local_kernel_scan_batch`, ``z``
+        and ``amp`` averaged over the walkers that evaluate), then per centre the width with the largest ``z``, the centres with
+        ``z > threshold`` walked from the largest ``z`` down, a centre within ``buffer`` (the units of the wavelengths; None: the
+        kept kernel's own reach of 4 sigma) of a kept one dropped, at most ``max_kernels`` kept (None: as many as the model can
+        still take).  Returns the list, sorted by ``mu``, of ``{"mu", "log_amp", "log_sigma"}`` with ``log_amp = log(amp)`` of the
+        Newton step: what ``model["local_cov"] = [*kernels_it_has, *model.propose_local_kernels()]`` takes, to be refined by
+        :meth:`train_covariance`.  The model is never changed.
+
+        ``z`` is a score statistic at FIXED remaining parameters, and one-sided: the amplitude of a kernel cannot be negative,
+        so only an excess of correlated residual power (``z > 0``) proposes one; under the null ``z`` is about standard normal
+        per candidate, and the largest of a whole scan of a few thousand correlated candidates reaches 3 by chance.  Candidates
+        are tested one at a time: two proposals may explain the same feature where the buffer lets them.  The reference's
+        ``find_residual_peaks`` / ``optimize_residual_peaks`` instead sigma-clip the averaged residuals and fit each peak's
+        kernel by Nelder-Mead on the full likelihood; here the covariance that is already fitted (global kernel, emulator,
+        existing local kernels) is accounted for exactly, every pixel and width is tested, and nothing is refitted."""
+        if P is None:
+            res, info, mus, sigmas = self._local_scan(None, mus, sigmas, wl_range)
+            self._raise_for_info(info[0])
+            z, amp = res["z"][0], res["amp"][0]
+        else:
+            res, info, mus, sigmas = self._local_scan(np.atleast_2d(np.asarray(P, dtype=np.float64)), mus, sigmas, wl_range)
+            good = info == 0
+            if not good.any():
+                raise ValueError("no walker of P evaluates: nothing to average")
+            z, amp = res["z"][good].mean(axis=0), res["amp"][good].mean(axis=0)
+        if max_kernels is None:
+            max_kernels = D.MAX_LOCAL - len(self._local_kernels())
+        return pick_local_kernels(z, amp, mus, sigmas, threshold, buffer, max_kernels)
