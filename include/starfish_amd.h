@@ -63,7 +63,7 @@ extern "C" {
                                     on a device SHARED with other processes the launch stalls when workgroups that hold claimed
                                     tasks are kept from running, and is given up after 25 ms without a single completed task
                                     (or 4 s in any one wait): see sf_persistent_potrf / sf_persistent_potrf_status.  Callers
-                                    recover by sf_persistent_potrf(0) and re-running the batch (starfish_amd/_device.py does,
+                                    recover by sf_persistent_potrf(0) and re-running the batch (starfish_amd/_runtime.py does,
                                     with a warning); it is never to be treated as a rejected walker */
 
 #define SF_INFO_NAN (-6)         /* the likelihood came out NaN although every stage reported success: lnl = -inf, but

@@ -12,176 +12,18 @@ from scipy.linalg import cho_solve, cholesky, solve_triangular
 
 from . import _lib
 from . import _rows as R
+# the names of the layers below, re-exported: the runtime every call shares and the multi-order plans
+from ._runtime import (  # noqa: F401
+    INFO_MESSAGES, APPLY_OPS, MEAN_GRAD_MAX_SLOTS, MAX_LOCAL, LOCAL_SCAN_MAX_PATCH, INFO_BANDWIDTH, INFO_INTERNAL,
+    HBM_RESERVE, _torch, check_solver, current_stream, device_of, empty, fetch_results, finish_structured,
+    grow_workspace, persistent_status, ptr, recover_from_internal, refused_output, result_buffers, retry_internal,
+    run_chunked, stream_ptr, to_dev, units_that_fit, workspace)
+from ._multi import (  # noqa: F401
+    BandedMultiFisherPlan, BandedMultiGradPlan, MultiGradPlan, MultiPlan, _BandedFisherUnits, _BandedUnits,
+    banded_units, collect_multi, column_map_csr, fisher_banded_multi, loglike_banded_multi_grad, loglike_multi,
+    loglike_multi_grad, merge_units, model_desc_key, reduce_fisher_host, reduce_orders_host, rerouted_units)
 
-INFO_MESSAGES = {
-    -1: "Querying emulator outside of original parameter range.",
-    -2: "vsini must be positive",
-    -3: "emulator weight covariance is not positive definite",
-    -4: "covariance support wider than the band half-width given to the banded solver",
-    -5: "internal error: a bounded wait inside a persistent kernel gave up (banded sweep or dataflow Cholesky; "
-        "no result of that call is valid -- is the GPU shared with another process?)",
-    -6: "the log-likelihood evaluated to NaN (non-finite input or intermediate)",
-}
-APPLY_OPS = {"L": 0, "Linv": 1, "LinvT": 2, "Cinv": 3}  # SF_APPLY_* of include/starfish_amd.h
-MEAN_GRAD_MAX_SLOTS = 16  # SF_MEAN_GRAD_MAX_SLOTS of include/starfish_amd.h
-MAX_LOCAL = 32  # SF_MAX_LOCAL of csrc/sf_common.h: local kernels per model
-LOCAL_SCAN_MAX_PATCH = 256  # SF_LOCAL_SCAN_MAX_PATCH of include/starfish_amd.h
-INFO_BANDWIDTH = -4
-INFO_INTERNAL = -5
 C_KMS = 2.99792458e5
-
-
-def persistent_status(lib):
-    """``sf_persistent_potrf_status`` as a dict (host memory of the library: read it after the stream was synchronised)."""
-    buf = (C.c_longlong * 8)()
-    _lib.check(lib.sf_persistent_potrf_status(buf), "sf_persistent_potrf_status")
-    keys = ("aborted_launches", "reason", "workgroups_started", "grid", "wait_ticks", "tasks_completed",
-            "launches", "enabled")
-    return dict(zip(keys, (int(v) for v in buf)))
-
-
-def recover_from_internal(lib, where, count, stacklevel=3):
-    """A dense call came back with SF_INFO_INTERNAL: the persistent-kernel Cholesky gave a launch up and the whole batch
-    is invalid (include/starfish_amd.h).  The reference would never turn that into a rejected proposal
-    (spectrum_model.py:400 raises out of cho_factor), so: say so loudly -- with what the aborting workgroup recorded --,
-    switch the PROCESS (all devices, all threads) to the launch sequences (no waits inside kernels) and let the caller
-    re-run the batch."""
-    import warnings
-
-    st = persistent_status(lib)
-    why = {1: "a wait between workgroups reached its 4-s bound",
-           2: "no task of the launch completed for 25 ms"}.get(st["reason"], "no abort record")
-    if st["grid"] and st["workgroups_started"] < st["grid"]:
-        why += f"; only {st['workgroups_started']} of its {st['grid']} workgroups had started (grid not co-resident)"
-    warnings.warn(
-        f"{where}: internal status -5 for {int(count)} unit(s) -- the persistent-kernel Cholesky gave a launch up ({why}, "
-        f"after {st['tasks_completed']} completed tasks): is this GPU shared with another process?  The kernel assumes "
-        "one process per GPU.  It is now disabled for this whole process, on every device and thread "
-        "(sf_persistent_potrf(0)), and the batch is re-run on the launch sequence.",
-        RuntimeWarning,
-        stacklevel=stacklevel,
-    )
-    lib.sf_persistent_potrf(0)
-
-
-def retry_internal(lib, where, evaluate, count=None, stacklevel=4):
-    """THE policy for SF_INFO_INTERNAL of the dense path.  ``evaluate(again) -> (result, info)`` runs the call and fetches
-    its status codes; ``again`` is False for the first run and True for the one repeat after
-    :func:`recover_from_internal` (never a silent -inf: warn, switch the persistent kernel off, evaluate again).  A -5 that
-    survives the repeat is never an ordinary per-unit status -- no value of the call is valid: RuntimeError.  ``count``:
-    the units the warning names (default: the -5 entries of ``info``); ``stacklevel``: the frame it is attributed to (default:
-    the one that called our caller)."""
-    result, info = evaluate(False)
-    bad = int(np.count_nonzero(np.asarray(info) == INFO_INTERNAL))
-    if not bad:
-        return result
-    recover_from_internal(lib, where, bad if count is None else count, stacklevel=stacklevel)
-    result, info = evaluate(True)
-    if np.any(np.asarray(info) == INFO_INTERNAL):
-        raise RuntimeError(INFO_MESSAGES[INFO_INTERNAL])
-    return result
-
-
-def _torch():
-    import torch
-
-    return torch
-
-
-def device_of(index=None):
-    torch = _torch()
-    if index is None:
-        index = torch.cuda.current_device() if torch.cuda.is_available() else 0
-    return torch.device("cuda", index)
-
-
-def to_dev(arr, dev):
-    torch = _torch()
-    a = np.ascontiguousarray(np.asarray(arr, dtype=np.float64))
-    return torch.from_numpy(a).to(dev)
-
-
-def ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def empty(shape, dev, dtype=None):
-    torch = _torch()
-    return torch.empty(shape, dtype=dtype or torch.float64, device=dev)
-
-
-def current_stream(dev):
-    return _torch().cuda.current_stream(dev)
-
-
-def stream_ptr(dev):
-    return C.c_void_p(current_stream(dev).cuda_stream)
-
-
-def workspace(nbytes, dev):
-    torch = _torch()
-    return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dev)
-
-
-def grow_workspace(slot, key, need, dev):
-    """The byte buffer ``slot[key]``, grown to at least ``need`` bytes.  ``slot`` is the mapping that owns the buffer (an
-    object's ``vars()`` or a dict): a buffer that is too small is dropped BEFORE the new one is allocated, which no
-    reference held by a caller may prevent.  The buffer is handed to kernels on whatever stream is current (EchelleModel
-    rotates orders over side streams), so that stream is recorded on it: the caching allocator then does not recycle a
-    dropped buffer before the work queued on it has finished."""
-    if slot[key] is None or slot[key].numel() < need:
-        slot[key] = None
-        slot[key] = workspace(need, dev)
-    slot[key].record_stream(current_stream(dev))
-    return slot[key]
-
-
-HBM_RESERVE = 0.15  # share of the free HBM that the chunk sizes leave alone
-
-
-def units_that_fit(dev, fixed_bytes, per_unit_bytes, held_bytes=0, limit=None):
-    """How many units of ``per_unit_bytes`` workspace fit the free HBM of ``dev`` next to ``fixed_bytes``, at least 1, at
-    most ``limit``.  ``held_bytes``: the buffer the caller is about to replace counts as free."""
-    free, _total = _torch().cuda.mem_get_info(dev)
-    cap = max(1, (int((free + held_bytes) * (1.0 - HBM_RESERVE)) - fixed_bytes) // per_unit_bytes)
-    return cap if limit is None else min(cap, int(limit))
-
-
-def run_chunked(lib, where, dev, slot, key, fixed_bytes, per_unit_bytes, limit, B, max_chunk, reserve, buffers, enqueue, download,
-                count=None):
-    """THE chunk loop of the batched calls: ``B`` units cut into chunks whose workspace fits the free HBM
-    (:func:`units_that_fit` of ``fixed_bytes``, ``per_unit_bytes`` and ``limit``; the buffer ``slot[key]`` counts as free), at
-    most ``max_chunk`` each; the results allocated (``buffers()``) and every chunk enqueued on ONE workspace
-    (``reserve(units)``, which grows ``slot[key]``) with ``enqueue(bufs, lo, hi, ws)``; ``download(bufs)``, a dict with "info",
-    returned; all of it once more if a status is SF_INFO_INTERNAL (:func:`retry_internal` with ``where`` and ``count``; its
-    warning names the frame that called the caller of our caller)."""
-    def run(again):
-        held = slot[key].numel() if slot[key] is not None else 0
-        chunk = min(B, max_chunk or B, units_that_fit(dev, fixed_bytes, per_unit_bytes, held, limit))
-        bufs = buffers()
-        ws = reserve(chunk)
-        for lo in range(0, B, chunk):
-            enqueue(bufs, lo, min(lo + chunk, B), ws)
-        res = download(bufs)
-        return res, res["info"]
-
-    return retry_internal(lib, where, run, count=count, stacklevel=6)
-
-
-def result_buffers(B, dev, resid_cols=None):
-    """Device outputs of a likelihood call of ``B`` units: the (4, B) "quad" lnl / logdet / sqmah / log_scale (ONE
-    device->host copy for the four double outputs), the int32 ``info`` and, asked for, the (B, resid_cols) residuals."""
-    torch = _torch()
-    return (empty((4, B), dev), empty((B,), dev, torch.int32),
-            empty((B, resid_cols), dev) if resid_cols is not None else None)
-
-
-def fetch_results(quad, info, resid=None):
-    """Download what :func:`result_buffers` allocated: dict of numpy arrays lnl, logdet, sqmah, log_scale, info (+ resid)."""
-    out = dict(zip(("lnl", "logdet", "sqmah", "log_scale"), quad.cpu().numpy()), info=info.cpu().numpy())
-    if resid is not None:
-        out["resid"] = resid.cpu().numpy()
-    return out
 
 
 def local_scan_patches(wave, cand):
@@ -237,45 +79,6 @@ def band_halfwidth_bound(wave, rows, n_grid, has_global, n_local, n_cheb):
     return np.minimum(hw, big).astype(np.int64)
 
 
-def check_solver(solver, choices=("dense", "banded", "auto"), or_none=False):
-    """``ValueError`` unless ``solver`` is one of ``choices`` (``or_none``: the message offers None too, which the caller has
-    already replaced by its default)."""
-    if solver not in choices:
-        names = ["None"] * or_none + [repr(c) for c in choices]
-        raise ValueError(f"solver must be {', '.join(names[:-1])} or {names[-1]}")
-
-
-def refused_output(B, shapes):
-    """What the band solver's dispatchers start from: every one of ``B`` walkers refused with INFO_BANDWIDTH -- ``lnl`` -inf,
-    ``info`` -4, NaN in every other result (``shapes``: key -> trailing shape)."""
-    out = dict(lnl=np.full(B, -np.inf))
-    out.update({key: np.full((B,) + tuple(shape), np.nan) for key, shape in shapes.items()})
-    out["info"] = np.full(B, INFO_BANDWIDTH, dtype=np.int32)
-    return out
-
-
-def finish_structured(out, fits, solver, dense):
-    """THE tail of the band solver's dispatchers, once the banded groups' results are in ``out`` (:func:`refused_output`
-    elsewhere).  An internal wait timeout of the sweep (-5, not expected: the bound keeps a logic error from hanging the GPU) is
-    recomputed by the dense solver -- under "banded" too -- instead of silently turning into a rejected walker; under "auto" so
-    are the walkers whose bound does not fit (``~fits``) and those the kernels flagged with -4.  ``dense(rest)`` gets their
-    ascending indices, once, and returns the keys of ``out`` for them.  The warning names the caller's frame."""
-    internal = out["info"] == INFO_INTERNAL
-    if internal.any():
-        import warnings
-
-        warnings.warn(f"banded solver: internal status -5 for {int(internal.sum())} walker(s); recomputed densely",
-                      RuntimeWarning, stacklevel=2)
-    rest = np.nonzero(internal)[0]
-    if solver == "auto":  # too wide for the banded kernels -> dense
-        rest = np.nonzero(~fits | (out["info"] == INFO_BANDWIDTH) | internal)[0]
-    if rest.size:
-        got = dense(rest)
-        for key in out:
-            out[key][rest] = got[key]
-    return out
-
-
 DIAGNOSE_WANTS = ("alpha", "cinv_diag", "cov_diag", "comp")
 
 
@@ -310,630 +113,6 @@ def factor_v11(v11, w_hat):
     linv = np.tril(solve_triangular(L, np.eye(L.shape[0]), lower=True))
     alpha = cho_solve((L, True), np.asarray(w_hat, dtype=np.float64))
     return np.ascontiguousarray(linv), np.ascontiguousarray(alpha)
-
-
-def model_desc_key(md):
-    """The fields of a ModelDesc as a hashable tuple (two orders may share a multi-order call only if equal)."""
-    return tuple(int(getattr(md, name)) for name, _ in md._fields_)
-
-
-class MultiPlan:
-    """Device-resident state of a repeated multi-order evaluation (sf_loglike_multi_batch): parameter rows,
-    outputs and workspace are allocated once; :meth:`enqueue` only launches.  ``orders`` are
-    :class:`DeviceOrder` objects of ONE device, ``rows_list[i]`` the (B_i, stride) C-ABI rows of order i.
-    ``md`` is one ModelDesc for every order (all rows of one layout), or a list with one ModelDesc per order
-    (sf_loglike_multi_batch_md: orders with their own row layouts still share one batched Cholesky).
-    Unit lists that do not fit the free HBM (or ``max_units``) are cut into several calls."""
-
-    def __init__(self, orders, md, rows_list, max_units=None):
-        torch = _torch()
-        self.orders = list(orders)
-        self.per_order = isinstance(md, (list, tuple))
-        self.md = list(md) if self.per_order else md
-        self.lib = orders[0].lib
-        self.dev = orders[0].dev
-        if any(o.dev != self.dev for o in orders):
-            raise ValueError("multi-order call: all orders must live on the same device")
-        if self.per_order:
-            if len(self.md) != len(self.orders) or len(rows_list) != len(self.orders):
-                raise ValueError(f"multi-order call: {len(self.md)} descriptors and {len(rows_list)} row blocks for "
-                                 f"{len(self.orders)} orders")
-            mds = self.md
-        else:
-            mds = [md] * len(self.orders)
-        strides = [o.param_stride(m) for o, m in zip(orders, mds)]
-        if not self.per_order and len(set(strides)) > 1:
-            raise ValueError(f"multi-order call: one descriptor gives the orders row strides {sorted(set(strides))}")
-        for want, r in zip(strides, rows_list):
-            if int(r.shape[-1]) != want:
-                raise ValueError(f"multi-order call: parameter rows of {int(r.shape[-1])} doubles do not match the "
-                                 f"descriptor's stride {want} (orders with different descriptors need one descriptor "
-                                 f"per order)")
-        self.sizes = [int(np.atleast_2d(r).shape[0]) if not torch.is_tensor(r) else int(r.shape[0]) for r in rows_list]
-        U = sum(self.sizes)
-        with torch.cuda.device(self.dev):
-            self.P = [r if torch.is_tensor(r) else to_dev(np.atleast_2d(r), self.dev) for r in rows_list]
-            self.quad, self.info, _ = result_buffers(U, self.dev)
-            # units that fit: the workspace is linear in the unit count up to the fixed Cholesky scratch.  With one
-            # descriptor per order the largest estimate of any order counts (e.g. the only order whose descriptor
-            # needs the broadening buffers: the call allocates them for all)
-            fixed, per_unit = 0, 1
-            for i in range(len(orders)) if self.per_order else (0,):
-                one = _lib.Segment(orders[i].ctx, ptr(self.P[i]).value, 1, 0)
-                desc = self._desc_array(mds[i:i + 1]) if self.per_order else C.byref(md)
-                w1 = self._workspace_bytes(C.byref(one), 1, desc)
-                one.B = 2
-                w2 = self._workspace_bytes(C.byref(one), 1, desc)
-                pu = max(w2 - w1, 1)
-                per_unit, fixed = max(per_unit, pu), max(fixed, w1 - pu)
-            lead = orders[0]
-            held = lead._ws_multi.numel() if lead._ws_multi is not None else 0
-            cap = units_that_fit(self.dev, fixed, per_unit, held, max_units or None)
-            self.pieces, cur, cur_n = [], [], 0
-            for i, n in enumerate(self.sizes):
-                lo = 0
-                while lo < n:
-                    take = min(n - lo, cap - cur_n)
-                    cur.append((i, lo, lo + take))
-                    cur_n += take
-                    lo += take
-                    if cur_n == cap:
-                        self.pieces.append(cur)
-                        cur, cur_n = [], 0
-            if cur:
-                self.pieces.append(cur)
-            offs = np.concatenate([[0], np.cumsum(self.sizes)])
-            self.calls, need = [], 0
-            for piece in self.pieces:
-                segs = (_lib.Segment * len(piece))()
-                for k, (i, lo, hi) in enumerate(piece):
-                    segs[k] = _lib.Segment(orders[i].ctx, ptr(self.P[i][lo:hi]).value, hi - lo, 0)
-                models = self._desc_array([mds[i] for i, _, _ in piece]) if self.per_order else C.byref(md)
-                nb = self._workspace_bytes(segs, len(piece), models)
-                if nb == 0:
-                    _lib.check(-1, "sf_multi_workspace_bytes")
-                need = max(need, nb)
-                u0 = int(offs[piece[0][0]] + piece[0][1])  # the pieces of one call are contiguous in unit order
-                self.calls.append((segs, len(piece), u0, sum(hi - lo for _, lo, hi in piece), models))
-            self.ws = grow_workspace(vars(lead), "_ws_multi", need, self.dev)
-
-    @staticmethod
-    def _desc_array(mds):
-        """``const sf_model_desc* const*`` of the given descriptors (the array keeps them alive)."""
-        arr = (C.POINTER(_lib.ModelDesc) * len(mds))(*[C.pointer(m) for m in mds])
-        arr._keep = mds
-        return arr
-
-    def _workspace_bytes(self, segs, nseg, models):
-        fn = self.lib.sf_multi_workspace_bytes_md if self.per_order else self.lib.sf_multi_workspace_bytes
-        return fn(segs, nseg, models)
-
-    @property
-    def units(self):
-        return sum(self.sizes)
-
-    def enqueue(self):
-        """Launch only: results land in ``self.quad`` / ``self.info`` once the device's current stream is done."""
-        torch = _torch()
-        fn, name = ((self.lib.sf_loglike_multi_batch_md, "sf_loglike_multi_batch_md") if self.per_order
-                    else (self.lib.sf_loglike_multi_batch, "sf_loglike_multi_batch"))
-        with torch.cuda.device(self.dev):
-            s = stream_ptr(self.dev)
-            q = self.quad
-            for segs, nseg, u0, n, models in self.calls:
-                rc = fn(
-                    segs, nseg, models, ptr(q[0][u0:u0 + n]), ptr(q[1][u0:u0 + n]), ptr(q[2][u0:u0 + n]),
-                    ptr(q[3][u0:u0 + n]), ptr(self.info[u0:u0 + n]), ptr(self.ws), self.ws.numel(), s,
-                )
-                _lib.check(rc, name)
-
-    def collect(self):
-        def fetch(again):  # (the first run was enqueued by the caller)
-            if again:
-                self.enqueue()
-            out = collect_multi(self.quad, self.info, self.sizes)
-            return out, np.concatenate([o["info"] for o in out])
-
-        return retry_internal(self.lib, "sf_loglike_multi_batch", fetch)
-
-
-def loglike_multi(orders, md, rows_list, max_units=None, sync=True):
-    """(order x walker) units of several orders of ONE device in one enqueue and one host synchronisation.
-    ``md``: one ModelDesc shared by every order, or a list with one per order (see :class:`MultiPlan`).
-    Returns a list of dicts (lnl, logdet, sqmah, log_scale, info) per order; with ``sync=False`` the
-    un-synchronised :class:`MultiPlan` (callers overlapping several devices call ``plan.collect()`` later)."""
-    plan = MultiPlan(orders, md, rows_list, max_units=max_units)
-    plan.enqueue()
-    return plan.collect() if sync else plan
-
-
-class MultiGradPlan(MultiPlan):
-    """Device-resident state of a repeated multi-order likelihood-and-gradient evaluation (sf_loglike_multi_grad_batch_md):
-    one factorisation per (order x walker) unit gives the likelihood and the gradient in every requested slot.  ``mds``: one
-    ModelDesc per order; ``requests[i]`` = ``(mean_columns, want_cov)``: the columns of order i's parameter row to
-    differentiate in (as :meth:`DeviceOrder.loglike_mean_grad` takes them; may be empty) and whether its covariance slots
-    (in :meth:`DeviceOrder.loglike_grad`'s order) are wanted.  The gradient row of a unit holds its order's mean slots in
-    request order, then its covariance slots.  Buffers are allocated once; unit lists that do not fit the free HBM (or
-    ``max_units``) are cut into several calls, a piece in which no order requests anything is a plain likelihood call."""
-
-    def __init__(self, orders, mds, rows_list, requests, max_units=None):
-        if len(requests) != len(orders):
-            raise ValueError(f"multi-order gradient: {len(requests)} requests for {len(orders)} orders")
-        self.requests = [([int(c) for c in cols], bool(cov)) for cols, cov in requests]
-        self.slots = [len(cols) + (R.cov_grad_slots(md) if cov else 0) for (cols, cov), md in zip(self.requests, mds)]
-        if not any(self.slots):
-            raise ValueError("multi-order gradient: nothing to differentiate (no order requests a slot)")
-        self.stride = max(self.slots)
-        self._slot_arrays = [(C.c_int32 * max(len(cols), 1))(*cols) for cols, _ in self.requests]
-        super().__init__(orders, list(mds), rows_list, max_units=max_units)
-        with _torch().cuda.device(self.dev):
-            self.grad = _torch().zeros((self.units, self.stride), dtype=_torch().float64, device=self.dev)
-
-    def _requests_array(self, idxs):
-        """``const sf_grad_request*`` of the given orders (the array keeps the column lists alive)."""
-        arr = (_lib.GradRequest * len(idxs))()
-        for k, i in enumerate(idxs):
-            cols, cov = self.requests[i]
-            arr[k] = _lib.GradRequest(self._slot_arrays[i], len(cols), int(cov))
-        arr._keep = self._slot_arrays
-        return arr
-
-    def _orders_of(self, segs, nseg):
-        """The orders of these segments, matched by context."""
-        by_ctx = {int(o.ctx): i for i, o in enumerate(self.orders)}
-        items = [segs[k] for k in range(nseg)] if isinstance(segs, C.Array) else [segs._obj]  # (an array, or byref of one)
-        return [by_ctx[int(seg.ctx)] for seg in items]
-
-    def _workspace_bytes(self, segs, nseg, models):
-        """The gradient call's workspace for these segments."""
-        idxs = self._orders_of(segs, nseg)
-        if not any(self.slots[i] for i in idxs):
-            return self.lib.sf_multi_workspace_bytes_md(segs, nseg, models)
-        return self.lib.sf_multi_grad_workspace_bytes_md(segs, nseg, models, self._requests_array(idxs), self.stride)
-
-    def enqueue(self):
-        """Launch only: results land in ``self.quad`` (rows 0 lnl, 3 log_scale), ``self.info`` and ``self.grad`` once the
-        device's current stream is done."""
-        torch = _torch()
-        with torch.cuda.device(self.dev):
-            s = stream_ptr(self.dev)
-            q = self.quad
-            for (segs, nseg, u0, n, models), piece in zip(self.calls, self.pieces):
-                idxs = [i for i, _, _ in piece]
-                if not any(self.slots[i] for i in idxs):
-                    rc = self.lib.sf_loglike_multi_batch_md(segs, nseg, models, ptr(q[0][u0:u0 + n]), None, None,
-                                                            ptr(q[3][u0:u0 + n]), ptr(self.info[u0:u0 + n]), ptr(self.ws),
-                                                            self.ws.numel(), s)
-                    _lib.check(rc, "sf_loglike_multi_batch_md")
-                    continue
-                rc = self.lib.sf_loglike_multi_grad_batch_md(
-                    segs, nseg, models, self._requests_array(idxs), ptr(q[0][u0:u0 + n]), ptr(q[3][u0:u0 + n]),
-                    ptr(self.info[u0:u0 + n]), ptr(self.grad[u0:u0 + n]), self.stride, ptr(self.ws), self.ws.numel(), s)
-                _lib.check(rc, "sf_loglike_multi_grad_batch_md")
-
-    def collect(self):
-        """Per order a dict of numpy arrays: lnl (B,), grad (B, slots of the order), log_scale (B,), info (B,); NaN rows
-        where info != 0.  After SF_INFO_INTERNAL the whole batch is run once more (:func:`retry_internal`)."""
-        def fetch(again):  # (the first run was enqueued by the caller)
-            if again:
-                self.enqueue()
-            lnl, log_scale = self.quad[0].cpu().numpy(), self.quad[3].cpu().numpy()
-            info, grad = self.info.cpu().numpy(), self.grad.cpu().numpy()
-            ends = np.cumsum(self.sizes)
-            out = [dict(lnl=lnl[hi - n:hi], grad=grad[hi - n:hi, :k], log_scale=log_scale[hi - n:hi], info=info[hi - n:hi])
-                   for n, hi, k in zip(self.sizes, ends, self.slots)]
-            return out, info
-
-        return retry_internal(self.lib, "sf_loglike_multi_grad_batch_md", fetch)
-
-    def reduce(self, sources):
-        """The sum over the orders on the device (sf_multi_grad_reduce), of what a finished call left in the plan's buffers:
-        ``sources[j]`` lists the ``(order, slot)`` pairs whose unit slots column j adds, ascending in the order.  Every
-        order must have the same number of walkers W.  Returns numpy ``lnl (W,)``, ``grad (W, len(sources))``, ``info (W,)``."""
-        torch = _torch()
-        if len(set(self.sizes)) != 1:
-            raise ValueError(f"sf_multi_grad_reduce: the orders have {sorted(set(self.sizes))} walkers")
-        W, ncols = self.sizes[0], len(sources)
-        col_ptr, col_src = column_map_csr(sources)
-        with torch.cuda.device(self.dev):
-            d_ptr, d_src = torch.from_numpy(col_ptr).to(self.dev), torch.from_numpy(col_src).to(self.dev)
-            lnl, grad = empty((W,), self.dev), empty((W, max(ncols, 1)), self.dev)
-            info = empty((W,), self.dev, torch.int32)
-            rc = self.lib.sf_multi_grad_reduce(len(self.sizes), W, ptr(self.quad[0]), ptr(self.info), ptr(self.grad), self.stride,
-                                               ptr(d_ptr), ptr(d_src), ncols, ptr(lnl), ptr(grad), max(ncols, 1), ptr(info),
-                                               stream_ptr(self.dev))
-            _lib.check(rc, "sf_multi_grad_reduce")
-            return lnl.cpu().numpy(), grad.cpu().numpy()[:, :ncols], info.cpu().numpy()
-
-
-def column_map_csr(sources):
-    """``sources[j]`` = [(order, slot), ...] -> the int32 arrays ``col_ptr (ncols + 1,)`` and ``col_src (nnz, 2)`` of
-    sf_multi_grad_reduce, the pairs of every column ascending in the order."""
-    col_ptr = np.zeros(len(sources) + 1, dtype=np.int32)
-    pairs = []
-    for j, src in enumerate(sources):
-        pairs += sorted((int(i), int(slot)) for i, slot in src)
-        col_ptr[j + 1] = len(pairs)
-    col_src = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
-    if not len(pairs):
-        col_src = np.zeros((1, 2), dtype=np.int32)
-    return col_ptr, np.ascontiguousarray(col_src)
-
-
-def reduce_orders_host(lnl, info, grads, sources):
-    """sf_multi_grad_reduce's rule on the host, for per-unit results that live on several devices: ``lnl``, ``info``
-    (n_orders, W), ``grads[i]`` (W, slots of order i).  Every sum runs over the orders in ascending index, ``s = g0;
-    s = s + g1; ...``; a column without a source is 0.0; ``info`` is the first non-zero code in that order, and a walker
-    that has one gets ``-inf`` and a NaN row."""
-    lnl, info = np.asarray(lnl, dtype=np.float64), np.asarray(info, dtype=np.int32)
-    W = lnl.shape[1]
-    total = lnl[0].copy()
-    for i in range(1, lnl.shape[0]):
-        total = total + lnl[i]
-    code = np.zeros(W, dtype=np.int32)
-    for i in range(info.shape[0]):
-        code = np.where(code == 0, info[i], code)
-    grad = np.zeros((W, len(sources)))
-    for j, src in enumerate(sources):
-        for q, (i, slot) in enumerate(sorted((int(i), int(slot)) for i, slot in src)):
-            grad[:, j] = grads[i][:, slot] if q == 0 else grad[:, j] + grads[i][:, slot]
-    bad = code != 0
-    total[bad] = -np.inf
-    grad[bad] = np.nan
-    return total, grad, code
-
-
-def loglike_multi_grad(orders, mds, rows_list, requests, max_units=None, sync=True):
-    """The likelihood and its gradient for the (order x walker) units of several orders of ONE device, one factorisation per
-    unit, in one enqueue and one host synchronisation (see :class:`MultiGradPlan` for ``mds`` and ``requests``).  Returns
-    a list of dicts (lnl, grad, log_scale, info) per order; with ``sync=False`` the un-synchronised plan."""
-    plan = MultiGradPlan(orders, mds, rows_list, requests, max_units=max_units)
-    plan.enqueue()
-    return plan.collect() if sync else plan
-
-
-def banded_units(bounds, windows):
-    """Which units of a multi-order gradient the band kernels take: ``bounds[i]`` (B_i,) the half-width bounds of order i's
-    units, ``windows[i]`` its LDS window.  Returns ``fits``, one boolean array per order.  Pure host logic."""
-    return [np.asarray(b) <= int(w) for b, w in zip(bounds, windows)]
-
-
-def rerouted_units(fits, infos, solver):
-    """The rule of :func:`finish_structured` per (order x walker) unit: ``infos[i]`` (B_i,) are the codes the band kernels
-    left (INFO_BANDWIDTH where ``fits[i]`` is false: those units never ran).  Returns per order the ascending walker indices
-    that go through the dense call: units with the internal status -5 under either solver; under "auto" also the units whose
-    bound does not fit and those the kernels flagged -4.  Under "banded" the latter two stay refused.  Pure host logic."""
-    check_solver(solver, ("banded", "auto"))
-    out = []
-    for f, info in zip(fits, infos):
-        info = np.asarray(info)
-        rest = info == INFO_INTERNAL
-        if solver == "auto":
-            rest = rest | ~np.asarray(f) | (info == INFO_BANDWIDTH)
-        out.append(np.nonzero(rest)[0])
-    return out
-
-
-def merge_units(outs, rest, dense):
-    """Put the dense results back by (order, walker): ``outs[i]`` the per-order dicts, ``rest[i]`` the walker indices of order
-    i that were re-routed, ``dense`` the dicts of the dense call for the orders that have any, in order.  In place."""
-    got = iter(dense)
-    for out, idx in zip(outs, rest):
-        if not len(idx):
-            continue
-        res = next(got)
-        for key in out:
-            out[key][idx] = res[key]
-    return outs
-
-
-class _BandedUnits(MultiGradPlan):
-    """The device side of :class:`BandedMultiGradPlan`: the units the band kernels take, every segment with the half-width
-    ``halfwidth`` (sf_loglike_banded_multi_grad_batch_md).  A piece of a cut unit list in which no order requests anything is
-    the plain (dense) multi-order likelihood, as in :class:`MultiGradPlan`."""
-
-    def __init__(self, orders, mds, rows_list, requests, halfwidth, max_units=None):
-        self.halfwidth = int(halfwidth)
-        super().__init__(orders, mds, rows_list, requests, max_units=max_units)
-
-    def _halfwidths(self, nseg):
-        return (C.c_int * nseg)(*([self.halfwidth] * nseg))
-
-    def _workspace_bytes(self, segs, nseg, models):
-        idxs = self._orders_of(segs, nseg)
-        if not any(self.slots[i] for i in idxs):
-            return self.lib.sf_multi_workspace_bytes_md(segs, nseg, models)
-        return self.lib.sf_banded_multi_grad_workspace_bytes_md(segs, nseg, models, self._requests_array(idxs),
-                                                                self._halfwidths(nseg), self.stride)
-
-    def enqueue(self):
-        torch = _torch()
-        with torch.cuda.device(self.dev):
-            s = stream_ptr(self.dev)
-            q = self.quad
-            for (segs, nseg, u0, n, models), piece in zip(self.calls, self.pieces):
-                idxs = [i for i, _, _ in piece]
-                if not any(self.slots[i] for i in idxs):
-                    rc = self.lib.sf_loglike_multi_batch_md(segs, nseg, models, ptr(q[0][u0:u0 + n]), None, None,
-                                                            ptr(q[3][u0:u0 + n]), ptr(self.info[u0:u0 + n]), ptr(self.ws),
-                                                            self.ws.numel(), s)
-                    _lib.check(rc, "sf_loglike_multi_batch_md")
-                    continue
-                rc = self.lib.sf_loglike_banded_multi_grad_batch_md(
-                    segs, nseg, models, self._requests_array(idxs), self._halfwidths(nseg), ptr(q[0][u0:u0 + n]),
-                    ptr(q[3][u0:u0 + n]), ptr(self.info[u0:u0 + n]), ptr(self.grad[u0:u0 + n]), self.stride, ptr(self.ws),
-                    self.ws.numel(), s)
-                _lib.check(rc, "sf_loglike_banded_multi_grad_batch_md")
-
-    def collect(self):
-        """As :meth:`MultiGradPlan.collect`, without its retry: the band sweep's internal status is recomputed densely per
-        unit (:func:`rerouted_units`), not by a second run of the batch."""
-        lnl, log_scale = self.quad[0].cpu().numpy(), self.quad[3].cpu().numpy()
-        info, grad = self.info.cpu().numpy(), self.grad.cpu().numpy()
-        ends = np.cumsum(self.sizes)
-        return [dict(lnl=lnl[hi - n:hi], grad=grad[hi - n:hi, :k], log_scale=log_scale[hi - n:hi], info=info[hi - n:hi])
-                for n, hi, k in zip(self.sizes, ends, self.slots)]
-
-
-class BandedMultiGradPlan:
-    """:class:`MultiGradPlan` on the band + Woodbury solver: the likelihood of every (order x walker) unit and its gradient
-    in every requested slot from one keeping sweep per unit, all units of the device in one launch sequence
-    (sf_loglike_banded_multi_grad_batch_md).  ``orders``, ``mds``, ``rows_list`` (host rows or tensors) and ``requests`` as
-    for :class:`MultiGradPlan`; :meth:`collect` returns the same per-order dicts and :meth:`reduce` the same order sum.
-
-    Every unit's half-width bound is computed on the host (:meth:`DeviceOrder.halfwidth_bound`); the units whose bound fits
-    their order's LDS window form one group, and every segment is given the group's largest bound, so that a unit's bits do
-    not depend on how the unit list is cut.  solver: "banded" -- the other units are refused with INFO_BANDWIDTH (-inf and a
-    NaN row); "auto" -- they, the units the kernels flag -4 and units with the internal status -5 go through the dense
-    :func:`loglike_multi_grad` with just those rows and are merged back by (order, walker).  Status -5 is recomputed densely
-    under "banded" too, with the warning of :func:`finish_structured`."""
-
-    def __init__(self, orders, mds, rows_list, requests, solver="banded", max_units=None):
-        check_solver(solver, ("banded", "auto"))
-        if len(requests) != len(orders):
-            raise ValueError(f"multi-order gradient: {len(requests)} requests for {len(orders)} orders")
-        torch = _torch()
-        self.orders, self.mds, self.solver, self.max_units = list(orders), list(mds), solver, max_units
-        self.requests = [([int(c) for c in cols], bool(cov)) for cols, cov in requests]
-        self.slots = [len(cols) + (R.cov_grad_slots(md) if cov else 0) for (cols, cov), md in zip(self.requests, self.mds)]
-        if not any(self.slots):
-            raise ValueError("multi-order gradient: nothing to differentiate (no order requests a slot)")
-        self.rows = [np.atleast_2d(r.cpu().numpy() if torch.is_tensor(r) else np.asarray(r, dtype=np.float64)) for r in rows_list]
-        self.sizes = [int(r.shape[0]) for r in self.rows]
-        self.bounds = [o.halfwidth_bound(md, r) for o, md, r in zip(self.orders, self.mds, self.rows)]
-        self.fits = banded_units(self.bounds, self._windows())
-        self.idx = [np.nonzero(f)[0] for f in self.fits]
-        self.on_device = [i for i, idx in enumerate(self.idx) if idx.size]  # the orders that have a unit for the band kernels
-        self.halfwidth = max((int(self.bounds[i][self.idx[i]].max()) for i in self.on_device), default=0)
-        self.plan = None
-        # (a group in which no order requests a slot has nothing for the gradient call: its units are refused or go dense)
-        if self.on_device and any(self.slots[i] for i in self.on_device):
-            self.plan = self._units([self.orders[i] for i in self.on_device], [self.mds[i] for i in self.on_device],
-                                    [self.rows[i][self.idx[i]] for i in self.on_device],
-                                    [self.requests[i] for i in self.on_device], self.halfwidth, max_units=max_units)
-        else:
-            self.fits = [np.zeros(n, dtype=bool) for n in self.sizes]
-            self.idx, self.on_device = [np.zeros(0, dtype=np.int64)] * len(self.sizes), []
-        self.complete = all(f.all() for f in self.fits)  # every unit is in the device plan, in unit order
-        self.rerouted = None
-        self._out = None
-
-    # what a plan on other band kernels (:class:`BandedMultiFisherPlan`) states anew: the device side, the window its units must
-    # fit, a refused order's results and the dense call of the re-routed units
-    _units = _BandedUnits
-
-    def _windows(self):
-        """Per order, the largest half-width bound the band kernels of this plan take."""
-        return [o.banded_window_halfwidth() for o in self.orders]
-
-    def _refused(self, n, k):
-        return refused_output(n, dict(grad=(k,), log_scale=()))
-
-    def _dense(self, which, rest):
-        """The dense results of the walkers ``rest[i]`` of the orders ``which``, one dict with the keys of :meth:`_refused` each."""
-        sub = ([self.orders[i] for i in which], [self.mds[i] for i in which], [self.rows[i][rest[i]] for i in which])
-        if any(self.slots[i] for i in which):
-            dense = loglike_multi_grad(*sub, [self.requests[i] for i in which], max_units=self.max_units)
-        else:
-            dense = [dict(o, grad=np.zeros((len(o["lnl"]), 0))) for o in loglike_multi(*sub, max_units=self.max_units)]
-        return [{key: d[key] for key in ("lnl", "grad", "log_scale", "info")} for d in dense]
-
-    @property
-    def units(self):
-        return sum(self.sizes)
-
-    def enqueue(self):
-        """Launch only (no host synchronisation)."""
-        if self.plan is not None:
-            self.plan.enqueue()
-
-    def collect(self):
-        """Per order a dict of numpy arrays: lnl (B,), grad (B, slots of the order), log_scale (B,), info (B,), as
-        :meth:`MultiGradPlan.collect`; refused units have ``-inf``, NaN and INFO_BANDWIDTH."""
-        outs = []
-        for n, k in zip(self.sizes, self.slots):
-            outs.append(self._refused(n, k))
-        if self.plan is not None:
-            for i, got in zip(self.on_device, self.plan.collect()):
-                for key, v in got.items():
-                    outs[i][key][self.idx[i]] = v
-        internal = sum(int(np.count_nonzero(o["info"] == INFO_INTERNAL)) for o in outs)
-        if internal:
-            import warnings
-
-            warnings.warn(f"banded solver: internal status -5 for {internal} unit(s); recomputed densely", RuntimeWarning,
-                          stacklevel=2)
-        rest = rerouted_units(self.fits, [o["info"] for o in outs], self.solver)
-        which = [i for i, idx in enumerate(rest) if len(idx)]
-        self.rerouted = sum(len(idx) for idx in rest)
-        if which:
-            merge_units(outs, rest, self._dense(which, rest))
-        self._out = outs
-        return outs
-
-    def reduce(self, sources):
-        """The sum over the orders of a collected call, as :meth:`MultiGradPlan.reduce`: on the device
-        (sf_multi_grad_reduce) when every unit ran on the band kernels and none was re-routed, else by
-        :func:`reduce_orders_host` of the collected units -- the same rule, the same bits."""
-        if self._out is None:
-            raise RuntimeError("BandedMultiGradPlan.reduce: collect() first")
-        if len(set(self.sizes)) != 1:
-            raise ValueError(f"sf_multi_grad_reduce: the orders have {sorted(set(self.sizes))} walkers")
-        if self.complete and not self.rerouted:
-            return self.plan.reduce(sources)
-        return reduce_orders_host(np.stack([o["lnl"] for o in self._out]), np.stack([o["info"] for o in self._out]),
-                                  [o["grad"] for o in self._out], sources)
-
-
-def loglike_banded_multi_grad(orders, mds, rows_list, requests, solver="banded", max_units=None, sync=True):
-    """:func:`loglike_multi_grad` on the band solver (:class:`BandedMultiGradPlan`; ``solver``: "banded" or "auto")."""
-    plan = BandedMultiGradPlan(orders, mds, rows_list, requests, solver=solver, max_units=max_units)
-    plan.enqueue()
-    return plan.collect() if sync else plan
-
-
-class _BandedFisherUnits(_BandedUnits):
-    """The device side of :class:`BandedMultiFisherPlan`: the units the band kernels take, every segment with the half-width
-    ``halfwidth`` (sf_fisher_banded_multi_batch_md).  ``self.fisher``: (units, pmax, pmax), a unit's matrix in its leading
-    p_i x p_i block."""
-
-    def __init__(self, orders, mds, rows_list, requests, halfwidth, max_units=None):
-        super().__init__(orders, mds, rows_list, requests, halfwidth, max_units=max_units)
-        with _torch().cuda.device(self.dev):  # (the base class's gradient rows, units x pmax doubles, stay unused)
-            self.fisher = empty((self.units, self.stride, self.stride), self.dev)
-
-    def _workspace_bytes(self, segs, nseg, models):
-        idxs = self._orders_of(segs, nseg)
-        return self.lib.sf_fisher_banded_multi_workspace_bytes_md(segs, nseg, models, self._requests_array(idxs),
-                                                                  self._halfwidths(nseg))
-
-    def enqueue(self):
-        torch = _torch()
-        with torch.cuda.device(self.dev):
-            s = stream_ptr(self.dev)
-            q, ld = self.quad, self.stride
-            for (segs, nseg, u0, n, models), piece in zip(self.calls, self.pieces):
-                rc = self.lib.sf_fisher_banded_multi_batch_md(
-                    segs, nseg, models, self._requests_array([i for i, _, _ in piece]), self._halfwidths(nseg),
-                    ptr(q[0][u0:u0 + n]), ptr(q[3][u0:u0 + n]), ptr(self.info[u0:u0 + n]), ptr(self.fisher[u0:u0 + n]), ld, ld * ld,
-                    ptr(self.ws), self.ws.numel(), s)
-                _lib.check(rc, "sf_fisher_banded_multi_batch_md")
-
-    def collect(self):
-        """Per order a dict of numpy arrays: lnl (B,), fisher (B, p_i, p_i), info (B,).  No retry, as :meth:`_BandedUnits.collect`."""
-        lnl, info, fisher = self.quad[0].cpu().numpy(), self.info.cpu().numpy(), self.fisher.cpu().numpy()
-        ends = np.cumsum(self.sizes)
-        return [dict(lnl=lnl[hi - n:hi], fisher=np.ascontiguousarray(fisher[hi - n:hi, :k, :k]), info=info[hi - n:hi])
-                for n, hi, k in zip(self.sizes, ends, self.slots)]
-
-    def reduce(self, sources):
-        """The sum of the unit matrices over the orders on the device (sf_multi_fisher_reduce), of what a finished call left in
-        the plan's buffers; ``sources`` as for :meth:`MultiGradPlan.reduce`.  Returns numpy ``lnl (W,)``,
-        ``fisher (W, len(sources), len(sources))``, ``info (W,)``."""
-        torch = _torch()
-        if len(set(self.sizes)) != 1:
-            raise ValueError(f"sf_multi_fisher_reduce: the orders have {sorted(set(self.sizes))} walkers")
-        W, ncols, ld = self.sizes[0], len(sources), self.stride
-        col_ptr, col_src = column_map_csr(sources)
-        with torch.cuda.device(self.dev):
-            d_ptr, d_src = torch.from_numpy(col_ptr).to(self.dev), torch.from_numpy(col_src).to(self.dev)
-            lnl, fisher = empty((W,), self.dev), empty((W, max(ncols * ncols, 1)), self.dev)
-            info = empty((W,), self.dev, torch.int32)
-            rc = self.lib.sf_multi_fisher_reduce(len(self.sizes), W, ptr(self.quad[0]), ptr(self.info), ptr(self.fisher), ld, ld * ld,
-                                                 ptr(d_ptr), ptr(d_src), ncols, ptr(lnl), ptr(fisher), max(ncols * ncols, 1),
-                                                 ptr(info), stream_ptr(self.dev))
-            _lib.check(rc, "sf_multi_fisher_reduce")
-            return lnl.cpu().numpy(), fisher.cpu().numpy()[:, :ncols * ncols].reshape(W, ncols, ncols), info.cpu().numpy()
-
-
-def reduce_fisher_host(lnl, info, fishers, sources):
-    """sf_multi_fisher_reduce's rule on the host: ``lnl``, ``info`` (n_orders, W), ``fishers[i]`` (W, p_i, p_i) the unit matrices
-    of order i, ``sources[j]`` the ``(order, slot)`` pairs of label j (at most one per order).  Entry ``(a, b)``, ``a >= b``, is
-    the sum of ``fishers[i][:, slot_a, slot_b]`` over the orders i that appear in both labels' lists, ascending, ``s = f0; s = s +
-    f1; ...``, exactly 0.0 without a common order, and is mirrored; ``lnl`` and ``info`` as :func:`reduce_orders_host`; a walker
-    with a non-zero code gets ``-inf`` and a NaN matrix.  The same adds in the same order as the device: the same bits."""
-    total, _none, code = reduce_orders_host(lnl, info, [], [])
-    W, p = total.shape[0], len(sources)
-    per_order = {}
-    for j, src in enumerate(sources):
-        for i, slot in src:
-            labels, slots = per_order.setdefault(int(i), ([], []))
-            if j in labels:
-                raise ValueError(f"label {j} has two sources in order {int(i)}")
-            labels.append(j)
-            slots.append(int(slot))
-    F, seen = np.zeros((W, p, p)), np.zeros((p, p), dtype=bool)
-    for i in sorted(per_order):
-        la, sl = (np.asarray(v, dtype=np.intp) for v in per_order[i])
-        block = np.asarray(fishers[i], dtype=np.float64)[:, sl[:, None], sl[None, :]]
-        ix = np.ix_(la, la)
-        F[:, la[:, None], la[None, :]] = np.where(seen[ix], F[:, la[:, None], la[None, :]] + block, block)
-        seen[ix] = True
-    lower = np.tril_indices(p, -1)
-    F[:, lower[1], lower[0]] = F[:, lower[0], lower[1]]
-    bad = code != 0
-    F[bad] = np.nan
-    return total, F, code
-
-
-class BandedMultiFisherPlan(BandedMultiGradPlan):
-    """The Fisher information of the mean-flux parameters (:meth:`DeviceOrder.fisher_mean`) of every (order x walker) unit of
-    ONE device from one sweep per unit, all units in one launch sequence (sf_fisher_banded_multi_batch_md).  ``columns[i]``: the
-    columns of order i's parameter row (1 .. MEAN_GRAD_MAX_SLOTS).  The rules of :class:`BandedMultiGradPlan`, shared with it
-    -- half-width bounds on the host, one group at the group's largest bound, :func:`rerouted_units`, :func:`merge_units` --
-    with the window at the CALL's row count ``1 + m + max p_i``: the units that fit it go to the band kernels; under "banded" the
-    others are refused (INFO_BANDWIDTH, NaN), under "auto" they, the units flagged -4 and those with status -5 go, per order,
-    through the dense ``fisher_mean`` and are merged back by (order, walker); -5 is recomputed densely under "banded" too.
-    :meth:`collect`: per order a dict lnl (B,), fisher (B, p_i, p_i), info (B,)."""
-
-    _units = _BandedFisherUnits
-
-    def __init__(self, orders, mds, rows_list, columns, solver="banded", max_units=None):
-        columns = [[int(c) for c in cols] for cols in columns]
-        for i, cols in enumerate(columns):
-            if not 1 <= len(cols) <= MEAN_GRAD_MAX_SLOTS:
-                raise ValueError(f"multi-order Fisher information: order {i} has {len(cols)} columns, not 1 .. {MEAN_GRAD_MAX_SLOTS}")
-        self.pmax = max((len(cols) for cols in columns), default=0)
-        super().__init__(orders, mds, rows_list, [(cols, False) for cols in columns], solver=solver, max_units=max_units)
-
-    def _windows(self):
-        """The bound of a unit fits where the window takes this plan's largest column count (sf_fisher_banded_max_slots)."""
-        return [max((w for w in range(0, o.banded_window_halfwidth() + 1, 16) if o.fisher_banded_max_slots(w) >= self.pmax),
-                    default=-1) for o in self.orders]
-
-    def _refused(self, n, k):
-        return refused_output(n, dict(fisher=(k, k)))
-
-    def _dense(self, which, rest):
-        return [self.orders[i].fisher_mean(self.mds[i], self.rows[i][rest[i]], self.requests[i][0], "dense", self.max_units)
-                for i in which]
-
-    def reduce(self, sources):
-        """The sum of the unit matrices over the orders of a collected call: on the device (sf_multi_fisher_reduce) when every
-        unit ran on the band kernels and none was re-routed, else by :func:`reduce_fisher_host` -- the same rule, the same bits."""
-        if self._out is None:
-            raise RuntimeError("BandedMultiFisherPlan.reduce: collect() first")
-        if len(set(self.sizes)) != 1:
-            raise ValueError(f"sf_multi_fisher_reduce: the orders have {sorted(set(self.sizes))} walkers")
-        if self.complete and not self.rerouted:
-            return self.plan.reduce(sources)
-        return reduce_fisher_host(np.stack([o["lnl"] for o in self._out]), np.stack([o["info"] for o in self._out]),
-                                  [o["fisher"] for o in self._out], sources)
-
-
-def fisher_banded_multi(orders, mds, rows_list, columns, solver="banded", max_units=None, sync=True):
-    """The likelihood and the Fisher information of the mean-flux parameters for the (order x walker) units of several orders of
-    ONE device on the band solver (:class:`BandedMultiFisherPlan`; ``solver``: "banded" or "auto").  Returns its per-order
-    dicts; with ``sync=False`` the un-synchronised plan."""
-    plan = BandedMultiFisherPlan(orders, mds, rows_list, columns, solver=solver, max_units=max_units)
-    plan.enqueue()
-    return plan.collect() if sync else plan
-
-
-def collect_multi(quad, info, sizes):
-    host = fetch_results(quad, info)
-    ends = np.cumsum(sizes)
-    return [{key: v[hi - n:hi] for key, v in host.items()} for n, hi in zip(sizes, ends)]
 
 
 class DeviceOrder:

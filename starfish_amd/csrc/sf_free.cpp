@@ -380,7 +380,7 @@ extern "C" int sf_debug_emulator_grad_contract(const double* d_grid, int M, int 
 }
 
 // Recovery switch of the callers (process-global): after a batch came back SF_INFO_INTERNAL the host layer turns the
-// persistent-kernel sequence off and re-runs the batch on a launch sequence (starfish_amd/_device.py).
+// persistent-kernel sequence off and re-runs the batch on a launch sequence (starfish_amd/_runtime.py).
 extern "C" int sf_persistent_potrf(int enable) { return sf_set_persistent_potrf(enable); }
 extern "C" int sf_persistent_potrf_status(long long* h_out8) {
     if (!h_out8) {

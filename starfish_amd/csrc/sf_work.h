@@ -420,13 +420,18 @@ static MultiGradWork carve_multi_grad(const sf_segment* segs, int nseg, const sf
 // Then per segment, in segment order, the per-unit data of the parts it asks for with the order's own n (AW_MEAN: xs, fin,
 // mpart, dcoef, kdot, mudot, zdot; part) and, for a segment with mean slots and vsini, coef, for the reason carve_multi_grad
 // gives.  seg[i].stage points at the segment's units in the shared staging area.
-struct BandMultiGradWork {
-    int nrhs, n16, halfwidth, ldb;
-    bool any_cov;
-    double *band, *gram, *logdet_band, *gtab, *stage, *fac, *T, *M, *sigma, *M2, *stage2;
-    size_t sfac;  // doubles of one unit's kept factor
+// what the multi-order calls on the band solver share: the frame, the band, the sweep's outputs and the segments' own data
+struct BandMultiWork {
+    int n16, halfwidth, ldb;
+    double *band, *gram, *logdet_band, *gtab;
     std::vector<AppliedWork> seg;
     size_t bytes;
+};
+struct BandMultiGradWork : BandMultiWork {
+    int nrhs;
+    bool any_cov;
+    double *stage, *fac, *T, *M, *sigma, *M2, *stage2;
+    size_t sfac;  // doubles of one unit's kept factor
 };
 static BandMultiGradWork carve_band_multi_grad(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
                                                const sf_grad_request* reqs, const Layout& L, int n16, int halfwidth, int U, void* p,
@@ -488,11 +493,9 @@ static BandMultiGradWork carve_band_multi_grad(const sf_segment* segs, int nseg,
 // share it) and fcomp [U][pmax^2], the compact blocks of k_fisher_band.  Then per segment, in segment order, what the tangent
 // columns read per unit with the order's own n: xs, dcoef (vsini), kdot, mudot.  (No coef of its own: the columns are written on
 // the segment's lane, behind its chain, before the lane's next segment overwrites the Work's.)
-struct BandMultiFisherWork {
-    int nin, pmax, n16, halfwidth, ldb;
-    double *band, *lead, *logdet_band, *gtab, *buf, *gram, *twist, *fcomp;
-    std::vector<AppliedWork> seg;
-    size_t bytes;
+struct BandMultiFisherWork : BandMultiWork {
+    int nin, pmax;
+    double *lead, *buf, *twist, *fcomp;
 };
 static BandMultiFisherWork carve_band_multi_fisher(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
                                                    const sf_grad_request* reqs, const Layout& L, int n16, int halfwidth, int pmax, int U,

@@ -3,6 +3,7 @@ parameters, in every thawed label -- and the two L-BFGS-B searches on them (:mod
 import numpy as np
 
 from .. import _device as D
+from .. import _multi as M
 from .. import _map
 from .. import _rows as R
 
@@ -288,7 +289,7 @@ class Gradients:
                 raise ValueError("no thawed parameter to differentiate in")
             dev, md, rows = self._pack(P, update_caches=False)
             columns = self._mean_gradient_columns(dev, md) if mean else []
-            lnl, info = self._scatter_combined(grad, md, D.loglike_multi_grad([dev], [md], [rows], [(columns, bool(cov))])[0], columns)
+            lnl, info = self._scatter_combined(grad, md, M.loglike_multi_grad([dev], [md], [rows], [(columns, bool(cov))])[0], columns)
             return (lnl, grad, info) if return_info else (lnl, grad)
         if solver == covariance_solver != "dense" and self.mean_gradient_labels and self.gradient_labels:
             dev, md, rows = self._pack(P, update_caches=False)

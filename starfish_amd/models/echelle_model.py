@@ -260,7 +260,7 @@ class EchelleModel:
         synchronisation per device; devices work concurrently.  The sum over orders happens on the host (no
         collective).  Walkers that fail in any order get ``-inf``; ``info`` is the first non-zero per-order code.
         With ``return_orders`` the (n_orders, B) per-order values are returned too."""
-        from .. import _device as D
+        from .. import _multi as M
 
         P = np.atleast_2d(np.asarray(P, dtype=np.float64))
         B = P.shape[0]
@@ -317,8 +317,8 @@ class EchelleModel:
             for idxs in self._by_device(packed):  # enqueue everything first, synchronise afterwards
                 devs = [packed[i][0] for i in idxs]
                 mds = [packed[i][1] for i in idxs]
-                same = all(D.model_desc_key(m) == D.model_desc_key(mds[0]) for m in mds)
-                pending.append((idxs, D.loglike_multi(devs, mds[0] if same else mds, [packed[i][2] for i in idxs],
+                same = all(M.model_desc_key(m) == M.model_desc_key(mds[0]) for m in mds)
+                pending.append((idxs, M.loglike_multi(devs, mds[0] if same else mds, [packed[i][2] for i in idxs],
                                                       sync=False)))
             for idxs, plan in pending:
                 for i, out in zip(idxs, plan.collect()):
@@ -337,9 +337,9 @@ class EchelleModel:
     def _gradient_layout(self, solver=None):
         """Host logic of the gradient, no device: ``(labels, cols, requests, sources)``.  ``solver``: None -- every order's
         own ``solver`` must be "dense"; "dense", "banded" or "auto" -- the solver of the gradient call, whatever the orders'
-        own is (anything else: the ``ValueError`` of :func:`starfish_amd._device.check_solver`).  ``cols[i]``: the columns of a
+        own is (anything else: the ``ValueError`` of :func:`starfish_amd._runtime.check_solver`).  ``cols[i]``: the columns of a
         parameter vector that hold order i's own labels; ``requests[i] = (mean_columns, want_cov)``: what order i asks the
-        device for (:class:`starfish_amd._device.MultiGradPlan`); ``sources[j]``: the ``(order, slot)`` pairs of the
+        device for (:class:`starfish_amd._multi.MultiGradPlan`); ``sources[j]``: the ``(order, slot)`` pairs of the
         per-unit gradient rows that label j adds up, ascending in the order -- a unit's row holds its order's mean slots in
         :attr:`SpectrumModel.mean_gradient_labels` order, then all covariance slots of its descriptor.  A shared label has a
         source in every order, an ``order{i}:`` label one, ``Rv`` none.  Raises ``ValueError``, naming the order, for what
@@ -388,7 +388,7 @@ class EchelleModel:
                             bit; a walker with a unit whose covariance support exceeds the LDS window gets ``-inf``, a NaN
                             row and info = -4;
                 "auto"  -- banded for the units whose half-width bound fits the window, the dense call for the rest."""
-        from .. import _device as D
+        from .. import _multi as M
 
         labels, cols, requests, sources = self._gradient_layout(solver)
         banded = solver in ("banded", "auto")
@@ -400,10 +400,10 @@ class EchelleModel:
         pending = []
         for idxs in self._by_device(packed):  # enqueue everything first, synchronise afterwards
             if not any(requests[i][0] or requests[i][1] for i in idxs):  # nothing thawed in these orders: lnl only
-                pending.append((idxs, D.loglike_multi([packed[i][0] for i in idxs], [packed[i][1] for i in idxs],
+                pending.append((idxs, M.loglike_multi([packed[i][0] for i in idxs], [packed[i][1] for i in idxs],
                                                       [packed[i][2] for i in idxs], sync=False)))
                 continue
-            call, kw = (D.loglike_banded_multi_grad, dict(solver=solver)) if banded else (D.loglike_multi_grad, {})
+            call, kw = (M.loglike_banded_multi_grad, dict(solver=solver)) if banded else (M.loglike_multi_grad, {})
             pending.append((idxs, call([packed[i][0] for i in idxs], [packed[i][1] for i in idxs],
                                        [packed[i][2] for i in idxs], [requests[i] for i in idxs], sync=False, **kw)))
         unit_lnl = np.full((len(self.orders), B), -np.inf)
@@ -413,10 +413,10 @@ class EchelleModel:
             for i, out in zip(idxs, plan.collect()):
                 unit_lnl[i], unit_info[i] = out["lnl"], out["info"]
                 unit_grad[i] = out.get("grad", unit_grad[i])
-        if len(pending) == 1 and isinstance(pending[0][1], (D.MultiGradPlan, D.BandedMultiGradPlan)):
+        if len(pending) == 1 and isinstance(pending[0][1], (M.MultiGradPlan, M.BandedMultiGradPlan)):
             lnl, grad, info = pending[0][1].reduce(sources)
         else:
-            lnl, grad, info = D.reduce_orders_host(unit_lnl, unit_info, unit_grad, sources)
+            lnl, grad, info = M.reduce_orders_host(unit_lnl, unit_info, unit_grad, sources)
         self.last_info = info
         out = (lnl, grad)
         if return_info:
@@ -499,8 +499,8 @@ class EchelleModel:
                             support exceeds the LDS window at the call's row count gets a NaN matrix and info = -4;
                 "auto"  -- banded for the units whose half-width bound fits that window, the dense call for the rest.
         The sum over the orders runs in ascending order index, on the device (``sf_multi_fisher_reduce``) when one band call
-        held every unit, else on the host by the same rule (:func:`starfish_amd._device.reduce_fisher_host`)."""
-        from .. import _device as D
+        held every unit, else on the host by the same rule (:func:`starfish_amd._multi.reduce_fisher_host`)."""
+        from .. import _multi as M
 
         labels, cols, columns, sources = self._fisher_layout(solver)
         P = np.atleast_2d(np.asarray(P, dtype=np.float64))
@@ -511,7 +511,7 @@ class EchelleModel:
         for idxs in self._by_device(packed):  # enqueue everything first, synchronise afterwards
             plan = None
             if solver in ("banded", "auto"):
-                plan = D.fisher_banded_multi([packed[i][0] for i in idxs], [packed[i][1] for i in idxs],
+                plan = M.fisher_banded_multi([packed[i][0] for i in idxs], [packed[i][1] for i in idxs],
                                              [packed[i][2] for i in idxs], [columns[i] for i in idxs], solver=solver, sync=False)
             pending.append((idxs, plan))
         unit = [None] * len(self.orders)
@@ -523,7 +523,7 @@ class EchelleModel:
         if len(pending) == 1 and pending[0][1] is not None:
             _lnl, fisher, info = pending[0][1].reduce(sources)
         else:
-            _lnl, fisher, info = D.reduce_fisher_host(np.stack([u["lnl"] for u in unit]), np.stack([u["info"] for u in unit]),
+            _lnl, fisher, info = M.reduce_fisher_host(np.stack([u["lnl"] for u in unit]), np.stack([u["info"] for u in unit]),
                                                       [u["fisher"] for u in unit], sources)
         self.last_info = info
         out = (fisher,)

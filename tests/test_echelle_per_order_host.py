@@ -190,3 +190,21 @@ def test_constructor_takes_per_order_as_a_keyword():
         EchelleModel(emu, data, gp, per_order=["logg"], **c)
     plain = EchelleModel(emu, data, gp, **c)
     assert plain.per_order is None and plain.labels == synth.LABELS
+
+
+def test_cut_units_keeps_unit_order_and_never_exceeds_the_cap():
+    """The cut of a multi-order unit list into calls (starfish_amd._multi.cut_units): pieces of ``(order, lo, hi)``."""
+    from starfish_amd._multi import cut_units
+
+    assert cut_units([3, 3, 3], 4) == [[(0, 0, 3), (1, 0, 1)], [(1, 1, 3), (2, 0, 2)], [(2, 2, 3)]]
+    for sizes in ([3, 3, 3], [1], [5, 1, 7, 2], [64, 130, 180, 96]):
+        total = sum(sizes)
+        units = [(i, u) for i, n in enumerate(sizes) for u in range(n)]
+        for cap in (total, total + 9):  # cap >= total: one piece of whole orders
+            assert cut_units(sizes, cap) == [[(i, 0, n) for i, n in enumerate(sizes)]]
+        assert cut_units(sizes, 1) == [[(i, u, u + 1)] for i, u in units]  # cap = 1: one unit per piece
+        for cap in range(1, total + 1):
+            pieces = cut_units(sizes, cap)
+            assert [(i, u) for piece in pieces for i, lo, hi in piece for u in range(lo, hi)] == units  # each once, in order
+            counts = [sum(hi - lo for _, lo, hi in piece) for piece in pieces]
+            assert max(counts) <= cap and all(c == cap for c in counts[:-1]) and all(hi > lo for p in pieces for _, lo, hi in p)

@@ -11,7 +11,7 @@ from gpu_helpers import device_order, oracle_order, pack_rows
 from oracle import sf_oracle as O
 from per_order_cases import PER, ball, oracle_params, per_order_models
 from starfish_amd import _device as D
-from starfish_amd import _lib, samplers, synth
+from starfish_amd import _lib, _multi, samplers, synth
 from starfish_amd.models import EchelleModel
 
 import transform_cases as TC
@@ -42,7 +42,7 @@ def count_plans(monkeypatch):
             super().__init__(*a, **kw)
             plans.append(self)
 
-    monkeypatch.setattr(D, "MultiPlan", Counting)
+    monkeypatch.setattr(_multi, "MultiPlan", Counting)
     return plans
 
 

@@ -275,6 +275,7 @@ def test_python_methods_cut_into_chunks_give_the_bits_of_one_call(monkeypatch):
     with row 2 not positive definite (the raw row of the test above; no vector of logs gives a negative lambda_xi, so the
     raw rows are handed in behind _hyper_rows): -inf, a NaN gradient row and its info, the neighbours' bits untouched."""
     from starfish_amd import _device as D
+    from starfish_amd import _runtime
     from starfish_amd import _lib
 
     need = _lib.require_gpu().sf_emulator_loglike_grad_workspace_bytes
@@ -297,7 +298,7 @@ def test_python_methods_cut_into_chunks_give_the_bits_of_one_call(monkeypatch):
         with monkeypatch.context() as mp:
             mp.setattr(emu, "_hyper_rows", lambda _, rows=rows: rows)
             with monkeypatch.context() as cut:
-                cut.setattr(D, "units_that_fit", lambda *a, **k: 2)
+                cut.setattr(_runtime, "units_that_fit", lambda *a, **k: 2)
                 chunked = both()
                 assert emu._train_dev["ws_batch"].numel() == need(M, P, m, 2)
             whole = both()

@@ -376,6 +376,7 @@ def test_multiplan_collect_raises_when_the_internal_status_survives_the_retry(mo
     """Advisor, round 5: MultiPlan.collect re-ran an aborted call once and then handed a SECOND -5 back as an ordinary
     per-unit status.  Host logic only (no device): collect_multi is replaced by a fake that keeps returning -5."""
     from starfish_amd import _device as D
+    from starfish_amd import _multi
 
     class FakeLib:
         def __init__(self):
@@ -396,7 +397,7 @@ def test_multiplan_collect_raises_when_the_internal_status_survives_the_retry(mo
     plan.enqueue = lambda: calls.append("enqueue")
     bad = [dict(lnl=np.full(2, -np.inf), logdet=np.zeros(2), sqmah=np.zeros(2), log_scale=np.zeros(2),
                 info=np.full(2, D.INFO_INTERNAL, dtype=np.int32))]
-    monkeypatch.setattr(D, "collect_multi", lambda quad, info, sizes: bad)
+    monkeypatch.setattr(_multi, "collect_multi", lambda quad, info, sizes: bad)
     with pytest.warns(RuntimeWarning, match="no task of the launch completed for 25 ms; only 400 of its 512 workgroups had started"):
         with pytest.raises(RuntimeError, match="internal error"):
             plan.collect()
@@ -404,7 +405,7 @@ def test_multiplan_collect_raises_when_the_internal_status_survives_the_retry(mo
     # ... and a retry that succeeds is returned
     good = [dict(bad[0], info=np.zeros(2, dtype=np.int32), lnl=np.ones(2))]
     seq = iter([bad, good])
-    monkeypatch.setattr(D, "collect_multi", lambda quad, info, sizes: next(seq))
+    monkeypatch.setattr(_multi, "collect_multi", lambda quad, info, sizes: next(seq))
     with pytest.warns(RuntimeWarning, match="disabled for this whole process"):
         out = plan.collect()
     assert (out[0]["info"] == 0).all()
@@ -597,6 +598,7 @@ def test_units_that_fit_gives_the_three_chunk_sizes_it_replaced(monkeypatch):
 
 def test_grow_workspace_reuses_replaces_and_records_the_stream(monkeypatch):
     from starfish_amd import _device as D
+    from starfish_amd import _runtime
 
     class Buffer:
         def __init__(self, nbytes):
@@ -615,8 +617,8 @@ def test_grow_workspace_reuses_replaces_and_records_the_stream(monkeypatch):
         made.append(Buffer(nbytes))
         return made[-1]
 
-    monkeypatch.setattr(D, "workspace", factory)
-    monkeypatch.setattr(D, "current_stream", lambda dev: ("stream of", dev))
+    monkeypatch.setattr(_runtime, "workspace", factory)
+    monkeypatch.setattr(_runtime, "current_stream", lambda dev: ("stream of", dev))
     slot = dict(ws=None)
     first = D.grow_workspace(slot, "ws", 100, "dev0")
     assert first is slot["ws"] is made[0] and first.nbytes == 100 and first.recorded == [("stream of", "dev0")]

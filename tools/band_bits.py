@@ -1,5 +1,5 @@
 """Bit comparison of everything the band solver's host layer returns, for refactors of starfish_amd/csrc/sf_banded.cpp and of
-the dispatchers in starfish_amd/_device.py:
+the dispatchers in starfish_amd/_device.py and starfish_amd/_multi.py:
     SF_LIB_PATH=<one build> python tools/band_bits.py > a.json
     SF_LIB_PATH=<another>   python tools/band_bits.py > b.json
     python tools/band_bits.py --compare a.json b.json      -> lists the keys that differ, exit code 1 if any

@@ -20,6 +20,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from starfish_amd import _device as D  # noqa: E402
+from starfish_amd import _multi  # noqa: E402
 from starfish_amd import synth  # noqa: E402
 from starfish_amd.models import EchelleModel  # noqa: E402
 
@@ -81,7 +82,7 @@ class CountingPlan(D.MultiPlan):
         calls.append(len(self.calls))
 
 
-D.MultiPlan = CountingPlan
+_multi.MultiPlan = CountingPlan
 
 
 def release(*models):
