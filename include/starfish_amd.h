@@ -676,6 +676,20 @@ int sf_band_logdet_gram_batch(const double* d_band, int n, int halfwidth, int ld
                               int batch, const double* d_rhs, int nrhs, int ldr, int64_t rhs_stride,
                               double* d_logdet, double* d_gram, int* d_info, void* stream);
 
+/* Test aid: sf_band_logdet_gram_batch (same arguments up to d_info, same results) with the form of its sweep chosen by the
+ * caller.  form 0: one sweep per matrix, exactly what sf_band_logdet_gram_batch runs; no workspace (d_work may be NULL).
+ * form 1: the two-sided sweep of the likelihood (two half sweeps per matrix, the merge of what they leave of the separator, a
+ * third sweep over it); needs n a multiple of 16 and n / 16 >= 3 nbr - 1 block columns, nbr = max(3, (halfwidth + 31) / 16).
+ * form -1: whichever of the two sf_loglike_banded_batch would run for this n, halfwidth and batch on the current device.
+ * Forms 1 and -1 take a workspace of sf_debug_band_forms_workspace_bytes (0 for form 0 and for arguments the call refuses).
+ * d_info[b] (zeroed by the call) = 1-based column of the first non-positive pivot, in the caller's numbering in every form.
+ * SF_EINVAL, before anything is enqueued, for a null pointer, another form, a shape form 1 cannot take, nrhs outside 1 .. 48
+ * or a half-width beyond the LDS window at that nrhs; SF_ENOMEM for a short workspace.  Never synchronises. */
+size_t sf_debug_band_forms_workspace_bytes(int n, int halfwidth, int batch, int nrhs, int form);
+int sf_debug_band_forms_batch(const double* d_band, int n, int halfwidth, int ldb, int64_t stride, int batch, const double* d_rhs,
+                              int nrhs, int ldr, int64_t rhs_stride, double* d_logdet, double* d_gram, int* d_info, int form,
+                              void* d_work, size_t work_bytes, void* stream);
+
 /* Stand-alone banded solve, the counterpart of sf_band_logdet_gram_batch that keeps the factor: for the same band matrices
  * and right-hand sides (nrhs in 1 .. 48) returns d_x[b*x_stride + r*ldx + i] = (A^-1 rhs_r)_i, i < n  (scipy.linalg.
  * cholesky_banded + cho_solve_banded), d_logdet[b] and, if d_gram is not NULL, the same Gram matrix.  d_band is not

@@ -295,6 +295,12 @@ SIGNATURES = {
         C.c_int,
         [_VP, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, _VP, C.c_int, C.c_int, C.c_int64, _VP, _VP, _VP, _VP],
     ),
+    "sf_debug_band_forms_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sf_debug_band_forms_batch": (
+        C.c_int,
+        [_VP, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, _VP, C.c_int, C.c_int, C.c_int64, _VP, _VP, _VP, C.c_int, _VP,
+         C.c_size_t, _VP],
+    ),
     "sf_band_solve_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "sf_band_solve_batch": (
         C.c_int,

@@ -176,8 +176,52 @@ extern "C" int sf_band_logdet_gram_batch(const double* d_band, int n, int halfwi
                                           d_logdet, d_gram, d_info), s);
 }
 
-// ----------------------------------------------------------------------------------- the full banded solve
 // what sf_band_solve_batch refuses before it touches the device; who == NULL: silently (the size query)
+static int band_solve_shape_ok(const char* who, int n, int halfwidth, int batch, int nrhs);
+// The same sweep with its form chosen by the caller (the stage tests): 0 = one sweep per matrix, what sf_band_logdet_gram_batch
+// runs; 1 = two half sweeps, merge and separator; -1 = what the likelihood's head would run for this order, half-width and batch
+static const char* const DEBUG_FORMS = "sf_debug_band_forms_batch";
+static int debug_band_forms_ok(bool say, int n, int halfwidth, int batch, int nrhs, int form) {
+    if (form < -1 || form > 1) {
+        if (say) sf_set_error("%s: form=%d must be 0 (single sweep), 1 (two half sweeps) or -1 (the likelihood's choice)", DEBUG_FORMS, form);
+        return SF_EINVAL;
+    }
+    SF_CHECK(band_solve_shape_ok(say ? DEBUG_FORMS : nullptr, n, halfwidth, batch, nrhs));
+    if (form == 1 && (n % BB || !sfb_twist_fits(n / BB, sfb_nbr(halfwidth)))) {
+        if (say)
+            sf_set_error("%s: two half sweeps need whole 16-row blocks and at least %d of them at half-width %d (n=%d)", DEBUG_FORMS,
+                         3 * sfb_nbr(halfwidth) - 1, halfwidth, n);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_debug_band_forms_workspace_bytes(int n, int halfwidth, int batch, int nrhs, int form) {
+    if (debug_band_forms_ok(false, n, halfwidth, batch, nrhs, form) || form == 0) return 0;
+    return sizeof(double) * sfb_twist_carve(nullptr, halfwidth, nrhs, batch).doubles;
+}
+extern "C" int sf_debug_band_forms_batch(const double* d_band, int n, int halfwidth, int ldb, int64_t stride, int batch,
+                                         const double* d_rhs, int nrhs, int ldr, int64_t rhs_stride, double* d_logdet, double* d_gram,
+                                         int* d_info, int form, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_band || !d_rhs || !d_logdet || !d_gram || !d_info || (form != 0 && !d_work)) {
+        sf_set_error("%s: null pointer", DEBUG_FORMS);
+        return SF_EINVAL;
+    }
+    SF_CHECK(debug_band_forms_ok(true, n, halfwidth, batch, nrhs, form));
+    if (ldb < halfwidth + 1 || ldr < n) {
+        sf_set_error("%s: ldb=%d < halfwidth + 1, or ldr=%d < n (%d)", DEBUG_FORMS, ldb, ldr, n);
+        return SF_EINVAL;
+    }
+    SF_CHECK(work_fits(work_bytes, sf_debug_band_forms_workspace_bytes(n, halfwidth, batch, nrhs, form)));
+    hipStream_t s = (hipStream_t)stream;
+    SF_HIP(hipMemsetAsync(d_info, 0, sizeof(int) * (size_t)batch, s));
+    const sf_band_call k = band_call(d_band, stride, ldb, halfwidth, n, batch, sf_band_rhs{d_rhs, rhs_stride, ldr, nrhs, nullptr, 0},
+                                     d_logdet, d_gram, d_info);
+    if (form == 1 || (form == -1 && sf_band_twisted_applicable(n, halfwidth, batch)))
+        return sf_launch_band_forms_twisted(k, (double*)d_work, s);
+    return sf_launch_band_forms(k, s);
+}
+
+// ----------------------------------------------------------------------------------- the full banded solve
 static int band_solve_shape_ok(const char* who, int n, int halfwidth, int batch, int nrhs) {
     if (n <= 0 || batch <= 0 || halfwidth < 0 || nrhs < 1 || nrhs > 48) {
         if (who) sf_set_error("%s: n=%d, batch=%d must be positive, halfwidth=%d >= 0, nrhs=%d in 1 .. 48", who, n, batch, halfwidth, nrhs);
