@@ -440,6 +440,30 @@ int sf_local_scan_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const do
  * a call of sf_local_scan_batch with the same ctx, model, B, d_params and ncand left behind. */
 int sf_debug_local_scan_contract(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, const double* d_cand,
                                  int ncand, double* d_out, void* d_work, size_t work_bytes, void* stream);
+/* The same scan on the band + Woodbury solver: no N x N matrix anywhere.  With C = Bd + Y^T Y, Sigma = Bd^-1 and Vs = Bd^-1 Y^T
+ * L_S^-T, W = C^-1 = Sigma - Vs Vs^T.  The head is the one sf_diagnose_banded_batch runs for the walker's own residual with
+ * d_cinv_diag (band filled entry by entry, keeping sweep, capacitance step, backward sweep, alpha, the selected inversion, Vs),
+ * run at the widest half-width the LDS window takes for the 1 + m rows, wmax = 144 / 128 / 112 for m <= 15 / 31 / 32, WHATEVER
+ * the model's own support is: the selected inversion is exact on the band it is run at and a band wider than the kernels' support
+ * holds zeros, so every patch of at most sf_local_scan_banded_max_patch = wmax + 1 pixels is served exactly, and a candidate's
+ * numbers depend on m alone -- not on the other candidates, the batch, the chunk or a group of walkers (same bits).  Behind the
+ * head the 64 x 64 tiles of W within 3 blocks of the diagonal are formed from the band of Sigma and the rank-m product on the fp64
+ * matrix cores, then the candidates run as in sf_local_scan_batch.  d_out as there (values agree to rounding, not bit for bit);
+ * d_lnl and d_info (both may be NULL) as the banded head leaves them: a walker whose covariance support exceeds wmax gets
+ * SF_INFO_BANDWIDTH, -inf and NaN rows.  A candidate with no pixel in reach gets exactly 0, 0, 0; one whose patch is wider than
+ * wmax + 1 pixels, or whose mu or sigma is not positive and finite, gets NaN for every walker; d_info[b] != 0 gives NaN rows.  The
+ * model may have no global and no local kernel (Bd is then diagonal).
+ * sf_local_scan_banded_max_patch: wmax + 1; 0: no window (m too large) or a grid that is not strictly increasing; SF_EINVAL: bad
+ * context or model.  SF_EINVAL, the message starting with the call's name, before anything is enqueued (size query 0): B or ncand
+ * outside 1 .. 65535; a bad context or model; a grid that is not strictly increasing; no window for 1 + m rows (use
+ * sf_local_scan_batch); null d_params, d_cand, d_out or d_work.  A short workspace: SF_ENOMEM.  d_work:
+ * sf_local_scan_banded_workspace_bytes: the workspace of sf_diagnose_banded_batch for one right-hand side with want_cinv_diag at
+ * wmax, two ints per candidate and, per walker, ceil(n / 64) * (2 min(ceil(n / 64) - 1, 3) + 1) tiles of 64 x 64 doubles -- linear
+ * in n.  Never synchronises. */
+int sf_local_scan_banded_max_patch(const sf_ctx* ctx, const sf_model_desc* model);
+size_t sf_local_scan_banded_workspace_bytes(const sf_ctx* ctx, const sf_model_desc* model, int B, int ncand);
+int sf_local_scan_banded_batch(sf_ctx* ctx, const sf_model_desc* model, int B, const double* d_params, const double* d_cand, int ncand,
+                               double* d_out, double* d_lnl, int* d_info, void* d_work, size_t work_bytes, void* stream);
 
 /* The likelihood and its gradient in the mean-flux parameters: vsini (column 0 of the parameter row), vz (1), log_scale (2), the
  * emulator grid parameters, the Chebyshev coefficients and Av.  They enter through the flux f, the scaled emulator rows X and

@@ -50,6 +50,21 @@ def local_scan_patches(wave, cand):
     return lo, hi
 
 
+def local_scan_route(solver, patch_pixels, limit):
+    """Which solver a scan of candidates with ``patch_pixels`` pixels each goes to when ``solver`` is "banded" or "auto" and the
+    band solver serves patches of at most ``limit`` pixels (:meth:`DeviceOrder.local_scan_banded_max_patch`; 0: it does not take
+    the order).  "auto" with a candidate beyond the limit, or without one, is "dense" for the whole call; "banded" without a limit
+    is a ``ValueError`` (with one, the device marks the candidates beyond it NaN).  Pure host logic."""
+    check_solver(solver, ("banded", "auto"))
+    wide = bool(np.any(np.asarray(patch_pixels) > limit))
+    if solver == "auto":
+        return "dense" if limit < 1 or wide else "auto"
+    if limit < 1:
+        raise ValueError('the band solver does not take this order (no LDS window for its 1 + m rows, or a wavelength grid that is '
+                         'not strictly increasing): use solver="dense" or "auto"')
+    return "banded"
+
+
 def band_halfwidth_bound(wave, rows, n_grid, has_global, n_local, n_cheb):
     """Per-walker upper bound on max|i-j| over the non-zero entries of the structured part of the
     covariance (global Matern taper r0 = 6 ls, Starfish/models/kernels.py:29; local patches r0 = 4 sigma,
@@ -776,20 +791,17 @@ class DeviceOrder:
     def local_scan_workspace_bytes(self, md, B, ncand):
         return self._size_query("local_scan_", md, B, ncand)
 
-    def local_scan(self, md, params, cand, max_chunk=None):
-        """The score scan for a NEW local kernel at amplitude 0 (sf_local_scan_batch): for every walker and every candidate
-        ``cand[q] = (mu, sigma in km/s)``, shared by the walkers, ``quad = alpha^T k alpha``, ``trace = tr(C^-1 k)`` and ``fisher =
-        1/2 tr(C^-1 k C^-1 k)`` with ``k`` the matrix a local kernel of that centre and width adds at amplitude 1 and ``alpha = C^-1
-        r``: ``1/2 (quad - trace)`` is the derivative of lnL in the new amplitude, ``fisher`` its information.  params: (B,
-        stride) rows as for :meth:`loglike`; the model may have no structured kernel at all.  Returns dict of numpy arrays: quad,
-        trace, fisher (B, ncand) -- zeros for a candidate with no pixel in reach, NaN for one whose patch is wider than
-        LOCAL_SCAN_MAX_PATCH pixels and for walkers with info != 0 --, lnl (B,) and info (B,) with :meth:`loglike`'s bits.  The
-        dense factor only.  Chunked and retried like :meth:`loglike_grad`; a candidate's numbers are the same bits whatever the
-        chunk, the batch and the other candidates are."""
+    def local_scan_banded_max_patch(self, md):
+        """Widest patch in pixels that :meth:`local_scan` serves on the band solver (sf_local_scan_banded_max_patch): the widest
+        half-width of the LDS window for the order's 1 + m rows, plus one; 0: the band solver does not take this order."""
+        return max(int(self.lib.sf_local_scan_banded_max_patch(self.ctx, C.byref(md))), 0) if self.n else 0
+
+    def local_scan_banded_workspace_bytes(self, md, B, ncand):
+        return self._size_query("local_scan_banded_", md, B, ncand)
+
+    def _local_scan_call(self, name, md, params, cand, max_chunk, workspace_bytes):
+        """:meth:`_run_chunked` for ``sf_<name>(ctx, &md, B, P, cand, ncand, out, lnl, info, ws, ...)``: the two scans."""
         torch = _torch()
-        cand = np.ascontiguousarray(np.asarray(cand, dtype=np.float64))
-        if cand.ndim != 2 or cand.shape[1] != 2 or not cand.shape[0]:
-            raise ValueError(f"cand of shape {cand.shape}: expected (ncand, 2) rows of mu, sigma with ncand >= 1")
         ncand = int(cand.shape[0])
         with torch.cuda.device(self.dev):
             P = self._rows(params)
@@ -807,8 +819,50 @@ class DeviceOrder:
                 return res
 
             # (a size of 0: the call refuses its arguments and says why -- it gets a workspace that is not NULL to say it)
-            size = lambda units: max(self.local_scan_workspace_bytes(md, units, ncand), 256)  # noqa: E731
-            return self._run_chunked("local_scan_batch", md, P, max_chunk, size, buffers, args, named)
+            size = lambda units: max(workspace_bytes(md, units, ncand), 256)  # noqa: E731
+            return self._run_chunked(name, md, P, max_chunk, size, buffers, args, named)
+
+    def local_scan(self, md, params, cand, max_chunk=None, solver="dense"):
+        """The score scan for a NEW local kernel at amplitude 0 (sf_local_scan_batch): for every walker and every candidate
+        ``cand[q] = (mu, sigma in km/s)``, shared by the walkers, ``quad = alpha^T k alpha``, ``trace = tr(C^-1 k)`` and ``fisher =
+        1/2 tr(C^-1 k C^-1 k)`` with ``k`` the matrix a local kernel of that centre and width adds at amplitude 1 and ``alpha = C^-1
+        r``: ``1/2 (quad - trace)`` is the derivative of lnL in the new amplitude, ``fisher`` its information.  params: (B,
+        stride) rows as for :meth:`loglike`; the model may have no structured kernel at all.  Returns dict of numpy arrays: quad,
+        trace, fisher (B, ncand) -- zeros for a candidate with no pixel in reach, NaN for one whose patch is wider than
+        LOCAL_SCAN_MAX_PATCH pixels and for walkers with info != 0 --, lnl (B,) and info (B,) with :meth:`loglike`'s bits.
+        Chunked and retried like :meth:`loglike_grad`; a candidate's numbers are the same bits whatever the chunk, the batch and
+        the other candidates are.
+
+        solver: "dense"  -- the dense factor and the tiles of its inverse (sf_local_scan_batch);
+                "banded" -- band + rank-m Woodbury solve and the selected inversion at the LDS window's widest half-width, whatever
+                            the walkers' own support (sf_local_scan_banded_batch): all walkers in one group, values agree with the
+                            dense call to rounding; a candidate whose patch is wider than :meth:`local_scan_banded_max_patch`
+                            pixels is NaN for every walker; walkers whose covariance support exceeds that half-width come back
+                            with info = -4, lnl = -inf and NaN rows;
+                "auto"   -- if a candidate's patch (:func:`local_scan_patches`) is wider than the banded limit, or the band solver
+                            does not take the order, the whole call is the dense one (one factorisation serves every candidate:
+                            splitting the list would pay for both); otherwise banded, with the walkers that do not fit, and those
+                            with the internal status -5, through the dense call (:func:`finish_structured`)."""
+        check_solver(solver)
+        cand = np.ascontiguousarray(np.asarray(cand, dtype=np.float64))
+        if cand.ndim != 2 or cand.shape[1] != 2 or not cand.shape[0]:
+            raise ValueError(f"cand of shape {cand.shape}: expected (ncand, 2) rows of mu, sigma with ncand >= 1")
+        if solver != "dense":
+            limit = self.local_scan_banded_max_patch(md)
+            lo, hi = local_scan_patches(self._keep[0], cand)
+            solver = local_scan_route(solver, hi - lo + 1, limit)
+        if solver == "dense":
+            return self._local_scan_call("local_scan_batch", md, params, cand, max_chunk, self.local_scan_workspace_bytes)
+        rows, hw = self._host_rows_and_bound(md, params)
+        fits = hw <= limit - 1
+        out = refused_output(rows.shape[0], {key: (cand.shape[0],) for key in ("quad", "trace", "fisher")})
+        idx = np.nonzero(fits)[0]
+        if idx.size:
+            got = self._local_scan_call("local_scan_banded_batch", md, rows[idx], cand, max_chunk,
+                                        self.local_scan_banded_workspace_bytes)
+            for key, v in got.items():
+                out[key][idx] = v
+        return finish_structured(out, fits, solver, lambda rest: self.local_scan(md, rows[rest], cand, max_chunk))
 
     def loglike_device(self, md, P_dev, out_lnl, info=None):
         """Enqueue-only variant for bench.py: device tensors in/out, no synchronisation."""

@@ -185,6 +185,12 @@ SIGNATURES = {
         C.c_int,
         [_VP, C.POINTER(ModelDesc), C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_size_t, _VP],
     ),
+    "sf_local_scan_banded_max_patch": (C.c_int, [_VP, C.POINTER(ModelDesc)]),
+    "sf_local_scan_banded_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int]),
+    "sf_local_scan_banded_batch": (
+        C.c_int,
+        [_VP, C.POINTER(ModelDesc), C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP, _VP, C.c_size_t, _VP],
+    ),
     "sf_loglike_mean_grad_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int]),
     "sf_loglike_mean_grad_batch": (
         C.c_int,

@@ -512,10 +512,36 @@ extern "C" size_t sf_diagnose_banded_workspace_bytes(const sf_ctx* c, const sf_m
                            carve(c, mdl, B, nullptr, 0, false).bytes).bytes;
 }
 // The likelihood's head with a keeping sweep over [R; Y] (or the gradient call's [r; Y]), the backward sweep and the mix for
-// k right-hand sides: alpha.  The band is filled entry by entry: on a log-uniform grid the likelihood's table of the global
-// kernel per diagonal (k_band_gtab) is off by the rounding of the grid, ~3e-11 in r, which a narrow kernel turns into element
-// errors far beyond the 1e-13 that diag(C^-1) is held to against the oracle's matrix; the likelihood's 1e-10 does not notice.  Then what is asked for: the selected inversion, Vs and the read-out of diag(C^-1); the diagonal
-// of C; the split of alpha by covariance component
+// k right-hand sides: alpha in the staging area.  The band is filled entry by entry: on a log-uniform grid the likelihood's table
+// of the global kernel per diagonal (k_band_gtab) is off by the rounding of the grid, ~3e-11 in r, which a narrow kernel turns
+// into element errors far beyond the 1e-13 that diag(C^-1) is held to against the oracle's matrix; the likelihood's 1e-10 does not
+// notice.  On a workspace carved with want_cinv_diag, behind them: the selected inversion (g.sigma) and Vs (g.vs).
+// (sf_diagnose_banded_batch; sf_local_scan_banded_batch with the walker's own residual)
+static int banded_diag_head(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int halfwidth, const double* d_rhs,
+                            int nrhs, int ldr, int64_t rhs_stride, double* d_flux, const Work& w, const BandDiagWork& g,
+                            hipStream_t s) {
+    const BandWork& bw = g.bw;
+    const AppliedWork& aw = g.aw;
+    const BandHeadRhs own = {d_rhs, nrhs, ldr, rhs_stride, g.rhs, g.gram, g.zero};
+    SF_CHECK(banded_head(c, mdl, B, d_params, halfwidth, w, bw,
+                         BandHead{g.fac, nullptr, nullptr, nullptr, aw.lnl, aw.info, d_flux, d_rhs ? &own : nullptr, true}, s));
+    const int n16 = (c->n + 15) / 16 * 16, m = c->m, nin = nrhs + m;  // (the sweep's order: whole blocks)
+    const double* gram = d_rhs ? g.gram : bw.gram;
+    {
+        ProfScope ps(s, PS_SOLVE);
+        // T = Bd^-1 [R^T, Y^T], then alpha = T M in the staging area (with caller right-hand sides the mix is the first to
+        // look at the capacitance matrix: it completes the status)
+        SF_CHECK(sf_launch_band_back(g.fac, n16, halfwidth, B, nin, aw.info, g.T, c->npad, (int64_t)nin * c->npad, s));
+        SF_CHECK(sf_launch_band_mix(gram, w.Lw, nrhs, m, 0, aw.info, d_rhs ? aw.info : nullptr, g.T, c->n, c->npad, B, g.M, aw.stage, s));
+    }
+    if (g.sigma) {
+        // the band of Sigma = Bd^-1 and Vs of C^-1 = Sigma - Vs Vs^T
+        SF_CHECK(sf_launch_band_selinv(g.fac, n16, halfwidth, B, nin, aw.info, g.sigma, bw.ldb, (int64_t)n16 * bw.ldb, s));
+        SF_CHECK(sf_launch_band_vs(gram, nrhs, m, 0, aw.info, g.T, c->n, c->npad, B, g.M2, g.vs, s));
+    }
+    return SF_OK;
+}
+// That head, then what is asked for: the read-out of diag(C^-1); the diagonal of C; the split of alpha by covariance component
 extern "C" int sf_diagnose_banded_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, int halfwidth,
                                         const double* d_rhs, int nrhs, int ldr, int64_t rhs_stride, double* d_alpha,
                                         double* d_cinv_diag, double* d_cov_diag, double* d_comp, double* d_flux, int* d_info,
@@ -540,31 +566,87 @@ extern "C" int sf_diagnose_banded_batch(sf_ctx* c, const sf_model_desc* mdl, int
     const BandWork& bw = g.bw;
     const AppliedWork& aw = g.aw;
     hipStream_t s = (hipStream_t)stream;
-    const BandHeadRhs own = {d_rhs, nrhs, ldr, rhs_stride, g.rhs, g.gram, g.zero};
-    SF_CHECK(banded_head(c, mdl, B, d_params, halfwidth, w, bw,
-                         BandHead{g.fac, nullptr, nullptr, nullptr, aw.lnl, aw.info, d_flux, d_rhs ? &own : nullptr, true}, s));
-    const int n16 = (c->n + 15) / 16 * 16, m = c->m, nin = nrhs + m;  // (the sweep's order: whole blocks)
-    const double* gram = d_rhs ? g.gram : bw.gram;
-    {
-        ProfScope ps(s, PS_SOLVE);
-        // T = Bd^-1 [R^T, Y^T], then alpha = T M in the staging area (with caller right-hand sides the mix is the first to
-        // look at the capacitance matrix: it completes the status)
-        SF_CHECK(sf_launch_band_back(g.fac, n16, halfwidth, B, nin, aw.info, g.T, c->npad, (int64_t)nin * c->npad, s));
-        SF_CHECK(sf_launch_band_mix(gram, w.Lw, nrhs, m, 0, aw.info, d_rhs ? aw.info : nullptr, g.T, c->n, c->npad, B, g.M, aw.stage, s));
-    }
+    SF_CHECK(banded_diag_head(c, mdl, B, d_params, halfwidth, d_rhs, nrhs, ldr, rhs_stride, d_flux, w, g, s));
+    const int n16 = (c->n + 15) / 16 * 16, m = c->m;  // (the sweep's order: whole blocks)
     SF_CHECK(sf_launch_apply_export(aw.stage, aw.info, c->n, c->npad, nrhs, B, d_alpha, s));
-    if (d_cinv_diag) {
-        // the band of Sigma = Bd^-1 and Vs of C^-1 = Sigma - Vs Vs^T
-        SF_CHECK(sf_launch_band_selinv(g.fac, n16, halfwidth, B, nin, aw.info, g.sigma, bw.ldb, (int64_t)n16 * bw.ldb, s));
-        SF_CHECK(sf_launch_band_vs(gram, nrhs, m, 0, aw.info, g.T, c->n, c->npad, B, g.M2, g.vs, s));
+    if (d_cinv_diag)
         SF_CHECK(sf_launch_band_cinv_diag(g.sigma, bw.ldb, (int64_t)n16 * bw.ldb, g.vs, c->npad, (int64_t)m * c->npad, m, aw.info, c->n,
                                           B, d_cinv_diag, s));
-    }
     if (d_cov_diag)
         SF_CHECK(sf_launch_band_cov_diag(bw.band, bw.ldb, (int64_t)c->npad * bw.ldb, w.Y, c->npad, (int64_t)c->mpad * c->npad, m,
                                          aw.info, c->n, B, d_cov_diag, s));
     if (d_comp)  // K_k alpha with the Y, parameter rows and sigma the head's transform chain and fill worked on
         SF_CHECK(sf_launch_cov_matvec(fill_args(c, mdl, d_params, w), m, aw.stage, c->npad, nrhs, B, aw.yv, aw.info, d_comp, s));
     if (d_info) SF_HIP(hipMemcpyAsync(d_info, aw.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return SF_OK;
+}
+
+// ----------------------------------------------------------------------------------- score scan for new local kernels on the band solver
+static const char* const LOCAL_SCAN_BANDED = "sf_local_scan_banded_batch";
+// The half-width the head runs at: the widest the LDS window takes for the 1 + m rows [r; Y], whatever the model's own support is
+// (a wider band than the kernels need holds zeros: exact) -- so that a candidate's numbers depend on m alone, not on the other
+// candidates, the batch or the group.  -1: no window, or a grid the band solver does not take
+static int local_scan_banded_halfwidth(const sf_ctx* c) {
+    if (!c->n || !c->monotonic || c->m < 1 || c->m > 32) return -1;
+    return sf_band_max_halfwidth(1 + c->m);
+}
+extern "C" int sf_local_scan_banded_max_patch(const sf_ctx* c, const sf_model_desc* mdl) {
+    if (model_ok(c, mdl)) return SF_EINVAL;
+    return local_scan_banded_halfwidth(c) + 1;
+}
+// what the call refuses on its counts, context and model; say == false: silently (the size query)
+static int local_scan_banded_ok(const sf_ctx* c, const sf_model_desc* mdl, int B, int ncand, bool say) {
+    if (B <= 0 || B > 65535 || ncand < 1 || ncand > 65535) {
+        if (say) sf_set_error("%s: B=%d and ncand=%d must lie in 1 .. 65535", LOCAL_SCAN_BANDED, B, ncand);
+        return SF_EINVAL;
+    }
+    if (model_ok(c, mdl)) {
+        const std::string why = sf_last_error();
+        if (say) sf_set_error("%s: %s", LOCAL_SCAN_BANDED, why.c_str());
+        return SF_EINVAL;
+    }
+    if (!c->n || !c->monotonic) {
+        if (say)
+            sf_set_error("%s: the wavelength grid is not monotonic (the band solver needs a strictly increasing one, and a candidate's "
+                         "pixels are no contiguous patch)", LOCAL_SCAN_BANDED);
+        return SF_EINVAL;
+    }
+    if (local_scan_banded_halfwidth(c) < 0) {
+        if (say)
+            sf_set_error("%s: 1 + %d rows exceed the LDS window at every half-width (use sf_local_scan_batch)", LOCAL_SCAN_BANDED, c->m);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+extern "C" size_t sf_local_scan_banded_workspace_bytes(const sf_ctx* c, const sf_model_desc* mdl, int B, int ncand) {
+    if (local_scan_banded_ok(c, mdl, B, ncand, false)) return 0;
+    return carve_band_local_scan(c, mdl, B, local_scan_banded_halfwidth(c), ncand, nullptr, 0, carve(c, mdl, B, nullptr, 0, false).bytes)
+        .bytes;
+}
+// The diagnostics' head for the walker's own residual with the selected inversion and Vs, at the window's widest half-width;
+// behind it the tiles of W = Sigma - Vs Vs^T, the candidates' patches and k_ls_cand with the alpha in the staging area
+extern "C" int sf_local_scan_banded_batch(sf_ctx* c, const sf_model_desc* mdl, int B, const double* d_params, const double* d_cand,
+                                          int ncand, double* d_out, double* d_lnl, int* d_info, void* d_work, size_t work_bytes,
+                                          void* stream) {
+    SF_CHECK(local_scan_banded_ok(c, mdl, B, ncand, true));
+    if (!d_params || !d_cand || !d_out || !d_work) {
+        sf_set_error("%s: d_params, d_cand, d_out and d_work are required", LOCAL_SCAN_BANDED);
+        return SF_EINVAL;
+    }
+    const int wmax = local_scan_banded_halfwidth(c), n16 = (c->n + 15) / 16 * 16, m = c->m;
+    const Work w = carve(c, mdl, B, d_work, work_bytes, false);
+    const BandLocalScanWork g = carve_band_local_scan(c, mdl, B, wmax, ncand, d_work, work_bytes, w.bytes);
+    if (work_bytes < g.bytes) {  // (said here, so that the message names the call)
+        sf_set_error("%s: workspace too small: have %zu, need %zu", LOCAL_SCAN_BANDED, work_bytes, g.bytes);
+        return SF_ENOMEM;
+    }
+    const BandDiagWork& d = g.d;
+    hipStream_t s = (hipStream_t)stream;
+    SF_CHECK(banded_diag_head(c, mdl, B, d_params, wmax, nullptr, 1, 0, 0, nullptr, w, d, s));
+    SF_CHECK(sf_launch_local_scan_banded(fill_args(c, mdl, d_params, w), B, d.sigma, d.bw.ldb, (int64_t)n16 * d.bw.ldb, wmax, d.vs,
+                                         c->npad, (int64_t)m * c->npad, m, d.aw.stage, c->npad, d.aw.info, d_cand, ncand, g.patch,
+                                         g.wband, d_out, s));
+    if (d_lnl) SF_HIP(hipMemcpyAsync(d_lnl, d.aw.lnl, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    if (d_info) SF_HIP(hipMemcpyAsync(d_info, d.aw.info, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s));
     return SF_OK;
 }

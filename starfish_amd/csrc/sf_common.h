@@ -233,6 +233,13 @@ int sf_launch_fisher_cov(const sf_fill_args& f, int batch, const double* winv, c
 size_t sf_local_scan_band_doubles(int n, int batch);
 int sf_launch_local_scan(const sf_fill_args& f, int batch, const double* winv, const double* alpha, int ld_alpha, const int* info,
                          const double* cand, int ncand, int* patch, double* wband, double* out, hipStream_t s);
+// sf_band_local_scan.h: the same scan from the band solver: sigma (lds doubles per row, ssigma per matrix) the band of Bd^-1 at
+// the half-width wmax, vs[b * svs + c * ldv + i] the m columns of Vs (ldv >= n rounded up to whole 64-pixel blocks); wband:
+// sf_local_scan_banded_doubles(n, batch) doubles; a patch wider than wmax + 1 pixels: NaN for every walker
+size_t sf_local_scan_banded_doubles(int n, int batch);
+int sf_launch_local_scan_banded(const sf_fill_args& f, int batch, const double* sigma, int lds, int64_t ssigma, int wmax,
+                                const double* vs, int ldv, int64_t svs, int m, const double* alpha, int ld_alpha, const int* info,
+                                const double* cand, int ncand, int* patch, double* wband, double* out, hipStream_t s);
 // sf_grad_frame.h: the sum over the orders of a multi-order gradient (sf_multi_grad_reduce)
 struct sf_multi_reduce_args {
     const double* unit_lnl;   // [nseg * W]

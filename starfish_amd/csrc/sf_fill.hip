@@ -22,6 +22,7 @@
 //   sf_cov_grad.h     k_cov_grad: the likelihood's gradient in the covariance hyper-parameters
 //   sf_fisher_cov.h   k_fc_winv, k_fc_left, k_fc_contract, k_fc_sum: the Fisher information of those hyper-parameters
 //   sf_local_scan.h   k_ls_wband, k_ls_patch, k_ls_cand: the score scan for a new local kernel at amplitude 0
+//   sf_band_local_scan.h  k_ls_wband_banded: the band of C^-1 for that scan from the band solver's selected inversion and Vs
 //   sf_band_cov_grad.h  k_band_cov_grad: the same gradient contracted over the band of Bd^-1 and the low-rank correction
 //   sf_emu_grad.h     k_emu_grad: the emulator training likelihood's gradient in its hyper-parameters
 #include "sf_common.h"
@@ -37,5 +38,6 @@
 #include "sf_cov_grad.h"
 #include "sf_fisher_cov.h"
 #include "sf_local_scan.h"
+#include "sf_band_local_scan.h"
 #include "sf_band_cov_grad.h"
 #include "sf_emu_grad.h"

@@ -11,7 +11,8 @@
 //                a patch of SF_LS_MAXP pixels can span beyond its first.  Nothing else of W is formed.
 //   k_ls_patch   one workgroup per candidate: [lo, hi] = the pixels with sf_local_metric <= 4 sigma (1 + 1e-9), the margin of
 //                sf_block_support.  (0, -1): no pixel in reach; a candidate that is no kernel (mu or sigma not positive and
-//                finite) is marked wider than the limit.
+//                finite) or whose patch is wider than the launcher's limit (max_patch: SF_LS_MAXP here, less on the band solver,
+//                sf_band_local_scan.h) is marked wider than SF_LS_MAXP.
 //   k_ls_cand    one 4-wave workgroup per (walker, candidate), over the blocks Ib0 = lo / 64 .. Ib1 = hi / 64 of the patch.  Per
 //                pair (I, J <= I), ascending: M = sum_K W_IK k_KJ and N = sum_K k_IK W_KJ (= the transpose of sum_K W_JK k_KI)
 //                on v_mfma_f64_16x16x4_f64 through sf_inv_sweep, K ascending; the tiles of k are generated into LDS from the
@@ -39,6 +40,7 @@ struct sf_ls_args {
     int* patch;           // [ncand][2]: lo, hi
     double* wband;        // [batch][nbr][2 reach + 1][64][64]
     double* out;          // [batch][ncand][3]
+    int max_patch;        // widest patch in pixels that k_ls_patch lets through (<= SF_LS_MAXP; the last field: k_ls_cand's offsets stay)
 };
 size_t sf_local_scan_band_doubles(int n, int batch) {
     const size_t nbr = (size_t)(n + SF_LEAF - 1) / SF_LEAF;
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(256) void k_ls_patch(const sf_ls_args a) {
     if (tid == 0) {
         lo = min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3]));
         hi = max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3]));
-        if (!kernel) lo = 0, hi = SF_LS_MAXP;  // (wider than the limit: NaN)
+        if (!kernel || hi - lo + 1 > a.max_patch) lo = 0, hi = SF_LS_MAXP;  // (wider than the limit: NaN)
         else if (hi < 0) lo = 0;
         a.patch[2 * q] = lo, a.patch[2 * q + 1] = hi;
     }
@@ -200,6 +202,7 @@ int sf_launch_local_scan(const sf_fill_args& f, int batch, const double* winv, c
     a.winv = winv, a.alpha = alpha, a.ld_alpha = ld_alpha, a.info = info, a.cand = cand, a.ncand = ncand, a.batch = batch;
     a.nbr = (f.n + SF_LEAF - 1) / SF_LEAF, a.reach = a.nbr - 1 < SF_LS_REACH ? a.nbr - 1 : SF_LS_REACH;
     a.patch = patch, a.wband = wband, a.out = out;
+    a.max_patch = SF_LS_MAXP;
     if (f.n <= 0 || !f.monotonic || f.npad % SF_LEAF != 0 || f.npad < a.nbr * SF_LEAF || ld_alpha < f.n || batch < 1 ||
         batch > 65535 || ncand < 1 || ncand > 65535) {
         sf_set_error("local scan: n > 0 on a monotonic grid, npad a multiple of %d, batch and ncand in 1 .. 65535", SF_LEAF);

@@ -325,6 +325,27 @@ static BandDiagWork carve_band_diag(const sf_ctx* c, const sf_model_desc* mdl, i
     return g;
 }
 
+// sf_local_scan_banded_batch, behind the Work of the same call: carve_band_diag's layout for one right-hand side (the walker's
+// own residual) with want_cinv_diag at the half-width the head runs at, then what AW_LOCAL_SCAN holds: patch, two ints per
+// candidate, and wband, [B][blocks][2 reach + 1][64][64] doubles with reach = min(blocks - 1, 3) (sf_local_scan_banded_doubles)
+// -- linear in n
+struct BandLocalScanWork {
+    BandDiagWork d;
+    int* patch;
+    double* wband;
+    size_t bytes;
+};
+static BandLocalScanWork carve_band_local_scan(const sf_ctx* c, const sf_model_desc* mdl, int B, int halfwidth, int ncand, void* p,
+                                               size_t cap, size_t base_bytes) {
+    BandLocalScanWork g{};
+    g.d = carve_band_diag(c, mdl, B, halfwidth, 1, true, false, p, cap, base_bytes);
+    Carve k(p, cap, g.d.bytes);
+    g.patch = k.take<int>(2 * (size_t)ncand);
+    g.wband = k.take<double>(sf_local_scan_banded_doubles(c->n, B));
+    g.bytes = sf_align_up(k.off, 256);
+    return g;
+}
+
 // sf_fisher_banded_mean_batch with p = nslots columns, behind the Work of the same call: the band solver's buffers (carve_band;
 // its gram takes the leading (1 + m)^2 block for the capacitance step), the applied layout with nin = 1 + m + p rows per walker
 // (carve_applied with AW_MEAN: the staging area holds the sweep's rows [r; Y; J]; lnl, info, xs and the tangents' buffers), then

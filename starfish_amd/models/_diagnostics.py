@@ -221,9 +221,9 @@ class Diagnostics:
     # The score (Lagrange-multiplier) test for adding a local kernel of centre mu and width sigma at amplitude A = 0 to the
     # covariance as it stands: with k the matrix the kernel adds at amplitude 1, alpha = C^-1 r and W = C^-1,
     # U = d lnL / dA = 1/2 (alpha^T k alpha - tr(W k)), its information I = 1/2 tr(W k W k), z = U / sqrt(I), A = U / I.
-    def _scan_candidates(self, mus, sigmas, wl_range):
+    def _scan_candidates(self, mus, sigmas, wl_range, banded_limit=None):
         """The centres and widths of a scan, checked on the host: (mus, sigmas, (len(sigmas) * len(mus), 2) candidate rows,
-        width-major)."""
+        width-major).  ``banded_limit``: under ``solver="banded"`` the widest patch the band solver serves."""
         wave = np.asarray(self.data.wave, dtype=np.float64)
         mus = wave.copy() if mus is None else np.atleast_1d(np.asarray(mus, dtype=np.float64)).copy()
         if wl_range is not None:
@@ -241,15 +241,29 @@ class Diagnostics:
             q = int(wide[0])
             raise ValueError(f"candidate mu={float(cand[q, 0])!r}, sigma={float(cand[q, 1])!r} km/s reaches {int(hi[q] - lo[q] + 1)} pixels: the "
                              f"device scans patches of at most {D.LOCAL_SCAN_MAX_PATCH} pixels")
+        if banded_limit is not None:
+            wide = np.nonzero(hi - lo + 1 > banded_limit)[0]
+            if wide.size:
+                q = int(wide[0])
+                raise ValueError(f"candidate mu={float(cand[q, 0])!r}, sigma={float(cand[q, 1])!r} km/s reaches {int(hi[q] - lo[q] + 1)} pixels: the "
+                                 f"band solver scans patches of at most {int(banded_limit)} pixels (solver=\"auto\" takes the dense factor "
+                                 "for such a scan)")
         return mus, sigmas, cand
 
-    def _local_scan(self, P, mus, sigmas, wl_range):
+    def _local_scan(self, P, mus, sigmas, wl_range, solver=None):
         """The scan of the rows of ``P`` (None: the model's own state): the result dict with a leading walker axis, the status,
-        the centres and the widths.  No cache is updated."""
-        mus, sigmas, cand = self._scan_candidates(mus, DEFAULT_SCAN_SIGMAS if sigmas is None else sigmas, wl_range)
+        the centres and the widths.  No cache is updated.  ``solver``: None / "dense" is the call as it always was; "banded" /
+        "auto" are handed to :meth:`DeviceOrder.local_scan`, "banded" after the candidates were held to its patch limit."""
+        solver = self._gradient_solver(solver)
+        limit = None
+        if solver == "banded":  # (a size query of the order's context; nothing is enqueued)
+            dev, md, _ = self._pack(P, update_caches=False)
+            limit = dev.local_scan_banded_max_patch(md)
+        mus, sigmas, cand = self._scan_candidates(mus, DEFAULT_SCAN_SIGMAS if sigmas is None else sigmas, wl_range, limit)
         dev, md, rows = self._pack(P, update_caches=False)
+        kw = {} if solver == "dense" else {"solver": solver}
         step = 65535  # (candidates per device call)
-        parts = [dev.local_scan(md, rows, cand[q:q + step]) for q in range(0, len(cand), step)]
+        parts = [dev.local_scan(md, rows, cand[q:q + step], **kw) for q in range(0, len(cand), step)]
         shape = (rows.shape[0], len(sigmas), len(mus))
         quad, trace, fisher = (np.concatenate([p[key] for p in parts], axis=1).reshape(shape) for key in ("quad", "trace", "fisher"))
         score = 0.5 * (quad - trace)
@@ -259,7 +273,7 @@ class Diagnostics:
         res = {"score": score, "information": fisher, "z": z, "amp": amp, "quad": quad, "trace": trace}
         return res, parts[0]["info"], mus, sigmas
 
-    def local_kernel_scan(self, mus=None, sigmas=None, wl_range=None):
+    def local_kernel_scan(self, mus=None, sigmas=None, wl_range=None, solver=None):
         """The score test for one more local kernel, for every centre in ``mus`` (None: every pixel's wavelength; ``wl_range`` =
         (lo, hi) keeps the centres inside it) and every width in ``sigmas`` (km/s; None: 8, 15, 30), at the current parameters
         and with every kernel the model already has in the covariance (sf_local_scan_batch): dict of arrays of shape
@@ -267,26 +281,33 @@ class Diagnostics:
         ``score / sqrt(information)``, "amp" = ``score / information`` (one Newton step in A), and the pieces "quad" = ``alpha^T k
         alpha`` and "trace" = ``tr(C^-1 k)``.  "z" and "amp" are NaN where the information is 0 (no pixel within 4 sigma of the
         centre).  A candidate that reaches more pixels than the device scans is a ``ValueError`` before any device call.  Raises
-        as :meth:`log_likelihood` does; the model's state is not modified."""
-        res, info, _, _ = self._local_scan(None, mus, sigmas, wl_range)
+        as :meth:`log_likelihood` does; the model's state is not modified.
+
+        ``solver``: None or "dense" -- the dense factor, whatever the model's own ``solver`` is; "banded" -- the band + Woodbury
+        solver and its selected inversion (sf_local_scan_banded_batch; values agree with the dense scan to rounding), which serves
+        patches of at most :meth:`DeviceOrder.local_scan_banded_max_patch` pixels (145 for up to 15 emulator components): a wider
+        candidate is a ``ValueError`` before any device call; "auto" -- the band solver where it serves every candidate and the
+        walker's covariance fits its window, the dense factor otherwise."""
+        res, info, _, _ = self._local_scan(None, mus, sigmas, wl_range, solver)
         self._raise_for_info(info[0])
         return {key: v[0] for key, v in res.items()}
 
-    def local_kernel_scan_batch(self, P, mus=None, sigmas=None, wl_range=None, return_info=False):
+    def local_kernel_scan_batch(self, P, mus=None, sigmas=None, wl_range=None, return_info=False, solver=None):
         """:meth:`local_kernel_scan` for B walkers (rows of ``P`` in :attr:`labels` order) in one batched device pass: the same
         keys with a leading B axis.  Walkers that fail get NaN rows, ``info`` their codes (those of
-        :meth:`log_likelihood_batch`).  The model's own state is not modified."""
-        res, info, _, _ = self._local_scan(np.atleast_2d(np.asarray(P, dtype=np.float64)), mus, sigmas, wl_range)
+        :meth:`log_likelihood_batch`).  The model's own state is not modified.  ``solver``: as for :meth:`local_kernel_scan`."""
+        res, info, _, _ = self._local_scan(np.atleast_2d(np.asarray(P, dtype=np.float64)), mus, sigmas, wl_range, solver)
         return (res, info) if return_info else res
 
-    def propose_local_kernels(self, threshold=4.0, buffer=None, max_kernels=None, sigmas=None, mus=None, wl_range=None, P=None):
+    def propose_local_kernels(self, threshold=4.0, buffer=None, max_kernels=None, sigmas=None, mus=None, wl_range=None, P=None,
+                              solver=None):
         """Where the residual asks for local kernels: :meth:`local_kernel_scan` (with ``P``: :meth:`local_kernel_scan_batch`, ``z``
         and ``amp`` averaged over the walkers that evaluate), then per centre the width with the largest ``z``, the centres with
         ``z > threshold`` walked from the largest ``z`` down, a centre within ``buffer`` (the units of the wavelengths; None: the
         kept kernel's own reach of 4 sigma) of a kept one dropped, at most ``max_kernels`` kept (None: as many as the model can
         still take).  Returns the list, sorted by ``mu``, of ``{"mu", "log_amp", "log_sigma"}`` with ``log_amp = log(amp)`` of the
         Newton step: what ``model["local_cov"] = [*kernels_it_has, *model.propose_local_kernels()]`` takes, to be refined by
-        :meth:`train_covariance`.  The model is never changed.
+        :meth:`train_covariance`.  The model is never changed.  ``solver``: as for :meth:`local_kernel_scan`.
 
         ``z`` is a score statistic at FIXED remaining parameters, and one-sided: the amplitude of a kernel cannot be negative,
         so only an excess of correlated residual power (``z > 0``) proposes one; under the null ``z`` is about standard normal
@@ -296,11 +317,11 @@ class Diagnostics:
         kernel by Nelder-Mead on the full likelihood; here the covariance that is already fitted (global kernel, emulator,
         existing local kernels) is accounted for exactly, every pixel and width is tested, and nothing is refitted."""
         if P is None:
-            res, info, mus, sigmas = self._local_scan(None, mus, sigmas, wl_range)
+            res, info, mus, sigmas = self._local_scan(None, mus, sigmas, wl_range, solver)
             self._raise_for_info(info[0])
             z, amp = res["z"][0], res["amp"][0]
         else:
-            res, info, mus, sigmas = self._local_scan(np.atleast_2d(np.asarray(P, dtype=np.float64)), mus, sigmas, wl_range)
+            res, info, mus, sigmas = self._local_scan(np.atleast_2d(np.asarray(P, dtype=np.float64)), mus, sigmas, wl_range, solver)
             good = info == 0
             if not good.any():
                 raise ValueError("no walker of P evaluates: nothing to average")

@@ -4,7 +4,9 @@ kernels as they are.
     python tools/asm_diff.py old.s new.s [name-part ...]
 Per kernel: identical instruction stream or not (comments dropped, basic-block labels and the kernel's own symbol
 normalised; the mangled names of argument structs may differ between the files), and for the kernels that differ, exist on
-one side only or contain one of the name parts: VGPRs, occupancy, LDS bytes and scratch bytes of both sides."""
+one side only or contain one of the name parts: VGPRs, occupancy, LDS bytes and scratch bytes of both sides.  A kernel whose
+instructions are the same and whose descriptor directives alone moved (.amdhsa_kernarg_size of an argument struct that grew)
+is reported as such, with the directives."""
 import re
 import sys
 
@@ -33,5 +35,10 @@ for k in sorted(set(old) | set(new)):
     same += equal
     if not equal or any(part in k for part in sys.argv[3:]):
         state = "identical" if equal else "differs" if a and b else "only in " + (sys.argv[1] if a else sys.argv[2])
+        if a and b and not equal:  # (the kernel descriptor's directives sit inside the function: an argument struct that grew)
+            code = [[ln for ln in side[1] if not ln.startswith(".amdhsa_")] for side in (a, b)]
+            if code[0] == code[1]:
+                moved = sorted(set(a[1]) ^ set(b[1]))
+                state = f"identical instructions, descriptor directives differ ({', '.join(moved)})"
         print(f"{(a or b)[0]}: {state}; {a[2] if a else '-'} -> {b[2] if b else '-'}")
 print(f"{same} kernels with identical instruction streams, {len(set(old) | set(new)) - same} differ or exist on one side only")
