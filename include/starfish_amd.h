@@ -668,6 +668,48 @@ int sf_multi_fisher_reduce(int nseg, int W, const double* d_unit_lnl, const int*
                            int fisher_ld, int fisher_stride, const int32_t* d_col_ptr, const int32_t* d_col_src, int ncols,
                            double* d_lnl, double* d_fisher, int out_stride, int* d_info, void* stream);
 
+/* The score scan for a new local kernel (sf_local_scan_banded_batch) for the units of several orders in one pass on the band +
+ * Woodbury solver.  segs and models are exactly as for sf_loglike_banded_multi_grad_batch_md and must satisfy what it requires of
+ * them: contexts of one device with the same number of eigenspectra and grid dimensions, a good descriptor and parameter rows
+ * per segment, 1 .. 65535 units per segment, every wavelength grid strictly increasing.  There is no h_halfwidth: the frame's
+ * half-width is wmax, the widest the LDS window takes for the 1 + m rows [r; Y] (144 / 128 / 112 for m <= 15 / 31 / 32), the rule
+ * of the single-order call -- a wider band than a unit needs holds zeros, so every patch of at most wmax + 1 pixels is served
+ * exactly whatever the orders' own support is.  A unit whose covariance support exceeds wmax gets SF_INFO_BANDWIDTH, -inf and NaN
+ * rows.  Candidates: h_cand_ptr (HOST, nseg + 1 ascending ints); segment i scans d_cand[2 q], d_cand[2 q + 1] = mu, sigma in km/s
+ * for h_cand_ptr[i] <= q < h_cand_ptr[i + 1], between 1 and 65535 of them, shared by its walkers; the lists of two segments may
+ * differ in length.  d_out is unit-major, segment after segment: segment i starts at 3 * sum_{j<i} B_j ncand_j, and inside it
+ * d_out[(b * ncand_i + q) * 3 + 0 .. 2] = quad, trace, fisher of walker b and the segment's candidate q, as in the single-order
+ * call: exactly 0, 0, 0 with no pixel in reach; NaN for a patch wider than wmax + 1 pixels and for a centre or width that is not
+ * positive and finite; NaN rows where d_info[u] != 0.  d_lnl and d_info (units in segment order) are required, d_log_scale may be
+ * NULL.  Per segment, on the streams sf_loglike_multi_batch_md runs its chains on: the band fill, entry by entry, and the
+ * transform chain; once per chunk of segments, over all its units in one launch each: keeping sweep, capacitance step, lnl /
+ * info, backward sweep and mix (alpha), selected inversion and Vs; then per segment the launches of the single-order scan (tiles
+ * of W, patches, candidates) with the order's own n, wavelength grid and candidates.  ONE frame from the whole call, never from a
+ * chunk: the largest n rounded up to 16 rows (shorter orders: identity rows, zero right-hand sides), the largest npad, the row
+ * count 1 + m and wmax.  Values agree with sf_local_scan_banded_batch on the same order to rounding.  The call never
+ * synchronises and uses no atomics, every sum has a fixed order: a repeated call gives the same bits.
+ * sf_local_scan_banded_multi_max_patch: wmax + 1 for that frame; 0: no window for 1 + m rows, or a grid that is not strictly
+ * increasing; SF_EINVAL: a bad segment list.  SF_EINVAL, the message starting with the call's name and naming the segment, before
+ * anything is enqueued (size query 0): a bad segment list, context, model or batch; a grid that is not strictly increasing; no
+ * window; a null h_cand_ptr, a list that is not ascending from a non-negative start or a segment with a count outside 1 ..
+ * 65535; null d_cand, d_out, d_lnl, d_info or d_work.  SF_ENOMEM: the workspace is too small.  d_work:
+ * sf_local_scan_banded_multi_workspace_bytes_md(...): the workspace of sf_loglike_multi_batch_md without its matrices; per unit,
+ * in the common frame, the band, the kept factor, the band of Bd^-1, T of 1 + m rows, alpha and Vs; and ONE patch list and ONE set
+ * of tiles of W, sized for the segment that needs the most (the segments' scans run one after the other). */
+int sf_local_scan_banded_multi_max_patch(const sf_segment* segs, int nseg, const sf_model_desc* const* models);
+size_t sf_local_scan_banded_multi_workspace_bytes_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                                     const int* h_cand_ptr);
+int sf_local_scan_banded_multi_batch_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models, const double* d_cand,
+                                        const int* h_cand_ptr, double* d_out, double* d_lnl, double* d_log_scale, int* d_info,
+                                        void* d_work, size_t work_bytes, void* stream);
+/* The averaged proposal of a scan: for B walkers and ncand candidates with d_out[(b * ncand + q) * 3 + 0 .. 2] = quad, trace,
+ * fisher (one segment's slice of the call above, or the output of a single-order scan), per candidate q the score statistic z =
+ * U / sqrt(fisher) and the Newton step amp = U / fisher with U = (quad - trace) / 2 -- both NaN where fisher == 0 -- added over
+ * the walkers with d_info[b] == 0 in ascending b (s = v_0; s = s + v_1; ...) and divided by their number: d_mean[2 q] = mean z,
+ * d_mean[2 q + 1] = mean amp.  *d_count (DEVICE) receives the number of walkers used; with none the means are NaN.  One thread
+ * per candidate, plain adds, no atomics: a repeated call gives the same bits.  SF_EINVAL: a null pointer, B < 1, ncand < 1. */
+int sf_local_scan_mean(int B, int ncand, const double* d_out, const int* d_info, double* d_mean, int* d_count, void* stream);
+
 /* ---- structure-exploiting solver -----------------------------------
  * Same value as sf_loglike_batch, computed without ever forming the N x N matrix: the covariance of
  * spectrum_model.py:334-363 is  C = Bd + Y^T Y  with Bd = sigma^2 + K_global + K_local + jitter

@@ -19,9 +19,11 @@ from ._runtime import (  # noqa: F401
     grow_workspace, persistent_status, ptr, recover_from_internal, refused_output, result_buffers, retry_internal,
     run_chunked, stream_ptr, to_dev, units_that_fit, workspace)
 from ._multi import (  # noqa: F401
-    BandedMultiFisherPlan, BandedMultiGradPlan, MultiGradPlan, MultiPlan, _BandedFisherUnits, _BandedUnits,
-    banded_units, collect_multi, column_map_csr, fisher_banded_multi, loglike_banded_multi_grad, loglike_multi,
-    loglike_multi_grad, merge_units, model_desc_key, reduce_fisher_host, reduce_orders_host, rerouted_units)
+    BandedMultiFisherPlan, BandedMultiGradPlan, BandedMultiScanPlan, MultiGradPlan, MultiPlan, _BandedFisherUnits,
+    _BandedScanUnits, _BandedUnits, banded_units, collect_multi, column_map_csr, fisher_banded_multi,
+    local_scan_banded_multi, loglike_banded_multi_grad, loglike_multi, loglike_multi_grad, merge_units, model_desc_key,
+    reduce_fisher_host, reduce_orders_host, rerouted_units, scan_cand_ptr, scan_mean_host, scan_out_offsets, scan_rounds,
+    scan_routes)
 
 C_KMS = 2.99792458e5
 

@@ -290,6 +290,17 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP],
     ),
+    "sf_local_scan_banded_multi_max_patch": (C.c_int, [C.POINTER(Segment), C.c_int, C.POINTER(C.POINTER(ModelDesc))]),
+    "sf_local_scan_banded_multi_workspace_bytes_md": (
+        C.c_size_t,
+        [C.POINTER(Segment), C.c_int, C.POINTER(C.POINTER(ModelDesc)), C.POINTER(C.c_int)],
+    ),
+    "sf_local_scan_banded_multi_batch_md": (
+        C.c_int,
+        [C.POINTER(Segment), C.c_int, C.POINTER(C.POINTER(ModelDesc)), _VP, C.POINTER(C.c_int), _VP, _VP, _VP, _VP, _VP, C.c_size_t,
+         _VP],
+    ),
+    "sf_local_scan_mean": (C.c_int, [C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP]),
     "sf_banded_max_halfwidth": (C.c_int, [_VP]),
     "sf_banded_window_halfwidth": (C.c_int, [_VP]),
     "sf_banded_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ModelDesc), C.c_int, C.c_int]),

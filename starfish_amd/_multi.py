@@ -2,7 +2,7 @@
 Multi-order calls: the (order x walker) units of several orders of ONE device in one launch sequence (csrc/sf_multi.cpp,
 csrc/sf_multi_banded.cpp).  One frame for a unit list (:class:`MultiPlan`: checks, upload, workspace, the cut into calls), four
 kinds of call on it -- likelihood, gradient, gradient and Fisher information on the band solver -- and one dispatcher for the
-band solver's two.  The orders are :class:`starfish_amd._device.DeviceOrder` objects; only their methods are called.
+band solver's two; the score scan for new local kernels on the band solver is a fifth kind with a dispatcher of its own.  The orders are :class:`starfish_amd._device.DeviceOrder` objects; only their methods are called.
 """
 
 import collections
@@ -609,5 +609,279 @@ def fisher_banded_multi(orders, mds, rows_list, columns, solver="banded", max_un
     ONE device on the band solver (:class:`BandedMultiFisherPlan`; ``solver``: "banded" or "auto").  Returns its per-order
     dicts; with ``sync=False`` the un-synchronised plan."""
     plan = BandedMultiFisherPlan(orders, mds, rows_list, columns, solver=solver, max_units=max_units)
+    plan.enqueue()
+    return plan.collect() if sync else plan
+
+
+# ------------------------------------------------------------------ score scan for new local kernels, all orders in one pass
+SCAN_MAX_CAND = 65535  # candidates per segment and call (sf_local_scan_banded_multi_batch_md)
+
+
+def scan_rounds(counts, step=SCAN_MAX_CAND):
+    """Candidate lists of ``counts[i]`` candidates cut into calls of at most ``step`` per order: a list of rounds, each a list of
+    ``(lo, hi, real)`` per order.  Every order stays in every round, so that all calls share one frame: an order whose list is
+    used up scans its last candidate once more (``real`` false: the result is dropped).  Pure host logic."""
+    counts = [int(c) for c in counts]
+    if not counts or min(counts) < 1:
+        raise ValueError("the scan needs at least one candidate per order")
+    rounds = []
+    for r in range(max(-(-c // step) for c in counts)):
+        rounds.append([(r * step, min((r + 1) * step, c), True) if r * step < c else (c - 1, c, False) for c in counts])
+    return rounds
+
+
+def scan_cand_ptr(counts):
+    """``h_cand_ptr`` of sf_local_scan_banded_multi_batch_md for segments of ``counts[i]`` candidates: (nseg + 1,) int32."""
+    return np.concatenate([[0], np.cumsum(np.asarray(counts, dtype=np.int64))]).astype(np.int32)
+
+
+def scan_out_offsets(sizes, counts):
+    """Where the triples of every segment of sf_local_scan_banded_multi_batch_md start, in doubles: ``3 sum_{j<i} B_j ncand_j``,
+    (nseg + 1,) int64 -- the last entry is the length of ``d_out``."""
+    per = 3 * np.asarray(sizes, dtype=np.int64) * np.asarray(counts, dtype=np.int64)
+    return np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
+
+
+def scan_routes(solver, patch_pixels, limits):
+    """Where the scan of every order of a multi-order call goes: ``patch_pixels[i]`` the patch sizes of order i's candidates,
+    ``limits[i]`` the widest patch the band solver serves for it (:func:`starfish_amd._device.local_scan_route` per order).
+    "banded": every order "banded" -- a candidate beyond the limit, or an order the band solver does not take, is a ``ValueError``
+    naming the order; "auto": "auto" per order, "dense" for an order with a candidate beyond the limit or without a limit (its
+    units all go through the order's dense scan).  Pure host logic."""
+    from ._device import local_scan_route
+
+    routes = []
+    for i, (px, limit) in enumerate(zip(patch_pixels, limits)):
+        px = np.asarray(px)
+        try:
+            route = local_scan_route(solver, px, int(limit))
+        except ValueError as e:
+            raise ValueError(f"order {i}: {e}") from None
+        if route == "banded" and px.size and int(px.max()) > int(limit):
+            raise ValueError(f"order {i}: a candidate reaches {int(px.max())} pixels: the band solver scans patches of at most "
+                             f"{int(limit)} pixels (solver=\"auto\" takes the dense factor for such an order)")
+        routes.append(route)
+    return routes
+
+
+def scan_mean_host(quad, trace, fisher, info):
+    """sf_local_scan_mean's rule on the host: ``quad``, ``trace``, ``fisher`` (B, ncand), ``info`` (B,).  Per candidate ``z = U /
+    sqrt(fisher)`` and ``amp = U / fisher`` with ``U = (quad - trace) / 2`` (NaN where ``fisher == 0``), added over the walkers with
+    ``info == 0`` in ascending order, ``s = v_0; s = s + v_1; ...``, and divided by their number: ``(z_mean, amp_mean, count)``;
+    no walker: NaN means and 0.  The same operations in the same order as the device: the same bits."""
+    quad, trace, fisher = (np.asarray(v, dtype=np.float64) for v in (quad, trace, fisher))
+    good = np.nonzero(np.asarray(info) == 0)[0]
+    ncand = quad.shape[1]
+    if not good.size:
+        return np.full(ncand, np.nan), np.full(ncand, np.nan), 0
+    score = 0.5 * (quad[good] - trace[good])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = np.where(fisher[good] == 0, np.nan, score / np.sqrt(fisher[good]))
+        amp = np.where(fisher[good] == 0, np.nan, score / fisher[good])
+    sz, sa = z[0].copy(), amp[0].copy()
+    for b in range(1, good.size):
+        sz, sa = sz + z[b], sa + amp[b]
+    return sz / good.size, sa / good.size, int(good.size)
+
+
+class _BandedScanUnits(MultiPlan):
+    """The device side of :class:`BandedMultiScanPlan`: the units the band kernels take, every order with its own candidates
+    ``cands[i]`` (n_i, 2) (sf_local_scan_banded_multi_batch_md).  Candidate lists longer than SCAN_MAX_CAND are scanned in several
+    rounds of calls with the same segments, so the same frame (:func:`scan_rounds`).  ``self.out[r]``: the triples of round r,
+    unit-major, segment after segment (:func:`scan_out_offsets`).  :meth:`collect`: per order lnl (B,), quad, trace, fisher (B,
+    n_i), info (B,); no retry, as :class:`_BandedUnits`."""
+
+    entry, query = "sf_local_scan_banded_multi_batch_md", "sf_local_scan_banded_multi_workspace_bytes_md"
+    keys, retries = ("lnl", "quad", "trace", "fisher", "info"), False
+
+    def __init__(self, orders, mds, rows_list, cands, max_units=None):
+        self.cands = [np.ascontiguousarray(np.asarray(c, dtype=np.float64)).reshape(-1, 2) for c in cands]
+        if len(self.cands) != len(orders):
+            raise ValueError(f"multi-order scan: {len(self.cands)} candidate lists for {len(orders)} orders")
+        self.rounds = scan_rounds([len(c) for c in self.cands])
+        self.counts = [[hi - lo for lo, hi, _ in rnd] for rnd in self.rounds]
+        self.cand_ptr = [scan_cand_ptr(c) for c in self.counts]
+        MultiPlan.__init__(self, orders, list(mds), rows_list, max_units=max_units)
+        self.offsets = [scan_out_offsets(self.sizes, c) for c in self.counts]
+        with _torch().cuda.device(self.dev):
+            self.d_cand = [to_dev(np.concatenate([c[lo:hi] for c, (lo, hi, _) in zip(self.cands, rnd)]), self.dev)
+                           for rnd in self.rounds]
+            self.out = [empty((int(off[-1]),), self.dev) for off in self.offsets]
+
+    def _cand_ptr(self, r, idxs):
+        """``h_cand_ptr`` of a call on the (consecutive) orders ``idxs`` in round r, into the round's candidate array."""
+        p = self.cand_ptr[r]
+        return (C.c_int * (len(idxs) + 1))(*[int(p[i]) for i in idxs], int(p[idxs[-1] + 1]))
+
+    def _workspace_bytes(self, call):
+        sizes = [self.lib.sf_local_scan_banded_multi_workspace_bytes_md(call.segs, call.nseg, call.models, self._cand_ptr(r, call.orders))
+                 for r in range(len(self.rounds))]
+        return 0 if min(sizes) == 0 else max(sizes)
+
+    def enqueue(self):
+        """Launch only: the triples land in ``self.out``, lnl and log_scale in ``self.quad`` (rows 0 and 3), the status in
+        ``self.info`` once the device's current stream is done."""
+        with _torch().cuda.device(self.dev):
+            s = stream_ptr(self.dev)
+            for r in range(len(self.rounds)):
+                for call, piece in zip(self.calls, self.pieces):
+                    i0, lo0, _ = piece[0]
+                    start = int(self.offsets[r][i0]) + 3 * lo0 * self.counts[r][i0]
+                    lnl, log_scale, info = (ptr(row[call.u0:call.u0 + call.n]) for row in (self.quad[0], self.quad[3], self.info))
+                    rc = self.lib.sf_local_scan_banded_multi_batch_md(call.segs, call.nseg, call.models, ptr(self.d_cand[r]),
+                                                                      self._cand_ptr(r, call.orders), ptr(self.out[r][start:]), lnl,
+                                                                      log_scale, info, ptr(self.ws), self.ws.numel(), s)
+                    _lib.check(rc, self.entry)
+
+    def _triples(self, i):
+        """Order i's triples on the device, one (B_i, n, 3) view per round that scans candidates of its own."""
+        return [self.out[r][int(self.offsets[r][i]):int(self.offsets[r][i + 1])].view(self.sizes[i], self.counts[r][i], 3)
+                for r, rnd in enumerate(self.rounds) if rnd[i][2]]
+
+    def _per_order(self):
+        lnl, info = self.quad[0].cpu().numpy(), self.info.cpu().numpy()
+        ends = np.cumsum(self.sizes)
+        outs = []
+        for i, (n, hi) in enumerate(zip(self.sizes, ends)):
+            t = np.concatenate([v.cpu().numpy() for v in self._triples(i)], axis=1)
+            outs.append(dict(lnl=lnl[hi - n:hi].copy(), quad=t[:, :, 0].copy(), trace=t[:, :, 1].copy(), fisher=t[:, :, 2].copy(),
+                             info=info[hi - n:hi].copy()))
+        return outs
+
+    def mean(self, i):
+        """``(z_mean, amp_mean, count)`` of order i over its walkers with info == 0, on the device (sf_local_scan_mean): only the
+        means come to the host."""
+        torch = _torch()
+        u0 = int(sum(self.sizes[:i]))
+        with torch.cuda.device(self.dev):
+            info = self.info[u0:u0 + self.sizes[i]]
+            count = empty((1,), self.dev, torch.int32)
+            means = []
+            for t in self._triples(i):
+                m = empty((int(t.shape[1]), 2), self.dev)
+                rc = self.lib.sf_local_scan_mean(self.sizes[i], int(t.shape[1]), ptr(t), ptr(info), ptr(m), ptr(count), stream_ptr(self.dev))
+                _lib.check(rc, "sf_local_scan_mean")
+                means.append(m)
+            host = np.concatenate([m.cpu().numpy() for m in means], axis=0)
+            return host[:, 0].copy(), host[:, 1].copy(), int(count.cpu().numpy()[0])
+
+
+class BandedMultiScanPlan:
+    """The score scan for a new local kernel (:meth:`DeviceOrder.local_scan`) for every (order x walker) unit of ONE device on the
+    band + Woodbury solver, all units in one launch sequence (sf_local_scan_banded_multi_batch_md).  ``orders``, ``mds``,
+    ``rows_list`` as for :class:`BandedMultiGradPlan`; ``cands[i]``: order i's own candidates, (n_i, 2) rows of mu, sigma in km/s.
+    The frame's half-width is the LDS window's widest for 1 + m rows whatever the units' support is, so a unit's bits do not depend
+    on the other units or on how the unit list is cut.  Routing by :func:`scan_routes`, :func:`banded_units`,
+    :func:`rerouted_units` and :func:`merge_units`: solver "banded" -- a candidate whose patch is wider than the band solver's
+    limit is a ``ValueError`` naming the order before any device call, a unit whose covariance support exceeds the window is
+    refused (INFO_BANDWIDTH, ``-inf``, NaN rows); "auto" -- such units, the units the kernels flag -4 and every unit of an order
+    with a candidate beyond the limit go through the order's dense ``local_scan``.  Status -5 is recomputed densely under either.
+    :meth:`collect`: per order the dict :meth:`DeviceOrder.local_scan` returns (quad, trace, fisher (B, n_i), lnl, info);
+    :meth:`mean`: per order ``(z_mean, amp_mean, count)``."""
+
+    def __init__(self, orders, mds, rows_list, cands, solver="banded", max_units=None):
+        from ._device import local_scan_patches
+
+        check_solver(solver, ("banded", "auto"))
+        torch = _torch()
+        self.orders, self.mds, self.solver, self.max_units = list(orders), list(mds), solver, max_units
+        self.cands = [np.ascontiguousarray(np.asarray(c, dtype=np.float64)) for c in cands]
+        if len(self.cands) != len(self.orders):
+            raise ValueError(f"multi-order scan: {len(self.cands)} candidate lists for {len(self.orders)} orders")
+        for i, c in enumerate(self.cands):
+            if c.ndim != 2 or c.shape[1] != 2 or not c.shape[0]:
+                raise ValueError(f"order {i}: cand of shape {c.shape}: expected (ncand, 2) rows of mu, sigma with ncand >= 1")
+        self.rows = [np.atleast_2d(r.cpu().numpy() if torch.is_tensor(r) else np.asarray(r, dtype=np.float64)) for r in rows_list]
+        self.sizes = [int(r.shape[0]) for r in self.rows]
+        self.limits = [o.local_scan_banded_max_patch(md) for o, md in zip(self.orders, self.mds)]
+        patches = [local_scan_patches(o._keep[0], c) for o, c in zip(self.orders, self.cands)]
+        self.routes = scan_routes(solver, [hi - lo + 1 for lo, hi in patches], self.limits)
+        self.bounds = [o.halfwidth_bound(md, r) for o, md, r in zip(self.orders, self.mds, self.rows)]
+        self.fits = banded_units(self.bounds, [lim - 1 if route != "dense" else -1 for lim, route in zip(self.limits, self.routes)])
+        self.idx = [np.nonzero(f)[0] for f in self.fits]
+        self.on_device = [i for i, idx in enumerate(self.idx) if idx.size]
+        self.plan = None
+        if self.on_device:
+            self.plan = _BandedScanUnits([self.orders[i] for i in self.on_device], [self.mds[i] for i in self.on_device],
+                                         [self.rows[i][self.idx[i]] for i in self.on_device],
+                                         [self.cands[i] for i in self.on_device], max_units=max_units)
+        self.rerouted = None
+        self._out = None
+
+    @property
+    def units(self):
+        return sum(self.sizes)
+
+    def enqueue(self):
+        """Launch only (no host synchronisation)."""
+        if self.plan is not None:
+            self.plan.enqueue()
+
+    def _dense(self, which, rest):
+        """The dense scan of the walkers ``rest[i]`` of the orders ``which``, per order, in calls of at most SCAN_MAX_CAND candidates."""
+        out = []
+        for i in which:
+            parts = [self.orders[i].local_scan(self.mds[i], self.rows[i][rest[i]], self.cands[i][q:q + SCAN_MAX_CAND], self.max_units)
+                     for q in range(0, len(self.cands[i]), SCAN_MAX_CAND)]
+            res = dict(lnl=parts[0]["lnl"], info=parts[0]["info"])
+            res.update({key: np.concatenate([p[key] for p in parts], axis=1) for key in ("quad", "trace", "fisher")})
+            out.append(res)
+        return out
+
+    def _rest(self, infos):
+        rest = rerouted_units(self.fits, infos, self.solver)
+        self.rerouted = sum(len(idx) for idx in rest)
+        return rest
+
+    def collect(self):
+        """Per order a dict of numpy arrays: quad, trace, fisher (B, n_i), lnl (B,), info (B,); refused units have ``-inf``, NaN
+        and INFO_BANDWIDTH."""
+        outs = [refused_output(n, {key: (len(c),) for key in ("quad", "trace", "fisher")}) for n, c in zip(self.sizes, self.cands)]
+        if self.plan is not None:
+            for i, got in zip(self.on_device, self.plan.collect()):
+                for key, v in got.items():
+                    outs[i][key][self.idx[i]] = v
+        internal = sum(int(np.count_nonzero(o["info"] == INFO_INTERNAL)) for o in outs)
+        if internal:
+            import warnings
+
+            warnings.warn(f"banded solver: internal status -5 for {internal} unit(s); recomputed densely", RuntimeWarning,
+                          stacklevel=2)
+        rest = self._rest([o["info"] for o in outs])
+        which = [i for i, idx in enumerate(rest) if len(idx)]
+        if which:
+            merge_units(outs, rest, self._dense(which, rest))
+        self._out = outs
+        return outs
+
+    def mean(self):
+        """Per order ``(z_mean, amp_mean, count)``: ``z = U / sqrt(fisher)`` and ``amp = U / fisher``, ``U = (quad - trace) / 2``,
+        averaged over the ``count`` walkers that evaluate in that order.  An order whose units all ran on the band kernels is
+        averaged on the device (sf_local_scan_mean: only the means are copied to the host); an order with a refused or re-routed
+        unit by the same rule on the host (:func:`scan_mean_host`) from the collected triples."""
+        infos = [np.full(n, INFO_BANDWIDTH, dtype=np.int32) for n in self.sizes]
+        if self.plan is not None:
+            codes = self.plan.info.cpu().numpy()
+            ends = np.cumsum(self.plan.sizes)
+            for k, i in enumerate(self.on_device):
+                infos[i][self.idx[i]] = codes[ends[k] - self.plan.sizes[k]:ends[k]]
+        rest = self._rest(infos)
+        on_device = {i: k for k, i in enumerate(self.on_device)}
+        host = [i for i in range(len(self.sizes)) if len(rest[i]) or i not in on_device or not self.fits[i].all()]
+        outs = self.collect() if host else None
+        means = []
+        for i in range(len(self.sizes)):
+            if i in host:
+                means.append(scan_mean_host(outs[i]["quad"], outs[i]["trace"], outs[i]["fisher"], outs[i]["info"]))
+            else:
+                means.append(self.plan.mean(on_device[i]))
+        return means
+
+
+def local_scan_banded_multi(orders, mds, rows_list, cands, solver="banded", max_units=None, sync=True):
+    """The score scan for new local kernels for the (order x walker) units of several orders of ONE device on the band solver
+    (:class:`BandedMultiScanPlan`; ``solver``: "banded" or "auto").  Returns its per-order dicts; with ``sync=False`` the
+    un-synchronised plan (``plan.collect()`` or ``plan.mean()`` later)."""
+    plan = BandedMultiScanPlan(orders, mds, rows_list, cands, solver=solver, max_units=max_units)
     plan.enqueue()
     return plan.collect() if sync else plan

@@ -1,8 +1,11 @@
 // C-ABI host layer: multi-order batches on the band + Woodbury solver (the dense calls and what the regrouping is for:
 // sf_multi.cpp).  sf_loglike_banded_multi_grad_batch_md is sf_loglike_multi_grad_batch_md without matrices: one launch of
 // each band sweep over all units of a chunk.  sf_fisher_banded_multi_batch_md is its regrouping for the Fisher information of the
-// mean-flux parameters (one plain sweep over [r; Y; J] per unit).
+// mean-flux parameters (one plain sweep over [r; Y; J] per unit), sf_local_scan_banded_multi_batch_md the one for the score scan
+// for new local kernels (the keeping sweep, alpha, the selected inversion and Vs, then every order's scan).
 #include <algorithm>
+#include <string>
+#include <vector>
 
 #include "sf_multi_pipeline.h"
 
@@ -81,7 +84,8 @@ static int banded_multi_open(const sf_segment* segs, int nseg, int U, size_t wor
     return pipe->begin(&c0->exec, (hipStream_t)stream, nseg, U);
 }
 // On a segment's lane sp: its band into the call's frame, then its transform chain.  w: the segment's slice of the Work with the
-// lane's transient buffers; u0: its first unit; xs: where the chain leaves the unscaled eigenspectra rows
+// lane's transient buffers; u0: its first unit; xs: where the chain leaves the unscaled eigenspectra rows (may be NULL).  A work
+// without G.gtab: every entry of the band from its own pixel pair, no table per diagonal (the diagnostics' fill, sf_banded.cpp)
 static int banded_multi_segment(const BandMultiWork& G, const sf_segment& seg, const sf_model_desc* mdl, const Work& w, int u0,
                                 double* xs, double* d_log_scale, hipStream_t sp) {
     const int64_t sband = (int64_t)G.n16 * G.ldb;
@@ -92,7 +96,7 @@ static int banded_multi_segment(const BandMultiWork& G, const sf_segment& seg, c
         f.C = nullptr, f.lda = 0, f.stride = 0, f.lower_only = 1, f.add_jitter = 1;
         f.npad = G.n16;  // (identity rows up to the frame's row count)
         SF_CHECK(sf_launch_band_fill(f, seg.B, G.band + (size_t)u0 * sband, G.halfwidth + 1, G.halfwidth, G.ldb, sband, w.info_c,
-                                     G.gtab + (size_t)u0 * (G.ldb + 2), sp));
+                                     G.gtab ? G.gtab + (size_t)u0 * (G.ldb + 2) : nullptr, sp));
     }
     ProfScope ps(sp, PS_TRANSFORM);
     return run_transforms(seg.ctx, mdl, seg.B, seg.d_params, w, nullptr, xs, nullptr, d_log_scale ? d_log_scale + u0 : nullptr, true, sp);
@@ -327,4 +331,165 @@ extern "C" int sf_fisher_banded_multi_batch_md(const sf_segment* segs, int nseg,
         }
     }
     return SF_OK;
+}
+
+// ----------------------------------------------------------------------------------- multi-order score scan on the band solver
+// sf_local_scan_banded_multi_batch_md: the launch structure of the gradient call above with the head that
+// sf_local_scan_banded_batch runs (banded_diag_head, sf_banded.cpp, for the walker's own residual with the selected inversion).
+// Per segment on its lane: the band fill, entry by entry, and the transform chain; per chunk on the caller's stream, over all
+// its units in one launch each: keeping sweep, capacitance step, lnl / info, backward sweep and mix (alpha: one staging row per
+// unit), selected inversion and Vs (the m columns alone); then per segment sf_launch_local_scan_banded as it is, with the order's
+// own n, grid and slice of the candidates, Sigma / Vs / alpha addressed with the frame's strides.  The frame is BandMultiFrame's
+// at the half-width wmax -- the LDS window's widest for 1 + m rows, the single-order call's rule -- whatever the orders' own
+// support is: there is no h_halfwidth.  No device code of its own.
+#define BANDED_MULTI_SCAN "sf_local_scan_banded_multi_batch_md"
+// what the call refuses on its segments before anything is enqueued, and its frame.  *no_band (may be NULL): the refusal is that
+// the band solver does not take the orders (a grid that is not strictly increasing, no window), which the patch query answers 0
+static int banded_multi_scan_frame(const sf_segment* segs, int nseg, const sf_model_desc* const* models, BandMultiFrame* F,
+                                   bool* no_band = nullptr) {
+    if (no_band) *no_band = false;
+    if (multi_layout(segs, nseg, models, &F->L, &F->U, &F->bmax, &F->uni)) {
+        const std::string why = sf_last_error();
+        sf_set_error("%s: %s", BANDED_MULTI_SCAN, why.c_str());
+        return SF_EINVAL;
+    }
+    F->n16 = 0;
+    for (int i = 0; i < nseg; ++i) {
+        const sf_ctx* c = segs[i].ctx;
+        if (segs[i].B > 65535) {  // (the fill and the candidates take one grid plane per unit)
+            sf_set_error("%s: segment %d: B=%d must lie in 1 .. 65535", BANDED_MULTI_SCAN, i, (int)segs[i].B);
+            return SF_EINVAL;
+        }
+        if (!c->monotonic) {
+            if (no_band) *no_band = true;
+            sf_set_error("%s: segment %d: the wavelength grid is not monotonic (the band solver needs a strictly increasing one, and a "
+                         "candidate's pixels are no contiguous patch)", BANDED_MULTI_SCAN, i);
+            return SF_EINVAL;
+        }
+        F->n16 = std::max(F->n16, (c->n + 15) / 16 * 16);
+    }
+    const int m = F->L.m;
+    F->halfwidth = m < 1 || m > 32 ? -1 : sf_band_max_halfwidth(1 + m);
+    if (F->halfwidth < 0) {
+        if (no_band) *no_band = true;
+        sf_set_error("%s: segment 0: 1 + %d rows exceed the LDS window at every half-width (use sf_local_scan_batch per order)",
+                     BANDED_MULTI_SCAN, m);
+        return SF_EINVAL;
+    }
+    return SF_OK;
+}
+// the candidate lists: nseg + 1 ascending ints on the host, 1 .. 65535 candidates per segment
+static int banded_multi_scan_cands_ok(int nseg, const int* h_cand_ptr) {
+    if (!h_cand_ptr) {
+        sf_set_error("%s: h_cand_ptr (nseg + 1 ascending ints on the host) is required", BANDED_MULTI_SCAN);
+        return SF_EINVAL;
+    }
+    if (h_cand_ptr[0] < 0) {
+        sf_set_error("%s: segment 0: h_cand_ptr starts at %d, a negative index", BANDED_MULTI_SCAN, h_cand_ptr[0]);
+        return SF_EINVAL;
+    }
+    for (int i = 0; i < nseg; ++i) {
+        const long long count = (long long)h_cand_ptr[i + 1] - h_cand_ptr[i];
+        if (count < 1 || count > 65535) {
+            sf_set_error("%s: segment %d: %lld candidates (h_cand_ptr %d .. %d) must lie in 1 .. 65535", BANDED_MULTI_SCAN, i, count,
+                         h_cand_ptr[i], h_cand_ptr[i + 1]);
+            return SF_EINVAL;
+        }
+    }
+    return SF_OK;
+}
+extern "C" int sf_local_scan_banded_multi_max_patch(const sf_segment* segs, int nseg, const sf_model_desc* const* models) {
+    BandMultiFrame F;
+    bool no_band = false;
+    if (banded_multi_scan_frame(segs, nseg, models, &F, &no_band)) return no_band ? 0 : SF_EINVAL;
+    return F.halfwidth + 1;
+}
+extern "C" size_t sf_local_scan_banded_multi_workspace_bytes_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                                                const int* h_cand_ptr) {
+    BandMultiFrame F;
+    if (banded_multi_scan_frame(segs, nseg, models, &F) || banded_multi_scan_cands_ok(nseg, h_cand_ptr)) return 0;
+    return carve_band_multi_scan(segs, nseg, h_cand_ptr, F.L, F.n16, F.halfwidth, F.U, nullptr, 0, carve_banded_multi(F, nullptr, 0).bytes)
+        .bytes;
+}
+extern "C" int sf_local_scan_banded_multi_batch_md(const sf_segment* segs, int nseg, const sf_model_desc* const* models,
+                                                   const double* d_cand, const int* h_cand_ptr, double* d_out, double* d_lnl,
+                                                   double* d_log_scale, int* d_info, void* d_work, size_t work_bytes, void* stream) {
+    BandMultiFrame F;
+    SF_CHECK(banded_multi_scan_frame(segs, nseg, models, &F));
+    SF_CHECK(banded_multi_scan_cands_ok(nseg, h_cand_ptr));
+    if (!d_cand || !d_out || !d_lnl || !d_info || !d_work) {
+        sf_set_error("%s: d_cand, d_out, d_lnl, d_info and a workspace are required", BANDED_MULTI_SCAN);
+        return SF_EINVAL;
+    }
+    const Layout& L = F.L;
+    const Work W = carve_banded_multi(F, d_work, work_bytes);
+    const BandMultiScanWork G = carve_band_multi_scan(segs, nseg, h_cand_ptr, L, F.n16, F.halfwidth, F.U, d_work, work_bytes, W.bytes);
+    if (work_bytes < G.bytes) {  // (said here, so that the message names the call)
+        sf_set_error("%s: workspace too small: have %zu, need %zu", BANDED_MULTI_SCAN, work_bytes, G.bytes);
+        return SF_ENOMEM;
+    }
+    MultiPipeline pipe;
+    SF_CHECK(banded_multi_open(segs, nseg, F.U, work_bytes, G.bytes, stream, &pipe));
+    hipStream_t s = pipe.s;
+    const int H = G.halfwidth, n16 = G.n16, nrhs = G.nrhs, m = L.m;
+    const int64_t sband = (int64_t)n16 * G.ldb, sT = (int64_t)nrhs * L.npad, svs = (int64_t)m * L.npad;
+    const size_t ng = (size_t)nrhs * nrhs;
+    std::vector<int64_t> out0(nseg);  // where a segment's triples start
+    int64_t triples = 0;
+    for (int i = 0; i < nseg; ++i) {
+        out0[i] = 3 * triples;
+        triples += (int64_t)segs[i].B * (h_cand_ptr[i + 1] - h_cand_ptr[i]);
+    }
+    for (int i = 0; i < nseg; ++i) {
+        const MultiSegment at = pipe.start(i);
+        const Work w = with_trans_set(slice(W, at.u0), at.lane);
+        SF_CHECK(banded_multi_segment(G, segs[i], models[i], w, at.u0, nullptr, d_log_scale, at.stream));
+        SF_CHECK(pipe.done(i, segs[i].B));
+    }
+    for (const MultiChunk& ch : pipe.chunks) {
+        SF_CHECK(pipe.join(ch));
+        const Work wc = slice(W, ch.u0);
+        const size_t u = (size_t)ch.u0;
+        int* info = d_info + ch.u0;
+        {
+            ProfScope ps(s, PS_POTRF);
+            const sf_band_call k = banded_multi_sweep(G, ch, wc, sf_band_rhs{wc.Y, (int64_t)L.mpad * L.npad, L.npad, nrhs, wc.resid, L.npad});
+            SF_CHECK(sf_launch_band_keep(k, G.fac + u * G.sfac, s));
+        }
+        {
+            ProfScope ps(s, PS_SOLVE);
+            SF_CHECK(sf_launch_woodbury(G.gram + u * ng, nrhs, ch.units, G.logdet_band + u, wc.logdet, wc.sqmah, wc.info_c, s));
+            SF_CHECK(sf_launch_finish(ch.units, wc.logdet, wc.sqmah, wc.info_e, wc.info_c, d_lnl + ch.u0, info, s));
+            // T = Bd^-1 [r, Y^T], alpha = T M in the staging row; the band of Sigma = Bd^-1 and Vs of C^-1 = Sigma - Vs Vs^T
+            // (k_band_mix takes one grid plane per unit: slices of at most 65535)
+            SF_CHECK(sf_launch_band_back(G.fac + u * G.sfac, n16, H, ch.units, nrhs, info, G.T + u * sT, L.npad, sT, s));
+            for (int lo = 0; lo < ch.units; lo += 65535) {
+                const int nb = std::min(ch.units - lo, 65535);
+                const size_t v = u + lo;
+                SF_CHECK(sf_launch_band_mix(G.gram + v * ng, wc.Lw + (size_t)lo * m * m, 1, m, 0, info + lo, nullptr, G.T + v * sT, n16, L.npad,
+                                            nb, G.M + v * nrhs, G.stage + v * L.npad, s));
+            }
+            SF_CHECK(sf_launch_band_selinv(G.fac + u * G.sfac, n16, H, ch.units, nrhs, info, G.sigma + u * sband, G.ldb, sband, s));
+            for (int lo = 0; lo < ch.units; lo += 65535) {
+                const int nb = std::min(ch.units - lo, 65535);
+                const size_t v = u + lo;
+                SF_CHECK(sf_launch_band_vs(G.gram + v * ng, 1, m, 0, info + lo, G.T + v * sT, n16, L.npad, nb, G.M2 + v * nrhs * m,
+                                           G.vs + v * svs, s));
+            }
+        }
+        for (int i = ch.s0; i < ch.s1; ++i) {
+            sf_ctx* c = segs[i].ctx;
+            const size_t su = (size_t)pipe.seg_u0[i];
+            const Work w = slice(W, pipe.seg_u0[i]);
+            SF_CHECK(sf_launch_local_scan_banded(fill_args(c, models[i], segs[i].d_params, w), segs[i].B, G.sigma + su * sband, G.ldb, sband,
+                                                 H, G.vs + su * svs, L.npad, svs, m, G.stage + su * L.npad, L.npad, d_info + su,
+                                                 d_cand + 2 * (int64_t)h_cand_ptr[i], h_cand_ptr[i + 1] - h_cand_ptr[i], G.patch, G.wband,
+                                                 d_out + out0[i], s));
+        }
+    }
+    return SF_OK;
+}
+// the averaged proposal of one segment's slice (sf_local_scan_multi.h)
+extern "C" int sf_local_scan_mean(int B, int ncand, const double* d_out, const int* d_info, double* d_mean, int* d_count, void* stream) {
+    return sf_launch_local_scan_mean(B, ncand, d_out, d_info, d_mean, d_count, (hipStream_t)stream);
 }

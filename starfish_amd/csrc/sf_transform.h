@@ -146,6 +146,8 @@ struct sf_multi_fisher_reduce_args {
     int* info;       // [W]
 };
 int sf_launch_multi_fisher_reduce(const sf_multi_fisher_reduce_args& a, hipStream_t s);
+// sf_local_scan_multi.h: per candidate the means of z and amp over the walkers with info == 0 (sf_local_scan_mean)
+int sf_launch_local_scan_mean(int B, int ncand, const double* out, const int* info, double* mean, int* count, hipStream_t s);
 
 int sf_launch_extinct_rows(const double* wave, int n, const double* flux, int rows, double Av, double Rv, int law,
                            double* out, hipStream_t s);  // law: 0 ccm89, 1 odonnell94, 2 calzetti00

@@ -18,6 +18,7 @@
 //   sf_mean_grad.h          the gradient in the mean-flux parameters: k_mean_stage, k_mean_finish, k_mean_pixel, k_mean_sum
 //   sf_fisher.h             the Fisher information of the mean-flux parameters: k_fisher_tangent, k_fisher_band, k_fisher_ztz
 //   sf_fisher_multi.h       the Fisher matrices of a multi-order call: k_fisher_spread, k_multi_fisher_reduce
+//   sf_local_scan_multi.h   the averaged proposal of a score scan: k_ls_mean
 #include "sf_common.h"
 #include "sf_device.h"
 #include "sf_transform.h"
@@ -29,3 +30,4 @@
 #include "sf_mean_grad.h"
 #include "sf_fisher.h"
 #include "sf_fisher_multi.h"
+#include "sf_local_scan_multi.h"

@@ -2,6 +2,7 @@
 // query runs on a null base and the entry point on the caller's pointer.  (A layout that lies behind the Work of the same
 // call is carved by one function too: it starts its Carve at the Work's size.)
 #pragma once
+#include <algorithm>
 #include <type_traits>
 #include <vector>
 
@@ -548,6 +549,50 @@ static BandMultiFisherWork carve_band_multi_fisher(const sf_segment* segs, int n
         w.mudot = k.take<double>(ngrid * B * c->m);
         u0 += B;
     }
+    g.bytes = sf_align_up(k.off, 256);
+    return g;
+}
+
+// ------------------------------------------------------------------- multi-order score scan on the band solver
+// (sf_local_scan_banded_multi_batch_md; behind the Work of the same call, which has no matrices: base_bytes = its size)  The common
+// frame of carve_band_multi_grad at the window's widest half-width for 1 + m rows.  For all U units, as carve_band and
+// carve_band_diag lay them out for one order and one right-hand side (the walker's own residual): band [U][n16][ldb] (filled
+// entry by entry: no table per diagonal), gram [U][(1 + m)^2], logdet_band, the staging area [U][npad] that ends up holding alpha,
+// fac (the kept factor of a sweep over n16 rows), T [U][1 + m][npad], M [U][1 + m], sigma [U][n16][ldb], M2 [U][(1 + m) m] and vs
+// [U][m][npad].  Then ONE patch list and ONE set of tiles of W for the whole call, sized for the segment that needs the most (2
+// ints per candidate; sf_local_scan_banded_doubles of its n and B): the segments' scans run one after the other on the caller's
+// stream, and every scan writes both before it reads them.
+struct BandMultiScanWork : BandMultiWork {
+    int nrhs;
+    double *stage, *fac, *T, *M, *sigma, *M2, *vs;
+    size_t sfac;  // doubles of one unit's kept factor
+    int* patch;
+    double* wband;
+};
+static BandMultiScanWork carve_band_multi_scan(const sf_segment* segs, int nseg, const int* h_cand_ptr, const Layout& L, int n16,
+                                               int halfwidth, int U, void* p, size_t cap, size_t base_bytes) {
+    Carve k(p, cap, base_bytes);
+    BandMultiScanWork g{};
+    g.nrhs = 1 + L.m, g.n16 = n16, g.halfwidth = halfwidth, g.ldb = (halfwidth + 2) & ~1;
+    g.sfac = sfb_keep_doubles(n16, sfb_nbr(halfwidth), sfb_nrb(g.nrhs));
+    const size_t u = (size_t)U, npad = (size_t)L.npad, ng = (size_t)g.nrhs * g.nrhs;
+    g.band = k.take<double>(u * n16 * g.ldb);
+    g.gram = k.take<double>(u * ng);
+    g.logdet_band = k.take<double>(u);
+    g.stage = k.take<double>(u * npad);
+    g.fac = k.take<double>(u * g.sfac);
+    g.T = k.take<double>(u * g.nrhs * npad);
+    g.M = k.take<double>(u * g.nrhs);
+    g.sigma = k.take<double>(u * n16 * g.ldb);
+    g.M2 = k.take<double>(u * g.nrhs * L.m);
+    g.vs = k.take<double>(u * L.m * npad);
+    size_t ncand = 0, tiles = 0;
+    for (int i = 0; i < nseg; ++i) {
+        ncand = std::max(ncand, (size_t)(h_cand_ptr[i + 1] - h_cand_ptr[i]));
+        tiles = std::max(tiles, sf_local_scan_banded_doubles(segs[i].ctx->n, segs[i].B));
+    }
+    g.patch = k.take<int>(2 * ncand);
+    g.wband = k.take<double>(tiles);
     g.bytes = sf_align_up(k.off, 256);
     return g;
 }

@@ -564,6 +564,195 @@ class EchelleModel:
                 terms.append((mean.index(labels[cols[i][own.index(key)]]), prior, float(self.orders[i][key])))
         return _map.laplace_covariance(self.fisher_information(solver=solver), mean, terms)
 
+    # ------------------------------------------------------------------ where do new local kernels belong, in every order?
+    def _scan_inputs(self, mus, sigmas, wl_range, solver=None):
+        """Host logic of the scan, no device work: per order ``(mus_i, sigmas_i, cand_i)`` as
+        :meth:`SpectrumModel._scan_candidates` checks them, or None for an order that ``wl_range`` leaves without a centre.
+        ``mus``: None -- every order's own pixels; else one array of centres per order.  ``sigmas``: None -- the default widths;
+        widths (km/s) shared by the orders; or one list of widths per order.  ``solver``: None -- every order's own ``solver`` must
+        be "dense"; under "banded" a candidate whose patch is wider than the band solver's limit is a ``ValueError``.  Every
+        ``ValueError`` names the order."""
+        from .. import _device as D
+        from ._diagnostics import DEFAULT_SCAN_SIGMAS
+
+        if solver is not None:
+            D.check_solver(solver, or_none=True)
+        n = len(self.orders)
+        if mus is not None and len(mus) != n:
+            raise ValueError(f"mus: {len(mus)} lists of centres for {n} orders (None: every order's own pixels)")
+        sigmas = DEFAULT_SCAN_SIGMAS if sigmas is None else sigmas
+        per_order = not np.isscalar(sigmas) and len(sigmas) > 0 and np.ndim(sigmas[0]) > 0
+        if per_order and len(sigmas) != n:
+            raise ValueError(f"sigmas: {len(sigmas)} lists of widths for {n} orders (or one list shared by all)")
+        out = []
+        for i, m in enumerate(self.orders):
+            if solver is None and m.solver != "dense":
+                raise ValueError(f"order {i}: solver=None runs the scan on the dense solver only, not solver={m.solver!r}; pass "
+                                 f"solver=")
+            centres = np.asarray(m.data.wave if mus is None else mus[i], dtype=np.float64).ravel()
+            if wl_range is not None:
+                centres = centres[(centres >= wl_range[0]) & (centres <= wl_range[1])]
+            if not centres.size:
+                out.append(None)
+                continue
+            limit = None
+            if solver == "banded":  # (a size query of the order's context; nothing is enqueued)
+                dev, md, _ = m._pack(None, update_caches=False)
+                limit = dev.local_scan_banded_max_patch(md)
+            try:
+                out.append(m._scan_candidates(centres, sigmas[i] if per_order else sigmas, None, limit))
+            except ValueError as e:
+                raise ValueError(f"order {i}: {e}") from None
+        return out
+
+    @staticmethod
+    def _scan_result(out, nsig, nmu):
+        """The dict of :meth:`SpectrumModel.local_kernel_scan_batch` from a device scan's quad, trace, fisher (B, nsig * nmu)."""
+        shape = (out["quad"].shape[0], nsig, nmu)
+        quad, trace, fisher = (np.asarray(out[key]).reshape(shape) for key in ("quad", "trace", "fisher"))
+        score = 0.5 * (quad - trace)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            z = np.where(fisher == 0, np.nan, score / np.sqrt(fisher))
+            amp = np.where(fisher == 0, np.nan, score / fisher)
+        return {"score": score, "information": fisher, "z": z, "amp": amp, "quad": quad, "trace": trace}
+
+    def _scan_run(self, P, inputs, solver, mean=False):
+        """The device side of the scan for the orders of ``inputs`` that have candidates: per order (None: skipped) the scan's
+        dict (quad, trace, fisher (B, ncand_i), lnl, info) -- with ``mean`` ``(z_mean, amp_mean, count)`` over the walkers that
+        evaluate there instead -- and the (n_orders, B) status codes, 0 for a skipped order."""
+        from .. import _multi as M
+
+        labels, cols = self._layout()
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        if P.shape[1] != len(labels):
+            raise ValueError("Param Vector does not match length of thawed parameters")
+        active = [i for i, v in enumerate(inputs) if v is not None]
+        packed = {i: self.orders[i]._pack(P[:, cols[i]], update_caches=False) for i in active}
+        outs = [None] * len(self.orders)
+        codes = np.zeros((len(self.orders), P.shape[0]), dtype=np.int32)
+        if solver in ("banded", "auto"):
+            pending = []
+            for group in self._by_device([packed[i] for i in active]):  # enqueue everything first, synchronise afterwards
+                idxs = [active[k] for k in group]
+                pending.append((idxs, M.local_scan_banded_multi([packed[i][0] for i in idxs], [packed[i][1] for i in idxs],
+                                                                [packed[i][2] for i in idxs], [inputs[i][2] for i in idxs],
+                                                                solver=solver, sync=False)))
+            for idxs, plan in pending:
+                for i, out in zip(idxs, plan.mean() if mean else plan.collect()):
+                    outs[i] = out
+                    if not mean:
+                        codes[i] = out["info"]
+            return outs, codes
+        for i in active:  # the loop over every order's dense scan
+            dev, md, rows = packed[i]
+            cand = inputs[i][2]
+            parts = [dev.local_scan(md, rows, cand[q:q + M.SCAN_MAX_CAND]) for q in range(0, len(cand), M.SCAN_MAX_CAND)]
+            out = dict(lnl=parts[0]["lnl"], info=parts[0]["info"])
+            out.update({key: np.concatenate([p[key] for p in parts], axis=1) for key in ("quad", "trace", "fisher")})
+            codes[i] = out["info"]
+            outs[i] = M.scan_mean_host(out["quad"], out["trace"], out["fisher"], out["info"]) if mean else out
+        return outs, codes
+
+    def local_kernel_scan_batch(self, P, mus=None, sigmas=None, wl_range=None, return_info=False, solver=None,
+                                return_orders=False):
+        """:meth:`SpectrumModel.local_kernel_scan_batch` for every order, for B parameter vectors (rows of ``P`` in :attr:`labels`
+        order; every order gets the columns of its own labels): a list with one dict per order -- "score", "information", "z",
+        "amp", "quad", "trace" of shape ``(B, len(sigmas), n_centres_i)`` -- the score test for one more local kernel at every
+        centre and width, with every kernel the order already has in its covariance.  ``mus``: None -- every order's own pixels;
+        else one array of centres per order.  ``wl_range`` = (lo, hi) keeps the centres inside it; an order left without centres
+        is skipped, its entry is None.  ``sigmas`` (km/s; None: 8, 15, 30): shared, or one list per order.  With ``return_info``
+        ``(results, info)``, ``info`` (B,) the first non-zero per-order code of every walker; with ``return_orders`` also the
+        (n_orders, B) per-order codes (0 for a skipped order).  A walker that fails in an order has NaN rows there.  The model's
+        state is not modified.
+
+        solver: None / "dense" -- the loop over every order's dense ``local_scan`` (None: every order's own ``solver`` must be
+                            "dense");
+                "banded" -- the band + Woodbury solver, all (order x walker) units of a device in one launch sequence
+                            (``sf_local_scan_banded_multi_batch_md``), everything enqueued before anything is synchronised; a
+                            candidate that reaches more pixels than the band solver scans (145 for up to 15 emulator components)
+                            is a ``ValueError`` naming the order before any device call; a unit whose covariance support exceeds
+                            the LDS window gets NaN rows and info = -4;
+                "auto"  -- banded for the units that fit the window, the order's dense scan for the rest and for every unit of an
+                            order with a candidate beyond the limit."""
+        inputs = self._scan_inputs(mus, sigmas, wl_range, solver)
+        outs, codes = self._scan_run(P, inputs, solver)
+        res = [None if out is None else self._scan_result(out, len(inp[1]), len(inp[0])) for out, inp in zip(outs, inputs)]
+        bad = codes != 0
+        info = np.where(bad.any(axis=0), codes[bad.argmax(axis=0), np.arange(codes.shape[1])], 0).astype(np.int32)
+        self.last_info = info
+        ret = (res,)
+        if return_info:
+            ret += (info,)
+        if return_orders:
+            ret += (codes,)
+        return ret if len(ret) > 1 else res
+
+    def local_kernel_scan(self, mus=None, sigmas=None, wl_range=None, solver=None):
+        """:meth:`local_kernel_scan_batch` at the current state: a list with one dict per order (None for a skipped one) of
+        arrays of shape ``(len(sigmas), n_centres_i)``.  Raises as :meth:`log_likelihood` does for a point the device flags; the
+        model's state is not modified."""
+        res, info = self.local_kernel_scan_batch(self.get_param_vector()[None, :], mus, sigmas, wl_range, return_info=True,
+                                                 solver=solver)
+        SpectrumModel._raise_for_info(info[0])
+        return [None if r is None else {key: v[0] for key, v in r.items()} for r in res]
+
+    def _scan_means(self, P, mus, sigmas, wl_range, solver):
+        """What :meth:`propose_local_kernels` picks from: per order None (skipped) or ``(z, amp, mus_i, sigmas_i)`` with ``z`` and
+        ``amp`` of shape ``(len(sigmas_i), len(mus_i))`` -- of the current state (``P`` None), or their means over the walkers of
+        ``P`` that evaluate in that order: from the device under "banded" / "auto" (``sf_local_scan_mean``), on the host by the
+        same rule under None / "dense"."""
+        inputs = self._scan_inputs(mus, sigmas, wl_range, solver)
+        if P is None:
+            outs, codes = self._scan_run(self.get_param_vector()[None, :], inputs, solver)
+            for i, out in enumerate(outs):
+                if out is not None:
+                    SpectrumModel._raise_for_info(codes[i, 0])
+            res = [None if out is None else self._scan_result(out, len(inp[1]), len(inp[0])) for out, inp in zip(outs, inputs)]
+            return [None if r is None else (r["z"][0], r["amp"][0], inp[0], inp[1]) for r, inp in zip(res, inputs)]
+        means, _codes = self._scan_run(P, inputs, solver, mean=True)
+        out = []
+        for i, (mean, inp) in enumerate(zip(means, inputs)):
+            if mean is None:
+                out.append(None)
+                continue
+            z, amp, count = mean
+            if not count:
+                raise ValueError(f"order {i}: no walker of P evaluates: nothing to average")
+            shape = (len(inp[1]), len(inp[0]))
+            out.append((z.reshape(shape), amp.reshape(shape), inp[0], inp[1]))
+        return out
+
+    def propose_local_kernels(self, threshold=4.0, buffer=None, max_kernels=None, sigmas=None, mus=None, wl_range=None, P=None,
+                              solver=None):
+        """Where every order's residual asks for local kernels: :meth:`local_kernel_scan` (with ``P``:
+        :meth:`local_kernel_scan_batch`, ``z`` and ``amp`` averaged per order over the walkers that evaluate in that order), then
+        per order the peak picking of :meth:`SpectrumModel.propose_local_kernels` (``threshold``, ``buffer``; at most
+        ``max_kernels`` per order, None: as many as each order can still take).  Returns a list with one list per order (empty for
+        a skipped order) of ``{"mu", "log_amp", "log_sigma"}``, sorted by ``mu``.  Raises a ``ValueError`` naming the order if no
+        walker of ``P`` evaluates there.  The model is never changed.  ``mus``, ``sigmas``, ``wl_range`` and ``solver`` as for
+        :meth:`local_kernel_scan_batch`; under "banded" / "auto" the means over the walkers are taken on the device
+        (``sf_local_scan_mean``) and only they are copied to the host.
+
+        The loop that builds the noise model of an echelle spectrum::
+
+            for i, new in enumerate(em.propose_local_kernels(solver="auto")):
+                em.orders[i]["local_cov"] = [*em.orders[i]._local_kernels(), *new]
+            em.train(gradient_solver="auto")
+
+        and again until nothing is proposed (see :meth:`SpectrumModel.propose_local_kernels` for what the statistic is)."""
+        from .. import _device as D
+        from ._diagnostics import pick_local_kernels
+
+        picked = []
+        for m, got in zip(self.orders, self._scan_means(P, mus, sigmas, wl_range, solver)):
+            if got is None:
+                picked.append([])
+                continue
+            z, amp, centres, widths = got
+            room = D.MAX_LOCAL - len(m._local_kernels()) if max_kernels is None else max_kernels
+            picked.append(pick_local_kernels(z, amp, centres, widths, threshold, buffer, room))
+        return picked
+
     def train(self, priors=None, *, gradient_solver=None, **kwargs):
         """MAP estimate over :attr:`labels`: ``scipy.optimize.minimize(method="L-BFGS-B", jac=True)`` on the analytic gradient
         of :meth:`log_likelihood_gradient_batch` -- a per-order fit has a few hundred parameters, which a simplex search
